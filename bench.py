@@ -381,6 +381,62 @@ def shard_leg(ag, torch, name, N, tower, R, games, precision, steps, warmup, sta
         eng.close()
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: what the timed self-play steps left for a caller, read through libagz's C ABI right after the last
+    timed step and written as out_dir/<name>.npy (float32; game ids and the engine counters float64), so that two builds can
+    be compared output for output.  Per live game, the root of its search tree: child visit counts, child total values,
+    priors (the network's policy at the root), the root's N / W / Q and its board.  Then, when any game has finished, the
+    finished game records (moves, search probabilities, root values, result); no empty array is written.  A game's contents depend on its id alone, but which slot it runs in does
+    not, so every array is in game-id order.  At most `budget` bytes in all: past it, a fixed sample drawn with `seed`.
+    Returns {name: shape}."""
+    import numpy as np
+    rng = np.random.RandomState(seed)
+    G, A, P = eng.cfg.games, eng.A, eng.P
+    out = {}
+    slot_bytes = 4 * (3 * A + 3 + P + 2)
+    gid = np.array([eng.debug_live_record(g)[0] for g in range(G)], np.uint64)
+    slots = np.argsort(gid, kind="stable")
+    if G * slot_bytes > budget // 2:
+        slots = slots[np.sort(rng.choice(G, budget // 2 // slot_bytes, replace=False))]
+    cn, cw, pr = (np.zeros((len(slots), A), np.float32) for _ in range(3))
+    nwq = np.zeros((len(slots), 3), np.float32)
+    board = np.zeros((len(slots), P), np.float32)
+    for i, g in enumerate(slots):
+        g = int(g)
+        root = eng.tree_root(g)
+        info = eng.node_info(g, root)
+        nwq[i] = (info.N, info.W, info.Q)
+        cn[i], cw[i], pr[i] = (eng.node_floats(g, root, f) for f in (0, 1, 2))      # AGZ_F_CHILD_N, _W, _PRIOR
+        board[i] = eng.node_board(g, root)
+    out.update(root_game_id=gid[slots].astype(np.float64), root_child_n=cn, root_child_w=cw, root_prior=pr, root_nwq=nwq,
+               root_board=board)
+    st = eng.stats()
+    out["counters"] = np.array([st[k] for k in sorted(st)], np.float64)               # (keys in sorted order)
+    recs = eng.records()
+    left = budget - sum(a.nbytes for a in out.values()) - 14 * 128                      # (.npy headers of all 14 arrays)
+    keep = []
+    for k in rng.permutation(len(recs)):
+        nbytes = 4 * recs[k]["num_moves"] * (A + 2) + 20
+        if nbytes <= left:
+            keep.append(k)
+            left -= nbytes
+    recs = [recs[k] for k in sorted(keep) if recs[k]["num_moves"] > 0]
+    if recs:
+        cat = lambda key: np.concatenate([r[key] for r in recs]).astype(np.float32)
+        out.update(record_game_id=np.array([r["game_id"] for r in recs], np.float64),
+                   record_num_moves=np.array([r["num_moves"] for r in recs], np.float32),
+                   record_result=np.array([r["result"] for r in recs], np.float32),
+                   record_final_score=np.array([r["final_score"] for r in recs], np.float32),
+                   record_moves=cat("moves"), record_pis=cat("pis"), record_qs=cat("qs"))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def self_launch(n, single_device):
     """`python bench.py --gpus N` with no launcher around it (WORLD_SIZE unset): start the N ranks here -- N copies of
     this very command, one process per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their
@@ -464,12 +520,12 @@ def main():
     ap.add_argument("--no-sustained", action="store_true", help="skip the 0.4 s sustained-MFMA-rate measurement behind the timed region")
     ap.add_argument("--no-alt-precision", action="store_true",
                     help="skip the extra (untimed for `value`) leg that repeats the K steps with --precision f32s")
-    ap.add_argument("--generation", type=int, default=None, metavar="G",
+    ap.add_argument("--generation", type=int, default=0, metavar="G",
                     help="after the timed K steps keep playing, untimed for `value`: a warm-up until G games have ended "
                          "naturally, then a window until G more have; the line gains a `generation` object with SURVEY.md 8d's "
                          "generation rate (sum of position.n of the games that ended in the window / wall time) next to the "
-                         "steady-state rate of the same window.  Default: a whole generation (G = --games = 1024) on the headline "
-                         "workload at N = 1 (0 = off), bounded by --generation-seconds")
+                         "steady-state rate of the same window.  Default 0 (off): `value` and `ms_per_step` always describe the K "
+                         "timed steps, and a run's length follows --steps.  N = 1 only, bounded by --generation-seconds")
     ap.add_argument("--generation-seconds", type=float, default=900.0,
                     help="hard cap on the generation leg (half for the warm-up generation, half for the measured one); a leg the "
                          "cap cut short reports what it saw and says so")
@@ -482,6 +538,9 @@ def main():
     ap.add_argument("--config-leg-steps", type=int, default=20)
     ap.add_argument("--single-device-test", action="store_true",
                     help="testing only: every rank uses cuda:0 and gloo, to exercise the multi-rank code path on a 1-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them left for a caller (every live game's search root, the "
+                         "finished records, the counters) as DIR/<name>.npy, at most 64 MB (rank 0; see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # no launcher: be the launcher
@@ -501,8 +560,6 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     headline = (args.board, args.tower, args.readouts, args.games, args.precision) == (9, 10, 400, 1024, "f32")
-    if args.generation is None:      # SURVEY.md 8d's definition rides along on the headline line
-        args.generation = args.games if (world == 1 and headline and args.stagger > 0) else 0
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} under a launcher that set WORLD_SIZE={world}: start {args.gpus} ranks, or "
                          f"run `python bench.py --gpus {args.gpus}` with WORLD_SIZE unset and it starts them itself")
@@ -578,6 +635,7 @@ def main():
     search_ms, search_steps = eng.profile_search_read()
     eng.profile_search(False)
     s1 = eng.stats()
+    dumped = dump_outputs(eng, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # N > 1: rank 0 repeats the K steps ALONE (every other rank waits at the barrier behind it), so that the line carries
     # the N = 1 rate of the same box and `weak_scaling_efficiency` needs no second run
@@ -884,21 +942,7 @@ def main():
             out["search_kernels"] = search_kernels_object(search_ms, search_steps, d if world == 1 else {**d, "evals": d["evals"] / world},
                                                           args.games, N, 1e3 * elapsed / args.steps, live_pmc_traffic.search)
         if generation is not None:
-            out["generation"] = generation
-            if not generation["capped"]:
-                # SURVEY.md 8d's definition of the metric is the generation rate (sum of position.n of the games that ENDED in a
-                # whole generation after a warm-up generation / wall time): when that leg ran to its end it IS `value`
-                # (VERDICT r5 #4); the K-step window stays in the line as `steady_state` and behind ms_per_step / steps / warmup
-                out["steady_state"] = {"value": value, "unit": "positions/s", "steps": args.steps, "ms_per_step": 1e3 * elapsed / args.steps,
-                                       "what": "moves that completed their full readout budget inside the K timed steps / their time "
-                                               "(every game mid-search at a random phase; no game ends in the window)"}
-                out["value"] = generation["generation_rate"]
-                out["value_definition"] = ("generation.generation_rate: sum of the lengths of the games that ended in the measured "
-                                           "generation / its wall time (SURVEY.md 8d; selfplay.jl:22-43), on the same engine right behind "
-                                           "the K timed steps; ms_per_step, steps, warmup and roofline describe the K-step window "
-                                           "(`steady_state`)")
-                out["end_to_end_algorithmic_tflops"] = out["value"] * fpos / world / 1e12
-                out["end_to_end_executed_mfma_frac"] = out["value"] * fpos * wino_ratio / (world * peak * 1e12)
+            out["generation"] = generation      # (SURVEY.md 8d's generation rate, beside `value`: never as it)
         if per_rank is not None:
             out["per_rank"] = per_rank      # each rank's own clock over the same K steps (`value` uses the slowest)
             if solo is not None:
@@ -909,6 +953,8 @@ def main():
                                                 "field should read here; it means something on one GPU per rank")
         if exchange is not None:
             out["exchange"] = exchange
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
         if alt is not None:
             out["alt_precision"] = alt
         if world == 1 and headline and args.stagger > 0 and not args.no_config_legs:

@@ -95,8 +95,11 @@ def lib():
     if _lib is not None:
         return _lib
     d = os.path.join(HERE, "hostsim")
-    if os.path.exists("/root/reference") or not os.path.exists(os.path.join(d, "libhostsim.so")):
+    try:          # always: make is incremental, and a library older than its sources would test stale code
         subprocess.run(["make", "-s", "-C", d], check=True)
+    except Exception:
+        if not os.path.exists(os.path.join(d, "libhostsim.so")):
+            raise
     L = C.CDLL(os.path.join(d, "libhostsim.so"))
     vp, i, f = C.c_void_p, C.c_int, C.c_float
     P = C.POINTER

@@ -51,3 +51,71 @@ def test_counter_summary_lists_the_search_kernels(tmp_path):
     assert s["bytes_per_launch"] == 1024.0 * (2 * 1000.0 + 500.0)                    # FETCH doubled (16 B/lane streaming reads), KiB counters
     pre = s["search_kernels"]["k_pre"]
     assert pre["dispatches"] == 2 and pre["FETCH_SIZE_bytes_per_dispatch"] == 1024.0 * 200.0 and pre["WRITE_SIZE_bytes_per_dispatch"] == 1024.0 * 20.0
+
+
+class _FakeEngine:
+    """the slice of the Engine API bench.dump_outputs reads, with deterministic contents"""
+
+    def __init__(self, games, N, nrec, moves):
+        import types
+        self.cfg, self.P, self.A = types.SimpleNamespace(games=games), N * N, N * N + 1
+        self.nrec, self.moves = nrec, moves
+
+    def debug_live_record(self, g):
+        return (g * 5 + 3) % self.cfg.games + 100, 0          # (game id, moves so far): ids in another order than slots
+
+    def tree_root(self, g):
+        return 1000 + g
+
+    def node_info(self, g, root):
+        import types
+        return types.SimpleNamespace(N=float(g), W=0.5 * g, Q=0.5)
+
+    def node_floats(self, g, root, field):
+        import numpy as np
+        return np.arange(self.A, dtype=np.float32) * (field + 1) + g
+
+    def node_board(self, g, root):
+        import numpy as np
+        return (np.arange(self.P) % 3 - 1).astype(np.int8)
+
+    def stats(self):
+        return {"steps": 7, "positions": 11, "evals": 13}
+
+    def records(self):
+        import numpy as np
+        return [dict(game_id=k, num_moves=self.moves, result=1 - 2 * (k % 2), final_score=0.5 + k,
+                     moves=np.arange(self.moves, dtype=np.int16), pis=np.full((self.moves, self.A), k, np.float32),
+                     qs=np.full(self.moves, -k, np.float32)) for k in range(self.nrec)]
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    import numpy as np
+    bench = _load("agz_bench", "bench.py")
+    eng = _FakeEngine(games=16, N=5, nrec=6, moves=10)
+    shapes = bench.dump_outputs(eng, str(tmp_path / "all"))
+    a = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert set(a) == set(shapes) and all(list(a[k].shape) == shapes[k] for k in a)
+    assert all(x.dtype in (np.float32, np.float64) and x.size > 0 for x in a.values())
+    assert a["root_child_n"].shape == (16, 26) and (a["root_game_id"] == np.arange(16) + 100).all()
+    # row k holds the game with the k-th smallest id: id 103 runs in slot 0, id 104 (row 4) in slot 13
+    assert (a["root_prior"][3] == np.arange(26) * 3).all() and (a["root_nwq"][4] == [13, 6.5, 0.5]).all()
+    assert (a["record_game_id"] == np.arange(6)).all() and a["record_pis"].shape == (60, 26)
+    assert list(a["counters"]) == [13, 11, 7]                     # evals, positions, steps: keys in sorted order
+    # no finished game yet (a short timed window): no record arrays at all, and no array is empty
+    shapes = bench.dump_outputs(_FakeEngine(games=16, N=5, nrec=0, moves=10), str(tmp_path / "none"))
+    assert not any(k.startswith("record_") for k in shapes) and all(np.prod(v) > 0 for v in shapes.values())
+    assert sorted(p.stem for p in (tmp_path / "none").iterdir()) == sorted(shapes)
+    # a budget too small for everything: a seeded sample, the same one every time, in slot / game-id order
+    big = _FakeEngine(games=4096, N=9, nrec=200, moves=80)
+    budget = 4 << 20
+    for d in ("s1", "s2"):
+        bench.dump_outputs(big, str(tmp_path / d), budget=budget)
+    files = sorted((tmp_path / "s1").iterdir())
+    assert sum(p.stat().st_size for p in files) <= budget
+    for p in files:
+        assert np.array_equal(np.load(p), np.load(tmp_path / "s2" / p.name))
+    s = {p.stem: np.load(p) for p in files}
+    assert 0 < len(s["root_game_id"]) < 4096 and (np.diff(s["root_game_id"]) > 0).all()
+    assert 0 < len(s["record_game_id"]) < 200 and (np.diff(s["record_game_id"]) > 0).all()
+    assert s["record_pis"].shape == (80 * len(s["record_game_id"]), 82)

@@ -1,6 +1,6 @@
 """Weight checkpoints in the reference's BSON format (src/train.jl:14-35,
 src/play.jl:3-21).  CPU: reader/writer round trips, shapes and ordering, byte-exact rewrite of the
-files shipped with the reference (only where /root/reference exists), oracle forward with the
+files shipped with the reference (stored under tests/golden/shipped_models), oracle forward with the
 shipped 9x9/tower-0 parameters against the committed fixture.  GPU: load_model -> forward within
 1e-4 of the float64 fixture; save_model writes back the same bytes."""
 import os
@@ -16,7 +16,7 @@ from golden.make_golden import OracleNetSink
 bw = ag.bson_weights
 L = orc.lib()
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF_MODELS = "/root/reference/models"
+REF_MODELS = os.path.join(G, "shipped_models")          # the reference's models/ directory, byte for byte
 
 
 def fixture_lists():
@@ -138,7 +138,6 @@ def test_shipped_stem_activations_have_unit_scale_under_the_std_reading():
     assert np.median(centred) < 0.5
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference checkout not present")
 def test_shipped_files_decode_and_rewrite_byte_exact():
     ck = bw.read_checkpoint(REF_MODELS)
     d, lists = fixture_lists()
