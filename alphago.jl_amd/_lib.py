@@ -118,6 +118,7 @@ def load():
         "agz_net_init_synthetic": (i32, [E, u64]),
         "agz_net_forward": (i32, [E, i8p, i8p, i32p, i8p, i32, f32p, f32p]),
         "agz_net_forward_features": (i32, [E, f32p, i32, f32p, f32p]),
+        "agz_net_forward_features_sym": (i32, [E, f32p, i32p, i32, f32p, f32p]),
         "agz_features": (i32, [E, i8p, i8p, i32p, i8p, i32, f32p]),
         "agz_net_time_forward": (i32, [E, i32, i32, f32p]),
         "agz_net_time_conv": (i32, [E, i32, i32, f32p]),
@@ -134,6 +135,7 @@ def load():
         "agz_go_score": (i32, [E, i8p, f32p, i32, f32p]),
         "agz_selfplay_start": (i32, [E, i64]),
         "agz_selfplay_step": (i32, [E, i32]),
+        "agz_selfplay_set_symmetry": (i32, [E, i32]),
         "agz_engine_stats": (i32, [E, P(Stats)]),
         "agz_selfplay_select": (i32, [E, i32p]),
         "agz_selfplay_leaf_features": (i32, [E, f32p]),
@@ -159,6 +161,7 @@ def load():
         "agz_replay_trim": (i32, [E, i64]),
         "agz_replay_clear": (i32, [E]),
         "agz_replay_batch": (i32, [E, P(i64), i32p, i32, C.c_void_p, C.c_void_p, C.c_void_p, i32]),
+        "agz_replay_batch_sym": (i32, [E, P(i64), i32p, i32p, i32, C.c_void_p, C.c_void_p, C.c_void_p, i32]),
         "agz_train_step": (i32, [E, C.c_void_p, C.c_void_p, C.c_void_p, i32, i32, f32, f32, f32p]),
         "agz_train_reset": (i32, [E]),
         "agz_comm_unique_id": (i32, [P(C.c_uint8)]),

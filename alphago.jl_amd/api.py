@@ -173,20 +173,39 @@ class NeuralNet:
         """tower arithmetic of nn(positions): "f32" (default) or "f16" (fp16 operands, f32 accumulate)"""
         self.engine.set_precision(precision)
 
-    def __call__(self, positions):            # neural_net.jl:57-73
+    def __call__(self, positions, symmetry=None):            # neural_net.jl:57-73
+        """symmetry (ours, DESIGN.md "Board symmetries"): None = the reference's one orientation; s in 0..7 or an
+        array of one s per position = each position evaluated under T_s, pi back in board orientation; "average" =
+        the mean pi and v over all eight symmetries"""
         single = isinstance(positions, Position)
         plist = [positions] if single else list(positions)
         if plist and not isinstance(plist[0], Position):
             feats = np.stack([np.asarray(p.feats, np.float32).reshape(-1) for p in plist])
-            pi, v = self.engine.forward_features(feats)
+            pi, v = self.forward_features(feats, symmetry)
+        elif symmetry is not None:
+            soa = [p.soa() for p in plist]
+            feats = self.engine.features(np.stack([s[0] for s in soa]), np.stack([s[1] for s in soa]),
+                                         [s[2] for s in soa], [s[3] for s in soa])
+            pi, v = self.forward_features(feats, symmetry)
         else:
             soa = [p.soa() for p in plist]
             pi, v = self.engine.forward(np.stack([s[0] for s in soa]), np.stack([s[1] for s in soa]),
                                         [s[2] for s in soa], [s[3] for s in soa])
         return (pi[0], float(v[0])) if single else (pi.T.copy(), v)      # pi is A x B like the reference
 
-    def forward_features(self, feats):
-        return self.engine.forward_features(feats)
+    def forward_features(self, feats, symmetry=None):
+        """feats [B, 17*N*N] -> (pi [B, A], v [B]); symmetry as in __call__"""
+        if symmetry is None:
+            return self.engine.forward_features(feats)
+        feats = np.ascontiguousarray(feats, np.float32)
+        B = feats.shape[0]
+        if isinstance(symmetry, str):
+            if symmetry != "average":
+                raise ValueError(f"symmetry {symmetry!r}: None, 0..7, an array of those, or 'average'")
+            pi, v = self.engine.forward_features_sym(np.repeat(feats, 8, axis=0), np.tile(np.arange(8, dtype=np.int32), B))
+            return pi.reshape(B, 8, -1).mean(axis=1, dtype=np.float64).astype(np.float32), \
+                v.reshape(B, 8).mean(axis=1, dtype=np.float64).astype(np.float32)
+        return self.engine.forward_features_sym(feats, symmetry)
 
 
 def load_model(model_dir, env, bn_field="auto"):
@@ -359,7 +378,7 @@ class MCTSPlayer:
     plain arrays or Tracker-style objects carrying `.data` (mcts_play.jl:90)."""
 
     def __init__(self, env, network, num_readouts=800, two_player_mode=False, resign_threshold=-0.9, seed=0,
-                 game_id=0):
+                 game_id=0, symmetry=None):
         self.env = env
         self.network = network
         self.num_readouts = num_readouts
@@ -372,6 +391,11 @@ class MCTSPlayer:
                              resign_threshold=resign_threshold, seed=seed, external_network=0 if internal else 1)
         if internal:
             network.engine.copy_weights_to(self.engine)
+        if symmetry is not None:
+            # (ours) leaf evaluation under board symmetries: None, "random" or a fixed s in 0..7 (Engine.set_symmetry)
+            if not internal:
+                raise ValueError("symmetry needs a NeuralNet of this package: a caller's network receives Positions")
+            self.engine.set_symmetry(symmetry)
         self._game_id = game_id
         self.qs, self.searches_pi = [], []
         self.result, self.result_string = 0, ""
@@ -559,11 +583,14 @@ def seed(s):
     _stream["seed"], _stream["next_game"] = int(s), 0
 
 
-def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="f32", game_id_base=None, **cfg):
+def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="f32", game_id_base=None, symmetry=None,
+             **cfg):
     """selfplay(env, nn, num_ro) (src/selfplay.jl:1-45) -> the finished game's player (SelfPlayPlayer), exactly the
     call train() makes (train.jl:57).  `games=G` (ours) plays G games concurrently on the device and returns a list of
     G such players ordered by game id.  Game ids continue from the previous call (module stream, `seed()`), unless
-    `seed` / `game_id_base` pin them.  precision="f16" plays with the fp16-operand tower; default exact f32."""
+    `seed` / `game_id_base` pin them.  precision="f16" plays with the fp16-operand tower; default exact f32.
+    symmetry (ours): None (the reference's search), "random" (every leaf evaluated under a drawn board symmetry) or a
+    fixed s in 0..7 (Engine.set_symmetry)."""
     single = games is None
     games = 1 if single else int(games)
     if seed is None:
@@ -578,6 +605,8 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
                  game_id_base=game_id_base, record_capacity_games=games + 8, **cfg)
     nn.engine.copy_weights_to(eng)
     eng.set_precision(precision)
+    if symmetry is not None:
+        eng.set_symmetry(symmetry)
     eng.start(games)
     while eng.records_count() < games:
         eng.step(16)
@@ -594,13 +623,14 @@ EvalStats = namedtuple("EvalStats", "games_won num_games win_rate resigned moves
 
 
 def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, seed=0, slots=None,
-             return_stats=False, **cfg):
+             return_stats=False, symmetry=None, **cfg):
     """evaluate(env, black_net, white_net; num_games, ro) (src/neural_net.jl:103-158): black_net plays
     Black and white_net White in `num_games` games of two two_player_mode MCTSPlayers (arg-max moves,
     no noise, resign at -0.9); True iff Black's win rate reaches 0.55.  All games run concurrently on
     the device (arena_mode: one slot pair per game, both networks resident).  The tally follows the
     reference literally: a game counts for Black when `result(black.root.position) == BLACK`, i.e.
-    by the Tromp-Taylor score of the final position, also after a resignation (:147)."""
+    by the Tromp-Taylor score of the final position, also after a resignation (:147).  symmetry (ours): as for
+    selfplay(), applied to both networks' evaluations."""
     if black_net.tower_height != white_net.tower_height:
         raise ValueError("the arena keeps both networks in one engine: tower heights must match")
     pairs = min(num_games, 512) if slots is None else slots
@@ -610,6 +640,8 @@ def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, se
     eng.net_select(1)
     white_net.engine.copy_weights_to(eng)
     eng.net_select(0)
+    if symmetry is not None:
+        eng.set_symmetry(symmetry)
     eng.start(num_games)
     while eng.records_count() < num_games:
         eng.step(16)

@@ -136,6 +136,10 @@ agz_status agz_net_forward(agz_engine* e, const int8_t* boards, const int8_t* de
 agz_status agz_net_forward_features(agz_engine* e, const float* feats, int32_t B, float* pi_out, float* v_out) {
   return guard(e, [&](agz::Engine& E) { E.net_forward_features(feats, B, pi_out, v_out); });
 }
+agz_status agz_net_forward_features_sym(agz_engine* e, const float* feats, const int32_t* sym, int32_t B, float* pi,
+                                        float* v) {
+  return guard(e, [&](agz::Engine& E) { E.net_forward_features_sym(feats, sym, B, pi, v); });
+}
 agz_status agz_features(agz_engine* e, const int8_t* boards, const int8_t* deltas, const int32_t* ndeltas,
                         const int8_t* to_play, int32_t B, float* out) {
   return guard(e, [&](agz::Engine& E) { E.features(boards, deltas, ndeltas, to_play, B, out); });
@@ -285,6 +289,17 @@ agz_status agz_replay_clear(agz_engine* e) { return guard(e, [&](agz::Engine& E)
 agz_status agz_replay_batch(agz_engine* e, const int64_t* game, const int32_t* ply, int32_t B, float* feats,
                             float* pi, float* z, int32_t out_is_device) {
   return guard(e, [&](agz::Engine& E) { E.replay_batch(game, ply, B, feats, pi, z, out_is_device != 0); });
+}
+
+agz_status agz_replay_batch_sym(agz_engine* e, const int64_t* game, const int32_t* ply, const int32_t* sym, int32_t B,
+                                float* feats, float* pi, float* z, int32_t out_is_device) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(sym, AGZ_BAD_ARGUMENT, "sym is NULL");
+    E.replay_batch(game, ply, B, feats, pi, z, out_is_device != 0, sym);
+  });
+}
+agz_status agz_selfplay_set_symmetry(agz_engine* e, int32_t mode) {
+  return guard(e, [&](agz::Engine& E) { E.set_symmetry(mode); });
 }
 
 agz_status agz_train_step(agz_engine* e, const float* feats, const float* pi, const float* z, int32_t B,

@@ -64,8 +64,9 @@ class Engine {
   void replay_game(int64_t k, int16_t* moves, float* pis, float* qs);
   void replay_trim(int64_t max_positions);
   void replay_clear();
+  // sym != NULL: sample b under the board symmetry T_sym[b] (agz_replay_batch_sym)
   void replay_batch(const int64_t* game, const int32_t* ply, int B, float* feats, float* pi, float* z,
-                    bool out_is_device);
+                    bool out_is_device, const int32_t* sym = nullptr);
   DevBuf<uint8_t>& pack_scratch() { return s_pack_; }
   // one optimisation step on the selected network (agz_train.hip)
   void train_step(const float* feats, const float* pi, const float* z, int B, bool is_device, float eta, float rho,
@@ -81,6 +82,9 @@ class Engine {
   void net_forward_positions(const int8_t* boards, const int8_t* deltas, const int32_t* ndeltas,
                              const int8_t* to_play, int B, float* pi_out, float* v_out);
   void net_forward_features(const float* feats, int B, float* pi_out, float* v_out);
+  void net_forward_features_sym(const float* feats, const int32_t* sym, int B, float* pi_out, float* v_out);
+  // board symmetry of the engine's own evaluations (agz_selfplay_set_symmetry): AGZ_SYMMETRY_NONE, 0..7, RANDOM
+  void set_symmetry(int mode);
   void features(const int8_t* boards, const int8_t* deltas, const int32_t* ndeltas, const int8_t* to_play,
                 int B, float* out);
   float time_forward(int B, int iters);
@@ -148,6 +152,8 @@ class Engine {
   DevBuf<uint8_t> s_leafrows_;
   DevBuf<int32_t> s_i32a_, s_i32b_, s_i32c_, s_i32d_;
   DevBuf<float> s_f32a_, s_f32b_;
+  DevBuf<float> s_symf_, s_symp_;     // feature / policy rows before their symmetry transform
+  DevBuf<int32_t> s_sym_;
   DevBuf<int16_t> s_i16a_;
   DevBuf<int64_t> s_i64a_;
   DevBuf<double> s_f64_;

@@ -201,6 +201,56 @@ __global__ __launch_bounds__(kWavesPerLeaf * kWave) void k_leaf_features(View V,
                 kWavesPerLeaf);
 }
 
+// The same under the board symmetry each leaf was recorded with (View::leaf_sym): launched instead of k_leaf_features
+// while agz_selfplay_set_symmetry is on, so that k_leaf_features itself stays what it is
+__global__ __launch_bounds__(kWavesPerLeaf * kWave) void k_leaf_features_sym(View V, int g0, int slots, float* x32, float* whcn) {
+  const int slot = (int)blockIdx.x;
+  if (slot >= slots) return;
+  const int g = g0 + slot / V.par, k = slot % V.par;
+  if (k >= V.gs[g].nleaves) return;
+  HipWave w((int)(threadIdx.x & (kWave - 1)));
+  const long row = (long)V.gs[g].leaf_base + k;
+  leaf_features<true>(w, V, g, k, x32 ? x32 + row * V.P * 32 : nullptr, whcn ? whcn + row * 17 * V.P : nullptr,
+                      (int)(threadIdx.x >> 6), kWavesPerLeaf);
+}
+
+// The network's policy of a leaf evaluated under T_s back to board orientation, in place: pi[p] = pi_net[T_s(p)], pass
+// unchanged (the value needs nothing).  One wave per leaf slot, the same slots / rows as k_leaf_features_sym.
+__global__ __launch_bounds__(kWave) void k_pi_unpermute(View V, int g0, int slots, float* pi) {
+  __shared__ float row[kAPMax];
+  const int slot = (int)blockIdx.x;
+  if (slot >= slots) return;
+  const int g = g0 + slot / V.par, k = slot % V.par;
+  if (k >= V.gs[g].nleaves) return;
+  const int s = V.leaf_sym[(long)g * V.par + k];
+  float* r = pi + ((long)V.gs[g].leaf_base + k) * V.A;
+  for (int a = (int)threadIdx.x; a < V.A; a += kWave) row[a] = r[a];
+  __syncthreads();
+  for (int a = (int)threadIdx.x; a < V.A; a += kWave) r[a] = row[sym_point(s, V.N, a)];
+}
+
+// Row b of `out` = row b of `in` under T_sym[b] (inverse = 0) or T_sym[b]^-1 (inverse = 1).  A row is `planes` blocks of
+// N*N point values (feature planes in agz_features order, or the board part of a policy row) followed by `tail` values
+// that are copied as they are (the pass entry).  Forward: out[plane][T_s(p)] = in[plane][p], written as a gather so the
+// stores are consecutive.  Un-permuting a policy the network produced under T_s is the inverse: out[p] = in[T_s(p)].
+__global__ __launch_bounds__(256) void k_sym_rows(const float* in, float* out, const int32_t* sym, int N, int planes,
+                                                  int tail, int inverse) {
+  const int b = (int)blockIdx.x, P = N * N;
+  const int body = planes * P, len = body + tail;
+  const int s = sym[b];
+  const int from = inverse ? s : sym_inverse(s);    // out[q] = in[T_from(q)]
+  const float* src = in + (long)b * len;
+  float* dst = out + (long)b * len;
+  for (int i = (int)threadIdx.x; i < len; i += (int)blockDim.x) {
+    int j = i;
+    if (i < body) {
+      const int plane = i / P;
+      j = plane * P + sym_point(from, N, i - plane * P);
+    }
+    dst[i] = src[j];
+  }
+}
+
 // The Vector{Position} a caller-supplied network receives (mcts_play.jl:89): per collected leaf of slot g, its own
 // board and the up-to-7 older boards behind the history planes (the same sources k_leaf_features reads), its NodeMeta
 // and the move before its last one -- gathered into contiguous rows for ONE copy to the host.
@@ -541,7 +591,10 @@ void Engine::step(int nsteps) {
     if (ev) (void)hipEventRecord(ev[2], stream_);
     hipLaunchKernelGGL(cfg_.arena_mode ? k_scan_arena : k_scan, dim3(1), dim3(256), 0, stream_, V_);
     if (ev) (void)hipEventRecord(ev[3], stream_);
-    hipLaunchKernelGGL(k_leaf_features, dim3(bcap_), dim3(kWavesPerLeaf * kWave), 0, stream_, V_, 0, bcap_, d_x32_.p, (float*)nullptr);
+    if (V_.symmetry)
+      hipLaunchKernelGGL(k_leaf_features_sym, dim3(bcap_), dim3(kWavesPerLeaf * kWave), 0, stream_, V_, 0, bcap_, d_x32_.p, (float*)nullptr);
+    else
+      hipLaunchKernelGGL(k_leaf_features, dim3(bcap_), dim3(kWavesPerLeaf * kWave), 0, stream_, V_, 0, bcap_, d_x32_.p, (float*)nullptr);
     if (ev) (void)hipEventRecord(ev[4], stream_);
     if (cfg_.arena_mode) {   // evaluate(): Black's players ask network 0, White's network 1
       const int half = bcap_ / 2;
@@ -551,6 +604,7 @@ void Engine::step(int nsteps) {
     } else {
       net_->forward(d_x32_.p, V_.batch_count, bcap_, d_pi_.p, d_v_.p);
     }
+    if (V_.symmetry) hipLaunchKernelGGL(k_pi_unpermute, dim3(bcap_), dim3(kWave), 0, stream_, V_, 0, bcap_, d_pi_.p);
     if (ev) (void)hipEventRecord(ev[5], stream_);
     hipLaunchKernelGGL(k_post, dim3(V_.games), dim3(kWave), 0, stream_, V_);
     if (ev) {
@@ -1012,10 +1066,12 @@ void Engine::weights_set_flat(const std::vector<float>& w) {
 }
 
 void Engine::replay_batch(const int64_t* game, const int32_t* ply, int B, float* feats, float* pi, float* z,
-                          bool out_is_device) {
+                          bool out_is_device, const int32_t* sym) {
   AGZ_REQUIRE(B >= 0, AGZ_BAD_ARGUMENT, "negative batch");
   if (B == 0) return;
   AGZ_REQUIRE(game && ply && feats, AGZ_BAD_ARGUMENT, "null pointer");
+  if (sym)
+    for (int b = 0; b < B; ++b) AGZ_REQUIRE(sym[b] >= 0 && sym[b] < 8, AGZ_BAD_ARGUMENT, "sym[%d] = %d: 0..7", b, sym[b]);
   std::vector<int64_t> off((size_t)B);
   for (int b = 0; b < B; ++b) {
     AGZ_REQUIRE(game[b] >= 0 && game[b] < (int64_t)rp_hdr_.size(), AGZ_BAD_ARGUMENT, "sample %d: game out of range", b);
@@ -1037,8 +1093,24 @@ void Engine::replay_batch(const int64_t* game, const int32_t* ply, int B, float*
   }
   AGZ_HIP(hipMemcpyAsync(s_i64a_.p, off.data(), sizeof(int64_t) * (size_t)B, hipMemcpyHostToDevice, stream_));
   AGZ_HIP(hipMemcpyAsync(s_i32a_.p, ply, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_replay_arena_batch, dim3(B), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
-                     (const int64_t*)s_i64a_.p, (const int32_t*)s_i32a_.p, s_boards_.p, df, dp, dz);
+  if (sym) {
+    // agz_replay_batch_sym: the samples as they are into scratch, then sample b under T_sym[b] into the outputs
+    s_sym_.ensure((size_t)B);
+    s_symf_.ensure(per * (size_t)B);
+    s_symp_.ensure((size_t)B * V_.A);
+    AGZ_HIP(hipMemcpyAsync(s_sym_.p, sym, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, stream_));
+    hipLaunchKernelGGL(k_replay_arena_batch, dim3(B), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
+                       (const int64_t*)s_i64a_.p, (const int32_t*)s_i32a_.p, s_boards_.p, s_symf_.p,
+                       dp ? s_symp_.p : nullptr, dz);
+    hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)s_symf_.p, df, (const int32_t*)s_sym_.p,
+                       V_.N, 17, 0, 0);
+    if (dp)
+      hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)s_symp_.p, dp,
+                         (const int32_t*)s_sym_.p, V_.N, 1, 1, 0);
+  } else {
+    hipLaunchKernelGGL(k_replay_arena_batch, dim3(B), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
+                       (const int64_t*)s_i64a_.p, (const int32_t*)s_i32a_.p, s_boards_.p, df, dp, dz);
+  }
   AGZ_HIP(hipGetLastError());
   if (!out_is_device) {
     AGZ_HIP(hipMemcpyAsync(feats, df, sizeof(float) * per * (size_t)B, hipMemcpyDeviceToHost, stream_));
@@ -1177,6 +1249,46 @@ void Engine::net_forward_features(const float* feats, int B, float* pi_out, floa
   AGZ_HIP(hipMemcpyAsync(v_out, s_f32b_.p + (size_t)B * V_.A, sizeof(float) * B, hipMemcpyDeviceToHost, stream_));
   AGZ_HIP(hipStreamSynchronize(stream_));
   net().check_async_error();      // a persistent tower launch that gave up: these outputs are garbage, say so now
+}
+
+// agz_net_forward_features_sym: row b under T_sym[b] (k_sym_rows), the plain forward, pi back to board orientation
+void Engine::net_forward_features_sym(const float* feats, const int32_t* sym, int B, float* pi_out, float* v_out) {
+  AGZ_REQUIRE(B >= 0, AGZ_BAD_ARGUMENT, "B < 0");
+  if (B == 0) return;
+  AGZ_REQUIRE(feats && sym && pi_out && v_out, AGZ_BAD_ARGUMENT, "null pointer");
+  for (int b = 0; b < B; ++b) AGZ_REQUIRE(sym[b] >= 0 && sym[b] < 8, AGZ_BAD_ARGUMENT, "sym[%d] = %d: 0..7", b, sym[b]);
+  const size_t P = V_.P;
+  d_whcn_.ensure((size_t)B * 17 * P);
+  d_count_.ensure(1);
+  s_sym_.ensure((size_t)B);
+  s_symf_.ensure((size_t)B * 17 * P);
+  s_symp_.ensure((size_t)B * V_.A);
+  s_f32a_.ensure((size_t)B * P * 32);
+  s_f32b_.ensure((size_t)B * (V_.A + 1));
+  AGZ_HIP(hipMemcpyAsync(d_whcn_.p, feats, sizeof(float) * (size_t)B * 17 * P, hipMemcpyHostToDevice, stream_));
+  AGZ_HIP(hipMemcpyAsync(s_sym_.p, sym, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, stream_));
+  AGZ_HIP(hipMemcpyAsync(d_count_.p, &B, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)d_whcn_.p, s_symf_.p,
+                     (const int32_t*)s_sym_.p, V_.N, 17, 0, 0);
+  launch_whcn_to_x32(s_symf_.p, B, V_.N, s_f32a_.p, stream_);
+  net().forward(s_f32a_.p, d_count_.p, B, s_f32b_.p, s_f32b_.p + (size_t)B * V_.A);
+  hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)s_f32b_.p, s_symp_.p,
+                     (const int32_t*)s_sym_.p, V_.N, 1, 1, 1);
+  AGZ_HIP(hipGetLastError());
+  AGZ_HIP(hipMemcpyAsync(pi_out, s_symp_.p, sizeof(float) * (size_t)B * V_.A, hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipMemcpyAsync(v_out, s_f32b_.p + (size_t)B * V_.A, sizeof(float) * B, hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  net().check_async_error();
+}
+
+void Engine::set_symmetry(int mode) {
+  AGZ_REQUIRE(mode >= AGZ_SYMMETRY_NONE && mode <= AGZ_SYMMETRY_RANDOM, AGZ_BAD_ARGUMENT,
+              "symmetry mode %d: -1 (none), 0..7 (fixed T_s) or 8 (random)", mode);
+  AGZ_REQUIRE(!cfg_.external_network, AGZ_BAD_ARGUMENT,
+              "symmetry applies to the engine's own network; with external_network=1 the caller evaluates Positions");
+  AGZ_REQUIRE(tree_batch_ == 0, AGZ_BAD_ARGUMENT,
+              "symmetry: not between agz_tree_search_select and agz_tree_search_incorporate");
+  V_.symmetry = mode < 0 ? 0 : mode + 1;    // the View travels to the kernels by value: effective from the next launch
 }
 
 // random stone features (not zeros: DVFS makes zero-filled operands look faster than real data)
@@ -1438,8 +1550,14 @@ int Engine::tree_search_incorporate(int g, const float* pi, const float* v) {
     } else {
       d_count_.ensure(1);
       AGZ_HIP(hipMemcpyAsync(d_count_.p, &n, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-      hipLaunchKernelGGL(k_leaf_features, dim3(V_.par), dim3(kWavesPerLeaf * kWave), 0, stream_, V_, g, V_.par, d_x32_.p, (float*)nullptr);
-      net_->forward(d_x32_.p, d_count_.p, std::min(bcap_, V_.par), d_pi_.p, d_v_.p);
+      if (V_.symmetry) {
+        hipLaunchKernelGGL(k_leaf_features_sym, dim3(V_.par), dim3(kWavesPerLeaf * kWave), 0, stream_, V_, g, V_.par, d_x32_.p, (float*)nullptr);
+        net_->forward(d_x32_.p, d_count_.p, std::min(bcap_, V_.par), d_pi_.p, d_v_.p);
+        hipLaunchKernelGGL(k_pi_unpermute, dim3(V_.par), dim3(kWave), 0, stream_, V_, g, V_.par, d_pi_.p);
+      } else {
+        hipLaunchKernelGGL(k_leaf_features, dim3(V_.par), dim3(kWavesPerLeaf * kWave), 0, stream_, V_, g, V_.par, d_x32_.p, (float*)nullptr);
+        net_->forward(d_x32_.p, d_count_.p, std::min(bcap_, V_.par), d_pi_.p, d_v_.p);
+      }
     }
   }
   TreeArgs T;

@@ -6,7 +6,30 @@
 
 #include "agz_state.h"
 
+#if defined(__HIPCC__)
+#define AGZ_SYM_FN __host__ __device__ __forceinline__
+#else
+#define AGZ_SYM_FN inline
+#endif
+
 namespace agz {
+
+// ---- the eight symmetries of the board (DESIGN.md "Board symmetries"), the one definition every kernel uses and
+// alphago_jl_amd.symmetry mirrors.  Point p = row + N*col (api.to_flat), p == N*N is pass.  T_s(row, col), s in 0..7:
+// (1) s & 4: swap row and col; (2) s & 2: row = N-1-row; (3) s & 1: col = N-1-col.  T_0 is the identity.
+// A transformed position has X'[plane][T_s(p)] = X[plane][p]; the prior of move p is net(X').pi[T_s(p)].
+AGZ_SYM_FN int sym_point(int s, int N, int p) {
+  if (p >= N * N) return p;
+  int r = p % N, c = p / N;
+  if (s & 4) { const int t = r; r = c; c = t; }
+  if (s & 2) r = N - 1 - r;
+  if (s & 1) c = N - 1 - c;
+  return r + N * c;
+}
+// T_s^-1 = T_inverse(s): the reflections (s < 4, and the two transposes 4, 7) are their own inverses; the two quarter
+// turns 5 and 6 are each other's (undoing "swap, then flip" flips first, and a row flip before the swap is a column
+// flip after it)
+AGZ_SYM_FN int sym_inverse(int s) { return s < 4 ? s : 4 | ((s & 1) << 1) | ((s >> 1) & 1); }
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
@@ -78,6 +101,8 @@ inline void for_each_buffer(View& V, F&& f) {
   f(V.counters, (size_t)CT_COUNT);
   f(V.batch_count, (size_t)2);
   f(V.ar_hdr, (size_t)5 * (V.games / 2 + 1));        // 4 header words + 1 abort word per pair (agz_search.h)
+  f(V.leaf_sym, leaves);
+  f(V.eval_ord, (size_t)V.games);
 }
 
 }  // namespace agz

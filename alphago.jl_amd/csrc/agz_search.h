@@ -891,6 +891,7 @@ AGZ_FN void game_start(W& w, const View& V, Scratch& S, int g, uint64_t game_id)
     G.free_top = V.cap; G.garbage = 0; G.nleaves = 0; G.err = 0; G.result = 0; G.was_resign = 0; G.nodes_used = 0;
     G.short_first = 0; G.short_searches = 0;
     G.phase = G_INIT;
+    V.eval_ord[g] = 0;
   }
   w.sync();
   const int id = pool_alloc(w, V, S, g);
@@ -1056,6 +1057,16 @@ AGZ_FN void record_leaf(W& w, const View& V, Scratch& S, int g, int k, int leaf,
     V.leaf_node[li] = leaf;
     V.leaf_plen[li] = plen;
     V.leaf_tp[li] = V.meta[node_index(V, g, leaf)].to_play;
+    // e = ordinal of this evaluation among all the game has sent to the network, counted whether or not a symmetry
+    // mode is on, so that switching the mode mid-game leaves the draw key of later evaluations what it would have been
+    const int e = V.eval_ord[g];
+    V.eval_ord[g] = e + 1;
+    if (V.symmetry) {
+      // the transform this evaluation is made under (DESIGN.md "Board symmetries"): fixed, or the e-th draw of the game
+      V.leaf_sym[li] = (int8_t)(V.symmetry <= 8 ? V.symmetry - 1
+                                                 : (int)agz_index(agz_draw_u64(V.seed, G.game_id, 0, AGZ_SITE_SYMMETRY,
+                                                                               (uint64_t)e), 8u));
+    }
   }
   w.sync();
 }
@@ -1355,7 +1366,9 @@ AGZ_FN void game_post(W& w, const View& V, Scratch& S, int g) {
 }
 
 // Feature planes of one leaf slot into the stem-input layout [P][32] (features.jl:3-26)
-template <class W>
+// Sym: the planes of the leaf's position under T_s, s = V.leaf_sym[leaf] -- X'[plane][p] = X[plane][T_s^-1(p)]: the remap
+// is on the read side, so the store pattern below is the same (Sym = false is the instantiation without symmetries)
+template <bool Sym = false, class W>
 // part / parts: this wave does the part-th of `parts` equal shares of the leaf's items (k_leaf_features gives a leaf four waves)
 AGZ_FN void leaf_features(W& w, const View& V, int g, int k, float* x32, float* whcn, int part = 0, int parts = 1) {
   const long li = (long)g * V.par + k;
@@ -1363,7 +1376,10 @@ AGZ_FN void leaf_features(W& w, const View& V, int g, int k, float* x32, float* 
   const int P = V.P;
   int src[8];
   for (int s = 0; s < 8; ++s) src[s] = V.leaf_featsrc[li * 8 + s];
+  int sinv = 0;
+  if constexpr (Sym) sinv = sym_inverse(V.leaf_sym[li]);
   auto stone = [&](int s, int p) -> int {
+    if constexpr (Sym) p = sym_point(sinv, V.N, p);
     return src[s] >= 0 ? V.board[node_index(V, g, src[s]) * V.PP + p] : V.hist[((long)g * 7 + (-src[s] - 1)) * V.PP + p];
   };
   if (x32) {
@@ -1497,6 +1513,7 @@ AGZ_FN void tree_op(W& w, const View& V, Scratch& S, const TreeArgs& T) {
         G.free_top = V.cap; G.garbage = 0; G.nleaves = 0; G.err = 0; G.result = 0; G.was_resign = 0; G.nodes_used = 0;
         G.short_searches = 0;
         G.phase = G_MANUAL;
+        V.eval_ord[g] = 0;
         G.resign_threshold = V.resign_threshold; G.resign_disabled = 0;
       }
       w.sync();

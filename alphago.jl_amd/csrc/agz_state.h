@@ -131,6 +131,11 @@ struct View {
   int32_t* ar_hdr;        // arena mailbox [games/2][4]: {local game index, plies played, done, -}
   const float* pi;        // [batch][A]
   const float* v;         // [batch]
+  // board symmetries (agz_selfplay_set_symmetry; zero = off, the View{} of the host simulator): 1 + s = every
+  // evaluation under T_s, 1 + AGZ_SYMMETRY_RANDOM = one T_s per evaluation from the draw stream (AGZ_SITE_SYMMETRY)
+  int32_t symmetry;
+  int8_t* leaf_sym;       // [games][par]: s of each recorded leaf (written only while symmetry != 0)
+  int32_t* eval_ord;      // [games]: network evaluations the slot's game has requested (the draw index)
 };
 
 }  // namespace agz

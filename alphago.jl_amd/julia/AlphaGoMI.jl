@@ -264,6 +264,41 @@ function (nn::NeuralNet)(positions::Vector{Position})
 end
 (nn::NeuralNet)(pos::Position) = ((p, v) = nn([pos]); (p[:, 1], v[1]))        # neural_net.jl:70-73
 
+# ---- board symmetries (ours; DESIGN.md "Board symmetries").  T_s, s in 0:7, on the 0-based point p = row + N*col:
+# s & 4 swaps row and col, then s & 2 flips the row, then s & 1 flips the column.  Engine-wide mode: nothing / -1 (off),
+# 0:7 (fixed T_s), :random / 8 (one drawn T_s per network evaluation).
+symmetry_mode(s) = s === nothing ? Int32(-1) : s === :random ? Int32(8) : Int32(s)
+set_symmetry!(e::Engine, s) =
+  check(e, ccall((:agz_selfplay_set_symmetry, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, symmetry_mode(s)))
+
+# feats N x N x 17 x B (or 17N^2 x B): the network on B positions, pi A x B and v B.  symmetry = nothing (the default):
+# one orientation, agz_net_forward_features.  An integer s in 0:7, or one per column: column b evaluated under T_s, pi
+# back in board orientation (agz_net_forward_features_sym).  :average: the mean pi and v over all eight T_s (each
+# position tiled x8 through the _sym entry point, summed in Float64 like the Python mirror).
+function forward_features(nn::NeuralNet, feats::Array{Float32}; symmetry = nothing)
+  A = nn.env.action_space
+  B = length(feats) ÷ (17 * nn.env.N * nn.env.N)
+  pi = zeros(Float32, A, B); v = zeros(Float32, B)
+  if symmetry === nothing
+    check(nn.engine, ccall((:agz_net_forward_features, libagz), Int32,
+          (Ptr{Cvoid}, Ptr{Float32}, Int32, Ptr{Float32}, Ptr{Float32}), nn.engine.handle, feats, B, pi, v))
+    return pi, v
+  end
+  if symmetry === :average
+    tiled = reshape(repeat(reshape(feats, :, 1, B), 1, 8, 1), :, 8 * B)     # column 8(b-1) + k + 1 = position b, T_k
+    p8, v8 = forward_features(nn, tiled; symmetry = repeat(Int32.(0:7), B))
+    pm = Float32.(dropdims(sum(Float64.(reshape(p8, A, 8, B)), dims = 2), dims = 2) ./ 8)
+    vm = Float32.(vec(sum(Float64.(reshape(v8, 8, B)), dims = 1)) ./ 8)
+    return pm, vm
+  end
+  sym = symmetry isa Integer ? fill(Int32(symmetry), B) : Int32.(collect(symmetry))
+  @assert length(sym) == B
+  check(nn.engine, ccall((:agz_net_forward_features_sym, libagz), Int32,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int32}, Int32, Ptr{Float32}, Ptr{Float32}),
+        nn.engine.handle, feats, sym, B, pi, v))
+  pi, v
+end
+
 # ------------------------------------------------------------------ MCTSPlayer (single tree, slot 0)
 # MCTSPlayer(env, network; num_readouts, two_player_mode, resign_threshold), mcts_play.jl:3-24.
 # `network` is any callable positions -> (pi, v) (duck-typed field, mcts_play.jl:5): a NeuralNet of
@@ -285,12 +320,13 @@ mutable struct MCTSPlayer
   recent::Vector{PlayerMove}            # start.recent + every move played since: root.position.recent (board.jl:299)
 end
 function MCTSPlayer(env::GoEnv, network; num_readouts = 800, two_player_mode = false,
-                    resign_threshold = -0.9, seed = 0)
+                    resign_threshold = -0.9, seed = 0, symmetry = nothing)
   τ = two_player_mode ? -1 : (env.N * env.N ÷ 12) ÷ 2 * 2
   th = network isa NeuralNet ? network.tower_height : 0
   e = Engine(board_size = env.N, tower_height = th, games = 1, num_readouts = num_readouts,
              parallel_readouts = 64, two_player_mode = two_player_mode,
              resign_threshold = resign_threshold, seed = seed, external_network = !(network isa NeuralNet))
+  symmetry === nothing || set_symmetry!(e, symmetry)
   MCTSPlayer(env, network, num_readouts, two_player_mode, τ, Float32[], Vector{Float32}[], 0, "",
              resign_threshold, e, nothing, PlayerMove[])
 end
@@ -661,7 +697,7 @@ const STREAM = Ref((UInt64(0), UInt64(0)))                     # (seed, next gam
 seed!(s::Integer) = (STREAM[] = (UInt64(s), UInt64(0)); nothing)
 
 function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Nothing, Int} = nothing,
-                  slots::Union{Nothing, Int} = nothing, seed = nothing, game_id_base = nothing)
+                  slots::Union{Nothing, Int} = nothing, seed = nothing, game_id_base = nothing, symmetry = nothing)
   G = games === nothing ? 1 : games
   if seed === nothing
     seed, next = STREAM[]
@@ -674,6 +710,7 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
   e = Engine(board_size = env.N, tower_height = nn.tower_height, games = slots === nothing ? min(G, 1024) : slots,
              num_readouts = num_ro, seed = seed, game_id_base = game_id_base, record_capacity_games = G + 8)
   copy_weights!(e, nn.engine)
+  symmetry === nothing || set_symmetry!(e, symmetry)
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, G))
   while ccall((:agz_records_count, libagz), Int64, (Ptr{Cvoid},), e.handle) < G
     check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 16))
@@ -786,7 +823,7 @@ set_precision!(e::Engine, p::Symbol) =      # :f32 (default, exact), :f16 (fp16 
 # games run concurrently.  Black's tally is `result(black.root.position) == BLACK` (:147), i.e.
 # final_score > 0, also for resigned games.
 function evaluate(env::GoEnv, black_net::NeuralNet, white_net::NeuralNet; num_games = 400, ro = 800,
-                  verbose::Bool = false, seed = 0, pairs::Int = min(num_games, 512))
+                  verbose::Bool = false, seed = 0, pairs::Int = min(num_games, 512), symmetry = nothing)
   @assert black_net.tower_height == white_net.tower_height
   e = Engine(board_size = env.N, tower_height = black_net.tower_height, games = 2 * pairs, num_readouts = ro,
              seed = seed, record_capacity_games = num_games + 8, arena_mode = true)
@@ -794,6 +831,7 @@ function evaluate(env::GoEnv, black_net::NeuralNet, white_net::NeuralNet; num_ga
   check(e, ccall((:agz_net_select, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 1))
   copy_weights!(e, white_net.engine)
   check(e, ccall((:agz_net_select, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 0))
+  symmetry === nothing || set_symmetry!(e, symmetry)
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, num_games))
   while ccall((:agz_records_count, libagz), Int64, (Ptr{Cvoid},), e.handle) < num_games
     check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 16))
@@ -906,6 +944,18 @@ function replay_batch(e::Engine, env::GoEnv, games::Vector{Int64}, plies::Vector
                  e.handle, games, plies, B, feats, pi, z, 0))
   feats, pi, z
 end
+
+# the same with sample b under the board symmetry T_sym[b] (augmentation); augment = true draws one s per sample
+function replay_batch(e::Engine, env::GoEnv, games::Vector{Int64}, plies::Vector{Int32}, sym::Vector{Int32})
+  B = length(games)
+  feats = zeros(Float32, env.N * env.N * 17, B); pi = zeros(Float32, env.action_space, B); z = zeros(Float32, B)
+  check(e, ccall((:agz_replay_batch_sym, libagz), Int32,
+                 (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int32),
+                 e.handle, games, plies, sym, B, feats, pi, z, 0))
+  feats, pi, z
+end
+sample(e::Engine, env::GoEnv, games::Vector{Int64}, plies::Vector{Int32}; augment::Bool = false, rng = Random.default_rng()) =
+  augment ? replay_batch(e, env, games, plies, Int32.(rand(rng, 0:7, length(games)))) : replay_batch(e, env, games, plies)
 
 # _train(nn, (positions, pi, z), Momentum(2f-2)) for one batch (neural_net.jl:85-101): returns
 # (total, policy, value, regulariser) losses before the update

@@ -76,10 +76,17 @@ class ReplayBuffer:
         order = rng.permutation(batch_size)                       # sample() returns them in random order
         return [out[i] for i in order], games
 
-    def sample(self, batch_size, rng, engine, out=None):
+    def sample(self, batch_size, rng, engine, out=None, augment=False):
         """-> (features [B][17*N*N] (numpy, or the CUDA tensor `out`), pi [A][B], results [B]) like
         get_replay_batch's (pos_replay, pi_replay = hcat(...), res_replay), the positions already
-        turned into the network's input planes by device replay"""
+        turned into the network's input planes by device replay.
+        augment (ours, DESIGN.md "Board symmetries"): sample b is returned under a board symmetry T_s, one s per sample
+        drawn from `rng` after the samples themselves -- features and the board part of pi transformed, pass and the
+        result unchanged.  This buffer keeps its games on the host, so the transform is applied to the host arrays
+        (numpy outputs only); games in the engine's device replay arena are augmented on the device by
+        Engine.replay_batch_sym / agz_replay_batch_sym."""
+        if augment and out is not None:
+            raise ValueError("augment=True returns numpy features; device batches: Engine.replay_batch_sym")
         pairs, games = self.sample_indices(batch_size, rng)
         used = sorted({g for g, _ in pairs})
         offs, chunks, o = {}, [], 0
@@ -91,6 +98,16 @@ class ReplayBuffer:
         feats = engine.replay_features(moves, [offs[g] for g, _ in pairs], [j for _, j in pairs], out=out)
         pi = np.stack([games[g]["pis"][j] for g, j in pairs], axis=1)
         res = np.array([games[g]["result"] for g, _ in pairs], np.int64)
+        if augment:
+            from . import symmetry
+            N = self.env.N
+            draw = rng.integers if hasattr(rng, "integers") else rng.randint
+            sym = np.asarray(draw(0, 8, size=batch_size), np.int64)
+            for s in range(1, 8):
+                rows = np.nonzero(sym == s)[0]
+                if rows.size:
+                    feats[rows] = symmetry.apply_features(feats[rows], s, N)
+                    pi[:, rows] = symmetry.apply_policy(pi[:, rows].T, s, N).T
         return feats, pi, res
 
     def positions(self):

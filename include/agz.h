@@ -129,6 +129,15 @@ agz_status agz_net_forward(agz_engine* e, const int8_t* boards, const int8_t* de
 /* same on a feature tensor N x N x 17 x B already in host memory */
 agz_status agz_net_forward_features(agz_engine* e, const float* feats, int32_t B, float* pi_out,
                                     float* v_out);
+/* Board symmetries (ours; the reference evaluates one orientation, features.jl:3-26).  Point p = row + N*col; for s in
+ * 0..7, T_s(row, col) does, in order: s & 4 swap row and col; s & 2 row = N-1-row; s & 1 col = N-1-col.  T_0 is the
+ * identity, pass maps to pass; the quarter turns 5 and 6 are each other's inverse, every other T_s is its own.  A row
+ * of features under T_s is X'[plane][T_s(p)] = X[plane][p]; the prior of move p is then net(X').pi[T_s(p)].
+ * agz_net_forward_features_sym: feature rows as agz_net_forward_features takes them ([plane][p] per row), row b is
+ * evaluated under T_sym[b], sym[b] in 0..7, and its pi comes back in board orientation (pi[p] = pi_net[T_s(p)], pass
+ * unchanged); v is the network's value of the transformed row. */
+agz_status agz_net_forward_features_sym(agz_engine* e, const float* feats, const int32_t* sym, int32_t B, float* pi,
+                                        float* v);
 /* get_feats(pos) -> N x N x 17 (x B), features.jl:3-26 */
 agz_status agz_features(agz_engine* e, const int8_t* boards, const int8_t* deltas,
                         const int32_t* ndeltas, const int8_t* to_play, int32_t B, float* out);
@@ -208,6 +217,21 @@ agz_status agz_go_score(agz_engine* e, const int8_t* boards, const float* komi, 
  * their slot recycled until `total_games` have been started (0 = recycle forever). */
 agz_status agz_selfplay_start(agz_engine* e, int64_t total_games);
 agz_status agz_selfplay_step(agz_engine* e, int32_t nsteps);          /* asynchronous */
+/* Board symmetries in the engine's own network evaluations (AlphaGo Zero's random-symmetry leaf evaluation; T_s as at
+ * agz_net_forward_features_sym).  mode AGZ_SYMMETRY_NONE (-1, the default): one orientation, the reference's search;
+ * 0..7: every evaluation under T_mode; AGZ_SYMMETRY_RANDOM (8): evaluation e of a game (0-based, in the order the
+ * game sends leaves to the network; terminal leaves are not evaluated and not counted) is made under
+ * T_s, s = agz_index(agz_draw_u64(seed, game_id, 0, AGZ_SITE_SYMMETRY, e), 8) (include/agz_draws.h).  The leaf's
+ * features are transformed, the network runs, its pi goes back to board orientation before it becomes the leaf's
+ * priors.  Covers agz_selfplay_step (arena_mode: both networks) and agz_tree_search / agz_tree_search_incorporate
+ * with pi == NULL; a pi the caller hands in is taken as it is.  Takes effect at the next step / select; refused
+ * (AGZ_BAD_ARGUMENT) for a mode outside -1..8, with external_network = 1, and between agz_tree_search_select and
+ * agz_tree_search_incorporate.  The evaluation counter e counts every leaf the game sends to the network, with the
+ * mode on or off (a mode switched on mid-game continues the game's ordinal), and restarts with every game
+ * (agz_selfplay_start's games, agz_tree_init). */
+#define AGZ_SYMMETRY_NONE (-1)
+#define AGZ_SYMMETRY_RANDOM 8
+agz_status agz_selfplay_set_symmetry(agz_engine* e, int32_t mode);
 typedef struct {
   int64_t steps;               /* tree_search! rounds executed                          */
   int64_t positions;           /* self-play moves played (= searches_pi entries)        */
@@ -313,6 +337,11 @@ agz_status agz_replay_clear(agz_engine* e);
  * the three outputs are host pointers, or device pointers when out_is_device != 0 */
 agz_status agz_replay_batch(agz_engine* e, const int64_t* game, const int32_t* ply, int32_t B, float* feats,
                             float* pi, float* z, int32_t out_is_device);
+/* the same with sample b under the board symmetry T_sym[b], sym[b] in 0..7 (agz_net_forward_features_sym): feats
+ * X'[plane][T_s(p)] = X[plane][p], pi'[T_s(p)] = pi[p] with pass unchanged, z unchanged.  Symmetry augmentation of
+ * training samples; device outputs feed agz_train_step directly. */
+agz_status agz_replay_batch_sym(agz_engine* e, const int64_t* game, const int32_t* ply, const int32_t* sym, int32_t B,
+                                float* feats, float* pi, float* z, int32_t out_is_device);
 
 /* ---------------------------------------------------------------- training step --------- */
 /* One optimisation step of `_train` (neural_net.jl:75-101; optimiser Momentum(2f-2), train.jl:54; call

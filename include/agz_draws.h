@@ -46,6 +46,10 @@
 #define AGZ_SITE_RESIGN 5u     /* move = 0, idx = 0                               */
 #define AGZ_SITE_WEIGHTS 6u    /* synthetic weight init: game = layer, idx = elem */
 #define AGZ_SITE_STAGGER 7u    /* bench-only random opening prefix                */
+#define AGZ_SITE_SYMMETRY 8u   /* dihedral transform of a network evaluation: move = 0,
+                                * idx = 0-based ordinal of the evaluation among those the
+                                * game has sent to the network (terminal leaves do not
+                                * count); s = agz_index(draw, 8)                    */
 
 static inline AGZ_HD uint64_t agz_mix64(uint64_t z) {
   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
