@@ -67,6 +67,12 @@ class NodeInfo(C.Structure):
                 ("done", C.c_int32), ("pos", PositionInfo)]
 
 
+class Analysis(C.Structure):
+    """agz_analysis: one position's result of the batched analysis mode (agz_analyze_results)"""
+    _fields_ = [("move", C.c_int32), ("status", C.c_int32), ("N", C.c_float), ("W", C.c_float), ("Q", C.c_float),
+                ("nodes_used", C.c_int32)]
+
+
 _lib = None
 
 
@@ -136,6 +142,9 @@ def load():
         "agz_selfplay_start": (i32, [E, i64]),
         "agz_selfplay_step": (i32, [E, i32]),
         "agz_selfplay_set_symmetry": (i32, [E, i32]),
+        "agz_analyze_start": (i32, [E, i8p, P(PositionInfo), i8p, i64, u64]),
+        "agz_analyze_progress": (i32, [E, P(i64)]),
+        "agz_analyze_results": (i32, [E, P(Analysis), f32p, f32p, f32p]),
         "agz_engine_stats": (i32, [E, P(Stats)]),
         "agz_selfplay_select": (i32, [E, i32p]),
         "agz_selfplay_leaf_features": (i32, [E, f32p]),

@@ -370,6 +370,27 @@ class NodeView:
         return pos
 
 
+def position_arrays(pos):
+    """A Position in the C ABI's terms (agz_tree_init, agz_analyze_start): board [P] int8 in point order, a PositionInfo
+    (n, to_play, ko, caps, last two moves, history_len, komi) and history [history_len][P] int8.  initialize_game!
+    keeps pos.board_deltas (board.jl:505-506): the up-to-7 older boards the history planes need are
+    B_{k+1} = B_k - delta_k (features.jl:8-14), newest first."""
+    env = pos.env
+    board = pos._flat()[0]
+    hist, b = [], board.astype(np.int16)
+    for k in range(min(7, pos.board_deltas.shape[0])):
+        b = b - np.ascontiguousarray(pos.board_deltas[k].T).reshape(-1)
+        hist.append(b.astype(np.int8))
+    info = _lib.PositionInfo()
+    info.n, info.to_play, info.ko = pos.n, pos.to_play, pos._ko0()
+    info.caps_black, info.caps_white = pos.caps
+    info.last_move = -1 if not pos.recent else to_flat(pos.recent[-1].move, env)
+    info.prev_move = -1 if len(pos.recent) < 2 else to_flat(pos.recent[-2].move, env)
+    info.history_len = len(hist)
+    info.komi = pos.komi
+    return board, info, np.stack(hist) if hist else np.zeros((0, env.N * env.N), np.int8)
+
+
 class MCTSPlayer:
     """MCTSPlayer(env, network; num_readouts, two_player_mode, resign_threshold), mcts_play.jl:3-24.
     `network` is any callable positions -> (pi A x B, v B) (the duck-typed field of mcts_play.jl:5): a NeuralNet of this
@@ -403,15 +424,9 @@ class MCTSPlayer:
 
     def initialize_game(self, pos=None):      # mcts_play.jl:110-118
         pos = Position(self.env) if pos is None else pos
-        last = -1 if not pos.recent else to_flat(pos.recent[-1].move, self.env)
-        # initialize_game!(player, pos) keeps pos.board_deltas (board.jl:505-506): the up-to-7 older boards the
-        # history planes need are B_{k+1} = B_k - delta_k (features.jl:8-14), newest first
-        hist, b = [], pos._flat()[0].astype(np.int16)
-        for k in range(min(7, pos.board_deltas.shape[0])):
-            b = b - np.ascontiguousarray(pos.board_deltas[k].T).reshape(-1)
-            hist.append(b.astype(np.int8))
-        self.engine.tree_init(0, pos._flat()[0], n=pos.n, to_play=pos.to_play, ko=pos._ko0(), caps=pos.caps,
-                              last_move=last, komi=pos.komi, history=np.stack(hist) if hist else None)
+        board, info, hist = position_arrays(pos)
+        self.engine.tree_init(0, board, n=pos.n, to_play=pos.to_play, ko=info.ko, caps=pos.caps,
+                              last_move=info.last_move, komi=pos.komi, history=hist if len(hist) else None)
         self.engine.set_draw(0, self._game_id, 0)
         self.qs, self.searches_pi = [], []
         self.result, self.result_string = 0, ""
@@ -617,6 +632,70 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     out = [SelfPlayPlayer(env, nn, num_ro, r) for r in eng.records()]
     eng.close()
     return out[0] if single else out
+
+
+# One position's result of analyze(): the move suggest_move would pick (board coordinates, None = pass; also None when
+# status is not OK and no move was picked), the root's N, W, Q and its child rows, status (_lib.OK, BAD_ARGUMENT,
+# POOL_EXHAUSTED, ASSERT_SOFTPICK; include/agz.h agz_analysis), the tree's size and the draw-stream game id
+Analysis = namedtuple("Analysis", "move N W Q child_N child_W child_Q prior status nodes_used game_id")
+
+
+def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=None, two_player_mode=False,
+            symmetry=None, precision="f32", **cfg):
+    """suggest_move over many positions in one device run (ours).  Record i is what
+    `MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + i, symmetry=symmetry)`,
+    `initialize_game(positions[i])`, `suggest_move()` computes (mcts_play.jl:110-118,144-151), bit for bit, except that
+    an invalid board gives status BAD_ARGUMENT instead of a search, and that a position whose last two moves were passes
+    is a finished root, as in the reference (MCTSNode keeps pos.done).  `slots` trees search at once (default
+    min(len(positions), 1024)); a slot that finishes a position takes the next.  `cfg`: further agz_config fields
+    (parallel_readouts = tree_search!'s 8 by default, max_nodes_per_game, pool_policy, ...)."""
+    positions = list(positions)
+    for k, p in enumerate(positions):
+        if not isinstance(p, Position):
+            raise TypeError(f"positions[{k}] is {type(p).__name__}, not a Position")
+        if p.env.N != env.N:
+            raise ValueError(f"positions[{k}] is a {p.env.N}x{p.env.N} position, env is {env.N}x{env.N}")
+    if int(num_readouts) < 1:
+        raise ValueError("num_readouts must be >= 1")
+    if not positions:
+        return []
+    B, P = len(positions), env.N * env.N
+    slots = min(B, 1024) if slots is None else int(slots)
+    if slots < 1:
+        raise ValueError("slots must be >= 1")
+    if not isinstance(nn, NeuralNet):
+        raise TypeError("analyze needs a NeuralNet of this package (the search runs on the device with its weights)")
+    boards = np.zeros((B, P), np.int8)
+    hist = np.zeros((B, 7, P), np.int8)
+    infos = (_lib.PositionInfo * B)()
+    for k, p in enumerate(positions):
+        boards[k], infos[k], h = position_arrays(p)
+        hist[k, :len(h)] = h
+    # one search per tree, no re-rooting: a tree holds at most 1 + R + 2 * parallel_readouts nodes
+    cfg.setdefault("max_nodes_per_game", 2 * int(num_readouts) + 256)
+    eng = Engine(board_size=env.N, tower_height=nn.tower_height, games=slots, num_readouts=int(num_readouts),
+                 seed=seed, two_player_mode=int(two_player_mode), **cfg)
+    try:
+        nn.engine.copy_weights_to(eng)
+        eng.set_precision(precision)
+        if symmetry is not None:
+            eng.set_symmetry(symmetry)
+        eng.analyze_start(boards, infos, hist, game_id_base)
+        while eng.analyze_progress() < B:
+            eng.step(16)
+            if eng.stats()["stalled_games"]:      # pool_policy = AGZ_POOL_STALL: a slot waits on its full pool
+                raise _lib.AgzError(_lib.POOL_EXHAUSTED, "a search is waiting on a full node pool (pool_policy = "
+                                                         "stall): raise max_nodes_per_game or use the default policy")
+        r = eng.analyze_results()
+    finally:
+        eng.close()
+    out = []
+    for k in range(B):
+        cn, cw = r["child_N"][k], r["child_W"][k]
+        out.append(Analysis(None if r["move"][k] < 0 else from_flat(int(r["move"][k]), env), r["N"][k], r["W"][k],
+                            r["Q"][k], cn, cw, cw / (np.float32(1) + cn), r["prior"][k], int(r["status"][k]),
+                            int(r["nodes_used"][k]), int(game_id_base) + k))
+    return out
 
 
 EvalStats = namedtuple("EvalStats", "games_won num_games win_rate resigned moves records")

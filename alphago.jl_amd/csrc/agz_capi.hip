@@ -302,6 +302,21 @@ agz_status agz_selfplay_set_symmetry(agz_engine* e, int32_t mode) {
   return guard(e, [&](agz::Engine& E) { E.set_symmetry(mode); });
 }
 
+// ---- batched analysis
+agz_status agz_analyze_start(agz_engine* e, const int8_t* boards, const agz_position_info* info, const int8_t* history,
+                             int64_t B, uint64_t game_id_base) {
+  return guard(e, [&](agz::Engine& E) { E.analyze_start(boards, info, history, B, game_id_base); });
+}
+agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out) {
+  return guard(e, [&](agz::Engine& E) {
+    const int64_t d = E.analyze_progress();
+    if (done_out) *done_out = d;
+  });
+}
+agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N, float* child_W, float* prior) {
+  return guard(e, [&](agz::Engine& E) { E.analyze_results(out, child_N, child_W, prior); });
+}
+
 agz_status agz_train_step(agz_engine* e, const float* feats, const float* pi, const float* z, int32_t B,
                           int32_t inputs_are_device, float eta, float rho, float* losses_out) {
   return guard(e, [&](agz::Engine& E) { E.train_step(feats, pi, z, B, inputs_are_device != 0, eta, rho, losses_out); });
@@ -393,6 +408,10 @@ int32_t agz_abi_layout(const char* name, int32_t* out, int32_t cap) {
     AGZ_OFF(agz_node_info, N); AGZ_OFF(agz_node_info, W); AGZ_OFF(agz_node_info, Q); AGZ_OFF(agz_node_info, parent);
     AGZ_OFF(agz_node_info, fmove); AGZ_OFF(agz_node_info, is_expanded); AGZ_OFF(agz_node_info, losses_applied);
     AGZ_OFF(agz_node_info, done); AGZ_OFF(agz_node_info, pos);
+  } else if (n == "agz_analysis") {
+    AGZ_SZ(agz_analysis);
+    AGZ_OFF(agz_analysis, move); AGZ_OFF(agz_analysis, status); AGZ_OFF(agz_analysis, N); AGZ_OFF(agz_analysis, W);
+    AGZ_OFF(agz_analysis, Q); AGZ_OFF(agz_analysis, nodes_used);
   } else {
     return -1;
   }

@@ -34,6 +34,11 @@ class Engine {
   void debug_live_record(int g, int k, uint64_t* game_id, int32_t* num_moves, int32_t* move, float* pi, float* q);
   void debug_set_stagger(int moves);
   int select_external();
+  // batched analysis (agz_analyze_*): suggest_move over B caller positions, stepped by step() / the external split
+  void analyze_start(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,
+                     uint64_t game_id_base);
+  int64_t analyze_progress();
+  void analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior);
   void leaf_features_external(float* feats_out);
   void incorporate_external(const float* pi, const float* v);
 
@@ -161,6 +166,12 @@ class Engine {
   int external_batch_ = 0;
   int tree_batch_ = 0;
   int64_t abandoned_ = 0;       // games dropped by slot_abandon since the last selfplay_start
+  // analysis mode: the caller's positions and the result tables of the last agz_analyze_start (View::an_*)
+  DevBuf<int8_t> an_board_, an_hist_;
+  DevBuf<agz_position_info> an_info_;
+  DevBuf<agz_analysis> an_res_;
+  DevBuf<float> an_rows_;       // [3][B][A]: child_N, child_W, prior
+  int64_t an_count_ = 0;
   // replay arena
   DevBuf<uint8_t> rp_buf_, s_pack_;
   size_t rp_used_ = 0;

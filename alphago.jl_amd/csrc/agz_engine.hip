@@ -564,6 +564,7 @@ void Engine::net_select(int which) {
 }
 
 void Engine::start(int64_t total_games) {
+  V_.analysis = 0;              // back to self-play (the analysis tables stay readable through analyze_results)
   V_.total_games = total_games;
   rec_sent_ = 0;
   abandoned_ = 0;
@@ -613,6 +614,81 @@ void Engine::step(int nsteps) {
     }
   }
   AGZ_HIP(hipGetLastError());
+}
+
+// ---- batched analysis
+
+void Engine::analyze_start(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,
+                           uint64_t game_id_base) {
+  AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "analysis: an arena_mode engine plays evaluate() games only");
+  AGZ_REQUIRE(boards && info && B >= 1, AGZ_BAD_ARGUMENT, "analysis: boards and info of B >= 1 positions");
+  const int P = V_.P, A = V_.A;
+  for (int64_t i = 0; i < B; ++i) {   // the scalar fields; the boards are checked on the device, per position
+    const agz_position_info& f = info[i];
+    AGZ_REQUIRE(f.to_play == 1 || f.to_play == -1, AGZ_BAD_ARGUMENT, "analysis: position %lld: to_play %d",
+                (long long)i, f.to_play);
+    AGZ_REQUIRE(f.history_len >= 0 && f.history_len <= 7, AGZ_BAD_ARGUMENT, "analysis: position %lld: history_len %d",
+                (long long)i, f.history_len);
+    AGZ_REQUIRE(history || f.history_len == 0, AGZ_BAD_ARGUMENT,
+                "analysis: position %lld: history_len %d without history boards", (long long)i, f.history_len);
+    AGZ_REQUIRE(f.n >= 0, AGZ_BAD_ARGUMENT, "analysis: position %lld: n %d", (long long)i, f.n);
+    AGZ_REQUIRE(f.ko >= -1 && f.ko < P, AGZ_BAD_ARGUMENT, "analysis: position %lld: ko %d", (long long)i, f.ko);
+    AGZ_REQUIRE(f.last_move >= -1 && f.last_move <= P, AGZ_BAD_ARGUMENT, "analysis: position %lld: last_move %d",
+                (long long)i, f.last_move);
+    AGZ_REQUIRE(f.prev_move >= -1 && f.prev_move <= P, AGZ_BAD_ARGUMENT, "analysis: position %lld: prev_move %d",
+                (long long)i, f.prev_move);
+  }
+  AGZ_HIP(hipStreamSynchronize(stream_));     // nothing in flight may still read the tables that are replaced here
+  an_board_.ensure((size_t)B * P);
+  an_hist_.ensure((size_t)B * 7 * P);
+  an_info_.ensure((size_t)B);
+  an_res_.ensure((size_t)B);
+  an_rows_.ensure((size_t)3 * B * A);
+  AGZ_HIP(hipMemcpyAsync(an_board_.p, boards, (size_t)B * P, hipMemcpyHostToDevice, stream_));
+  if (history) AGZ_HIP(hipMemcpyAsync(an_hist_.p, history, (size_t)B * 7 * P, hipMemcpyHostToDevice, stream_));
+  else AGZ_HIP(hipMemsetAsync(an_hist_.p, 0, (size_t)B * 7 * P, stream_));
+  AGZ_HIP(hipMemcpyAsync(an_info_.p, info, sizeof(agz_position_info) * B, hipMemcpyHostToDevice, stream_));
+  AGZ_HIP(hipMemsetAsync(an_res_.p, 0, sizeof(agz_analysis) * B, stream_));
+  AGZ_HIP(hipMemsetAsync(an_rows_.p, 0, sizeof(float) * 3 * B * A, stream_));
+  AGZ_HIP(hipMemsetAsync(V_.an_ctr, 0, sizeof(unsigned long long) * 2, stream_));
+  // every slot idle, as agz_selfplay_start leaves them; the counters and the records ring keep their self-play content
+  std::vector<GameState> gs(V_.games);
+  std::memset(gs.data(), 0, sizeof(GameState) * gs.size());
+  for (auto& g : gs) g.phase = G_IDLE;
+  AGZ_HIP(hipMemcpyAsync(V_.gs, gs.data(), sizeof(GameState) * gs.size(), hipMemcpyHostToDevice, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  an_count_ = B;
+  V_.analysis = 1;
+  V_.an_count = B;
+  V_.an_id_base = game_id_base;
+  V_.an_board = an_board_.p;
+  V_.an_hist = an_hist_.p;
+  V_.an_info = an_info_.p;
+  V_.an_res = an_res_.p;
+  V_.an_childN = an_rows_.p;
+  V_.an_childW = an_rows_.p + (size_t)B * A;
+  V_.an_prior = an_rows_.p + (size_t)2 * B * A;
+  external_batch_ = external_batch2_ = 0;
+}
+
+int64_t Engine::analyze_progress() {
+  AGZ_REQUIRE(an_count_ > 0, AGZ_BAD_ARGUMENT, "analysis: no agz_analyze_start on this engine");
+  unsigned long long done = 0;
+  AGZ_HIP(hipMemcpyAsync(&done, V_.an_ctr + 1, sizeof(done), hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  net_->check_async_error();
+  return (int64_t)done;
+}
+
+void Engine::analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior) {
+  const int64_t done = analyze_progress(), B = an_count_;
+  AGZ_REQUIRE(done >= B, AGZ_NOT_READY, "analysis: %lld of %lld positions finished", (long long)done, (long long)B);
+  const size_t rows = (size_t)B * V_.A;
+  if (out) AGZ_HIP(hipMemcpyAsync(out, an_res_.p, sizeof(agz_analysis) * B, hipMemcpyDeviceToHost, stream_));
+  if (child_N) AGZ_HIP(hipMemcpyAsync(child_N, an_rows_.p, sizeof(float) * rows, hipMemcpyDeviceToHost, stream_));
+  if (child_W) AGZ_HIP(hipMemcpyAsync(child_W, an_rows_.p + rows, sizeof(float) * rows, hipMemcpyDeviceToHost, stream_));
+  if (prior) AGZ_HIP(hipMemcpyAsync(prior, an_rows_.p + 2 * rows, sizeof(float) * rows, hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
 }
 
 void Engine::profile_search_enable(bool on) {
@@ -775,6 +851,21 @@ void Engine::slot_abandon(int g) {
   AGZ_HIP(hipStreamSynchronize(stream_));
   AGZ_REQUIRE(G.phase == G_SEARCH || G.phase == G_INIT || G.phase == G_INIT_WAIT, AGZ_BAD_ARGUMENT,
               "slot %d is not playing a self-play game (phase %d)", g, G.phase);
+  if (V_.analysis) {
+    // the slot's position is given up: its result says so (move -1, the statistics the search reached), and it counts
+    // as finished; agz_stats.abandoned_games keeps its self-play meaning
+    int64_t i = 0;
+    unsigned long long done = 0;
+    AGZ_HIP(hipMemcpyAsync(&i, V_.an_slot + g, sizeof(i), hipMemcpyDeviceToHost, stream_));
+    AGZ_HIP(hipMemcpyAsync(&done, V_.an_ctr + 1, sizeof(done), hipMemcpyDeviceToHost, stream_));
+    AGZ_HIP(hipStreamSynchronize(stream_));
+    agz_analysis r;
+    r.move = -1; r.status = AGZ_POOL_EXHAUSTED; r.N = G.rootN; r.W = G.rootW; r.Q = G.rootW / (1.0f + G.rootN);
+    r.nodes_used = G.nodes_used;
+    ++done;
+    AGZ_HIP(hipMemcpyAsync(V_.an_res + i, &r, sizeof(r), hipMemcpyHostToDevice, stream_));
+    AGZ_HIP(hipMemcpyAsync(V_.an_ctr + 1, &done, sizeof(done), hipMemcpyHostToDevice, stream_));
+  }
   G.phase = G_IDLE;
   G.nleaves = 0;
   G.npend = 0;
@@ -782,7 +873,7 @@ void Engine::slot_abandon(int g) {
   G.stalled = 0;
   AGZ_HIP(hipMemcpyAsync(V_.gs + g, &G, sizeof(G), hipMemcpyHostToDevice, stream_));
   AGZ_HIP(hipStreamSynchronize(stream_));
-  ++abandoned_;
+  if (!V_.analysis) ++abandoned_;
 }
 
 // ---- records

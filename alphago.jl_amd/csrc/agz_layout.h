@@ -103,6 +103,8 @@ inline void for_each_buffer(View& V, F&& f) {
   f(V.ar_hdr, (size_t)5 * (V.games / 2 + 1));        // 4 header words + 1 abort word per pair (agz_search.h)
   f(V.leaf_sym, leaves);
   f(V.eval_ord, (size_t)V.games);
+  f(V.an_ctr, (size_t)2);
+  f(V.an_slot, (size_t)V.games);
 }
 
 }  // namespace agz

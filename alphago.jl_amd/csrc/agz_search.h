@@ -933,6 +933,68 @@ AGZ_FN void game_start(W& w, const View& V, Scratch& S, int g, uint64_t game_id)
   }
 }
 
+// A caller's position before it becomes a root (analysis mode): every point in {-1, 0, +1}, no stone group without a
+// liberty (the LDS labelling of the move rules), the ko point, if set, empty.  The board is left in S.sb.
+template <class W>
+AGZ_FN bool root_board_valid(W& w, const View& V, Scratch& S, const int8_t* board, int ko) {
+  int bad = 0;
+  w.for_each(V.P, [&](int p) {
+    const int c = board[p];
+    S.sb[p] = (int8_t)c;
+    if (c < -1 || c > 1) bad++;
+  });
+  bad = w.reduce_sum(bad);
+  w.sync();
+  if (bad) return false;
+  if (ko >= 0 && ko < V.P && S.sb[ko] != 0) return false;
+  label_components(w, V, S, true);
+  group_liberties(w, V, S);
+  int dead = 0;
+  w.for_each(V.P, [&](int p) { if (S.sb[p] != 0 && S.maxlib[S.label[p]] < 0) dead++; });
+  dead = w.reduce_sum(dead);
+  w.sync();
+  return dead == 0;
+}
+
+// initialize_game!(player, pos) (mcts_play.jl:110-118) on slot g: an empty pool, `board` [P] as the root, the
+// info.history_len boards of `hist` ([.][P], newest first) as the history ring, the slot in `phase`.  The one install of
+// agz_tree_init (TOP_INIT, analysis = false, unchanged) and of the analysis mode (analysis = true): there an invalid
+// board returns false before the slot is touched, and a position whose last two moves were passes is a finished root
+// -- MCTSNode(pos) keeps pos.done (mcts.jl:66-80, board.jl:437), which agz_position_info carries as those two moves.
+// The draw key (G.game_id, G.sel) and the readout target are the caller's.
+template <class W>
+AGZ_FN bool root_install(W& w, const View& V, Scratch& S, int g, const int8_t* board, const int8_t* hist,
+                         const agz_position_info& info, int phase, bool analysis) {
+  GameState& G = V.gs[g];
+  if (analysis && !root_board_valid(w, V, S, board, info.ko)) return false;
+  w.for_each(V.cap, [&](int i) { V.freelist[(long)g * V.cap + i] = V.cap - 1 - i; });
+  w.sync();
+  if (w.leader()) {
+    G.rootN = 0.f; G.rootW = 0.f; G.target = 0.f; G.komi = info.komi;
+    G.sel = 0; G.move_count = 0; G.nqs = 0; G.hist_len = info.history_len;
+    G.free_top = V.cap; G.garbage = 0; G.nleaves = 0; G.err = 0; G.result = 0; G.was_resign = 0; G.nodes_used = 0;
+    G.short_searches = 0;
+    G.phase = phase;
+    V.eval_ord[g] = 0;
+    G.resign_threshold = V.resign_threshold; G.resign_disabled = 0;
+  }
+  w.sync();
+  for (int h = 0; hist && h < info.history_len && h < 7; ++h)
+    w.for_each(V.P, [&](int p) { V.hist[((long)g * 7 + h) * V.PP + p] = hist[(long)h * V.P + p]; });
+  const int id = pool_alloc(w, V, S, g);
+  w.for_each(V.P, [&](int p) { S.sb[p] = board[p]; });
+  w.sync();
+  NodeMeta m;
+  m.parent = -1; m.n = info.n; m.ko = info.ko; m.caps_b = info.caps_black; m.caps_w = info.caps_white;
+  m.fmove = -1; m.last_move = (int16_t)info.last_move; m.losses = 0; m.to_play = (int8_t)info.to_play;
+  m.flags = analysis && info.last_move == V.P && info.prev_move == V.P ? NF_DONE : 0;
+  m.pad = 0;
+  node_init_from_scratch(w, V, S, g, id, m);
+  if (w.leader()) G.root = id;
+  w.sync();
+  return true;
+}
+
 // set_result! + extract_data (mcts_play.jl:100-108,126-139): copy the finished game into the
 // record arena and release the slot.
 template <class W>
@@ -1260,6 +1322,85 @@ AGZ_FN void arena_move_phase(W& w, const View& V, Scratch& S, int g) {
   w.sync();
 }
 
+// ---------------------------------------------------------------- batched analysis ----
+// suggest_move (mcts_play.jl:144-151) for caller positions i = 0..an_count-1, any number per slot (DESIGN.md "Batched
+// analysis").  G_IDLE: claim the next index, install position i as the root with draw key (seed, an_id_base + i) and
+// target R -- initialize_game! -- or retire the slot.  G_SEARCH: game_select_phase, i.e. tree_search!.  Budget spent, or
+// a full pool under AGZ_POOL_MOVE_EARLY: pick_move, the row of position i in the result tables, back to G_IDLE.  No
+// noise, no pre-expansion, no record, no re-rooting: the next install resets the pool.
+
+// position i's row of the result tables: the header, and the root's three A-wide rows in consecutive stores
+template <class W>
+AGZ_FN void analysis_finish(W& w, const View& V, Scratch& S, int g) {
+  GameState& G = V.gs[g];
+  const long long i = V.an_slot[g];
+  const long ri = node_index(V, g, G.root);
+  int status = G.rootN < G.target ? AGZ_POOL_EXHAUSTED : AGZ_OK;     // only the full-pool rule ends a search early
+  int a = -1;
+  if (pick_move(w, V, S, g, &a) != AGZ_OK) { status = AGZ_ASSERT_SOFTPICK; a = -1; }
+  const int A = V.A;
+  w.for_each(A, [&](int k) {
+    V.an_childN[i * A + k] = V.childN[ri * V.AP + k];
+    V.an_childW[i * A + k] = V.childW[ri * V.AP + k];
+    V.an_prior[i * A + k] = V.childP[ri * V.AP + k];
+  });
+  if (w.leader()) {
+    agz_analysis r;
+    r.move = a; r.status = status; r.N = G.rootN; r.W = G.rootW; r.Q = G.rootW / (1.0f + G.rootN);
+    r.nodes_used = G.nodes_used;
+    V.an_res[i] = r;
+    G.phase = G_IDLE; G.nleaves = 0; G.err = 0; G.stalled = 0;
+  }
+  w.sync();
+  w.count(&V.an_ctr[1], 1);
+}
+
+template <class W>
+AGZ_FN void analysis_pre(W& w, const View& V, Scratch& S, int g) {
+  GameState& G = V.gs[g];
+  if (G.phase == G_RETIRED) {
+    if (w.leader()) G.nleaves = 0;
+    w.sync();
+    return;
+  }
+  if (G.phase == G_SEARCH) {
+    const bool full = G.err == AGZ_POOL_EXHAUSTED;
+    const bool finish = !(G.rootN < G.target) || pool_full_can_move(w, V, g);
+    if (w.leader()) G.stalled = full && !finish;        // AGZ_POOL_STALL: the slot waits for agz_slot_abandon
+    w.sync();
+    if (finish) analysis_finish(w, V, S, g);
+  }
+  while (G.phase == G_IDLE) {
+    if (w.leader()) G.nleaves = 0;
+    w.sync();
+    const long long i = (long long)w.fetch_add(&V.an_ctr[0], 1ull);
+    if (i >= V.an_count) {
+      if (w.leader()) G.phase = G_RETIRED;
+      w.sync();
+      return;
+    }
+    const agz_position_info info = V.an_info[i];
+    if (!root_install(w, V, S, g, V.an_board + i * V.P, V.an_hist + i * 7 * V.P, info, G_SEARCH, true)) {
+      if (w.leader()) {
+        agz_analysis r;
+        r.move = -1; r.status = AGZ_BAD_ARGUMENT; r.N = 0.f; r.W = 0.f; r.Q = 0.f; r.nodes_used = 0;
+        V.an_res[i] = r;
+      }
+      w.sync();
+      w.count(&V.an_ctr[1], 1);
+      continue;                                         // nothing searched: claim the next position in this k_pre
+    }
+    if (w.leader()) {
+      V.an_slot[g] = i;
+      G.game_id = V.an_id_base + (uint64_t)i;
+      G.target = G.rootN + (float)V.R;                  // suggest_move: N(root) >= N0 + num_readouts
+      G.short_first = 0; G.stalled = 0;
+    }
+    w.sync();
+  }
+  if (G.phase == G_SEARCH) game_select_phase(w, V, S, g, V.par, V.defer_expand != 0);
+}
+
 // Phase A+B of a self-play step for game slot g: lifecycle, per-move phase, select.
 template <class W>
 AGZ_FN void game_pre(W& w, const View& V, Scratch& S, int g) {
@@ -1271,6 +1412,7 @@ AGZ_FN void game_pre(W& w, const View& V, Scratch& S, int g) {
   if (G.garbage > 0 && G.phase != G_MANUAL) free_pending(w, V, S, g, kFreeBudget);
   AGZ_STAMP(w, V, CT_T_FREE);
   if (V.arena && G.phase != G_MANUAL) { arena_pre(w, V, S, g); return; }
+  if (V.analysis && G.phase != G_MANUAL) { analysis_pre(w, V, S, g); return; }
   if (G.phase == G_MANUAL || G.phase == G_RETIRED) {
     if (w.leader() && G.phase == G_RETIRED) G.nleaves = 0;
     w.sync();
@@ -1505,31 +1647,8 @@ AGZ_FN void tree_op(W& w, const View& V, Scratch& S, const TreeArgs& T) {
   switch (T.op) {
     case TOP_INIT: {
       // initialize_game!(player, pos), mcts_play.jl:110-118
-      w.for_each(V.cap, [&](int i) { V.freelist[(long)g * V.cap + i] = V.cap - 1 - i; });
-      w.sync();
-      if (w.leader()) {
-        G.rootN = 0.f; G.rootW = 0.f; G.target = 0.f; G.komi = T.info.komi;
-        G.sel = 0; G.move_count = 0; G.nqs = 0; G.hist_len = T.info.history_len;
-        G.free_top = V.cap; G.garbage = 0; G.nleaves = 0; G.err = 0; G.result = 0; G.was_resign = 0; G.nodes_used = 0;
-        G.short_searches = 0;
-        G.phase = G_MANUAL;
-        V.eval_ord[g] = 0;
-        G.resign_threshold = V.resign_threshold; G.resign_disabled = 0;
-      }
-      w.sync();
-      for (int h = 0; h < T.info.history_len && h < 7; ++h)
-        w.for_each(V.P, [&](int p) { V.hist[((long)g * 7 + h) * V.PP + p] = T.history[(long)h * V.P + p]; });
-      const int id = pool_alloc(w, V, S, g);
-      w.for_each(V.P, [&](int p) { S.sb[p] = T.board[p]; });
-      w.sync();
-      NodeMeta m;
-      m.parent = -1; m.n = T.info.n; m.ko = T.info.ko; m.caps_b = T.info.caps_black; m.caps_w = T.info.caps_white;
-      m.fmove = -1; m.last_move = (int16_t)T.info.last_move; m.losses = 0; m.to_play = (int8_t)T.info.to_play;
-      m.flags = 0; m.pad = 0;
-      node_init_from_scratch(w, V, S, g, id, m);
-      if (w.leader()) G.root = id;
-      w.sync();
-      r0 = id;
+      root_install(w, V, S, g, T.board, T.history, T.info, G_MANUAL, false);
+      r0 = G.root;
     } break;
     case TOP_SELECT: {
       int plen = 0;

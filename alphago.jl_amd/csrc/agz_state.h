@@ -136,6 +136,20 @@ struct View {
   int32_t symmetry;
   int8_t* leaf_sym;       // [games][par]: s of each recorded leaf (written only while symmetry != 0)
   int32_t* eval_ord;      // [games]: network evaluations the slot's game has requested (the draw index)
+  // analysis mode (agz_analyze_start; zero = off, the View{} of the host simulator): every slot searches caller positions
+  // i = 0..an_count-1 as MCTSPlayer.suggest_move does, draw-stream game id an_id_base + i (DESIGN.md "Batched analysis")
+  int32_t analysis;
+  int64_t an_count;
+  uint64_t an_id_base;
+  unsigned long long* an_ctr;         // [2]: {next position index to claim, positions finished}
+  int64_t* an_slot;                   // [games]: the position the slot is searching
+  const int8_t* an_board;             // [an_count][P]
+  const int8_t* an_hist;              // [an_count][7][P]: older boards newest first (history_len of them are real)
+  const agz_position_info* an_info;   // [an_count]
+  agz_analysis* an_res;               // [an_count]
+  float* an_childN;                   // [an_count][A]: the root's rows when the search ended
+  float* an_childW;
+  float* an_prior;
 };
 
 }  // namespace agz

@@ -23,7 +23,7 @@ using Random
 export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
-       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!,
+       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze,
        # the node-level surface test/test_mcts.jl:2-5 and test/test_mcts_player.jl:3-6 import
        MCTSNode, select_leaf, maybe_add_child!, add_virtual_loss!, revert_virtual_loss!,
        incorporate_results!, inject_noise!, child_action_score, child_Q, child_U, child_N, child_W,
@@ -66,6 +66,10 @@ end
 struct AgzGameHeader
   game_id::UInt64; num_moves::Int32; result::Int32; was_resign::Int32; resign_disabled::Int32
   final_score::Float32; short_searches::Int32
+end
+
+struct AgzAnalysis         # agz_analysis, include/agz.h: one position's result of analyze
+  move::Int32; status::Int32; N::Float32; W::Float32; Q::Float32; nodes_used::Int32
 end
 
 struct AgzStats            # agz_stats, include/agz.h: eighteen Int64 counters
@@ -331,11 +335,11 @@ function MCTSPlayer(env::GoEnv, network; num_readouts = 800, two_player_mode = f
              resign_threshold, e, nothing, PlayerMove[])
 end
 
-function initialize_game!(p::MCTSPlayer, pos = nothing)                        # mcts_play.jl:110-118
-  pos === nothing && (pos = Position(p.env))
-  last = isempty(pos.recent) ? -1 : to_flat(pos.recent[end].move, p.env) - 1
-  # the reference keeps pos.board_deltas (board.jl:505-506); the engine wants the older boards themselves,
-  # newest first: B_{k+1} = B_k - delta_k (features.jl:8-14)
+# A Position in the C ABI's terms (agz_tree_init, agz_analyze_start): board, AgzPositionInfo and the older boards.
+# The reference keeps pos.board_deltas (board.jl:505-506); the engine wants the older boards themselves, newest first:
+# B_{k+1} = B_k - delta_k (features.jl:8-14)
+function position_arrays(env::GoEnv, pos::Position)
+  last = isempty(pos.recent) ? -1 : to_flat(pos.recent[end].move, env) - 1
   k = min(7, size(pos.board_deltas, 3))
   hist = Matrix{Int8}(undef, length(pos.board), k)
   b = copy(pos.board)
@@ -343,8 +347,15 @@ function initialize_game!(p::MCTSPlayer, pos = nothing)                        #
     b = b .- pos.board_deltas[:, :, i]
     hist[:, i] = vec(b)
   end
-  prev = length(pos.recent) < 2 ? -1 : to_flat(pos.recent[end-1].move, p.env) - 1
+  prev = length(pos.recent) < 2 ? -1 : to_flat(pos.recent[end-1].move, env) - 1
   info = AgzPositionInfo(pos.n, pos.to_play, ko0(pos), pos.caps[1], pos.caps[2], last, prev, k, pos.komi)
+  pos.board, info, hist
+end
+
+function initialize_game!(p::MCTSPlayer, pos = nothing)                        # mcts_play.jl:110-118
+  pos === nothing && (pos = Position(p.env))
+  _, info, hist = position_arrays(p.env, pos)
+  k = Int(info.history_len)
   check(p.engine, ccall((:agz_tree_init, libagz), Int32,
         (Ptr{Cvoid}, Int32, Ptr{Int8}, Ref{AgzPositionInfo}, Ptr{Int8}),
         p.engine.handle, 0, pos.board, info, k == 0 ? C_NULL : hist))      # ccall roots `hist` for the call
@@ -739,6 +750,45 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
   end
   sort!(players, by = r -> r.game_id)
   games === nothing ? players[1] : players
+end
+
+# analyze(env, nn, positions; num_readouts) (ours): suggest_move over many positions in one device run.  Result i is what
+# MCTSPlayer(env, nn; num_readouts, two_player_mode) with draw-stream seed `seed` and game id game_id_base + i - 1,
+# initialize_game!(player, positions[i]) and suggest_move(player) compute, bit for bit (include/agz.h agz_analyze_start).
+# Each result is a NamedTuple: move (board coordinates, nothing for a pass or when no move was picked), N, W, Q of the
+# root, child_N / child_W / child_Q / child_prior (length A), status (AGZ_OK, AGZ_BAD_ARGUMENT for an invalid board,
+# AGZ_POOL_EXHAUSTED, AGZ_ASSERT_SOFTPICK) and nodes_used.
+function analyze(env::GoEnv, nn::NeuralNet, positions::Vector{Position}; num_readouts::Int = 800, seed = 0,
+                 game_id_base = 0, slots::Union{Nothing, Int} = nothing, two_player_mode = false, symmetry = nothing)
+  B, P, A = length(positions), env.N * env.N, env.action_space
+  B == 0 && return NamedTuple[]
+  boards = zeros(Int8, P, B); hist = zeros(Int8, P, 7, B); info = Vector{AgzPositionInfo}(undef, B)
+  for (i, pos) in enumerate(positions)
+    b, info[i], h = position_arrays(env, pos)
+    boards[:, i] = vec(b); hist[:, 1:size(h, 2), i] = h
+  end
+  # one search per tree, no re-rooting: a tree holds at most 1 + R + 2 parallel_readouts nodes
+  e = Engine(board_size = env.N, tower_height = nn.tower_height, games = slots === nothing ? min(B, 1024) : slots,
+             num_readouts = num_readouts, seed = seed, two_player_mode = two_player_mode,
+             max_nodes_per_game = 2 * num_readouts + 256)
+  copy_weights!(e, nn.engine)
+  symmetry === nothing || set_symmetry!(e, symmetry)
+  check(e, ccall((:agz_analyze_start, libagz), Int32, (Ptr{Cvoid}, Ptr{Int8}, Ptr{AgzPositionInfo}, Ptr{Int8}, Int64, UInt64),
+                 e.handle, boards, info, hist, B, game_id_base))
+  done = Ref{Int64}(0)
+  while true
+    check(e, ccall((:agz_analyze_progress, libagz), Int32, (Ptr{Cvoid}, Ref{Int64}), e.handle, done))
+    done[] >= B && break
+    check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 16))
+    check_pool(e)     # a search waiting on a full pool (AGZ_POOL_STALL) cannot finish
+  end
+  res = Vector{AgzAnalysis}(undef, B)
+  cn, cw, pr = zeros(Float32, A, B), zeros(Float32, A, B), zeros(Float32, A, B)
+  check(e, ccall((:agz_analyze_results, libagz), Int32, (Ptr{Cvoid}, Ptr{AgzAnalysis}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+                 e.handle, res, cn, cw, pr))
+  [(move = r.move < 0 ? nothing : from_flat(r.move + 1, env), N = r.N, W = r.W, Q = r.Q, child_N = cn[:, i],
+    child_W = cw[:, i], child_Q = cw[:, i] ./ (1f0 .+ cn[:, i]), child_prior = pr[:, i], status = Int(r.status),
+    nodes_used = Int(r.nodes_used)) for (i, r) in enumerate(res)]
 end
 
 # get_replay_batch(pos_buffer, π_buffer, res_buffer; batch_size), src/train.jl:4-12: batch_size distinct entries,

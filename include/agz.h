@@ -393,7 +393,7 @@ agz_status agz_broadcast_weights(agz_engine* e, agz_comm* comm, int32_t root, in
 /* ---------------------------------------------------------------- ABI self-description --- */
 /* sizeof and field offsets of the PODs above as this library was compiled, so that a host mirror (ctypes
  * Structure, Julia struct) can be checked against them: name in {"agz_config", "agz_stats",
- * "agz_game_header", "agz_position_info", "agz_node_info"}; out[0] = sizeof, out[1..n] = offsetof of the n
+ * "agz_game_header", "agz_position_info", "agz_node_info", "agz_analysis"}; out[0] = sizeof, out[1..n] = offsetof of the n
  * fields in declaration order; returns n, or -1 for an unknown name / too small a buffer. */
 int32_t agz_abi_layout(const char* name, int32_t* out, int32_t cap);
 
@@ -464,6 +464,44 @@ agz_status agz_tree_node_children(agz_engine* e, int32_t g, int32_t node, int32_
 agz_status agz_tree_node_board(agz_engine* e, int32_t g, int32_t node, int8_t* out /* [N*N] */);
 agz_status agz_tree_pending_vlosses(agz_engine* e, int32_t g, int32_t* out);
 agz_status agz_tree_set_draw(agz_engine* e, int32_t g, uint64_t game_id, uint32_t sel);
+
+/* ---------------------------------------------------------------- batched analysis ------ */
+/* suggest_move over many caller positions in one device run (ours; the reference analyses one position per MCTSPlayer,
+ * mcts_play.jl:110-118,144-151).  Position i (0-based) gives exactly what
+ *   MCTSPlayer(env, nn; num_readouts, two_player_mode) with draw-stream seed agz_config.seed and game id
+ *   game_id_base + i;  initialize_game!(player, pos_i);  suggest_move(player)
+ * gives: tree_search!(player, parallel_readouts) until N(root) >= num_readouts, then pick_move.  No Dirichlet noise, no
+ * pre-expansion, soft pick below tau_threshold unless two_player_mode.  The result does not depend on the number of
+ * slots or on which slot searches position i.  A slot that finishes a position claims the next one at once, so B may
+ * be far larger than agz_config.games.  Board symmetries (agz_selfplay_set_symmetry) apply as in the tree path.
+ *
+ * agz_analyze_start: boards int8[B][N*N], info[B] and history int8[B][7][N*N] (or NULL: no older boards) in the
+ * conventions of agz_tree_init (info[i].history_len of the 7 boards are real).  It copies the positions to the device,
+ * resets every slot (the way agz_selfplay_start does) and leaves the records ring and the counters agz_selfplay_start
+ * resets as they are.  Scalar fields are checked here: to_play = +-1, history_len in 0..7, n >= 0, ko in -1..N*N-1,
+ * last_move / prev_move in -1..N*N; a bad one fails the whole call naming the position.  The board is checked on the
+ * device when the position is installed: every point in {-1, 0, +1}, no group without a liberty, the ko point empty;
+ * a bad board gives that position AGZ_BAD_ARGUMENT (move -1, nothing searched).  Refused in arena_mode.
+ * agz_selfplay_step (internal network) or agz_selfplay_select / _leaf_features / _incorporate (external network) then
+ * step the run; agz_analyze_progress (synchronises) says how many positions are finished; agz_analyze_results copies
+ * them out (AGZ_NOT_READY until all B are).  A later agz_selfplay_start returns the engine to self-play.
+ *
+ * status per position: AGZ_OK; AGZ_BAD_ARGUMENT (invalid board); AGZ_POOL_EXHAUSTED (the node pool filled up: under
+ * AGZ_POOL_MOVE_EARLY the search ended early, the move and statistics are valid and N < num_readouts; under
+ * AGZ_POOL_STALL the slot waits until agz_slot_abandon gives the position up, move -1); AGZ_ASSERT_SOFTPICK (pick_move's
+ * assertion, mcts_play.jl:67; move -1).  N, W of the root (the DummyNode, mcts.jl:27-39), Q = W / (1 + N)
+ * (mcts.jl:96-102), nodes_used = tree size when the search ended. */
+typedef struct {
+  int32_t move;                /* action picked, -1 when none */
+  int32_t status;
+  float N, W, Q;
+  int32_t nodes_used;
+} agz_analysis;
+agz_status agz_analyze_start(agz_engine* e, const int8_t* boards, const agz_position_info* info, const int8_t* history,
+                             int64_t B, uint64_t game_id_base);
+agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out);
+/* out[B], child_N / child_W / prior [B][A] (the root's rows when the search ended); any of them may be NULL */
+agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N, float* child_W, float* prior);
 
 /* Test hooks (device-side evaluation of the draw stream, single-tree introspection setters) are declared in
  * include/agz_debug.h: exported by the library for the parity tests, not part of the drop-in surface. */

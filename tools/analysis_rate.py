@@ -1,0 +1,148 @@
+#!/usr/bin/env python3
+"""Throughput of the batched analysis mode (DESIGN.md "Batched analysis") at the BASELINE.json configs[1] shape (9x9,
+tower 10, R = 400, 1024 slots), on mid-game positions taken from self-play records:
+  1. positions/s of alphago_jl_amd.analyze over --positions positions (wall time of the call, engine set-up included);
+  2. positions/s of MCTSPlayer.initialize_game + suggest_move (the single-tree path) on a --sample of them;
+  3. ms per step of an analysis run next to ms per self-play step, engines of the same shape, alternating windows.
+The records come from a short self-play run at --gen-readouts readouts (only the positions matter, not their quality).
+Prints one JSON object."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def positions_from_records(ag, env, recs, count, lo, hi, rng):
+    """Position objects (board, board_deltas, recent, ko, caps) at a random ply in [lo, hi) of the games, rebuilt by
+    batched agz_go_play replay of their move lists"""
+    N, P = env.N, env.N * env.N
+    games = [r for r in recs if int(r["num_moves"]) > lo]
+    picks = [(games[rng.randint(len(games))], 0) for _ in range(count)]
+    picks = [(r, rng.randint(lo, min(hi, int(r["num_moves"])))) for r, _ in picks]
+    eng = ag.Engine(board_size=N, tower_height=0, games=1, num_readouts=1, max_nodes_per_game=8)
+    B = len(picks)
+    boards = np.zeros((B, P), np.int8)
+    ko = np.full(B, -1, np.int32)
+    tp = np.ones(B, np.int8)
+    caps = np.zeros((B, 2), np.int64)
+    deltas = [[] for _ in range(B)]
+    recent = [[] for _ in range(B)]
+    for k in range(max(p for _, p in picks)):
+        live = np.array([b for b in range(B) if k < picks[b][1]])
+        mv = np.array([int(picks[b][0]["moves"][k]) for b in live], np.int32)
+        nb, nko, ncap, st = eng.go_play(boards[live], tp[live], ko[live], mv)
+        assert (st == 0).all()
+        for j, b in enumerate(live):
+            color = int(tp[b])
+            d = np.where(nb[j] != boards[b], color, 0).astype(np.int8).reshape(N, N).T     # [row, col]
+            deltas[b] = [d] + deltas[b][:6]
+            recent[b].append(ag.PlayerMove(color, ag.from_flat(int(mv[j]), env)))
+            caps[b, 0 if color == 1 else 1] += int(ncap[j])
+        boards[live], ko[live], tp[live] = nb, nko, -tp[live]
+    eng.close()
+    out = []
+    for b, (_, ply) in enumerate(picks):
+        out.append(ag.Position(env, board=boards[b].reshape(N, N).T, n=ply, caps=tuple(int(c) for c in caps[b]),
+                               ko=None if ko[b] < 0 else ag.from_flat(int(ko[b]), env), recent=recent[b],
+                               board_deltas=np.stack(deltas[b]) if deltas[b] else None, to_play=int(tp[b])))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--board", type=int, default=9)
+    ap.add_argument("--tower", type=int, default=10)
+    ap.add_argument("--readouts", type=int, default=400)
+    ap.add_argument("--slots", type=int, default=1024)
+    ap.add_argument("--positions", type=int, default=4096)
+    ap.add_argument("--sample", type=int, default=32, help="positions searched by MCTSPlayer.suggest_move")
+    ap.add_argument("--gen-readouts", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=10, help="steps per timing window")
+    ap.add_argument("--pairs", type=int, default=4)
+    args = ap.parse_args()
+
+    import alphago_jl_amd as ag
+
+    N, R, S = args.board, args.readouts, args.slots
+    env = ag.GoEnv(N)
+    nn = ag.NeuralNet(env, tower_height=args.tower, seed=0)
+    rng = np.random.RandomState(0)
+
+    # self-play records -> mid-game positions
+    t0 = time.perf_counter()
+    recs = [dict(num_moves=len(p.moves), moves=[ag.to_flat(c, env) for c in p.moves])
+            for p in ag.selfplay(env, nn, args.gen_readouts, games=S, seed=3, game_id_base=0)]
+    gen_s = time.perf_counter() - t0
+    P = N * N
+    positions = positions_from_records(ag, env, recs, args.positions, P // 8, P // 2, rng)
+
+    # 1. analyze
+    ag.analyze(env, nn, positions[:S], num_readouts=R, slots=S)        # warm-up (kernel loading, allocation)
+    t0 = time.perf_counter()
+    res = ag.analyze(env, nn, positions, num_readouts=R, slots=S)
+    an_s = time.perf_counter() - t0
+    statuses = {int(s): sum(1 for a in res if a.status == s) for s in {a.status for a in res}}
+
+    # 2. the single-tree path
+    sample = positions[: args.sample]
+    player = ag.MCTSPlayer(env, nn, num_readouts=R, seed=0)
+    player.initialize_game(sample[0])
+    player.suggest_move()                                              # warm-up
+    t0 = time.perf_counter()
+    for k, pos in enumerate(sample):
+        player._game_id = k                                            # the draw key analyze() gives position k
+        player.initialize_game(pos)
+        player.suggest_move()
+    sm_s = time.perf_counter() - t0
+    player.engine.close()
+
+    # 3. step time: an analysis run and self-play on engines of the same shape, alternating windows
+    shape = dict(board_size=N, tower_height=args.tower, games=S, num_readouts=R, parallel_readouts=8, seed=1)
+    ea = ag.Engine(**shape)
+    nn.engine.copy_weights_to(ea)
+    boards = np.zeros((len(positions), P), np.int8)
+    hist = np.zeros((len(positions), 7, P), np.int8)
+    infos = (ag._lib.PositionInfo * len(positions))()
+    for k, p in enumerate(positions):
+        boards[k], infos[k], h = ag.position_arrays(p)
+        hist[k, :len(h)] = h
+    ea.analyze_start(boards, infos, hist, 0)
+    es = ag.Engine(stagger_moves=60, record_capacity_games=2 * S + 64, **shape)
+    nn.engine.copy_weights_to(es)
+    es.start(0)
+    es.step((R + 7) // 8 + 15)
+    ea.step(10)
+    ea.sync()
+    es.sync()
+    windows = {"analysis": [], "selfplay": []}
+    for k in range(args.pairs):
+        order = (("analysis", ea), ("selfplay", es)) if k % 2 == 0 else (("selfplay", es), ("analysis", ea))
+        for name, e in order:
+            t0 = time.perf_counter()
+            e.step(args.steps)
+            e.sync()
+            windows[name].append(1e3 * (time.perf_counter() - t0) / args.steps)
+    busy = ea.stats()["live_games"]
+    es.records_clear()
+    ea.close()
+    es.close()
+    ma, ms = statistics.median(windows["analysis"]), statistics.median(windows["selfplay"])
+    print(json.dumps(dict(
+        shape=dict(board=N, tower=args.tower, readouts=R, slots=S), positions=len(positions),
+        generation=dict(games=len(recs), readouts=args.gen_readouts, seconds=round(gen_s, 1)),
+        analyze=dict(seconds=round(an_s, 3), positions_per_s=round(len(positions) / an_s, 1), statuses=statuses),
+        suggest_move=dict(positions=len(sample), seconds=round(sm_s, 3), positions_per_s=round(len(sample) / sm_s, 2)),
+        ratio=round((len(positions) / an_s) / (len(sample) / sm_s), 1),
+        step_ms=dict(windows=windows, analysis_median=round(ma, 3), selfplay_median=round(ms, 3),
+                     analysis_over_selfplay=round(ma / ms, 4), analysis_slots_busy_at_end=busy))))
+
+
+if __name__ == "__main__":
+    main()
