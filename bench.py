@@ -9,15 +9,23 @@ positions) -> expand / back up, plus the per-move phase (resign check, pick, pla
 for the games whose 400-readout budget is spent.  A "position" = one self-play move that received
 its full 400 readouts inside the run.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: starts its own N ranks)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full]  (N > 1 without a launcher: starts its own N ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  value = positions played by all ranks / max-over-ranks time of
-exactly K steps bracketed by barrier + device sync.  Extra objects:
-  roofline      the dominant kernel (3x3 256->256 conv, v_mfma_f32_32x32x2_f32): algorithmic
-                TFLOP/s from HIP events around every tower-conv launch of the timed region
-  cpu_baseline  the CPU oracle (a port of the reference algorithm in the reference's execution
-                shape: one game at a time, batches of 8) timed on this host, bounded sample
+exactly K steps bracketed by barrier + device sync.  A plain run does only what that figure needs
+(setup, W warm-up steps, K timed steps, --dump-outputs, the line); the objects it carries are read
+off the timed steps themselves:
+  roofline        the dominant kernel (3x3 256->256 conv, v_mfma_f32_32x32x2_f32): algorithmic
+                  TFLOP/s from HIP events around every tower-conv launch of the timed region
+  search_kernels  the search / feature kernels of the timed steps, from the same kind of events
+  power           socket power and shader clock sampled over the timed steps
+--full adds the legs that take runs of their own (extra_legs; each --no-* option drops one):
+  roofline.traffic from two live rocprofv3 --pmc passes of this command, roofline.sustained_mfma*,
+  alt_precision (the K steps again in f32s), config3 / config4 (one GPU's shard of BASELINE
+  configs[3] / [4]), and
+  cpu_baseline    the CPU oracle (a port of the reference algorithm in the reference's execution
+                  shape: one game at a time, batches of 8) timed on this host, bounded sample
 """
 import argparse
 import json
@@ -87,8 +95,7 @@ def live_pmc_traffic(args, seconds_cap=240.0):
             cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable,
                    os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--board", str(args.board), "--tower", str(args.tower),
                    "--readouts", str(args.readouts), "--games", str(args.games), "--stagger", str(args.stagger),
-                   "--precision", args.precision, "--winograd", str(args.winograd), "--tower-streams", "1", "--no-cpu-baseline",
-                   "--no-alt-precision", "--no-config-legs", "--generation", "0", "--no-sustained", "--no-live-traffic"]
+                   "--precision", args.precision, "--winograd", str(args.winograd), "--tower-streams", "1", "--generation", "0"]
             left = seconds_cap - (time.time() - t0)
             if left < 20:
                 return None, f"counter passes over their {seconds_cap:.0f} s budget"
@@ -495,7 +502,28 @@ def self_launch(n, single_device):
     return rc
 
 
-def main():
+def extra_legs(args, world):
+    """The legs a run adds behind its timed steps on top of the headline figure: none without --full.  With it, every one
+    that applies to this run, less those a --no-* option drops.  (--generation G is a request of its own, and the per-rank
+    rates, rank 0's solo repeat and the replay exchange are what --gpus N > 1 measures: neither is counted here.)"""
+    if not args.full:
+        return set()
+    headline = (args.board, args.tower, args.readouts, args.games, args.precision) == (9, 10, 400, 1024, "f32")
+    legs = set()
+    if world == 1 and headline and args.stagger > 0 and not args.no_live_traffic:
+        legs.add("live_traffic")       # roofline.traffic measured now (live_pmc_traffic)
+    if args.precision == "f32" and not args.no_sustained:
+        legs.add("sustained")          # roofline.sustained_mfma, .sustained_mfma_changing_operands
+    if world == 1 and args.precision == "f32" and not args.no_alt_precision:
+        legs.add("alt_precision")
+    if world == 1 and headline and args.stagger > 0 and not args.no_config_legs:
+        legs.add("config_legs")        # config3, config4
+    if world == 1 and not args.no_cpu_baseline:
+        legs.add("cpu_baseline")
+    return legs
+
+
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
@@ -505,8 +533,12 @@ def main():
     ap.add_argument("--readouts", type=int, default=400)
     ap.add_argument("--games", type=int, default=1024, help="concurrent games per GPU")
     ap.add_argument("--stagger", type=int, default=60, help="random opening prefix (moves) so games are at mixed stages")
+    ap.add_argument("--full", action="store_true",
+                    help="after the line's own figures also run the legs that take runs of their own: live PMC traffic passes, "
+                         "sustained-MFMA rates, the f32s leg, the configs[3] / configs[4] legs, the CPU baseline (see extra_legs; "
+                         "the --no-* options below drop single legs).  Off by default: a plain run does only what `value` needs")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--precision", default="f32", choices=["f32", "f16", "f32s"],
                     help="tower arithmetic: f32 (default, the BASELINE metric), f16 = the fp16 MFMA path of BASELINE configs[4], "
                          "f32s = the f32 network with Winograd operands split into two f16 halves (fp16 MFMA, f32-grade results)")
@@ -517,9 +549,9 @@ def main():
                     help="agz_net_set_tower_streams: the F(4x4,3x3) tower as 2 (default) or 1 layer chains")
     ap.add_argument("--tower-persistent", action="store_true",
                     help="run the f32 Winograd tower as one persistent launch (agz_net_set_tower_persistent; same bits, HISTORY.md 4f)")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the 0.4 s sustained-MFMA-rate measurement behind the timed region")
+    ap.add_argument("--no-sustained", action="store_true", help="--full without the 0.4 s sustained-MFMA-rate measurement behind the timed region")
     ap.add_argument("--no-alt-precision", action="store_true",
-                    help="skip the extra (untimed for `value`) leg that repeats the K steps with --precision f32s")
+                    help="--full without the extra (untimed for `value`) leg that repeats the K steps with --precision f32s")
     ap.add_argument("--generation", type=int, default=0, metavar="G",
                     help="after the timed K steps keep playing, untimed for `value`: a warm-up until G games have ended "
                          "naturally, then a window until G more have; the line gains a `generation` object with SURVEY.md 8d's "
@@ -530,10 +562,11 @@ def main():
                     help="hard cap on the generation leg (half for the warm-up generation, half for the measured one); a leg the "
                          "cap cut short reports what it saw and says so")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="take roofline.traffic from the committed profiles/ file instead of two live rocprofv3 --pmc passes of this "
-                         "command (the default at N = 1 on the headline workload when rocprofv3 is installed)")
+                    help="--full taking roofline.traffic from the committed profiles/ file instead of two live rocprofv3 --pmc passes "
+                         "of this command (what --full does at N = 1 on the headline workload when rocprofv3 is installed; a plain "
+                         "run always takes the file)")
     ap.add_argument("--no-config-legs", action="store_true",
-                    help="skip the two bounded legs that run one GPU's shard of BASELINE configs[3] (19x19, tower 20, 800 "
+                    help="--full without the two bounded legs that run one GPU's shard of BASELINE configs[3] (19x19, tower 20, 800 "
                          "readouts, 256 games, f32) and configs[4] (fp16 tower, 1600 readouts, 512 games) after the headline")
     ap.add_argument("--config-leg-steps", type=int, default=20)
     ap.add_argument("--single-device-test", action="store_true",
@@ -541,7 +574,11 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them left for a caller (every live game's search root, the "
                          "finished records, the counters) as DIR/<name>.npy, at most 64 MB (rank 0; see dump_outputs)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # no launcher: be the launcher
         sys.exit(self_launch(args.gpus, args.single_device_test))
@@ -559,7 +596,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    headline = (args.board, args.tower, args.readouts, args.games, args.precision) == (9, 10, 400, 1024, "f32")
+    legs = extra_legs(args, world)
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} under a launcher that set WORLD_SIZE={world}: start {args.gpus} ranks, or "
                          f"run `python bench.py --gpus {args.gpus}` with WORLD_SIZE unset and it starts them itself")
@@ -656,9 +693,9 @@ def main():
 
     # Extra leg, reported beside `value`, never as it: the same K steps with the Winograd operands carried as two f16
     # halves (AGZ_PRECISION_F32S: f32 network, f32 accumulate, fp16 MFMA; agrees with the float64 oracle as closely
-    # as the exact-f32 path does, tests/test_gpu_nn32s.py).  N = 1 only, exact-f32 runs only.
+    # as the exact-f32 path does, tests/test_gpu_nn32s.py).  --full, N = 1 and exact-f32 runs only.
     alt = None
-    if world == 1 and args.precision == "f32" and not args.no_alt_precision:
+    if "alt_precision" in legs:
         try:
             eng.set_precision("f32s")
             eng.step(args.warmup)
@@ -833,7 +870,7 @@ def main():
         rows_per_launch = conv_flop / max(conv_n, 1) / (2.0 * 9 * 256 * 256)
         traffic_committed = None
         traffic, traffic_src = pmc_traffic(rows_per_launch, N, args.precision, f43)
-        if world == 1 and headline and args.stagger > 0 and not args.no_live_traffic:
+        if "live_traffic" in legs:
             # driver-witnessed: counters collected on THIS box, now; the committed file is the fallback
             try:
                 bpr, src = live_pmc_traffic(args)
@@ -884,7 +921,7 @@ def main():
             "executed_flop_per_launch_avg": conv_flop * wino_ratio / max(conv_n, 1),
             "algorithmic_flop_per_launch_avg": conv_flop / max(conv_n, 1),
         }
-        if not f16 and not f32s and exe_tf is not None and not args.no_sustained:
+        if "sustained" in legs and exe_tf is not None:
             # context, not the contract's `peak`: the constant-operand MFMA-only figure of rounds 3-4 (bounded by its own loop), measured
             # now, after the timed region (0.4 s of back-to-back register-only MFMA launches; HISTORY.md 4f)
             try:
@@ -957,7 +994,7 @@ def main():
             out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
         if alt is not None:
             out["alt_precision"] = alt
-        if world == 1 and headline and args.stagger > 0 and not args.no_config_legs:
+        if "config_legs" in legs:
             # BASELINE configs[3] / configs[4], one GPU's shard each, driver-witnessed: never `value`
             for key, cfg in (("config3", ("configs[3]", 19, 20, 800, 256, "f32")), ("config4", ("configs[4]", 19, 20, 1600, 512, "f16"))):
                 try:
@@ -965,7 +1002,7 @@ def main():
                                          5, 60, local_rank)
                 except Exception as ex:      # never at the expense of the line
                     out[key] = {"config": cfg[0], "error": f"{type(ex).__name__}: {ex}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if "cpu_baseline" in legs:
             try:
                 out["cpu_baseline"] = cpu_baseline(N, tower, R, args.cpu_baseline_seconds)
             except Exception as e:  # the baseline leg must never take the GPU number down with it

@@ -1,5 +1,6 @@
 """bench.py's pure helpers (no GPU): the `search_kernels` object SURVEY.md 8d asks for (search / feature / legal kernels as
-microseconds per step and HBM GB/s) and the counter summary behind it (tools/pmc_traffic.py)."""
+microseconds per step and HBM GB/s), the counter summary behind it (tools/pmc_traffic.py), --dump-outputs and the legs --full
+adds behind the timed steps."""
 import csv
 import importlib.util
 import os
@@ -119,3 +120,20 @@ def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
     assert 0 < len(s["root_game_id"]) < 4096 and (np.diff(s["root_game_id"]) > 0).all()
     assert 0 < len(s["record_game_id"]) < 200 and (np.diff(s["record_game_id"]) > 0).all()
     assert s["record_pis"].shape == (80 * len(s["record_game_id"]), 82)
+
+
+def test_a_plain_run_adds_no_leg_and_full_adds_every_one_that_applies():
+    bench = _load("agz_bench", "bench.py")
+    parse = bench.arg_parser().parse_args
+    every = {"live_traffic", "sustained", "alt_precision", "config_legs", "cpu_baseline"}
+    assert bench.extra_legs(parse(["--steps", "20", "--warmup", "5"]), 1) == set()
+    assert bench.extra_legs(parse(["--steps", "20", "--warmup", "5", "--no-cpu-baseline"]), 1) == set()
+    assert bench.extra_legs(parse(["--full"]), 1) == every
+    assert bench.extra_legs(parse(["--full", "--no-live-traffic", "--no-config-legs"]), 1) == every - {"live_traffic", "config_legs"}
+    assert bench.extra_legs(parse(["--full", "--no-sustained", "--no-alt-precision", "--no-cpu-baseline"]), 1) == {"live_traffic", "config_legs"}
+    # the live counter passes and the configs[3] / [4] legs belong to the headline workload, the f32s leg and the sustained
+    # MFMA rates to exact-f32 runs; at N > 1 only the sustained rates remain
+    assert bench.extra_legs(parse(["--full", "--board", "5", "--tower", "1"]), 1) == {"sustained", "alt_precision", "cpu_baseline"}
+    assert bench.extra_legs(parse(["--full", "--stagger", "0"]), 1) == {"sustained", "alt_precision", "cpu_baseline"}
+    assert bench.extra_legs(parse(["--full", "--precision", "f16"]), 1) == {"cpu_baseline"}
+    assert bench.extra_legs(parse(["--full", "--gpus", "2"]), 2) == {"sustained"}

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""BASELINE.md section 4 from a bench.py line (the driver's command): python tools/fill_baseline_table.py profiles/r06_bench_default.json"""
+"""BASELINE.md section 4 from a `bench.py --full --generation G` line (the legs and the generation rate it reads are off in a plain
+run): python tools/fill_baseline_table.py profiles/r06_bench_default.json"""
 import json
 import os
 import sys
@@ -9,7 +10,7 @@ src = sys.argv[1]
 d = json.loads(open(src).read().strip().splitlines()[-1])
 cb, c3, c4, g = d["cpu_baseline"], d["config3"], d["config4"], d["generation"]
 steady = d.get("steady_state", {}).get("value", d["value"])
-rows = f"""## 4. Results table (filled by the build, round 6; one MI355X, `{os.path.relpath(src, ROOT)}` = `python bench.py --steps {d['steps']} --warmup {d['warmup']}`, the driver's command)
+rows = f"""## 4. Results table (filled by the build, round 6; one MI355X, `{os.path.relpath(src, ROOT)}` = `python bench.py --full --generation {g['requested_games']} --steps {d['steps']} --warmup {d['warmup']}`)
 
 | config | backend | GPUs / cores | positions/s | evals/position | roofline.achieved | notes |
 |---|---|---|---|---|---|---|
