@@ -592,7 +592,7 @@ void Trainer::step(const float* feats, const float* pi, const float* z, int B, b
 
   // ---- forward, training mode
   // small batches: nine tap-split workgroups per tile and a fixed-order sum (42 workgroups of 128 rows do not fill 256 CUs)
-  const bool taps = conv3x3_direct_blocks(B, N) < 192;
+  const bool taps = conv3x3_direct_blocks(B, N) < 192;      // mirrored by train_paths() in tests/train_twin.py
   d_zero_.ensure(kC);
   AGZ_HIP(hipMemsetAsync(d_zero_.p, 0, sizeof(float) * kC, s));
   if (taps) d_part_.ensure((size_t)9 * B * N * N * kC);
@@ -691,8 +691,8 @@ void Trainer::step(const float* feats, const float* pi, const float* z, int B, b
     hipLaunchKernelGGL(k_take_sums, dim3(1), dim3(256), 0, s, (const double*)sums, (int)kC, P4(l, 1).grad.p);
   };
   // rows per weight-gradient block: ~2600 (the reference's batch of 32 at 9x9), more blocks for more rows
-  const int wsplit = (int)std::min<long>(16, std::max<long>(1, (M + 2047) / 2592));
-  const int wchunk = (int)(((M + wsplit - 1) / wsplit + 7) / 8 * 8);
+  const int wsplit = (int)std::min<long>(16, std::max<long>(1, (M + 2047) / 2592));  // mirrored by train_paths(), tests/train_twin.py
+  const int wchunk = (int)(((M + wsplit - 1) / wsplit + 7) / 8 * 8);                 // mirrored by train_paths(), tests/train_twin.py
   if (wsplit > 1) d_wpart_.ensure((size_t)wsplit * kC * 9 * kC);
   auto wgrad = [&](int l, const float* in, const float* du) {
     const int cinp = l == 0 ? kCinStemPad : kC;

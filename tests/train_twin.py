@@ -10,6 +10,18 @@ K_W, K_B, K_BETA, K_GAMMA, K_MEAN, K_VAR, K_EPS = range(7)
 L_VCONV, L_PCONV, L_VFC1, L_VFC2, L_PFC = -1, -2, -3, -4, -5
 
 
+def train_paths(N, B):
+    """The code paths Trainer::step (agz_train.hip) takes for a batch of B positions at N x N, from its three host-side
+    formulas: (taps, wsplit, wchunk).  taps: the 3x3 forward and input gradient run as the nine-way tap split
+    (launch_conv3x3_direct_taps) rather than launch_conv3x3_direct.  wsplit, wchunk: k_wgrad3x3 splits the M = B N^2 rows
+    into wsplit partial gradients of wchunk rows (a multiple of 8), the last one M - (wsplit - 1) wchunk rows."""
+    M = B * N * N
+    taps = -(-M // 128) * 2 < 192                    # conv3x3_direct_blocks(B, N): 128-row x 128-channel tiles
+    wsplit = min(16, max(1, (M + 2047) // 2592))
+    wchunk = ((M + wsplit - 1) // wsplit + 7) // 8 * 8
+    return taps, wsplit, wchunk
+
+
 class Twin:
     def __init__(self, N, tower, get, dtype=DT):
         """get(layer, kind) -> flat float32 numpy array (e.g. Engine.get_weights).  dtype = torch.float32 makes the
@@ -36,6 +48,9 @@ class Twin:
         w = self.th[(l, K_W)].reshape(cout, cin, k, k).permute(0, 1, 3, 2)      # column-major [a,b,ci,o] -> [o,ci,a,b]
         w = torch.flip(w, dims=(2, 3))                                        # NNlib conv is a true convolution
         y = torch.nn.functional.conv2d(x, w, self.th[(l, K_B)], padding=k // 2)
+        if not training and self.eps[l] <= 0:                                 # a checkpoint's eps = 0 (torch refuses it)
+            c = lambda t: t[None, :, None, None]
+            return (y - c(self.run[l][0])) / torch.sqrt(c(self.run[l][1])) * c(self.th[(l, K_GAMMA)]) + c(self.th[(l, K_BETA)])
         return torch.nn.functional.batch_norm(y, self.run[l][0], self.run[l][1], self.th[(l, K_GAMMA)], self.th[(l, K_BETA)],
                                               training=training, momentum=0.1,
                                               eps=max(self.eps[l], 1e-5) if training else self.eps[l])
