@@ -143,6 +143,7 @@ def load():
         "agz_selfplay_step": (i32, [E, i32]),
         "agz_selfplay_set_symmetry": (i32, [E, i32]),
         "agz_analyze_start": (i32, [E, i8p, P(PositionInfo), i8p, i64, u64]),
+        "agz_review_start": (i32, [E, P(C.c_int16), P(i64), i8p, P(PositionInfo), i8p, i64, u64]),
         "agz_analyze_progress": (i32, [E, P(i64)]),
         "agz_analyze_results": (i32, [E, P(Analysis), f32p, f32p, f32p]),
         "agz_engine_stats": (i32, [E, P(Stats)]),

@@ -698,6 +698,114 @@ def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=
     return out
 
 
+def review_arrays(env, games):
+    """Recorded games in agz_review_start's terms: (moves int16 [total], game_offset int64 [G+1]).  A game is a move list
+    (board coordinates, None = pass, or flat actions 0..N*N), a record dict of Engine.records() (its "moves") or a
+    player selfplay() returned (its .moves)."""
+    P = env.N * env.N
+    flat, off = [], [0]
+    for j, g in enumerate(games):
+        if isinstance(g, SelfPlayPlayer):
+            seq = g.moves
+        elif isinstance(g, dict):
+            if "moves" not in g:
+                raise TypeError(f"games[{j}] is a dict without 'moves'")
+            seq = g["moves"]
+        elif isinstance(g, (list, tuple, np.ndarray)):
+            seq = g
+        else:
+            raise TypeError(f"games[{j}] is {type(g).__name__}, not a move list, a record dict or a selfplay() player")
+        for k, m in enumerate(seq):
+            if m is None:
+                a = P
+            elif isinstance(m, (int, np.integer)) and not isinstance(m, bool):
+                a = int(m)
+            elif isinstance(m, (tuple, list, np.ndarray)) and len(m) == 2:
+                r, c = int(m[0]), int(m[1])
+                if not (0 <= r < env.N and 0 <= c < env.N):
+                    raise ValueError(f"games[{j}] move {k}: {tuple(m)} is off the {env.N}x{env.N} board")
+                a = to_flat((r, c), env)
+            else:
+                raise TypeError(f"games[{j}] move {k}: {m!r} is neither a coordinate pair, None nor a flat action")
+            if not 0 <= a <= P:
+                raise ValueError(f"games[{j}] move {k}: action {a} is not in 0..{P}")
+            flat.append(a)
+        off.append(len(flat))
+    return np.array(flat, np.int16), np.array(off, np.int64)
+
+
+def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, seed=0, game_id_base=0, slots=None,
+           symmetry=None, precision="f32", **cfg):
+    """Batched game review (ours; the loop of play(), src/play.jl:25-77, over recorded games): for game j, what
+    `p = MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + j, symmetry=symmetry)`,
+    `p.initialize_game(starts[j])`, then for every recorded move m_k `p.suggest_move()` and `p.play_move(m_k)` compute,
+    bit for bit: one list of Analysis per game, entry k taken at the k-th suggest_move (the move picked, the root's N, W,
+    Q and rows).  The recorded move, not the suggested one, re-roots the tree, so its subtree is kept.  games: move lists
+    (coordinates / None / flat actions), Engine.records() dicts or selfplay() players.  starts: None (every game from the
+    empty board with agz_config.komi) or one Position (or None) per game.  A recorded move that cannot be played (illegal,
+    or after the game ended) gives its ply and every later one of that game status BAD_ARGUMENT, move None; the earlier
+    plies and the other games are not affected.  `slots` trees search at once (default min(len(games),
+    1024)).  `cfg`: further agz_config fields (parallel_readouts, max_nodes_per_game, pool_policy, komi, ...)."""
+    games = list(games)
+    moves, off = review_arrays(env, games)
+    if starts is not None:
+        starts = list(starts)
+        if len(starts) != len(games):
+            raise ValueError(f"{len(starts)} starts for {len(games)} games")
+        for k, p in enumerate(starts):
+            if p is not None and not isinstance(p, Position):
+                raise TypeError(f"starts[{k}] is {type(p).__name__}, not a Position")
+            if p is not None and p.env.N != env.N:
+                raise ValueError(f"starts[{k}] is a {p.env.N}x{p.env.N} position, env is {env.N}x{env.N}")
+    if isinstance(num_readouts, bool) or not isinstance(num_readouts, (int, np.integer)) or int(num_readouts) < 1:
+        raise ValueError("num_readouts must be an integer >= 1")
+    if not games:
+        return []
+    G, P = len(games), env.N * env.N
+    slots = min(G, 1024) if slots is None else int(slots)
+    if slots < 1:
+        raise ValueError("slots must be >= 1")
+    if not isinstance(nn, NeuralNet):
+        raise TypeError("review needs a NeuralNet of this package (the search runs on the device with its weights)")
+    boards = infos = hist = None
+    if starts is not None:
+        boards = np.zeros((G, P), np.int8)
+        hist = np.zeros((G, 7, P), np.int8)
+        infos = (_lib.PositionInfo * G)()
+        for k, p in enumerate(starts):
+            p = Position(env, komi=cfg.get("komi", 7.5)) if p is None else p
+            boards[k], infos[k], h = position_arrays(p)
+            hist[k, :len(h)] = h
+    # trees are re-rooted and kept, as in self-play: the engine's default pool (agz_config.max_nodes_per_game)
+    eng = Engine(board_size=env.N, tower_height=nn.tower_height, games=slots, num_readouts=int(num_readouts),
+                 seed=seed, two_player_mode=int(two_player_mode), **cfg)
+    try:
+        nn.engine.copy_weights_to(eng)
+        eng.set_precision(precision)
+        if symmetry is not None:
+            eng.set_symmetry(symmetry)
+        eng.review_start(moves, off, boards, infos, hist, game_id_base)
+        total = int(off[-1])
+        while eng.review_progress() < total:
+            eng.step(16)
+            if eng.stats()["stalled_games"]:      # pool_policy = AGZ_POOL_STALL: a slot waits on its full pool
+                raise _lib.AgzError(_lib.POOL_EXHAUSTED, "a search is waiting on a full node pool (pool_policy = "
+                                                         "stall): raise max_nodes_per_game or use the default policy")
+        r = eng.review_results()
+    finally:
+        eng.close()
+    out = []
+    for j in range(G):
+        rows = []
+        for i in range(int(off[j]), int(off[j + 1])):
+            cn, cw = r["child_N"][i], r["child_W"][i]
+            rows.append(Analysis(None if r["move"][i] < 0 else from_flat(int(r["move"][i]), env), r["N"][i], r["W"][i],
+                                 r["Q"][i], cn, cw, cw / (np.float32(1) + cn), r["prior"][i], int(r["status"][i]),
+                                 int(r["nodes_used"][i]), int(game_id_base) + j))
+        out.append(rows)
+    return out
+
+
 EvalStats = namedtuple("EvalStats", "games_won num_games win_rate resigned moves records")
 
 

@@ -307,6 +307,10 @@ agz_status agz_analyze_start(agz_engine* e, const int8_t* boards, const agz_posi
                              int64_t B, uint64_t game_id_base) {
   return guard(e, [&](agz::Engine& E) { E.analyze_start(boards, info, history, B, game_id_base); });
 }
+agz_status agz_review_start(agz_engine* e, const int16_t* moves, const int64_t* game_offset, const int8_t* boards,
+                            const agz_position_info* info, const int8_t* history, int64_t G, uint64_t game_id_base) {
+  return guard(e, [&](agz::Engine& E) { E.review_start(moves, game_offset, boards, info, history, G, game_id_base); });
+}
 agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out) {
   return guard(e, [&](agz::Engine& E) {
     const int64_t d = E.analyze_progress();

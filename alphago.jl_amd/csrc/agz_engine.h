@@ -37,6 +37,9 @@ class Engine {
   // batched analysis (agz_analyze_*): suggest_move over B caller positions, stepped by step() / the external split
   void analyze_start(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,
                      uint64_t game_id_base);
+  // batched game review (agz_review_start): play() over G recorded games on reused trees, rows read as in analysis
+  void review_start(const int16_t* moves, const int64_t* game_offset, const int8_t* boards, const agz_position_info* info,
+                    const int8_t* history, int64_t G, uint64_t game_id_base);
   int64_t analyze_progress();
   void analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior);
   void leaf_features_external(float* feats_out);
@@ -171,7 +174,15 @@ class Engine {
   DevBuf<agz_position_info> an_info_;
   DevBuf<agz_analysis> an_res_;
   DevBuf<float> an_rows_;       // [3][B][A]: child_N, child_W, prior
-  int64_t an_count_ = 0;
+  int64_t an_count_ = 0;         // rows of the current run
+  DevBuf<int16_t> rv_moves_;    // review mode: the recorded moves and game offsets (View::rv_*)
+  DevBuf<int64_t> rv_off_;
+  std::vector<int64_t> rv_off_host_;
+  void check_positions(const char* mode, const char* item, const agz_position_info* info, const int8_t* history,
+                       int64_t B);
+  void upload_positions(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,
+                        int64_t rows);
+  void begin_analysis_run(int64_t B, int64_t rows, uint64_t game_id_base);
   // replay arena
   DevBuf<uint8_t> rp_buf_, s_pack_;
   size_t rp_used_ = 0;

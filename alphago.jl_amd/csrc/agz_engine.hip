@@ -565,6 +565,7 @@ void Engine::net_select(int which) {
 
 void Engine::start(int64_t total_games) {
   V_.analysis = 0;              // back to self-play (the analysis tables stay readable through analyze_results)
+  V_.review = 0;
   V_.total_games = total_games;
   rec_sent_ = 0;
   abandoned_ = 0;
@@ -622,34 +623,58 @@ void Engine::analyze_start(const int8_t* boards, const agz_position_info* info, 
                            uint64_t game_id_base) {
   AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "analysis: an arena_mode engine plays evaluate() games only");
   AGZ_REQUIRE(boards && info && B >= 1, AGZ_BAD_ARGUMENT, "analysis: boards and info of B >= 1 positions");
-  const int P = V_.P, A = V_.A;
-  for (int64_t i = 0; i < B; ++i) {   // the scalar fields; the boards are checked on the device, per position
+  check_positions("analysis", "position", info, history, B);
+  AGZ_HIP(hipStreamSynchronize(stream_));     // nothing in flight may still read the tables that are replaced here
+  upload_positions(boards, info, history, B, B);
+  V_.review = 0;
+  V_.rv_moves = nullptr;
+  V_.rv_off = nullptr;
+  begin_analysis_run(B, B, game_id_base);
+}
+
+// the scalar fields of caller positions; the boards are checked on the device, per position (root_board_valid)
+void Engine::check_positions(const char* mode, const char* item, const agz_position_info* info,
+                             const int8_t* history, int64_t B) {
+  const int P = V_.P;
+  for (int64_t i = 0; i < B; ++i) {
     const agz_position_info& f = info[i];
-    AGZ_REQUIRE(f.to_play == 1 || f.to_play == -1, AGZ_BAD_ARGUMENT, "analysis: position %lld: to_play %d",
+    AGZ_REQUIRE(f.to_play == 1 || f.to_play == -1, AGZ_BAD_ARGUMENT, "%s: %s %lld: to_play %d", mode, item,
                 (long long)i, f.to_play);
-    AGZ_REQUIRE(f.history_len >= 0 && f.history_len <= 7, AGZ_BAD_ARGUMENT, "analysis: position %lld: history_len %d",
+    AGZ_REQUIRE(f.history_len >= 0 && f.history_len <= 7, AGZ_BAD_ARGUMENT, "%s: %s %lld: history_len %d", mode, item,
                 (long long)i, f.history_len);
-    AGZ_REQUIRE(history || f.history_len == 0, AGZ_BAD_ARGUMENT,
-                "analysis: position %lld: history_len %d without history boards", (long long)i, f.history_len);
-    AGZ_REQUIRE(f.n >= 0, AGZ_BAD_ARGUMENT, "analysis: position %lld: n %d", (long long)i, f.n);
-    AGZ_REQUIRE(f.ko >= -1 && f.ko < P, AGZ_BAD_ARGUMENT, "analysis: position %lld: ko %d", (long long)i, f.ko);
-    AGZ_REQUIRE(f.last_move >= -1 && f.last_move <= P, AGZ_BAD_ARGUMENT, "analysis: position %lld: last_move %d",
+    AGZ_REQUIRE(history || f.history_len == 0, AGZ_BAD_ARGUMENT, "%s: %s %lld: history_len %d without history boards",
+                mode, item, (long long)i, f.history_len);
+    AGZ_REQUIRE(f.n >= 0, AGZ_BAD_ARGUMENT, "%s: %s %lld: n %d", mode, item, (long long)i, f.n);
+    AGZ_REQUIRE(f.ko >= -1 && f.ko < P, AGZ_BAD_ARGUMENT, "%s: %s %lld: ko %d", mode, item, (long long)i, f.ko);
+    AGZ_REQUIRE(f.last_move >= -1 && f.last_move <= P, AGZ_BAD_ARGUMENT, "%s: %s %lld: last_move %d", mode, item,
                 (long long)i, f.last_move);
-    AGZ_REQUIRE(f.prev_move >= -1 && f.prev_move <= P, AGZ_BAD_ARGUMENT, "analysis: position %lld: prev_move %d",
+    AGZ_REQUIRE(f.prev_move >= -1 && f.prev_move <= P, AGZ_BAD_ARGUMENT, "%s: %s %lld: prev_move %d", mode, item,
                 (long long)i, f.prev_move);
   }
-  AGZ_HIP(hipStreamSynchronize(stream_));     // nothing in flight may still read the tables that are replaced here
+}
+
+// B positions into the an_* tables, result tables of `rows` rows cleared (the stream is idle)
+void Engine::upload_positions(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,
+                              int64_t rows) {
+  const int P = V_.P, A = V_.A;
+  const size_t R = (size_t)(rows > 0 ? rows : 1);
   an_board_.ensure((size_t)B * P);
   an_hist_.ensure((size_t)B * 7 * P);
   an_info_.ensure((size_t)B);
-  an_res_.ensure((size_t)B);
-  an_rows_.ensure((size_t)3 * B * A);
+  an_res_.ensure(R);
+  an_rows_.ensure((size_t)3 * R * A);
   AGZ_HIP(hipMemcpyAsync(an_board_.p, boards, (size_t)B * P, hipMemcpyHostToDevice, stream_));
   if (history) AGZ_HIP(hipMemcpyAsync(an_hist_.p, history, (size_t)B * 7 * P, hipMemcpyHostToDevice, stream_));
   else AGZ_HIP(hipMemsetAsync(an_hist_.p, 0, (size_t)B * 7 * P, stream_));
   AGZ_HIP(hipMemcpyAsync(an_info_.p, info, sizeof(agz_position_info) * B, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemsetAsync(an_res_.p, 0, sizeof(agz_analysis) * B, stream_));
-  AGZ_HIP(hipMemsetAsync(an_rows_.p, 0, sizeof(float) * 3 * B * A, stream_));
+  AGZ_HIP(hipMemsetAsync(an_res_.p, 0, sizeof(agz_analysis) * R, stream_));
+  AGZ_HIP(hipMemsetAsync(an_rows_.p, 0, sizeof(float) * 3 * R * A, stream_));
+}
+
+// B claimable items (positions, or games in review mode) filling `rows` result rows: counters cleared, every slot idle
+void Engine::begin_analysis_run(int64_t B, int64_t rows, uint64_t game_id_base) {
+  const int A = V_.A;
+  const size_t R = (size_t)(rows > 0 ? rows : 1);
   AGZ_HIP(hipMemsetAsync(V_.an_ctr, 0, sizeof(unsigned long long) * 2, stream_));
   // every slot idle, as agz_selfplay_start leaves them; the counters and the records ring keep their self-play content
   std::vector<GameState> gs(V_.games);
@@ -657,7 +682,7 @@ void Engine::analyze_start(const int8_t* boards, const agz_position_info* info, 
   for (auto& g : gs) g.phase = G_IDLE;
   AGZ_HIP(hipMemcpyAsync(V_.gs, gs.data(), sizeof(GameState) * gs.size(), hipMemcpyHostToDevice, stream_));
   AGZ_HIP(hipStreamSynchronize(stream_));
-  an_count_ = B;
+  an_count_ = rows;
   V_.analysis = 1;
   V_.an_count = B;
   V_.an_id_base = game_id_base;
@@ -666,13 +691,60 @@ void Engine::analyze_start(const int8_t* boards, const agz_position_info* info, 
   V_.an_info = an_info_.p;
   V_.an_res = an_res_.p;
   V_.an_childN = an_rows_.p;
-  V_.an_childW = an_rows_.p + (size_t)B * A;
-  V_.an_prior = an_rows_.p + (size_t)2 * B * A;
+  V_.an_childW = an_rows_.p + R * A;
+  V_.an_prior = an_rows_.p + 2 * R * A;
   external_batch_ = external_batch2_ = 0;
 }
 
+// ---- batched game review
+
+void Engine::review_start(const int16_t* moves, const int64_t* game_offset, const int8_t* boards,
+                          const agz_position_info* info, const int8_t* history, int64_t G, uint64_t game_id_base) {
+  AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "review: an arena_mode engine plays evaluate() games only");
+  AGZ_REQUIRE(game_offset && G >= 1, AGZ_BAD_ARGUMENT, "review: game_offset of G + 1 entries, G >= 1");
+  AGZ_REQUIRE((boards == nullptr) == (info == nullptr), AGZ_BAD_ARGUMENT,
+              "review: start boards and info are given together or not at all");
+  AGZ_REQUIRE(boards || !history, AGZ_BAD_ARGUMENT, "review: history without start boards");
+  const int P = V_.P;
+  AGZ_REQUIRE(game_offset[0] == 0, AGZ_BAD_ARGUMENT, "review: game_offset[0] = %lld, not 0", (long long)game_offset[0]);
+  for (int64_t j = 0; j < G; ++j)
+    AGZ_REQUIRE(game_offset[j + 1] >= game_offset[j], AGZ_BAD_ARGUMENT,
+                "review: game %lld: game_offset decreases (%lld -> %lld)", (long long)j, (long long)game_offset[j],
+                (long long)game_offset[j + 1]);
+  const int64_t total = game_offset[G];
+  AGZ_REQUIRE(moves || total == 0, AGZ_BAD_ARGUMENT, "review: %lld moves without a move array", (long long)total);
+  for (int64_t j = 0; j < G; ++j)
+    for (int64_t t = game_offset[j]; t < game_offset[j + 1]; ++t)
+      AGZ_REQUIRE(moves[t] >= 0 && moves[t] <= P, AGZ_BAD_ARGUMENT, "review: game %lld: move %lld is %d, not in 0..%d",
+                  (long long)j, (long long)(t - game_offset[j]), (int)moves[t], P);
+  std::vector<int8_t> dboards;
+  std::vector<agz_position_info> dinfo;
+  if (!boards) {       // the empty board with agz_config.komi, Black to play
+    dboards.assign((size_t)G * P, 0);
+    agz_position_info f;
+    std::memset(&f, 0, sizeof(f));
+    f.n = 0; f.to_play = 1; f.ko = -1; f.caps_black = 0; f.caps_white = 0; f.last_move = -1; f.prev_move = -1;
+    f.history_len = 0; f.komi = V_.komi;
+    dinfo.assign((size_t)G, f);
+    boards = dboards.data();
+    info = dinfo.data();
+  }
+  check_positions("review", "game", info, history, G);
+  AGZ_HIP(hipStreamSynchronize(stream_));     // nothing in flight may still read the tables that are replaced here
+  upload_positions(boards, info, history, G, total);
+  rv_moves_.ensure((size_t)(total > 0 ? total : 1));
+  rv_off_.ensure((size_t)G + 1);
+  if (total > 0) AGZ_HIP(hipMemcpyAsync(rv_moves_.p, moves, sizeof(int16_t) * total, hipMemcpyHostToDevice, stream_));
+  AGZ_HIP(hipMemcpyAsync(rv_off_.p, game_offset, sizeof(int64_t) * (G + 1), hipMemcpyHostToDevice, stream_));
+  rv_off_host_.assign(game_offset, game_offset + G + 1);
+  V_.review = 1;
+  V_.rv_moves = rv_moves_.p;
+  V_.rv_off = rv_off_.p;
+  begin_analysis_run(G, total, game_id_base);
+}
+
 int64_t Engine::analyze_progress() {
-  AGZ_REQUIRE(an_count_ > 0, AGZ_BAD_ARGUMENT, "analysis: no agz_analyze_start on this engine");
+  AGZ_REQUIRE(V_.an_res != nullptr, AGZ_BAD_ARGUMENT, "analysis: no agz_analyze_start on this engine");
   unsigned long long done = 0;
   AGZ_HIP(hipMemcpyAsync(&done, V_.an_ctr + 1, sizeof(done), hipMemcpyDeviceToHost, stream_));
   AGZ_HIP(hipStreamSynchronize(stream_));
@@ -682,7 +754,7 @@ int64_t Engine::analyze_progress() {
 
 void Engine::analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior) {
   const int64_t done = analyze_progress(), B = an_count_;
-  AGZ_REQUIRE(done >= B, AGZ_NOT_READY, "analysis: %lld of %lld positions finished", (long long)done, (long long)B);
+  AGZ_REQUIRE(done >= B, AGZ_NOT_READY, "analysis: %lld of %lld rows finished", (long long)done, (long long)B);
   const size_t rows = (size_t)B * V_.A;
   if (out) AGZ_HIP(hipMemcpyAsync(out, an_res_.p, sizeof(agz_analysis) * B, hipMemcpyDeviceToHost, stream_));
   if (child_N) AGZ_HIP(hipMemcpyAsync(child_N, an_rows_.p, sizeof(float) * rows, hipMemcpyDeviceToHost, stream_));
@@ -854,16 +926,25 @@ void Engine::slot_abandon(int g) {
   if (V_.analysis) {
     // the slot's position is given up: its result says so (move -1, the statistics the search reached), and it counts
     // as finished; agz_stats.abandoned_games keeps its self-play meaning
+    // (review mode: the rest of the game is given up -- the current ply's row as above, the later rows move -1 and
+    // nothing searched, all AGZ_POOL_EXHAUSTED)
     int64_t i = 0;
     unsigned long long done = 0;
     AGZ_HIP(hipMemcpyAsync(&i, V_.an_slot + g, sizeof(i), hipMemcpyDeviceToHost, stream_));
     AGZ_HIP(hipMemcpyAsync(&done, V_.an_ctr + 1, sizeof(done), hipMemcpyDeviceToHost, stream_));
     AGZ_HIP(hipStreamSynchronize(stream_));
-    agz_analysis r;
-    r.move = -1; r.status = AGZ_POOL_EXHAUSTED; r.N = G.rootN; r.W = G.rootW; r.Q = G.rootW / (1.0f + G.rootN);
+    int64_t row = i, nrows = 1;
+    if (V_.review) {
+      row = rv_off_host_[i] + G.move_count;
+      nrows = rv_off_host_[i + 1] - row;
+    }
+    std::vector<agz_analysis> rs((size_t)nrows);
+    for (auto& r : rs) { r.move = -1; r.status = AGZ_POOL_EXHAUSTED; r.N = 0.f; r.W = 0.f; r.Q = 0.f; r.nodes_used = 0; }
+    agz_analysis& r = rs[0];
+    r.N = G.rootN; r.W = G.rootW; r.Q = G.rootW / (1.0f + G.rootN);
     r.nodes_used = G.nodes_used;
-    ++done;
-    AGZ_HIP(hipMemcpyAsync(V_.an_res + i, &r, sizeof(r), hipMemcpyHostToDevice, stream_));
+    done += (unsigned long long)nrows;
+    AGZ_HIP(hipMemcpyAsync(V_.an_res + row, rs.data(), sizeof(agz_analysis) * nrows, hipMemcpyHostToDevice, stream_));
     AGZ_HIP(hipMemcpyAsync(V_.an_ctr + 1, &done, sizeof(done), hipMemcpyHostToDevice, stream_));
   }
   G.phase = G_IDLE;

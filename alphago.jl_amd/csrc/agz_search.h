@@ -1329,11 +1329,17 @@ AGZ_FN void arena_move_phase(W& w, const View& V, Scratch& S, int g) {
 // a full pool under AGZ_POOL_MOVE_EARLY: pick_move, the row of position i in the result tables, back to G_IDLE.  No
 // noise, no pre-expansion, no record, no re-rooting: the next install resets the pool.
 
-// position i's row of the result tables: the header, and the root's three A-wide rows in consecutive stores
+// the result row of the slot's current search: position an_slot[g], or in review mode ply G.move_count of game an_slot[g]
+AGZ_FN long long analysis_row(const View& V, int g) {
+  const long long j = V.an_slot[g];
+  return V.review ? V.rv_off[j] + V.gs[g].move_count : j;
+}
+
+// the slot's row of the result tables: the header, and the root's three A-wide rows in consecutive stores
 template <class W>
 AGZ_FN void analysis_finish(W& w, const View& V, Scratch& S, int g) {
   GameState& G = V.gs[g];
-  const long long i = V.an_slot[g];
+  const long long i = analysis_row(V, g);
   const long ri = node_index(V, g, G.root);
   int status = G.rootN < G.target ? AGZ_POOL_EXHAUSTED : AGZ_OK;     // only the full-pool rule ends a search early
   int a = -1;
@@ -1355,6 +1361,108 @@ AGZ_FN void analysis_finish(W& w, const View& V, Scratch& S, int g) {
   w.count(&V.an_ctr[1], 1);
 }
 
+// ---------------------------------------------------------------- batched game review ----
+// play() (src/play.jl:25-77) over recorded games (DESIGN.md "Batched game review"): game j's ply k is suggest_move on the
+// tree, then play_move!(player, m_k) with the recorded move, which re-roots the same tree.  The slot's ply is G.move_count.
+
+// rows k .. n-1 of game j (k = G.move_count) get `status` and move -1 with nothing searched; the slot goes idle
+template <class W>
+AGZ_FN void review_give_up(W& w, const View& V, int g, int status) {
+  GameState& G = V.gs[g];
+  const long long j = V.an_slot[g];
+  const long long r0 = V.rv_off[j] + G.move_count, r1 = V.rv_off[j + 1];
+  w.for_each((int)(r1 - r0), [&](int t) {
+    agz_analysis r;
+    r.move = -1; r.status = status; r.N = 0.f; r.W = 0.f; r.Q = 0.f; r.nodes_used = 0;
+    V.an_res[r0 + t] = r;
+  });
+  w.sync();
+  if (w.leader()) { G.phase = G_IDLE; G.nleaves = 0; G.err = 0; G.stalled = 0; }
+  w.sync();
+  w.count(&V.an_ctr[1], (unsigned long long)(r1 - r0));
+}
+
+// Before ply k's search: the game is over (k = n), or m_k must be playable at the root -- legal there (legal_bit: an
+// empty point, not the ko point, no suicide; a pass always) and the root not finished (two passes, max_game_length).  An
+// invalid record gives up the rest of the game (rows k.. BAD_ARGUMENT).  Otherwise suggest_move's target.
+template <class W>
+AGZ_FN void review_next_ply(W& w, const View& V, int g) {
+  GameState& G = V.gs[g];
+  const long long j = V.an_slot[g];
+  const long long off = V.rv_off[j], n = V.rv_off[j + 1] - off;
+  if (G.move_count >= n) {
+    if (w.leader()) { G.phase = G_IDLE; G.nleaves = 0; G.err = 0; G.stalled = 0; }
+    w.sync();
+    return;
+  }
+  const int a = V.rv_moves[off + G.move_count];
+  const long ri = node_index(V, g, G.root);
+  if (node_is_done(V, g, G.root) || !legal_bit(V, ri, a)) {
+    review_give_up(w, V, g, AGZ_BAD_ARGUMENT);
+    return;
+  }
+  if (w.leader()) { G.phase = G_SEARCH; G.target = G.rootN + (float)V.R; G.stalled = 0; }   // N(root) >= N0 + R
+  w.sync();
+}
+
+// play_move!(player, m_k) (mcts_play.jl:26-50) without the record: find or create the child, re-root (the dropped
+// siblings go to the garbage stack game_pre drains), then the next ply.  A child the full pool cannot hold is made room
+// for by discarding the root's other subtrees first: the re-root drops them anyway, so the result is the unbounded
+// tree's.
+template <class W>
+AGZ_FN void review_play(W& w, const View& V, Scratch& S, int g) {
+  GameState& G = V.gs[g];
+  const long long j = V.an_slot[g];
+  const int a = V.rv_moves[V.rv_off[j] + G.move_count];
+  const int root = G.root;
+  const long ri = node_index(V, g, root);
+  int child = V.child[ri * V.AP + a];
+  if (child < 0) child = node_create_child(w, V, S, g, root, a);
+  if (child == -1) {
+    if (w.leader()) {
+      for (int b = 0; b < V.A; ++b) {
+        const int c = V.child[ri * V.AP + b];
+        if (c < 0) continue;
+        V.child[ri * V.AP + b] = -1;
+        V.freelist[(long)g * V.cap + V.cap - G.garbage - 1] = c;
+        G.garbage = G.garbage + 1;
+      }
+      G.err = 0;
+    }
+    w.sync();
+    free_pending(w, V, S, g, V.cap);
+    child = node_create_child(w, V, S, g, root, a);
+  }
+  if (child < 0) {                                      // (a pool of fewer than two nodes)
+    if (w.leader()) G.move_count = G.move_count + 1;
+    w.sync();
+    review_give_up(w, V, g, AGZ_POOL_EXHAUSTED);
+    return;
+  }
+  reroot(w, V, S, g, a, child);
+  if (w.leader()) { G.move_count = G.move_count + 1; G.err = 0; }
+  w.sync();
+  review_next_ply(w, V, g);
+}
+
+// G_IDLE in review mode: claim game j, install its start (an invalid board gives up all its rows), ply 0
+template <class W>
+AGZ_FN void review_claim(W& w, const View& V, Scratch& S, int g, long long j) {
+  GameState& G = V.gs[g];
+  const agz_position_info info = V.an_info[j];
+  if (w.leader()) V.an_slot[g] = j;
+  w.sync();
+  if (V.rv_off[j + 1] == V.rv_off[j]) return;          // no moves, no rows
+  const bool ok = root_install(w, V, S, g, V.an_board + j * V.P, V.an_hist + j * 7 * V.P, info, G_SEARCH, true);
+  if (w.leader()) {
+    G.move_count = 0;
+    if (ok) { G.game_id = V.an_id_base + (uint64_t)j; G.short_first = 0; }
+  }
+  w.sync();
+  if (!ok) { review_give_up(w, V, g, AGZ_BAD_ARGUMENT); return; }
+  review_next_ply(w, V, g);
+}
+
 template <class W>
 AGZ_FN void analysis_pre(W& w, const View& V, Scratch& S, int g) {
   GameState& G = V.gs[g];
@@ -1368,7 +1476,10 @@ AGZ_FN void analysis_pre(W& w, const View& V, Scratch& S, int g) {
     const bool finish = !(G.rootN < G.target) || pool_full_can_move(w, V, g);
     if (w.leader()) G.stalled = full && !finish;        // AGZ_POOL_STALL: the slot waits for agz_slot_abandon
     w.sync();
-    if (finish) analysis_finish(w, V, S, g);
+    if (finish) {
+      analysis_finish(w, V, S, g);
+      if (V.review) review_play(w, V, S, g);
+    }
   }
   while (G.phase == G_IDLE) {
     if (w.leader()) G.nleaves = 0;
@@ -1378,6 +1489,10 @@ AGZ_FN void analysis_pre(W& w, const View& V, Scratch& S, int g) {
       if (w.leader()) G.phase = G_RETIRED;
       w.sync();
       return;
+    }
+    if (V.review) {
+      review_claim(w, V, S, g, i);
+      continue;
     }
     const agz_position_info info = V.an_info[i];
     if (!root_install(w, V, S, g, V.an_board + i * V.P, V.an_hist + i * 7 * V.P, info, G_SEARCH, true)) {

@@ -150,6 +150,12 @@ struct View {
   float* an_childN;                   // [an_count][A]: the root's rows when the search ended
   float* an_childW;
   float* an_prior;
+  // review sub-mode (agz_review_start; analysis = 1 as well, zero = off): the claimed items are games j = 0..an_count-1,
+  // an_board / an_hist / an_info hold their start positions, and game j's plies k write rows rv_off[j] + k of the result
+  // tables (DESIGN.md "Batched game review"); G.move_count is the slot's ply k
+  int32_t review;
+  const int16_t* rv_moves;            // [rv_off[an_count]]: the recorded moves, game after game
+  const int64_t* rv_off;              // [an_count + 1]: game j's moves and rows are rv_off[j] .. rv_off[j+1]-1
 };
 
 }  // namespace agz

@@ -23,7 +23,7 @@ using Random
 export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
-       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze,
+       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review,
        # the node-level surface test/test_mcts.jl:2-5 and test/test_mcts_player.jl:3-6 import
        MCTSNode, select_leaf, maybe_add_child!, add_virtual_loss!, revert_virtual_loss!,
        incorporate_results!, inject_noise!, child_action_score, child_Q, child_U, child_N, child_W,
@@ -789,6 +789,68 @@ function analyze(env::GoEnv, nn::NeuralNet, positions::Vector{Position}; num_rea
   [(move = r.move < 0 ? nothing : from_flat(r.move + 1, env), N = r.N, W = r.W, Q = r.Q, child_N = cn[:, i],
     child_W = cw[:, i], child_Q = cw[:, i] ./ (1f0 .+ cn[:, i]), child_prior = pr[:, i], status = Int(r.status),
     nodes_used = Int(r.nodes_used)) for (i, r) in enumerate(res)]
+end
+
+# review(env, nn, games; num_readouts) (ours): the loop of play() (src/play.jl:25-77) over recorded games in one device
+# run.  games[j] is a SelfPlayPlayer or a move list (board coordinates, nothing = pass, or 1-based flat moves); starts is
+# nothing (the empty board) or one Position per game.  Result j is a vector of the NamedTuples analyze returns, entry k
+# what MCTSPlayer(env, nn; num_readouts, two_player_mode) with draw-stream seed `seed` and game id game_id_base + j - 1,
+# initialize_game!(player, starts[j]) and then suggest_move(player) / play_move!(player, m_k) compute at its k-th
+# suggest_move, bit for bit (include/agz.h agz_review_start).  A recorded move that cannot be played gives its ply and
+# the later ones of that game status AGZ_BAD_ARGUMENT.
+function review(env::GoEnv, nn::NeuralNet, games::Vector; num_readouts::Int = 800, starts = nothing,
+                two_player_mode = true, seed = 0, game_id_base = 0, slots::Union{Nothing, Int} = nothing,
+                symmetry = nothing)
+  G, P, A = length(games), env.N * env.N, env.action_space
+  G == 0 && return Vector{NamedTuple}[]
+  num_readouts >= 1 || throw(ArgumentError("num_readouts must be >= 1"))
+  moves = Int16[]; off = Int64[0]
+  for g in games
+    seq = g isa SelfPlayPlayer ? g.moves : g
+    for m in seq
+      f = m === nothing ? P + 1 : m isa Integer ? Int(m) : to_flat(m, env)
+      1 <= f <= P + 1 || throw(ArgumentError("move $m is not on the $(env.N)x$(env.N) board"))
+      push!(moves, Int16(f - 1))
+    end
+    push!(off, length(moves))
+  end
+  boards = C_NULL; info = C_NULL; hist = C_NULL
+  if starts !== nothing
+    length(starts) == G || throw(ArgumentError("$(length(starts)) starts for $G games"))
+    boards = zeros(Int8, P, G); hist = zeros(Int8, P, 7, G); info = Vector{AgzPositionInfo}(undef, G)
+    for (j, pos) in enumerate(starts)
+      b, info[j], h = position_arrays(env, pos === nothing ? Position(env) : pos)
+      boards[:, j] = vec(b); hist[:, 1:size(h, 2), j] = h
+    end
+  end
+  # trees are re-rooted and kept, as in self-play: the engine's default pool
+  e = Engine(board_size = env.N, tower_height = nn.tower_height, games = slots === nothing ? min(G, 1024) : slots,
+             num_readouts = num_readouts, seed = seed, two_player_mode = two_player_mode)
+  copy_weights!(e, nn.engine)
+  symmetry === nothing || set_symmetry!(e, symmetry)
+  check(e, ccall((:agz_review_start, libagz), Int32,
+                 (Ptr{Cvoid}, Ptr{Int16}, Ptr{Int64}, Ptr{Int8}, Ptr{AgzPositionInfo}, Ptr{Int8}, Int64, UInt64),
+                 e.handle, moves, off, boards, info, hist, G, game_id_base))
+  total = off[end]
+  done = Ref{Int64}(0)
+  while true
+    check(e, ccall((:agz_analyze_progress, libagz), Int32, (Ptr{Cvoid}, Ref{Int64}), e.handle, done))
+    done[] >= total && break
+    check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 16))
+    check_pool(e)     # a search waiting on a full pool (AGZ_POOL_STALL) cannot finish
+  end
+  res = Vector{AgzAnalysis}(undef, total)
+  cn, cw, pr = zeros(Float32, A, total), zeros(Float32, A, total), zeros(Float32, A, total)
+  check(e, ccall((:agz_analyze_results, libagz), Int32, (Ptr{Cvoid}, Ptr{AgzAnalysis}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+                 e.handle, res, cn, cw, pr))
+  row(i, j0) = (r = res[i]; (move = r.move < 0 ? nothing : from_flat(r.move + 1, env), N = r.N, W = r.W, Q = r.Q,
+            child_N = cn[:, i], child_W = cw[:, i], child_Q = cw[:, i] ./ (1f0 .+ cn[:, i]), child_prior = pr[:, i],
+            status = Int(r.status), nodes_used = Int(r.nodes_used), game_id = UInt64(game_id_base + j0)))
+  out = Vector{Vector{NamedTuple}}(undef, G)
+  for j in 1:G
+    out[j] = [row(i, j - 1) for i in off[j]+1:off[j+1]]
+  end
+  out
 end
 
 # get_replay_batch(pos_buffer, π_buffer, res_buffer; batch_size), src/train.jl:4-12: batch_size distinct entries,

@@ -503,6 +503,33 @@ agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out);
 /* out[B], child_N / child_W / prior [B][A] (the root's rows when the search ended); any of them may be NULL */
 agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N, float* child_W, float* prior);
 
+/* ---------------------------------------------------------------- batched game review --- */
+/* play() (src/play.jl:25-77) over many recorded games in one device run (ours; the reference reviews a game with one
+ * MCTSPlayer).  Game j (0-based) is a start position and moves m_0 .. m_{n_j-1}; its row k (0-based) gives exactly what
+ *   p = MCTSPlayer(env, nn; num_readouts, two_player_mode) with draw-stream seed agz_config.seed and game id
+ *   game_id_base + j;  initialize_game!(p, start_j);  for k: suggest_move(p), then play_move!(p, m_k)
+ * gives at its k-th suggest_move: the move picked and the root's N, W, Q and rows.  play_move! with the recorded move
+ * re-roots the same tree, so the subtree under m_k is kept and ply k + 1 searches until N(root) >= N0 + num_readouts.
+ * No Dirichlet noise, no resignation, no record.  The rows do not depend on the number of slots, on which slot takes a
+ * game, or on splitting the games over runs with matching game_id_base.  Board symmetries apply as in the tree path.
+ *
+ * agz_review_start: moves int16[total] (actions 0..N*N, N*N = pass), game j's moves game_offset[j] .. game_offset[j+1]-1
+ * (game_offset int64[G+1], 0 first, non-decreasing, total last); boards / info / history: the start positions, in the
+ * conventions of agz_analyze_start, one per game, or boards = info = history = NULL for the empty board with
+ * agz_config.komi.  Host checks (a bad value fails the call naming the game): the moves' range, the offsets, the
+ * agz_position_info fields as agz_analyze_start checks them.  Refused in arena_mode.  The run is stepped as an analysis
+ * run and read with agz_analyze_progress / agz_analyze_results, which count and return the total rows: game j's ply k is
+ * row game_offset[j] + k.
+ *
+ * status per row: as agz_analyze_results', and: AGZ_BAD_ARGUMENT (move -1, nothing searched) for every row of a game
+ * from the first recorded move that cannot be played (illegal at that root, or after the game ended: two passes or
+ * max_game_length) -- or for all its rows when the start board is invalid; the earlier rows and other games are not
+ * affected.  AGZ_POOL_EXHAUSTED under AGZ_POOL_MOVE_EARLY is a short but valid row and the game goes on; under
+ * AGZ_POOL_STALL the slot waits, and agz_slot_abandon gives up the rest of the game (its current row carries the
+ * statistics reached, the later rows none; all move -1). */
+agz_status agz_review_start(agz_engine* e, const int16_t* moves, const int64_t* game_offset, const int8_t* boards,
+                            const agz_position_info* info, const int8_t* history, int64_t G, uint64_t game_id_base);
+
 /* Test hooks (device-side evaluation of the draw stream, single-tree introspection setters) are declared in
  * include/agz_debug.h: exported by the library for the parity tests, not part of the drop-in surface. */
 

@@ -22,10 +22,16 @@ sys.path.insert(0, ROOT)
 def positions_from_records(ag, env, recs, count, lo, hi, rng):
     """Position objects (board, board_deltas, recent, ko, caps) at a random ply in [lo, hi) of the games, rebuilt by
     batched agz_go_play replay of their move lists"""
-    N, P = env.N, env.N * env.N
     games = [r for r in recs if int(r["num_moves"]) > lo]
     picks = [(games[rng.randint(len(games))], 0) for _ in range(count)]
     picks = [(r, rng.randint(lo, min(hi, int(r["num_moves"])))) for r, _ in picks]
+    return positions_at(ag, env, picks)
+
+
+def positions_at(ag, env, picks):
+    """the Position before ply p of record r for every (r, p) of `picks` (records: dicts with flat "moves"), rebuilt by
+    batched agz_go_play replay"""
+    N, P = env.N, env.N * env.N
     eng = ag.Engine(board_size=N, tower_height=0, games=1, num_readouts=1, max_nodes_per_game=8)
     B = len(picks)
     boards = np.zeros((B, P), np.int8)
@@ -34,7 +40,7 @@ def positions_from_records(ag, env, recs, count, lo, hi, rng):
     caps = np.zeros((B, 2), np.int64)
     deltas = [[] for _ in range(B)]
     recent = [[] for _ in range(B)]
-    for k in range(max(p for _, p in picks)):
+    for k in range(max([p for _, p in picks], default=0)):
         live = np.array([b for b in range(B) if k < picks[b][1]])
         mv = np.array([int(picks[b][0]["moves"][k]) for b in live], np.int32)
         nb, nko, ncap, st = eng.go_play(boards[live], tp[live], ko[live], mv)
