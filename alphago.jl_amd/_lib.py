@@ -142,6 +142,8 @@ def load():
         "agz_selfplay_start": (i32, [E, i64]),
         "agz_selfplay_step": (i32, [E, i32]),
         "agz_selfplay_set_symmetry": (i32, [E, i32]),
+        "agz_selfplay_set_hold": (i32, [E, i32]),
+        "agz_selfplay_release": (i32, [E]),
         "agz_analyze_start": (i32, [E, i8p, P(PositionInfo), i8p, i64, u64]),
         "agz_review_start": (i32, [E, P(C.c_int16), P(i64), i8p, P(PositionInfo), i8p, i64, u64]),
         "agz_analyze_progress": (i32, [E, P(i64)]),
@@ -172,6 +174,12 @@ def load():
         "agz_replay_clear": (i32, [E]),
         "agz_replay_batch": (i32, [E, P(i64), i32p, i32, C.c_void_p, C.c_void_p, C.c_void_p, i32]),
         "agz_replay_batch_sym": (i32, [E, P(i64), i32p, i32p, i32, C.c_void_p, C.c_void_p, C.c_void_p, i32]),
+        "agz_replay_ingest_records": (i32, [E, i64, i64, P(i64)]),
+        "agz_replay_set_window": (i32, [E, i64]),
+        "agz_replay_live_positions": (i64, [E]),
+        "agz_device_alloc": (i32, [E, i64, P(C.c_void_p)]),
+        "agz_device_free": (i32, [E, C.c_void_p]),
+        "agz_replay_sample": (i32, [E, i32, u64, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "agz_train_step": (i32, [E, C.c_void_p, C.c_void_p, C.c_void_p, i32, i32, f32, f32, f32p]),
         "agz_train_reset": (i32, [E]),
         "agz_comm_unique_id": (i32, [P(C.c_uint8)]),

@@ -903,3 +903,128 @@ def _train(nn, input_data, opt, epochs=1):
         for lo, hi in zip(cuts[:-1], cuts[1:]):
             loss_avg += float(e.train_step(feats[lo:hi], pi[:, lo:hi].T, z[lo:hi], eta=opt.eta, rho=opt.rho)[0])
     return loss_avg / epochs
+
+
+def _result_string(h):
+    """player.result_string of a finished game from its record header (mcts_play.jl:100-108, board.jl:546-555)"""
+    if h["was_resign"]:
+        return "B+R" if h["result"] == BLACK else "W+R"
+    sc = float(h["final_score"])
+    return f"B+{sc:.1f}" if sc > 0 else f"W+{-sc:.1f}" if sc < 0 else "DRAW"
+
+
+def _minibatch_cuts(n):
+    """_train's chunking (api._train): 32-position minibatches, a single left-over position joins the one before it"""
+    cuts = list(range(0, n, 32)) + [n]
+    if len(cuts) > 2 and cuts[-1] - cuts[-2] == 1:
+        del cuts[-2]
+    return cuts
+
+
+def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp_freq=1000, readouts=800,
+          tower_height=19, model=None, start_training_after=50000, slots=None, seed=0, game_id_base=0, symmetry=None,
+          augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, **cfg):
+    """train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model,
+    start_training_after) (src/train.jl:38-92) with `slots` games in flight on the device.  One engine
+    plays, keeps the replay arena and trains; per step: agz_selfplay_step(1), one read of how many games finished, and
+    for each of them in game-id order: its record into the arena (device to device), the window set to the newest
+    memory_size entries, the game counter i advanced, then -- once the window holds start_training_after entries --
+    _train on a device-drawn get_replay_batch(batch_size) (agz_replay_sample with draw key (seed, i)) in `epochs` passes of
+    32-position agz_train_step minibatches, Momentum(2f-2); every ckp_freq games a checkpoint.  Finished slots are held
+    until the step's training is done, so every game starts on the weights the games finished before it left; slots = 1
+    is the reference's sequential loop.  Ours: seed / game_id_base (the draw stream of the games: they are game ids
+    game_id_base .. game_id_base + num_games - 1), symmetry (as in selfplay), augment (each sample under a drawn board symmetry), precision,
+    checkpoint_dir (save_model into checkpoint_dir/game_<i> every ckp_freq games; None: no checkpoints), callback (what
+    the reference prints goes here), return_log (also return one dict per game), profile (a dict filled with steps,
+    wall_s, train_s, train_steps, positions and host_syncs: the library calls of the loop that synchronise the engine's
+    stream, each at least once; tools/train_rate.py).  Returns the trained NeuralNet (model itself when given)."""
+    import time
+    import torch
+    from . import bson_weights as bw
+    import os
+    num_games, batch_size, epochs = int(num_games), int(batch_size), int(epochs)
+    if num_games < 1 or batch_size < 2 or epochs < 1 or int(ckp_freq) < 1:
+        raise ValueError("num_games, epochs, ckp_freq >= 1 and batch_size >= 2 (BatchNorm needs two positions)")
+    cur_nn = NeuralNet(env, tower_height=tower_height) if model is None else model       # train.jl:43
+    slots = min(num_games, 1024) if slots is None else int(slots)
+    if slots < 1:
+        raise ValueError("slots must be >= 1")
+    callback = callback or (lambda line: None)
+    eng = Engine(board_size=env.N, tower_height=cur_nn.tower_height, games=slots, num_readouts=int(readouts), seed=seed,
+                 game_id_base=game_id_base, record_capacity_games=slots + 8, **cfg)
+    log = []
+    try:
+        cur_nn.engine.copy_weights_to(eng)
+        eng.set_precision(precision)
+        if symmetry is not None:
+            eng.set_symmetry(symmetry)
+        opt = Momentum(2e-2)                                                            # train.jl:54
+        dev = torch.device("cuda", eng.cfg.device)
+        feats = torch.empty((batch_size, 17 * eng.P), dtype=torch.float32, device=dev)
+        pi = torch.empty((batch_size, eng.A), dtype=torch.float32, device=dev)
+        z = torch.empty(batch_size, dtype=torch.float32, device=dev)
+        cuts = _minibatch_cuts(batch_size)
+        eng.set_hold(True)
+        eng.start(num_games)
+        eng.release()
+        i = step = trained = claimed = 0
+        started = {}                                   # game index -> (step of its first network call, trainings before)
+        parked = slots
+        t0, t_train, n_steps, n_pos, syncs = time.perf_counter(), 0.0, 0, 0, 0
+        while i < num_games:
+            take = min(parked, num_games - claimed)
+            for k in range(claimed, claimed + take):
+                started[k] = (step + 1, trained)
+            claimed += take
+            eng.step(1)
+            step += 1
+            n = eng.records_count()                    # the step's one synchronising read
+            syncs += 1
+            if n == 0:
+                parked = 0
+                if step % 256 == 0 and eng.stats()["stalled_games"]:
+                    raise _lib.AgzError(_lib.POOL_EXHAUSTED, "a game is waiting on a full node pool (pool_policy = "
+                                                             "stall): raise max_nodes_per_game or use the default policy")
+                continue
+            heads = sorted(((eng.record_header(k), k) for k in range(n)), key=lambda hk: hk[0]["game_id"])
+            recs = {r["index"]: r for r in eng.records()} if return_log else None
+            syncs += 2 * n + 1                         # n headers, n ingests, records_clear
+            for h, k in heads:
+                n_pos += int(h["num_moves"])
+                eng.replay_ingest_records(k, 1)                                          # push_data, train.jl:60-61
+                eng.replay_set_window(memory_size)                                       # shrink, train.jl:63-65
+                i += 1
+                loss = None
+                if eng.replay_live_positions() >= start_training_after:                  # train.jl:67
+                    t1 = time.perf_counter()
+                    eng.replay_sample(batch_size, i, 8 if augment else -1, feats, pi, z)  # train.jl:68-69
+                    loss = 0.0
+                    for _ in range(epochs):                                              # _train, train.jl:70
+                        for lo, hi in zip(cuts[:-1], cuts[1:]):
+                            loss += float(eng.train_step_device(feats[lo:hi], pi[lo:hi], z[lo:hi], hi - lo, eta=opt.eta,
+                                                                rho=opt.rho)[0])
+                    loss /= epochs
+                    t_train += time.perf_counter() - t1
+                    n_steps += epochs * (len(cuts) - 1)
+                    syncs += epochs * (len(cuts) - 1)     # each step returns its losses
+                    trained += 1
+                    callback(f"Episode {i} over. Loss: {loss}. Winner: {_result_string(h)}. "
+                             f"Moves: {h['num_moves']}.")                                 # train.jl:71-73
+                if i % int(ckp_freq) == 0 and checkpoint_dir is not None:              # train.jl:86-89
+                    bw.write_checkpoint(os.path.join(checkpoint_dir, f"game_{i}"), bw.extract_param_lists(eng))
+                    callback("Model saved. ")
+                if return_log:
+                    gi = int(h["game_id"]) - int(game_id_base)
+                    log.append(dict(i=i, game_id=int(h["game_id"]), step=step, start_step=started[gi][0],
+                                    trained_before_start=started[gi][1], trained_after=trained, loss=loss,
+                                    live=eng.replay_live_positions(), record=recs[k]))
+            eng.records_clear()
+            eng.release()
+            parked = n
+        if profile is not None:
+            profile.update(steps=step, wall_s=time.perf_counter() - t0, train_s=t_train, train_steps=n_steps,
+                           positions=n_pos, host_syncs=syncs)
+        eng.copy_weights_to(cur_nn.engine)
+    finally:
+        eng.close()
+    return (cur_nn, log) if return_log else cur_nn

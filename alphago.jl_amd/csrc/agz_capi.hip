@@ -291,6 +291,39 @@ agz_status agz_replay_batch(agz_engine* e, const int64_t* game, const int32_t* p
   return guard(e, [&](agz::Engine& E) { E.replay_batch(game, ply, B, feats, pi, z, out_is_device != 0); });
 }
 
+agz_status agz_replay_ingest_records(agz_engine* e, int64_t first, int64_t count, int64_t* added_out) {
+  return guard(e, [&](agz::Engine& E) {
+    const int64_t n = E.replay_ingest_records(first, count);
+    if (added_out) *added_out = n;
+  });
+}
+agz_status agz_replay_set_window(agz_engine* e, int64_t max_entries) {
+  return guard(e, [&](agz::Engine& E) { E.replay_set_window(max_entries); });
+}
+int64_t agz_replay_live_positions(agz_engine* e) { return (e && e->impl) ? e->impl->replay_live_positions() : -1; }
+agz_status agz_replay_sample(agz_engine* e, int32_t B, uint64_t call, int32_t sym_mode, float* feats, float* pi, float* z,
+                             int64_t* game_out, int32_t* ply_out) {
+  return guard(e, [&](agz::Engine& E) { E.replay_sample(B, call, sym_mode, feats, pi, z, game_out, ply_out); });
+}
+agz_status agz_selfplay_set_hold(agz_engine* e, int32_t on) {
+  return guard(e, [&](agz::Engine& E) { E.set_hold(on != 0); });
+}
+agz_status agz_selfplay_release(agz_engine* e) { return guard(e, [&](agz::Engine& E) { E.release(); }); }
+agz_status agz_device_alloc(agz_engine* e, int64_t bytes, void** out) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(out && bytes > 0, AGZ_BAD_ARGUMENT, "bad allocation request");
+    *out = nullptr;
+    AGZ_HIP(hipSetDevice(E.config().device));
+    AGZ_HIP(hipMalloc(out, (size_t)bytes));
+  });
+}
+agz_status agz_device_free(agz_engine* e, void* p) {
+  return guard(e, [&](agz::Engine& E) {
+    E.sync();
+    if (p) AGZ_HIP(hipFree(p));
+  });
+}
+
 agz_status agz_replay_batch_sym(agz_engine* e, const int64_t* game, const int32_t* ply, const int32_t* sym, int32_t B,
                                 float* feats, float* pi, float* z, int32_t out_is_device) {
   return guard(e, [&](agz::Engine& E) {

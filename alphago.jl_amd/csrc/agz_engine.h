@@ -49,10 +49,10 @@ class Engine {
   int64_t records_count();
   void record_header(int64_t k, agz_game_header* out);
   void record_game(int64_t k, int16_t* moves, float* pis, float* qs);
-  int64_t records_packed_size(int64_t first = 0);
+  int64_t records_packed_size(int64_t first = 0, int64_t last = -1);    // last = -1: records_count()
   void records_export_packed(void* dst, int64_t capacity, bool is_device);
   void records_clear();
-  int64_t pack_records_device(uint8_t* dst, int64_t capacity, int64_t* nbytes, int64_t first = 0);
+  int64_t pack_records_device(uint8_t* dst, int64_t capacity, int64_t* nbytes, int64_t first = 0, int64_t last = -1);
   // records [0, records_exchanged()) have been filed by agz_allgather_records since the last agz_records_clear
   int64_t records_exchanged() const { return rec_sent_; }
   void records_mark_exchanged(int64_t upto) { rec_sent_ = upto; }
@@ -61,6 +61,8 @@ class Engine {
   // device replay arena: finished games of every rank, packed, resident in HBM
   int64_t replay_ingest(const void* packed, int64_t nbytes, bool is_device);
   int64_t replay_ingest_local();
+  // records [first, first + count) of this engine's ring into the arena, device to device (agz_replay_ingest_records)
+  int64_t replay_ingest_records(int64_t first, int64_t count);
   int64_t replay_ingest_gathered(const void* buf, bool is_device, size_t nbytes, const std::vector<int64_t>& coff,
                                  const std::vector<int64_t>& cbytes, const std::vector<int64_t>& cnrec);
   int64_t replay_ingest_chunks(const uint8_t* dbuf, const std::vector<int64_t>& coff,
@@ -72,6 +74,12 @@ class Engine {
   void replay_game(int64_t k, int16_t* moves, float* pis, float* qs);
   void replay_trim(int64_t max_positions);
   void replay_clear();
+  // the sampling window of train(): the newest max_entries entries stay live (agz_replay_set_window)
+  void replay_set_window(int64_t max_entries);
+  int64_t replay_live_positions() const { return rp_positions_ - rp_cum_[(size_t)rp_first_game_] - rp_first_ply_; }
+  // get_replay_batch without the host: B distinct live entries drawn on the device (agz_replay_sample)
+  void replay_sample(int B, uint64_t call, int sym_mode, float* feats, float* pi, float* z, int64_t* game_out,
+                     int32_t* ply_out);
   // sym != NULL: sample b under the board symmetry T_sym[b] (agz_replay_batch_sym)
   void replay_batch(const int64_t* game, const int32_t* ply, int B, float* feats, float* pi, float* z,
                     bool out_is_device, const int32_t* sym = nullptr);
@@ -93,6 +101,9 @@ class Engine {
   void net_forward_features_sym(const float* feats, const int32_t* sym, int B, float* pi_out, float* v_out);
   // board symmetry of the engine's own evaluations (agz_selfplay_set_symmetry): AGZ_SYMMETRY_NONE, 0..7, RANDOM
   void set_symmetry(int mode);
+  // finished-slot hold of train() (agz_selfplay_set_hold / agz_selfplay_release)
+  void set_hold(bool on);
+  void release();
   void features(const int8_t* boards, const int8_t* deltas, const int32_t* ndeltas, const int8_t* to_play,
                 int B, float* out);
   float time_forward(int B, int iters);
@@ -134,6 +145,7 @@ class Engine {
 
  private:
   void replay_reserve(size_t bytes);
+  void replay_drop_front(size_t drop);
   void upload_view_outputs();
   void fill_synthetic_inputs(int B);
   void check_game(int g) const;
@@ -189,6 +201,16 @@ class Engine {
   int64_t rp_positions_ = 0;
   std::vector<int64_t> rp_off_;
   std::vector<agz_game_header> rp_hdr_;
+  std::vector<int64_t> rp_cum_{0};  // [count + 1]: positions of the games before game k
+  int64_t rp_first_game_ = 0;       // the window (agz_replay_set_window): entries before ply rp_first_ply_ of game
+  int64_t rp_first_ply_ = 0;        // rp_first_game_ are dead
+  DevBuf<int64_t> d_rp_cum_, d_rp_off_;   // device copies of rp_cum_ / rp_off_ for the sampler
+  int64_t rp_dev_n_ = 0;            // games whose rp_cum_ / rp_off_ entries are on the device
+  DevBuf<int64_t> smp_off_, smp_game_;
+  DevBuf<int32_t> smp_ply_, smp_sym_;
+  DevBuf<int8_t> smp_boards_;
+  DevBuf<float> smp_f_, smp_p_;
+  DevBuf<int32_t> hold_rel_;        // View::released
   int64_t rec_sent_ = 0;
   bool stepped_ = false;           // a step has run since the last start(): agz_debug_set_stagger is refused
 };

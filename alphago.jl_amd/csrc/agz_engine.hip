@@ -448,6 +448,75 @@ __global__ __launch_bounds__(kWave) void k_replay_arena_batch(View V, const uint
   if (z_out && w.leader()) z_out[b] = (float)h.result;
 }
 
+// agz_selfplay_release: every slot parked in G_IDLE may claim its next game at the next k_pre
+__global__ void k_release(View V) {
+  const int g = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (g < V.games && V.gs[g].phase == G_IDLE) V.released[g] = 1;
+}
+
+// agz_replay_sample, the draw: B distinct entries of the window [0, L) by Floyd's algorithm -- for b = 0..B-1 with
+// j = L - B + b: t_b = agz_index(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_SAMPLE, j), j + 1); sample b is t_b unless
+// t_b is already taken by a sample before it, then j.  All t_b are drawn at once; "t_b is taken" is
+//   dup(b)  -- some b' < b drew the same t (the first of them took it, or t was taken before that one), or
+//   t_b = j' = L - B + b' for a b' < b that fell back to j' itself (b' collided),
+// and b' < b: the second case is a chain through strictly smaller b that each thread follows on its own.  dup is the
+// first-drawer test of an LDS hash table (atomicCAS on the key, atomicMin on the drawer).  Each entry e of the window is
+// then mapped to (game, ply) by a binary search for the last k with cum[k] <= first + e over the arena's position prefix.
+constexpr int kSampleMax = 2048, kSampleHash = 4096, kSampleThreads = 1024;
+__global__ __launch_bounds__(kSampleThreads) void k_replay_sample(uint64_t seed, uint64_t call, int B, int64_t L,
+                                                                  int64_t first, const int64_t* cum, const int64_t* goff,
+                                                                  int64_t ngames, int sym_mode, int64_t* rec_off,
+                                                                  int32_t* ply, int32_t* sym, int64_t* game_out,
+                                                                  int32_t* ply_out) {
+  __shared__ int32_t s_t[kSampleMax];
+  __shared__ int32_t s_dup[kSampleMax];
+  __shared__ int32_t s_key[kSampleHash];
+  __shared__ int32_t s_min[kSampleHash];
+  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  const int64_t j0 = L - B;
+  for (int h = tid; h < kSampleHash; h += nt) { s_key[h] = -1; s_min[h] = 0x7fffffff; }
+  __syncthreads();
+  for (int b = tid; b < B; b += nt) {
+    const uint64_t j = (uint64_t)(j0 + b);
+    const int32_t t = (int32_t)agz_index(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_SAMPLE, j), (uint32_t)(j + 1));
+    s_t[b] = t;
+    uint32_t h = ((uint32_t)t * 0x9E3779B1u) >> (32 - 12);       // kSampleHash = 2^12 slots, at most half of them used
+    for (;;) {
+      const int32_t k = atomicCAS(&s_key[h], -1, t);
+      if (k == -1 || k == t) break;
+      h = (h + 1) & (kSampleHash - 1);
+    }
+    atomicMin(&s_min[h], b);
+    s_dup[b] = (int32_t)h;                                       // the slot, until every drawer is in
+  }
+  __syncthreads();
+  for (int b = tid; b < B; b += nt) s_dup[b] = s_min[s_dup[b]] < b;
+  __syncthreads();
+  for (int b = tid; b < B; b += nt) {
+    bool taken = false;
+    for (int x = b;;) {
+      if (s_dup[x]) { taken = true; break; }
+      const int64_t tx = s_t[x];
+      if (tx >= j0 && tx - j0 < x) x = (int)(tx - j0); else break;
+    }
+    const int64_t a = first + (taken ? j0 + b : (int64_t)s_t[b]);
+    int64_t lo = 0, hi = ngames;                                  // cum[lo] <= a < cum[hi]
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (cum[mid] <= a) lo = mid; else hi = mid;
+    }
+    const int32_t p = (int32_t)(a - cum[lo]);
+    rec_off[b] = goff[lo];
+    ply[b] = p;
+    if (sym)
+      sym[b] = sym_mode == AGZ_SYMMETRY_RANDOM
+                   ? (int32_t)agz_index(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_SYM, (uint64_t)b), 8u)
+                   : sym_mode;
+    if (game_out) game_out[b] = lo;
+    if (ply_out) ply_out[b] = p;
+  }
+}
+
 __global__ void k_debug_draws(uint64_t seed, uint64_t game, uint32_t move, int n, double alpha, double* out) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a < n) out[a] = agz_dirichlet_gamma(seed, game, move, (uint32_t)a, alpha);
@@ -570,6 +639,7 @@ void Engine::start(int64_t total_games) {
   rec_sent_ = 0;
   abandoned_ = 0;
   stepped_ = false;
+  if (hold_rel_.p) hold_rel_.zero(stream_);     // with the hold on, the fresh slots wait for a first release
   AGZ_HIP(hipMemsetAsync(V_.counters, 0, sizeof(unsigned long long) * CT_COUNT, stream_));
   AGZ_HIP(hipMemsetAsync(V_.ar_hdr, 0, sizeof(int32_t) * 5 * (V_.games / 2 + 1), stream_));
   std::vector<GameState> gs(V_.games);
@@ -988,8 +1058,8 @@ void Engine::record_game(int64_t k, int16_t* moves, float* pis, float* qs) {
 static size_t packed_record_bytes(const View& V, int nm) { return packed_bytes(V.A, nm); }
 
 // bytes of the packed form of records [first, count)
-int64_t Engine::records_packed_size(int64_t first) {
-  const int64_t n = records_count() - first;
+int64_t Engine::records_packed_size(int64_t first, int64_t last) {
+  const int64_t n = (last < 0 ? records_count() : last) - first;
   if (n <= 0) return 0;
   std::vector<agz_game_header> h((size_t)n);
   AGZ_HIP(hipMemcpy(h.data(), V_.fin_hdr + first, sizeof(agz_game_header) * (size_t)n, hipMemcpyDeviceToHost));
@@ -1000,8 +1070,8 @@ int64_t Engine::records_packed_size(int64_t first) {
 
 // pack the finished records [first, count) into `dst` (device memory, >= records_packed_size(first) bytes): one D2H
 // of the headers to lay the records out, one kernel to move them.  Returns the number of records packed.
-int64_t Engine::pack_records_device(uint8_t* dst, int64_t capacity, int64_t* nbytes, int64_t first) {
-  const int64_t n = records_count() - first;
+int64_t Engine::pack_records_device(uint8_t* dst, int64_t capacity, int64_t* nbytes, int64_t first, int64_t last) {
+  const int64_t n = (last < 0 ? records_count() : last) - first;
   *nbytes = 0;
   if (n <= 0) return 0;
   std::vector<agz_game_header> h((size_t)n);
@@ -1106,6 +1176,7 @@ int64_t Engine::replay_ingest_chunks(const uint8_t* dbuf, const std::vector<int6
       rp_off_.push_back((int64_t)rp_used_ + off[first[c] + i] - coff[c]);
       rp_hdr_.push_back(hdr[first[c] + i]);
       rp_positions_ += hdr[first[c] + i].num_moves;
+      rp_cum_.push_back(rp_positions_);
     }
     added += found[c];
     rp_used_ += (size_t)cbytes[c];
@@ -1151,6 +1222,20 @@ int64_t Engine::replay_ingest_local() {
   return added;
 }
 
+// records [first, first + count) of the ring, device to device; the exchange watermark (rec_sent_) does not move
+int64_t Engine::replay_ingest_records(int64_t first, int64_t count) {
+  const int64_t have = records_count();
+  AGZ_REQUIRE(first >= 0 && count >= 0 && first + count <= have, AGZ_BAD_ARGUMENT,
+              "records %lld..%lld: the ring holds %lld", (long long)first, (long long)(first + count), (long long)have);
+  AGZ_REQUIRE(have <= V_.fin_cap, AGZ_BAD_ARGUMENT, "the record ring has wrapped (record_capacity_games): records lost");
+  if (count == 0) return 0;
+  const int64_t need = records_packed_size(first, first + count);
+  s_pack_.ensure((size_t)need);
+  int64_t nb = 0;
+  const int64_t n = pack_records_device(s_pack_.p, need, &nb, first, first + count);
+  return replay_ingest_chunks(s_pack_.p, {0}, {nb}, {n});
+}
+
 void Engine::replay_header(int64_t k, agz_game_header* out) const {
   AGZ_REQUIRE(k >= 0 && k < (int64_t)rp_hdr_.size(), AGZ_BAD_ARGUMENT, "replay game %lld out of range", (long long)k);
   *out = rp_hdr_[(size_t)k];
@@ -1177,7 +1262,13 @@ void Engine::replay_trim(int64_t max_positions) {
   while (drop < rp_hdr_.size() && pos > max_positions) pos -= rp_hdr_[drop++].num_moves;
   if (drop == 0) return;
   if (drop == rp_hdr_.size()) { replay_clear(); return; }
+  replay_drop_front(drop);
+}
+
+// forget the oldest `drop` games (0 < drop < count): one copy of the rest into a fresh buffer
+void Engine::replay_drop_front(size_t drop) {
   const size_t cut = (size_t)rp_off_[drop], keep = rp_used_ - cut;
+  const int64_t pos = rp_positions_ - rp_cum_[drop];
   DevBuf<uint8_t> nb;
   nb.alloc(std::max(keep, (size_t)1 << 20));
   AGZ_HIP(hipMemcpyAsync(nb.p, rp_buf_.p + cut, keep, hipMemcpyDeviceToDevice, stream_));
@@ -1187,15 +1278,105 @@ void Engine::replay_trim(int64_t max_positions) {
   rp_off_.erase(rp_off_.begin(), rp_off_.begin() + drop);
   rp_hdr_.erase(rp_hdr_.begin(), rp_hdr_.begin() + drop);
   for (auto& o : rp_off_) o -= (int64_t)cut;
+  const int64_t c0 = rp_cum_[drop];
+  rp_cum_.erase(rp_cum_.begin(), rp_cum_.begin() + drop);
+  for (auto& c : rp_cum_) c -= c0;
   rp_used_ = keep;
   rp_positions_ = pos;
+  if (rp_first_game_ >= (int64_t)drop) {
+    rp_first_game_ -= (int64_t)drop;
+  } else {
+    rp_first_game_ = 0;
+    rp_first_ply_ = 0;
+  }
+  rp_dev_n_ = 0;
 }
 
 void Engine::replay_clear() {
   rp_off_.clear();
   rp_hdr_.clear();
+  rp_cum_.assign(1, 0);
   rp_used_ = 0;
   rp_positions_ = 0;
+  rp_first_game_ = 0;
+  rp_first_ply_ = 0;
+  rp_dev_n_ = 0;
+}
+
+// the window of train() (shrink, train.jl:52, per entry): entries before the newest max_entries are dead; the window's
+// start never moves back.  Dead games are dropped physically only once they hold more than half of the arena's bytes,
+// so the copy is amortised over many calls.  max_entries < 0: every entry live again (nothing dropped comes back).
+void Engine::replay_set_window(int64_t max_entries) {
+  if (max_entries < 0) { rp_first_game_ = 0; rp_first_ply_ = 0; return; }
+  const int64_t cur = rp_cum_[(size_t)rp_first_game_] + rp_first_ply_;
+  const int64_t first = std::max(cur, rp_positions_ - max_entries);
+  int64_t k = rp_first_game_;
+  const int64_t n = (int64_t)rp_hdr_.size();
+  while (k < n && rp_cum_[(size_t)k + 1] <= first) ++k;
+  rp_first_game_ = k;
+  rp_first_ply_ = first - rp_cum_[(size_t)k];
+  if (k == n) {                     // nothing live
+    replay_clear();
+    return;
+  }
+  if (k > 0 && (size_t)rp_off_[(size_t)k] > rp_used_ / 2) replay_drop_front((size_t)k);
+}
+
+// get_replay_batch (train.jl:4-12) with the draw on the device: k_replay_sample picks B distinct live entries and maps
+// them to (record offset, ply), k_replay_arena_batch (and k_sym_rows) turn them into the batch.  No host copy of the
+// samples; only the arena's index (rp_cum_ / rp_off_) is uploaded, and only what changed since the last call.
+void Engine::replay_sample(int B, uint64_t call, int sym_mode, float* feats, float* pi, float* z, int64_t* game_out,
+                           int32_t* ply_out) {
+  const int64_t L = replay_live_positions();
+  AGZ_REQUIRE(B >= 1 && B <= kSampleMax, AGZ_BAD_ARGUMENT, "batch %d: 1..%d samples", B, kSampleMax);
+  AGZ_REQUIRE(B <= L, AGZ_BAD_ARGUMENT, "batch %d from a window of %lld entries (sampling without replacement)", B,
+              (long long)L);
+  AGZ_REQUIRE(L <= 0x7fffffffLL, AGZ_BAD_ARGUMENT, "window of %lld entries: at most 2^31 - 1", (long long)L);
+  AGZ_REQUIRE(sym_mode >= AGZ_SYMMETRY_NONE && sym_mode <= AGZ_SYMMETRY_RANDOM, AGZ_BAD_ARGUMENT,
+              "sym_mode %d: -1 (none), 0..7 (fixed T_s) or 8 (drawn)", sym_mode);
+  AGZ_REQUIRE(feats, AGZ_BAD_ARGUMENT, "feats is NULL");
+  const int64_t n = (int64_t)rp_hdr_.size();
+  if (d_rp_cum_.n < (size_t)n + 1 || d_rp_off_.n < (size_t)n) {
+    const size_t cap = std::max<size_t>(2 * (size_t)n + 1, 1024);
+    d_rp_cum_.alloc(cap);
+    d_rp_off_.alloc(cap);
+    rp_dev_n_ = 0;
+  }
+  if (rp_dev_n_ < n) {
+    AGZ_HIP(hipMemcpyAsync(d_rp_off_.p + rp_dev_n_, rp_off_.data() + rp_dev_n_, sizeof(int64_t) * (size_t)(n - rp_dev_n_),
+                           hipMemcpyHostToDevice, stream_));
+    AGZ_HIP(hipMemcpyAsync(d_rp_cum_.p + rp_dev_n_, rp_cum_.data() + rp_dev_n_,
+                           sizeof(int64_t) * (size_t)(n + 1 - rp_dev_n_), hipMemcpyHostToDevice, stream_));
+    AGZ_HIP(hipStreamSynchronize(stream_));      // the host vectors may move with the next ingest
+    rp_dev_n_ = n;
+  }
+  const size_t per = (size_t)17 * V_.P;
+  smp_off_.ensure(kSampleMax);
+  smp_ply_.ensure(kSampleMax);
+  smp_sym_.ensure(kSampleMax);
+  smp_boards_.ensure((size_t)B * 8 * V_.PP);
+  const bool with_sym = sym_mode != AGZ_SYMMETRY_NONE;
+  hipLaunchKernelGGL(k_replay_sample, dim3(1), dim3(kSampleThreads), 0, stream_, (uint64_t)V_.seed, call, B, L,
+                     rp_cum_[(size_t)rp_first_game_] + rp_first_ply_, (const int64_t*)d_rp_cum_.p,
+                     (const int64_t*)d_rp_off_.p, n, sym_mode, smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr,
+                     game_out, ply_out);
+  AGZ_HIP(hipGetLastError());
+  if (with_sym) {
+    smp_f_.ensure(per * (size_t)B);
+    smp_p_.ensure((size_t)B * V_.A);
+    hipLaunchKernelGGL(k_replay_arena_batch, dim3(B), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
+                       (const int64_t*)smp_off_.p, (const int32_t*)smp_ply_.p, smp_boards_.p, smp_f_.p,
+                       pi ? smp_p_.p : nullptr, z);
+    hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)smp_f_.p, feats,
+                       (const int32_t*)smp_sym_.p, V_.N, 17, 0, 0);
+    if (pi)
+      hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)smp_p_.p, pi,
+                         (const int32_t*)smp_sym_.p, V_.N, 1, 1, 0);
+  } else {
+    hipLaunchKernelGGL(k_replay_arena_batch, dim3(B), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
+                       (const int64_t*)smp_off_.p, (const int32_t*)smp_ply_.p, smp_boards_.p, feats, pi, z);
+  }
+  AGZ_HIP(hipGetLastError());
 }
 
 void Engine::train_step(const float* feats, const float* pi, const float* z, int B, bool is_device, float eta, float rho,
@@ -1451,6 +1632,21 @@ void Engine::net_forward_features_sym(const float* feats, const int32_t* sym, in
   AGZ_HIP(hipMemcpyAsync(v_out, s_f32b_.p + (size_t)B * V_.A, sizeof(float) * B, hipMemcpyDeviceToHost, stream_));
   AGZ_HIP(hipStreamSynchronize(stream_));
   net().check_async_error();
+}
+
+void Engine::set_hold(bool on) {
+  AGZ_REQUIRE(!V_.arena, AGZ_BAD_ARGUMENT, "the hold is for self-play slots; arena slots come in pairs");
+  if (on && !hold_rel_.p) hold_rel_.alloc((size_t)V_.games);
+  if (hold_rel_.p) hold_rel_.zero(stream_);     // pending releases go: a parked slot waits for the next release
+  V_.hold = on ? 1 : 0;                         // by value into the kernels: effective from the next step
+  V_.released = hold_rel_.p;
+  AGZ_HIP(hipStreamSynchronize(stream_));
+}
+
+void Engine::release() {
+  if (!V_.hold) return;
+  hipLaunchKernelGGL(k_release, dim3((V_.games + 255) / 256), dim3(256), 0, stream_, V_);
+  AGZ_HIP(hipGetLastError());
 }
 
 void Engine::set_symmetry(int mode) {

@@ -1549,6 +1549,14 @@ AGZ_FN void game_pre(W& w, const View& V, Scratch& S, int g) {
   if (G.phase == G_IDLE) {
     if (w.leader()) G.nleaves = 0;
     w.sync();
+    if (V.hold) {
+      // parked until the host releases the slot: train() trains between its games' finish and the next game's start
+      const int32_t rel = V.released[g];
+      w.sync();
+      if (!rel) return;
+      if (w.leader()) V.released[g] = 0;
+      w.sync();
+    }
     // claim the next global game index; retire the slot when the quota is used up
     const long long idx = (long long)w.fetch_add(&V.counters[CT_CLAIMED], 1ull);
     if (V.total_games > 0 && idx >= V.total_games) {

@@ -156,6 +156,10 @@ struct View {
   int32_t review;
   const int16_t* rv_moves;            // [rv_off[an_count]]: the recorded moves, game after game
   const int64_t* rv_off;              // [an_count + 1]: game j's moves and rows are rv_off[j] .. rv_off[j+1]-1
+  // finished-slot hold (agz_selfplay_set_hold; zero = off, the View{} of the host simulator): a slot in G_IDLE claims its
+  // next game only when agz_selfplay_release has set its flag, and clears the flag as it claims
+  int32_t hold;
+  int32_t* released;                  // [games]
 };
 
 }  // namespace agz

@@ -20,7 +20,7 @@ module AlphaGoMI
 using Printf: @sprintf
 using Random
 
-export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, extract_data, initialize_game!,
+export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, train, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
        SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review,
@@ -1077,6 +1077,80 @@ function train_step!(e::Engine, feats::Matrix{Float32}, pi::Matrix{Float32}, z::
                  (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Float32, Float32, Ptr{Float32}),
                  e.handle, feats, pi, z, length(z), 0, eta, rho, losses))
   Tuple(losses)
+end
+
+# train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model, start_training_after)
+# (src/train.jl:38-92) with `slots` games in flight (DESIGN.md §5e; the Python mirror is api.train).  One engine plays,
+# keeps the arena and trains; per step: agz_selfplay_step(1), one read of the finished games, and for each in game-id
+# order: push_data (agz_replay_ingest_records, train.jl:60-61), shrink (agz_replay_set_window, :63-65), then _train on a
+# device-drawn get_replay_batch (agz_replay_sample with draw key (seed, i), :67-70) in 32-position agz_train_step
+# minibatches, Momentum(2f-2).  The hold keeps finished slots parked until agz_selfplay_release, so every game starts on
+# the weights the games finished before it left; slots = 1 is the reference's loop.
+function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, batch_size::Int = 32, epochs = 1,
+               ckp_freq::Int = 1000, readouts::Int = 800, tower_height::Int = 19, model = nothing,
+               start_training_after = 50000, slots::Union{Nothing, Int} = nothing, seed = 0, game_id_base = 0,
+               augment::Bool = false, callback::Function = println)
+  cur_nn = model === nothing ? NeuralNet(env; tower_height = tower_height) : model                       # train.jl:43
+  S = slots === nothing ? min(num_games, 1024) : slots
+  e = Engine(board_size = env.N, tower_height = cur_nn.tower_height, games = S, num_readouts = readouts, seed = seed,
+             game_id_base = game_id_base, record_capacity_games = S + 8)
+  copy_weights!(e, cur_nn.engine)
+  opt = Momentum(2f-2)                                                                                     # train.jl:54
+  P, A = env.N * env.N, env.action_space
+  bufs = [Ref{Ptr{Cvoid}}(C_NULL) for _ in 1:3]
+  for (r, n) in zip(bufs, (17 * P * batch_size, A * batch_size, batch_size))
+    check(e, ccall((:agz_device_alloc, libagz), Int32, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), e.handle, 4 * n, r))
+  end
+  feats, pi, z = (r[] for r in bufs)
+  cuts = vcat(collect(0:32:batch_size-1), batch_size)
+  length(cuts) > 2 && cuts[end] - cuts[end-1] == 1 && deleteat!(cuts, length(cuts) - 1)   # BatchNorm needs two rows
+  check(e, ccall((:agz_selfplay_set_hold, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 1))
+  check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, num_games))
+  check(e, ccall((:agz_selfplay_release, libagz), Int32, (Ptr{Cvoid},), e.handle))
+  i = 0
+  while i < num_games
+    check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 1))
+    n = ccall((:agz_records_count, libagz), Int64, (Ptr{Cvoid},), e.handle)
+    n == 0 && continue
+    heads = Tuple{AgzGameHeader, Int64}[]
+    for k in 0:n-1
+      h = Ref{AgzGameHeader}()
+      check(e, ccall((:agz_records_header, libagz), Int32, (Ptr{Cvoid}, Int64, Ref{AgzGameHeader}), e.handle, k, h))
+      push!(heads, (h[], k))
+    end
+    sort!(heads, by = hk -> hk[1].game_id)
+    for (h, k) in heads
+      check(e, ccall((:agz_replay_ingest_records, libagz), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}),
+                     e.handle, k, 1, C_NULL))                                                          # train.jl:60-61
+      check(e, ccall((:agz_replay_set_window, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, memory_size))   # :63-65
+      i += 1
+      if ccall((:agz_replay_live_positions, libagz), Int64, (Ptr{Cvoid},), e.handle) >= start_training_after   # :67
+        check(e, ccall((:agz_replay_sample, libagz), Int32,
+                       (Ptr{Cvoid}, Int32, UInt64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                       e.handle, batch_size, i, augment ? 8 : -1, feats, pi, z, C_NULL, C_NULL))        # :68-69
+        loss = 0f0
+        losses = zeros(Float32, 4)
+        for _ in 1:epochs, j in 1:length(cuts)-1                                                       # :70
+          lo, B = cuts[j], cuts[j+1] - cuts[j]
+          check(e, ccall((:agz_train_step, libagz), Int32,
+                         (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Float32, Float32, Ptr{Float32}),
+                         e.handle, Ptr{Float32}(feats) + 4 * 17 * P * lo, Ptr{Float32}(pi) + 4 * A * lo,
+                         Ptr{Float32}(z) + 4 * lo, B, 1, opt.eta, opt.rho, losses))
+          loss += losses[1]
+        end
+        rs = h.was_resign != 0 ? (h.result == BLACK ? "B+R" : "W+R") : result_string(h.final_score)
+        callback("Episode $i over. Loss: $(loss / epochs). Winner: $rs. Moves: $(h.num_moves).")        # :71-73
+      end
+      # (checkpoints, train.jl:86-89: the Python mirror writes them; this stub has no BSON writer)
+    end
+    check(e, ccall((:agz_records_clear, libagz), Int32, (Ptr{Cvoid},), e.handle))
+    check(e, ccall((:agz_selfplay_release, libagz), Int32, (Ptr{Cvoid},), e.handle))
+  end
+  copy_weights!(cur_nn.engine, e)
+  for r in bufs
+    check(e, ccall((:agz_device_free, libagz), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), e.handle, r[]))
+  end
+  cur_nn                                                                                                    # :91
 end
 
 end # module

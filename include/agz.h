@@ -232,6 +232,14 @@ agz_status agz_selfplay_step(agz_engine* e, int32_t nsteps);          /* asynchr
 #define AGZ_SYMMETRY_NONE (-1)
 #define AGZ_SYMMETRY_RANDOM 8
 agz_status agz_selfplay_set_symmetry(agz_engine* e, int32_t mode);
+/* The hold of train() (ours; train.jl:56-57 plays game i + 1 on the weights _train left after game i).  With the hold
+ * on, a slot that finishes a game records it as usual and parks in G_IDLE instead of taking its next game in the same
+ * step; agz_selfplay_release lets every slot parked at that moment claim its next game id (game_id_base + k * stride,
+ * the usual rule) at the next step, so a host that trains between the two calls starts every later game on the trained
+ * weights.  agz_selfplay_start's fresh slots wait for a first release too.  set_hold clears pending releases; it is
+ * refused in arena_mode.  Hold off (the default): the step is unchanged. */
+agz_status agz_selfplay_set_hold(agz_engine* e, int32_t on);
+agz_status agz_selfplay_release(agz_engine* e);                     /* asynchronous */
 typedef struct {
   int64_t steps;               /* tree_search! rounds executed                          */
   int64_t positions;           /* self-play moves played (= searches_pi entries)        */
@@ -342,6 +350,33 @@ agz_status agz_replay_batch(agz_engine* e, const int64_t* game, const int32_t* p
  * training samples; device outputs feed agz_train_step directly. */
 agz_status agz_replay_batch_sym(agz_engine* e, const int64_t* game, const int32_t* ply, const int32_t* sym, int32_t B,
                                 float* feats, float* pi, float* z, int32_t out_is_device);
+/* push_data (train.jl:51,60-61) for this engine's own records k = first .. first+count-1 (agz_records_header's
+ * numbering), device to device, in that order; the agz_allgather_records watermark does not move.  added_out may be
+ * NULL.  AGZ_BAD_ARGUMENT when the range is outside the ring or the ring has wrapped. */
+agz_status agz_replay_ingest_records(agz_engine* e, int64_t first, int64_t count, int64_t* added_out);
+/* shrink (train.jl:52-53: keep exactly the last memory_size entries) as a sampling window: the entries before the newest
+ * max_entries are dead -- also part of a game -- and the window's start never moves back (max_entries < 0: every entry
+ * still in the arena live again).  Dead whole games are dropped physically only when they hold more than half of the
+ * arena's bytes, so the copy is amortised.  agz_replay_clear resets the window; agz_replay_trim keeps the part of it
+ * that lies in the games it keeps (all of them live when the window's start was dropped); agz_replay_count,
+ * _positions, _header, _game, _batch keep counting every game still in the arena. */
+agz_status agz_replay_set_window(agz_engine* e, int64_t max_entries);
+int64_t agz_replay_live_positions(agz_engine* e);        /* entries in the window = length(pos_buffer) after shrink */
+/* get_replay_batch (train.jl:4-12: sample(1:length(pos_buffer), B, replace=false)) drawn and built on the device.  With
+ * L = agz_replay_live_positions and window entry e = 0..L-1 (oldest first), sample b = 0..B-1 is Floyd's algorithm:
+ * j = L - B + b, t = agz_index(agz_draw_u64(agz_config.seed, call, 0, AGZ_SITE_REPLAY_SAMPLE, j), j + 1); sample b is
+ * entry t unless an earlier sample took t, then entry j.  Entry e is ply (first live ply + e) counted through the arena's
+ * games.  sym_mode -1: as agz_replay_batch; 0..7: every sample under T_sym_mode; AGZ_SYMMETRY_RANDOM (8): sample b under
+ * T_s, s = agz_index(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_SYM, b), 8), as agz_replay_batch_sym.  feats float[B]
+ * [N*N*17], pi float[B][A], z float[B], game_out int64[B] (arena game index), ply_out int32[B]: DEVICE pointers; pi, z,
+ * game_out, ply_out may be NULL.  1 <= B <= min(L, 2048).  Asynchronous on the engine's stream (agz_train_step with
+ * inputs_are_device reads the outputs in order). */
+agz_status agz_replay_sample(agz_engine* e, int32_t B, uint64_t call, int32_t sym_mode, float* feats, float* pi, float* z,
+                             int64_t* game_out, int32_t* ply_out);
+/* device memory on the engine's GPU for a host without its own allocator (the Julia stub's train): agz_replay_sample's
+ * outputs, agz_train_step's device inputs.  Freed by agz_device_free (after the engine's stream has used it). */
+agz_status agz_device_alloc(agz_engine* e, int64_t bytes, void** out);
+agz_status agz_device_free(agz_engine* e, void* p);
 
 /* ---------------------------------------------------------------- training step --------- */
 /* One optimisation step of `_train` (neural_net.jl:75-101; optimiser Momentum(2f-2), train.jl:54; call

@@ -50,6 +50,11 @@
                                 * idx = 0-based ordinal of the evaluation among those the
                                 * game has sent to the network (terminal leaves do not
                                 * count); s = agz_index(draw, 8)                    */
+#define AGZ_SITE_REPLAY_SAMPLE 9u  /* agz_replay_sample (Floyd): game = call, move = 0,
+                                    * idx = j, the step's upper end; entry
+                                    * agz_index(draw, j + 1)                        */
+#define AGZ_SITE_REPLAY_SYM 10u    /* agz_replay_sample's drawn symmetry: game = call,
+                                    * move = 0, idx = sample b; s = agz_index(draw, 8) */
 
 static inline AGZ_HD uint64_t agz_mix64(uint64_t z) {
   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
