@@ -2,6 +2,7 @@
 // gfx950 kernels (inference only).  Topology: /root/reference/src/neural_net.jl:13-33,57-73,
 // /root/reference/src/resnet.jl:11-32.  See DESIGN.md "Network kernels".
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <functional>
 #include <memory>
@@ -26,7 +27,12 @@ struct DenseHost {
 };
 
 bool wino4_applies(int N);      // agz_wino4.hip (declared with the rest of its interface below)
-bool wino5_applies(int N);      // agz_wino5.hip
+bool wino_fusable(int N);       // agz_wino.hip
+
+// How the tower's layers run (Net::tower_form): the direct implicit GEMM, fp16 operands (agz_conv16.hip), Winograd
+// F(3x3,3x3) one launch per layer or as ONE persistent launch (agz_wino.hip), its five-pass form (agz_wino5.hip), or
+// F(4x4,3x3) (agz_wino4.hip)
+enum class TowerForm { Direct, F16, Wino3, Wino3Persistent, Wino5, Wino4 };
 
 class Net {
  public:
@@ -68,16 +74,14 @@ class Net {
   // exact-f32 arithmetic), 2 = Winograd F(3x3,3x3) on every board size (A/B runs), 0 = the direct implicit GEMM
   // 3 = 1 with the tower layers of small boards (whole-board tile blocks, N <= 12) on the five-pass 64 x 128 form of
   // F(3x3,3x3) (agz_wino5.hip) instead of k_wino_gemm4
-  void set_winograd(int mode) { winograd_ = mode != 0; wino_f33_only_ = mode == 2; wino5_ = mode == 3; }
-  bool use_wino5() const { return winograd_ && wino5_ && precision_ == 0 && tower_ > 0 && wino5_applies(N_); }
-  bool winograd() const { return winograd_; }
+  void set_winograd(int mode) { winograd_ = mode; }
+  bool winograd() const { return winograd_ != 0; }
   // The Winograd tower of a large batch as n independent layer chains (ranges of its tile blocks, cut at board boundaries)
   // on n streams: the hardware scheduler interleaves their workgroups, the CUs stop marching through K loops and store
   // bursts in lockstep (-5 % per forward at 19x19 / 2048 positions, -1.6 % per step at 9x9 / 8192; outputs are
   // bit-identical: same kernels, same rows).  Applies to whole-board F(3x3,3x3) blocks and to the F(4x4,3x3) tower.
   void set_tower_streams(int n) { tower_streams_ = n < 1 ? 1 : n > kMaxTowerStreams ? kMaxTowerStreams : n; }
   int tower_streams() const { return tower_streams_; }
-  bool use_wino4() const { return winograd_ && !wino_f33_only_ && precision_ == 0 && tower_ > 0 && wino4_applies(N_); }
   // the f32 Winograd tower as ONE persistent launch (k_wino_tower) instead of one launch per layer, where it applies
   // (whole-board tile blocks, 256 CUs with 32 resident workgroups per XCD); same arithmetic, same bits.  Off by
   // default: it needs 3.7 % fewer cycles and the clock comes down by as much (HISTORY.md 4f) -- same wall time.
@@ -91,6 +95,18 @@ class Net {
   // 2 = exact-f32 network with the Winograd operands carried as two f16 halves (agz_wino.hip, split form)
   void set_precision(int p) { precision_ = p; }
   int precision() const { return precision_; }
+  // The tower form these settings select -- the one place that decides it.  The fp16 tower takes any Winograd mode (which
+  // only picks its stem); F(4x4,3x3) and the five-pass form need exact f32.  Wino3Persistent is what the settings ask for:
+  // forward() drops it to Wino3 where wino_tower_supported() says no (asked after the stem is enqueued: the first call per
+  // device launches a census kernel and synchronises).
+  TowerForm tower_form() const {
+    if (tower_ == 0) return TowerForm::Direct;
+    if (precision_ == 1) return TowerForm::F16;
+    if (winograd_ == 0) return TowerForm::Direct;
+    if (precision_ == 0 && winograd_ != 2 && wino4_applies(N_)) return TowerForm::Wino4;
+    if (precision_ == 0 && winograd_ == 3 && wino_fusable(N_)) return TowerForm::Wino5;
+    return tower_persistent_ && wino_fusable(N_) ? TowerForm::Wino3Persistent : TowerForm::Wino3;
+  }
 
   // what this board sustains on nothing but independent v_mfma_f32_32x32x2_f32 (one launch of ~10 ms after another for
   // `millis`, the median of the second half): the power-limited f32 MFMA rate bench.py quotes next to the nominal peak
@@ -114,6 +130,19 @@ class Net {
 
  private:
   void pack();
+  // forward() = stem -> tower (one of these, by form) -> heads
+  void stem(TowerForm form, const float* d_x32, const int* d_count, int bcap);
+  void direct_tower(const int* d_count, int bcap);
+  void f16_tower(const int* d_count, int bcap);
+  void wino_tower(TowerForm form, const int* d_count, int bcap);
+  void persistent_tower(const int* d_count, int bcap);
+  // where a Winograd tower layer reads and writes: V in, residual, y, the next layer's V (null: not wanted)
+  struct LayerIO { const float *vin, *res; float *y, *vout; };
+  LayerIO layer_io(int l, bool dense) const;
+  void wino_layer(TowerForm form, int l, const LayerIO& io, const int* d_count, int bcap, hipStream_t st, int part = 0,
+                  int parts = 1);
+  template <class Layer> void run_chains(int chains, const Layer& layer);
+  template <class Launch> void timed(int layers, const Launch& launch);
 
   int N_, P_, A_, tower_;
   hipStream_t stream_;
@@ -140,7 +169,7 @@ class Net {
   // workspace
   int bcap_ = 0;
   DevBuf<float> d_a_, d_b_, d_t_, d_vh_, d_ph_;
-  bool winograd_ = true, wino_f33_only_ = false, wino5_ = false;
+  int winograd_ = 1;                           // set_winograd's mode
   DevBuf<float> d_uwino5_;                     // five-pass F(3x3,3x3) weights (agz_wino5.hip), packed when first used
   bool packed5_ = false;
   DevBuf<float> d_uwino4_;                     // F(4x4,3x3) transformed weights (agz_wino4.hip), packed when first used
@@ -149,8 +178,6 @@ class Net {
   int tower_streams_ = 2;
   hipStream_t streamx_[kMaxTowerStreams - 1] = {nullptr, nullptr, nullptr};      // chains 1.. (chain 0 runs on stream_)
   hipEvent_t ev_fork_ = nullptr, ev_join_[kMaxTowerStreams - 1] = {nullptr, nullptr, nullptr};
-  bool fork_chains(int parts);                 // side streams wait for stream_; true if this tower is being timed
-  void join_chains(int parts, bool timed_tower);      // stream_ waits for the side streams
   DevBuf<float> d_uwino_s_, d_scale_s_;        // split form: weights as halves, scale x 1 / (operand scales)
   bool packed_split_ = false;
   DevBuf<float> d_uwino_, d_vimg_, d_vimg2_;   // transformed weights (stage images) / transformed activations (ping-pong)
@@ -166,7 +193,7 @@ class Net {
   std::vector<char> tower_layers_host_;      // what d_tower_layers_ holds
   int32_t* tower_err_ = nullptr;             // pinned host: the scheduler's error word of the previous forward
   // profiling
-  std::vector<int> prof_mult_;               // layers behind event pair i (1, or the whole tower for the persistent launch)
+  std::vector<int> prof_mult_;               // layers behind event pair i (1, or the whole tower: chained or persistent)
   bool prof_on_ = false;
   std::vector<hipEvent_t> prof_ev_;
   std::vector<int> prof_fwd_of_;
@@ -219,6 +246,22 @@ void wino_pack_weights(const ConvHost& c, float* out, int ns = kWinoStages);    
 void launch_wino_pack(const float* d_w, long wstride, int cin, int layers, float* d_out, int ns, bool split, hipStream_t s);
 size_t wino_weight_floats(int ns = kWinoStages);
 size_t wino_v_floats(int bcap, int T);
+long wino_blocks(int bcap, int T);           // tile blocks of a batch (64 rows; whole boards where they fit: 63 at 9x9)
+// The part-th of `parts` equal ranges [tb0, tb1) of `blocks` tile blocks (`pairs`: of whole block pairs).  Ranges that hold
+// whole boards depend on nothing outside them: they can run as independent layer chains on different streams (Net::forward).
+inline void wino_block_range(int blocks, int part, int parts, bool pairs, int& tb0, int& tb1) {
+  AGZ_REQUIRE(parts >= 1 && part >= 0 && part < parts, AGZ_BAD_ARGUMENT, "tile-block range %d of %d", part, parts);
+  int per = (blocks + parts - 1) / parts;
+  if (pairs) per = (per + 1) & ~1;
+  tb0 = std::min(blocks, part * per);
+  tb1 = part + 1 == parts ? blocks : std::min(blocks, tb0 + per);
+}
+// throws if a batch of `bcap` positions at NxN in `blocks` tile blocks of `rows` rows leaves 32-bit tile indices or
+// activation byte offsets
+inline void wino_check_32bit(long blocks, int rows, int bcap, int N) {
+  AGZ_REQUIRE((blocks + 1) * rows < (1L << 31) && (long)bcap * N * N * kC * 4 < (1L << 32), AGZ_BAD_ARGUMENT,
+              "batch of %d positions at %dx%d: tile index / activation byte offset exceeds 32 bits", bcap, N, N);
+}
 // x -> V (the 25 transformed planes as GEMM stage images); needed in front of the first Winograd layer, and
 // in front of every layer when the board's tiles do not pack into whole-board tile blocks (!wino_fusable)
 // fixup: dense tile blocks (!wino_fusable(N), e.g. 19x19) whose previous GEMM already emitted the V of every tile whose
@@ -246,7 +289,6 @@ float wino_split_descale();
 
 // Winograd F(3x3,3x3) tower layer in five one-row passes over a 64-tile x 128-cout workgroup tile (agz_wino5.hip): reads the
 // V images of agz_wino.hip's kernels, its own U image; whole-board tile blocks (N <= 12), exact f32
-bool wino5_applies(int N);
 void wino5_pack_weights(const ConvHost& c, float* out);                              // host restatement (test reference)
 void launch_wino5_pack(const float* d_w, long wstride, int layers, float* d_out, hipStream_t s);
 size_t wino5_weight_floats();

@@ -600,8 +600,9 @@ void Net::pack() {
   const size_t w0 = flux_offset(0, AGZ_K_WEIGHT);
   const size_t w1 = tower_ > 0 ? flux_offset(1, AGZ_K_WEIGHT) : 0;
   const long tstride = tower_ > 0 ? (long)(flux_offset(2, AGZ_K_WEIGHT) - w1) : 0;      // tower layers (2 per block) are equally spaced
+  const TowerForm form = tower_form();
   if (derived_dirty_) { packed4_ = packed5_ = packed16_ = packed_split_ = false; }
-  if (use_wino5() && !packed5_) {
+  if (form == TowerForm::Wino5 && !packed5_) {
     d_uwino5_.ensure(wino5_weight_floats() * 2 * tower_);
     launch_wino5_pack(F + w1, tstride, 2 * tower_, d_uwino5_.p, stream_);
     packed5_ = true;
@@ -613,12 +614,12 @@ void Net::pack() {
     launch_wino_pack(F + w0, 0, kCinStem, 1, d_ustem_s_.p, kWinoStemStages, true, stream_);
     packed_split_ = true;
   }
-  if (use_wino4() && !packed4_) {
+  if (form == TowerForm::Wino4 && !packed4_) {
     d_uwino4_.ensure(wino4_weight_floats() * 2 * tower_);
     launch_wino4_pack(F + w1, tstride, 2 * tower_, d_uwino4_.p, stream_);
     packed4_ = true;
   }
-  if (precision_ == 1 && tower_ > 0 && !packed16_) {
+  if (form == TowerForm::F16 && !packed16_) {
     d_wi16_.ensure(conv16_image_halves() * 2 * tower_);
     launch_conv16_pack(F + w1, tstride, 2 * tower_, d_wi16_.p, stream_);
     packed16_ = true;
@@ -689,14 +690,14 @@ long Net::debug_pack_diff(int which) {
       return bad;
     }
     case 2: {      // F(4x4,3x3) images
-      if (!use_wino4()) return 0;
+      if (tower_form() != TowerForm::Wino4) return 0;
       long bad = 0;
       std::vector<float> u(wino4_weight_floats());
       for (int l = 0; l < 2 * tower_; ++l) { wino4_pack_weights(tconv_[l], u.data()); bad += diff(d_uwino4_.p + u.size() * l, u.data(), u.size() * 4); }
       return bad;
     }
     case 3: {      // fp16 images (precision f16 selected)
-      if (precision_ != 1 || tower_ == 0) return 0;
+      if (tower_form() != TowerForm::F16) return 0;
       long bad = 0;
       std::vector<uint16_t> wi(conv16_image_halves());
       for (int l = 0; l < 2 * tower_; ++l) { conv16_pack_images(tconv_[l], wi.data()); bad += diff(d_wi16_.p + wi.size() * l, wi.data(), wi.size() * 2); }
@@ -718,7 +719,7 @@ long Net::debug_pack_diff(int which) {
       return bad + diff(d_scale_s_.p, sc.data(), sc.size() * 4);
     }
     case 6: {      // five-pass F(3x3,3x3) images (agz_net_set_winograd(3))
-      if (!use_wino5()) return 0;
+      if (tower_form() != TowerForm::Wino5) return 0;
       long bad = 0;
       std::vector<float> u(wino5_weight_floats());
       for (int l = 0; l < 2 * tower_; ++l) { wino5_pack_weights(tconv_[l], u.data()); bad += diff(d_uwino5_.p + u.size() * l, u.data(), u.size() * 4); }
@@ -810,45 +811,59 @@ void launch_conv3x3_direct_taps(const float* x, const float* wt, const float* on
   hipLaunchKernelGGL(k_sum_taps, dim3(g), dim3(256), 0, s, (const float*)part, stride, shift, y, d_count, N * N);
 }
 
-// Tower layer chains (agz_net_set_tower_streams): chain 0 runs on stream_, chains 1.. on streams of their own that wait for
-// everything enqueued so far (fork) and that stream_ waits for afterwards (join).  With more than one chain the layers
-// overlap, so the profile keeps ONE event pair around the whole tower (2 * tower layers).  Returns whether this tower is
-// being timed.
-static int tower_chunks() {
-#ifdef AGZ_TIMING_EXPERIMENTS
-  static const int n = getenv("AGZ_TOWER_CHUNKS") ? atoi(getenv("AGZ_TOWER_CHUNKS")) : 0;     // tools/chunks_sweep.sh
-  return n;
-#else
-  return 0;
-#endif
+// An event pair around launch() for bench.py's HIP-event roofline leg (agz_profile_conv_read), standing for `layers` tower
+// layers: 1 for a layer launched on its own, the whole tower when its layers overlap (chains) or share one launch (persistent)
+template <class Launch> void Net::timed(int layers, const Launch& launch) {
+  const bool p = prof_on_ && prof_n_ < kProfMax;
+  if (p) (void)hipEventRecord(prof_ev_[2 * prof_n_], stream_);
+  launch();
+  if (p) {
+    (void)hipEventRecord(prof_ev_[2 * prof_n_ + 1], stream_);
+    prof_mult_[prof_n_] = layers;
+    prof_fwd_of_[prof_n_++] = prof_fwd_;
+  }
 }
 
-bool Net::fork_chains(int parts) {
-  const bool pt = prof_on_ && prof_n_ < kProfMax;
-  if (parts <= 1) return pt;
+// Tower layer chains (agz_net_set_tower_streams): the tower of the part-th of `chains` ranges of tile blocks is a chain of
+// layers that depends on nothing outside its range.  Chain 0 runs on stream_, chains 1.. on streams of their own that wait
+// for everything enqueued so far (fork) and that stream_ waits for afterwards (join).  layer(l, part, stream) enqueues
+// tower layer l of chain `part`.
+template <class Layer> void Net::run_chains(int chains, const Layer& layer) {
+  const int nl = 2 * tower_;
+  if (chains == 1) {
+    for (int l = 0; l < nl; ++l) timed(1, [&] { layer(l, 0, stream_); });
+    return;
+  }
   if (!ev_fork_) AGZ_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-  for (int i = 0; i + 1 < parts; ++i)
+  for (int i = 0; i + 1 < chains; ++i)
     if (!streamx_[i]) {
       AGZ_HIP(hipStreamCreateWithFlags(&streamx_[i], hipStreamNonBlocking));
       AGZ_HIP(hipEventCreateWithFlags(&ev_join_[i], hipEventDisableTiming));
     }
-  if (pt) (void)hipEventRecord(prof_ev_[2 * prof_n_], stream_);
-  AGZ_HIP(hipEventRecord(ev_fork_, stream_));
-  for (int i = 0; i + 1 < parts; ++i) AGZ_HIP(hipStreamWaitEvent(streamx_[i], ev_fork_, 0));
-  return pt;
+  auto join = [&] {      // (never throws: it also runs while an exception is in flight)
+    for (int i = 0; i + 1 < chains; ++i) {
+      (void)hipEventRecord(ev_join_[i], streamx_[i]);
+      (void)hipStreamWaitEvent(stream_, ev_join_[i], 0);
+    }
+  };
+  timed(nl, [&] {      // the chains' layers overlap: one event pair around the whole tower
+    AGZ_HIP(hipEventRecord(ev_fork_, stream_));
+    for (int i = 0; i + 1 < chains; ++i) AGZ_HIP(hipStreamWaitEvent(streamx_[i], ev_fork_, 0));
+    try {      // (a launcher that throws must not leave the side streams un-joined: ADVICE r4)
+      for (int part = 0; part < chains; ++part)
+        for (int l = 0; l < nl; ++l) layer(l, part, part == 0 ? stream_ : streamx_[part - 1]);
+    } catch (...) {
+      join();
+      throw;
+    }
+    join();
+  });
 }
 
-void Net::join_chains(int parts, bool pt) {
-  if (parts <= 1) return;
-  for (int i = 0; i + 1 < parts; ++i) {          // (never throws: it also runs while an exception is in flight)
-    (void)hipEventRecord(ev_join_[i], streamx_[i]);
-    (void)hipStreamWaitEvent(stream_, ev_join_[i], 0);
-  }
-  if (pt) {
-    (void)hipEventRecord(prof_ev_[2 * prof_n_ + 1], stream_);
-    prof_mult_[prof_n_] = 2 * tower_;
-    prof_fwd_of_[prof_n_++] = prof_fwd_;
-  }
+// layer chains for a batch of `tiles` tiles in blocks of `rows`: as many as asked for while each still fills the chip a few
+// times over (at least ~4 workgroup rounds = 256 tile blocks)
+static int chain_count(int streams, long tiles, int rows) {
+  return (int)std::max<long>(1, std::min<long>(streams, (tiles + rows - 1) / rows / 256));
 }
 
 void Net::check_async_error() {
@@ -861,237 +876,177 @@ void Net::check_async_error() {
   }
 }
 
+// The stem, into d_a_ (block 0's residual).  It goes through the Winograd GEMM too when the tower does (8 K-loop stages for
+// its 17 -> 32 padded input planes instead of a direct convolution over K = 9 x 32).  For the F(3x3,3x3) towers its
+// epilogue also emits the first tower layer's V (dense tile blocks: the fix-up transform the rest), and the one k_wino_in
+// per forward shrinks to the 32-channel feature planes.  The fp16 and F(4x4,3x3) towers take its y only; the F(4x4,3x3)
+// tower's one full input transform follows.
+void Net::stem(TowerForm form, const float* d_x32, const int* d_count, int bcap) {
+  float* a = d_a_.p;
+  if (winograd_ == 0 || tower_ == 0) {
+    launch_conv3x3_direct(d_x32, d_wstem_.p, d_scale_.p, d_shift_.p, nullptr, a, d_count, bcap, N_, 1, kCinStemPad, stream_);
+  } else if (form == TowerForm::F16 || form == TowerForm::Wino4) {
+    float* v = form == TowerForm::F16 ? d_vimg_.p : d_vimg2_.p;
+    launch_wino_in(d_x32, v, d_count, bcap, N_, false, stream_, kWinoStemStages);
+    launch_wino_gemm(v, d_ustem_.p, d_scale_.p, d_shift_.p, nullptr, a, nullptr, d_count, bcap, N_, 1, false, stream_,
+                     kWinoStemStages);
+    if (form == TowerForm::Wino4) launch_wino4_in(a, d_vimg_.p, d_count, bcap, N_, stream_, false);
+  } else {
+    const bool split = precision_ == 2;
+    launch_wino_in(d_x32, d_vimg2_.p, d_count, bcap, N_, split, stream_, kWinoStemStages);
+    launch_wino_gemm(d_vimg2_.p, split ? d_ustem_s_.p : d_ustem_.p, split ? d_scale_s_.p + (size_t)2 * tower_ * kC : d_scale_.p,
+                     d_shift_.p, nullptr, a, d_vimg_.p, d_count, bcap, N_, 1, split, stream_, kWinoStemStages);
+    if (!wino_fusable(N_)) launch_wino_in(a, d_vimg_.p, d_count, bcap, N_, split, stream_, kWinoStages, true);
+  }
+}
+
+// relu(BN2(conv2(relu(BN1(conv1(x))))) + x), resnet.jl:26-32, as the direct implicit GEMM (agz_net_set_winograd(0)).  The
+// affine of tower layer l is row l + 1 of d_scale_ / d_shift_ (row 0: the stem's).
+void Net::direct_tower(const int* d_count, int bcap) {
+  const size_t per = (size_t)kC * 9 * kC;
+  const float* sc = d_scale_.p + kC;
+  const float* sh = d_shift_.p + kC;
+  float *a = d_a_.p, *b = d_b_.p, *t = d_t_.p;
+  for (int blk = 0; blk < tower_; ++blk) {
+    const int l1 = 2 * blk, l2 = 2 * blk + 1;
+    timed(1, [&] {
+      launch_conv3x3_direct(a, d_wtower_.p + per * l1, sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, nullptr, t, d_count, bcap,
+                            N_, 1, kC, stream_);
+    });
+    timed(1, [&] {
+      launch_conv3x3_direct(t, d_wtower_.p + per * l2, sc + (size_t)l2 * kC, sh + (size_t)l2 * kC, a, b, d_count, bcap, N_, 1,
+                            kC, stream_);
+    });
+    std::swap(a, b);
+  }
+}
+
+// fp16 tower (agz_conv16.hip): half activations between the f32 stem output and the f32 input of the heads (d_b_); the
+// residual of block 0 is the unrounded f32 stem output
+void Net::f16_tower(const int* d_count, int bcap) {
+  const size_t iper = conv16_image_halves();
+  const float* sc = d_scale_.p + kC;
+  const float* sh = d_shift_.p + kC;
+  const float* a = d_a_.p;
+  uint16_t *cur = d_hb_.p, *nxt = d_ha_.p;
+  launch_f32_to_f16(a, cur, d_count, bcap, N_, stream_);
+  for (int blk = 0; blk < tower_; ++blk) {
+    const int l1 = 2 * blk, l2 = 2 * blk + 1;
+    const bool first = blk == 0, last = blk + 1 == tower_;
+    timed(1, [&] {
+      launch_conv16_dma(cur, d_wi16_.p + iper * l1, sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, nullptr, 0, d_ht_.p, 0,
+                        d_count, bcap, N_, 1, stream_);
+    });
+    timed(1, [&] {
+      launch_conv16_dma(d_ht_.p, d_wi16_.p + iper * l2, sc + (size_t)l2 * kC, sh + (size_t)l2 * kC,
+                        first ? (const void*)a : (const void*)cur, first ? 1 : 0, last ? (void*)d_b_.p : (void*)nxt,
+                        last ? 1 : 0, d_count, bcap, N_, 1, stream_);
+    });
+    std::swap(cur, nxt);
+  }
+}
+
+// A Winograd tower's layer l: conv1 of a block reads V from d_vimg_ and emits the next layer's V into d_vimg2_ (y only where
+// the fix-up transform of dense tile blocks reads it, in d_t_); conv2 reads d_vimg2_, adds the block input (d_a_ for even
+// blocks, d_b_ for odd ones), writes the block output into the other and -- but for the last -- the next block's V into d_vimg_
+Net::LayerIO Net::layer_io(int l, bool dense) const {
+  if (l % 2 == 0) return {d_vimg_.p, nullptr, dense ? d_t_.p : nullptr, d_vimg2_.p};
+  const bool odd = (l / 2) % 2;
+  return {d_vimg2_.p, odd ? d_b_.p : d_a_.p, odd ? d_a_.p : d_b_.p, l + 1 == 2 * tower_ ? nullptr : d_vimg_.p};
+}
+
+// tower layer l on a Winograd form (Wino3Persistent: one layer of Wino3's): V -> y (affine, residual, ReLU) and / or the next
+// layer's V, which the fix-up transform completes from y on dense tile blocks.  part / parts: a range of tile blocks (a chain)
+void Net::wino_layer(TowerForm form, int l, const LayerIO& io, const int* d_count, int bcap, hipStream_t st, int part, int parts) {
+  const float* sc = d_scale_.p + (size_t)(l + 1) * kC;
+  const float* sh = d_shift_.p + (size_t)(l + 1) * kC;
+  if (form == TowerForm::Wino4) {
+    // (a y without residual -- conv1's -- is read by the fix-up transform only: with paired packing it is stored only there)
+    launch_wino4_gemm(io.vin, d_uwino4_.p + wino4_weight_floats() * l, sc, sh, io.res, io.y, io.vout, d_count, bcap, N_, 1, st,
+                      part, parts, io.y && !io.res && wino4_paired(N_));
+    if (io.vout && !wino4_whole_boards(N_)) launch_wino4_in(io.y, io.vout, d_count, bcap, N_, st, true, part, parts);
+  } else if (form == TowerForm::Wino5) {
+    launch_wino5_gemm(io.vin, d_uwino5_.p + wino5_weight_floats() * l, sc, sh, io.res, io.y, io.vout, d_count, bcap, N_, 1, st,
+                      part, parts);
+  } else {
+    const bool split = precision_ == 2;      // (the split form's scales: tower layer l in row l)
+    const float* u = (split ? d_uwino_s_.p : d_uwino_.p) + wino_weight_floats() * l;
+    launch_wino_gemm(io.vin, u, split ? d_scale_s_.p + (size_t)l * kC : sc, sh, io.res, io.y, io.vout, d_count, bcap, N_, 1, split,
+                     st, kWinoStages, part, parts);
+    if (io.vout && !wino_fusable(N_)) launch_wino_in(io.y, io.vout, d_count, bcap, N_, split, st, kWinoStages, true);
+  }
+}
+
+// The Winograd towers (Wino3, Wino5, Wino4) with the input transform of layer l+1 fused into the GEMM of layer l: conv1 of a
+// block leaves nothing but V in HBM, conv2 leaves the block output (the next residual, and the heads' input) and the next
+// block's V.  Whole-board tile blocks emit every tile's V from the epilogue.  Dense blocks (19x19) emit the tiles whose patch
+// lies inside their block -- three quarters of them -- and a fix-up transform does the rest from y, which every layer
+// therefore writes (round 2 ran the full k_wino_in in front of every layer there: 20 % of a step, MFMA pipe idle).
+// F(4x4,3x3) (boards of 13x13 and larger, agz_wino4.hip: 2.49 multiplies per output point at 19x19 against 3.39) cuts its
+// tile-block ranges at board boundaries with whole-board (N = 13..16) and paired (N = 17..19) packing alike; F(3x3,3x3) with
+// whole-board blocks only, and dense blocks run as one chain.  Measured on the 9x9 headline (8192 positions, the layer on
+// the board's power limit), alternating runs on one box: 46.80 / 47.00 ms per step with one chain, 46.20 / 46.08 with two
+// (-1.6 %), bit-identical outputs; a later sweep (tools/chains_sweep.sh): 46.8 / 47.7 with one, 46.4 / 46.6 with two, 46.6 /
+// 46.8 with three, 47.0 / 47.0 with four.
+void Net::wino_tower(TowerForm form, const int* d_count, int bcap) {
+  const bool f44 = form == TowerForm::Wino4;
+  const bool dense = f44 ? !wino4_whole_boards(N_) : !wino_fusable(N_);
+  const int T = f44 ? (N_ + 3) / 4 : (N_ + 2) / 3;
+  const int chains = dense && !f44 ? 1 : chain_count(tower_streams_, (long)bcap * T * T, f44 ? 64 : 63);
+  run_chains(chains, [&](int l, int part, hipStream_t st) {
+    wino_layer(form, l, layer_io(l, dense), d_count, bcap, st, part, chains);
+  });
+}
+
+// the same layers as wino_tower's (Wino3, whole-board tile blocks), as a table for ONE persistent launch (k_wino_tower)
+void Net::persistent_tower(const int* d_count, int bcap) {
+  const bool split = precision_ == 2;
+  const float* usrc = split ? d_uwino_s_.p : d_uwino_.p;
+  const float* sc = split ? d_scale_s_.p : d_scale_.p + kC;
+  const float* sh = d_shift_.p + kC;
+  const int nl = 2 * tower_;
+  std::vector<WinoTowerLayer> tab(nl);
+  for (int l = 0; l < nl; ++l) {
+    const LayerIO io = layer_io(l, false);
+    tab[l] = {io.vin, usrc + wino_weight_floats() * l, sc + (size_t)l * kC, sh + (size_t)l * kC, io.res, io.y, io.vout,
+              (io.y ? 1 : 0) | (io.vout ? 2 : 0), 1};
+  }
+  const size_t tbytes = sizeof(WinoTowerLayer) * tab.size();
+  if (tower_layers_host_.size() != tbytes || std::memcmp(tower_layers_host_.data(), tab.data(), tbytes) != 0) {
+    AGZ_HIP(hipStreamSynchronize(stream_));      // (rare: first forward, or the workspace moved)
+    tower_layers_host_.assign((const char*)tab.data(), (const char*)tab.data() + tbytes);
+    d_tower_layers_.ensure(tbytes);
+    AGZ_HIP(hipMemcpy(d_tower_layers_.p, tower_layers_host_.data(), tbytes, hipMemcpyHostToDevice));
+  }
+  d_tower_sched_.ensure(wino_tower_sched_ints(nl, bcap, N_));
+  if (!tower_err_) {
+    AGZ_HIP(hipHostMalloc((void**)&tower_err_, sizeof(int32_t), hipHostMallocDefault));
+    *tower_err_ = 0;
+  }
+  timed(nl, [&] { launch_wino_tower(d_tower_layers_.p, nl, d_tower_sched_.p, d_count, bcap, N_, split, stream_); });
+  (void)hipMemcpyAsync(tower_err_, d_tower_sched_.p + kWinoTowerErrWord, sizeof(int32_t), hipMemcpyDeviceToHost, stream_);
+}
+
 void Net::forward(const float* d_x32, const int* d_count, int bcap, float* d_pi, float* d_v) {
   check_async_error();      // (whichever launch form this forward takes)
-  if (use_wino4()) wino4_validate(bcap, N_);      // before anything is enqueued
+  TowerForm form = tower_form();
+  if (form == TowerForm::Wino4) wino4_validate(bcap, N_);      // before anything is enqueued
   pack();
   reserve(bcap);
-  const int grid = conv_grid(bcap, P_);
-  float *a = d_a_.p, *b = d_b_.p, *t = d_t_.p;
   if (prof_on_ && prof_fwd_ < kProfMax)
     (void)hipMemcpyAsync(&prof_counts_[prof_fwd_], d_count, sizeof(int32_t), hipMemcpyDeviceToHost, stream_);
-  // The stem goes through the Winograd GEMM too when the tower does (8 K-loop stages for its 17 -> 32 padded input
-  // planes instead of a direct convolution over K = 9 x 32): its epilogue then also emits the first tower layer's V,
-  // and the one k_wino_in per forward shrinks to the 32-channel feature planes.
-  const bool stem_wino = winograd_ && tower_ > 0;
-  if (!stem_wino)
-    hipLaunchKernelGGL((k_conv3x3_mfma<kCinStemPad>), dim3(grid), dim3(256), 0, stream_, d_x32, d_wstem_.p,
-                       d_scale_.p, d_shift_.p, (const float*)nullptr, a, d_count, N_, 1);
-  // every tower-conv launch goes through here so that bench.py's HIP-event roofline leg sees it
-  auto timed = [&](auto&& launch) {
-    const bool p = prof_on_ && prof_n_ < kProfMax;
-    if (p) (void)hipEventRecord(prof_ev_[2 * prof_n_], stream_);
-    launch();
-    if (p) {
-      (void)hipEventRecord(prof_ev_[2 * prof_n_ + 1], stream_);
-      prof_mult_[prof_n_] = 1;
-      prof_fwd_of_[prof_n_++] = prof_fwd_;
-    }
-  };
-  const float* sc = d_scale_.p + kC;     // affine of tower layer l at + l * kC
-  const float* sh = d_shift_.p + kC;
-  if (precision_ == 1 && tower_ > 0) {
-    // fp16 tower (agz_conv16.hip): half activations between the f32 stem output and the f32 input of
-    // the heads; the residual of block 0 is the unrounded f32 stem output
-    const size_t iper = conv16_image_halves();
-    uint16_t *cur = d_hb_.p, *nxt = d_ha_.p;
-    if (stem_wino) {                                 // the f32 stem as an 8-stage Winograd GEMM (y only)
-      launch_wino_in(d_x32, d_vimg_.p, d_count, bcap, N_, false, stream_, kWinoStemStages);
-      launch_wino_gemm(d_vimg_.p, d_ustem_.p, d_scale_.p, d_shift_.p, nullptr, a, nullptr, d_count, bcap, N_, 1, false, stream_,
-                       kWinoStemStages);
-    }
-    launch_f32_to_f16(a, cur, d_count, bcap, N_, stream_);
-    for (int blk = 0; blk < tower_; ++blk) {
-      const int l1 = 2 * blk, l2 = 2 * blk + 1;
-      const bool first = blk == 0, last = blk + 1 == tower_;
-      timed([&] {
-        launch_conv16_dma(cur, d_wi16_.p + iper * l1, sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, nullptr, 0, d_ht_.p, 0,
-                          d_count, bcap, N_, 1, stream_);
-      });
-      timed([&] {
-        launch_conv16_dma(d_ht_.p, d_wi16_.p + iper * l2, sc + (size_t)l2 * kC, sh + (size_t)l2 * kC,
-                          first ? (const void*)a : (const void*)cur, first ? 1 : 0, last ? (void*)b : (void*)nxt,
-                          last ? 1 : 0, d_count, bcap, N_, 1, stream_);
-      });
-      std::swap(cur, nxt);
-    }
-    a = b;     // the heads read the f32 output of the last block
-  } else {
-    const size_t per = (size_t)kC * 9 * kC, uper = wino_weight_floats();
-    const bool split = precision_ == 2 && winograd_;
-    const float* usrc = split ? d_uwino_s_.p : d_uwino_.p;
-    if (split) sc = d_scale_s_.p;
-    if (winograd_) {
-      // Winograd with the input transform of layer l+1 fused into the GEMM of layer l: only the first layer needs a full
-      // k_wino_in; conv1 of a block leaves nothing but V in HBM, conv2 leaves the block output (the next residual,
-      // and the heads' input) and the next block's V.  Whole-board tile blocks (N <= 12) emit every tile's V from the
-      // epilogue.  Dense blocks (19x19) emit the tiles whose 5x5 patch lies inside their block -- three quarters of
-      // them -- and a fix-up pass of k_wino_in transforms the rest from y, which every layer therefore writes
-      // (round 2 ran the full k_wino_in in front of every layer there: 20 % of a step, MFMA pipe idle).
-      const bool dense = !wino_fusable(N_);
-      float *vcur = d_vimg_.p, *vnxt = d_vimg2_.p;
-      if (use_wino4() && stem_wino) {
-        // Boards of 13x13 and larger, exact f32: the tower on F(4x4,3x3) (agz_wino4.hip: 2.49 multiplies per output point
-        // at 19x19 against 3.39).  The stem stays an 8-stage F(3x3,3x3) GEMM (y only); one full input transform in front
-        // of the first tower layer, then every layer's epilogue emits the next V -- all of it when tile blocks hold
-        // whole boards (N = 13..16), the block ends through the fix-up transform otherwise.
-        const size_t per4 = wino4_weight_floats();
-        const bool dense4 = !wino4_whole_boards(N_);
-        launch_wino_in(d_x32, vnxt, d_count, bcap, N_, false, stream_, kWinoStemStages);
-        launch_wino_gemm(vnxt, d_ustem_.p, d_scale_.p, d_shift_.p, nullptr, a, nullptr, d_count, bcap, N_, 1, false, stream_,
-                         kWinoStemStages);
-        launch_wino4_in(a, vcur, d_count, bcap, N_, stream_, false);
-        // Two chains on two streams when the batch is large enough to fill the chip twice over (>= 4 workgroup rounds
-        // per chain); the chains touch disjoint rows of the same buffers.
-        // (a chain should still fill the chip a few times over: at least ~4 workgroup rounds = 256 tile blocks each)
-        const long tblocks = ((long)bcap * ((N_ + 3) / 4) * ((N_ + 3) / 4) + 63) / 64;
-        const int nst = (int)std::max<long>(1, std::min<long>(tower_streams_, tblocks / 256));
-        // (experiment, AGZ_TOWER_CHUNKS: more ranges than streams -- a stream runs its ranges one after the other, each through
-        // all layers, so that a range's V might stay in the Infinity Cache between consecutive layers; HISTORY.md 12)
-        const int parts = nst <= 1 ? 1 : (int)std::max<long>(nst, std::min<long>(tower_chunks(), tblocks / 64));
-        const bool pt = fork_chains(nst);
-        try {                          // (a launcher that throws must not leave the side streams un-joined: ADVICE r4)
-        for (int part = 0; part < parts; ++part) {
-          hipStream_t st = part % nst == 0 ? stream_ : streamx_[part % nst - 1];
-          float *pa = a, *pb = b, *vc = vcur, *vn = vnxt;
-          for (int blk = 0; blk < tower_; ++blk) {
-            const int l1 = 2 * blk, l2 = 2 * blk + 1;
-            const bool last = blk + 1 == tower_;
-            auto layer1 = [&] {
-              // (conv1's y is read by the fix-up transform only: with paired packing it is stored only there)
-              launch_wino4_gemm(vc, d_uwino4_.p + per4 * l1, sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, nullptr, dense4 ? t : nullptr,
-                                vn, d_count, bcap, N_, 1, st, part, parts, dense4 && wino4_paired(N_));
-              if (dense4) launch_wino4_in(t, vn, d_count, bcap, N_, st, true, part, parts);
-            };
-            auto layer2 = [&] {
-              launch_wino4_gemm(vn, d_uwino4_.p + per4 * l2, sc + (size_t)l2 * kC, sh + (size_t)l2 * kC, pa, pb, last ? nullptr : vc,
-                                d_count, bcap, N_, 1, st, part, parts);
-              if (dense4 && !last) launch_wino4_in(pb, vc, d_count, bcap, N_, st, true, part, parts);
-            };
-            if (parts == 1) { timed(layer1); timed(layer2); }
-            else { layer1(); layer2(); }
-            std::swap(pa, pb);
-          }
-        }
-        } catch (...) {
-          join_chains(nst, pt);
-          throw;
-        }
-        join_chains(nst, pt);
-        if (tower_ % 2) std::swap(a, b);               // the block outputs alternate between a and b
-      } else {
-      if (stem_wino) {
-        launch_wino_in(d_x32, vnxt, d_count, bcap, N_, split, stream_, kWinoStemStages);
-        launch_wino_gemm(vnxt, split ? d_ustem_s_.p : d_ustem_.p, split ? d_scale_s_.p + (size_t)2 * tower_ * kC : d_scale_.p,
-                         d_shift_.p, nullptr, a, vcur, d_count, bcap, N_, 1, split, stream_, kWinoStemStages);
-        if (dense) launch_wino_in(a, vcur, d_count, bcap, N_, split, stream_, kWinoStages, true);
-      }
-      const bool five = use_wino5() && !dense && stem_wino;      // tower layers on the five-pass 64 x 128 form (agz_wino5.hip)
-      const size_t per5 = wino5_weight_floats();
-      const bool persistent = tower_persistent_ && !five && !dense && stem_wino && wino_tower_supported(stream_);
-      if (persistent) {
-        // the same layers as the loop below, as a table for ONE persistent launch (k_wino_tower)
-        const int nl = 2 * tower_;
-        std::vector<WinoTowerLayer> tab(nl);
-        float *pa = a, *pb = b, *vc = vcur, *vn = vnxt;
-        for (int blk = 0; blk < tower_; ++blk) {
-          const int l1 = 2 * blk, l2 = 2 * blk + 1;
-          const bool last = blk + 1 == tower_;
-          tab[l1] = {vc, usrc + uper * l1, sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, nullptr, nullptr, vn, 2, 1};
-          tab[l2] = {vn, usrc + uper * l2, sc + (size_t)l2 * kC, sh + (size_t)l2 * kC, pa, pb, last ? nullptr : vc, last ? 1 : 3, 1};
-          std::swap(pa, pb);
-        }
-        const size_t tbytes = sizeof(WinoTowerLayer) * tab.size();
-        if (tower_layers_host_.size() != tbytes || std::memcmp(tower_layers_host_.data(), tab.data(), tbytes) != 0) {
-          AGZ_HIP(hipStreamSynchronize(stream_));      // (rare: first forward, or the workspace moved)
-          tower_layers_host_.assign((const char*)tab.data(), (const char*)tab.data() + tbytes);
-          d_tower_layers_.ensure(tbytes);
-          AGZ_HIP(hipMemcpy(d_tower_layers_.p, tower_layers_host_.data(), tbytes, hipMemcpyHostToDevice));
-        }
-        d_tower_sched_.ensure(wino_tower_sched_ints(nl, bcap, N_));
-        if (!tower_err_) {
-          AGZ_HIP(hipHostMalloc((void**)&tower_err_, sizeof(int32_t), hipHostMallocDefault));
-          *tower_err_ = 0;
-        }
-        const bool p = prof_on_ && prof_n_ < kProfMax;
-        if (p) (void)hipEventRecord(prof_ev_[2 * prof_n_], stream_);
-        launch_wino_tower(d_tower_layers_.p, nl, d_tower_sched_.p, d_count, bcap, N_, split, stream_);
-        if (p) {
-          (void)hipEventRecord(prof_ev_[2 * prof_n_ + 1], stream_);
-          prof_mult_[prof_n_] = nl;
-          prof_fwd_of_[prof_n_++] = prof_fwd_;
-        }
-        (void)hipMemcpyAsync(tower_err_, d_tower_sched_.p + kWinoTowerErrWord, sizeof(int32_t), hipMemcpyDeviceToHost, stream_);
-        if (tower_ % 2) std::swap(a, b);               // the block outputs alternate between a and b
-      } else {
-      // relu(BN2(conv2(relu(BN1(conv1(x))))) + x), resnet.jl:26-32.  With whole-board tile blocks the batch's tile blocks can
-      // run as independent layer chains on several streams, like the F(4x4,3x3) tower's (above): agz_net_set_tower_streams,
-      // default 2.  Measured on the 9x9 headline (8192 positions, the layer on the board's power limit), alternating runs
-      // on one box: 46.80 / 47.00 ms per step with one chain, 46.20 / 46.08 with two (-1.6 %), bit-identical outputs; a later
-      // sweep (tools/chains_sweep.sh): 46.8 / 47.7 with one, 46.4 / 46.6 with two, 46.6 / 46.8 with three, 47.0 / 47.0 with four.
-      const int chains33 = tower_streams_;
-      const long tblocks3 = ((long)bcap * ((N_ + 2) / 3) * ((N_ + 2) / 3) + 62) / 63;
-      const int nst = dense ? 1 : (int)std::max<long>(1, std::min<long>(std::min(chains33, (int)kMaxTowerStreams), tblocks3 / 256));
-      const int parts = nst <= 1 ? 1 : (int)std::max<long>(nst, std::min<long>(tower_chunks(), tblocks3 / 64));
-      const bool pt = fork_chains(nst);
-      try {
-      for (int part = 0; part < parts; ++part) {
-        hipStream_t st = part % nst == 0 ? stream_ : streamx_[part % nst - 1];
-        float *pa = a, *pb = b;
-        for (int blk = 0; blk < tower_; ++blk) {
-          const int l1 = 2 * blk, l2 = 2 * blk + 1;
-          const bool last = blk + 1 == tower_;
-          auto layer1 = [&] {
-            if (five) {
-              launch_wino5_gemm(vcur, d_uwino5_.p + per5 * l1, sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, nullptr, nullptr, vnxt,
-                                d_count, bcap, N_, 1, st, part, parts);
-              return;
-            }
-            launch_wino_gemm(vcur, usrc + uper * l1, sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, nullptr, dense ? t : nullptr, vnxt,
-                             d_count, bcap, N_, 1, split, st, kWinoStages, part, parts);
-            if (dense) launch_wino_in(t, vnxt, d_count, bcap, N_, split, st, kWinoStages, true);
-          };
-          auto layer2 = [&] {
-            if (five) {
-              launch_wino5_gemm(vnxt, d_uwino5_.p + per5 * l2, sc + (size_t)l2 * kC, sh + (size_t)l2 * kC, pa, pb,
-                                last ? nullptr : vcur, d_count, bcap, N_, 1, st, part, parts);
-              return;
-            }
-            launch_wino_gemm(vnxt, usrc + uper * l2, sc + (size_t)l2 * kC, sh + (size_t)l2 * kC, pa, pb,
-                             last ? nullptr : vcur, d_count, bcap, N_, 1, split, st, kWinoStages, part, parts);
-            if (dense && !last) launch_wino_in(pb, vcur, d_count, bcap, N_, split, st, kWinoStages, true);
-          };
-          if (parts == 1) { timed(layer1); timed(layer2); }
-          else { layer1(); layer2(); }
-          std::swap(pa, pb);
-        }
-      }
-      } catch (...) {
-        join_chains(nst, pt);
-        throw;
-      }
-      join_chains(nst, pt);
-      if (tower_ % 2) std::swap(a, b);               // the block outputs alternate between a and b
-      }
-      }
-    } else {                                         // the direct implicit GEMM (agz_net_set_winograd(0)); the stem ran above
-      for (int blk = 0; blk < tower_; ++blk) {
-        const int l1 = 2 * blk, l2 = 2 * blk + 1;
-        timed([&] {
-          hipLaunchKernelGGL((k_conv3x3_mfma<kC>), dim3(grid), dim3(256), 0, stream_, (const float*)a, d_wtower_.p + per * l1,
-                             sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, (const float*)nullptr, t, d_count, N_, 1);
-        });
-        timed([&] {
-          hipLaunchKernelGGL((k_conv3x3_mfma<kC>), dim3(grid), dim3(256), 0, stream_, (const float*)t, d_wtower_.p + per * l2,
-                             sc + (size_t)l2 * kC, sh + (size_t)l2 * kC, (const float*)a, b, d_count, N_, 1);
-        });
-        std::swap(a, b);
-      }
-    }
+  stem(form, d_x32, d_count, bcap);
+  if (form == TowerForm::Wino3Persistent && !wino_tower_supported(stream_)) form = TowerForm::Wino3;
+  switch (form) {
+    case TowerForm::Direct: direct_tower(d_count, bcap); break;
+    case TowerForm::F16: f16_tower(d_count, bcap); break;
+    case TowerForm::Wino3Persistent: persistent_tower(d_count, bcap); break;
+    default: wino_tower(form, d_count, bcap); break;
   }
+  // the heads read the last block's output: d_b_ after the fp16 tower, else d_a_ / d_b_ alternately
+  const float* x = form == TowerForm::F16 || tower_ % 2 ? d_b_.p : d_a_.p;
   const int hgrid = std::min(ceil_div((long)bcap * P_, 4), 256 * 16);
-  hipLaunchKernelGGL(k_head_conv, dim3(hgrid), dim3(256), 0, stream_, (const float*)a, d_head_.p, d_vh_.p,
-                     d_ph_.p, d_count, P_);
+  hipLaunchKernelGGL(k_head_conv, dim3(hgrid), dim3(256), 0, stream_, x, d_head_.p, d_vh_.p, d_ph_.p, d_count, P_);
   const size_t smem = sizeof(float) * (size_t)(3 * P_ + A_ + 4);
   hipLaunchKernelGGL(k_head_fc, dim3(bcap), dim3(256), smem, stream_, (const float*)d_vh_.p,
                      (const float*)d_ph_.p, d_vfc1w_, d_vfc1b_, d_vfc2w_, d_vfc2b_, d_pfcw_,
@@ -1242,29 +1197,15 @@ void Net::launch_tower_conv_once(const int* d_count, int bcap) {
   pack();
   reserve(bcap);
   AGZ_REQUIRE(tower_ > 0, AGZ_BAD_ARGUMENT, "no tower conv in a tower_height=0 network");
-  const int grid = conv_grid(bcap, P_);
-  if (precision_ == 1)
+  const TowerForm form = tower_form();
+  if (form == TowerForm::F16)
     launch_conv16_dma(d_ha_.p, d_wi16_.p, d_scale_.p + kC, d_shift_.p + kC, nullptr, 0, d_ht_.p, 0, d_count, bcap, N_, 1,
                       stream_);
-  else if (use_wino4()) {
-    launch_wino4_gemm(d_vimg_.p, d_uwino4_.p, d_scale_.p + kC, d_shift_.p + kC, d_a_.p, d_t_.p, d_vimg2_.p, d_count, bcap, N_, 1, stream_);
-    if (!wino4_whole_boards(N_)) launch_wino4_in(d_t_.p, d_vimg2_.p, d_count, bcap, N_, stream_, true);
-  }
-  else if (use_wino5())                       // (time_conv: a steady-state layer of the five-pass form)
-    launch_wino5_gemm(d_vimg_.p, d_uwino5_.p, d_scale_.p + kC, d_shift_.p + kC, d_a_.p, d_t_.p, d_vimg2_.p, d_count, bcap, N_, 1, stream_);
-  else if (winograd_ && wino_fusable(N_)) {   // a steady-state tower layer: residual in, y and the next V out
-    const bool split = precision_ == 2;
-    launch_wino_gemm(d_vimg_.p, split ? d_uwino_s_.p : d_uwino_.p, split ? d_scale_s_.p : d_scale_.p + kC, d_shift_.p + kC,
-                     d_a_.p, d_t_.p, d_vimg2_.p, d_count, bcap, N_, 1, split, stream_);
-  } else if (winograd_) {                       // dense tile blocks: the GEMM emits most of the next V, the fix-up pass the rest
-    const bool split = precision_ == 2;
-    launch_wino_gemm(d_vimg_.p, split ? d_uwino_s_.p : d_uwino_.p, split ? d_scale_s_.p : d_scale_.p + kC, d_shift_.p + kC,
-                     d_a_.p, d_t_.p, d_vimg2_.p, d_count, bcap, N_, 1, split, stream_);
-    launch_wino_in(d_t_.p, d_vimg2_.p, d_count, bcap, N_, split, stream_, kWinoStages, true);
-  }
-  else
-  hipLaunchKernelGGL((k_conv3x3_mfma<kC>), dim3(grid), dim3(256), 0, stream_, (const float*)d_a_.p,
-                     d_wtower_.p, d_scale_.p + kC, d_shift_.p + kC, (const float*)nullptr, d_t_.p, d_count, N_, 1);
+  else if (form == TowerForm::Direct)
+    launch_conv3x3_direct(d_a_.p, d_wtower_.p, d_scale_.p + kC, d_shift_.p + kC, nullptr, d_t_.p, d_count, bcap, N_, 1, kC,
+                          stream_);
+  else      // a steady-state Winograd layer: residual in, y and the next V out (+ the fix-up transform of dense blocks)
+    wino_layer(form, 0, {d_vimg_.p, d_a_.p, d_t_.p, d_vimg2_.p}, d_count, bcap, stream_);
   AGZ_HIP(hipGetLastError());
 }
 

@@ -887,7 +887,7 @@ void launch_wino_pack(const float* d_w, long wstride, int cin, int layers, float
 float wino_split_descale() { return 1.f / (kSplitV * kSplitU); }
 
 size_t wino_weight_floats(int ns) { return (size_t)(kC / WC) * ns * B_STAGE; }
-static long wino_blocks(int bcap, int T) {
+long wino_blocks(int bcap, int T) {
   const long rpb = wino_rows_per_block(T);
   return ((long)bcap * T * T + rpb - 1) / rpb;
 }
@@ -898,19 +898,20 @@ void launch_wino_in(const float* x, float* vimg, const int* d_count, int bcap, i
                     bool fixup) {
   const int T = (N + 2) / 3;
   const int blocks = (int)wino_blocks(bcap, T);
-  if (fixup) {      // the rows the previous GEMM's epilogue left out (dense tile blocks; a tower layer's 64 stages)
-    AGZ_REQUIRE(ns == kWinoStages && !wino_whole_boards(T), AGZ_BAD_ARGUMENT, "fix-up transform: dense tile blocks, tower layers");
-    if (split) hipLaunchKernelGGL((k_wino_in<32, true, true, WNS, true>), dim3(2 * blocks), dim3(256), 0, s, x, vimg, d_count, N, T);
-    else hipLaunchKernelGGL((k_wino_in<32, true, false, WNS, true>), dim3(2 * blocks), dim3(256), 0, s, x, vimg, d_count, N, T);
-    return;
+  // fixup: the rows the previous GEMM's epilogue left out (dense tile blocks; a tower layer's 64 stages)
+  AGZ_REQUIRE(!fixup || (ns == kWinoStages && !wino_whole_boards(T)), AGZ_BAD_ARGUMENT, "fix-up transform: dense tile blocks, tower layers");
+#define WIN_LAUNCH(SPLIT_, NS_, FIXUP_) \
+  hipLaunchKernelGGL((k_wino_in<32, true, SPLIT_, NS_, FIXUP_>), dim3(2 * blocks), dim3(256), 0, s, x, vimg, d_count, N, T)
+  constexpr int S = kWinoStemStages;
+  switch ((fixup ? 4 : ns == S ? 2 : 0) | (split ? 1 : 0)) {
+    case 5: WIN_LAUNCH(true, WNS, true); break;
+    case 4: WIN_LAUNCH(false, WNS, true); break;
+    case 3: WIN_LAUNCH(true, S, false); break;
+    case 2: WIN_LAUNCH(false, S, false); break;
+    case 1: WIN_LAUNCH(true, WNS, false); break;
+    default: WIN_LAUNCH(false, WNS, false); break;
   }
-  if (ns == kWinoStemStages) {
-    if (split) hipLaunchKernelGGL((k_wino_in<32, true, true, kWinoStemStages>), dim3(2 * blocks), dim3(256), 0, s, x, vimg, d_count, N, T);
-    else hipLaunchKernelGGL((k_wino_in<32, true, false, kWinoStemStages>), dim3(2 * blocks), dim3(256), 0, s, x, vimg, d_count, N, T);
-    return;
-  }
-  if (split) hipLaunchKernelGGL((k_wino_in<32, true, true>), dim3(2 * blocks), dim3(256), 0, s, x, vimg, d_count, N, T);
-  else hipLaunchKernelGGL((k_wino_in<32, true, false>), dim3(2 * blocks), dim3(256), 0, s, x, vimg, d_count, N, T);
+#undef WIN_LAUNCH
 }
 
 // y == nullptr: the activations are not needed in HBM (only their transform is); vnext == nullptr: no next
@@ -919,45 +920,35 @@ void launch_wino_gemm(const float* vimg, const float* uimg, const float* scale, 
                       float* y, float* vnext, const int* d_count, int bcap, int N, int relu, bool split, hipStream_t s, int ns, int part,
                       int parts) {
   const int T = (N + 2) / 3;
-  // part / parts: the part-th of `parts` equal ranges of tile blocks.  With whole-board blocks a range's layers depend on
-  // nothing outside it, so ranges can run as independent layer chains on different streams (Net::forward)
   const int all_blocks = (int)wino_blocks(bcap, T);
-  AGZ_REQUIRE(parts >= 1 && part >= 0 && part < parts && (parts == 1 || wino_whole_boards(T)), AGZ_BAD_ARGUMENT,
-              "tile-block range %d of %d", part, parts);
-  const int per_part = (all_blocks + parts - 1) / parts;
-  const int tb0 = std::min(all_blocks, part * per_part), tb1 = part + 1 == parts ? all_blocks : std::min(all_blocks, tb0 + per_part);
+  int tb0, tb1;
+  wino_block_range(all_blocks, part, parts, false, tb0, tb1);
+  AGZ_REQUIRE(parts == 1 || wino_whole_boards(T), AGZ_BAD_ARGUMENT, "F(3x3,3x3): %d layer chains need whole-board tile blocks", parts);
   if (tb1 <= tb0) return;
   const int blocks = tb1 - tb0;
   const int per_xcd = 4 * ((blocks + 7) / 8);   // see the placement comment in k_wino_gemm4
   const dim3 grid(8 * per_xcd), block(256);
-  AGZ_REQUIRE((long)(all_blocks + 1) * WT < (1L << 31) && (long)bcap * N * N * kC * 4 < (1L << 32), AGZ_BAD_ARGUMENT,
-              "batch of %d positions at %dx%d: tile index / activation byte offset exceeds 32 bits", bcap, N, N);
-  if (ns == kWinoStemStages) {                   // the stem: its output is always wanted in HBM (block 0's residual)
-    constexpr int S = kWinoStemStages;
-    if (split) {
-      if (vnext) hipLaunchKernelGGL((k_wino_gemm4<3, true, S>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1);
-      else hipLaunchKernelGGL((k_wino_gemm4<1, true, S>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1);
-    } else {
-      if (vnext) hipLaunchKernelGGL((k_wino_gemm4<3, false, S>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1);
-      else hipLaunchKernelGGL((k_wino_gemm4<1, false, S>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1);
-    }
-    return;
+  wino_check_32bit(all_blocks, WT, bcap, N);
+  // MODE bit 0: write y, bit 1: emit the next V.  The stem's output is always wanted in HBM (block 0's residual).
+  const bool stem = ns == kWinoStemStages;
+  const int mode = vnext ? (y || stem ? 3 : 2) : 1;
+#define WG_LAUNCH(MODE_, SPLIT_, NS_)                                                                                     \
+  hipLaunchKernelGGL((k_wino_gemm4<MODE_, SPLIT_, NS_>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, \
+                     N, T, relu, tb0, tb1)
+  constexpr int S = kWinoStemStages;
+  switch (mode | (split ? 4 : 0) | (stem ? 8 : 0)) {
+    case 15: WG_LAUNCH(3, true, S); break;
+    case 13: WG_LAUNCH(1, true, S); break;
+    case 11: WG_LAUNCH(3, false, S); break;
+    case 9: WG_LAUNCH(1, false, S); break;
+    case 7: WG_LAUNCH(3, true, WNS); break;
+    case 6: WG_LAUNCH(2, true, WNS); break;
+    case 5: WG_LAUNCH(1, true, WNS); break;
+    case 3: WG_LAUNCH(3, false, WNS); break;
+    case 2: WG_LAUNCH(2, false, WNS); break;
+    default: WG_LAUNCH(1, false, WNS); break;
   }
-  if (split) {
-    if (y && vnext)
-      hipLaunchKernelGGL((k_wino_gemm4<3, true>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1);
-    else if (vnext)
-      hipLaunchKernelGGL((k_wino_gemm4<2, true>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1);
-    else
-      hipLaunchKernelGGL((k_wino_gemm4<1, true>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1);
-    return;
-  }
-  if (y && vnext)
-    hipLaunchKernelGGL((k_wino_gemm4<3>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1);
-  else if (vnext)
-    hipLaunchKernelGGL((k_wino_gemm4<2>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1);
-  else
-    hipLaunchKernelGGL((k_wino_gemm4<1>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1);
+#undef WG_LAUNCH
 }
 
 size_t wino_tower_sched_ints(int layers, int bcap, int N) {
@@ -993,8 +984,7 @@ bool wino_tower_supported(hipStream_t s) {
 void launch_wino_tower(const void* d_layers, int layers, int* d_sched, const int* d_count, int bcap, int N, bool split, hipStream_t s) {
   const int T = (N + 2) / 3;
   AGZ_REQUIRE(wino_whole_boards(T), AGZ_BAD_ARGUMENT, "the persistent tower kernel needs whole-board tile blocks");
-  AGZ_REQUIRE((long)(wino_blocks(bcap, T) + 1) * WT < (1L << 31) && (long)bcap * N * N * kC * 4 < (1L << 32), AGZ_BAD_ARGUMENT,
-              "batch of %d positions at %dx%d: tile index / activation byte offset exceeds 32 bits", bcap, N, N);
+  wino_check_32bit(wino_blocks(bcap, T), WT, bcap, N);
   const int blocks_cap = (int)wino_blocks(bcap, T);
   (void)hipMemsetAsync(d_sched, 0, sizeof(int) * wino_tower_sched_ints(layers, bcap, N), s);
   constexpr int order = 0;

@@ -687,25 +687,16 @@ bool wino4_paired(int N) { return w4_paired((N + 3) / 4); }
 // multiplies per output point: F(4x4,3x3) against F(3x3,3x3); the larger tile pays from 13x13 up
 bool wino4_applies(int N) { return N >= 13; }
 
-static void wino4_check(int bcap, int N) {
-  const int T = (N + 3) / 4;
-  AGZ_REQUIRE((long)(wino4_blocks(bcap, T) + 1) * W4T < (1L << 31) && (long)bcap * N * N * kC * 4 < (1L << 32), AGZ_BAD_ARGUMENT,
-              "batch of %d positions at %dx%d: tile index / activation byte offset exceeds 32 bits", bcap, N, N);
-}
-
-void wino4_validate(int bcap, int N) { wino4_check(bcap, N); }
+void wino4_validate(int bcap, int N) { wino_check_32bit(wino4_blocks(bcap, (N + 3) / 4), W4T, bcap, N); }
 
 // part / parts: this launch covers the part-th of `parts` equal ranges of tile blocks (cut at block-pair boundaries, so that
 // no board straddles two ranges: a range's layers depend on nothing outside it, and ranges can run on different streams).
 // An even block index is a board boundary only with whole-board (N = 13..16) or paired (N = 17..19) packing: dense
 // non-paired packing (T >= 6) must run as one range (unreachable while board_size <= 19).
 static void wino4_range(int blocks, int part, int parts, int& tb0, int& tb1, int T) {
-  AGZ_REQUIRE(parts >= 1 && part >= 0 && part < parts, AGZ_BAD_ARGUMENT, "block range %d of %d", part, parts);
+  wino_block_range(blocks, part, parts, true, tb0, tb1);
   AGZ_REQUIRE(parts == 1 || w4_whole_boards(T) || w4_paired(T), AGZ_BAD_ARGUMENT,
               "F(4x4,3x3): %d layer chains need whole-board or paired tile packing (T = %d packs densely)", parts, T);
-  const int per = ((blocks + parts - 1) / parts + 1) & ~1;      // even: whole block pairs
-  tb0 = std::min(blocks, part * per);
-  tb1 = part + 1 == parts ? blocks : std::min(blocks, tb0 + per);
 }
 
 void launch_wino4_in(const float* x, float* vimg, const int* d_count, int bcap, int N, hipStream_t s, bool fixup, int part, int parts) {
@@ -713,7 +704,7 @@ void launch_wino4_in(const float* x, float* vimg, const int* d_count, int bcap, 
   int tb0, tb1;
   wino4_range((int)wino4_blocks(bcap, T), part, parts, tb0, tb1, T);
   if (tb1 <= tb0) return;
-  wino4_check(bcap, N);
+  wino4_validate(bcap, N);
   if (fixup) {
     AGZ_REQUIRE(!w4_whole_boards(T) && T + 1 <= 8, AGZ_BAD_ARGUMENT, "fix-up transform: dense tile blocks, at most 8 rows at a block's ends");
     hipLaunchKernelGGL((k_wino4_in<true>), dim3(2 * (tb1 - tb0)), dim3(256), 0, s, x, vimg, d_count, N, T, tb0, tb1);
@@ -732,7 +723,7 @@ void launch_wino4_gemm(const float* vimg, const float* uimg, const float* scale,
   const int blocks = tb1 - tb0;
   const int per_xcd = 4 * ((blocks + 7) / 8);
   const dim3 grid(8 * per_xcd), block(256);
-  wino4_check(bcap, N);
+  wino4_validate(bcap, N);
   AGZ_REQUIRE(y || vnext, AGZ_BAD_ARGUMENT, "F(4x4,3x3) GEMM: nothing to write");
   // ypart: y only where the fix-up transform reads it (paired packing, no residual: conv1 of a block) -- bit 30 of the
   // kernel's last argument

@@ -69,13 +69,12 @@ constexpr int W5RN0 = (W5RING * W5STAGE * 4 + 4095) / 4096;      // first residu
 static_assert(W5DIST == 2 || W5DIST == 3, "vmcnt immediates in the kernel");
 static_assert(W5RING * W5STAGE <= W5IMG, "the stage ring lies under the tile image");
 
-// (agz_wino.hip: wino_rows_per_block / wino_whole_boards -- rows of a 64-row tile block that carry tiles)
+// (agz_wino.hip: wino_rows_per_block -- rows of a 64-row tile block that carry tiles)
 __host__ __device__ inline int w5_rows_per_block(int T) {
   const int tt = T * T;
   const int whole = (W5T / tt) * tt;
   return (tt <= W5T && whole * 10 >= W5T * 9) ? whole : W5T;
 }
-__host__ __device__ inline bool w5_whole_boards(int T) { return w5_rows_per_block(T) % (T * T) == 0 && T * T <= W5T; }
 // a unit image row (either operand): the unit's 4 channels as two pairs, pair h at slot (h + (row >> 4)) & 1
 // (agz_wino.hip: wino_v_off -- the layout V is stored in)
 __host__ __device__ __forceinline__ int w5_off(int row, int h) { return row * 4 + 2 * ((h + (row >> 4)) & 1); }
@@ -584,24 +583,20 @@ void launch_wino5_pack(const float* d_w, long wstride, int layers, float* d_out,
   hipLaunchKernelGGL(k_wino5_pack, dim3(grid), dim3(256), 0, s, d_w, wstride, layers, d_out, per);     // (every word of an image is written)
 }
 size_t wino5_weight_floats() { return (size_t)(kC / W5C) * W5UBLOCK; }
-bool wino5_applies(int N) { return w5_whole_boards((N + 2) / 3); }
 
 // the arguments of launch_wino_gemm (agz_wino.hip) for a tower layer in exact f32; uimg: launch_wino5_pack's image
 void launch_wino5_gemm(const float* vimg, const float* uimg, const float* scale, const float* shift, const float* res,
                        float* y, float* vnext, const int* d_count, int bcap, int N, int relu, hipStream_t s, int part, int parts) {
   const int T = (N + 2) / 3;
-  AGZ_REQUIRE(w5_whole_boards(T), AGZ_BAD_ARGUMENT, "five-pass F(3x3,3x3): whole-board tile blocks only (N <= 12), got %d", N);
-  const long rpb = w5_rows_per_block(T);
-  const int all_blocks = (int)(((long)bcap * T * T + rpb - 1) / rpb);
-  AGZ_REQUIRE(parts >= 1 && part >= 0 && part < parts, AGZ_BAD_ARGUMENT, "tile-block range %d of %d", part, parts);
+  AGZ_REQUIRE(wino_fusable(N), AGZ_BAD_ARGUMENT, "five-pass F(3x3,3x3): whole-board tile blocks only (N <= 12), got %d", N);
   AGZ_REQUIRE(y || vnext, AGZ_BAD_ARGUMENT, "five-pass F(3x3,3x3) GEMM: nothing to write");
-  const int per_part = (all_blocks + parts - 1) / parts;
-  const int tb0 = std::min(all_blocks, part * per_part), tb1 = part + 1 == parts ? all_blocks : std::min(all_blocks, tb0 + per_part);
+  const int all_blocks = (int)wino_blocks(bcap, T);      // (W5T = agz_wino.hip's 64-row tile blocks)
+  int tb0, tb1;
+  wino_block_range(all_blocks, part, parts, false, tb0, tb1);
   if (tb1 <= tb0) return;
   const int blocks = tb1 - tb0;
   const dim3 grid(8 * 2 * ((blocks + 7) / 8)), block(256);
-  AGZ_REQUIRE((long)(all_blocks + 1) * W5T < (1L << 31) && (long)bcap * N * N * kC * 4 < (1L << 32), AGZ_BAD_ARGUMENT,
-              "batch of %d positions at %dx%d: tile index / activation byte offset exceeds 32 bits", bcap, N, N);
+  wino_check_32bit(all_blocks, W5T, bcap, N);
 #define W5_LAUNCH(MODE_) hipLaunchKernelGGL((k_wino5_gemm<MODE_>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1)
 #ifdef AGZ_TIMING_EXPERIMENTS
   static int traced = 0;

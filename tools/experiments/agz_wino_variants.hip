@@ -1012,7 +1012,7 @@ void launch_wino_pack(const float* d_w, long wstride, int cin, int layers, float
 float wino_split_descale() { return 1.f / (kSplitV * kSplitU); }
 
 size_t wino_weight_floats(int ns) { return (size_t)(kC / WC) * ns * B_STAGE; }
-static long wino_blocks(int bcap, int T) {
+long wino_blocks(int bcap, int T) {
   const long rpb = wino_rows_per_block(T);
   return ((long)bcap * T * T + rpb - 1) / rpb;
 }
