@@ -73,6 +73,12 @@ class Analysis(C.Structure):
                 ("nodes_used", C.c_int32)]
 
 
+class Line(C.Structure):
+    """agz_line: one candidate move of a node with its principal variation (agz_analyze_lines / agz_tree_lines)"""
+    _fields_ = [("move", C.c_int32), ("pv_len", C.c_int32), ("N", C.c_float), ("W", C.c_float), ("prior", C.c_float),
+                ("end_W", C.c_float)]
+
+
 _lib = None
 
 
@@ -148,6 +154,9 @@ def load():
         "agz_review_start": (i32, [E, P(C.c_int16), P(i64), i8p, P(PositionInfo), i8p, i64, u64]),
         "agz_analyze_progress": (i32, [E, P(i64)]),
         "agz_analyze_results": (i32, [E, P(Analysis), f32p, f32p, f32p]),
+        "agz_analyze_set_lines": (i32, [E, i32, i32, i32]),
+        "agz_analyze_lines": (i32, [E, P(Line), i16p, f32p]),
+        "agz_tree_lines": (i32, [E, i32, i32, i32, i32, i32, P(Line), i16p, f32p]),
         "agz_engine_stats": (i32, [E, P(Stats)]),
         "agz_selfplay_select": (i32, [E, i32p]),
         "agz_selfplay_leaf_features": (i32, [E, f32p]),

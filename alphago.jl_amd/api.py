@@ -345,6 +345,50 @@ class NodeView:
         ch = self._p.engine.node_children(0, self.id)
         return {int(a): NodeView(self._p, int(c)) for a, c in enumerate(ch) if c >= 0}
 
+    # ---- analysis lines (ours; the commented-out most_visited_path / mvp_gg / describe of mcts.jl:255-327 are the
+    # definition): one agz_tree_lines call each, the walk runs on the device
+    def lines(self, k=4, depth=16, min_visits=1):
+        """the top k candidate moves of this node (child_N, then child_prior descending, then the action ascending)
+        with their principal variations: a list of Line"""
+        _check_lines(k, depth, min_visits)
+        if k == 0:
+            return []
+        return _line_rows(self._p.env, self._p.engine.tree_lines(0, self.id, k, depth, min_visits))
+
+    def most_visited_path(self):              # mcts.jl:267-281
+        """the first line's principal variation as "<kgs> (<N>) ==> ... Q: <Q of its end>"; a tie of child_N at this
+        node is decided by the prior (the candidate order), below it by findmax as in the reference.  "GAME END" (a
+        most visited child that is no node) is not printed: the walk ends there."""
+        ln = self.lines(1, 64, 1)
+        if not ln:
+            return "Q: %.5f\n" % self.Q
+        env = self._p.env
+        return "".join(f"{to_kgs(c, env)} ({_jl_f32(n)}) ==> " for c, n in zip(ln[0].pv, ln[0].pv_N)) + "Q: %.5f\n" % ln[0].end_Q
+
+    def mvp_gg(self):                         # mcts.jl:283-293
+        """the most visited path in go-gui VAR format while maximum(child_N) > 1, e.g. 'D4 Q16 ...'"""
+        ln = self.lines(1, 64, 2)
+        if not ln or not ln[0].N > 1:
+            return ""
+        return " ".join(to_kgs(c, self._p.env) for c in ln[0].pv)
+
+    def describe(self):                       # mcts.jl:295-327, without the P-Dir column (original_prior is not stored)
+        env = self._p.env
+        cn, prior = self.child_N, self.child_prior
+        score, cq, cu = self.child_action_score, self.child_Q, self.child_U
+        soft_n = cn / max(np.float32(1), cn.sum())
+        p_delta = soft_n - prior
+        p_rel = np.zeros_like(p_delta)
+        mask = prior != 0
+        p_rel[mask] = p_delta[mask] / prior[mask]
+        out = ["%.4f\n" % self.Q, self.most_visited_path(),
+               "move : action    Q     U     P    N  soft-N  p-delta  p-rel"]
+        for ln in self.lines(15, 1, 1):       # the rows in candidate order (the reference: child_N, then action score)
+            a = to_flat(ln.move, env)
+            out.append("\n%s   : % .3f % .3f %.3f %.3f %5d %.4f % .5f % .2f" % (
+                to_kgs(ln.move, env), score[a], cq[a], cu[a], prior[a], int(cn[a]), soft_n[a], p_delta[a], p_rel[a]))
+        return "".join(out)
+
     @property
     def position(self):
         info = self._info
@@ -368,6 +412,12 @@ class NodeView:
                 tp = -tp
             pos.recent = rec
         return pos
+
+
+def _jl_f32(x):
+    """a Float32 as Julia's string interpolation prints it"""
+    x = np.float32(x)
+    return str(int(x)) + ".0" if x == np.floor(x) and abs(x) < 1e7 else np.format_float_positional(x, unique=True)
 
 
 def position_arrays(pos):
@@ -640,15 +690,54 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
 Analysis = namedtuple("Analysis", "move N W Q child_N child_W child_Q prior status nodes_used game_id")
 
 
+# One candidate move of an analysed node with its principal variation (include/agz.h agz_line): move and
+# the pv entries as board coordinates (None = pass, pv[0] = move), N / W / prior = the candidate's entries of the node's
+# rows, Q = W / (1 + N), pv_N[d] = the child_N entry pv[d] was chosen by, end_Q = Q of the line's last move
+Line = namedtuple("Line", "move N W Q prior pv pv_N end_Q")
+# a row of analyze() / review() with lines > 0: Analysis's fields, then the list of Line (at most `lines` of them)
+AnalysisLines = namedtuple("AnalysisLines", Analysis._fields + ("lines",))
+
+
+def _check_lines(lines, pv_depth, pv_min_visits):
+    for name, v in (("lines", lines), ("pv_depth", pv_depth), ("pv_min_visits", pv_min_visits)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer")
+    if not 0 <= lines <= 16:
+        raise ValueError("lines must be in 0..16")
+    if not 1 <= pv_depth <= 64:
+        raise ValueError("pv_depth must be in 1..64")
+    if pv_min_visits < 1:
+        raise ValueError("pv_min_visits must be >= 1")
+
+
+def _line_rows(env, t):
+    """the Line list of one row of the tables Engine.analyze_lines / tree_lines return ([K], [K][D])"""
+    out = []
+    one = np.float32(1)
+    for k in range(len(t["move"])):
+        n = int(t["pv_len"][k])
+        if t["move"][k] < 0 or n < 1:
+            continue
+        pvn = t["pv_N"][k, :n].copy()
+        out.append(Line(from_flat(int(t["move"][k]), env), t["N"][k], t["W"][k], t["W"][k] / (one + t["N"][k]),
+                        t["prior"][k], [from_flat(int(a), env) for a in t["pv"][k, :n]], pvn,
+                        t["end_W"][k] / (one + pvn[-1])))
+    return out
+
+
 def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=None, two_player_mode=False,
-            symmetry=None, precision="f32", **cfg):
+            symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, **cfg):
     """suggest_move over many positions in one device run (ours).  Record i is what
     `MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + i, symmetry=symmetry)`,
     `initialize_game(positions[i])`, `suggest_move()` computes (mcts_play.jl:110-118,144-151), bit for bit, except that
     an invalid board gives status BAD_ARGUMENT instead of a search, and that a position whose last two moves were passes
     is a finished root, as in the reference (MCTSNode keeps pos.done).  `slots` trees search at once (default
     min(len(positions), 1024)); a slot that finishes a position takes the next.  `cfg`: further agz_config fields
-    (parallel_readouts = tree_search!'s 8 by default, max_nodes_per_game, pool_policy, ...)."""
+    (parallel_readouts = tree_search!'s 8 by default, max_nodes_per_game, pool_policy, ...).
+    lines > 0 (at most 16): the rows are AnalysisLines, i.e. Analysis plus `lines`, the root's top candidates with
+    principal variations of at most pv_depth moves taken when the search ended (pv_min_visits 1 walks
+    like most_visited_path, 2 like mvp_gg); everything else in the row is what lines = 0 gives."""
+    _check_lines(lines, pv_depth, pv_min_visits)
     positions = list(positions)
     for k, p in enumerate(positions):
         if not isinstance(p, Position):
@@ -680,6 +769,8 @@ def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=
         eng.set_precision(precision)
         if symmetry is not None:
             eng.set_symmetry(symmetry)
+        if lines:
+            eng.analyze_set_lines(lines, pv_depth, pv_min_visits)
         eng.analyze_start(boards, infos, hist, game_id_base)
         while eng.analyze_progress() < B:
             eng.step(16)
@@ -687,14 +778,16 @@ def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=
                 raise _lib.AgzError(_lib.POOL_EXHAUSTED, "a search is waiting on a full node pool (pool_policy = "
                                                          "stall): raise max_nodes_per_game or use the default policy")
         r = eng.analyze_results()
+        t = eng.analyze_lines() if lines else None
     finally:
         eng.close()
     out = []
     for k in range(B):
         cn, cw = r["child_N"][k], r["child_W"][k]
-        out.append(Analysis(None if r["move"][k] < 0 else from_flat(int(r["move"][k]), env), r["N"][k], r["W"][k],
-                            r["Q"][k], cn, cw, cw / (np.float32(1) + cn), r["prior"][k], int(r["status"][k]),
-                            int(r["nodes_used"][k]), int(game_id_base) + k))
+        a = Analysis(None if r["move"][k] < 0 else from_flat(int(r["move"][k]), env), r["N"][k], r["W"][k],
+                     r["Q"][k], cn, cw, cw / (np.float32(1) + cn), r["prior"][k], int(r["status"][k]),
+                     int(r["nodes_used"][k]), int(game_id_base) + k)
+        out.append(AnalysisLines(*a, _line_rows(env, {f: v[k] for f, v in t.items()})) if lines else a)
     return out
 
 
@@ -735,7 +828,7 @@ def review_arrays(env, games):
 
 
 def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, seed=0, game_id_base=0, slots=None,
-           symmetry=None, precision="f32", **cfg):
+           symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, **cfg):
     """Batched game review (ours; the loop of play(), src/play.jl:25-77, over recorded games): for game j, what
     `p = MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + j, symmetry=symmetry)`,
     `p.initialize_game(starts[j])`, then for every recorded move m_k `p.suggest_move()` and `p.play_move(m_k)` compute,
@@ -745,7 +838,10 @@ def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, 
     empty board with agz_config.komi) or one Position (or None) per game.  A recorded move that cannot be played (illegal,
     or after the game ended) gives its ply and every later one of that game status BAD_ARGUMENT, move None; the earlier
     plies and the other games are not affected.  `slots` trees search at once (default min(len(games),
-    1024)).  `cfg`: further agz_config fields (parallel_readouts, max_nodes_per_game, pool_policy, komi, ...)."""
+    1024)).  `cfg`: further agz_config fields (parallel_readouts, max_nodes_per_game, pool_policy, komi, ...).
+    lines > 0: the rows are AnalysisLines as in analyze(); the lines of ply k are taken when its search ended, before
+    the recorded move re-roots the tree."""
+    _check_lines(lines, pv_depth, pv_min_visits)
     games = list(games)
     moves, off = review_arrays(env, games)
     if starts is not None:
@@ -784,6 +880,8 @@ def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, 
         eng.set_precision(precision)
         if symmetry is not None:
             eng.set_symmetry(symmetry)
+        if lines:
+            eng.analyze_set_lines(lines, pv_depth, pv_min_visits)
         eng.review_start(moves, off, boards, infos, hist, game_id_base)
         total = int(off[-1])
         while eng.review_progress() < total:
@@ -792,6 +890,7 @@ def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, 
                 raise _lib.AgzError(_lib.POOL_EXHAUSTED, "a search is waiting on a full node pool (pool_policy = "
                                                          "stall): raise max_nodes_per_game or use the default policy")
         r = eng.review_results()
+        t = eng.analyze_lines() if lines else None
     finally:
         eng.close()
     out = []
@@ -799,9 +898,10 @@ def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, 
         rows = []
         for i in range(int(off[j]), int(off[j + 1])):
             cn, cw = r["child_N"][i], r["child_W"][i]
-            rows.append(Analysis(None if r["move"][i] < 0 else from_flat(int(r["move"][i]), env), r["N"][i], r["W"][i],
-                                 r["Q"][i], cn, cw, cw / (np.float32(1) + cn), r["prior"][i], int(r["status"][i]),
-                                 int(r["nodes_used"][i]), int(game_id_base) + j))
+            a = Analysis(None if r["move"][i] < 0 else from_flat(int(r["move"][i]), env), r["N"][i], r["W"][i],
+                         r["Q"][i], cn, cw, cw / (np.float32(1) + cn), r["prior"][i], int(r["status"][i]),
+                         int(r["nodes_used"][i]), int(game_id_base) + j)
+            rows.append(AnalysisLines(*a, _line_rows(env, {f: v[i] for f, v in t.items()})) if lines else a)
         out.append(rows)
     return out
 

@@ -354,6 +354,18 @@ agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N,
   return guard(e, [&](agz::Engine& E) { E.analyze_results(out, child_N, child_W, prior); });
 }
 
+// ---- analysis lines
+agz_status agz_analyze_set_lines(agz_engine* e, int32_t K, int32_t D, int32_t min_visits) {
+  return guard(e, [&](agz::Engine& E) { E.analyze_set_lines(K, D, min_visits); });
+}
+agz_status agz_analyze_lines(agz_engine* e, agz_line* lines, int16_t* pv, float* pv_N) {
+  return guard(e, [&](agz::Engine& E) { E.analyze_lines(lines, pv, pv_N); });
+}
+agz_status agz_tree_lines(agz_engine* e, int32_t g, int32_t node, int32_t K, int32_t D, int32_t min_visits,
+                          agz_line* lines, int16_t* pv, float* pv_N) {
+  return guard(e, [&](agz::Engine& E) { E.tree_lines(g, node, K, D, min_visits, lines, pv, pv_N); });
+}
+
 agz_status agz_train_step(agz_engine* e, const float* feats, const float* pi, const float* z, int32_t B,
                           int32_t inputs_are_device, float eta, float rho, float* losses_out) {
   return guard(e, [&](agz::Engine& E) { E.train_step(feats, pi, z, B, inputs_are_device != 0, eta, rho, losses_out); });
@@ -449,6 +461,10 @@ int32_t agz_abi_layout(const char* name, int32_t* out, int32_t cap) {
     AGZ_SZ(agz_analysis);
     AGZ_OFF(agz_analysis, move); AGZ_OFF(agz_analysis, status); AGZ_OFF(agz_analysis, N); AGZ_OFF(agz_analysis, W);
     AGZ_OFF(agz_analysis, Q); AGZ_OFF(agz_analysis, nodes_used);
+  } else if (n == "agz_line") {
+    AGZ_SZ(agz_line);
+    AGZ_OFF(agz_line, move); AGZ_OFF(agz_line, pv_len); AGZ_OFF(agz_line, N); AGZ_OFF(agz_line, W);
+    AGZ_OFF(agz_line, prior); AGZ_OFF(agz_line, end_W);
   } else {
     return -1;
   }

@@ -42,6 +42,10 @@ class Engine {
                     const int8_t* history, int64_t G, uint64_t game_id_base);
   int64_t analyze_progress();
   void analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior);
+  // analysis lines (agz_analyze_set_lines / agz_analyze_lines / agz_tree_lines): top-K candidates with their PVs
+  void analyze_set_lines(int K, int D, int min_visits);
+  void analyze_lines(agz_line* lines, int16_t* pv, float* pv_N);
+  void tree_lines(int g, int node, int K, int D, int min_visits, agz_line* lines, int16_t* pv, float* pv_N);
   void leaf_features_external(float* feats_out);
   void incorporate_external(const float* pi, const float* v);
 
@@ -190,6 +194,11 @@ class Engine {
   DevBuf<int16_t> rv_moves_;    // review mode: the recorded moves and game offsets (View::rv_*)
   DevBuf<int64_t> rv_off_;
   std::vector<int64_t> rv_off_host_;
+  int lines_k_ = 0, lines_d_ = 16, lines_min_ = 1;   // agz_analyze_set_lines: what the next start call switches on
+  DevBuf<agz_line> an_line_;    // [rows][K]       the lines tables of the current run (View::an_line / an_pv / an_pvN)
+  DevBuf<int16_t> an_pv_;       // [rows][K][D]
+  DevBuf<float> an_pvN_;        // [rows][K][D]
+  DevBuf<uint8_t> s_lines_;     // agz_tree_lines: lines, pv_N, pv of one node behind one another
   void check_positions(const char* mode, const char* item, const agz_position_info* info, const int8_t* history,
                        int64_t B);
   void upload_positions(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,

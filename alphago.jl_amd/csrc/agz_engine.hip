@@ -285,6 +285,15 @@ __global__ __launch_bounds__(kWave) void k_tree_op(View V, TreeArgs T) {
   tree_op(w, V, S, T);
 }
 
+// agz_tree_lines: node_lines for one node of single tree g (a kernel of its own: TreeArgs keeps its layout and
+// k_tree_op its registers)
+__global__ __launch_bounds__(kWave) void k_tree_lines(View V, int g, int node, int K, int D, int min_visits, agz_line* out,
+                                                       int16_t* pv, float* pv_N) {
+  AGZ_SCRATCH(S)
+  HipWave w;
+  node_lines(w, V, S, g, node, K, D, min_visits, out, pv, pv_N);
+}
+
 __global__ __launch_bounds__(kWave) void k_go_play(View V, const int8_t* boards, const int8_t* tp, const int32_t* ko,
                                                     const int32_t* moves, int B, int8_t* bo, int32_t* ko_o,
                                                     int32_t* nc, int32_t* st) {
@@ -763,7 +772,71 @@ void Engine::begin_analysis_run(int64_t B, int64_t rows, uint64_t game_id_base) 
   V_.an_childN = an_rows_.p;
   V_.an_childW = an_rows_.p + R * A;
   V_.an_prior = an_rows_.p + 2 * R * A;
+  // analysis lines (agz_analyze_set_lines): every slot of the three tables starts unused, which is what a row that is
+  // never searched keeps
+  V_.an_lines = lines_k_;
+  V_.an_pv_depth = lines_k_ ? lines_d_ : 0;
+  V_.an_pv_min = lines_k_ ? lines_min_ : 0;
+  V_.an_line = nullptr;
+  V_.an_pv = nullptr;
+  V_.an_pvN = nullptr;
+  if (lines_k_ > 0) {
+    const size_t nl = R * (size_t)lines_k_, np = nl * (size_t)lines_d_;
+    an_line_.ensure(nl);
+    an_pv_.ensure(np);
+    an_pvN_.ensure(np);
+    agz_line unused;
+    unused.move = -1; unused.pv_len = 0; unused.N = 0.f; unused.W = 0.f; unused.prior = 0.f; unused.end_W = 0.f;
+    const std::vector<agz_line> fill(nl, unused);
+    AGZ_HIP(hipMemcpyAsync(an_line_.p, fill.data(), sizeof(agz_line) * nl, hipMemcpyHostToDevice, stream_));
+    AGZ_HIP(hipMemsetAsync(an_pv_.p, 0xff, sizeof(int16_t) * np, stream_));
+    AGZ_HIP(hipMemsetAsync(an_pvN_.p, 0, sizeof(float) * np, stream_));
+    AGZ_HIP(hipStreamSynchronize(stream_));
+    V_.an_line = an_line_.p;
+    V_.an_pv = an_pv_.p;
+    V_.an_pvN = an_pvN_.p;
+  }
   external_batch_ = external_batch2_ = 0;
+}
+
+void Engine::analyze_set_lines(int K, int D, int min_visits) {
+  AGZ_REQUIRE(K >= 0 && K <= 16, AGZ_BAD_ARGUMENT, "lines: K = %d, not in 0..16", K);
+  AGZ_REQUIRE(D >= 1 && D <= 64, AGZ_BAD_ARGUMENT, "lines: D = %d, not in 1..64", D);
+  AGZ_REQUIRE(min_visits >= 1, AGZ_BAD_ARGUMENT, "lines: min_visits = %d, not >= 1", min_visits);
+  lines_k_ = K;
+  lines_d_ = D;
+  lines_min_ = min_visits;
+}
+
+void Engine::analyze_lines(agz_line* lines, int16_t* pv, float* pv_N) {
+  const int64_t done = analyze_progress(), B = an_count_;
+  AGZ_REQUIRE(V_.an_lines > 0, AGZ_BAD_ARGUMENT, "lines: the run was started with lines off (agz_analyze_set_lines)");
+  AGZ_REQUIRE(done >= B, AGZ_NOT_READY, "analysis: %lld of %lld rows finished", (long long)done, (long long)B);
+  const size_t nl = (size_t)B * V_.an_lines, np = nl * V_.an_pv_depth;
+  if (lines && nl) AGZ_HIP(hipMemcpyAsync(lines, an_line_.p, sizeof(agz_line) * nl, hipMemcpyDeviceToHost, stream_));
+  if (pv && np) AGZ_HIP(hipMemcpyAsync(pv, an_pv_.p, sizeof(int16_t) * np, hipMemcpyDeviceToHost, stream_));
+  if (pv_N && np) AGZ_HIP(hipMemcpyAsync(pv_N, an_pvN_.p, sizeof(float) * np, hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+}
+
+// the lines of any node of single tree g: one launch, one copy (the three tables lie behind one another in s_lines_)
+void Engine::tree_lines(int g, int node, int K, int D, int min_visits, agz_line* lines, int16_t* pv, float* pv_N) {
+  check_node(g, node);
+  AGZ_REQUIRE(K >= 1 && K <= 16, AGZ_BAD_ARGUMENT, "lines: K = %d, not in 1..16", K);
+  AGZ_REQUIRE(D >= 1 && D <= 64, AGZ_BAD_ARGUMENT, "lines: D = %d, not in 1..64", D);
+  AGZ_REQUIRE(min_visits >= 1, AGZ_BAD_ARGUMENT, "lines: min_visits = %d, not >= 1", min_visits);
+  const size_t kd = (size_t)K * D;
+  const size_t off_n = sizeof(agz_line) * K, off_pv = off_n + sizeof(float) * kd, total = off_pv + sizeof(int16_t) * kd;
+  s_lines_.ensure(total);
+  uint8_t* d = s_lines_.p;
+  hipLaunchKernelGGL(k_tree_lines, dim3(1), dim3(kWave), 0, stream_, V_, g, node, K, D, min_visits, (agz_line*)d,
+                     (int16_t*)(d + off_pv), (float*)(d + off_n));
+  std::vector<uint8_t> h(total);
+  AGZ_HIP(hipMemcpyAsync(h.data(), d, total, hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  if (lines) std::memcpy(lines, h.data(), off_n);
+  if (pv_N) std::memcpy(pv_N, h.data() + off_n, sizeof(float) * kd);
+  if (pv) std::memcpy(pv, h.data() + off_pv, sizeof(int16_t) * kd);
 }
 
 // ---- batched game review

@@ -1322,6 +1322,168 @@ AGZ_FN void arena_move_phase(W& w, const View& V, Scratch& S, int g) {
   w.sync();
 }
 
+// ---------------------------------------------------------------- analysis lines ----
+// The top-K candidates of a node and the principal variation (PV) behind each: most_visited_path, mvp_gg and describe
+// of mcts.jl:255-327 (commented out there; their text is the definition).  Every value is an exact read of a stored
+// row, no arithmetic, so a host walk over the same rows gives the same bits.  For a node X:
+//   * candidates of X: the actions a with child_N[a] > 0, by child_N descending, then child_prior descending, then a
+//     ascending; the first K are the lines.  (describe sorts by the action score second; the prior is a stored value.)
+//   * PV of candidate a, depth limit D >= 1, min_visits >= 1: pv[0] = a, c = child[X][a].  While len < D and c is a
+//     node: m = max of c's child_N; stop if m < min_visits; b = the lowest action with child_N == m (findmax, no draw);
+//     append b; c = child[c][b].  min_visits 1 is most_visited_path, 2 is mvp_gg (maximum(child_N) > 1).
+//   * pv_N[d] = the child_N entry pv[d] was chosen by.  Per line: the candidate's N, W, prior at X, end_W = the child_W
+//     entry of the last PV move, pv_len.
+//   * unused line slots: move -1, pv_len 0, floats 0; pv beyond pv_len: -1, pv_N 0.
+// The walk is level by level over groups of up to four lines: at one depth the group's rows are requested together
+// (R = ceil(A / 64) values per lane and line), then reduced, so a group costs about two dependent memory round trips
+// per level (the rows; then child / child_W of the chosen entries) whatever its size.
+
+constexpr int kLineGroup = 4;
+
+// One wave item per lane slot l (for_each over kWave: a lane of the GPU wave takes exactly its own l), R row entries
+// a = l + 64 r each; per-slot partials are combined by the reductions below.
+// The best untaken candidate of node row xi: (child_N, child_prior, a) in the candidate order, or -1 when none is left.
+template <int R, class W>
+AGZ_FN int lines_next_candidate(W& w, const View& V, const Scratch& S, long xi) {
+  const int A = V.A;
+  const float ninf = -__builtin_huge_valf();
+  float bn = ninf, bp = ninf;
+  int bi = kIntMax;
+  w.for_each(kWave, [&](int l) {
+    float vn[R], vp[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {                     // both rows first (clamped, not predicated), then the compares
+      const int a = l + kWave * r, aa = a < A ? a : A - 1;
+      vn[r] = V.childN[xi * V.AP + aa];
+      vp[r] = V.childP[xi * V.AP + aa];
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int a = l + kWave * r;
+      const float n = vn[r], p = vp[r];
+      const bool open = (a < A) & !S.flag[a < A ? a : 0] & (n > 0.0f);      // (& and |: nothing short-circuits a load)
+      const bool better = (n > bn) | ((n == bn) & ((p > bp) | ((p == bp) & (a < bi))));
+      if (open & better) { bn = n; bp = p; bi = a; }
+    }
+  });
+  const float mn = w.reduce_max_f(bn);
+  const float mp = w.reduce_max_f(bn == mn ? bp : ninf);
+  const int idx = w.reduce_min(bn == mn && bp == mp ? bi : kIntMax);
+  return idx == kIntMax ? -1 : idx;
+}
+
+// One PV level of a group: m[j] = max of child_N row[j], b[j] = its lowest action.  Every row is a valid node row (a
+// finished line passes any; its result is ignored), so all loads are issued before the first value is used.
+template <int R, class W>
+AGZ_FN void lines_level(W& w, const View& V, const long (&row)[kLineGroup], float (&m)[kLineGroup], int (&b)[kLineGroup]) {
+  const int A = V.A;
+  const float ninf = -__builtin_huge_valf();
+  float mx[kLineGroup];
+  int ix[kLineGroup];
+#pragma unroll
+  for (int j = 0; j < kLineGroup; ++j) { mx[j] = ninf; ix[j] = kIntMax; }
+  w.for_each(kWave, [&](int l) {
+    float v[kLineGroup][R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int a = l + kWave * r, aa = a < A ? a : A - 1;
+#pragma unroll
+      for (int j = 0; j < kLineGroup; ++j) v[j][r] = V.childN[row[j] * V.AP + aa];
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int a = l + kWave * r;
+      if (a >= A) continue;
+#pragma unroll
+      for (int j = 0; j < kLineGroup; ++j) {
+        const float c = v[j][r];
+        if (c > mx[j] || (c == mx[j] && a < ix[j])) { mx[j] = c; ix[j] = a; }
+      }
+    }
+  });
+#pragma unroll
+  for (int j = 0; j < kLineGroup; ++j) {
+    m[j] = w.reduce_max_f(mx[j]);
+    b[j] = w.reduce_min(mx[j] == m[j] ? ix[j] : kIntMax);
+  }
+}
+
+template <int R, class W>
+AGZ_FN void node_lines_rows(W& w, const View& V, Scratch& S, int g, int node, int K, int D, int min_visits,
+                            agz_line* out, int16_t* pv, float* pv_N) {
+  const long xi = node_index(V, g, node);
+  const int AP = V.AP;
+  const float need = (float)min_visits;
+  w.for_each(AP, [&](int a) { S.flag[a] = 0; });           // the "taken" mask of the candidates
+  w.for_each(K * D, [&](int i) { pv[i] = -1; pv_N[i] = 0.f; });
+  w.for_each(K, [&](int k) {
+    agz_line e;
+    e.move = -1; e.pv_len = 0; e.N = 0.f; e.W = 0.f; e.prior = 0.f; e.end_W = 0.f;
+    out[k] = e;
+  });
+  w.sync();
+  bool more = true;
+  for (int k0 = 0; k0 < K && more; k0 += kLineGroup) {
+    agz_line ln[kLineGroup];
+    int cur[kLineGroup];
+#pragma unroll
+    for (int j = 0; j < kLineGroup; ++j) {
+      ln[j].move = -1; ln[j].pv_len = 0; ln[j].N = 0.f; ln[j].W = 0.f; ln[j].prior = 0.f; ln[j].end_W = 0.f;
+      cur[j] = -1;
+      if (k0 + j >= K || !more) continue;
+      const int a = lines_next_candidate<R>(w, V, S, xi);
+      if (a < 0) { more = false; continue; }
+      ln[j].move = a; ln[j].pv_len = 1;
+      ln[j].N = V.childN[xi * AP + a]; ln[j].W = V.childW[xi * AP + a]; ln[j].prior = V.childP[xi * AP + a];
+      ln[j].end_W = ln[j].W;
+      cur[j] = V.child[xi * AP + a];
+      if (w.leader()) { S.flag[a] = 1; pv[(long)(k0 + j) * D] = (int16_t)a; pv_N[(long)(k0 + j) * D] = ln[j].N; }
+      w.sync();
+    }
+    for (int d = 1; d < D; ++d) {
+      long row[kLineGroup];
+      bool live[kLineGroup], any = false;
+#pragma unroll
+      for (int j = 0; j < kLineGroup; ++j) {
+        live[j] = cur[j] >= 0 && cur[j] < V.cap;
+        row[j] = live[j] ? node_index(V, g, cur[j]) : xi;
+        any = any || live[j];
+      }
+      if (!any) break;
+      float m[kLineGroup];
+      int b[kLineGroup];
+      lines_level<R>(w, V, row, m, b);
+#pragma unroll
+      for (int j = 0; j < kLineGroup; ++j) {
+        if (!live[j]) continue;
+        if (m[j] < need) { cur[j] = -1; continue; }
+        ln[j].pv_len = d + 1;
+        ln[j].end_W = V.childW[row[j] * AP + b[j]];
+        cur[j] = V.child[row[j] * AP + b[j]];
+        if (w.leader()) { pv[(long)(k0 + j) * D + d] = (int16_t)b[j]; pv_N[(long)(k0 + j) * D + d] = m[j]; }
+      }
+    }
+    if (w.leader()) {
+#pragma unroll
+      for (int j = 0; j < kLineGroup; ++j)
+        if (ln[j].move >= 0) out[k0 + j] = ln[j];
+    }
+  }
+  w.sync();
+}
+
+// the K lines of `node` of slot g into out [K], pv [K][D], pv_N [K][D] (all entries are written)
+template <class W>
+AGZ_FN void node_lines(W& w, const View& V, Scratch& S, int g, int node, int K, int D, int min_visits, agz_line* out,
+                       int16_t* pv, float* pv_N) {
+  switch ((V.A + kWave - 1) / kWave) {
+    case 1: node_lines_rows<1>(w, V, S, g, node, K, D, min_visits, out, pv, pv_N); break;
+    case 2: node_lines_rows<2>(w, V, S, g, node, K, D, min_visits, out, pv, pv_N); break;     // 9x9
+    case 3: node_lines_rows<3>(w, V, S, g, node, K, D, min_visits, out, pv, pv_N); break;     // 13x13
+    default: node_lines_rows<6>(w, V, S, g, node, K, D, min_visits, out, pv, pv_N);           // 19x19 (A <= 384)
+  }
+}
+
 // ---------------------------------------------------------------- batched analysis ----
 // suggest_move (mcts_play.jl:144-151) for caller positions i = 0..an_count-1, any number per slot (DESIGN.md "Batched
 // analysis").  G_IDLE: claim the next index, install position i as the root with draw key (seed, an_id_base + i) and
@@ -1350,6 +1512,11 @@ AGZ_FN void analysis_finish(W& w, const View& V, Scratch& S, int g) {
     V.an_childW[i * A + k] = V.childW[ri * V.AP + k];
     V.an_prior[i * A + k] = V.childP[ri * V.AP + k];
   });
+  if (V.an_lines > 0) {                                 // (review mode: before review_play re-roots)
+    const long long kd = (long long)V.an_lines * V.an_pv_depth;
+    node_lines(w, V, S, g, G.root, V.an_lines, V.an_pv_depth, V.an_pv_min, V.an_line + i * V.an_lines, V.an_pv + i * kd,
+               V.an_pvN + i * kd);
+  }
   if (w.leader()) {
     agz_analysis r;
     r.move = a; r.status = status; r.N = G.rootN; r.W = G.rootW; r.Q = G.rootW / (1.0f + G.rootN);

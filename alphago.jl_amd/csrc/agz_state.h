@@ -160,6 +160,13 @@ struct View {
   // next game only when agz_selfplay_release has set its flag, and clears the flag as it claims
   int32_t hold;
   int32_t* released;                  // [games]
+  // analysis lines (agz_analyze_set_lines; zero = off, the View{} of the host simulator): analysis_finish also writes
+  // the root's top an_lines candidates and their principal variations (node_lines, agz_search.h) into row
+  // analysis_row() of three more result tables
+  int32_t an_lines, an_pv_depth, an_pv_min;   // K, D, min_visits
+  agz_line* an_line;                  // [rows][K]
+  int16_t* an_pv;                     // [rows][K][D]
+  float* an_pvN;                      // [rows][K][D]
 };
 
 }  // namespace agz

@@ -23,7 +23,7 @@ using Random
 export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, train, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
-       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review,
+       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, node_lines, most_visited_path, mvp_gg,
        # the node-level surface test/test_mcts.jl:2-5 and test/test_mcts_player.jl:3-6 import
        MCTSNode, select_leaf, maybe_add_child!, add_virtual_loss!, revert_virtual_loss!,
        incorporate_results!, inject_noise!, child_action_score, child_Q, child_U, child_N, child_W,
@@ -70,6 +70,10 @@ end
 
 struct AgzAnalysis         # agz_analysis, include/agz.h: one position's result of analyze
   move::Int32; status::Int32; N::Float32; W::Float32; Q::Float32; nodes_used::Int32
+end
+
+struct AgzLine             # agz_line, include/agz.h: one candidate move with its principal variation
+  move::Int32; pv_len::Int32; N::Float32; W::Float32; prior::Float32; end_W::Float32
 end
 
 struct AgzStats            # agz_stats, include/agz.h: eighteen Int64 counters
@@ -588,6 +592,45 @@ function children(x::MCTSNode)                                                  
                  e.handle, 0, x.id, ids))
   Dict(f => MCTSNode(x.player, ids[f]) for f in eachindex(ids) if ids[f] >= 0)
 end
+# ---- analysis lines (ours; most_visited_path / mvp_gg / describe of mcts.jl:255-327, commented out there, are the
+# definition: include/agz.h "analysis lines").  A line is a NamedTuple: move and pv as board coordinates (nothing = pass,
+# pv[1] == move), N / W / prior = the candidate's entries of the node's rows, Q = W / (1 + N), pv_N[d] = the child_N entry
+# pv[d] was chosen by, end_Q = Q of the line's last move.
+kgs_name(c, env::GoEnv) = c === nothing ? "pass" : string("ABCDEFGHJKLMNOPQRST"[c[2]], env.N + 1 - c[1])
+function line_rows(env::GoEnv, ln::AbstractVector{AgzLine}, pv::AbstractMatrix{Int16}, pvn::AbstractMatrix{Float32})
+  out = NamedTuple[]
+  for k in eachindex(ln)
+    l = ln[k]
+    (l.move < 0 || l.pv_len < 1) && continue
+    n = Int(l.pv_len)
+    push!(out, (move = from_flat(l.move + 1, env), N = l.N, W = l.W, Q = l.W / (1f0 + l.N), prior = l.prior,
+                pv = [from_flat(Int(a) + 1, env) for a in pv[1:n, k]], pv_N = pvn[1:n, k],
+                end_Q = l.end_W / (1f0 + pvn[n, k])))
+  end
+  out
+end
+# the top k candidates of node x (child_N, then child_prior descending, then the move ascending) with their principal
+# variations of at most `depth` moves: one agz_tree_lines call, the walk runs on the device
+function node_lines(x::MCTSNode, k::Integer = 4, depth::Integer = 16, min_visits::Integer = 1)
+  e = x.player.engine
+  ln = Vector{AgzLine}(undef, k); pv = zeros(Int16, depth, k); pvn = zeros(Float32, depth, k)
+  check(e, ccall((:agz_tree_lines, libagz), Int32,
+                 (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32, Ptr{AgzLine}, Ptr{Int16}, Ptr{Float32}),
+                 e.handle, 0, x.id, k, depth, min_visits, ln, pv, pvn))
+  line_rows(x.player.env, ln, pv, pvn)
+end
+function most_visited_path(x::MCTSNode)                                         # mcts.jl:267-281
+  ln = node_lines(x, 1, 64, 1)
+  isempty(ln) && return @sprintf("Q: %.5f\n", Q(x))
+  env = x.player.env
+  join(["$(kgs_name(c, env)) ($(n)) ==> " for (c, n) in zip(ln[1].pv, ln[1].pv_N)]) * @sprintf("Q: %.5f\n", ln[1].end_Q)
+end
+function mvp_gg(x::MCTSNode)                                                    # mcts.jl:283-293
+  ln = node_lines(x, 1, 64, 2)
+  (isempty(ln) || !(ln[1].N > 1)) && return ""
+  join([kgs_name(c, x.player.env) for c in ln[1].pv], " ")
+end
+
 function position(x::MCTSNode)                                                  # the node's GoPosition, mcts.jl:44
   p = x.player; e = p.engine; env = p.env
   info = node_info(x)
@@ -759,7 +802,9 @@ end
 # root, child_N / child_W / child_Q / child_prior (length A), status (AGZ_OK, AGZ_BAD_ARGUMENT for an invalid board,
 # AGZ_POOL_EXHAUSTED, AGZ_ASSERT_SOFTPICK) and nodes_used.
 function analyze(env::GoEnv, nn::NeuralNet, positions::Vector{Position}; num_readouts::Int = 800, seed = 0,
-                 game_id_base = 0, slots::Union{Nothing, Int} = nothing, two_player_mode = false, symmetry = nothing)
+                 game_id_base = 0, slots::Union{Nothing, Int} = nothing, two_player_mode = false, symmetry = nothing,
+                 lines::Int = 0, pv_depth::Int = 16, pv_min_visits::Int = 1)
+  check_lines(lines, pv_depth, pv_min_visits)
   B, P, A = length(positions), env.N * env.N, env.action_space
   B == 0 && return NamedTuple[]
   boards = zeros(Int8, P, B); hist = zeros(Int8, P, 7, B); info = Vector{AgzPositionInfo}(undef, B)
@@ -773,6 +818,8 @@ function analyze(env::GoEnv, nn::NeuralNet, positions::Vector{Position}; num_rea
              max_nodes_per_game = 2 * num_readouts + 256)
   copy_weights!(e, nn.engine)
   symmetry === nothing || set_symmetry!(e, symmetry)
+  lines > 0 && check(e, ccall((:agz_analyze_set_lines, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Int32),
+                              e.handle, lines, pv_depth, pv_min_visits))
   check(e, ccall((:agz_analyze_start, libagz), Int32, (Ptr{Cvoid}, Ptr{Int8}, Ptr{AgzPositionInfo}, Ptr{Int8}, Int64, UInt64),
                  e.handle, boards, info, hist, B, game_id_base))
   done = Ref{Int64}(0)
@@ -786,9 +833,25 @@ function analyze(env::GoEnv, nn::NeuralNet, positions::Vector{Position}; num_rea
   cn, cw, pr = zeros(Float32, A, B), zeros(Float32, A, B), zeros(Float32, A, B)
   check(e, ccall((:agz_analyze_results, libagz), Int32, (Ptr{Cvoid}, Ptr{AgzAnalysis}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
                  e.handle, res, cn, cw, pr))
-  [(move = r.move < 0 ? nothing : from_flat(r.move + 1, env), N = r.N, W = r.W, Q = r.Q, child_N = cn[:, i],
-    child_W = cw[:, i], child_Q = cw[:, i] ./ (1f0 .+ cn[:, i]), child_prior = pr[:, i], status = Int(r.status),
-    nodes_used = Int(r.nodes_used)) for (i, r) in enumerate(res)]
+  rows = [(move = r.move < 0 ? nothing : from_flat(r.move + 1, env), N = r.N, W = r.W, Q = r.Q, child_N = cn[:, i],
+           child_W = cw[:, i], child_Q = cw[:, i] ./ (1f0 .+ cn[:, i]), child_prior = pr[:, i], status = Int(r.status),
+           nodes_used = Int(r.nodes_used)) for (i, r) in enumerate(res)]
+  lines > 0 || return rows
+  ln, pv, pvn = read_lines(e, B, lines, pv_depth)
+  [merge(rows[i], (lines = line_rows(env, ln[:, i], pv[:, :, i], pvn[:, :, i]),)) for i in 1:B]
+end
+
+function check_lines(lines, pv_depth, pv_min_visits)
+  0 <= lines <= 16 || throw(ArgumentError("lines must be in 0..16"))
+  1 <= pv_depth <= 64 || throw(ArgumentError("pv_depth must be in 1..64"))
+  pv_min_visits >= 1 || throw(ArgumentError("pv_min_visits must be >= 1"))
+end
+# the lines tables of a finished analysis / review run: lines K x rows, pv and pv_N D x K x rows
+function read_lines(e, rows, K, D)
+  ln = Matrix{AgzLine}(undef, K, rows); pv = zeros(Int16, D, K, rows); pvn = zeros(Float32, D, K, rows)
+  check(e, ccall((:agz_analyze_lines, libagz), Int32, (Ptr{Cvoid}, Ptr{AgzLine}, Ptr{Int16}, Ptr{Float32}),
+                 e.handle, ln, pv, pvn))
+  ln, pv, pvn
 end
 
 # review(env, nn, games; num_readouts) (ours): the loop of play() (src/play.jl:25-77) over recorded games in one device
@@ -800,7 +863,8 @@ end
 # the later ones of that game status AGZ_BAD_ARGUMENT.
 function review(env::GoEnv, nn::NeuralNet, games::Vector; num_readouts::Int = 800, starts = nothing,
                 two_player_mode = true, seed = 0, game_id_base = 0, slots::Union{Nothing, Int} = nothing,
-                symmetry = nothing)
+                symmetry = nothing, lines::Int = 0, pv_depth::Int = 16, pv_min_visits::Int = 1)
+  check_lines(lines, pv_depth, pv_min_visits)
   G, P, A = length(games), env.N * env.N, env.action_space
   G == 0 && return Vector{NamedTuple}[]
   num_readouts >= 1 || throw(ArgumentError("num_readouts must be >= 1"))
@@ -828,6 +892,8 @@ function review(env::GoEnv, nn::NeuralNet, games::Vector; num_readouts::Int = 80
              num_readouts = num_readouts, seed = seed, two_player_mode = two_player_mode)
   copy_weights!(e, nn.engine)
   symmetry === nothing || set_symmetry!(e, symmetry)
+  lines > 0 && check(e, ccall((:agz_analyze_set_lines, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Int32),
+                              e.handle, lines, pv_depth, pv_min_visits))
   check(e, ccall((:agz_review_start, libagz), Int32,
                  (Ptr{Cvoid}, Ptr{Int16}, Ptr{Int64}, Ptr{Int8}, Ptr{AgzPositionInfo}, Ptr{Int8}, Int64, UInt64),
                  e.handle, moves, off, boards, info, hist, G, game_id_base))
@@ -846,9 +912,11 @@ function review(env::GoEnv, nn::NeuralNet, games::Vector; num_readouts::Int = 80
   row(i, j0) = (r = res[i]; (move = r.move < 0 ? nothing : from_flat(r.move + 1, env), N = r.N, W = r.W, Q = r.Q,
             child_N = cn[:, i], child_W = cw[:, i], child_Q = cw[:, i] ./ (1f0 .+ cn[:, i]), child_prior = pr[:, i],
             status = Int(r.status), nodes_used = Int(r.nodes_used), game_id = UInt64(game_id_base + j0)))
+  ln, pv, pvn = lines > 0 ? read_lines(e, total, lines, pv_depth) : (nothing, nothing, nothing)
+  withlines(i, r) = lines > 0 ? merge(r, (lines = line_rows(env, ln[:, i], pv[:, :, i], pvn[:, :, i]),)) : r
   out = Vector{Vector{NamedTuple}}(undef, G)
   for j in 1:G
-    out[j] = [row(i, j - 1) for i in off[j]+1:off[j+1]]
+    out[j] = [withlines(i, row(i, j - 1)) for i in off[j]+1:off[j+1]]
   end
   out
 end

@@ -428,7 +428,7 @@ agz_status agz_broadcast_weights(agz_engine* e, agz_comm* comm, int32_t root, in
 /* ---------------------------------------------------------------- ABI self-description --- */
 /* sizeof and field offsets of the PODs above as this library was compiled, so that a host mirror (ctypes
  * Structure, Julia struct) can be checked against them: name in {"agz_config", "agz_stats",
- * "agz_game_header", "agz_position_info", "agz_node_info", "agz_analysis"}; out[0] = sizeof, out[1..n] = offsetof of the n
+ * "agz_game_header", "agz_position_info", "agz_node_info", "agz_analysis", "agz_line"}; out[0] = sizeof, out[1..n] = offsetof of the n
  * fields in declaration order; returns n, or -1 for an unknown name / too small a buffer. */
 int32_t agz_abi_layout(const char* name, int32_t* out, int32_t cap);
 
@@ -564,6 +564,37 @@ agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N,
  * statistics reached, the later rows none; all move -1). */
 agz_status agz_review_start(agz_engine* e, const int16_t* moves, const int64_t* game_offset, const int8_t* boards,
                             const agz_position_info* info, const int8_t* history, int64_t G, uint64_t game_id_base);
+
+/* ---------------------------------------------------------------- analysis lines -------- */
+/* The top-K candidate moves of a searched node and the principal variation (PV) the search expects behind each: what
+ * most_visited_path, mvp_gg and describe of src/mcts.jl:255-327 define (commented out there; their text is the
+ * definition followed here).  All values are exact reads of the node rows child_N / child_W / child_prior / children,
+ * no arithmetic.  For a node X:
+ *   candidates of X: the actions a with child_N[a] > 0, by child_N descending, then child_prior descending, then a
+ *     ascending; the first K are the lines.  (describe's second key is the action score; the prior is a stored value,
+ *     so the order is reproducible bit for bit by anyone who reads the rows.)
+ *   PV of candidate a, depth limit D >= 1, min_visits >= 1: pv[0] = a, c = child of X under a.  While pv_len < D and c
+ *     is a node: m = max of c's child_N; stop if m < min_visits; b = the lowest action with child_N == m (findmax, no
+ *     draw); append b; c = child of c under b.  min_visits 1 is most_visited_path, 2 is mvp_gg (maximum(child_N) > 1).
+ *   pv_N[d] = the child_N entry pv[d] was chosen by (pv_N[0] = the candidate's N).  Per line: the candidate's N, W and
+ *     prior at X, end_W = the child_W entry of the last PV move (Q of the line's end = end_W / (1 + pv_N[pv_len-1])).
+ *   Unused line slots: move -1, pv_len 0, the floats 0; pv entries beyond pv_len: -1, pv_N 0.
+ * Off by default; with it off every table, record and counter of a run is what it is without this section. */
+typedef struct {
+  int32_t move, pv_len;
+  float N, W, prior, end_W;
+} agz_line;
+/* K = 0 switches lines off (default).  0 <= K <= 16, 1 <= D <= 64, min_visits >= 1.  Takes effect at the next
+ * agz_analyze_start / agz_review_start: every finished search then also writes the lines of its root, taken when the
+ * search ended (in a review run: before the recorded move re-roots the tree).  Rows that are never searched keep K
+ * unused slots. */
+agz_status agz_analyze_set_lines(agz_engine* e, int32_t K, int32_t D, int32_t min_visits);
+/* lines [rows][K], pv [rows][K][D], pv_N [rows][K][D]; any may be NULL.  AGZ_NOT_READY until every row is
+ * finished; AGZ_BAD_ARGUMENT when the run was started with lines off. */
+agz_status agz_analyze_lines(agz_engine* e, agz_line* lines, int16_t* pv, float* pv_N);
+/* the same for any node of single tree g (the MCTSPlayer path): one launch, one copy */
+agz_status agz_tree_lines(agz_engine* e, int32_t g, int32_t node, int32_t K, int32_t D, int32_t min_visits,
+                          agz_line* lines, int16_t* pv, float* pv_N);
 
 /* Test hooks (device-side evaluation of the draw stream, single-tree introspection setters) are declared in
  * include/agz_debug.h: exported by the library for the parity tests, not part of the drop-in surface. */

@@ -5,6 +5,9 @@ tower 10, R = 400, 1024 slots), on mid-game positions taken from self-play recor
   2. positions/s of MCTSPlayer.initialize_game + suggest_move (the single-tree path) on a --sample of them;
   3. ms per step of an analysis run next to ms per self-play step, engines of the same shape, alternating windows.
 The records come from a short self-play run at --gen-readouts readouts (only the positions matter, not their quality).
+With --lines K (and --pv-depth D) it measures the cost of the analysis lines instead: two analysis runs
+over the same positions on engines of the same shape in this process, lines on and lines off, in alternating windows of
+--steps steps, then the search kernels of both under the engine's event profile.
 Prints one JSON object."""
 import argparse
 import json
@@ -61,6 +64,80 @@ def positions_at(ag, env, picks):
     return out
 
 
+def lines_cost(ag, args, env, nn, positions, gen_s):
+    """ms per analysis step with lines on against lines off: alternating windows, the runs in step with each other (a
+    slot finishes a search about every readouts / 8 steps, so the windows have to span several times that), then the
+    search kernels of the runs over further steps.  The allowance is the one DESIGN.md §5f derives: the off median plus
+    D + 2 dependent round trips (k_leaf_features reads as three of them) plus the off windows' own spread."""
+    N, R, S, K, D = args.board, args.readouts, args.slots, args.lines, args.pv_depth
+    P = N * N
+    shape = dict(board_size=N, tower_height=args.tower, games=S, num_readouts=R, parallel_readouts=8, seed=1,
+                 max_nodes_per_game=2 * R + 256)
+    boards = np.zeros((len(positions), P), np.int8)
+    hist = np.zeros((len(positions), 7, P), np.int8)
+    infos = (ag._lib.PositionInfo * len(positions))()
+    for k, p in enumerate(positions):
+        boards[k], infos[k], h = ag.position_arrays(p)
+        hist[k, :len(h)] = h
+    # two engines per arm, created off, on, on2, off2: the second pair is the A/A control that tells an engine-instance
+    # effect (where its buffers landed) from the cost of the lines
+    names = tuple(args.engine_order.split(","))
+    assert sorted(names) == ["off", "off2", "on", "on2"], "--engine-order is a permutation of off,on,on2,off2"
+    eng = {}
+    for name in names:
+        e = eng[name] = ag.Engine(**shape)
+        nn.engine.copy_weights_to(e)
+        if name.startswith("on"):
+            e.analyze_set_lines(K, D, args.pv_min_visits)
+        e.analyze_start(boards, infos, hist, 0)
+        e.step(10)
+        e.sync()
+    windows = {name: [] for name in names}
+    for k in range(args.pairs):
+        for j in range(len(names)):
+            name = names[(j + k) % len(names)]
+            e = eng[name]
+            t0 = time.perf_counter()
+            e.step(args.steps)
+            e.sync()
+            windows[name].append(1e3 * (time.perf_counter() - t0) / args.steps)
+    done_windows = {name: eng[name].analyze_progress() for name in names}
+    kernels, prof_steps = {}, min(512, args.steps * max(1, args.pairs // 2))
+    for name, e in eng.items():
+        e.profile_search(True)
+        e.step(prof_steps)
+        ms, n = e.profile_search_read()
+        e.profile_search(False)
+        kernels[name] = {k: round(1e3 * v / max(n, 1), 2) for k, v in ms.items()}        # us per step
+    done_end = {name: eng[name].analyze_progress() for name in names}
+    for e in eng.values():
+        e.close()
+    # One of four engines of one shape in one process has run 1.7-1.9 ms per step slower than the other three in every
+    # run so far, whichever arm it belonged to (the second one created: profiles/analysis_lines_configs1.json), so each
+    # arm is read off its faster engine, and the A/A differences are quoted beside it.
+    med = {name: statistics.median(w) for name, w in windows.items()}
+    best_off = min(("off", "off2"), key=lambda n: med[n])
+    best_on = min(("on", "on2"), key=lambda n: med[n])
+    m_off, m_on = med[best_off], med[best_on]
+    spread = max(windows[best_off]) - min(windows[best_off])
+    trip_us = kernels[best_off]["k_leaf_features"] / 3
+    allowance = m_off + (D + 2) * trip_us / 1e3 + spread
+    return dict(
+        shape=dict(board=N, tower=args.tower, readouts=R, slots=S), positions=len(positions),
+        generation=dict(readouts=args.gen_readouts, seconds=round(gen_s, 1)),
+        lines=dict(K=K, pv_depth=D, pv_min_visits=args.pv_min_visits),
+        step_ms=dict(steps_per_window=args.steps, engines_in_creation_order=list(names), windows=windows,
+                     median_by_engine={n: round(v, 3) for n, v in med.items()},
+                     off_vs_off2=round(abs(med["off"] - med["off2"]), 3), on_vs_on2=round(abs(med["on"] - med["on2"]), 3),
+                     off_engine=best_off, on_engine=best_on, off_median=round(m_off, 3), on_median=round(m_on, 3),
+                     off_spread=round(spread, 3), on_minus_off=round(m_on - m_off, 3),
+                     on_over_off=round(m_on / m_off, 4)),
+        rows_finished_after_windows=done_windows, rows_finished_at_end=done_end,
+        search_kernels_us_per_step=dict(steps=prof_steps, **kernels),
+        allowance=dict(round_trip_us=round(trip_us, 2), allowance_ms=round(allowance, 3),
+                       within=bool(m_on <= allowance)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--board", type=int, default=9)
@@ -72,6 +149,11 @@ def main():
     ap.add_argument("--gen-readouts", type=int, default=32)
     ap.add_argument("--steps", type=int, default=10, help="steps per timing window")
     ap.add_argument("--pairs", type=int, default=4)
+    ap.add_argument("--lines", type=int, default=0, help="K > 0: compare analysis steps with K lines on against lines off")
+    ap.add_argument("--pv-depth", type=int, default=16)
+    ap.add_argument("--pv-min-visits", type=int, default=1)
+    ap.add_argument("--engine-order", default="off,on,on2,off2",
+                    help="--lines: creation order of the four engines (two with lines on, two off)")
     args = ap.parse_args()
 
     import alphago_jl_amd as ag
@@ -88,6 +170,10 @@ def main():
     gen_s = time.perf_counter() - t0
     P = N * N
     positions = positions_from_records(ag, env, recs, args.positions, P // 8, P // 2, rng)
+
+    if args.lines > 0:
+        print(json.dumps(lines_cost(ag, args, env, nn, positions, gen_s)))
+        return
 
     # 1. analyze
     ag.analyze(env, nn, positions[:S], num_readouts=R, slots=S)        # warm-up (kernel loading, allocation)
