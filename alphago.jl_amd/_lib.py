@@ -150,6 +150,8 @@ def load():
         "agz_selfplay_set_symmetry": (i32, [E, i32]),
         "agz_selfplay_set_hold": (i32, [E, i32]),
         "agz_selfplay_release": (i32, [E]),
+        "agz_selfplay_set_starts": (i32, [E, i8p, P(PositionInfo), i8p, i64]),
+        "agz_selfplay_starts_count": (i64, [E]),
         "agz_analyze_start": (i32, [E, i8p, P(PositionInfo), i8p, i64, u64]),
         "agz_review_start": (i32, [E, P(C.c_int16), P(i64), i8p, P(PositionInfo), i8p, i64, u64]),
         "agz_analyze_progress": (i32, [E, P(i64)]),
@@ -173,6 +175,7 @@ def load():
         "agz_net_select": (i32, [E, i32]),
         "agz_records_features": (i32, [E, i64, f32p]),
         "agz_replay_features": (i32, [E, i16p, i64, i32p, i32p, i32, C.c_void_p, i32]),
+        "agz_replay_features_starts": (i32, [E, i16p, i64, i32p, i32p, i32p, i32, C.c_void_p, i32]),
         "agz_replay_ingest_packed": (i32, [E, C.c_void_p, i64, i32, P(i64)]),
         "agz_replay_ingest_gathered": (i32, [E, C.c_void_p, i32, i32, i64, P(i64), P(i64)]),
         "agz_replay_count": (i64, [E]),

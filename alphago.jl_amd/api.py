@@ -589,10 +589,17 @@ class SelfPlayPlayer:
     `.result`, `.result_string`, `.qs`, `.searches_pi` (mcts_play.jl:3-15) as the device recorded them,
     `.root.position` (the final GoPosition with its whole `recent` list: `.n`, `.board`, `.caps`, ...) and
     `extract_data(player)`.  The tree itself stayed on the device and was recycled with its slot.  Also carries the
-    record's fields (`game_id`, `moves` as board coordinates / None, `was_resign`, `short_searches`)."""
+    record's fields (`game_id`, `moves` as board coordinates / None, `was_resign`, `short_searches`).  `start` (ours) is
+    the Position the game began at -- an entry of selfplay(..., starts=...) -- or None for the empty board: the moves,
+    searches_pi and qs cover the plies played from there; `start_index` is that entry's index in the table (-1: none),
+    which is what ReplayBuffer keeps to replay the game on the device."""
 
-    def __init__(self, env, network, num_readouts, rec):
+    def __init__(self, env, network, num_readouts, rec, start=None):
         self.env, self.network, self.num_readouts = env, network, num_readouts
+        self.start = start
+        self.start_index = int(rec.get("start", -1)) if start is not None else -1
+        if start is not None and self.start_index < 0:
+            raise ValueError("a start position needs the record's `start` index (Engine.records())")
         self.two_player_mode = False
         self.tau_threshold = (env.N * env.N // 12) // 2 * 2
         self.game_id = int(rec["game_id"])
@@ -614,7 +621,7 @@ class SelfPlayPlayer:
     def _replay(self):
         """replay_position (board.jl:557-578): the positions before each move and the final one, by agz_go_play"""
         if self._replayed is None:
-            pos, before = Position(self.env), []
+            pos, before = (Position(self.env) if self.start is None else self.start), []
             for c in self.moves:
                 before.append(pos)
                 pos = pos.play_move(c)
@@ -632,7 +639,8 @@ class SelfPlayPlayer:
         return True
 
     def extract_data(self):                    # mcts_play.jl:126-139
-        assert len(self.searches_pi) == self.root.position.n, "GoPosition history is incomplete"
+        start_n = 0 if self.start is None else self.start.n
+        assert len(self.searches_pi) == self.root.position.n - start_n, "GoPosition history is incomplete"
         before, _ = self._replay()
         return list(before), [p.copy() for p in self.searches_pi], [self.result] * len(before)
 
@@ -649,13 +657,15 @@ def seed(s):
 
 
 def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="f32", game_id_base=None, symmetry=None,
-             **cfg):
+             starts=None, **cfg):
     """selfplay(env, nn, num_ro) (src/selfplay.jl:1-45) -> the finished game's player (SelfPlayPlayer), exactly the
     call train() makes (train.jl:57).  `games=G` (ours) plays G games concurrently on the device and returns a list of
     G such players ordered by game id.  Game ids continue from the previous call (module stream, `seed()`), unless
     `seed` / `game_id_base` pin them.  precision="f16" plays with the fp16-operand tower; default exact f32.
     symmetry (ours): None (the reference's search), "random" (every leaf evaluated under a drawn board symmetry) or a
-    fixed s in 0..7 (Engine.set_symmetry)."""
+    fixed s in 0..7 (Engine.set_symmetry).  starts (ours): a list of Positions; the game with id gid begins at
+    starts[gid % len(starts)] (initialize_game!(player, pos), mcts_play.jl:110-118) instead of the empty board, and its
+    player carries that Position as `.start` (Engine.set_starts)."""
     single = games is None
     games = 1 if single else int(games)
     if seed is None:
@@ -672,6 +682,8 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     eng.set_precision(precision)
     if symmetry is not None:
         eng.set_symmetry(symmetry)
+    if starts:
+        eng.set_starts(starts)
     eng.start(games)
     while eng.records_count() < games:
         eng.step(16)
@@ -679,7 +691,7 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
             eng.close()
             raise _lib.AgzError(_lib.POOL_EXHAUSTED, "a game is waiting on a full node pool (pool_policy = stall): raise "
                                                      "max_nodes_per_game or use the default policy")
-    out = [SelfPlayPlayer(env, nn, num_ro, r) for r in eng.records()]
+    out = [SelfPlayPlayer(env, nn, num_ro, r, starts[r["start"]] if starts else None) for r in eng.records()]
     eng.close()
     return out[0] if single else out
 
@@ -910,14 +922,16 @@ EvalStats = namedtuple("EvalStats", "games_won num_games win_rate resigned moves
 
 
 def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, seed=0, slots=None,
-             return_stats=False, symmetry=None, **cfg):
+             return_stats=False, symmetry=None, starts=None, **cfg):
     """evaluate(env, black_net, white_net; num_games, ro) (src/neural_net.jl:103-158): black_net plays
     Black and white_net White in `num_games` games of two two_player_mode MCTSPlayers (arg-max moves,
     no noise, resign at -0.9); True iff Black's win rate reaches 0.55.  All games run concurrently on
     the device (arena_mode: one slot pair per game, both networks resident).  The tally follows the
     reference literally: a game counts for Black when `result(black.root.position) == BLACK`, i.e.
     by the Tromp-Taylor score of the final position, also after a resignation (:147).  symmetry (ours): as for
-    selfplay(), applied to both networks' evaluations."""
+    selfplay(), applied to both networks' evaluations.  starts (ours): an opening suite -- game g begins at the Position
+    starts[g % len(starts)] with komi, stones and side to move as given there; the player of the colour to move searches
+    first, black_net still plays Black.  The records (return_stats) carry the entry as `start`."""
     if black_net.tower_height != white_net.tower_height:
         raise ValueError("the arena keeps both networks in one engine: tower heights must match")
     pairs = min(num_games, 512) if slots is None else slots
@@ -929,6 +943,8 @@ def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, se
     eng.net_select(0)
     if symmetry is not None:
         eng.set_symmetry(symmetry)
+    if starts:
+        eng.set_starts(starts)
     eng.start(num_games)
     while eng.records_count() < num_games:
         eng.step(16)
@@ -1023,7 +1039,8 @@ def _minibatch_cuts(n):
 
 def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp_freq=1000, readouts=800,
           tower_height=19, model=None, start_training_after=50000, slots=None, seed=0, game_id_base=0, symmetry=None,
-          augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, **cfg):
+          augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, starts=None,
+          **cfg):
     """train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model,
     start_training_after) (src/train.jl:38-92) with `slots` games in flight on the device.  One engine
     plays, keeps the replay arena and trains; per step: agz_selfplay_step(1), one read of how many games finished, and
@@ -1037,7 +1054,9 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
     checkpoint_dir (save_model into checkpoint_dir/game_<i> every ckp_freq games; None: no checkpoints), callback (what
     the reference prints goes here), return_log (also return one dict per game), profile (a dict filled with steps,
     wall_s, train_s, train_steps, positions and host_syncs: the library calls of the loop that synchronise the engine's
-    stream, each at least once; tools/train_rate.py).  Returns the trained NeuralNet (model itself when given)."""
+    stream, each at least once; tools/train_rate.py), starts (a list of Positions: the game with id gid begins at
+    starts[gid % len(starts)], and the replay arena rebuilds its training positions from there; as in selfplay).
+    Returns the trained NeuralNet (model itself when given)."""
     import time
     import torch
     from . import bson_weights as bw
@@ -1064,6 +1083,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
         pi = torch.empty((batch_size, eng.A), dtype=torch.float32, device=dev)
         z = torch.empty(batch_size, dtype=torch.float32, device=dev)
         cuts = _minibatch_cuts(batch_size)
+        if starts:
+            eng.set_starts(starts)
         eng.set_hold(True)
         eng.start(num_games)
         eng.release()

@@ -272,6 +272,7 @@ agz_status agz_replay_ingest_gathered(agz_engine* e, const void* buf, int32_t is
   });
 }
 int64_t agz_replay_count(agz_engine* e) { return (e && e->impl) ? e->impl->replay_count() : -1; }
+int64_t agz_selfplay_starts_count(agz_engine* e) { return (e && e->impl) ? e->impl->starts_count() : -1; }
 int64_t agz_replay_positions(agz_engine* e) { return (e && e->impl) ? e->impl->replay_positions() : -1; }
 agz_status agz_replay_header(agz_engine* e, int64_t k, agz_game_header* out) {
   return guard(e, [&](agz::Engine& E) {
@@ -309,6 +310,10 @@ agz_status agz_selfplay_set_hold(agz_engine* e, int32_t on) {
   return guard(e, [&](agz::Engine& E) { E.set_hold(on != 0); });
 }
 agz_status agz_selfplay_release(agz_engine* e) { return guard(e, [&](agz::Engine& E) { E.release(); }); }
+agz_status agz_selfplay_set_starts(agz_engine* e, const int8_t* boards, const agz_position_info* info,
+                                   const int8_t* history, int64_t S) {
+  return guard(e, [&](agz::Engine& E) { E.set_starts(boards, info, history, S); });
+}
 agz_status agz_device_alloc(agz_engine* e, int64_t bytes, void** out) {
   return guard(e, [&](agz::Engine& E) {
     AGZ_REQUIRE(out && bytes > 0, AGZ_BAD_ARGUMENT, "bad allocation request");
@@ -480,6 +485,14 @@ agz_status agz_replay_features(agz_engine* e, const int16_t* moves, int64_t nmov
   return guard(e, [&](agz::Engine& E) {
     AGZ_REQUIRE(B == 0 || (game_offset && ply && out && (moves || nmoves == 0)), AGZ_BAD_ARGUMENT, "null pointer");
     E.replay_batch_features(moves, nmoves, game_offset, ply, B, out, out_is_device != 0);
+  });
+}
+agz_status agz_replay_features_starts(agz_engine* e, const int16_t* moves, int64_t nmoves, const int32_t* game_offset,
+                                      const int32_t* ply, const int32_t* start, int32_t B, float* out,
+                                      int32_t out_is_device) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(B == 0 || (game_offset && ply && out && (moves || nmoves == 0)), AGZ_BAD_ARGUMENT, "null pointer");
+    E.replay_batch_features(moves, nmoves, game_offset, ply, B, out, out_is_device != 0, start);
   });
 }
 

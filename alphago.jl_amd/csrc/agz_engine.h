@@ -40,6 +40,9 @@ class Engine {
   // batched game review (agz_review_start): play() over G recorded games on reused trees, rows read as in analysis
   void review_start(const int16_t* moves, const int64_t* game_offset, const int8_t* boards, const agz_position_info* info,
                     const int8_t* history, int64_t G, uint64_t game_id_base);
+  // start positions of self-play / arena games and of everything that replays their records (agz_selfplay_set_starts)
+  void set_starts(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t S);
+  int64_t starts_count() const { return V_.st_count; }
   int64_t analyze_progress();
   void analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior);
   // analysis lines (agz_analyze_set_lines / agz_analyze_lines / agz_tree_lines): top-K candidates with their PVs
@@ -95,8 +98,9 @@ class Engine {
   // flat parameter vector of the selected network in layers() order (broadcast_weights)
   std::vector<float> weights_flat();
   void weights_set_flat(const std::vector<float>& w);
+  // start != NULL: sample b's move list begins at table entry start[b], -1 = the empty board (agz_replay_features_starts)
   void replay_batch_features(const int16_t* moves, int64_t nmoves, const int32_t* off, const int32_t* ply, int B,
-                             float* out, bool out_is_device);
+                             float* out, bool out_is_device, const int32_t* start = nullptr);
 
   // network
   void net_forward_positions(const int8_t* boards, const int8_t* deltas, const int32_t* ndeltas,
@@ -220,6 +224,8 @@ class Engine {
   DevBuf<int8_t> smp_boards_;
   DevBuf<float> smp_f_, smp_p_;
   DevBuf<int32_t> hold_rel_;        // View::released
+  DevBuf<int8_t> st_board_, st_hist_;       // the start-position table in force (View::st_*)
+  DevBuf<agz_position_info> st_info_;
   int64_t rec_sent_ = 0;
   bool stepped_ = false;           // a step has run since the last start(): agz_debug_set_stagger is refused
 };

@@ -323,17 +323,27 @@ __global__ __launch_bounds__(kWave) void k_go_score(View V, const int8_t* boards
 
 // replay_position (board.jl:557-578) on the device: rebuild the 17 planes of positions of a game
 // from its move list.  One wave walks one game: block b replays moves[off[b] .. off[b]+nm[b]) from
-// the empty board and writes the features of the position BEFORE move k for every k >= emit_from[b]
-// to out + out_off[b] + (k - emit_from[b]) * 17*P.  (record_features: one block, emit_from 0;
+// the empty board, Black first -- or, with start >= 0, from entry `start` of the start-position table (View::st_*:
+// its board, its to_play and its history_len real older boards as the history planes) -- and writes the features of
+// the position BEFORE move k for every k >= emit_from[b] to out + out_off[b] + (k - emit_from[b]) * 17*P.  (record_features: one block, emit_from 0;
 // get_replay_batch, train.jl:4-12: one block per sampled (game, ply), nm = ply+1, emit_from = ply.)
 template <class W>
 __device__ __forceinline__ void replay_emit(W& w, const View& V, Scratch& S, const int16_t* moves, int nm, int from,
-                                            int8_t* hist, float* out) {
+                                            int8_t* hist, float* out, long start = -1) {
   const int P = V.P;
   // hist[0] = current board, hist[k] = k moves ago; avail = number of real older boards
   w.for_each(8 * V.PP, [&](int i) { hist[i] = 0; });
   w.sync();
   int tp = 1, avail = 0;
+  if (start >= 0) {
+    const agz_position_info f = V.st_info[start];
+    tp = f.to_play;
+    avail = f.history_len < 7 ? f.history_len : 7;
+    w.for_each(P, [&](int p) { hist[p] = V.st_board[start * P + p]; });
+    for (int h = 0; h < avail; ++h)
+      w.for_each(P, [&](int p) { hist[(h + 1) * V.PP + p] = V.st_hist[(start * 7 + h) * P + p]; });
+    w.sync();
+  }
   for (int k = 0; k < nm; ++k) {
     if (k >= from) {
       w.for_each(P, [&](int p) {
@@ -374,11 +384,27 @@ __global__ __launch_bounds__(kWave) void k_replay_features(View V, const int16_t
                                                             const int32_t* nms, const int32_t* emit_from,
                                                             const int64_t* out_off,
                                                             int8_t* hist_all /*[blocks][8][PP] scratch in HBM*/,
-                                                            float* out_all) {
+                                                            float* out_all, const int32_t* start /*[blocks] or NULL*/) {
   AGZ_SCRATCH(S)
   HipWave w;
   const int b = blockIdx.x;
-  replay_emit(w, V, S, moves + off[b], nms[b], emit_from[b], hist_all + (long)b * 8 * V.PP, out_all + out_off[b]);
+  replay_emit(w, V, S, moves + off[b], nms[b], emit_from[b], hist_all + (long)b * 8 * V.PP, out_all + out_off[b],
+              start ? (long)start[b] : -1);
+}
+
+// the table entry a record's game began at, by the index rule of agz_selfplay_set_starts; -1: no table, the empty board
+__host__ __device__ inline long record_start(const View& V, uint64_t game_id) {
+  return V.st_count > 0 ? (long)((V.arena ? game_id >> 1 : game_id) % (uint64_t)V.st_count) : -1;
+}
+
+// agz_selfplay_set_starts: one wave per candidate entry, ok[s] = its board passes root_board_valid
+__global__ __launch_bounds__(kWave) void k_starts_valid(View V, const int8_t* boards, const agz_position_info* info,
+                                                         int32_t* ok) {
+  AGZ_SCRATCH(S)
+  HipWave w;
+  const long s = blockIdx.x;
+  const bool good = root_board_valid(w, V, S, boards + s * V.P, info[s].ko);
+  if (w.leader()) ok[s] = good;
 }
 
 // ---- the device replay arena (agz_replay_*): packed records
@@ -452,7 +478,8 @@ __global__ __launch_bounds__(kWave) void k_replay_arena_batch(View V, const uint
   const int16_t* mv = reinterpret_cast<const int16_t*>(r + sizeof(agz_game_header));
   const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * (size_t)h.num_moves + 3) & ~(size_t)3;
   const float* pi = reinterpret_cast<const float*>(r + o_pi) + (size_t)ply[b] * A;
-  replay_emit(w, V, S, mv, ply[b] + 1, ply[b], hist_all + (long)b * 8 * V.PP, feats + (long)b * 17 * V.P);
+  replay_emit(w, V, S, mv, ply[b] + 1, ply[b], hist_all + (long)b * 8 * V.PP, feats + (long)b * 17 * V.P,
+              record_start(V, h.game_id));
   if (pi_out) w.for_each(A, [&](int i) { pi_out[(long)b * A + i] = pi[i]; });
   if (z_out && w.leader()) z_out[b] = (float)h.result;
 }
@@ -709,6 +736,75 @@ void Engine::analyze_start(const int8_t* boards, const agz_position_info* info, 
   V_.rv_moves = nullptr;
   V_.rv_off = nullptr;
   begin_analysis_run(B, B, game_id_base);
+}
+
+// ---- start positions of self-play and arena games (agz_selfplay_set_starts)
+
+void Engine::set_starts(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t S) {
+  AGZ_REQUIRE(S >= 0 && S <= 0x7fffffffLL, AGZ_BAD_ARGUMENT, "starts: S = %lld", (long long)S);
+  AGZ_REQUIRE(S == 0 || (boards && info), AGZ_BAD_ARGUMENT, "starts: boards and info of S positions");
+  AGZ_REQUIRE(S == 0 || V_.stagger == 0, AGZ_BAD_ARGUMENT,
+              "starts: a table and the bench stagger exclude each other (the stagger prefix starts on the empty board)");
+  // records are rebuilt through the table: it changes only while nothing is kept that was played under the old one
+  const int64_t held = records_count();
+  AGZ_REQUIRE(held == 0 && rp_hdr_.empty(), AGZ_BAD_ARGUMENT,
+              "starts: the record ring holds %lld games and the replay arena %lld; clear both first", (long long)held,
+              (long long)rp_hdr_.size());
+  // ... and while no game is on its way into the ring (a run that has not stepped yet has claimed none: the table set
+  // there is that run's)
+  if (!V_.analysis && stepped_) {
+    agz_stats st;
+    stats(&st);
+    AGZ_REQUIRE(st.live_games == 0, AGZ_BAD_ARGUMENT, "starts: %lld games of the current run are still being played",
+                (long long)st.live_games);
+  }
+  const int P = V_.P, mgl = V_.max_game_length;
+  if (S > 0) {
+    check_positions("starts", "entry", info, history, S);
+    for (int64_t i = 0; i < S; ++i) {
+      AGZ_REQUIRE(!(info[i].last_move == P && info[i].prev_move == P), AGZ_BAD_ARGUMENT,
+                  "starts: entry %lld is a finished game (two passes)", (long long)i);
+      AGZ_REQUIRE(info[i].n < mgl, AGZ_BAD_ARGUMENT, "starts: entry %lld is a finished game (n %d >= max_game_length %d)",
+                  (long long)i, info[i].n, mgl);
+    }
+  }
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  if (S == 0) {
+    V_.st_count = 0;
+    V_.st_board = nullptr;
+    V_.st_hist = nullptr;
+    V_.st_info = nullptr;
+    return;
+  }
+  // the candidate goes into buffers of its own and is checked there; the table in force is replaced only by a good one
+  DevBuf<int8_t> nb, nh;
+  DevBuf<agz_position_info> ni;
+  DevBuf<int32_t> ok;
+  nb.alloc((size_t)S * P);
+  nh.alloc((size_t)S * 7 * P);
+  ni.alloc((size_t)S);
+  ok.alloc((size_t)S);
+  AGZ_HIP(hipMemcpyAsync(nb.p, boards, (size_t)S * P, hipMemcpyHostToDevice, stream_));
+  if (history) AGZ_HIP(hipMemcpyAsync(nh.p, history, (size_t)S * 7 * P, hipMemcpyHostToDevice, stream_));
+  else AGZ_HIP(hipMemsetAsync(nh.p, 0, (size_t)S * 7 * P, stream_));
+  AGZ_HIP(hipMemcpyAsync(ni.p, info, sizeof(agz_position_info) * (size_t)S, hipMemcpyHostToDevice, stream_));
+  hipLaunchKernelGGL(k_starts_valid, dim3((unsigned)S), dim3(kWave), 0, stream_, V_, (const int8_t*)nb.p,
+                     (const agz_position_info*)ni.p, ok.p);
+  AGZ_HIP(hipGetLastError());
+  std::vector<int32_t> good((size_t)S);
+  AGZ_HIP(hipMemcpyAsync(good.data(), ok.p, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  for (int64_t i = 0; i < S; ++i)
+    AGZ_REQUIRE(good[(size_t)i], AGZ_BAD_ARGUMENT,
+                "starts: entry %lld: bad board (a point outside -1..1, a group without liberty or a stone on the ko point)",
+                (long long)i);
+  std::swap(st_board_.p, nb.p); std::swap(st_board_.n, nb.n);
+  std::swap(st_hist_.p, nh.p); std::swap(st_hist_.n, nh.n);
+  std::swap(st_info_.p, ni.p); std::swap(st_info_.n, ni.n);
+  V_.st_count = (int32_t)S;
+  V_.st_board = st_board_.p;
+  V_.st_hist = st_hist_.p;
+  V_.st_info = st_info_.p;
 }
 
 // the scalar fields of caller positions; the boards are checked on the device, per position (root_board_valid)
@@ -980,6 +1076,8 @@ void Engine::incorporate_external(const float* pi, const float* v) {
 
 void Engine::debug_set_stagger(int moves) {
   AGZ_REQUIRE(moves >= 0 && !cfg_.arena_mode, AGZ_BAD_ARGUMENT, "stagger: >= 0 moves, not in arena_mode");
+  AGZ_REQUIRE(moves == 0 || V_.st_count == 0, AGZ_BAD_ARGUMENT,
+              "stagger: excluded while a table of start positions is set (the stagger prefix starts on the empty board)");
   AGZ_REQUIRE(!stepped_, AGZ_BAD_ARGUMENT, "stagger: set it before the first step of a run (before or right after agz_selfplay_start)");
   V_.stagger = moves;            // the View travels to the kernels by value: effective from the next launch
 }
@@ -1559,15 +1657,15 @@ void Engine::record_features(int64_t k, float* out) {
   const size_t per = (size_t)17 * V_.P;
   s_f32a_.ensure(per * (size_t)h.num_moves);
   s_boards_.ensure((size_t)8 * V_.PP);
-  s_i32a_.ensure(3);
+  s_i32a_.ensure(4);
   s_i64a_.ensure(1);
-  const int32_t args[3] = {0, h.num_moves, 0};
+  const int32_t args[4] = {0, h.num_moves, 0, (int32_t)record_start(V_, h.game_id)};
   const int64_t zero = 0;
   AGZ_HIP(hipMemcpyAsync(s_i32a_.p, args, sizeof(args), hipMemcpyHostToDevice, stream_));
   AGZ_HIP(hipMemcpyAsync(s_i64a_.p, &zero, sizeof(zero), hipMemcpyHostToDevice, stream_));
   hipLaunchKernelGGL(k_replay_features, dim3(1), dim3(kWave), 0, stream_, V_,
                      (const int16_t*)(V_.fin_moves + k * V_.max_game_length), s_i32a_.p, s_i32a_.p + 1, s_i32a_.p + 2,
-                     s_i64a_.p, s_boards_.p, s_f32a_.p);
+                     s_i64a_.p, s_boards_.p, s_f32a_.p, (const int32_t*)(s_i32a_.p + 3));
   AGZ_HIP(hipMemcpyAsync(out, s_f32a_.p, sizeof(float) * per * (size_t)h.num_moves, hipMemcpyDeviceToHost, stream_));
   AGZ_HIP(hipStreamSynchronize(stream_));
 }
@@ -1576,10 +1674,10 @@ void Engine::record_features(int64_t k, float* out) {
 // moves: the games' action lists back to back; off[b] = where sample b's game starts; ply[b] = which
 // position of that game (0 = empty board).
 void Engine::replay_batch_features(const int16_t* moves, int64_t nmoves, const int32_t* off, const int32_t* ply,
-                                   int B, float* out, bool out_is_device) {
+                                   int B, float* out, bool out_is_device, const int32_t* start) {
   AGZ_REQUIRE(B >= 0 && nmoves >= 0, AGZ_BAD_ARGUMENT, "negative count");
   if (B == 0) return;
-  std::vector<int32_t> h32((size_t)3 * B);
+  std::vector<int32_t> h32((size_t)4 * B);
   std::vector<int64_t> h64(B);
   const size_t per = (size_t)17 * V_.P;
   for (int b = 0; b < B; ++b) {
@@ -1589,12 +1687,15 @@ void Engine::replay_batch_features(const int16_t* moves, int64_t nmoves, const i
     h32[b] = off[b];
     h32[B + b] = ply[b] + 1;
     h32[2 * B + b] = ply[b];
+    h32[3 * B + b] = start ? start[b] : -1;
+    AGZ_REQUIRE(h32[3 * B + b] >= -1 && h32[3 * B + b] < V_.st_count, AGZ_BAD_ARGUMENT,
+                "sample %d: start %d, the table holds %d entries (-1 = empty board)", b, h32[3 * B + b], V_.st_count);
     h64[b] = (int64_t)b * (int64_t)per;
   }
   for (int64_t i = 0; i < nmoves; ++i)
     AGZ_REQUIRE(moves[i] >= 0 && moves[i] <= V_.P, AGZ_BAD_ARGUMENT, "move outside 0..N*N");
   s_i16a_.ensure((size_t)std::max<int64_t>(nmoves, 1));
-  s_i32a_.ensure((size_t)3 * B);
+  s_i32a_.ensure((size_t)4 * B);
   s_i64a_.ensure(B);
   s_boards_.ensure((size_t)B * 8 * V_.PP);
   float* dst = out;
@@ -1606,7 +1707,7 @@ void Engine::replay_batch_features(const int16_t* moves, int64_t nmoves, const i
   AGZ_HIP(hipMemcpyAsync(s_i32a_.p, h32.data(), sizeof(int32_t) * h32.size(), hipMemcpyHostToDevice, stream_));
   AGZ_HIP(hipMemcpyAsync(s_i64a_.p, h64.data(), sizeof(int64_t) * h64.size(), hipMemcpyHostToDevice, stream_));
   hipLaunchKernelGGL(k_replay_features, dim3(B), dim3(kWave), 0, stream_, V_, (const int16_t*)s_i16a_.p, s_i32a_.p,
-                     s_i32a_.p + B, s_i32a_.p + 2 * B, s_i64a_.p, s_boards_.p, dst);
+                     s_i32a_.p + B, s_i32a_.p + 2 * B, s_i64a_.p, s_boards_.p, dst, (const int32_t*)(s_i32a_.p + 3 * B));
   AGZ_HIP(hipGetLastError());
   if (!out_is_device)
     AGZ_HIP(hipMemcpyAsync(out, dst, sizeof(float) * per * (size_t)B, hipMemcpyDeviceToHost, stream_));

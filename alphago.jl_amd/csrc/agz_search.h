@@ -875,17 +875,42 @@ AGZ_FN void reroot(W& w, const View& V, Scratch& S, int g, int a, int child) {
   w.sync();
 }
 
-// initialize_game! on an empty board (mcts_play.jl:110-118) + the selfplay.jl:9 resign coin
+// (defined below, behind root_board_valid)
 template <class W>
-AGZ_FN void game_start(W& w, const View& V, Scratch& S, int g, uint64_t game_id) {
+AGZ_FN bool root_install(W& w, const View& V, Scratch& S, int g, const int8_t* board, const int8_t* hist,
+                         const agz_position_info& info, int phase, bool analysis);
+
+// the selfplay.jl:9 resign coin of game `game_id` (move 0 of its draw stream, wherever the game starts)
+AGZ_FN void game_resign_coin(const View& V, GameState& G, uint64_t game_id) {
+  const double u = agz_u01(agz_draw_u64(V.seed, game_id, 0, AGZ_SITE_RESIGN, 0));
+  G.resign_disabled = u < V.resign_disable_frac;
+  G.resign_threshold = G.resign_disabled ? -1.0 : V.resign_threshold;
+}
+
+// initialize_game! on an empty board (mcts_play.jl:110-118) + the selfplay.jl:9 resign coin.  With a table of start
+// positions set (View::st_*), initialize_game!(player, start) on entry start_key mod st_count instead: the root, the
+// history ring, komi and position.n are the entry's, so every draw of the game is keyed by the entry's n onwards.
+template <class W>
+AGZ_FN void game_start(W& w, const View& V, Scratch& S, int g, uint64_t game_id, uint64_t start_key) {
   GameState& G = V.gs[g];
+  if (V.st_count > 0) {
+    const long s = (long)(start_key % (uint64_t)V.st_count);
+    const agz_position_info info = V.st_info[s];
+    root_install(w, V, S, g, V.st_board + s * V.P, V.st_hist + s * 7 * V.P, info, G_INIT, false);
+    if (w.leader()) {
+      G.game_id = game_id;
+      game_resign_coin(V, G, game_id);
+      G.short_first = 0;
+    }
+    w.sync();
+    w.count(&V.counters[CT_STARTED], 1);
+    return;
+  }
   w.for_each(V.cap, [&](int i) { V.freelist[(long)g * V.cap + i] = V.cap - 1 - i; });
   w.sync();
   if (w.leader()) {
     G.game_id = game_id;
-    const double u = agz_u01(agz_draw_u64(V.seed, game_id, 0, AGZ_SITE_RESIGN, 0));
-    G.resign_disabled = u < V.resign_disable_frac;
-    G.resign_threshold = G.resign_disabled ? -1.0 : V.resign_threshold;
+    game_resign_coin(V, G, game_id);
     G.rootN = 0.f; G.rootW = 0.f; G.target = 0.f; G.komi = V.komi;
     G.sel = 0; G.move_count = 0; G.nqs = 0; G.hist_len = 0;
     G.free_top = V.cap; G.garbage = 0; G.nleaves = 0; G.err = 0; G.result = 0; G.was_resign = 0; G.nodes_used = 0;
@@ -1196,12 +1221,16 @@ template <class W>
 AGZ_FN void arena_start(W& w, const View& V, Scratch& S, int g, uint64_t index) {
   GameState& G = V.gs[g];
   const int k = G.arena_k;
-  game_start(w, V, S, g, 2 * index + (uint64_t)(g & 1));
+  game_start(w, V, S, g, 2 * index + (uint64_t)(g & 1), index);
+  // the player whose colour is to move searches first: `num_move % 2` (:118-119) on the empty start is Black, slot
+  // parity 0; a start from the table may have White to move
+  int waits = g & 1;
+  if (V.st_count > 0) waits = (g & 1) != (V.meta[node_index(V, g, G.root)].to_play == 1 ? 0 : 1);
   if (w.leader()) {
     G.arena_k = k;
     G.resign_disabled = 0;
     G.resign_threshold = V.resign_threshold;     // MCTSPlayer default, evaluate passes none (:110-111)
-    if (g & 1) G.phase = G_ARENA_WAIT;
+    if (waits) G.phase = G_ARENA_WAIT;
     else { G.target = G.rootN + (float)V.R; G.phase = G_SEARCH; }     // :121-126, root not pre-expanded
   }
   w.sync();
@@ -1731,7 +1760,8 @@ AGZ_FN void game_pre(W& w, const View& V, Scratch& S, int g) {
       w.sync();
       return;
     }
-    game_start(w, V, S, g, V.id_base + (uint64_t)idx * V.id_stride);
+    const uint64_t gid = V.id_base + (uint64_t)idx * V.id_stride;
+    game_start(w, V, S, g, gid, gid);
   }
   if (G.phase == G_INIT) {
     // selfplay.jl:16-20: the very first select_leaf returns the unexpanded root; it is sent to

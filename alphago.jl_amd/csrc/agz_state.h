@@ -167,6 +167,14 @@ struct View {
   agz_line* an_line;                  // [rows][K]
   int16_t* an_pv;                     // [rows][K][D]
   float* an_pvN;                      // [rows][K][D]
+  // start positions (agz_selfplay_set_starts; zero = off, the View{} of the host simulator and of fill_dims): self-play
+  // game `gid` begins at entry gid mod st_count, arena game g (ids 2g, 2g + 1) at entry g mod st_count, and every
+  // kernel that rebuilds a record's positions begins there too.  Tables of their own: analysis
+  // overwrites the an_* ones
+  int32_t st_count;                   // S
+  const int8_t* st_board;             // [S][P]
+  const int8_t* st_hist;              // [S][7][P]: older boards newest first (history_len of them are real)
+  const agz_position_info* st_info;   // [S]
 };
 
 }  // namespace agz

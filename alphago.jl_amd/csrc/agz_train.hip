@@ -31,8 +31,22 @@ namespace {
 
 constexpr float kLossPiW = 0.01f, kLossVW = 0.01f, kRegW = 1e-4f, kBnMomentum = 0.1f;
 
-// ---- column statistics: sums[c] = sum_m u[m][c], sums[C + c] = sum_m u[m][c]^2 (double, atomics over row slices)
-__global__ __launch_bounds__(256) void k_colsums(const float* __restrict__ u, long M, int C, double* __restrict__ sums) {
+// ---- the column reductions run over kRowSlices row slices (gridDim.y, or gridDim.x of k_head1x1_wgrad).  Slice y
+// leaves its double partial sums in part[y][n]; k_sum_slices adds the slices in the order y = 0, 1, ...: one order,
+// whatever the blocks' timing, so a step is a function of its inputs alone.  (The slices used to meet in atomics; the
+// gradient of a bias in front of a BatchNorm is a sum whose exact value is zero, its rounding residue depended on the
+// order the atomics arrived in, and two runs of one schedule ended with different bits in those biases.)
+constexpr int kRowSlices = 64;
+__global__ void k_sum_slices(const double* __restrict__ part, int slices, int n, double* __restrict__ sums) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+  for (int y = 0; y < slices; ++y) s += part[(size_t)y * n + i];
+  sums[i] = s;
+}
+
+// ---- column statistics: sums[c] = sum_m u[m][c], sums[C + c] = sum_m u[m][c]^2 (double; part[slice][2 C])
+__global__ __launch_bounds__(256) void k_colsums(const float* __restrict__ u, long M, int C, double* __restrict__ part) {
   __shared__ double red[2][4][64];
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;
@@ -47,8 +61,9 @@ __global__ __launch_bounds__(256) void k_colsums(const float* __restrict__ u, lo
   red[1][rl][cl] = s2;
   __syncthreads();
   if (rl == 0 && c < C) {
-    atomicAdd(&sums[c], red[0][0][cl] + red[0][1][cl] + red[0][2][cl] + red[0][3][cl]);
-    atomicAdd(&sums[C + c], red[1][0][cl] + red[1][1][cl] + red[1][2][cl] + red[1][3][cl]);
+    double* sums = part + (size_t)blockIdx.y * 2 * C;
+    sums[c] = red[0][0][cl] + red[0][1][cl] + red[0][2][cl] + red[0][3][cl];
+    sums[C + c] = red[1][0][cl] + red[1][1][cl] + red[1][2][cl] + red[1][3][cl];
   }
 }
 
@@ -72,7 +87,7 @@ __global__ void k_bn_fwd(const float* __restrict__ u, long M, int C, const doubl
 // BatchNorm backward, reduction: with dy = dout (.* [out > 0] if relu): sums[c] = sum dy, sums[C + c] = sum dy xhat
 __global__ __launch_bounds__(256) void k_bn_bwd_sums(const float* __restrict__ dout, const float* __restrict__ out,
                                                       const float* __restrict__ u, const float* __restrict__ stats,
-                                                      long M, int C, int relu, double* __restrict__ sums) {
+                                                      long M, int C, int relu, double* __restrict__ part) {
   __shared__ double red[2][4][64];
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;
@@ -90,8 +105,9 @@ __global__ __launch_bounds__(256) void k_bn_bwd_sums(const float* __restrict__ d
   red[1][rl][cl] = s2;
   __syncthreads();
   if (rl == 0 && c < C) {
-    atomicAdd(&sums[c], red[0][0][cl] + red[0][1][cl] + red[0][2][cl] + red[0][3][cl]);
-    atomicAdd(&sums[C + c], red[1][0][cl] + red[1][1][cl] + red[1][2][cl] + red[1][3][cl]);
+    double* sums = part + (size_t)blockIdx.y * 2 * C;
+    sums[c] = red[0][0][cl] + red[0][1][cl] + red[0][2][cl] + red[0][3][cl];
+    sums[C + c] = red[1][0][cl] + red[1][1][cl] + red[1][2][cl] + red[1][3][cl];
   }
 }
 
@@ -329,9 +345,9 @@ __global__ void k_head1x1_dgrad(const float* __restrict__ dcv, const float* __re
   dx[i] = dcv[m] * wv[c] + dcp[m * 2] * wp[c] + dcp[m * 2 + 1] * wp[kC + c];
 }
 // dwv[c] = sum_m dcv[m] x[m][c]; dwp[j][c]; dbv, dbp.  One thread per channel, the rows in gridDim.x slices whose double
-// partial sums meet in sums[0..3 kC + 3) (zeroed by the caller; one block over all rows was 10 % of a batch-32 step)
+// partial sums go to part[slice][3 kC + 3] (k_sum_slices; one block over all rows was 10 % of a batch-32 step)
 __global__ __launch_bounds__(256) void k_head1x1_wgrad(const float* __restrict__ x, const float* __restrict__ dcv,
-                                                        const float* __restrict__ dcp, long M, double* __restrict__ sums) {
+                                                        const float* __restrict__ dcp, long M, double* __restrict__ part) {
   const int c = threadIdx.x;
   const long per = (M + gridDim.x - 1) / gridDim.x, lo = blockIdx.x * per, hi = lo + per < M ? lo + per : M;
   double sv = 0.0, s0 = 0.0, s1 = 0.0, bv = 0.0, b0 = 0.0, b1 = 0.0;
@@ -342,10 +358,11 @@ __global__ __launch_bounds__(256) void k_head1x1_wgrad(const float* __restrict__
     s1 += xv * dcp[m * 2 + 1];
     if (c == 0) { bv += dcv[m]; b0 += dcp[m * 2]; b1 += dcp[m * 2 + 1]; }
   }
-  atomicAdd(&sums[c], sv);
-  atomicAdd(&sums[kC + c], s0);
-  atomicAdd(&sums[2 * kC + c], s1);
-  if (c == 0) { atomicAdd(&sums[3 * kC], bv); atomicAdd(&sums[3 * kC + 1], b0); atomicAdd(&sums[3 * kC + 2], b1); }
+  double* sums = part + (size_t)blockIdx.x * (3 * kC + 3);
+  sums[c] = sv;
+  sums[kC + c] = s0;
+  sums[2 * kC + c] = s1;
+  if (c == 0) { sums[3 * kC] = bv; sums[3 * kC + 1] = b0; sums[3 * kC + 2] = b1; }
 }
 __global__ __launch_bounds__(256) void k_head1x1_wgrad_take(const double* __restrict__ sums, float* __restrict__ dwv,
                                                              float* __restrict__ dwp, float* __restrict__ dbv, float* __restrict__ dbp) {
@@ -544,7 +561,7 @@ void Trainer::step(const float* feats, const float* pi, const float* z, int B, b
   d_gb_.ensure(act);
   d_gc_.ensure(act);
   d_stats_.ensure((size_t)3 * kC * L + 16);
-  d_sums_.ensure((size_t)4 * kC + 8);
+  d_sums_.ensure((size_t)4 * kC + 8 + (size_t)kRowSlices * (3 * kC + 3));     // sums, losses, the slices' partial sums
   d_ones_.ensure(kC);
   d_wd_.ensure((size_t)kC * 9 * kC);
   d_small_.ensure((size_t)M * 9 + (size_t)B * (A * 3 + 256 * 2 + 8) + 64);
@@ -580,9 +597,13 @@ void Trainer::step(const float* feats, const float* pi, const float* z, int B, b
   float* dd1 = dsv + B;                      // [B][256]
   double* d_losses = reinterpret_cast<double*>(d_sums_.p) + 4 * kC;       // [4] behind the column sums
   double* sums = reinterpret_cast<double*>(d_sums_.p);
-  auto zero_sums = [&](int C) { AGZ_HIP(hipMemsetAsync(sums, 0, sizeof(double) * 2 * C, s)); };
+  double* part = sums + 4 * kC + 8;           // [kRowSlices][n <= 3 kC + 3]
+  // sums[0..n) = the slices' partial sums added in slice order (behind every column reduction)
+  auto add_slices = [&](int n) {
+    hipLaunchKernelGGL(k_sum_slices, dim3((n + 255) / 256), dim3(256), 0, s, (const double*)part, kRowSlices, n, sums);
+  };
   AGZ_HIP(hipMemsetAsync(d_losses, 0, sizeof(double) * 4, s));
-  const int RS = 64;                          // row slices of the column reductions
+  const int RS = kRowSlices;                  // row slices of the column reductions
 
   auto P4 = [&](int l, int k) -> Param& { return *params_[(size_t)4 * l + k]; };
   float* stats0 = d_stats_.p;
@@ -603,8 +624,8 @@ void Trainer::step(const float* feats, const float* pi, const float* z, int B, b
     else
       launch_conv3x3_direct(in, P4(l, 0).theta.p, d_ones_.p, P4(l, 1).theta.p, nullptr, U(l), d_cnt_.p, B, N, 0,
                             l == 0 ? kCinStemPad : kC, s);
-    zero_sums(kC);
-    hipLaunchKernelGGL(k_colsums, dim3(kC / 64, RS), dim3(256), 0, s, (const float*)U(l), M, (int)kC, sums);
+    hipLaunchKernelGGL(k_colsums, dim3(kC / 64, RS), dim3(256), 0, s, (const float*)U(l), M, (int)kC, part);
+    add_slices(2 * kC);
     hipLaunchKernelGGL(k_bn_fwd, g1(M * kC), dim3(256), 0, s, (const float*)U(l), M, (int)kC, (const double*)sums,
                        (const float*)P4(l, 2).theta.p, (const float*)P4(l, 3).theta.p, train_eps(net_.conv(l)->eps), res, O(l), 1, ST(l));
   };
@@ -623,12 +644,12 @@ void Trainer::step(const float* feats, const float* pi, const float* z, int B, b
   float* st_p = st_v + 3;                      // 2-channel BN: {mean[2], var[2], rstd[2]}
   hipLaunchKernelGGL(k_head1x1_fwd, dim3(256), dim3(256), 0, s, xL, M, (const float*)Wv.theta.p, (const float*)Bv.theta.p,
                      (const float*)Wp.theta.p, (const float*)Bp.theta.p, cv, cp);
-  zero_sums(2);
-  hipLaunchKernelGGL(k_colsums, dim3(1, RS), dim3(256), 0, s, (const float*)cv, M, 1, sums);
+  hipLaunchKernelGGL(k_colsums, dim3(1, RS), dim3(256), 0, s, (const float*)cv, M, 1, part);
+  add_slices(2);
   hipLaunchKernelGGL(k_bn_fwd, g1(M), dim3(256), 0, s, (const float*)cv, M, 1, (const double*)sums, (const float*)Gv.theta.p,
                      (const float*)BEv.theta.p, train_eps(net_.conv(AGZ_L_VALUE_CONV)->eps), (const float*)nullptr, hv, 1, st_v);
-  zero_sums(2);
-  hipLaunchKernelGGL(k_colsums, dim3(1, RS), dim3(256), 0, s, (const float*)cp, M, 2, sums);
+  hipLaunchKernelGGL(k_colsums, dim3(1, RS), dim3(256), 0, s, (const float*)cp, M, 2, part);
+  add_slices(4);
   hipLaunchKernelGGL(k_bn_fwd, g1(M * 2), dim3(256), 0, s, (const float*)cp, M, 2, (const double*)sums,
                      (const float*)Gp.theta.p, (const float*)BEp.theta.p, train_eps(net_.conv(AGZ_L_POLICY_CONV)->eps),
                      (const float*)nullptr, hp, 1, st_p);
@@ -657,20 +678,20 @@ void Trainer::step(const float* feats, const float* pi, const float* z, int B, b
   hipLaunchKernelGGL(k_dense_dgrad, dim3((P + 255) / 256, B), dim3(256), 0, s, (const float*)W1.theta.p, (const float*)dd1, B, P,
                      256, (const float*)nullptr, 0, P, dhv);
   // head BatchNorms (ReLU mask from hv / hp), in place: dhv -> dcv, dhp -> dcp
-  zero_sums(2);
   hipLaunchKernelGGL(k_bn_bwd_sums, dim3(1, RS), dim3(256), 0, s, (const float*)dhv, (const float*)hv, (const float*)cv,
-                     (const float*)st_v, M, 1, 1, sums);
+                     (const float*)st_v, M, 1, 1, part);
+  add_slices(2);
   hipLaunchKernelGGL(k_bn_bwd_apply, g1(M), dim3(256), 0, s, (const float*)dhv, (const float*)hv, (const float*)cv,
                      (const float*)st_v, (const float*)Gv.theta.p, (const double*)sums, M, 1, 1, dcv, (float*)nullptr, Gv.grad.p,
                      BEv.grad.p);
-  zero_sums(2);
   hipLaunchKernelGGL(k_bn_bwd_sums, dim3(1, RS), dim3(256), 0, s, (const float*)dhp, (const float*)hp, (const float*)cp,
-                     (const float*)st_p, M, 2, 1, sums);
+                     (const float*)st_p, M, 2, 1, part);
+  add_slices(4);
   hipLaunchKernelGGL(k_bn_bwd_apply, g1(M * 2), dim3(256), 0, s, (const float*)dhp, (const float*)hp, (const float*)cp,
                      (const float*)st_p, (const float*)Gp.theta.p, (const double*)sums, M, 2, 1, dcp, (float*)nullptr, Gp.grad.p,
                      BEp.grad.p);
-  AGZ_HIP(hipMemsetAsync(sums, 0, sizeof(double) * (3 * kC + 3), s));
-  hipLaunchKernelGGL(k_head1x1_wgrad, dim3(RS), dim3(256), 0, s, xL, (const float*)dcv, (const float*)dcp, M, sums);
+  hipLaunchKernelGGL(k_head1x1_wgrad, dim3(RS), dim3(256), 0, s, xL, (const float*)dcv, (const float*)dcp, M, part);
+  add_slices(3 * kC + 3);
   hipLaunchKernelGGL(k_head1x1_wgrad_take, dim3(1), dim3(256), 0, s, (const double*)sums, Wv.grad.p, Wp.grad.p, Bv.grad.p,
                      Bp.grad.p);
   float* g = d_ga_.p;      // gradient wrt the current block output
@@ -680,14 +701,14 @@ void Trainer::step(const float* feats, const float* pi, const float* z, int B, b
   // ---- backward: tower and stem
   // BN backward of layer l with upstream `dout` (ReLU mask from O(l)); du -> `du`; dres (optional) gets the masked dout
   auto bn_back = [&](int l, const float* dout, float* du, float* dres) {
-    zero_sums(kC);
     hipLaunchKernelGGL(k_bn_bwd_sums, dim3(kC / 64, RS), dim3(256), 0, s, dout, (const float*)O(l), (const float*)U(l),
-                       (const float*)ST(l), M, (int)kC, 1, sums);
+                       (const float*)ST(l), M, (int)kC, 1, part);
+    add_slices(2 * kC);
     hipLaunchKernelGGL(k_bn_bwd_apply, g1(M * kC), dim3(256), 0, s, dout, (const float*)O(l), (const float*)U(l),
                        (const float*)ST(l), (const float*)P4(l, 2).theta.p, (const double*)sums, M, (int)kC, 1, du, dres,
                        P4(l, 2).grad.p, P4(l, 3).grad.p);
-    zero_sums(kC);
-    hipLaunchKernelGGL(k_colsums, dim3(kC / 64, RS), dim3(256), 0, s, (const float*)du, M, (int)kC, sums);
+    hipLaunchKernelGGL(k_colsums, dim3(kC / 64, RS), dim3(256), 0, s, (const float*)du, M, (int)kC, part);
+    add_slices(2 * kC);
     hipLaunchKernelGGL(k_take_sums, dim3(1), dim3(256), 0, s, (const double*)sums, (int)kC, P4(l, 1).grad.p);
   };
   // rows per weight-gradient block: ~2600 (the reference's batch of 32 at 9x9), more blocks for more rows

@@ -34,7 +34,10 @@ def pack_records(records, A):
     return np.frombuffer(bytes(out), dtype=np.uint8).copy()
 
 
-def unpack_records(buf, A):
+def unpack_records(buf, A, starts=0, arena=False):
+    """packed records -> dicts.  starts = S > 0: the games were played from a table of S start positions
+    (Engine.set_starts, the same table on every rank); each dict then carries `start`, the entry its game began at by
+    the index rule (game_id mod S; arena: (game_id // 2) mod S), which ReplayBuffer keeps for device replay."""
     buf = np.ascontiguousarray(buf, np.uint8)
     raw = buf.tobytes()
     out, off = [], 0
@@ -51,7 +54,7 @@ def unpack_records(buf, A):
         off += -off % 8
         out.append(dict(game_id=game_id, num_moves=n, result=result, was_resign=was_resign,
                         resign_disabled=resign_disabled, final_score=final_score, short_searches=short, moves=moves, pis=pis,
-                        qs=qs))
+                        qs=qs, start=int((game_id // 2 if arena else game_id) % starts) if starts > 0 else -1))
     return out
 
 
@@ -91,7 +94,9 @@ def allgather_records(engine_or_records, A, group=None, force_collective=False):
         packed = engine_or_records.records_packed_device() if on_device else engine_or_records.records_packed()
     else:
         packed = pack_records(engine_or_records, A)
-    recs = unpack_records(allgather_packed(packed, group, force_collective=force_collective), A)
+    S = engine_or_records.starts_count() if hasattr(engine_or_records, "starts_count") else 0
+    arena = bool(getattr(getattr(engine_or_records, "cfg", None), "arena_mode", 0))
+    recs = unpack_records(allgather_packed(packed, group, force_collective=force_collective), A, S, arena)
     return sorted(recs, key=lambda r: r["game_id"])
 
 

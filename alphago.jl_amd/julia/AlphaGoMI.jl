@@ -23,7 +23,7 @@ using Random
 export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, train, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
-       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, node_lines, most_visited_path, mvp_gg,
+       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, set_starts!, node_lines, most_visited_path, mvp_gg,
        # the node-level surface test/test_mcts.jl:2-5 and test/test_mcts_player.jl:3-6 import
        MCTSNode, select_leaf, maybe_add_child!, add_virtual_loss!, revert_virtual_loss!,
        incorporate_results!, inject_noise!, child_action_score, child_Q, child_U, child_N, child_W,
@@ -734,13 +734,16 @@ struct SelfPlayPlayer
   game_id::UInt64
   moves::Vector{Int}                    # 1-based flat moves, N^2+1 = pass
   short_searches::Int                   # moves played on fewer than num_ro readouts (full node pool, agz_config.pool_policy); 0 = the reference's game
+  start::Union{Nothing, Position}       # the position the game began at (selfplay(...; starts)), nothing = the empty board
+  start_index::Int                      # its 0-based entry of the table of start positions, -1 = none
 end
 is_done(p::SelfPlayPlayer) = true
 get_position(p::SelfPlayPlayer) = p.root.position
 
 # extract_data(player), mcts_play.jl:126-139: every result entry is the final game result
 function extract_data(p::SelfPlayPlayer)
-  length(p.searches_π) == p.root.position.n || throw(AssertionError("length(searches_π) == root.position.n"))
+  n0 = p.start === nothing ? 0 : p.start.n
+  length(p.searches_π) == p.root.position.n - n0 || throw(AssertionError("length(searches_π) == root.position.n - start.n"))
   copy(p.positions), deepcopy(p.searches_π), fill(p.result, length(p.positions))
 end
 
@@ -750,8 +753,35 @@ end
 const STREAM = Ref((UInt64(0), UInt64(0)))                     # (seed, next game id)
 seed!(s::Integer) = (STREAM[] = (UInt64(s), UInt64(0)); nothing)
 
+# A table of start positions (ours; include/agz.h agz_selfplay_set_starts): the self-play game with id gid begins at
+# starts[gid % S + 1] -- initialize_game!(player, pos), mcts_play.jl:110-118 -- and arena game g at starts[g % S + 1];
+# everything that replays the records begins there too.  An empty vector clears the table.
+function set_starts!(e::Engine, env::GoEnv, starts::Vector{Position})
+  S, P = length(starts), env.N * env.N
+  boards = zeros(Int8, P, max(S, 1)); hist = zeros(Int8, P, 7, max(S, 1)); info = Vector{AgzPositionInfo}(undef, max(S, 1))
+  for (i, pos) in enumerate(starts)
+    b, info[i], h = position_arrays(env, pos)
+    boards[:, i] = vec(b); hist[:, 1:size(h, 2), i] = h
+  end
+  check(e, ccall((:agz_selfplay_set_starts, libagz), Int32, (Ptr{Cvoid}, Ptr{Int8}, Ptr{AgzPositionInfo}, Ptr{Int8}, Int64),
+                 e.handle, boards, info, hist, S))
+end
+starts_count(e::Engine) = Int(ccall((:agz_selfplay_starts_count, libagz), Int64, (Ptr{Cvoid},), e.handle))
+
+# replay_position (board.jl:557-578) from a start position: the position before each move and the final one
+function replay_positions_from(start::Position, moves)
+  positions = Position[]
+  pos = start
+  for m in moves
+    push!(positions, pos)
+    pos = play_move!(pos, m)
+  end
+  positions, pos
+end
+
 function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Nothing, Int} = nothing,
-                  slots::Union{Nothing, Int} = nothing, seed = nothing, game_id_base = nothing, symmetry = nothing)
+                  slots::Union{Nothing, Int} = nothing, seed = nothing, game_id_base = nothing, symmetry = nothing,
+                  starts::Union{Nothing, Vector{Position}} = nothing)
   G = games === nothing ? 1 : games
   if seed === nothing
     seed, next = STREAM[]
@@ -765,6 +795,7 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
              num_readouts = num_ro, seed = seed, game_id_base = game_id_base, record_capacity_games = G + 8)
   copy_weights!(e, nn.engine)
   symmetry === nothing || set_symmetry!(e, symmetry)
+  starts === nothing || set_starts!(e, env, starts)
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, G))
   while ccall((:agz_records_count, libagz), Int64, (Ptr{Cvoid},), e.handle) < G
     check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 16))
@@ -786,10 +817,12 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
     for f in fmoves
       push!(recent, PlayerMove(color, from_flat(f, env))); color = -color
     end
-    positions, final = replay_positions(env, 7.5, recent)
+    si = starts === nothing || isempty(starts) ? -1 : Int(h[].game_id % UInt64(length(starts)))
+    positions, final = si < 0 ? replay_positions(env, 7.5, recent) :
+                                replay_positions_from(starts[si + 1], [from_flat(f, env) for f in fmoves])
     push!(players, SelfPlayPlayer(env, nn, num_ro, false, τ, qs[1:n], [pis[:, i] for i in 1:n], Int(h[].result), rs,
                                   FinishedRoot(final), h[].resign_disabled != 0 ? -1.0 : -0.9, final, positions,
-                                  h[].game_id, fmoves, Int(h[].short_searches)))
+                                  h[].game_id, fmoves, Int(h[].short_searches), si < 0 ? nothing : starts[si + 1], si))
   end
   sort!(players, by = r -> r.game_id)
   games === nothing ? players[1] : players
@@ -1003,7 +1036,8 @@ set_precision!(e::Engine, p::Symbol) =      # :f32 (default, exact), :f16 (fp16 
 # games run concurrently.  Black's tally is `result(black.root.position) == BLACK` (:147), i.e.
 # final_score > 0, also for resigned games.
 function evaluate(env::GoEnv, black_net::NeuralNet, white_net::NeuralNet; num_games = 400, ro = 800,
-                  verbose::Bool = false, seed = 0, pairs::Int = min(num_games, 512), symmetry = nothing)
+                  verbose::Bool = false, seed = 0, pairs::Int = min(num_games, 512), symmetry = nothing,
+                  starts::Union{Nothing, Vector{Position}} = nothing)
   @assert black_net.tower_height == white_net.tower_height
   e = Engine(board_size = env.N, tower_height = black_net.tower_height, games = 2 * pairs, num_readouts = ro,
              seed = seed, record_capacity_games = num_games + 8, arena_mode = true)
@@ -1012,6 +1046,7 @@ function evaluate(env::GoEnv, black_net::NeuralNet, white_net::NeuralNet; num_ga
   copy_weights!(e, white_net.engine)
   check(e, ccall((:agz_net_select, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 0))
   symmetry === nothing || set_symmetry!(e, symmetry)
+  starts === nothing || set_starts!(e, env, starts)      # an opening suite: game g begins at starts[g % S + 1]
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, num_games))
   while ccall((:agz_records_count, libagz), Int64, (Ptr{Cvoid},), e.handle) < num_games
     check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 16))
@@ -1030,7 +1065,9 @@ end
 # ------------------------------------------------------------------ replay batches
 # get_replay_batch(pos_buffer, π_buffer, res_buffer; batch_size), src/train.jl:4-12, with the
 # positions kept as move lists: `games[g]` is a SelfPlayPlayer, a sample is (g, ply) with ply = 0 the
-# empty board.  Returns the N x N x 17 x B feature tensor get_feats would build, π (A x B), results.
+# empty board -- or, for games played from a table of start positions (selfplay(...; starts)), the game's start: `e`
+# must have the same table set (set_starts!).  Returns the N x N x 17 x B feature tensor get_feats would build, π (A x B),
+# results.
 function get_replay_batch(e::Engine, env::GoEnv, games::Vector{SelfPlayPlayer}, samples::Vector{Tuple{Int,Int}})
   used = sort(unique(first.(samples)))
   offs = Dict{Int,Int32}(); moves = Int16[]
@@ -1041,9 +1078,10 @@ function get_replay_batch(e::Engine, env::GoEnv, games::Vector{SelfPlayPlayer}, 
   B = length(samples)
   off = Int32[offs[g] for (g, _) in samples]; ply = Int32[j for (_, j) in samples]
   feats = zeros(Float32, env.N, env.N, 17, B)
-  check(e, ccall((:agz_replay_features, libagz), Int32,
-                 (Ptr{Cvoid}, Ptr{Int16}, Int64, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Float32}, Int32),
-                 e.handle, moves, length(moves), off, ply, B, feats, 0))
+  start = Int32[games[g].start_index for (g, _) in samples]
+  check(e, ccall((:agz_replay_features_starts, libagz), Int32,
+                 (Ptr{Cvoid}, Ptr{Int16}, Int64, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Float32}, Int32),
+                 e.handle, moves, length(moves), off, ply, start, B, feats, 0))
   π = hcat((games[g].searches_π[j + 1] for (g, j) in samples)...)
   feats, π, [games[g].result for (g, _) in samples]
 end
@@ -1157,7 +1195,8 @@ end
 function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, batch_size::Int = 32, epochs = 1,
                ckp_freq::Int = 1000, readouts::Int = 800, tower_height::Int = 19, model = nothing,
                start_training_after = 50000, slots::Union{Nothing, Int} = nothing, seed = 0, game_id_base = 0,
-               augment::Bool = false, callback::Function = println)
+               augment::Bool = false, callback::Function = println,
+               starts::Union{Nothing, Vector{Position}} = nothing)
   cur_nn = model === nothing ? NeuralNet(env; tower_height = tower_height) : model                       # train.jl:43
   S = slots === nothing ? min(num_games, 1024) : slots
   e = Engine(board_size = env.N, tower_height = cur_nn.tower_height, games = S, num_readouts = readouts, seed = seed,
@@ -1172,6 +1211,7 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
   feats, pi, z = (r[] for r in bufs)
   cuts = vcat(collect(0:32:batch_size-1), batch_size)
   length(cuts) > 2 && cuts[end] - cuts[end-1] == 1 && deleteat!(cuts, length(cuts) - 1)   # BatchNorm needs two rows
+  starts === nothing || set_starts!(e, env, starts)      # game gid begins at starts[gid % S + 1]; the arena replays from there
   check(e, ccall((:agz_selfplay_set_hold, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 1))
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, num_games))
   check(e, ccall((:agz_selfplay_release, libagz), Int32, (Ptr{Cvoid},), e.handle))

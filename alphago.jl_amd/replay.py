@@ -10,7 +10,9 @@ and its result -- not as materialised Position objects: positions are rebuilt on
 device, by replaying the move list (`agz_replay_features`, the counterpart of `replay_position`,
 board.jl:557-578).  Entry k of the buffer is (game g, ply j); trimming is per entry exactly like
 the reference (the oldest game may be partially trimmed: its late plies stay sampleable, the move
-list is kept whole because replay needs it).  Records gathered from other ranks
+list is kept whole because replay needs it).  A game played from a table of start positions
+(Engine.set_starts) keeps the index of its entry (`start` of its record) and is replayed from there
+(`agz_replay_features_starts`) on an engine that has the same table set.  Records gathered from other ranks
 (distributed.allgather_records) go through the same `push_record`.
 """
 import collections
@@ -22,7 +24,8 @@ class ReplayBuffer:
     def __init__(self, env, memory_size=500000):
         self.env = env
         self.memory_size = int(memory_size)
-        self._games = collections.deque()      # dicts: moves int16[n], pis f32[n][A], result, first (oldest live ply)
+        self._games = collections.deque()      # dicts: moves int16[n], pis f32[n][A], result, first (oldest live ply),
+        #                                        start (entry of the start-position table, -1 = the empty board)
         self._len = 0
 
     def __len__(self):
@@ -37,16 +40,21 @@ class ReplayBuffer:
             moves = np.array([to_flat(c, self.env) for c in rec.moves], np.int16)
             pis = np.asarray(rec.searches_pi, np.float32).reshape(len(moves), -1)
             result = rec.result
+            start = int(getattr(rec, "start_index", -1))
+            if getattr(rec, "start", None) is not None and start < 0:
+                raise ValueError("the game began at a start position but carries no table index (start_index): "
+                                 "its move list cannot be replayed from the empty board")
         else:
             moves = np.asarray(rec["moves"], np.int16)
             n = len(moves)
             pis = np.asarray(rec["pis"], np.float32).reshape(n, -1) if n else np.zeros((0, self.env.action_space), np.float32)
             result = rec["result"]
+            start = int(rec.get("start", -1)) if hasattr(rec, "get") else -1
         n = len(moves)
         if n == 0:
             return
         assert pis.shape == (n, self.env.action_space), "searches_pi does not match the move list"   # mcts_play.jl:127
-        self._games.append(dict(moves=moves, pis=pis, result=int(result), first=0))
+        self._games.append(dict(moves=moves, pis=pis, result=int(result), first=0, start=start))
         self._len += n
         while self._len > self.memory_size:
             g = self._games[0]
@@ -95,7 +103,9 @@ class ReplayBuffer:
             chunks.append(games[g]["moves"])
             o += len(games[g]["moves"])
         moves = np.concatenate(chunks) if chunks else np.zeros(0, np.int16)
-        feats = engine.replay_features(moves, [offs[g] for g, _ in pairs], [j for _, j in pairs], out=out)
+        start = [games[g]["start"] for g, _ in pairs]
+        kw = dict(start=start) if any(s >= 0 for s in start) else {}      # (no table: the call it has always been)
+        feats = engine.replay_features(moves, [offs[g] for g, _ in pairs], [j for _, j in pairs], out=out, **kw)
         pi = np.stack([games[g]["pis"][j] for g, j in pairs], axis=1)
         res = np.array([games[g]["result"] for g, _ in pairs], np.int64)
         if augment:

@@ -317,6 +317,12 @@ agz_status agz_records_features(agz_engine* e, int64_t k, float* out);
 agz_status agz_replay_features(agz_engine* e, const int16_t* moves, int64_t nmoves,
                                const int32_t* game_offset, const int32_t* ply, int32_t B, float* out,
                                int32_t out_is_device);
+/* agz_replay_features for hosts that keep the move lists of games played from a table of start positions
+ * (agz_selfplay_set_starts): sample b's move list begins at entry start[b] of the table in force, -1 = the empty
+ * board; ply 0 is the start position itself.  start = NULL is agz_replay_features. */
+agz_status agz_replay_features_starts(agz_engine* e, const int16_t* moves, int64_t nmoves,
+                                      const int32_t* game_offset, const int32_t* ply, const int32_t* start, int32_t B,
+                                      float* out, int32_t out_is_device);
 
 /* ---------------------------------------------------------------- replay arena + exchange -- */
 /* The replay buffer of train() (pos_buffer / pi_buffer / res_buffer, train.jl:47-66) as a device-resident
@@ -534,6 +540,35 @@ typedef struct {
 } agz_analysis;
 agz_status agz_analyze_start(agz_engine* e, const int8_t* boards, const agz_position_info* info, const int8_t* history,
                              int64_t B, uint64_t game_id_base);
+/* A table of start positions (initialize_game!(player, pos), mcts_play.jl:110-118, for the bulk loops): S >= 1
+ * positions in the conventions of agz_analyze_start -- boards int8[S][N*N], info[S], history int8[S][7][N*N] or NULL.
+ * While a table is set, self-play game `gid` (game_id_base + k * stride) starts from entry gid mod S and arena game g
+ * (its two players have the ids 2g and 2g + 1) from entry g mod S, on any rank and in any slot.  The game is
+ * selfplay.jl:1-45 / neural_net.jl:113-148 from that root: komi, to_play, ko, captures and position.n are the entry's,
+ * every draw is keyed by position.n as the reference's player keys it, the soft pick holds while position.n < tau, the
+ * game ends by two passes or at position.n >= max_game_length, and in the arena the player whose colour is to move
+ * searches first.  A record keeps its layout: num_moves, moves, pis and qs cover the plies played from the start,
+ * result and final_score are of the final position.  Everything that rebuilds a record's positions finds the start
+ * through the record's game_id by the same rule and begins there -- the entry's board, to_play and its history_len
+ * older boards as the history planes: agz_records_features, agz_replay_batch(_sym), agz_replay_sample.  S = 0 clears
+ * the table; with none set (the default) every path is what it is without this call.  Analysis, review and the
+ * single-tree calls ignore the table.  Synchronises.  Refused with the previous table left in force, naming the entry:
+ *   - a scalar field agz_analyze_start would refuse;
+ *   - a finished start: last_move and prev_move both pass, or n >= max_game_length;
+ *   - a board with a point outside {-1, 0, 1}, a group without a liberty or a stone on the ko point (checked on the
+ *     device over the whole table, at this call);
+ *   - while the record ring or the replay arena holds games, or games of a run are still being played (their positions
+ *     are rebuilt through the table): agz_records_clear / agz_replay_clear first;
+ *   - together with agz_debug_set_stagger > 0.
+ * The games of the next agz_selfplay_start begin on the new table.  A run that has been started and not stepped yet
+ * has claimed no game: a table set there is the table of that run.
+ * The record-to-start rule reads the game id as the engine that replays it does: an arena_mode engine takes
+ * game_id / 2, any other engine game_id.  Records therefore go into the arena of an engine of the kind that played
+ * them (self-play records into a self-play engine, evaluate() records into an arena_mode engine), with the same table
+ * set; the library cannot tell the two kinds of id apart. */
+agz_status agz_selfplay_set_starts(agz_engine* e, const int8_t* boards, const agz_position_info* info,
+                                   const int8_t* history, int64_t S);
+int64_t agz_selfplay_starts_count(agz_engine* e);                   /* entries of the table in force, 0 = none */
 agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out);
 /* out[B], child_N / child_W / prior [B][A] (the root's rows when the search ended); any of them may be NULL */
 agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N, float* child_W, float* prior);
