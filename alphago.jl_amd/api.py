@@ -592,7 +592,9 @@ class SelfPlayPlayer:
     record's fields (`game_id`, `moves` as board coordinates / None, `was_resign`, `short_searches`).  `start` (ours) is
     the Position the game began at -- an entry of selfplay(..., starts=...) -- or None for the empty board: the moves,
     searches_pi and qs cover the plies played from there; `start_index` is that entry's index in the table (-1: none),
-    which is what ReplayBuffer keeps to replay the game on the device."""
+    which is what ReplayBuffer keeps to replay the game on the device.  `full_search` (ours) is one bool per move:
+    False for the plies of a fast search under selfplay(..., playout_cap=...), whose searches_pi row is all zero (no
+    policy target); all True without the cap."""
 
     def __init__(self, env, network, num_readouts, rec, start=None):
         self.env, self.network, self.num_readouts = env, network, num_readouts
@@ -606,6 +608,7 @@ class SelfPlayPlayer:
         self.resign_threshold = -1.0 if rec.get("resign_disabled") else -0.9       # selfplay.jl:9
         self.moves = [from_flat(int(a), env) for a in rec["moves"]]
         self.searches_pi = [np.array(p, np.float32) for p in rec["pis"]]
+        self.full_search = [bool(np.any(p != 0)) for p in self.searches_pi]
         self.qs = np.array(rec["qs"], np.float32)
         self.result = int(rec["result"])
         self.was_resign = bool(rec["was_resign"])
@@ -638,11 +641,12 @@ class SelfPlayPlayer:
     def is_done(self):                         # mcts_play.jl:120
         return True
 
-    def extract_data(self):                    # mcts_play.jl:126-139
+    def extract_data(self, targets_only=False):                    # mcts_play.jl:126-139
         start_n = 0 if self.start is None else self.start.n
         assert len(self.searches_pi) == self.root.position.n - start_n, "GoPosition history is incomplete"
         before, _ = self._replay()
-        return list(before), [p.copy() for p in self.searches_pi], [self.result] * len(before)
+        keep = [k for k in range(len(before)) if self.full_search[k] or not targets_only]
+        return [before[k] for k in keep], [self.searches_pi[k].copy() for k in keep], [self.result] * len(keep)
 
 
 # The reference draws from Julia's global RNG (selfplay.jl:9, mcts.jl:133,235, mcts_play.jl:61,66): successive selfplay
@@ -657,7 +661,7 @@ def seed(s):
 
 
 def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="f32", game_id_base=None, symmetry=None,
-             starts=None, **cfg):
+             starts=None, playout_cap=None, **cfg):
     """selfplay(env, nn, num_ro) (src/selfplay.jl:1-45) -> the finished game's player (SelfPlayPlayer), exactly the
     call train() makes (train.jl:57).  `games=G` (ours) plays G games concurrently on the device and returns a list of
     G such players ordered by game id.  Game ids continue from the previous call (module stream, `seed()`), unless
@@ -665,7 +669,9 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     symmetry (ours): None (the reference's search), "random" (every leaf evaluated under a drawn board symmetry) or a
     fixed s in 0..7 (Engine.set_symmetry).  starts (ours): a list of Positions; the game with id gid begins at
     starts[gid % len(starts)] (initialize_game!(player, pos), mcts_play.jl:110-118) instead of the empty board, and its
-    player carries that Position as `.start` (Engine.set_starts)."""
+    player carries that Position as `.start` (Engine.set_starts).  playout_cap (ours): (r, p) -- playout cap
+    randomization (Engine.set_playout_cap): a move is searched in full (noise, num_ro readouts) with probability p and
+    otherwise fast (no noise, r readouts, an all-zero searches_pi row); the player's `full_search` tells which."""
     single = games is None
     games = 1 if single else int(games)
     if seed is None:
@@ -684,6 +690,8 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
         eng.set_symmetry(symmetry)
     if starts:
         eng.set_starts(starts)
+    if playout_cap is not None:
+        eng.set_playout_cap(*playout_cap)
     eng.start(games)
     while eng.records_count() < games:
         eng.step(16)
@@ -967,12 +975,13 @@ def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, se
     return ok
 
 
-def extract_data(player, record=None):
+def extract_data(player, record=None, targets_only=False):
     """extract_data(player) -> (positions, pis, results), mcts_play.jl:126-139: one argument, the player selfplay()
     returned or a live MCTSPlayer (train.jl:58).  The round <= 5 form extract_data(env, record) for a bare GameRecord
-    is still accepted."""
+    is still accepted.  targets_only=True (ours, for selfplay(..., playout_cap=...) players) drops the plies of fast
+    searches -- the all-zero pi rows -- from all three lists; the default keeps every ply, zero rows included."""
     if record is None:
-        return player.extract_data()
+        return player.extract_data(targets_only=True) if targets_only else player.extract_data()
     env, pos, positions = player, Position(player), []
     for c in record.moves:
         positions.append(pos)
@@ -1040,7 +1049,7 @@ def _minibatch_cuts(n):
 def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp_freq=1000, readouts=800,
           tower_height=19, model=None, start_training_after=50000, slots=None, seed=0, game_id_base=0, symmetry=None,
           augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, starts=None,
-          **cfg):
+          playout_cap=None, **cfg):
     """train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model,
     start_training_after) (src/train.jl:38-92) with `slots` games in flight on the device.  One engine
     plays, keeps the replay arena and trains; per step: agz_selfplay_step(1), one read of how many games finished, and
@@ -1055,7 +1064,9 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
     the reference prints goes here), return_log (also return one dict per game), profile (a dict filled with steps,
     wall_s, train_s, train_steps, positions and host_syncs: the library calls of the loop that synchronise the engine's
     stream, each at least once; tools/train_rate.py), starts (a list of Positions: the game with id gid begins at
-    starts[gid % len(starts)], and the replay arena rebuilds its training positions from there; as in selfplay).
+    starts[gid % len(starts)], and the replay arena rebuilds its training positions from there; as in selfplay),
+    playout_cap ((r, p): playout cap randomization as in selfplay, with a targets-only arena -- memory_size and
+    start_training_after then count target entries, the plies of full searches, and only those are sampled).
     Returns the trained NeuralNet (model itself when given)."""
     import time
     import torch
@@ -1085,6 +1096,9 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
         cuts = _minibatch_cuts(batch_size)
         if starts:
             eng.set_starts(starts)
+        if playout_cap is not None:
+            eng.set_playout_cap(*playout_cap)
+            eng.replay_set_targets_only(playout_cap[0] > 0)
         eng.set_hold(True)
         eng.start(num_games)
         eng.release()

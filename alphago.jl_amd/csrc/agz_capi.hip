@@ -314,6 +314,18 @@ agz_status agz_selfplay_set_starts(agz_engine* e, const int8_t* boards, const ag
                                    const int8_t* history, int64_t S) {
   return guard(e, [&](agz::Engine& E) { E.set_starts(boards, info, history, S); });
 }
+agz_status agz_selfplay_set_playout_cap(agz_engine* e, int32_t fast_readouts, double full_prob) {
+  return guard(e, [&](agz::Engine& E) { E.set_playout_cap(fast_readouts, full_prob); });
+}
+agz_status agz_selfplay_playout_cap_counts(agz_engine* e, int64_t out[2]) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+    E.playout_cap_counts(out);
+  });
+}
+agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on) {
+  return guard(e, [&](agz::Engine& E) { E.replay_set_targets_only(on != 0); });
+}
 agz_status agz_device_alloc(agz_engine* e, int64_t bytes, void** out) {
   return guard(e, [&](agz::Engine& E) {
     AGZ_REQUIRE(out && bytes > 0, AGZ_BAD_ARGUMENT, "bad allocation request");

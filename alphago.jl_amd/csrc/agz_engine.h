@@ -43,6 +43,9 @@ class Engine {
   // start positions of self-play / arena games and of everything that replays their records (agz_selfplay_set_starts)
   void set_starts(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t S);
   int64_t starts_count() const { return V_.st_count; }
+  // playout cap randomization of self-play (agz_selfplay_set_playout_cap): fast_readouts = 0 is off
+  void set_playout_cap(int fast_readouts, double full_prob);
+  void playout_cap_counts(int64_t out[2]);
   int64_t analyze_progress();
   void analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior);
   // analysis lines (agz_analyze_set_lines / agz_analyze_lines / agz_tree_lines): top-K candidates with their PVs
@@ -83,7 +86,11 @@ class Engine {
   void replay_clear();
   // the sampling window of train(): the newest max_entries entries stay live (agz_replay_set_window)
   void replay_set_window(int64_t max_entries);
-  int64_t replay_live_positions() const { return rp_positions_ - rp_cum_[(size_t)rp_first_game_] - rp_first_ply_; }
+  int64_t replay_live_positions() const {
+    return rp_entry_cum().back() - rp_entry_cum()[(size_t)rp_first_game_] - rp_first_ply_;
+  }
+  // targets-only arena (agz_replay_set_targets_only): an entry is a ply whose pi row is not all zero
+  void replay_set_targets_only(bool on);
   // get_replay_batch without the host: B distinct live entries drawn on the device (agz_replay_sample)
   void replay_sample(int B, uint64_t call, int sym_mode, float* feats, float* pi, float* z, int64_t* game_out,
                      int32_t* ply_out);
@@ -154,6 +161,9 @@ class Engine {
  private:
   void replay_reserve(size_t bytes);
   void replay_drop_front(size_t drop);
+  void replay_scan_targets(size_t first_new);
+  // the prefix the window and the sampler count entries by: every ply, or target plies only
+  const std::vector<int64_t>& rp_entry_cum() const { return rp_targets_only_ ? rp_tcum_ : rp_cum_; }
   void upload_view_outputs();
   void fill_synthetic_inputs(int B);
   void check_game(int g) const;
@@ -219,6 +229,15 @@ class Engine {
   int64_t rp_first_ply_ = 0;        // rp_first_game_ are dead
   DevBuf<int64_t> d_rp_cum_, d_rp_off_;   // device copies of rp_cum_ / rp_off_ for the sampler
   int64_t rp_dev_n_ = 0;            // games whose rp_cum_ / rp_off_ entries are on the device
+  // targets-only mode: rp_tcum_[k] = target plies of the games before game k (next to rp_cum_; the window's
+  // rp_first_ply_ is then an index into rp_first_game_'s target list); d_rp_tply_[rp_cum_[k] + i] = the i-th target ply
+  // of game k, written by k_replay_targets at ingest
+  bool rp_targets_only_ = false;
+  std::vector<int64_t> rp_tcum_{0};
+  DevBuf<int64_t> d_rp_tcum_;
+  DevBuf<int16_t> d_rp_tply_;
+  DevBuf<int64_t> tgt_idx_;         // replay_scan_targets: offsets and position prefix of the games just filed
+  DevBuf<int32_t> tgt_cnt_;         // ... and their target counts
   DevBuf<int64_t> smp_off_, smp_game_;
   DevBuf<int32_t> smp_ply_, smp_sym_;
   DevBuf<int8_t> smp_boards_;

@@ -484,6 +484,31 @@ __global__ __launch_bounds__(kWave) void k_replay_arena_batch(View V, const uint
   if (z_out && w.leader()) z_out[b] = (float)h.result;
 }
 
+// agz_replay_set_targets_only, the index: one wave per newly filed game scans its pi rows; a ply whose row is not all
+// zero is a policy target (a fast search of agz_selfplay_set_playout_cap and an arena record leave zero rows).  The
+// game's target plies go, in order, to tply[cum[g] ..] -- its share of an array laid out by the arena's position prefix,
+// which has room for every ply -- and their number to count[g].
+__global__ __launch_bounds__(kWave) void k_replay_targets(const uint8_t* arena, const int64_t* rec_off,
+                                                           const int64_t* cum, int A, int16_t* tply, int32_t* count) {
+  HipWave w;
+  const int g = blockIdx.x;
+  const uint8_t* r = arena + rec_off[g];
+  const agz_game_header h = *reinterpret_cast<const agz_game_header*>(r);
+  const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * (size_t)h.num_moves + 3) & ~(size_t)3;
+  const float* pi = reinterpret_cast<const float*>(r + o_pi);
+  int16_t* out = tply + cum[g];
+  int n = 0;
+  for (int k = 0; k < h.num_moves; ++k) {
+    bool nz = false;
+    w.for_each(A, [&](int i) { nz = nz || pi[(size_t)k * A + i] != 0.f; });
+    if (w.any(nz)) {
+      if (w.leader()) out[n] = (int16_t)k;
+      ++n;
+    }
+  }
+  if (w.leader()) count[g] = n;
+}
+
 // agz_selfplay_release: every slot parked in G_IDLE may claim its next game at the next k_pre
 __global__ void k_release(View V) {
   const int g = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -498,9 +523,12 @@ __global__ void k_release(View V) {
 // and b' < b: the second case is a chain through strictly smaller b that each thread follows on its own.  dup is the
 // first-drawer test of an LDS hash table (atomicCAS on the key, atomicMin on the drawer).  Each entry e of the window is
 // then mapped to (game, ply) by a binary search for the last k with cum[k] <= first + e over the arena's position prefix.
+// Targets-only arena (tply != NULL): the entries are target plies, cum is the target prefix, and the entry's index
+// inside its game is looked up in the game's target list tply[pcum[k] ..] (k_replay_targets) to give the ply.
 constexpr int kSampleMax = 2048, kSampleHash = 4096, kSampleThreads = 1024;
 __global__ __launch_bounds__(kSampleThreads) void k_replay_sample(uint64_t seed, uint64_t call, int B, int64_t L,
                                                                   int64_t first, const int64_t* cum, const int64_t* goff,
+                                                                  const int64_t* pcum, const int16_t* tply,
                                                                   int64_t ngames, int sym_mode, int64_t* rec_off,
                                                                   int32_t* ply, int32_t* sym, int64_t* game_out,
                                                                   int32_t* ply_out) {
@@ -541,7 +569,8 @@ __global__ __launch_bounds__(kSampleThreads) void k_replay_sample(uint64_t seed,
       const int64_t mid = (lo + hi) >> 1;
       if (cum[mid] <= a) lo = mid; else hi = mid;
     }
-    const int32_t p = (int32_t)(a - cum[lo]);
+    int32_t p = (int32_t)(a - cum[lo]);
+    if (tply) p = (int32_t)tply[pcum[lo] + p];
     rec_off[b] = goff[lo];
     ply[b] = p;
     if (sym)
@@ -736,6 +765,35 @@ void Engine::analyze_start(const int8_t* boards, const agz_position_info* info, 
   V_.rv_moves = nullptr;
   V_.rv_off = nullptr;
   begin_analysis_run(B, B, game_id_base);
+}
+
+// ---- playout cap randomization (agz_selfplay_set_playout_cap)
+
+void Engine::set_playout_cap(int fast_readouts, double full_prob) {
+  AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "playout cap: an arena_mode engine plays evaluate() games only");
+  AGZ_REQUIRE(fast_readouts >= 0 && fast_readouts <= V_.R, AGZ_BAD_ARGUMENT,
+              "playout cap: %d fast readouts, 0 (off) or 1..num_readouts = %d", fast_readouts, V_.R);
+  AGZ_REQUIRE(fast_readouts == 0 || (full_prob >= 0.0 && full_prob <= 1.0), AGZ_BAD_ARGUMENT,
+              "playout cap: full_prob %g not in [0, 1]", full_prob);
+  // a game asks the coin again when it plays the move: the setting changes only between games
+  if (!V_.analysis && stepped_) {
+    agz_stats st;
+    stats(&st);
+    AGZ_REQUIRE(st.live_games == 0, AGZ_BAD_ARGUMENT, "playout cap: %lld games of the current run are still being played",
+                (long long)st.live_games);
+  }
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  V_.cap_fast = fast_readouts;
+  V_.cap_full_prob = fast_readouts > 0 ? full_prob : 1.0;
+}
+
+void Engine::playout_cap_counts(int64_t out[2]) {
+  unsigned long long c[2];
+  static_assert(CT_CAP_FAST == CT_CAP_FULL + 1, "the two counters are read as one pair");
+  AGZ_HIP(hipMemcpyAsync(c, V_.counters + CT_CAP_FULL, sizeof(c), hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  out[0] = (int64_t)c[0];
+  out[1] = (int64_t)c[1];
 }
 
 // ---- start positions of self-play and arena games (agz_selfplay_set_starts)
@@ -1339,6 +1397,7 @@ int64_t Engine::replay_ingest_chunks(const uint8_t* dbuf, const std::vector<int6
   AGZ_HIP(hipStreamSynchronize(stream_));
   AGZ_REQUIRE(bad == 0, AGZ_BAD_ARGUMENT, "packed records are malformed (a record runs past its chunk or a count does not match)");
   replay_reserve(rp_used_ + (size_t)total_bytes);
+  const size_t first_new = rp_hdr_.size();
   int64_t added = 0;
   for (int c = 0; c < nc; ++c) {
     if (cbytes[c] == 0) continue;
@@ -1352,6 +1411,7 @@ int64_t Engine::replay_ingest_chunks(const uint8_t* dbuf, const std::vector<int6
     added += found[c];
     rp_used_ += (size_t)cbytes[c];
   }
+  if (rp_targets_only_ && added > 0) replay_scan_targets(first_new);
   AGZ_HIP(hipStreamSynchronize(stream_));
   return added;
 }
@@ -1446,6 +1506,19 @@ void Engine::replay_drop_front(size_t drop) {
   AGZ_HIP(hipStreamSynchronize(stream_));
   std::swap(nb.p, rp_buf_.p);
   std::swap(nb.n, rp_buf_.n);
+  if (rp_targets_only_) {           // the target lists lie by position prefix: they move up with it
+    DevBuf<int16_t> nt;
+    nt.alloc(std::max((size_t)pos, (size_t)1 << 16));
+    if (pos > 0)
+      AGZ_HIP(hipMemcpyAsync(nt.p, d_rp_tply_.p + rp_cum_[drop], sizeof(int16_t) * (size_t)pos, hipMemcpyDeviceToDevice,
+                             stream_));
+    AGZ_HIP(hipStreamSynchronize(stream_));
+    std::swap(nt.p, d_rp_tply_.p);
+    std::swap(nt.n, d_rp_tply_.n);
+    const int64_t t0 = rp_tcum_[drop];
+    rp_tcum_.erase(rp_tcum_.begin(), rp_tcum_.begin() + drop);
+    for (auto& c : rp_tcum_) c -= t0;
+  }
   rp_off_.erase(rp_off_.begin(), rp_off_.begin() + drop);
   rp_hdr_.erase(rp_hdr_.begin(), rp_hdr_.begin() + drop);
   for (auto& o : rp_off_) o -= (int64_t)cut;
@@ -1463,10 +1536,12 @@ void Engine::replay_drop_front(size_t drop) {
   rp_dev_n_ = 0;
 }
 
+// (the targets-only mode is a setting of the arena, not part of its contents: it stays as it is)
 void Engine::replay_clear() {
   rp_off_.clear();
   rp_hdr_.clear();
   rp_cum_.assign(1, 0);
+  rp_tcum_.assign(1, 0);
   rp_used_ = 0;
   rp_positions_ = 0;
   rp_first_game_ = 0;
@@ -1479,18 +1554,58 @@ void Engine::replay_clear() {
 // so the copy is amortised over many calls.  max_entries < 0: every entry live again (nothing dropped comes back).
 void Engine::replay_set_window(int64_t max_entries) {
   if (max_entries < 0) { rp_first_game_ = 0; rp_first_ply_ = 0; return; }
-  const int64_t cur = rp_cum_[(size_t)rp_first_game_] + rp_first_ply_;
-  const int64_t first = std::max(cur, rp_positions_ - max_entries);
+  const std::vector<int64_t>& ec = rp_entry_cum();       // every ply, or (targets-only) the target plies
+  const int64_t cur = ec[(size_t)rp_first_game_] + rp_first_ply_;
+  const int64_t first = std::max(cur, ec.back() - max_entries);
   int64_t k = rp_first_game_;
   const int64_t n = (int64_t)rp_hdr_.size();
-  while (k < n && rp_cum_[(size_t)k + 1] <= first) ++k;
+  while (k < n && ec[(size_t)k + 1] <= first) ++k;
   rp_first_game_ = k;
-  rp_first_ply_ = first - rp_cum_[(size_t)k];
+  rp_first_ply_ = first - ec[(size_t)k];
   if (k == n) {                     // nothing live
     replay_clear();
     return;
   }
   if (k > 0 && (size_t)rp_off_[(size_t)k] > rp_used_ / 2) replay_drop_front((size_t)k);
+}
+
+// The arena counts entries by target plies (agz_replay_set_targets_only).  Only while it is empty: the index of target
+// plies is built as games are filed.
+void Engine::replay_set_targets_only(bool on) {
+  AGZ_REQUIRE(rp_hdr_.empty(), AGZ_BAD_ARGUMENT, "targets only: the replay arena holds %lld games; clear it first",
+              (long long)rp_hdr_.size());
+  rp_targets_only_ = on;
+  rp_first_game_ = 0;
+  rp_first_ply_ = 0;
+}
+
+// games [first_new, count) have just been filed: k_replay_targets writes their target lists, the host extends the
+// target prefix by their counts
+void Engine::replay_scan_targets(size_t first_new) {
+  const size_t n = rp_hdr_.size(), m = n - first_new;
+  if (d_rp_tply_.n < (size_t)rp_positions_) {
+    DevBuf<int16_t> nt;
+    nt.alloc(std::max<size_t>(2 * (size_t)rp_positions_, (size_t)1 << 16));
+    const size_t have = (size_t)rp_cum_[first_new];
+    if (have) AGZ_HIP(hipMemcpyAsync(nt.p, d_rp_tply_.p, sizeof(int16_t) * have, hipMemcpyDeviceToDevice, stream_));
+    AGZ_HIP(hipStreamSynchronize(stream_));
+    std::swap(nt.p, d_rp_tply_.p);
+    std::swap(nt.n, d_rp_tply_.n);
+  }
+  DevBuf<int64_t>& d_idx = tgt_idx_;          // kept between calls: train() files one game at a time
+  DevBuf<int32_t>& d_cnt = tgt_cnt_;
+  d_idx.ensure(2 * m);
+  d_cnt.ensure(m);
+  AGZ_HIP(hipMemcpyAsync(d_idx.p, rp_off_.data() + first_new, sizeof(int64_t) * m, hipMemcpyHostToDevice, stream_));
+  AGZ_HIP(hipMemcpyAsync(d_idx.p + m, rp_cum_.data() + first_new, sizeof(int64_t) * m, hipMemcpyHostToDevice, stream_));
+  hipLaunchKernelGGL(k_replay_targets, dim3((unsigned)m), dim3(kWave), 0, stream_, (const uint8_t*)rp_buf_.p,
+                     (const int64_t*)d_idx.p, (const int64_t*)(d_idx.p + m), V_.A, d_rp_tply_.p, d_cnt.p);
+  AGZ_HIP(hipGetLastError());
+  std::vector<int32_t> cnt(m);
+  AGZ_HIP(hipMemcpyAsync(cnt.data(), d_cnt.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  rp_tcum_.resize(first_new + 1);
+  for (size_t i = 0; i < m; ++i) rp_tcum_.push_back(rp_tcum_.back() + cnt[i]);
 }
 
 // get_replay_batch (train.jl:4-12) with the draw on the device: k_replay_sample picks B distinct live entries and maps
@@ -1507,10 +1622,11 @@ void Engine::replay_sample(int B, uint64_t call, int sym_mode, float* feats, flo
               "sym_mode %d: -1 (none), 0..7 (fixed T_s) or 8 (drawn)", sym_mode);
   AGZ_REQUIRE(feats, AGZ_BAD_ARGUMENT, "feats is NULL");
   const int64_t n = (int64_t)rp_hdr_.size();
-  if (d_rp_cum_.n < (size_t)n + 1 || d_rp_off_.n < (size_t)n) {
+  if (d_rp_cum_.n < (size_t)n + 1 || d_rp_off_.n < (size_t)n || (rp_targets_only_ && d_rp_tcum_.n < (size_t)n + 1)) {
     const size_t cap = std::max<size_t>(2 * (size_t)n + 1, 1024);
     d_rp_cum_.alloc(cap);
     d_rp_off_.alloc(cap);
+    if (rp_targets_only_) d_rp_tcum_.alloc(cap);
     rp_dev_n_ = 0;
   }
   if (rp_dev_n_ < n) {
@@ -1518,6 +1634,9 @@ void Engine::replay_sample(int B, uint64_t call, int sym_mode, float* feats, flo
                            hipMemcpyHostToDevice, stream_));
     AGZ_HIP(hipMemcpyAsync(d_rp_cum_.p + rp_dev_n_, rp_cum_.data() + rp_dev_n_,
                            sizeof(int64_t) * (size_t)(n + 1 - rp_dev_n_), hipMemcpyHostToDevice, stream_));
+    if (rp_targets_only_)
+      AGZ_HIP(hipMemcpyAsync(d_rp_tcum_.p + rp_dev_n_, rp_tcum_.data() + rp_dev_n_,
+                             sizeof(int64_t) * (size_t)(n + 1 - rp_dev_n_), hipMemcpyHostToDevice, stream_));
     AGZ_HIP(hipStreamSynchronize(stream_));      // the host vectors may move with the next ingest
     rp_dev_n_ = n;
   }
@@ -1528,9 +1647,10 @@ void Engine::replay_sample(int B, uint64_t call, int sym_mode, float* feats, flo
   smp_boards_.ensure((size_t)B * 8 * V_.PP);
   const bool with_sym = sym_mode != AGZ_SYMMETRY_NONE;
   hipLaunchKernelGGL(k_replay_sample, dim3(1), dim3(kSampleThreads), 0, stream_, (uint64_t)V_.seed, call, B, L,
-                     rp_cum_[(size_t)rp_first_game_] + rp_first_ply_, (const int64_t*)d_rp_cum_.p,
-                     (const int64_t*)d_rp_off_.p, n, sym_mode, smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr,
-                     game_out, ply_out);
+                     rp_entry_cum()[(size_t)rp_first_game_] + rp_first_ply_,
+                     (const int64_t*)(rp_targets_only_ ? d_rp_tcum_.p : d_rp_cum_.p), (const int64_t*)d_rp_off_.p,
+                     (const int64_t*)d_rp_cum_.p, (const int16_t*)(rp_targets_only_ ? d_rp_tply_.p : nullptr), n, sym_mode,
+                     smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, game_out, ply_out);
   AGZ_HIP(hipGetLastError());
   if (with_sym) {
     smp_f_.ensure(per * (size_t)B);

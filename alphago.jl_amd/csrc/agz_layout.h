@@ -67,6 +67,8 @@ inline void fill_dims(View& V, const agz_config& c) {
   V.resign_disable_frac = c.resign_disable_fraction;
   V.komi = c.komi;
   V.defer_expand = 0;
+  V.cap_fast = 0;                // agz_selfplay_set_playout_cap
+  V.cap_full_prob = 1.0;
 }
 
 // visits every buffer of the View: f(pointer-reference, element count)

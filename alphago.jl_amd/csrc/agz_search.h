@@ -1066,6 +1066,14 @@ AGZ_FN bool pool_full_can_move(W& w, const View& V, int g) {
   return s > 0.f || (argmax && V.childN[ri * V.AP + V.P] > 0.f);
 }
 
+// Playout cap randomization (View::cap_fast > 0): is the search of this game's root of ply n a full one?  The coin is
+// a function of (seed, game, n) alone, so the move phase that ends a search asks again what the phase that began it
+// was told.  Off: every search is full.
+AGZ_FN bool playout_cap_full(const View& V, uint64_t game_id, int n) {
+  if (V.cap_fast <= 0) return true;
+  return agz_u01(agz_draw_u64(V.seed, game_id, (uint32_t)n, AGZ_SITE_PLAYOUT_CAP, 0)) < V.cap_full_prob;
+}
+
 // The selfplay.jl:22-43 loop body between two readout phases, for a game whose budget is spent:
 // resign check -> pick -> play (record pi and Q, re-root) -> done check -> noise for the next move.
 template <class W>
@@ -1093,14 +1101,20 @@ AGZ_FN void game_move_phase(W& w, const View& V, Scratch& S, int g) {
   if (pick_move(w, V, S, g, &a) != AGZ_OK) a = V.P;  // the reference dies on its assertion; we pass
   // play_move!(player, c): record pi and Q, then re-root (mcts_play.jl:26-50)
   const int k = G.move_count;
+  // a fast search (playout cap) leaves no policy target: its row is all zero; the bench stagger's short first search
+  // keeps its own budget and counts as full
+  const bool fast = !G.short_first && !playout_cap_full(V, G.game_id, rm.n);
   if (k < V.max_game_length) {
-    children_as_pi(w, V, S, ri, rm.n <= V.tau, V.rec_pi + ((long)g * V.max_game_length + k) * V.A);
+    float* row = V.rec_pi + ((long)g * V.max_game_length + k) * V.A;
+    if (fast) w.for_each(V.A, [&](int i) { row[i] = 0.f; });
+    else children_as_pi(w, V, S, ri, rm.n <= V.tau, row);
     if (w.leader()) {
       V.rec_moves[(long)g * V.max_game_length + k] = (int16_t)a;
       V.rec_q[(long)g * V.max_game_length + k] = q;
     }
   }
   w.sync();
+  if (V.cap_fast > 0) w.count(&V.counters[fast ? CT_CAP_FAST : CT_CAP_FULL], 1);
   AGZ_STAMP(w, V, CT_T_PICK);
   int child = V.child[ri * V.AP + a];
   if (child < 0) child = node_create_child(w, V, S, g, root, a);
@@ -1120,8 +1134,9 @@ AGZ_FN void game_move_phase(W& w, const View& V, Scratch& S, int g) {
     game_finish(w, V, S, g, result_of(sc), 0, sc);
     return;
   }
-  inject_noise(w, V, S, g, child);
-  if (w.leader()) G.target = G.rootN + (float)V.R;
+  const bool next_full = playout_cap_full(V, G.game_id, V.meta[node_index(V, g, child)].n);
+  if (next_full) inject_noise(w, V, S, g, child);
+  if (w.leader()) G.target = G.rootN + (float)(next_full ? V.R : V.cap_fast);
   w.sync();
   AGZ_STAMP(w, V, CT_T_NOISE);
 }
@@ -1811,9 +1826,10 @@ AGZ_FN void game_post(W& w, const View& V, Scratch& S, int g) {
   }
   (void)n_before;
   if (G.phase == G_INIT_WAIT) {
-    inject_noise(w, V, S, g, G.root);
+    const bool full = G.short_first || playout_cap_full(V, G.game_id, V.meta[node_index(V, g, G.root)].n);
+    if (full) inject_noise(w, V, S, g, G.root);
     if (w.leader()) {
-      float budget = (float)V.R;
+      float budget = (float)(full ? V.R : V.cap_fast);
       if (G.short_first) {
         const double u = agz_u01(agz_draw_u64(V.seed, G.game_id, 0, AGZ_SITE_STAGGER, 1000000u));
         budget = (float)(1 + (int)(u * (double)(V.R - 1)));

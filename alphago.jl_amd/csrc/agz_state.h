@@ -82,6 +82,7 @@ enum Counter : int {
   CT_T_CREATE, CT_N_CREATE,   // node_create_child (leaf expansion: board update in scratch), all callers
   CT_POOL_SHORT,   // moves played early because the pool was full
   CT_PEAK_NODES,   // max over games of nodes_used at the moment of a move
+  CT_CAP_FULL, CT_CAP_FAST,   // playout cap on (View::cap_fast > 0): moves played after a full / a fast search
   CT_COUNT
 };
 
@@ -175,6 +176,12 @@ struct View {
   const int8_t* st_board;             // [S][P]
   const int8_t* st_hist;              // [S][7][P]: older boards newest first (history_len of them are real)
   const agz_position_info* st_info;   // [S]
+  // playout cap randomization (agz_selfplay_set_playout_cap; zero = off, the View{} of the host simulator and of
+  // fill_dims): a self-play game about to search the root of ply n is full iff
+  // agz_u01(agz_draw_u64(seed, game_id, n, AGZ_SITE_PLAYOUT_CAP, 0)) < cap_full_prob -- noise and R readouts, pi recorded;
+  // otherwise fast -- no noise, cap_fast readouts, the ply's pi row all zero
+  int32_t cap_fast;                   // r
+  double cap_full_prob;               // p
 };
 
 }  // namespace agz

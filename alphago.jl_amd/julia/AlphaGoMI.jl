@@ -23,7 +23,7 @@ using Random
 export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, train, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
-       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, set_starts!, node_lines, most_visited_path, mvp_gg,
+       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, set_starts!, set_playout_cap!, playout_cap_counts, extract_targets, node_lines, most_visited_path, mvp_gg,
        # the node-level surface test/test_mcts.jl:2-5 and test/test_mcts_player.jl:3-6 import
        MCTSNode, select_leaf, maybe_add_child!, add_virtual_loss!, revert_virtual_loss!,
        incorporate_results!, inject_noise!, child_action_score, child_Q, child_U, child_N, child_W,
@@ -736,6 +736,7 @@ struct SelfPlayPlayer
   short_searches::Int                   # moves played on fewer than num_ro readouts (full node pool, agz_config.pool_policy); 0 = the reference's game
   start::Union{Nothing, Position}       # the position the game began at (selfplay(...; starts)), nothing = the empty board
   start_index::Int                      # its 0-based entry of the table of start positions, -1 = none
+  full_search::Vector{Bool}             # per move: false for a fast search of selfplay(...; playout_cap), whose searches_π entry is all zero
 end
 is_done(p::SelfPlayPlayer) = true
 get_position(p::SelfPlayPlayer) = p.root.position
@@ -745,6 +746,13 @@ function extract_data(p::SelfPlayPlayer)
   n0 = p.start === nothing ? 0 : p.start.n
   length(p.searches_π) == p.root.position.n - n0 || throw(AssertionError("length(searches_π) == root.position.n - start.n"))
   copy(p.positions), deepcopy(p.searches_π), fill(p.result, length(p.positions))
+end
+
+# extract_data without the plies of fast searches (selfplay(...; playout_cap)): their all-zero π rows are no policy targets
+function extract_targets(p::SelfPlayPlayer)
+  positions, pis, results = extract_data(p)
+  keep = findall(p.full_search)
+  positions[keep], pis[keep], results[keep]
 end
 
 # The reference draws from Julia's global RNG (selfplay.jl:9, mcts.jl:133,235, mcts_play.jl:61,66), so successive
@@ -768,6 +776,23 @@ function set_starts!(e::Engine, env::GoEnv, starts::Vector{Position})
 end
 starts_count(e::Engine) = Int(ccall((:agz_selfplay_starts_count, libagz), Int64, (Ptr{Cvoid},), e.handle))
 
+# Playout cap randomization (ours; include/agz.h agz_selfplay_set_playout_cap): the search of the root of ply n is full
+# (noise, num_readouts, π recorded) iff u01(draw(seed, game, n, site 11, 0)) < p, else fast (no noise, r readouts, the
+# ply's π row all zero: no policy target).  r = 0 switches it off.
+function set_playout_cap!(e::Engine, r::Integer, p::Real)
+  check(e, ccall((:agz_selfplay_set_playout_cap, libagz), Int32, (Ptr{Cvoid}, Int32, Float64), e.handle, r, p))
+end
+# (full, fast) moves played since agz_selfplay_start while the cap was on
+function playout_cap_counts(e::Engine)
+  out = zeros(Int64, 2)
+  check(e, ccall((:agz_selfplay_playout_cap_counts, libagz), Int32, (Ptr{Cvoid}, Ptr{Int64}), e.handle, out))
+  Int(out[1]), Int(out[2])
+end
+# the arena's entries are the plies with a non-zero π row (agz_replay_set_targets_only); only while it is empty
+function replay_set_targets_only!(e::Engine, on::Bool = true)
+  check(e, ccall((:agz_replay_set_targets_only, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, on ? 1 : 0))
+end
+
 # replay_position (board.jl:557-578) from a start position: the position before each move and the final one
 function replay_positions_from(start::Position, moves)
   positions = Position[]
@@ -781,7 +806,7 @@ end
 
 function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Nothing, Int} = nothing,
                   slots::Union{Nothing, Int} = nothing, seed = nothing, game_id_base = nothing, symmetry = nothing,
-                  starts::Union{Nothing, Vector{Position}} = nothing)
+                  starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing)
   G = games === nothing ? 1 : games
   if seed === nothing
     seed, next = STREAM[]
@@ -796,6 +821,7 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
   copy_weights!(e, nn.engine)
   symmetry === nothing || set_symmetry!(e, symmetry)
   starts === nothing || set_starts!(e, env, starts)
+  playout_cap === nothing || set_playout_cap!(e, playout_cap[1], playout_cap[2])      # (r, p)
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, G))
   while ccall((:agz_records_count, libagz), Int64, (Ptr{Cvoid},), e.handle) < G
     check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 16))
@@ -822,7 +848,8 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
                                 replay_positions_from(starts[si + 1], [from_flat(f, env) for f in fmoves])
     push!(players, SelfPlayPlayer(env, nn, num_ro, false, τ, qs[1:n], [pis[:, i] for i in 1:n], Int(h[].result), rs,
                                   FinishedRoot(final), h[].resign_disabled != 0 ? -1.0 : -0.9, final, positions,
-                                  h[].game_id, fmoves, Int(h[].short_searches), si < 0 ? nothing : starts[si + 1], si))
+                                  h[].game_id, fmoves, Int(h[].short_searches), si < 0 ? nothing : starts[si + 1], si,
+                                  Bool[any(!iszero, view(pis, :, i)) for i in 1:n]))
   end
   sort!(players, by = r -> r.game_id)
   games === nothing ? players[1] : players
@@ -1196,7 +1223,7 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
                ckp_freq::Int = 1000, readouts::Int = 800, tower_height::Int = 19, model = nothing,
                start_training_after = 50000, slots::Union{Nothing, Int} = nothing, seed = 0, game_id_base = 0,
                augment::Bool = false, callback::Function = println,
-               starts::Union{Nothing, Vector{Position}} = nothing)
+               starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing)
   cur_nn = model === nothing ? NeuralNet(env; tower_height = tower_height) : model                       # train.jl:43
   S = slots === nothing ? min(num_games, 1024) : slots
   e = Engine(board_size = env.N, tower_height = cur_nn.tower_height, games = S, num_readouts = readouts, seed = seed,
@@ -1212,6 +1239,10 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
   cuts = vcat(collect(0:32:batch_size-1), batch_size)
   length(cuts) > 2 && cuts[end] - cuts[end-1] == 1 && deleteat!(cuts, length(cuts) - 1)   # BatchNorm needs two rows
   starts === nothing || set_starts!(e, env, starts)      # game gid begins at starts[gid % S + 1]; the arena replays from there
+  if playout_cap !== nothing      # (r, p): memory_size and start_training_after then count target entries (full searches)
+    set_playout_cap!(e, playout_cap[1], playout_cap[2])
+    replay_set_targets_only!(e, playout_cap[1] > 0)
+  end
   check(e, ccall((:agz_selfplay_set_hold, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 1))
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, num_games))
   check(e, ccall((:agz_selfplay_release, libagz), Int32, (Ptr{Cvoid},), e.handle))

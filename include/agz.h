@@ -379,6 +379,17 @@ int64_t agz_replay_live_positions(agz_engine* e);        /* entries in the windo
  * inputs_are_device reads the outputs in order). */
 agz_status agz_replay_sample(agz_engine* e, int32_t B, uint64_t call, int32_t sym_mode, float* feats, float* pi, float* z,
                              int64_t* game_out, int32_t* ply_out);
+/* Targets-only arena: with on != 0 an arena ENTRY is a ply whose pi row is not all zero -- a policy target.  Zero rows
+ * are the convention for "no policy target": the fast searches of agz_selfplay_set_playout_cap write them, and so do
+ * arena (evaluate) records.  agz_replay_set_window, agz_replay_live_positions and agz_replay_sample then count, keep and
+ * draw target plies only: L is the number of live target plies, entry e the (first live target + e)-th target ply counted
+ * through the arena's games, and the Floyd draw over 0..L-1 is the one stated above, unchanged.  A sampled (game, ply) is
+ * built as always, by replaying every move of the game up to that ply.  Each ingest call indexes the games it files on
+ * the device (one wave per game scans the pi rows).  agz_replay_count, _positions, _header, _game, _batch and _trim
+ * keep counting every ply.  The mode can be changed only while the arena is empty (AGZ_BAD_ARGUMENT otherwise);
+ * agz_replay_clear empties the arena and leaves the mode as it is.  Off (the default): every call is what it is without
+ * this one. */
+agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on);
 /* device memory on the engine's GPU for a host without its own allocator (the Julia stub's train): agz_replay_sample's
  * outputs, agz_train_step's device inputs.  Freed by agz_device_free (after the engine's stream has used it). */
 agz_status agz_device_alloc(agz_engine* e, int64_t bytes, void** out);
@@ -569,6 +580,24 @@ agz_status agz_analyze_start(agz_engine* e, const int8_t* boards, const agz_posi
 agz_status agz_selfplay_set_starts(agz_engine* e, const int8_t* boards, const agz_position_info* info,
                                    const int8_t* history, int64_t S);
 int64_t agz_selfplay_starts_count(agz_engine* e);                   /* entries of the table in force, 0 = none */
+/* Playout cap randomization for self-play: most moves get a small search and are played but not trained on, a random
+ * fraction gets the full search and becomes the policy targets.  fast_readouts = r, full_prob = p; r = 0 switches it
+ * off (the default), otherwise 1 <= r <= num_readouts and 0 <= p <= 1.  Whenever a self-play game is about to search the
+ * root of ply n = position.n (after the pre-expansion of its start, and after every move), the search is
+ *   full  iff  agz_u01(agz_draw_u64(agz_config.seed, game_id, n, AGZ_SITE_PLAYOUT_CAP, 0)) < p.
+ * A full search is the move without this call: Dirichlet noise on the root, num_readouts readouts, pi recorded.  A fast
+ * search adds no noise and runs r readouts; its move is chosen by the same rule (soft pick while n < tau, arg-max
+ * after), moves and qs are recorded as usual, and the ply's pi row of the record is ALL ZEROS: "no policy target".
+ * A consumer that samples every ply gets no policy loss from such a row (the loss is -sum pi log p); a targets-only
+ * arena (agz_replay_set_targets_only) skips them.  The resign check, tree reuse, the pool policy, symmetry, the hold and
+ * the starts table (n begins at the start's n) are unchanged; the bench stagger's shortened first search keeps its
+ * budget and counts as full.  The arena, analysis, review and the single-tree calls always search num_readouts.
+ * Synchronises.  Refused (AGZ_BAD_ARGUMENT, the setting in force kept): an arena_mode engine, r or p out of range,
+ * games of a run still being played (as agz_selfplay_set_starts). */
+agz_status agz_selfplay_set_playout_cap(agz_engine* e, int32_t fast_readouts, double full_prob);
+/* out[0] = moves played after a full search, out[1] = after a fast one, since agz_selfplay_start, counted only while
+ * the cap is on.  Synchronises. */
+agz_status agz_selfplay_playout_cap_counts(agz_engine* e, int64_t out[2]);
 agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out);
 /* out[B], child_N / child_W / prior [B][A] (the root's rows when the search ended); any of them may be NULL */
 agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N, float* child_W, float* prior);

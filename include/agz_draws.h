@@ -55,6 +55,9 @@
                                     * agz_index(draw, j + 1)                        */
 #define AGZ_SITE_REPLAY_SYM 10u    /* agz_replay_sample's drawn symmetry: game = call,
                                     * move = 0, idx = sample b; s = agz_index(draw, 8) */
+#define AGZ_SITE_PLAYOUT_CAP 11u   /* agz_selfplay_set_playout_cap: move = position.n of the
+                                    * root about to be searched, idx = 0; a full search
+                                    * iff agz_u01(draw) < full_prob                    */
 
 static inline AGZ_HD uint64_t agz_mix64(uint64_t z) {
   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;

@@ -1,0 +1,261 @@
+"""Playout cap randomization (agz_selfplay_set_playout_cap) on the host simulator: before the search of the root of ply
+n a self-play game draws full = u01(draw(seed, game, n, site 11, 0)) < p; a full move is today's move (noise, R readouts,
+pi recorded), a fast one has no noise, r readouts and an all-zero pi row.  Games are held bit for bit to the twin of
+tests/cap_twin.py; the numpy restatement of the targets-only replay sampler is held to a brute-force enumeration.
+CPU only."""
+import ctypes as C
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+import alphago_jl_amd as ag
+import cap_twin as ct
+import orc
+import starts_twin as tw
+from test_hostsim_selfplay import OracleNet, bits_equal, oracle_game, run_engine
+
+L = orc.lib()
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NO_RESIGN = dict(resign_threshold=-2.0, resign_disable_fraction=0.0)     # every game plays to its natural end
+
+
+def run_cap_sim(N, net, R, r, p, seed, games, slots, starts=None, max_steps=400000, **cfg):
+    sim = ct.CapSim(board_size=N, games=slots, num_readouts=R, seed=seed, game_id_base=0, game_id_stride=1,
+                    record_capacity_games=games + 8, **cfg)
+    if starts:
+        sim.set_starts(starts)
+    sim.set_playout_cap(r, p)
+    sim.start(games)
+    steps = 0
+    while sim.counters()["finished"] < games and steps < max_steps:
+        sim.step(net.on_feats)
+        steps += 1
+    recs, cnt, caps = sim.records(), sim.counters(), sim.cap_counts()
+    sim.close()
+    return recs, cnt, caps
+
+
+def assert_cap_game_equal(r, o, what):
+    assert r["num_moves"] == o["num_moves"], (what, r["num_moves"], o["num_moves"])
+    assert (r["moves"] == o["moves"]).all(), what
+    assert r["result"] == o["result"] and r["was_resign"] == o["was_resign"], what
+    assert r["resign_disabled"] == o["resign_disabled"], what
+    assert np.float32(r["final_score"]) == np.float32(o["final_score"]), what
+    assert bits_equal(r["qs"], o["qs"]), what
+    full = o["full"]
+    got = np.ascontiguousarray(r["pis"], np.float32)
+    assert (got[~full].view(np.uint32) == 0).all(), (what, "a fast row is not all zero")
+    assert bits_equal(got[full], o["pis"][full]), what
+    assert (got[full] != 0).any(axis=1).all(), (what, "a full row is all zero")
+    assert r["short_searches"] == 0, what
+
+
+def assert_mixed(twins):
+    """the condition of the comparison set: every game has a full and a fast move, at least three of each over the set"""
+    nfull = nfast = 0
+    for o in twins:
+        assert o["full"].any() and (~o["full"]).any(), "a game of the set is all full or all fast"
+        nfull += int(o["full"].sum())
+        nfast += int((~o["full"]).sum())
+    assert nfull >= 3 and nfast >= 3, (nfull, nfast)
+
+
+# ---------------------------------------------------------------- the twin is the reference loop
+
+@pytest.mark.parametrize("N,R,games", [(5, 16, 4), (9, 16, 1)])
+def test_twin_at_p_1_is_or_selfplay_ex(N, R, games):
+    net = OracleNet(N, 1, seed=0)
+    for gid in range(games):
+        o = oracle_game(N, net, R, 3, gid, -0.9, 0.05)
+        t = ct.twin_selfplay_cap(N, net.cb, R, 4, 1.0, 3, gid, None, -0.9, 0.05)
+        assert t["full"].all() and t["searched_full"].all()
+        assert t["num_moves"] == o["num_moves"] and (t["moves"] == o["moves"][: t["num_moves"]]).all()
+        assert t["result"] == o["result"] and t["evals"] == o["evals"]
+        assert t["was_resign"] == (o["result_string"] in (b"B+R", b"W+R"))
+        assert bits_equal(t["pis"], o["pis"]) and bits_equal(t["qs"], o["qs"])
+    net.close()
+
+
+def test_twin_coin_is_the_stated_draw():
+    """u01 and the draw as include/agz_draws.h spell them, recomputed without the oracle's helpers"""
+    hdr = open(os.path.join(ROOT, "include", "agz_draws.h")).read()
+    assert re.search(r"#define AGZ_SITE_PLAYOUT_CAP 11u\b", hdr)
+    for seed, game, n in ((0, 0, 0), (5, 17, 33), (2 ** 40 + 3, 2 ** 33, 80)):
+        bits = L.or_draw_u64(seed, game, n, ct.SITE_PLAYOUT_CAP, 0)
+        u = ((bits >> 11) + 0.5) / 9007199254740992.0
+        for p in (0.0, 0.25, 0.5, 1.0):
+            assert ct.coin_full(seed, game, n, p) == (u < p)
+    assert not any(ct.coin_full(1, g, n, 0.0) for g in range(4) for n in range(20))
+    assert all(ct.coin_full(1, g, n, 1.0) for g in range(4) for n in range(20))
+
+
+# ---------------------------------------------------------------- the simulator under the cap is the twin
+
+CASES = [       # N, R, r, p, seed, games, slots
+    (5, 16, 4, 0.4, 2, 6, 3),
+    (5, 12, 12, 0.5, 11, 3, 2),          # r = R: only the noise and the target differ
+    (9, 16, 4, 0.3, 5, 2, 2),
+]
+
+
+@pytest.mark.parametrize("N,R,r,p,seed,games,slots", CASES)
+def test_sim_with_the_cap_equals_the_twin(N, R, r, p, seed, games, slots):
+    net = OracleNet(N, 1, seed=0)
+    recs, cnt, caps = run_cap_sim(N, net, R, r, p, seed, games, slots, **NO_RESIGN)
+    assert len(recs) == games and cnt["pool_exhausted"] == 0
+    twins, evals = [], 0
+    for rec in recs:
+        gid = int(rec["game_id"])
+        o = ct.twin_selfplay_cap(N, net.cb, R, r, p, seed, gid, None, -2.0, 0.0)
+        assert_cap_game_equal(rec, o, gid)
+        assert (o["full"] == ct.pattern(seed, gid, 0, o["num_moves"], p)).all()
+        assert ((np.asarray(rec["pis"]) != 0).any(axis=1) == ct.pattern(seed, gid, 0, rec["num_moves"], p)).all()
+        twins.append(o)
+        evals += o["evals"]
+    assert_mixed(twins)
+    assert cnt["evals"] == evals and cnt["positions"] == sum(o["num_moves"] for o in twins)
+    assert caps == (sum(int(o["full"].sum()) for o in twins), sum(int((~o["full"]).sum()) for o in twins))
+    net.close()
+
+
+def test_sim_with_the_cap_from_a_start_and_with_resignation():
+    """games from a table of starts (the coin is keyed by the entry's n onwards), with a resign threshold of -0.1 that
+    half of them meet: the search that resigns was decided too (fast in some games, full in another) and plays no move"""
+    N, R, r, p, seed, thr = 5, 16, 4, 0.4, 3, -0.1
+    net = OracleNet(N, 1, seed=0)
+    starts = tw.random_starts(N, (4, 7, 1), seed=0)
+    recs, cnt, caps = run_cap_sim(N, net, R, r, p, seed, 6, 3, starts=starts, resign_threshold=thr,
+                                  resign_disable_fraction=0.0)
+    twins = []
+    for rec in recs:
+        gid = int(rec["game_id"])
+        st = starts[gid % len(starts)]
+        o = ct.twin_selfplay_cap(N, net.cb, R, r, p, seed, gid, st, thr, 0.0)
+        assert o["start_n"] == st.n
+        assert len(o["searched_full"]) == o["num_moves"] + o["was_resign"]
+        assert_cap_game_equal(rec, o, gid)
+        assert (o["full"] == ct.pattern(seed, gid, st.n, o["num_moves"], p)).all()
+        twins.append(o)
+    assert_mixed(twins)
+    assert {o["was_resign"] for o in twins} == {0, 1}, "games end both ways"
+    assert {bool(o["searched_full"][-1]) for o in twins if o["was_resign"]} == {True, False}, \
+        "a fast search and a full search each resigned a game"
+    assert cnt["evals"] == sum(o["evals"] for o in twins)
+    assert caps == (sum(int(o["full"].sum()) for o in twins), sum(int((~o["full"]).sum()) for o in twins))
+    net.close()
+
+
+def test_cap_off_and_p_1_are_todays_games():
+    """r = 0 is off; (R, 1.0) is on with every search full: both play today's games, counters included"""
+    N, R, seed, games = 5, 16, 2, 4
+    net = OracleNet(N, 1, seed=0)
+    want, wct, _ = run_engine(N, net, R, seed, games, 3)
+    for r, p, counted in ((0, 0.3, False), (R, 1.0, True)):
+        got, gct, caps = run_cap_sim(N, net, R, r, p, seed, games, 3)
+        assert len(got) == len(want) == games
+        for x, y in zip(got, want):
+            for k in ("game_id", "num_moves", "result", "was_resign", "resign_disabled", "short_searches"):
+                assert x[k] == y[k], k
+            assert np.float32(x["final_score"]) == np.float32(y["final_score"])
+            assert (x["moves"] == y["moves"]).all() and bits_equal(x["pis"], y["pis"]) and bits_equal(x["qs"], y["qs"])
+        assert gct == wct
+        assert caps == ((sum(x["num_moves"] for x in want), 0) if counted else (0, 0))
+    net.close()
+
+
+# ---------------------------------------------------------------- the targets-only sampler, restated and enumerated
+
+def test_sampler_restatement_against_brute_force():
+    """floyd_entries gives B distinct entries of 0..L-1; over many calls every entry of a small window is drawn, and
+    sample_targets maps entry e to the e-th non-zero row of the window, counted through the games"""
+    rng = np.random.RandomState(0)
+    A = 5
+    games = []
+    for nm in (3, 0, 4, 2, 5, 1):                 # a game without moves and games without targets among them
+        pis = rng.rand(nm, A).astype(np.float32)
+        pis[rng.rand(nm) < 0.5] = 0.0
+        games.append(pis)
+    games[3][:] = 0.0
+    brute = [(g, k) for g, pis in enumerate(games) for k in range(len(pis)) if pis[k].any()]
+    assert ct.target_entries(games) == brute and 3 <= len(brute) < sum(len(g) for g in games)
+    assert all(g != 3 and g != 1 for g, _ in brute)
+    for window in (None, len(brute), len(brute) - 2, 2, 1):
+        live = brute if window is None else brute[len(brute) - window:]
+        seen = set()
+        for call in range(200):
+            for B in (1, min(2, len(live)), len(live)):
+                got, Lw = ct.sample_targets(7, call, B, games, window)
+                assert Lw == len(live) and len(got) == B and len(set(got)) == B
+                assert set(got) <= set(live)
+                if B == len(live):
+                    assert set(got) == set(live)
+                # entry e is the e-th live target: recompute the map from the raw Floyd entries
+                ent = ct.floyd_entries(7, call, B, len(live))
+                assert got == [live[e] for e in ent]
+                seen |= set(got)
+        assert seen == set(live)
+    # Floyd's algorithm, spelled out once more with a list instead of a set
+    for Lw, B, call in ((10, 4, 0), (6, 6, 3), (100, 17, 9)):
+        out = []
+        for b in range(B):
+            j = Lw - B + b
+            bits = L.or_draw_u64(7, call, 0, 9, j)
+            t = ((bits >> 32) * (j + 1)) >> 32
+            out.append(j if t in out else t)
+        assert out == ct.floyd_entries(7, call, B, Lw) and len(set(out)) == B and max(out) < Lw
+
+
+# ---------------------------------------------------------------- the ABI
+
+NEW_CALLS = ("agz_selfplay_set_playout_cap", "agz_selfplay_playout_cap_counts", "agz_replay_set_targets_only")
+
+
+def test_header_declares_the_new_calls_and_keeps_the_abi():
+    hdr = open(os.path.join(ROOT, "include", "agz.h")).read()
+    assert re.search(r"#define AGZ_VERSION 103\b", hdr)
+    for name in NEW_CALLS:
+        assert re.search(r"\b%s\s*\(" % name, hdr), name
+    assert C.sizeof(ag._lib.Config) == 112 and C.sizeof(ag._lib.GameHeader) == 32
+    lib = ag.load()
+    assert lib.agz_version() == 103
+    for name in NEW_CALLS:
+        assert name in lib._agz_signatures and hasattr(lib, name)
+    for who in ("selfplay", "train"):
+        assert "playout_cap" in inspect.signature(getattr(ag, who)).parameters, who
+    assert "targets_only" in inspect.signature(ag.extract_data).parameters
+    for m in ("set_playout_cap", "playout_cap_counts", "replay_set_targets_only"):
+        assert hasattr(ag.Engine, m), m
+    jl = open(os.path.join(ROOT, "alphago.jl_amd", "julia", "AlphaGoMI.jl")).read()
+    for name in NEW_CALLS:
+        assert ":%s" % name in jl, name
+
+
+def test_player_full_search_and_extract_data():
+    """SelfPlayPlayer.full_search follows the pi rows; extract_data(player, targets_only=True) drops the fast plies from
+    all three lists (built from a record dict: no device needed until positions are replayed)"""
+    A = 26
+    pis = np.zeros((4, A), np.float32)
+    pis[0, 3] = 1.0
+    pis[2, 25] = 1.0
+    rec = dict(game_id=0, moves=np.array([25, 25, 25, 25], np.int16), pis=pis, qs=np.zeros(4, np.float32), result=1,
+               was_resign=1, final_score=0.0)
+    pl = ag.SelfPlayPlayer(ag.GoEnv(5), None, 8, rec)
+    assert pl.full_search == [True, False, True, False]
+
+    class Pos:                                   # stands in for the replayed positions (the replay itself is device work)
+        def __init__(self, n):
+            self.n = n
+
+    before = [Pos(k) for k in range(4)]
+    pl._replayed = (before, Pos(4))
+    positions, got, res = ag.extract_data(pl)
+    assert positions == before and len(got) == 4 and res == [1] * 4
+    assert all((a == b).all() for a, b in zip(got, pis)) and not got[1].any() and not got[3].any()
+    positions, got, res = ag.extract_data(pl, targets_only=True)
+    assert positions == [before[0], before[2]] and res == [1, 1]
+    assert len(got) == 2 and (got[0] == pis[0]).all() and (got[1] == pis[2]).all()
+    got[0][:] = 7                                # copies: the player's rows are untouched
+    assert pl.searches_pi[0][3] == 1.0
