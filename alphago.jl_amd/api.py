@@ -345,6 +345,11 @@ class NodeView:
         ch = self._p.engine.node_children(0, self.id)
         return {int(a): NodeView(self._p, int(c)) for a, c in enumerate(ch) if c >= 0}
 
+    def pruned_pi(self, k=2.0):
+        """children_as_pi of this node with policy target pruning under k (ours, Engine.set_forced_playouts): the
+        forced visits the search did not agree with are left out; squashed iff the node's n <= tau"""
+        return self._p.engine.tree_pruned_pi(0, self.id, k)
+
     # ---- analysis lines (ours; the commented-out most_visited_path / mvp_gg / describe of mcts.jl:255-327 are the
     # definition, DESIGN.md §5f): one agz_tree_lines call each, the walk runs on the device
     def lines(self, k=4, depth=16, min_visits=1):
@@ -661,7 +666,7 @@ def seed(s):
 
 
 def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="f32", game_id_base=None, symmetry=None,
-             starts=None, playout_cap=None, **cfg):
+             starts=None, playout_cap=None, forced_playouts=None, prune_targets=True, **cfg):
     """selfplay(env, nn, num_ro) (src/selfplay.jl:1-45) -> the finished game's player (SelfPlayPlayer), exactly the
     call train() makes (train.jl:57).  `games=G` (ours) plays G games concurrently on the device and returns a list of
     G such players ordered by game id.  Game ids continue from the previous call (module stream, `seed()`), unless
@@ -671,7 +676,10 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     starts[gid % len(starts)] (initialize_game!(player, pos), mcts_play.jl:110-118) instead of the empty board, and its
     player carries that Position as `.start` (Engine.set_starts).  playout_cap (ours): (r, p) -- playout cap
     randomization (Engine.set_playout_cap): a move is searched in full (noise, num_ro readouts) with probability p and
-    otherwise fast (no noise, r readouts, an all-zero searches_pi row); the player's `full_search` tells which."""
+    otherwise fast (no noise, r readouts, an all-zero searches_pi row); the player's `full_search` tells which.
+    forced_playouts (ours): k -- forced playouts (Engine.set_forced_playouts; KataGo plays 2): in a full search a visited
+    root child below sqrt(k P sum(N)) visits is searched first; prune_targets (default on with k) records the searches_pi
+    row with the forced visits the search did not agree with left out."""
     single = games is None
     games = 1 if single else int(games)
     if seed is None:
@@ -692,6 +700,8 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
         eng.set_starts(starts)
     if playout_cap is not None:
         eng.set_playout_cap(*playout_cap)
+    if forced_playouts:
+        eng.set_forced_playouts(forced_playouts, prune_targets)
     eng.start(games)
     while eng.records_count() < games:
         eng.step(16)
@@ -1049,7 +1059,7 @@ def _minibatch_cuts(n):
 def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp_freq=1000, readouts=800,
           tower_height=19, model=None, start_training_after=50000, slots=None, seed=0, game_id_base=0, symmetry=None,
           augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, starts=None,
-          playout_cap=None, **cfg):
+          playout_cap=None, forced_playouts=None, prune_targets=True, **cfg):
     """train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model,
     start_training_after) (src/train.jl:38-92) with `slots` games in flight on the device.  One engine
     plays, keeps the replay arena and trains; per step: agz_selfplay_step(1), one read of how many games finished, and
@@ -1066,7 +1076,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
     stream, each at least once; tools/train_rate.py), starts (a list of Positions: the game with id gid begins at
     starts[gid % len(starts)], and the replay arena rebuilds its training positions from there; as in selfplay),
     playout_cap ((r, p): playout cap randomization as in selfplay, with a targets-only arena -- memory_size and
-    start_training_after then count target entries, the plies of full searches, and only those are sampled).
+    start_training_after then count target entries, the plies of full searches, and only those are sampled),
+    forced_playouts (k) and prune_targets (forced playouts and policy target pruning in the full searches, as in selfplay).
     Returns the trained NeuralNet (model itself when given)."""
     import time
     import torch
@@ -1099,6 +1110,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
         if playout_cap is not None:
             eng.set_playout_cap(*playout_cap)
             eng.replay_set_targets_only(playout_cap[0] > 0)
+        if forced_playouts:
+            eng.set_forced_playouts(forced_playouts, prune_targets)
         eng.set_hold(True)
         eng.start(num_games)
         eng.release()

@@ -323,6 +323,18 @@ agz_status agz_selfplay_playout_cap_counts(agz_engine* e, int64_t out[2]) {
     E.playout_cap_counts(out);
   });
 }
+agz_status agz_selfplay_set_forced_playouts(agz_engine* e, double k, int32_t prune) {
+  return guard(e, [&](agz::Engine& E) { E.set_forced_playouts(k, prune); });
+}
+agz_status agz_selfplay_forced_counts(agz_engine* e, int64_t out[2]) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+    E.forced_counts(out);
+  });
+}
+agz_status agz_tree_pruned_pi(agz_engine* e, int32_t g, int32_t node, double k, float* out) {
+  return guard(e, [&](agz::Engine& E) { E.tree_pruned_pi(g, node, k, out); });
+}
 agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on) {
   return guard(e, [&](agz::Engine& E) { E.replay_set_targets_only(on != 0); });
 }

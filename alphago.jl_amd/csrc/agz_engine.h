@@ -46,6 +46,10 @@ class Engine {
   // playout cap randomization of self-play (agz_selfplay_set_playout_cap): fast_readouts = 0 is off
   void set_playout_cap(int fast_readouts, double full_prob);
   void playout_cap_counts(int64_t out[2]);
+  // forced playouts and policy target pruning of self-play (agz_selfplay_set_forced_playouts): k = 0 is off
+  void set_forced_playouts(double k, int prune);
+  void forced_counts(int64_t out[2]);
+  void tree_pruned_pi(int g, int node, double k, float* out);
   int64_t analyze_progress();
   void analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior);
   // analysis lines (agz_analyze_set_lines / agz_analyze_lines / agz_tree_lines): top-K candidates with their PVs

@@ -294,6 +294,16 @@ __global__ __launch_bounds__(kWave) void k_tree_lines(View V, int g, int node, i
   node_lines(w, V, S, g, node, K, D, min_visits, out, pv, pv_N);
 }
 
+// agz_tree_pruned_pi: pruned_pi of one node of single tree g under forced_k = k, whatever the engine's setting; the
+// squash is the node's own n <= tau, the scale that of the node's own N
+__global__ __launch_bounds__(kWave) void k_tree_pruned_pi(View V, int g, int node, double k, float* out) {
+  AGZ_SCRATCH(S)
+  HipWave w;
+  V.forced_k = k;
+  const long ni = node_index(V, g, node);
+  pruned_pi(w, V, S, ni, *slotN(V, g, node), V.meta[ni].n <= V.tau, out);
+}
+
 __global__ __launch_bounds__(kWave) void k_go_play(View V, const int8_t* boards, const int8_t* tp, const int32_t* ko,
                                                     const int32_t* moves, int B, int8_t* bo, int32_t* ko_o,
                                                     int32_t* nc, int32_t* st) {
@@ -785,6 +795,44 @@ void Engine::set_playout_cap(int fast_readouts, double full_prob) {
   AGZ_HIP(hipStreamSynchronize(stream_));
   V_.cap_fast = fast_readouts;
   V_.cap_full_prob = fast_readouts > 0 ? full_prob : 1.0;
+}
+
+// ---- forced playouts and policy target pruning (agz_selfplay_set_forced_playouts)
+
+void Engine::set_forced_playouts(double k, int prune) {
+  AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "forced playouts: an arena_mode engine plays evaluate() games only");
+  AGZ_REQUIRE(k >= 0.0 && k <= 1024.0, AGZ_BAD_ARGUMENT, "forced playouts: k = %g, not in 0 (off) .. 1024", k);   // NaN fails
+  AGZ_REQUIRE(prune == 0 || k > 0.0, AGZ_BAD_ARGUMENT, "forced playouts: pruning needs k > 0");
+  // a search forced from its first descent and a target pruned by the same k: the setting changes only between games
+  if (!V_.analysis && stepped_) {
+    agz_stats st;
+    stats(&st);
+    AGZ_REQUIRE(st.live_games == 0, AGZ_BAD_ARGUMENT,
+                "forced playouts: %lld games of the current run are still being played", (long long)st.live_games);
+  }
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  V_.forced_k = k;
+  V_.forced_prune = prune != 0;
+}
+
+void Engine::forced_counts(int64_t out[2]) {
+  unsigned long long c[2];
+  static_assert(CT_PRUNED_ROWS == CT_FORCED_SEL + 1, "the two counters are read as one pair");
+  AGZ_HIP(hipMemcpyAsync(c, V_.counters + CT_FORCED_SEL, sizeof(c), hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  out[0] = (int64_t)c[0];
+  out[1] = (int64_t)c[1];
+}
+
+void Engine::tree_pruned_pi(int g, int node, double k, float* out) {
+  check_node(g, node);
+  AGZ_REQUIRE(k >= 0.0 && k <= 1024.0, AGZ_BAD_ARGUMENT, "pruned pi: k = %g, not in 0..1024", k);
+  AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+  s_f32a_.ensure(V_.A);
+  hipLaunchKernelGGL(k_tree_pruned_pi, dim3(1), dim3(kWave), 0, stream_, V_, g, node, k, s_f32a_.p);
+  AGZ_HIP(hipGetLastError());
+  AGZ_HIP(hipMemcpyAsync(out, s_f32a_.p, sizeof(float) * V_.A, hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
 }
 
 void Engine::playout_cap_counts(int64_t out[2]) {

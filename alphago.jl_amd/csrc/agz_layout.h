@@ -69,6 +69,8 @@ inline void fill_dims(View& V, const agz_config& c) {
   V.defer_expand = 0;
   V.cap_fast = 0;                // agz_selfplay_set_playout_cap
   V.cap_full_prob = 1.0;
+  V.forced_k = 0.0;              // agz_selfplay_set_forced_playouts
+  V.forced_prune = 0;
 }
 
 // visits every buffer of the View: f(pointer-reference, element count)

@@ -498,13 +498,28 @@ AGZ_FN double action_score_v(float n, float wv, float p, float to_play, double s
   return (double)qs + u;
 }
 
+// Forced playouts (View::forced_k = k > 0).  At the root level of a descent a legal child that has been
+// visited at all is UNDER-FORCED while N_a < sqrt(k * P_a * T), T = sum of the root's child visits; stated without the
+// root, in f64, in this order of operations.  Under-forced children all score kForcedScore, above every real score, so
+// the unchanged arg-max and tie rule picks among them.
+constexpr double kForcedScore = 1.0e300;
+AGZ_FN bool under_forced(double k, float n, float p, float total) {
+  return n > 0.0f && (double)n * (double)n < (k * (double)p) * (double)total;
+}
+
+// Does a descent of game slot g from its root run under the forced rule?  Self-play full searches do (every search
+// with the playout cap off); fast searches, the arena, analysis and review never; a single tree (G_MANUAL) follows the
+// setting.  root_n = position.n of the root about to be searched.
+AGZ_FN bool forced_search(const View& V, const GameState& G, int root_n);
+
 // select_leaf for waves that keep a node's child rows in registers (W::kRegisterRows, the GPU): R = ceil(AP / 64)
 // row elements per lane.  The generic form below walks FOUR dependent global round trips per tree level (meta ->
 // the node's own N in its parent's row -> its child rows for the scores -> the chosen child's id); here everything
 // that depends only on the node id -- meta, N / W / P / child-id rows, the legal words -- is requested at once, the
 // node's own N comes along from the parent's row of the level above, and the chosen child's id and N come out of the
 // registers by shuffle: one round trip per level.  Same arithmetic, same tie-break draws: the tree is bit-identical.
-template <int R, class W>
+// Forced: the descent starts at the root of a search under the forced rule; its depth 0 level alone applies it.
+template <int R, bool Forced, class W>
 AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer) {
   GameState& G = V.gs[g];
   const int A = V.A, AP = V.AP, pass = V.P;
@@ -552,12 +567,26 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
       double sc[R];
       double best = -1.0e300;
       bool have = false;
+      float total = 0.f;
+      if constexpr (Forced) {
+        if (depth == 0) {
+#pragma unroll
+          for (int r = 0; r < R; ++r) total += w.lane + 64 * r < A ? cn[r] : 0.f;
+          total = w.reduce_sum_f(total);   // visit counts are integers: order-free and exact
+        }
+      }
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         sc[r] = action_score_v(cn[r], cw[r], cp[r], tp, scale);
+        if constexpr (Forced) {
+          if (depth == 0 && under_forced(V.forced_k, cn[r], cp[r], total)) sc[r] = kForcedScore;
+        }
         if (lg[r] && (!have || sc[r] > best)) { best = sc[r]; have = true; }
       }
       best = w.reduce_max(have ? best : -1.0e300);
+      if constexpr (Forced) {
+        if (depth == 0 && best == kForcedScore) w.count(&V.counters[CT_FORCED_SEL], 1);
+      }
       int cnt = 0, idx = kIntMax;
 #pragma unroll
       for (int r = 0; r < R; ++r) {
@@ -597,14 +626,25 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
 
 // select_leaf from `from`; the visited nodes are left in S.path[0..len).  Returns the leaf.
 template <class W>
-AGZ_FN int select_leaf(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer = false) {
+AGZ_FN int select_leaf(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer = false,
+                       bool forced = false) {
   if constexpr (W::kRegisterRows) {
-    switch ((V.AP + 63) >> 6) {
-      case 1: return select_leaf_rows<1>(w, V, S, g, from, plen_out, defer);
-      case 2: return select_leaf_rows<2>(w, V, S, g, from, plen_out, defer);     // 9x9
-      case 3: return select_leaf_rows<3>(w, V, S, g, from, plen_out, defer);     // 13x13
-      case 6: return select_leaf_rows<6>(w, V, S, g, from, plen_out, defer);     // 19x19
-      default: break;
+    if (forced) {
+      switch ((V.AP + 63) >> 6) {
+        case 1: return select_leaf_rows<1, true>(w, V, S, g, from, plen_out, defer);
+        case 2: return select_leaf_rows<2, true>(w, V, S, g, from, plen_out, defer);
+        case 3: return select_leaf_rows<3, true>(w, V, S, g, from, plen_out, defer);
+        case 6: return select_leaf_rows<6, true>(w, V, S, g, from, plen_out, defer);
+        default: break;
+      }
+    } else {
+      switch ((V.AP + 63) >> 6) {
+        case 1: return select_leaf_rows<1, false>(w, V, S, g, from, plen_out, defer);
+        case 2: return select_leaf_rows<2, false>(w, V, S, g, from, plen_out, defer);     // 9x9
+        case 3: return select_leaf_rows<3, false>(w, V, S, g, from, plen_out, defer);     // 13x13
+        case 6: return select_leaf_rows<6, false>(w, V, S, g, from, plen_out, defer);     // 19x19
+        default: break;
+      }
     }
   }
   GameState& G = V.gs[g];
@@ -629,17 +669,28 @@ AGZ_FN int select_leaf(W& w, const View& V, Scratch& S, int g, int from, int* pl
     } else {
       const double scale = puct_scale(V, n_new);
       const float tp = (float)m.to_play;
+      const bool fr = forced && depth == 0;         // the forced rule: the root level only
+      float total = 0.f;
+      if (fr) {
+        w.for_each(A, [&](int a) { total += V.childN[ni * V.AP + a]; });
+        total = w.reduce_sum_f(total);   // visit counts are integers: order-free and exact
+      }
+      auto score = [&](int a) {
+        if (fr && under_forced(V.forced_k, V.childN[ni * V.AP + a], V.childP[ni * V.AP + a], total)) return kForcedScore;
+        return action_score(V, ni, a, tp, scale);
+      };
       double best = -1.0e300;
       bool have = false;
       w.for_each(A, [&](int a) {
         if (!legal_bit(V, ni, a)) return;
-        const double s = action_score(V, ni, a, tp, scale);
+        const double s = score(a);
         if (!have || s > best) { best = s; have = true; }
       });
       best = w.reduce_max(have ? best : -1.0e300);
+      if (fr && best == kForcedScore) w.count(&V.counters[CT_FORCED_SEL], 1);
       int cnt = 0, idx = kIntMax;
       w.for_each(V.AP, [&](int a) {
-        const bool f = a < A && legal_bit(V, ni, a) && action_score(V, ni, a, tp, scale) == best;
+        const bool f = a < A && legal_bit(V, ni, a) && score(a) == best;
         S.flag[a] = f;
         if (f) { cnt++; idx = a < idx ? a : idx; }
       });
@@ -784,6 +835,62 @@ AGZ_FN void children_as_pi(W& w, const View& V, Scratch& S, long ni, bool squash
     w.for_each(A, [&](int a) { out[a] = (float)(S.dbuf[a] / s); });
   }
   w.sync();
+}
+
+// Policy target pruning: children_as_pi of the node's visits with the forced playouts (k = V.forced_k)
+// that the search did not agree with taken out.  c* = the most visited child, lowest index on ties; S* = its PUCT score
+// under scale = puct_scale(rootN).  Every other visited child a keeps
+//   N'_a = min(N_a, max(N_a - sqrt(k P_a T), N_min, 0)),   N_min = scale P_a / (S* - q_a) - 1  (N_a when S* <= q_a),
+// the visits at which its score would still not pass S*, and none at all when what is left of a reduced child is <= 1.
+// All f64 but q_a, which is action_score's f32.  The row is N' (squash: N'^0.98) over its f64 sum in ascending index
+// order, narrowed to f32 last -- for an unchanged row bit for bit children_as_pi's.  Returns whether some N'_a < N_a.
+template <class W>
+AGZ_FN bool pruned_pi(W& w, const View& V, Scratch& S, long ni, float rootN, bool squash, float* out) {
+  const int A = V.A;
+  const float* cN = V.childN + ni * V.AP;
+  float mx = -1.0f, part = 0.f;
+  w.for_each(A, [&](int a) { const float c = cN[a]; mx = c > mx ? c : mx; part += c; });
+  mx = w.reduce_max_f(mx);
+  const float total = w.reduce_sum_f(part);   // visit counts are integers: order-free and exact
+  int cs = kIntMax;
+  w.for_each(A, [&](int a) { if (cN[a] == mx && a < cs) cs = a; });
+  cs = w.reduce_min(cs);
+  const float tp = (float)V.meta[ni].to_play;
+  const double scale = puct_scale(V, rootN);
+  const double s_star = action_score(V, ni, cs, tp, scale);
+  const double k = V.forced_k;
+  bool changed = false;
+  w.sync();
+  w.for_each(A, [&](int a) {
+    const float n = cN[a];
+    double keep = (double)n;
+    if (a != cs && n > 0.0f) {
+      const double p = (double)V.childP[ni * V.AP + a];
+      const double nf = sqrt((k * p) * (double)total);
+      const float denom = 1.0f + n;
+      const float q = V.childW[ni * V.AP + a] / denom;
+      const float qs = q * tp;
+      const double gap = s_star - (double)qs;
+      const double n_min = gap <= 0.0 ? (double)n : (scale * p) / gap - 1.0;
+      double m = (double)n - nf;
+      m = n_min > m ? n_min : m;
+      m = m > 0.0 ? m : 0.0;
+      m = m < (double)n ? m : (double)n;
+      if (m < (double)n) {
+        if (m <= 1.0) m = 0.0;
+        changed = true;
+      }
+      keep = m;
+    }
+    S.dbuf[a] = squash ? agz_pow(keep, 0.98) : keep;
+  });
+  changed = w.any(changed);
+  w.sync();
+  double s = 0.0;
+  for (int a = 0; a < A; ++a) s += S.dbuf[a];   // fixed ascending order on every lane
+  w.for_each(A, [&](int a) { out[a] = (float)(S.dbuf[a] / s); });
+  w.sync();
+  return changed;
 }
 
 // pick_move (mcts_play.jl:52-71).  Returns AGZ_OK / AGZ_ASSERT_SOFTPICK.
@@ -1074,6 +1181,12 @@ AGZ_FN bool playout_cap_full(const View& V, uint64_t game_id, int n) {
   return agz_u01(agz_draw_u64(V.seed, game_id, (uint32_t)n, AGZ_SITE_PLAYOUT_CAP, 0)) < V.cap_full_prob;
 }
 
+AGZ_FN bool forced_search(const View& V, const GameState& G, int root_n) {
+  if (!(V.forced_k > 0.0) || V.arena || V.analysis) return false;
+  if (G.phase == G_MANUAL) return true;
+  return G.short_first || playout_cap_full(V, G.game_id, root_n);
+}
+
 // The selfplay.jl:22-43 loop body between two readout phases, for a game whose budget is spent:
 // resign check -> pick -> play (record pi and Q, re-root) -> done check -> noise for the next move.
 template <class W>
@@ -1106,8 +1219,13 @@ AGZ_FN void game_move_phase(W& w, const View& V, Scratch& S, int g) {
   const bool fast = !G.short_first && !playout_cap_full(V, G.game_id, rm.n);
   if (k < V.max_game_length) {
     float* row = V.rec_pi + ((long)g * V.max_game_length + k) * V.A;
-    if (fast) w.for_each(V.A, [&](int i) { row[i] = 0.f; });
-    else children_as_pi(w, V, S, ri, rm.n <= V.tau, row);
+    if (fast) {
+      w.for_each(V.A, [&](int i) { row[i] = 0.f; });
+    } else if (V.forced_prune && V.forced_k > 0.0) {     // the forced playouts do not belong in the target
+      if (pruned_pi(w, V, S, ri, G.rootN, rm.n <= V.tau, row)) w.count(&V.counters[CT_PRUNED_ROWS], 1);
+    } else {
+      children_as_pi(w, V, S, ri, rm.n <= V.tau, row);
+    }
     if (w.leader()) {
       V.rec_moves[(long)g * V.max_game_length + k] = (int16_t)a;
       V.rec_q[(long)g * V.max_game_length + k] = q;
@@ -1183,10 +1301,12 @@ AGZ_FN void game_select_phase(W& w, const View& V, Scratch& S, int g, int par, b
   // the tree may have been re-rooted, or its garbage released, since)
   if (w.leader()) { G.npend = 0; G.err = 0; }
   w.sync();
+  // one decision per phase: the root does not change inside it
+  const bool forced = V.forced_k > 0.0 && forced_search(V, G, V.meta[node_index(V, g, G.root)].n);
   while (nleaves < par && failsafe < 2 * par) {
     failsafe++;
     int plen = 0;
-    const int leaf = select_leaf(w, V, S, g, G.root, &plen, defer);
+    const int leaf = select_leaf(w, V, S, g, G.root, &plen, defer, forced);
     if (node_is_done(V, g, leaf)) {
       load_board(w, V, S, node_index(V, g, leaf));
       const float value = (float)result_of(area_score(w, V, S, G.komi));
@@ -1988,7 +2108,8 @@ AGZ_FN void tree_op(W& w, const View& V, Scratch& S, const TreeArgs& T) {
     } break;
     case TOP_SELECT: {
       int plen = 0;
-      r0 = select_leaf(w, V, S, g, T.node, &plen);
+      r0 = select_leaf(w, V, S, g, T.node, &plen, false,
+                       T.node == G.root && forced_search(V, G, V.meta[node_index(V, g, G.root)].n));
     } break;
     case TOP_ADD_CHILD: {
       const long ni = node_index(V, g, T.node);

@@ -83,6 +83,9 @@ enum Counter : int {
   CT_POOL_SHORT,   // moves played early because the pool was full
   CT_PEAK_NODES,   // max over games of nodes_used at the moment of a move
   CT_CAP_FULL, CT_CAP_FAST,   // playout cap on (View::cap_fast > 0): moves played after a full / a fast search
+  // forced playouts on (View::forced_k > 0): root descents the forced rule decided / recorded pi rows that policy target
+  // pruning changed (appended here: tests/cap_twin.py pins CT_PEAK_NODES's place)
+  CT_FORCED_SEL, CT_PRUNED_ROWS,
   CT_COUNT
 };
 
@@ -182,6 +185,12 @@ struct View {
   // otherwise fast -- no noise, cap_fast readouts, the ply's pi row all zero
   int32_t cap_fast;                   // r
   double cap_full_prob;               // p
+  // forced playouts and policy target pruning (agz_selfplay_set_forced_playouts; zero = off, the View{} of the host
+  // simulator and of fill_dims): in a full self-play search (and in the single-tree calls that descend from the tree's
+  // root) a visited root child a with N_a^2 < forced_k * P_a * sum N is selected ahead of the PUCT arg-max; with
+  // forced_prune the pi row of a full search is written by pruned_pi instead of children_as_pi
+  double forced_k;                    // k
+  int32_t forced_prune;
 };
 
 }  // namespace agz

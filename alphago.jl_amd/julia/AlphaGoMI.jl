@@ -23,7 +23,7 @@ using Random
 export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, train, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
-       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, set_starts!, set_playout_cap!, playout_cap_counts, extract_targets, node_lines, most_visited_path, mvp_gg,
+       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, set_starts!, set_playout_cap!, playout_cap_counts, set_forced_playouts!, forced_counts, pruned_pi, extract_targets, node_lines, most_visited_path, mvp_gg,
        # the node-level surface test/test_mcts.jl:2-5 and test/test_mcts_player.jl:3-6 import
        MCTSNode, select_leaf, maybe_add_child!, add_virtual_loss!, revert_virtual_loss!,
        incorporate_results!, inject_noise!, child_action_score, child_Q, child_U, child_N, child_W,
@@ -793,6 +793,27 @@ function replay_set_targets_only!(e::Engine, on::Bool = true)
   check(e, ccall((:agz_replay_set_targets_only, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, on ? 1 : 0))
 end
 
+# Forced playouts and policy target pruning (ours; include/agz.h agz_selfplay_set_forced_playouts): in a full self-play
+# search a visited root child a with N_a^2 < k P_a sum(N) is selected ahead of the PUCT arg-max; with prune the recorded π
+# row leaves out the forced visits the search did not agree with.  k = 0 switches both off; KataGo plays k = 2.
+function set_forced_playouts!(e::Engine, k::Real, prune::Bool = true)
+  check(e, ccall((:agz_selfplay_set_forced_playouts, libagz), Int32, (Ptr{Cvoid}, Float64, Int32), e.handle, k,
+                 (prune && k != 0) ? 1 : 0))
+end
+# (root descents the forced rule decided, recorded π rows that pruning changed) since agz_selfplay_start
+function forced_counts(e::Engine)
+  out = zeros(Int64, 2)
+  check(e, ccall((:agz_selfplay_forced_counts, libagz), Int32, (Ptr{Cvoid}, Ptr{Int64}), e.handle, out))
+  Int(out[1]), Int(out[2])
+end
+# the pruned π row of node `node` of single tree g under k, whatever the engine's setting
+function pruned_pi(e::Engine, g::Integer, node::Integer, k::Real, A::Integer)
+  out = zeros(Float32, A)
+  check(e, ccall((:agz_tree_pruned_pi, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Float32}), e.handle, g,
+                 node, k, out))
+  out
+end
+
 # replay_position (board.jl:557-578) from a start position: the position before each move and the final one
 function replay_positions_from(start::Position, moves)
   positions = Position[]
@@ -806,7 +827,8 @@ end
 
 function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Nothing, Int} = nothing,
                   slots::Union{Nothing, Int} = nothing, seed = nothing, game_id_base = nothing, symmetry = nothing,
-                  starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing)
+                  starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing,
+                  forced_playouts = nothing, prune_targets::Bool = true)
   G = games === nothing ? 1 : games
   if seed === nothing
     seed, next = STREAM[]
@@ -822,6 +844,7 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
   symmetry === nothing || set_symmetry!(e, symmetry)
   starts === nothing || set_starts!(e, env, starts)
   playout_cap === nothing || set_playout_cap!(e, playout_cap[1], playout_cap[2])      # (r, p)
+  forced_playouts === nothing || set_forced_playouts!(e, forced_playouts, prune_targets)   # k
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, G))
   while ccall((:agz_records_count, libagz), Int64, (Ptr{Cvoid},), e.handle) < G
     check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 16))
@@ -1223,7 +1246,8 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
                ckp_freq::Int = 1000, readouts::Int = 800, tower_height::Int = 19, model = nothing,
                start_training_after = 50000, slots::Union{Nothing, Int} = nothing, seed = 0, game_id_base = 0,
                augment::Bool = false, callback::Function = println,
-               starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing)
+               starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing,
+               forced_playouts = nothing, prune_targets::Bool = true)
   cur_nn = model === nothing ? NeuralNet(env; tower_height = tower_height) : model                       # train.jl:43
   S = slots === nothing ? min(num_games, 1024) : slots
   e = Engine(board_size = env.N, tower_height = cur_nn.tower_height, games = S, num_readouts = readouts, seed = seed,
@@ -1243,6 +1267,7 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
     set_playout_cap!(e, playout_cap[1], playout_cap[2])
     replay_set_targets_only!(e, playout_cap[1] > 0)
   end
+  forced_playouts === nothing || set_forced_playouts!(e, forced_playouts, prune_targets)   # k, as in selfplay
   check(e, ccall((:agz_selfplay_set_hold, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 1))
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, num_games))
   check(e, ccall((:agz_selfplay_release, libagz), Int32, (Ptr{Cvoid},), e.handle))

@@ -513,6 +513,10 @@ agz_status agz_tree_node_set_floats(agz_engine* e, int32_t g, int32_t node, int3
 agz_status agz_tree_node_set_N(agz_engine* e, int32_t g, int32_t node, float value);
 agz_status agz_tree_node_set_n(agz_engine* e, int32_t g, int32_t node, int32_t n);
 agz_status agz_tree_node_children(agz_engine* e, int32_t g, int32_t node, int32_t* out /* [A] */);
+/* the pruned pi row (agz_selfplay_set_forced_playouts, PRUNED TARGET) of one node of single tree g under the k given
+ * here, whatever the engine's setting: the node's rows, scale from the node's own N, squashed iff the node's n <= tau.
+ * out float[A].  k = 0 gives children_as_pi's row.  One small kernel; synchronises. */
+agz_status agz_tree_pruned_pi(agz_engine* e, int32_t g, int32_t node, double k, float* out);
 agz_status agz_tree_node_board(agz_engine* e, int32_t g, int32_t node, int8_t* out /* [N*N] */);
 agz_status agz_tree_pending_vlosses(agz_engine* e, int32_t g, int32_t* out);
 agz_status agz_tree_set_draw(agz_engine* e, int32_t g, uint64_t game_id, uint32_t sel);
@@ -598,6 +602,39 @@ agz_status agz_selfplay_set_playout_cap(agz_engine* e, int32_t fast_readouts, do
 /* out[0] = moves played after a full search, out[1] = after a fast one, since agz_selfplay_start, counted only while
  * the cap is on.  Synchronises. */
 agz_status agz_selfplay_playout_cap_counts(agz_engine* e, int64_t out[2]);
+/* Forced playouts and policy target pruning for self-play (KataGo's pair of rules).  k = 0 switches both
+ * off (the default); KataGo plays k = 2.  prune != 0 asks for the pruned target as well and needs k > 0.
+ * FORCED SELECTION, at the root level of a descent only (depth 0 of a descent that starts at the root).  After the
+ * pass-first rule of mcts.jl:119-126, which keeps its precedence: let T = sum over all A actions of the root's child_N
+ * (a Float32 sum of integers).  A legal child a is UNDER-FORCED iff child_N[a] > 0 and
+ *   (double)N * (double)N < ((double)k * (double)P[a]) * (double)T        (N = child_N[a], P = child_prior)
+ * in Float64 in this order.  If any child is under-forced, every under-forced child scores one common value above every
+ * real score, and the unchanged tie rule (the lowest index, or the AGZ_SITE_PUCT_TIE draw keyed sel * 1024 + depth)
+ * picks among them.  Levels below the root are untouched.
+ * PRUNED TARGET, when a move is recorded.  With the root's rows N, W, P, tp = to_play, scale = c_puct * sqrtf(1 + N(root))
+ * and T as above: c* = the child with the most visits, the lowest index on ties (no draw); S* = its action score.  For
+ * every other a with N_a > 0, in Float64 except q:
+ *   nf = sqrt((k * P_a) * T);  q = (W_a / (1.0f + N_a)) * tp in Float32;  gap = S* - q;
+ *   N_min = N_a if gap <= 0, else (scale * P_a) / gap - 1;  N'_a = min(N_a, max(N_a - nf, N_min, 0));
+ *   if N'_a < N_a and N'_a <= 1 then N'_a = 0.
+ * N'_c* = N_c*, and N'_a = 0 where N_a = 0.  The pi row is children_as_pi's transform of N': N'_a (agz_pow(N'_a, 0.98)
+ * while n <= tau) over the Float64 sum in ascending index order, narrowed to Float32 last -- bit for bit today's row
+ * when no N'_a differs from N_a.  The move played, the recorded q, the resign check and the re-rooting use the raw
+ * visits.
+ * WHERE.  Self-play full searches only: every search with the playout cap off; with it on the searches the coin made
+ * full (the bench stagger's shortened first search counts as full).  Fast searches are neither forced nor recorded, as
+ * before.  The arena never forces or prunes; analysis and review, on any engine, never do either.  The single-tree calls
+ * agz_tree_select_leaf, agz_tree_search and agz_tree_search_select FOLLOW THE ENGINE'S SETTING whenever the descent starts
+ * at the tree's root (agz_tree_select_leaf from another node does not force): that is how a host-driven MCTSPlayer loop
+ * equals device self-play, and how hand-made rows reach the rule.  agz_tree_play_move records children_as_pi as before;
+ * agz_tree_pruned_pi gives the pruned row of any node.
+ * No draw site is added and none moves; records, agz_game_header, agz_config and agz_stats do not change.
+ * Synchronises.  Refused (AGZ_BAD_ARGUMENT, the setting in force kept): an arena_mode engine; k negative, NaN or above
+ * 1024; prune != 0 with k == 0; games of a run still being played (as agz_selfplay_set_playout_cap). */
+agz_status agz_selfplay_set_forced_playouts(agz_engine* e, double k, int32_t prune);
+/* out[0] = root descents that the forced rule decided (some child was under-forced), out[1] = recorded pi rows that
+ * pruning changed (some N'_a < N_a), since agz_selfplay_start.  Synchronises. */
+agz_status agz_selfplay_forced_counts(agz_engine* e, int64_t out[2]);
 agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out);
 /* out[B], child_N / child_W / prior [B][A] (the root's rows when the search ended); any of them may be NULL */
 agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N, float* child_W, float* prior);

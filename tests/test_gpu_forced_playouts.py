@@ -1,0 +1,400 @@
+"""Forced playouts and policy target pruning on the device (agz_selfplay_set_forced_playouts, agz_tree_pruned_pi,
+DESIGN.md §5i).
+
+Every self-play game must be, bit for bit, the twin's game (tests/forced_twin.py: the reference's loop with the forced
+root descent in its full searches and the pruned target in their pi rows) on the engine's own forward -- under the
+playout cap, from a table of starts, with drawn symmetries.  The single-tree calls reach the rule with hand-made rows at
+the four register-row widths of the descent.  Off is the engine that never made the call, byte for byte; analysis never
+forces; train(..., forced_playouts=...) plays the twin's games on the weights of each round."""
+import numpy as np
+import pytest
+
+import alphago_jl_amd as ag
+import forced_twin as ft
+import orc
+import starts_twin as tw
+from alphago_jl_amd import symmetry as sy
+from gpu_common import GpuNetForOracle
+from test_hostsim_selfplay import bits_equal
+
+pytestmark = pytest.mark.gpu
+L = orc.lib()
+BAD_ARGUMENT = ag._lib.BAD_ARGUMENT
+CAP = (8, 0.5)
+THR = -0.1
+
+
+def play(eng, games, chunk=8):
+    eng.start(games)
+    for _ in range(400000):
+        eng.step(chunk)
+        if eng.records_count() >= games:
+            break
+    recs, st = eng.records(), eng.stats()
+    assert len(recs) == games and st["pool_exhausted"] == 0 and st["pool_short_searches"] == 0
+    return sorted(recs, key=lambda r: r["game_id"]), st
+
+
+def assert_game_equal(r, o, what):
+    full = o["full"]
+    print(f"game {what}: {r['num_moves']} moves ({int(full.sum())} full), result {r['result']}, resign {r['was_resign']}; "
+          f"twin {o['num_moves']} / {o['result']} / {o['was_resign']}, evals {o['evals']}, forced {o['forced_sel']}, "
+          f"rows changed {int(o['pruned_rows'].sum())}")
+    assert r["num_moves"] == o["num_moves"], what
+    assert (r["moves"] == o["moves"]).all(), what
+    assert r["result"] == o["result"] and r["was_resign"] == o["was_resign"], what
+    assert r["resign_disabled"] == o["resign_disabled"], what
+    assert np.float32(r["final_score"]) == np.float32(o["final_score"]), what
+    assert bits_equal(r["qs"], o["qs"]), what
+    if r["num_moves"]:
+        got = np.ascontiguousarray(r["pis"], np.float32)
+        assert (got[~full].view(np.uint32) == 0).all(), (what, "a fast row is not all zero")
+        assert bits_equal(got[full], o["pis"][full]), what
+    assert r["short_searches"] == 0, what
+
+
+def check_set(eng, recs, st, twins):
+    for r, o in zip(recs, twins):
+        assert_game_equal(r, o, int(r["game_id"]))
+    for o in twins:           # the condition of the comparison set
+        assert o["forced_sel"] >= 1, "a game of the set has no forced selection"
+        assert o["pruned_rows"].any(), "a game of the set has no row that pruning changed"
+    nforced, nrows = sum(o["forced_sel"] for o in twins), sum(int(o["pruned_rows"].sum()) for o in twins)
+    print(f"{len(recs)} games: {nforced} forced selections, {nrows} rows changed, evals {st['evals']}")
+    assert eng.forced_counts() == (nforced, nrows)
+    assert st["evals"] == sum(o["evals"] for o in twins)
+    assert st["positions"] == sum(o["num_moves"] for o in twins)
+    assert eng.playout_cap_counts() == (sum(int(o["full"].sum()) for o in twins),
+                                        sum(int((~o["full"]).sum()) for o in twins))
+
+
+# ---------------------------------------------------------------- bit-exact games
+
+@pytest.mark.parametrize("N,tower,R,k,games,slots,seed,plies", [
+    (9, 2, 32, 2.0, 6, 32, 4, (6, 11, 2)),
+    (9, 2, 32, 16.0, 6, 32, 4, (6, 11, 2)),
+    (5, 1, 16, 2.0, 6, 32, 3, (4, 7, 1)),
+    (5, 1, 16, 16.0, 5, 32, 3, (4, 7, 1)),
+])
+def test_games_equal_the_twin(N, tower, R, k, games, slots, seed, plies):
+    starts = tw.random_starts(N, plies, seed=0)
+    eng = ag.Engine(board_size=N, tower_height=tower, games=slots, num_readouts=R, seed=seed,
+                    record_capacity_games=games + 8, resign_threshold=THR, resign_disable_fraction=0.0)
+    eng.init_synthetic(0)
+    b, i, h = tw.opos_arrays(starts)
+    eng.set_starts(boards=b, info=i, history=h)
+    eng.set_playout_cap(*CAP)
+    eng.set_forced_playouts(k)
+    recs, st = play(eng, games)
+    fwd = ag.Engine(board_size=N, tower_height=tower, games=1, num_readouts=8, max_nodes_per_game=16)
+    fwd.init_synthetic(0)
+    cb = GpuNetForOracle(fwd).cb
+    twins = [ft.twin_selfplay_forced(N, cb, R, CAP[0], CAP[1], k, True, seed, int(r["game_id"]),
+                                     starts[int(r["game_id"]) % len(starts)], THR, 0.0) for r in recs]
+    check_set(eng, recs, st, twins)
+    eng.close()
+    fwd.close()
+
+
+def test_games_with_random_symmetry_equal_the_twin():
+    from test_gpu_symmetry import SymNetForOracle, peaked_engine
+    N, tower, R, k, games, seed = 9, 1, 32, 2.0, 3, 4
+    starts = tw.random_starts(N, (6, 11, 2), seed=0)
+    eng = peaked_engine(N, tower, games=games, num_readouts=R, seed=seed, record_capacity_games=games + 8,
+                        resign_threshold=THR, resign_disable_fraction=0.0)
+    b, i, h = tw.opos_arrays(starts)
+    eng.set_starts(boards=b, info=i, history=h)
+    eng.set_symmetry("random")
+    eng.set_playout_cap(*CAP)
+    eng.set_forced_playouts(k)
+    recs, st = play(eng, games)
+    fwd = peaked_engine(N, tower, games=1, num_readouts=8, max_nodes_per_game=16)
+    twins = []
+    for r in recs:
+        gid = int(r["game_id"])
+        net = SymNetForOracle(fwd, seed, gid, sy.RANDOM)
+        twins.append(ft.twin_selfplay_forced(N, net.cb, R, CAP[0], CAP[1], k, True, seed, gid, starts[gid % 3], THR, 0.0))
+    check_set(eng, recs, st, twins)
+    eng.close()
+    fwd.close()
+
+
+# ---------------------------------------------------------------- the single-tree known answers
+
+EX_N = [60, 20, 12, 1, 6]
+EX_P = [0.50, 0.20, 0.10, 0.05, 0.15]
+EX_W = [30.5, 0, 6.25, 0, 3.5]
+
+
+def set_rows(eng, N, at, rootN, n):
+    """a fresh single tree on slot 0 whose expanded root holds the example's children at actions `at`"""
+    A = N * N + 1
+    root = eng.tree_init(0, np.zeros(N * N, np.int8), n=n)
+    assert eng.select_leaf(0, root) == root
+    assert eng.incorporate_results(0, root, np.full(A, 1.0 / A, np.float32), 0.0, root) == 0
+    rows = []
+    for field, vals in ((ag._lib.F_CHILD_N, EX_N), (ag._lib.F_CHILD_W, EX_W), (ag._lib.F_CHILD_PRIOR, EX_P)):
+        row = np.zeros(A, np.float32)
+        row[list(at)] = np.asarray(vals, np.float32)
+        eng.node_set_floats(0, root, field, row)
+        rows.append(row)
+    eng.node_set_N(0, root, rootN)
+    return root, rows
+
+
+@pytest.mark.parametrize("N", [5, 9, 13, 19])
+def test_single_tree_known_answers(N):
+    """N = 5, 9, 13, 19: select_leaf_rows<1|2|3|6>.  The under-forced child sits at action A - 2 (the last point) and,
+    separately, at the pass: the last register row and its lane mapping"""
+    A = N * N + 1
+    tau = ((N * N // 12) // 2) * 2
+    eng = ag.Engine(board_size=N, tower_height=1, games=1, num_readouts=8, max_nodes_per_game=64, c_puct=1.0, seed=1)
+    eng.init_synthetic(0)
+    for u in (A - 2, A - 1):
+        at = (0, A // 3, A // 2, u, (2 * A) // 3)
+        assert len(set(at)) == 5
+        for n in (tau + 1, 0):                      # plain and squashed rows
+            root, rows = set_rows(eng, N, at, 99.0, n)
+            for k in (2.0, 0.0, 16.0):
+                got = eng.tree_pruned_pi(0, root, k)
+                want, changed = ft.pruned_pi(*rows, 1, 99.0, 1.0, k, n <= tau)
+                assert changed == (k > 0) and bits_equal(got, want), (N, u, n, k)
+            want2, _ = ft.pruned_pi(*rows, 1, 99.0, 1.0, 2.0, n <= tau)
+            assert want2[u] == 0.0 and abs(float(want2.astype(np.float64).sum()) - 1.0) < 1e-6
+        # the forced pick, and the PUCT arg-max with the setting off
+        score, _, scale = ft.action_scores(rows[0], rows[1], rows[2], 1, 99.0, 1.0)
+        assert scale == 10.0
+        best = int(np.argmax(score))
+        assert best == at[4]
+        assert list(np.flatnonzero(ft.under_forced(2.0, rows[0], rows[2], 99.0))) == [u]
+        for k, want_pick, counted in ((2.0, u, 1), (0.0, best, 0)):
+            eng.set_forced_playouts(k)
+            root, rows = set_rows(eng, N, at, 98.0, tau + 1)
+            before = eng.forced_counts()
+            leaf = eng.select_leaf(0, root)
+            pick = np.flatnonzero(eng.node_children(0, root) == leaf)
+            assert list(pick) == [want_pick], (N, u, k, pick)
+            assert eng.forced_counts() == (before[0] + counted, before[1])
+            assert eng.node_info(0, root).N == 99.0
+        eng.set_forced_playouts(0.0)
+    eng.close()
+
+
+def test_node_view_pruned_pi():
+    env = ag.GoEnv(5)
+    nn = ag.NeuralNet(env, tower_height=1, seed=0)
+    pl = ag.MCTSPlayer(env, nn, num_readouts=16)
+    pl.initialize_game()
+    for _ in range(5):
+        pl.tree_search(8)
+    cn = pl.root.child_N
+    want, _ = ft.pruned_pi(cn, pl.root.child_W, pl.root.child_prior, 1, pl.root.N, pl.engine.cfg.c_puct, 2.0, True)
+    assert bits_equal(pl.root.pruned_pi(2.0), want)
+    assert bits_equal(pl.root.pruned_pi(0.0), ft.pi_of(cn.astype(np.float64), True))
+
+
+# ---------------------------------------------------------------- off is off
+
+def test_off_is_the_engine_that_never_made_the_call():
+    N, tower, R, games = 9, 1, 16, 4
+    out = []
+    for how in ("never", "zero", "reset", "on"):
+        eng = ag.Engine(board_size=N, tower_height=tower, games=games, num_readouts=R, seed=2,
+                        record_capacity_games=games + 8)
+        eng.init_synthetic(0)
+        eng.set_playout_cap(*CAP)
+        if how == "zero":
+            eng.set_forced_playouts(0.0, False)
+        if how in ("reset", "on"):
+            eng.set_forced_playouts(2.0, True)
+        if how == "reset":
+            eng.set_forced_playouts(0.0)
+        recs, st = play(eng, games)
+        out.append((eng.records_packed().copy(), st, eng.forced_counts(), eng.debug_counters().copy()))
+        eng.close()
+    for packed, st, fc, raw in out[1:3]:
+        assert packed.tobytes() == out[0][0].tobytes()
+        assert st == out[0][1]
+        assert fc == (0, 0) and (raw == out[0][3]).all()
+    assert out[3][0].tobytes() != out[0][0].tobytes() and out[3][2][0] > 0 and out[3][2][1] > 0
+
+
+# ---------------------------------------------------------------- refusals
+
+def test_refusals():
+    N, R = 5, 16
+
+    def refused(fn, word):
+        with pytest.raises(ag.AgzError) as e:
+            fn()
+        assert e.value.status == BAD_ARGUMENT and word in str(e.value), str(e.value)
+
+    arena = ag.Engine(board_size=N, tower_height=1, games=2, num_readouts=R, arena_mode=1)
+    refused(lambda: arena.set_forced_playouts(2.0), "arena")
+    arena.close()
+    eng = ag.Engine(board_size=N, tower_height=1, games=2, num_readouts=R, seed=1, record_capacity_games=8,
+                    resign_threshold=-2.0, resign_disable_fraction=0.0)
+    eng.init_synthetic(0)
+    for bad in (-0.5, 1024.5, float("nan"), float("inf")):
+        refused(lambda: eng.set_forced_playouts(bad), "k =")
+    assert eng.L.agz_selfplay_set_forced_playouts(eng.h, 0.0, 1) == BAD_ARGUMENT      # pruning without forcing
+    eng.set_forced_playouts(1024.0)
+    eng.set_forced_playouts(2.0, False)
+    eng.set_forced_playouts(16.0, True)
+    eng.start(2)
+    eng.set_forced_playouts(16.0, True)          # started, not stepped: no game claimed yet
+    eng.step(3)
+    refused(lambda: eng.set_forced_playouts(0.0), "still being played")
+    refused(lambda: eng.set_forced_playouts(2.0), "still being played")
+    while eng.records_count() < 2:
+        eng.step(8)
+    assert eng.forced_counts()[0] > 0            # the refused calls left (16, prune) in force
+    eng.set_forced_playouts(0.0)                 # the run is over
+    with pytest.raises(ag.AgzError):
+        eng.tree_pruned_pi(0, 0, -1.0)
+    eng.close()
+
+
+# ---------------------------------------------------------------- analysis never forces
+
+def test_analysis_is_untouched():
+    N, R = 5, 16
+    starts = tw.random_starts(N, (4, 7, 1, 9), seed=0)
+    b, i, h = tw.opos_arrays(starts)
+    res = []
+    for k in (0.0, 16.0):
+        eng = ag.Engine(board_size=N, tower_height=1, games=4, num_readouts=R, seed=5)
+        eng.init_synthetic(0)
+        if k:
+            eng.set_forced_playouts(k)
+        eng.analyze_start(b, i, h, game_id_base=7)
+        for _ in range(4000):
+            eng.step(4)
+            if eng.analyze_progress() >= len(starts):
+                break
+        res.append((eng.analyze_results(), eng.forced_counts()))
+        eng.close()
+    assert sorted(res[0][0]) == sorted(res[1][0])
+    for key in res[0][0]:
+        assert np.asarray(res[0][0][key]).tobytes() == np.asarray(res[1][0][key]).tobytes(), key
+    assert res[1][1] == (0, 0)
+
+
+# ---------------------------------------------------------------- train(..., forced_playouts=...)
+
+TRAIN = dict(N=5, TOWER=1, R=16, k=2.0, SEED=3, num_games=8, slots=4, memory=40, B=8, start_after=8)
+
+
+def host_schedule(nn0):
+    """train()'s schedule with the cap, a targets-only arena and forced playouts, composed of single calls, with the
+    weights after every training kept (the method of tests/test_gpu_playout_cap.py::host_schedule)"""
+    from test_gpu_playout_cap import arena_pis
+    from test_gpu_train_batched import _weights
+    import cap_twin as ct
+    c = TRAIN
+    num_games, slots = c["num_games"], c["slots"]
+    eng = ag.Engine(board_size=c["N"], tower_height=c["TOWER"], games=slots, num_readouts=c["R"], seed=c["SEED"],
+                    record_capacity_games=slots + 8)
+    nn0.engine.copy_weights_to(eng)
+    eng.set_playout_cap(*CAP)
+    eng.replay_set_targets_only(True)
+    eng.set_forced_playouts(c["k"], True)
+    eng.set_hold(True)
+    eng.start(num_games)
+    eng.release()
+    snaps = [_weights(eng)]
+    i, claimed, pending, ref, steps, start_step, targets = 0, 0, min(slots, num_games), [], 0, {}, 0
+    while i < num_games:
+        for g in range(claimed, claimed + pending):
+            start_step[g] = steps + 1
+        claimed += pending
+        eng.step(1)
+        steps += 1
+        n = eng.records_count()
+        for r in sorted(eng.records(), key=lambda r: r["game_id"]):
+            assert eng.replay_ingest_records(r["index"], 1) == 1
+            eng.replay_set_window(c["memory"])
+            i += 1
+            targets += int((r["pis"] != 0).any(axis=1).sum()) if r["num_moves"] else 0
+            live = eng.replay_live_positions()
+            assert live == min(c["memory"], targets)
+            loss = None
+            if live >= c["start_after"]:
+                pairs, _ = ct.sample_targets(c["SEED"], i, c["B"], arena_pis(eng), window=live)
+                g = np.array([a for a, _ in pairs], np.int64)
+                q = np.array([b for _, b in pairs], np.int32)
+                f, pi, z = eng.replay_batch(g, q)
+                loss = float(eng.train_step(f, pi, z, eta=np.float32(0.02), rho=0.9)[0])
+                snaps.append(_weights(eng))
+            ref.append(dict(i=i, record=r, loss=loss, step=steps, live=live))
+        eng.records_clear()
+        eng.release()
+        pending = min(n, num_games - claimed)
+    counts = eng.forced_counts()
+    eng.close()
+    return ref, snaps, start_step, counts
+
+
+def test_train_with_forced_playouts_plays_the_twins_games():
+    from test_gpu_starts import weight_mismatches
+    c = TRAIN
+    N, TOWER, R, SEED, k = c["N"], c["TOWER"], c["R"], c["SEED"], c["k"]
+    env = ag.GoEnv(N)
+    nn0 = ag.NeuralNet(env, tower_height=TOWER, seed=1)
+    ref, snaps, start_step, counts = host_schedule(nn0)
+    assert sum(g["loss"] is not None for g in ref) >= 4
+    chk = ag.Engine(board_size=N, tower_height=TOWER, games=1, num_readouts=8, max_nodes_per_game=16)
+    cb = GpuNetForOracle(chk).cb
+    loaded = [None]
+    switched = 0
+    twins = []
+    for gme in ref:
+        rec = gme["record"]
+        gid = int(rec["game_id"])
+        rnd = [0]
+
+        def on_round():
+            step = start_step[gid] + rnd[0]
+            rnd[0] += 1
+            t = sum(1 for h in ref if h["step"] < step and h["loss"] is not None)
+            if loaded[0] != t:
+                for (layer, kind), w in snaps[t].items():
+                    chk.set_weights(layer, kind, w)
+                loaded[0] = t
+
+        o = ft.twin_selfplay_forced(N, cb, R, CAP[0], CAP[1], k, True, SEED, gid, None, -0.9, 0.05, on_round=on_round)
+        assert_game_equal(rec, o, gid)
+        twins.append(o)
+        first = sum(1 for h in ref if h["step"] < start_step[gid] and h["loss"] is not None)
+        switched += loaded[0] != first
+    assert switched > 0, "some game was in flight across a training step"
+    nforced, nrows = sum(o["forced_sel"] for o in twins), sum(int(o["pruned_rows"].sum()) for o in twins)
+    assert nforced >= 3 and nrows >= 3 and counts == (nforced, nrows)
+
+    nn, log = ag.train(env, num_games=c["num_games"], memory_size=c["memory"], batch_size=c["B"], readouts=R, model=nn0,
+                       start_training_after=c["start_after"], slots=c["slots"], seed=SEED, callback=None, return_log=True,
+                       epochs=1, playout_cap=CAP, forced_playouts=k)
+    assert len(log) == len(ref) == c["num_games"]
+    for x, y in zip(log, ref):
+        a, b = x["record"], y["record"]
+        assert a["game_id"] == b["game_id"] and a["num_moves"] == b["num_moves"] and a["result"] == b["result"]
+        assert (a["moves"] == b["moves"]).all() and bits_equal(a["pis"], b["pis"]) and bits_equal(a["qs"], b["qs"])
+        assert x["loss"] == y["loss"] and x["live"] == y["live"]
+    bad = weight_mismatches(nn.engine, snaps[-1])
+    assert not bad, bad
+    chk.close()
+
+
+def test_selfplay_takes_the_keywords():
+    N, R, k = 5, 16, 2.0
+    env = ag.GoEnv(N)
+    nn = ag.NeuralNet(env, tower_height=1, seed=0)
+    kw = dict(games=3, seed=2, game_id_base=0, playout_cap=CAP, resign_threshold=-2.0, resign_disable_fraction=0.0)
+    cb = GpuNetForOracle(nn.engine).cb
+    for prune in (True, False):
+        players = ag.selfplay(env, nn, R, forced_playouts=k, prune_targets=prune, **kw)
+        for gid, pl in enumerate(players):
+            o = ft.twin_selfplay_forced(N, cb, R, CAP[0], CAP[1], k, prune, 2, gid, None, -2.0, 0.0)
+            assert [ag.to_flat(m, env) for m in pl.moves] == list(o["moves"]) and pl.result == o["result"]
+            assert pl.full_search == list(o["full"])
+            assert bits_equal(np.stack(pl.searches_pi), o["pis"])
