@@ -158,6 +158,9 @@ def load():
         "agz_selfplay_set_forced_playouts": (i32, [E, C.c_double, i32]),
         "agz_selfplay_forced_counts": (i32, [E, P(i64)]),
         "agz_tree_pruned_pi": (i32, [E, i32, i32, C.c_double, f32p]),
+        "agz_selfplay_set_gumbel": (i32, [E, i32, C.c_double, C.c_double]),
+        "agz_selfplay_gumbel_counts": (i32, [E, P(i64)]),
+        "agz_tree_gumbel_pi": (i32, [E, i32, i32, C.c_double, C.c_double, f32p]),
         "agz_analyze_start": (i32, [E, i8p, P(PositionInfo), i8p, i64, u64]),
         "agz_review_start": (i32, [E, P(C.c_int16), P(i64), i8p, P(PositionInfo), i8p, i64, u64]),
         "agz_analyze_progress": (i32, [E, P(i64)]),

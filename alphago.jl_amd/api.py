@@ -350,6 +350,12 @@ class NodeView:
         forced visits the search did not agree with are left out; squashed iff the node's n <= tau"""
         return self._p.engine.tree_pruned_pi(0, self.id, k)
 
+    def gumbel_pi(self, c_visit=50.0, c_scale=1.0):
+        """the improved-policy row of this node (ours, Engine.set_gumbel): softmax over its legal actions of
+        log(prior) + sigma(q), sigma = (c_visit + max child_N) * c_scale * (0.5 + 0.5 q); an unvisited child's q is the
+        node's own network value"""
+        return self._p.engine.tree_gumbel_pi(0, self.id, c_visit, c_scale)
+
     # ---- analysis lines (ours; the commented-out most_visited_path / mvp_gg / describe of mcts.jl:255-327 are the
     # definition, DESIGN.md §5f): one agz_tree_lines call each, the walk runs on the device
     def lines(self, k=4, depth=16, min_visits=1):
@@ -666,7 +672,8 @@ def seed(s):
 
 
 def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="f32", game_id_base=None, symmetry=None,
-             starts=None, playout_cap=None, forced_playouts=None, prune_targets=True, **cfg):
+             starts=None, playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
+             gumbel_c_scale=1.0, **cfg):
     """selfplay(env, nn, num_ro) (src/selfplay.jl:1-45) -> the finished game's player (SelfPlayPlayer), exactly the
     call train() makes (train.jl:57).  `games=G` (ours) plays G games concurrently on the device and returns a list of
     G such players ordered by game id.  Game ids continue from the previous call (module stream, `seed()`), unless
@@ -679,7 +686,12 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     otherwise fast (no noise, r readouts, an all-zero searches_pi row); the player's `full_search` tells which.
     forced_playouts (ours): k -- forced playouts (Engine.set_forced_playouts; KataGo plays 2): in a full search a visited
     root child below sqrt(k P sum(N)) visits is searched first; prune_targets (default on with k) records the searches_pi
-    row with the forced visits the search did not agree with left out."""
+    row with the forced visits the search did not agree with left out.
+    gumbel (ours): m -- the Gumbel root search (Engine.set_gumbel) in the full searches: up to m root candidates by
+    Gumbel-top-k, Sequential Halving, the searches_pi row is softmax(log prior + sigma(q)); gumbel_c_visit and
+    gumbel_c_scale are sigma's constants.  It composes with playout_cap, starts and symmetry, not with forced_playouts."""
+    if gumbel and forced_playouts:
+        raise ValueError("gumbel and forced_playouts are two rules for the same decision: ask for one")
     single = games is None
     games = 1 if single else int(games)
     if seed is None:
@@ -702,6 +714,8 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
         eng.set_playout_cap(*playout_cap)
     if forced_playouts:
         eng.set_forced_playouts(forced_playouts, prune_targets)
+    if gumbel:
+        eng.set_gumbel(gumbel, gumbel_c_visit, gumbel_c_scale)
     eng.start(games)
     while eng.records_count() < games:
         eng.step(16)
@@ -1059,7 +1073,8 @@ def _minibatch_cuts(n):
 def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp_freq=1000, readouts=800,
           tower_height=19, model=None, start_training_after=50000, slots=None, seed=0, game_id_base=0, symmetry=None,
           augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, starts=None,
-          playout_cap=None, forced_playouts=None, prune_targets=True, **cfg):
+          playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
+          gumbel_c_scale=1.0, **cfg):
     """train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model,
     start_training_after) (src/train.jl:38-92) with `slots` games in flight on the device.  One engine
     plays, keeps the replay arena and trains; per step: agz_selfplay_step(1), one read of how many games finished, and
@@ -1077,7 +1092,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
     starts[gid % len(starts)], and the replay arena rebuilds its training positions from there; as in selfplay),
     playout_cap ((r, p): playout cap randomization as in selfplay, with a targets-only arena -- memory_size and
     start_training_after then count target entries, the plies of full searches, and only those are sampled),
-    forced_playouts (k) and prune_targets (forced playouts and policy target pruning in the full searches, as in selfplay).
+    forced_playouts (k) and prune_targets (forced playouts and policy target pruning in the full searches, as in selfplay),
+    gumbel (m), gumbel_c_visit and gumbel_c_scale (the Gumbel root search in the full searches, as in selfplay).
     Returns the trained NeuralNet (model itself when given)."""
     import time
     import torch
@@ -1086,6 +1102,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
     num_games, batch_size, epochs = int(num_games), int(batch_size), int(epochs)
     if num_games < 1 or batch_size < 2 or epochs < 1 or int(ckp_freq) < 1:
         raise ValueError("num_games, epochs, ckp_freq >= 1 and batch_size >= 2 (BatchNorm needs two positions)")
+    if gumbel and forced_playouts:
+        raise ValueError("gumbel and forced_playouts are two rules for the same decision: ask for one")
     cur_nn = NeuralNet(env, tower_height=tower_height) if model is None else model       # train.jl:43
     slots = min(num_games, 1024) if slots is None else int(slots)
     if slots < 1:
@@ -1112,6 +1130,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
             eng.replay_set_targets_only(playout_cap[0] > 0)
         if forced_playouts:
             eng.set_forced_playouts(forced_playouts, prune_targets)
+        if gumbel:
+            eng.set_gumbel(gumbel, gumbel_c_visit, gumbel_c_scale)
         eng.set_hold(True)
         eng.start(num_games)
         eng.release()

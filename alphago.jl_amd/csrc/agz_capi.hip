@@ -335,6 +335,18 @@ agz_status agz_selfplay_forced_counts(agz_engine* e, int64_t out[2]) {
 agz_status agz_tree_pruned_pi(agz_engine* e, int32_t g, int32_t node, double k, float* out) {
   return guard(e, [&](agz::Engine& E) { E.tree_pruned_pi(g, node, k, out); });
 }
+agz_status agz_selfplay_set_gumbel(agz_engine* e, int32_t m, double c_visit, double c_scale) {
+  return guard(e, [&](agz::Engine& E) { E.set_gumbel(m, c_visit, c_scale); });
+}
+agz_status agz_selfplay_gumbel_counts(agz_engine* e, int64_t out[2]) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+    E.gumbel_counts(out);
+  });
+}
+agz_status agz_tree_gumbel_pi(agz_engine* e, int32_t g, int32_t node, double c_visit, double c_scale, float* out) {
+  return guard(e, [&](agz::Engine& E) { E.tree_gumbel_pi(g, node, c_visit, c_scale, out); });
+}
 agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on) {
   return guard(e, [&](agz::Engine& E) { E.replay_set_targets_only(on != 0); });
 }

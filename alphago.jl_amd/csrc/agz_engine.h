@@ -50,6 +50,10 @@ class Engine {
   void set_forced_playouts(double k, int prune);
   void forced_counts(int64_t out[2]);
   void tree_pruned_pi(int g, int node, double k, float* out);
+  // Gumbel root search of self-play (agz_selfplay_set_gumbel): m = 0 is off
+  void set_gumbel(int m, double c_visit, double c_scale);
+  void gumbel_counts(int64_t out[2]);
+  void tree_gumbel_pi(int g, int node, double c_visit, double c_scale, float* out);
   int64_t analyze_progress();
   void analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior);
   // analysis lines (agz_analyze_set_lines / agz_analyze_lines / agz_tree_lines): top-K candidates with their PVs

@@ -304,6 +304,16 @@ __global__ __launch_bounds__(kWave) void k_tree_pruned_pi(View V, int g, int nod
   pruned_pi(w, V, S, ni, *slotN(V, g, node), V.meta[ni].n <= V.tau, out);
 }
 
+// agz_tree_gumbel_pi: gumbel_pi of one node of single tree g under the constants given, whatever the engine's setting
+__global__ __launch_bounds__(kWave) void k_tree_gumbel_pi(View V, int g, int node, double c_visit, double c_scale,
+                                                           float* out) {
+  AGZ_SCRATCH(S)
+  HipWave w;
+  V.gumbel_cvisit = c_visit;
+  V.gumbel_cscale = c_scale;
+  gumbel_pi(w, V, S, node_index(V, g, node), out);
+}
+
 __global__ __launch_bounds__(kWave) void k_go_play(View V, const int8_t* boards, const int8_t* tp, const int32_t* ko,
                                                     const int32_t* moves, int B, int8_t* bo, int32_t* ko_o,
                                                     int32_t* nc, int32_t* st) {
@@ -715,7 +725,7 @@ void Engine::start(int64_t total_games) {
   abandoned_ = 0;
   stepped_ = false;
   if (hold_rel_.p) hold_rel_.zero(stream_);     // with the hold on, the fresh slots wait for a first release
-  AGZ_HIP(hipMemsetAsync(V_.counters, 0, sizeof(unsigned long long) * CT_COUNT, stream_));
+  AGZ_HIP(hipMemsetAsync(V_.counters, 0, sizeof(unsigned long long) * kCounterSlots, stream_));
   AGZ_HIP(hipMemsetAsync(V_.ar_hdr, 0, sizeof(int32_t) * 5 * (V_.games / 2 + 1), stream_));
   std::vector<GameState> gs(V_.games);
   std::memset(gs.data(), 0, sizeof(GameState) * gs.size());
@@ -803,6 +813,7 @@ void Engine::set_forced_playouts(double k, int prune) {
   AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "forced playouts: an arena_mode engine plays evaluate() games only");
   AGZ_REQUIRE(k >= 0.0 && k <= 1024.0, AGZ_BAD_ARGUMENT, "forced playouts: k = %g, not in 0 (off) .. 1024", k);   // NaN fails
   AGZ_REQUIRE(prune == 0 || k > 0.0, AGZ_BAD_ARGUMENT, "forced playouts: pruning needs k > 0");
+  AGZ_REQUIRE(!(k > 0.0) || V_.gumbel_m == 0, AGZ_BAD_ARGUMENT, "forced playouts: the Gumbel root search is on (m = %d)", V_.gumbel_m);
   // a search forced from its first descent and a target pruned by the same k: the setting changes only between games
   if (!V_.analysis && stepped_) {
     agz_stats st;
@@ -813,6 +824,49 @@ void Engine::set_forced_playouts(double k, int prune) {
   AGZ_HIP(hipStreamSynchronize(stream_));
   V_.forced_k = k;
   V_.forced_prune = prune != 0;
+}
+
+// ---- Gumbel root search (agz_selfplay_set_gumbel)
+
+void Engine::set_gumbel(int m, double c_visit, double c_scale) {
+  AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "gumbel: an arena_mode engine plays evaluate() games only");
+  AGZ_REQUIRE(m == 0 || (m >= 2 && m <= kGumbelMax), AGZ_BAD_ARGUMENT, "gumbel: m = %d, not 0 (off) or in 2..%d", m,
+              kGumbelMax);
+  AGZ_REQUIRE(c_visit >= 0.0 && c_visit <= 1.0e9, AGZ_BAD_ARGUMENT, "gumbel: c_visit = %g, not in 0 .. 1e9", c_visit);   // NaN fails
+  AGZ_REQUIRE(c_scale > 0.0 && c_scale <= 1.0e9, AGZ_BAD_ARGUMENT, "gumbel: c_scale = %g, not in (0, 1e9]", c_scale);
+  AGZ_REQUIRE(m == 0 || !(V_.forced_k > 0.0), AGZ_BAD_ARGUMENT, "gumbel: forced playouts are on (k = %g)", V_.forced_k);
+  // a search keeps one rule from its first descent to its move: the setting changes only between games
+  if (!V_.analysis && stepped_) {
+    agz_stats st;
+    stats(&st);
+    AGZ_REQUIRE(st.live_games == 0, AGZ_BAD_ARGUMENT, "gumbel: %lld games of the current run are still being played",
+                (long long)st.live_games);
+  }
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  V_.gumbel_m = m;
+  V_.gumbel_cvisit = m > 0 ? c_visit : 0.0;
+  V_.gumbel_cscale = m > 0 ? c_scale : 0.0;
+}
+
+void Engine::gumbel_counts(int64_t out[2]) {
+  unsigned long long c[2];
+  static_assert(CT_GUMBEL_HALVED == CT_GUMBEL_BEGUN + 1, "the two counters are read as one pair");
+  AGZ_HIP(hipMemcpyAsync(c, V_.counters + CT_GUMBEL_BEGUN, sizeof(c), hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  out[0] = (int64_t)c[0];
+  out[1] = (int64_t)c[1];
+}
+
+void Engine::tree_gumbel_pi(int g, int node, double c_visit, double c_scale, float* out) {
+  check_node(g, node);
+  AGZ_REQUIRE(c_visit >= 0.0 && c_visit <= 1.0e9, AGZ_BAD_ARGUMENT, "gumbel pi: c_visit = %g, not in 0 .. 1e9", c_visit);
+  AGZ_REQUIRE(c_scale > 0.0 && c_scale <= 1.0e9, AGZ_BAD_ARGUMENT, "gumbel pi: c_scale = %g, not in (0, 1e9]", c_scale);
+  AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+  s_f32a_.ensure(V_.A);
+  hipLaunchKernelGGL(k_tree_gumbel_pi, dim3(1), dim3(kWave), 0, stream_, V_, g, node, c_visit, c_scale, s_f32a_.p);
+  AGZ_HIP(hipGetLastError());
+  AGZ_HIP(hipMemcpyAsync(out, s_f32a_.p, sizeof(float) * V_.A, hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
 }
 
 void Engine::forced_counts(int64_t out[2]) {

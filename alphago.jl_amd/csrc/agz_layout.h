@@ -71,6 +71,9 @@ inline void fill_dims(View& V, const agz_config& c) {
   V.cap_full_prob = 1.0;
   V.forced_k = 0.0;              // agz_selfplay_set_forced_playouts
   V.forced_prune = 0;
+  V.gumbel_m = 0;                // agz_selfplay_set_gumbel
+  V.gumbel_cvisit = 0.0;
+  V.gumbel_cscale = 0.0;
 }
 
 // visits every buffer of the View: f(pointer-reference, element count)
@@ -102,13 +105,14 @@ inline void for_each_buffer(View& V, F&& f) {
   f(V.fin_moves, (size_t)V.fin_cap * mgl);
   f(V.fin_pi, (size_t)V.fin_cap * mgl * V.A);
   f(V.fin_q, (size_t)V.fin_cap * mgl);
-  f(V.counters, (size_t)CT_COUNT);
+  f(V.counters, (size_t)kCounterSlots);
   f(V.batch_count, (size_t)2);
   f(V.ar_hdr, (size_t)5 * (V.games / 2 + 1));        // 4 header words + 1 abort word per pair (agz_search.h)
   f(V.leaf_sym, leaves);
   f(V.eval_ord, (size_t)V.games);
   f(V.an_ctr, (size_t)2);
   f(V.an_slot, (size_t)V.games);
+  f(V.gumbel, (size_t)V.games);
 }
 
 }  // namespace agz

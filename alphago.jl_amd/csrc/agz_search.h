@@ -518,9 +518,13 @@ AGZ_FN bool forced_search(const View& V, const GameState& G, int root_n);
 // that depends only on the node id -- meta, N / W / P / child-id rows, the legal words -- is requested at once, the
 // node's own N comes along from the parent's row of the level above, and the chosen child's id and N come out of the
 // registers by shuffle: one round trip per level.  Same arithmetic, same tie-break draws: the tree is bit-identical.
-// Forced: the descent starts at the root of a search under the forced rule; its depth 0 level alone applies it.
-template <int R, bool Forced, class W>
-AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer) {
+// Mode, the root level (depth 0) of the descent alone: kSelForced -- the descent starts at the root of a search under the
+// forced rule; kSelGiven -- the caller chose the root action (root_pick, the Gumbel root search); the pass-first rule
+// keeps its precedence, nothing is scored and no tie draw is made there.
+constexpr int kSelPlain = 0, kSelForced = 1, kSelGiven = 2;
+template <int R, int Mode, class W>
+AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer, int root_pick) {
+  constexpr bool Forced = Mode == kSelForced;
   GameState& G = V.gs[g];
   const int A = V.A, AP = V.AP, pass = V.P;
   const uint32_t move_key = (uint32_t)V.meta[node_index(V, g, G.root)].n;
@@ -559,8 +563,12 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
       return x;
     };
     int pick;
+    bool given = false;
+    if constexpr (Mode == kSelGiven) given = depth == 0;
     if (m.last_move == pass && row_f(cn, pass) == 0.0f) {
       pick = pass;    // HACK of mcts.jl:119-126: look at the double pass first
+    } else if (given) {
+      pick = root_pick;
     } else {
       const double scale = puct_scale(V, n_new);
       const float tp = (float)m.to_play;
@@ -627,22 +635,30 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
 // select_leaf from `from`; the visited nodes are left in S.path[0..len).  Returns the leaf.
 template <class W>
 AGZ_FN int select_leaf(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer = false,
-                       bool forced = false) {
+                       bool forced = false, int root_pick = -1) {
   if constexpr (W::kRegisterRows) {
-    if (forced) {
+    if (root_pick >= 0) {
       switch ((V.AP + 63) >> 6) {
-        case 1: return select_leaf_rows<1, true>(w, V, S, g, from, plen_out, defer);
-        case 2: return select_leaf_rows<2, true>(w, V, S, g, from, plen_out, defer);
-        case 3: return select_leaf_rows<3, true>(w, V, S, g, from, plen_out, defer);
-        case 6: return select_leaf_rows<6, true>(w, V, S, g, from, plen_out, defer);
+        case 1: return select_leaf_rows<1, kSelGiven>(w, V, S, g, from, plen_out, defer, root_pick);
+        case 2: return select_leaf_rows<2, kSelGiven>(w, V, S, g, from, plen_out, defer, root_pick);
+        case 3: return select_leaf_rows<3, kSelGiven>(w, V, S, g, from, plen_out, defer, root_pick);
+        case 6: return select_leaf_rows<6, kSelGiven>(w, V, S, g, from, plen_out, defer, root_pick);
+        default: break;
+      }
+    } else if (forced) {
+      switch ((V.AP + 63) >> 6) {
+        case 1: return select_leaf_rows<1, kSelForced>(w, V, S, g, from, plen_out, defer, -1);
+        case 2: return select_leaf_rows<2, kSelForced>(w, V, S, g, from, plen_out, defer, -1);
+        case 3: return select_leaf_rows<3, kSelForced>(w, V, S, g, from, plen_out, defer, -1);
+        case 6: return select_leaf_rows<6, kSelForced>(w, V, S, g, from, plen_out, defer, -1);
         default: break;
       }
     } else {
       switch ((V.AP + 63) >> 6) {
-        case 1: return select_leaf_rows<1, false>(w, V, S, g, from, plen_out, defer);
-        case 2: return select_leaf_rows<2, false>(w, V, S, g, from, plen_out, defer);     // 9x9
-        case 3: return select_leaf_rows<3, false>(w, V, S, g, from, plen_out, defer);     // 13x13
-        case 6: return select_leaf_rows<6, false>(w, V, S, g, from, plen_out, defer);     // 19x19
+        case 1: return select_leaf_rows<1, kSelPlain>(w, V, S, g, from, plen_out, defer, -1);
+        case 2: return select_leaf_rows<2, kSelPlain>(w, V, S, g, from, plen_out, defer, -1);     // 9x9
+        case 3: return select_leaf_rows<3, kSelPlain>(w, V, S, g, from, plen_out, defer, -1);     // 13x13
+        case 6: return select_leaf_rows<6, kSelPlain>(w, V, S, g, from, plen_out, defer, -1);     // 19x19
         default: break;
       }
     }
@@ -666,6 +682,8 @@ AGZ_FN int select_leaf(W& w, const View& V, Scratch& S, int g, int from, int* pl
     int pick;
     if (m.last_move == pass && V.childN[ni * V.AP + pass] == 0.0f) {
       pick = pass;    // HACK of mcts.jl:119-126: look at the double pass first
+    } else if (root_pick >= 0 && depth == 0) {
+      pick = root_pick;   // the Gumbel root search chose the root action
     } else {
       const double scale = puct_scale(V, n_new);
       const float tp = (float)m.to_play;
@@ -1008,6 +1026,7 @@ AGZ_FN void game_start(W& w, const View& V, Scratch& S, int g, uint64_t game_id,
       G.game_id = game_id;
       game_resign_coin(V, G, game_id);
       G.short_first = 0;
+      V.gumbel[g].n = -1;
     }
     w.sync();
     w.count(&V.counters[CT_STARTED], 1);
@@ -1024,6 +1043,7 @@ AGZ_FN void game_start(W& w, const View& V, Scratch& S, int g, uint64_t game_id,
     G.short_first = 0; G.short_searches = 0;
     G.phase = G_INIT;
     V.eval_ord[g] = 0;
+    V.gumbel[g].n = -1;
   }
   w.sync();
   const int id = pool_alloc(w, V, S, g);
@@ -1187,6 +1207,223 @@ AGZ_FN bool forced_search(const View& V, const GameState& G, int root_n) {
   return G.short_first || playout_cap_full(V, G.game_id, root_n);
 }
 
+
+// ------------------------------------------------------------------ Gumbel root search
+// "Policy improvement by planning with Gumbel" (Danihelka et al., ICLR 2022) at the root of a full self-play search
+// (View::gumbel_m = m > 0).  THE DEFINITIONS, for the root with rows N, W, P, tp = to_play, position.n =
+// n_root, and a legal action a:
+//   logit(a) = agz_log((double)P[a]) when P[a] > 0, else -1.0e30
+//   g(a)     = -agz_log(-agz_log(agz_u01(agz_draw_u64(seed, game_id, n_root, AGZ_SITE_GUMBEL, a))))
+//   qs(a)    = the f32 (W[a] / (1.0f + N[a])) * tp of action_score.  incorporate initialises every child's W to the
+//              parent's value, so an unvisited child's qs is the root's own network value: the "completed Q"
+//   sigma(a) = ((c_visit + (double)maxN) * c_scale) * (0.5 + 0.5 * (double)qs(a)),  maxN = max of N[.] over all A
+//              actions; f64, in this order
+//   s(a)     = (g(a) + logit(a)) + sigma(a)
+// BEGIN (the first select phase with the root expanded and the slot's state not this root's): n = G.target - G.rootN;
+// the survivors are the m_0 = min(m, #legal) legal actions with the largest g + logit, ties to the lower action, stored
+// in that order; P = the smallest integer >= 1 with 2^P >= m_0.  PHASES: phase p with m_p survivors ends when G.rootN
+// reaches its start plus Q_p = max(1, floor(n / (P m_p))) m_p, cut to what remains of n; reverted duplicates do not
+// count.  HALVE (start of a select phase, phase over, budget left): order the survivors by s descending, ties to the
+// lower action, keep the first m_{p+1} = max(2, floor(m_p / 2)) (1 if m_p = 1).  ROOT LEVEL of a descent: after the
+// pass-first rule, the survivor with the smallest child_N, visits in flight included, the first in stored order on ties;
+// no score, no tie draw.  Below the root: PUCT, unchanged.  A select phase stops collecting at the phase end.
+// MOVE: the survivor with the largest s, ties to the lower action.  TARGET: gumbel_pi.  No Dirichlet noise.
+constexpr double kGumbelNoLogit = -1.0e30;
+
+// Is the search of game slot g's root a Gumbel search?  forced_search's test: self-play full searches only (every search
+// with the playout cap off); fast searches, the arena, analysis, review and single trees (G_MANUAL) never.
+AGZ_FN bool gumbel_search(const View& V, const GameState& G, int root_n) {
+  if (V.gumbel_m <= 0 || V.arena || V.analysis || G.phase == G_MANUAL) return false;
+  return G.short_first || playout_cap_full(V, G.game_id, root_n);
+}
+
+AGZ_FN double gumbel_logit(float p) { return p > 0.0f ? agz_log((double)p) : kGumbelNoLogit; }
+
+AGZ_FN double gumbel_g(const View& V, uint64_t game_id, int n_root, int a) {
+  return -agz_log(-agz_log(agz_u01(agz_draw_u64(V.seed, game_id, (uint32_t)n_root, AGZ_SITE_GUMBEL, (uint64_t)a))));
+}
+
+AGZ_FN double gumbel_sigma(const View& V, long ni, int a, float tp, float maxN) {
+  const float denom = 1.0f + V.childN[ni * V.AP + a];
+  const float q = V.childW[ni * V.AP + a] / denom;
+  const float qs = q * tp;
+  return ((V.gumbel_cvisit + (double)maxN) * V.gumbel_cscale) * (0.5 + 0.5 * (double)qs);
+}
+
+template <class W>
+AGZ_FN float row_max_N(W& w, const View& V, long ni) {
+  float mx = 0.f;
+  w.for_each(V.A, [&](int a) { const float c = V.childN[ni * V.AP + a]; mx = c > mx ? c : mx; });
+  return w.reduce_max_f(mx);
+}
+
+AGZ_FN int gumbel_quota(int n, int P, int m) {
+  const int per = n / (P * m);
+  return (per < 1 ? 1 : per) * m;
+}
+
+// the end of a phase of m survivors that starts now
+AGZ_FN float gumbel_phase_end(const GameState& G, int n, int P, int m) {
+  const int left = (int)(G.target - G.rootN), q = gumbel_quota(n, P, m);
+  return G.rootN + (float)(q < left ? q : left);
+}
+
+template <class W>
+AGZ_FN void gumbel_begin(W& w, const View& V, Scratch& S, int g) {
+  GameState& G = V.gs[g];
+  GumbelState& T = V.gumbel[g];
+  const long ri = node_index(V, g, G.root);
+  const int A = V.A, n_root = V.meta[ri].n;
+  int nlegal = 0;
+  w.for_each(V.AP, [&](int a) {
+    const bool lg = a < A && legal_bit(V, ri, a);
+    S.flag[a] = lg;                                        // legal and not yet taken
+    S.dbuf[a] = lg ? gumbel_g(V, G.game_id, n_root, a) + gumbel_logit(V.childP[ri * V.AP + a]) : 0.0;
+    if (lg) nlegal++;
+  });
+  nlegal = w.reduce_sum(nlegal);
+  w.sync();
+  int m0 = V.gumbel_m < nlegal ? V.gumbel_m : nlegal;
+  const double ninf = -__builtin_huge_val();
+  for (int k = 0; k < m0; ++k) {
+    double best = ninf;
+    w.for_each(A, [&](int a) { if (S.flag[a] && S.dbuf[a] > best) best = S.dbuf[a]; });
+    best = w.reduce_max(best);
+    int idx = kIntMax;
+    w.for_each(A, [&](int a) { if (S.flag[a] && S.dbuf[a] == best && a < idx) idx = a; });
+    idx = w.reduce_min(idx);
+    w.sync();
+    if (idx >= A) { m0 = k; break; }                       // (a NaN prior: nothing compares equal to the maximum)
+    if (w.leader()) { S.flag[idx] = 0; T.act[k] = (int16_t)idx; }
+    w.sync();
+  }
+  if (m0 < 1) {                                            // (every prior NaN: search the pass alone)
+    if (w.leader()) T.act[0] = (int16_t)V.P;
+    m0 = 1;
+  }
+  int P = 1;
+  while ((1 << P) < m0) ++P;
+  const int n = (int)(G.target - G.rootN);
+  if (w.leader()) {
+    T.n = n_root; T.cnt = m0; T.budget = n; T.P = P;
+    T.end = gumbel_phase_end(G, n, P, m0);
+  }
+  w.sync();
+  w.count(&V.counters[CT_GUMBEL_BEGUN], 1);
+}
+
+// s(a) of survivor i into S.dbuf[i], i < cnt; returns the largest
+template <class W>
+AGZ_FN double gumbel_scores(W& w, const View& V, Scratch& S, int g) {
+  const GameState& G = V.gs[g];
+  const GumbelState& T = V.gumbel[g];
+  const long ri = node_index(V, g, G.root);
+  const int n_root = V.meta[ri].n;
+  const float tp = (float)V.meta[ri].to_play;
+  const float maxN = row_max_N(w, V, ri);
+  double best = -__builtin_huge_val();
+  w.sync();
+  w.for_each(T.cnt, [&](int i) {
+    const int a = T.act[i];
+    const double s = (gumbel_g(V, G.game_id, n_root, a) + gumbel_logit(V.childP[ri * V.AP + a])) +
+                     gumbel_sigma(V, ri, a, tp, maxN);
+    S.dbuf[i] = s;
+    if (s > best) best = s;
+  });
+  best = w.reduce_max(best);
+  w.sync();
+  return best;
+}
+
+template <class W>
+AGZ_FN void gumbel_halve(W& w, const View& V, Scratch& S, int g) {
+  GameState& G = V.gs[g];
+  GumbelState& T = V.gumbel[g];
+  const int cnt = T.cnt, half = cnt / 2;
+  const int keep = cnt == 1 ? 1 : (half > 2 ? half : 2);
+  gumbel_scores(w, V, S, g);
+  w.for_each(cnt, [&](int i) {                             // rank by s descending, the lower action first on ties
+    const double s = S.dbuf[i];
+    const int a = T.act[i];
+    int rank = 0;
+    for (int j = 0; j < cnt; ++j) {
+      const double sj = S.dbuf[j];
+      const int aj = T.act[j];
+      if (sj > s || (sj == s && aj < a)) rank++;
+    }
+    S.label[rank] = a;
+  });
+  w.sync();
+  w.for_each(keep, [&](int i) { T.act[i] = (int16_t)S.label[i]; });
+  if (w.leader()) { T.cnt = keep; T.end = gumbel_phase_end(G, T.budget, T.P, keep); }
+  w.sync();
+  w.count(&V.counters[CT_GUMBEL_HALVED], 1);
+}
+
+// The start of a select phase of a Gumbel search: begin, or halve, when due.  Returns whether the slot's state is set
+// up for this root (an unexpanded root has none yet: its descents end at the root).
+template <class W>
+AGZ_FN bool gumbel_select_start(W& w, const View& V, Scratch& S, int g) {
+  const GameState& G = V.gs[g];
+  const long ri = node_index(V, g, G.root);
+  if (!(V.meta[ri].flags & NF_EXPANDED)) return false;
+  const GumbelState& T = V.gumbel[g];
+  if (T.n != V.meta[ri].n) gumbel_begin(w, V, S, g);
+  else if (!(G.rootN < T.end) && T.end < G.target) gumbel_halve(w, V, S, g);
+  return true;
+}
+
+// the root action of the next descent
+AGZ_FN int gumbel_root_pick(const View& V, int g) {
+  const GumbelState& T = V.gumbel[g];
+  const float* cN = V.childN + node_index(V, g, V.gs[g].root) * V.AP;
+  int pick = T.act[0];
+  float best = cN[pick];
+  for (int i = 1; i < T.cnt; ++i) {
+    const int a = T.act[i];
+    const float c = cN[a];
+    if (c < best) { best = c; pick = a; }
+  }
+  return pick;
+}
+
+// the move of a Gumbel search: the survivor with the largest s, the lower action on ties
+template <class W>
+AGZ_FN int gumbel_move(W& w, const View& V, Scratch& S, int g) {
+  const GumbelState& T = V.gumbel[g];
+  const double best = gumbel_scores(w, V, S, g);
+  int idx = kIntMax;
+  w.for_each(T.cnt, [&](int i) { const int a = T.act[i]; if (S.dbuf[i] == best && a < idx) idx = a; });
+  idx = w.reduce_min(idx);
+  w.sync();
+  return idx < V.A ? idx : T.act[0];                       // (NaN scores: nothing compares equal to the maximum)
+}
+
+// The improved policy of node row ri into out[A] under V.gumbel_cvisit / V.gumbel_cscale: over legal a,
+// x(a) = logit(a) + sigma(a), out[a] = (float)(agz_exp(x(a) - max x) / sum), the f64 sum over S.dbuf in ascending index
+// order; illegal actions get 0; no squash.
+template <class W>
+AGZ_FN void gumbel_pi(W& w, const View& V, Scratch& S, long ri, float* out) {
+  const int A = V.A;
+  const float tp = (float)V.meta[ri].to_play;
+  const float maxN = row_max_N(w, V, ri);
+  double mx = -__builtin_huge_val();
+  w.sync();
+  w.for_each(A, [&](int a) {
+    if (!legal_bit(V, ri, a)) return;
+    const double x = gumbel_logit(V.childP[ri * V.AP + a]) + gumbel_sigma(V, ri, a, tp, maxN);
+    S.dbuf[a] = x;
+    if (x > mx) mx = x;
+  });
+  mx = w.reduce_max(mx);
+  w.for_each(A, [&](int a) { S.dbuf[a] = legal_bit(V, ri, a) ? agz_exp(S.dbuf[a] - mx) : 0.0; });
+  w.sync();
+  double s = 0.0;
+  for (int a = 0; a < A; ++a) s += S.dbuf[a];   // fixed ascending order on every lane
+  w.for_each(A, [&](int a) { out[a] = (float)(S.dbuf[a] / s); });
+  w.sync();
+}
+
 // The selfplay.jl:22-43 loop body between two readout phases, for a game whose budget is spent:
 // resign check -> pick -> play (record pi and Q, re-root) -> done check -> noise for the next move.
 template <class W>
@@ -1210,17 +1447,24 @@ AGZ_FN void game_move_phase(W& w, const View& V, Scratch& S, int g) {
     return;
   }
   AGZ_STAMP_BEGIN(w);
-  int a = V.P;
-  if (pick_move(w, V, S, g, &a) != AGZ_OK) a = V.P;  // the reference dies on its assertion; we pass
-  // play_move!(player, c): record pi and Q, then re-root (mcts_play.jl:26-50)
-  const int k = G.move_count;
   // a fast search (playout cap) leaves no policy target: its row is all zero; the bench stagger's short first search
   // keeps its own budget and counts as full
   const bool fast = !G.short_first && !playout_cap_full(V, G.game_id, rm.n);
+  const bool gumbel = V.gumbel_m > 0 && !fast;       // the search that ends here was a Gumbel search
+  int a = V.P;
+  if (gumbel && V.gumbel[g].n == rm.n) {             // (state never set up: the pool filled before the root was expanded)
+    a = gumbel_move(w, V, S, g);
+  } else if (pick_move(w, V, S, g, &a) != AGZ_OK) {
+    a = V.P;  // the reference dies on its assertion; we pass
+  }
+  // play_move!(player, c): record pi and Q, then re-root (mcts_play.jl:26-50)
+  const int k = G.move_count;
   if (k < V.max_game_length) {
     float* row = V.rec_pi + ((long)g * V.max_game_length + k) * V.A;
     if (fast) {
       w.for_each(V.A, [&](int i) { row[i] = 0.f; });
+    } else if (gumbel) {
+      gumbel_pi(w, V, S, ri, row);
     } else if (V.forced_prune && V.forced_k > 0.0) {     // the forced playouts do not belong in the target
       if (pruned_pi(w, V, S, ri, G.rootN, rm.n <= V.tau, row)) w.count(&V.counters[CT_PRUNED_ROWS], 1);
     } else {
@@ -1253,7 +1497,7 @@ AGZ_FN void game_move_phase(W& w, const View& V, Scratch& S, int g) {
     return;
   }
   const bool next_full = playout_cap_full(V, G.game_id, V.meta[node_index(V, g, child)].n);
-  if (next_full) inject_noise(w, V, S, g, child);
+  if (next_full && V.gumbel_m <= 0) inject_noise(w, V, S, g, child);     // a Gumbel search gets no noise
   if (w.leader()) G.target = G.rootN + (float)(next_full ? V.R : V.cap_fast);
   w.sync();
   AGZ_STAMP(w, V, CT_T_NOISE);
@@ -1303,10 +1547,13 @@ AGZ_FN void game_select_phase(W& w, const View& V, Scratch& S, int g, int par, b
   w.sync();
   // one decision per phase: the root does not change inside it
   const bool forced = V.forced_k > 0.0 && forced_search(V, G, V.meta[node_index(V, g, G.root)].n);
-  while (nleaves < par && failsafe < 2 * par) {
+  // Gumbel root search: begin or halve as due; then the caller's root action per descent, up to the phase end
+  bool gumbel = false;
+  if (V.gumbel_m > 0 && gumbel_search(V, G, V.meta[node_index(V, g, G.root)].n)) gumbel = gumbel_select_start(w, V, S, g);
+  while (nleaves < par && failsafe < 2 * par && (!gumbel || G.rootN < V.gumbel[g].end)) {
     failsafe++;
     int plen = 0;
-    const int leaf = select_leaf(w, V, S, g, G.root, &plen, defer, forced);
+    const int leaf = select_leaf(w, V, S, g, G.root, &plen, defer, forced, gumbel ? gumbel_root_pick(V, g) : -1);
     if (node_is_done(V, g, leaf)) {
       load_board(w, V, S, node_index(V, g, leaf));
       const float value = (float)result_of(area_score(w, V, S, G.komi));
@@ -1947,7 +2194,7 @@ AGZ_FN void game_post(W& w, const View& V, Scratch& S, int g) {
   (void)n_before;
   if (G.phase == G_INIT_WAIT) {
     const bool full = G.short_first || playout_cap_full(V, G.game_id, V.meta[node_index(V, g, G.root)].n);
-    if (full) inject_noise(w, V, S, g, G.root);
+    if (full && V.gumbel_m <= 0) inject_noise(w, V, S, g, G.root);       // a Gumbel search gets no noise
     if (w.leader()) {
       float budget = (float)(full ? V.R : V.cap_fast);
       if (G.short_first) {

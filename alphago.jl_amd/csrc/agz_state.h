@@ -71,6 +71,20 @@ static_assert(sizeof(GameState) == 112, "GameState layout (tests/hs.py mirrors i
 
 constexpr int kMaxPend = 16;    // deferred leaf expansions per game and step (2 x parallel_readouts at most)
 
+// Gumbel root search (agz_selfplay_set_gumbel): the Sequential Halving state of one game slot's current
+// search.  Kept beside GameState, not in it (tests/hs.py mirrors that layout).
+constexpr int kGumbelMax = 16;  // upper bound on the root candidates m
+struct GumbelState {
+  int32_t n;                 // position.n of the root this state belongs to, -1 = none (game_start)
+  int32_t cnt;               // survivors m_p
+  int32_t budget;            // n of the search: G.target - G.rootN when it began
+  int32_t P;                 // phases of the schedule: the smallest P >= 1 with 2^P >= m_0
+  float end;                 // the root N at which the current phase ends
+  int32_t pad;
+  int16_t act[kGumbelMax];   // the survivors' actions, in rank order
+};
+static_assert(sizeof(GumbelState) == 56, "GumbelState layout");
+
 enum Counter : int {
   CT_STEPS = 0, CT_POSITIONS, CT_STARTED, CT_FINISHED, CT_EVALS, CT_DUP, CT_TERMINAL, CT_ROOTVISITS,
   CT_POOL_EXHAUSTED, CT_RESIGNED, CT_CLAIMED,
@@ -88,6 +102,10 @@ enum Counter : int {
   CT_FORCED_SEL, CT_PRUNED_ROWS,
   CT_COUNT
 };
+// Gumbel root search on (View::gumbel_m > 0): searches begun (gumbel_begin) / halvings made (gumbel_halve).  The two
+// slots after CT_PRUNED_ROWS, named outside the enum: tests/test_forced_playouts.py pins the enum's last two names.
+constexpr int CT_GUMBEL_BEGUN = CT_COUNT, CT_GUMBEL_HALVED = CT_COUNT + 1;
+constexpr int kCounterSlots = CT_COUNT + 2;     // what View::counters holds
 
 struct View {
   // dimensions
@@ -191,6 +209,12 @@ struct View {
   // forced_prune the pi row of a full search is written by pruned_pi instead of children_as_pi
   double forced_k;                    // k
   int32_t forced_prune;
+  // Gumbel root search (agz_selfplay_set_gumbel; zero = off, the View{} of the host simulator and of fill_dims): a full
+  // self-play search samples up to gumbel_m root candidates by Gumbel-top-k, spends its budget on them by Sequential
+  // Halving, plays the best s(a) and records softmax(logit + sigma(q)) as the pi row (agz_search.h)
+  int32_t gumbel_m;                   // m
+  double gumbel_cvisit, gumbel_cscale;
+  GumbelState* gumbel;                // [games]
 };
 
 }  // namespace agz

@@ -23,7 +23,7 @@ using Random
 export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, train, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
-       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, set_starts!, set_playout_cap!, playout_cap_counts, set_forced_playouts!, forced_counts, pruned_pi, extract_targets, node_lines, most_visited_path, mvp_gg,
+       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, set_starts!, set_playout_cap!, playout_cap_counts, set_forced_playouts!, forced_counts, pruned_pi, set_gumbel!, gumbel_counts, gumbel_pi, extract_targets, node_lines, most_visited_path, mvp_gg,
        # the node-level surface test/test_mcts.jl:2-5 and test/test_mcts_player.jl:3-6 import
        MCTSNode, select_leaf, maybe_add_child!, add_virtual_loss!, revert_virtual_loss!,
        incorporate_results!, inject_noise!, child_action_score, child_Q, child_U, child_N, child_W,
@@ -814,6 +814,27 @@ function pruned_pi(e::Engine, g::Integer, node::Integer, k::Real, A::Integer)
   out
 end
 
+# Gumbel root search (ours; include/agz.h agz_selfplay_set_gumbel): a full self-play search samples up to m root
+# candidates by Gumbel-top-k, spends its readouts on them by Sequential Halving, plays the survivor with the largest
+# g + logit + σ(q) and records softmax(logit + σ(q)) as the π row.  m = 0 switches it off; not together with forced playouts.
+function set_gumbel!(e::Engine, m::Integer, c_visit::Real = 50.0, c_scale::Real = 1.0)
+  check(e, ccall((:agz_selfplay_set_gumbel, libagz), Int32, (Ptr{Cvoid}, Int32, Float64, Float64), e.handle, m, c_visit,
+                 c_scale))
+end
+# (Gumbel searches begun, halvings made) since agz_selfplay_start
+function gumbel_counts(e::Engine)
+  out = zeros(Int64, 2)
+  check(e, ccall((:agz_selfplay_gumbel_counts, libagz), Int32, (Ptr{Cvoid}, Ptr{Int64}), e.handle, out))
+  Int(out[1]), Int(out[2])
+end
+# the improved-policy row of node `node` of single tree g under the constants given, whatever the engine's setting
+function gumbel_pi(e::Engine, g::Integer, node::Integer, c_visit::Real, c_scale::Real, A::Integer)
+  out = zeros(Float32, A)
+  check(e, ccall((:agz_tree_gumbel_pi, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Ptr{Float32}),
+                 e.handle, g, node, c_visit, c_scale, out))
+  out
+end
+
 # replay_position (board.jl:557-578) from a start position: the position before each move and the final one
 function replay_positions_from(start::Position, moves)
   positions = Position[]
@@ -828,7 +849,10 @@ end
 function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Nothing, Int} = nothing,
                   slots::Union{Nothing, Int} = nothing, seed = nothing, game_id_base = nothing, symmetry = nothing,
                   starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing,
-                  forced_playouts = nothing, prune_targets::Bool = true)
+                  forced_playouts = nothing, prune_targets::Bool = true,
+                  gumbel = nothing, gumbel_c_visit::Real = 50.0, gumbel_c_scale::Real = 1.0)
+  (gumbel !== nothing && gumbel != 0 && forced_playouts !== nothing && forced_playouts != 0) &&
+    throw(ArgumentError("gumbel and forced_playouts are two rules for the same decision: ask for one"))
   G = games === nothing ? 1 : games
   if seed === nothing
     seed, next = STREAM[]
@@ -845,6 +869,7 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
   starts === nothing || set_starts!(e, env, starts)
   playout_cap === nothing || set_playout_cap!(e, playout_cap[1], playout_cap[2])      # (r, p)
   forced_playouts === nothing || set_forced_playouts!(e, forced_playouts, prune_targets)   # k
+  gumbel === nothing || set_gumbel!(e, gumbel, gumbel_c_visit, gumbel_c_scale)             # m
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, G))
   while ccall((:agz_records_count, libagz), Int64, (Ptr{Cvoid},), e.handle) < G
     check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 16))
@@ -1247,7 +1272,10 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
                start_training_after = 50000, slots::Union{Nothing, Int} = nothing, seed = 0, game_id_base = 0,
                augment::Bool = false, callback::Function = println,
                starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing,
-               forced_playouts = nothing, prune_targets::Bool = true)
+               forced_playouts = nothing, prune_targets::Bool = true,
+               gumbel = nothing, gumbel_c_visit::Real = 50.0, gumbel_c_scale::Real = 1.0)
+  (gumbel !== nothing && gumbel != 0 && forced_playouts !== nothing && forced_playouts != 0) &&
+    throw(ArgumentError("gumbel and forced_playouts are two rules for the same decision: ask for one"))
   cur_nn = model === nothing ? NeuralNet(env; tower_height = tower_height) : model                       # train.jl:43
   S = slots === nothing ? min(num_games, 1024) : slots
   e = Engine(board_size = env.N, tower_height = cur_nn.tower_height, games = S, num_readouts = readouts, seed = seed,
@@ -1268,6 +1296,7 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
     replay_set_targets_only!(e, playout_cap[1] > 0)
   end
   forced_playouts === nothing || set_forced_playouts!(e, forced_playouts, prune_targets)   # k, as in selfplay
+  gumbel === nothing || set_gumbel!(e, gumbel, gumbel_c_visit, gumbel_c_scale)             # m, as in selfplay
   check(e, ccall((:agz_selfplay_set_hold, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 1))
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, num_games))
   check(e, ccall((:agz_selfplay_release, libagz), Int32, (Ptr{Cvoid},), e.handle))

@@ -517,6 +517,10 @@ agz_status agz_tree_node_children(agz_engine* e, int32_t g, int32_t node, int32_
  * here, whatever the engine's setting: the node's rows, scale from the node's own N, squashed iff the node's n <= tau.
  * out float[A].  k = 0 gives children_as_pi's row.  One small kernel; synchronises. */
 agz_status agz_tree_pruned_pi(agz_engine* e, int32_t g, int32_t node, double k, float* out);
+/* the improved-policy row of the Gumbel root search (agz_selfplay_set_gumbel, TARGET) of one node of single tree g under
+ * the constants given here, whatever the engine's setting: the node's rows, legal mask and to_play.  out float[A].
+ * c_visit >= 0, c_scale > 0.  One small kernel; synchronises. */
+agz_status agz_tree_gumbel_pi(agz_engine* e, int32_t g, int32_t node, double c_visit, double c_scale, float* out);
 agz_status agz_tree_node_board(agz_engine* e, int32_t g, int32_t node, int8_t* out /* [N*N] */);
 agz_status agz_tree_pending_vlosses(agz_engine* e, int32_t g, int32_t* out);
 agz_status agz_tree_set_draw(agz_engine* e, int32_t g, uint64_t game_id, uint32_t sel);
@@ -635,6 +639,43 @@ agz_status agz_selfplay_set_forced_playouts(agz_engine* e, double k, int32_t pru
 /* out[0] = root descents that the forced rule decided (some child was under-forced), out[1] = recorded pi rows that
  * pruning changed (some N'_a < N_a), since agz_selfplay_start.  Synchronises. */
 agz_status agz_selfplay_forced_counts(agz_engine* e, int64_t out[2]);
+/* Gumbel root search for self-play ("Policy improvement by planning with Gumbel", Danihelka et al., ICLR 2022; DESIGN.md
+ * §5j).  m = 0 switches it off (the default); m in 2..16 is the largest number of root candidates.  c_visit >= 0 (the
+ * paper: 50), c_scale > 0 (the paper: 1.0 for q in [0, 1]).
+ * SCORES.  For the root with rows N, W, P, tp = to_play, position.n = n_root, and a legal action a:
+ *   logit(a) = agz_log((double)P[a]) when P[a] > 0, else -1.0e30
+ *   g(a)     = -agz_log(-agz_log(agz_u01(agz_draw_u64(seed, game_id, n_root, AGZ_SITE_GUMBEL, a))))
+ *   qs(a)    = (W[a] / (1.0f + N[a])) * tp in Float32 -- an unvisited child's W is the root's own network value
+ *   sigma(a) = ((c_visit + (double)maxN) * c_scale) * (0.5 + 0.5 * (double)qs(a)),  maxN = max of N over all A actions
+ *   s(a)     = (g(a) + logit(a)) + sigma(a)                               (Float64, in this order)
+ * SEARCH.  At the first select phase of a search whose root is expanded: n = target - N(root); the survivors are the
+ * m_0 = min(m, #legal) legal actions with the largest g + logit (ties: the lower action), in that order; P = the smallest
+ * integer >= 1 with 2^P >= m_0.  Phase p with m_p survivors ends when N(root) reaches its start plus
+ * Q_p = max(1, floor(n / (P m_p))) m_p, cut to what remains of n; reverted duplicates do not count.  At the start of a
+ * select phase after a phase end with budget left the survivors are ordered by s descending (ties: the lower action)
+ * and the first m_{p+1} = max(2, floor(m_p / 2)) stay (1 if m_p = 1).  At the root level of a descent, after the
+ * pass-first rule of mcts.jl:119-126, the pick is the survivor with the smallest child_N, visits in flight included, the
+ * first in stored order on ties: no score, no tie draw (the select counter of the draw key advances as ever).  Below
+ * the root: PUCT, unchanged.  A select phase stops collecting at the phase end, so a search makes exactly n root visits
+ * unless the pool fills.  No Dirichlet noise is injected for a Gumbel search.
+ * MOVE.  The survivor with the largest s, the lower action on ties; no soft pick and no pick-tie draw at any move
+ * number.  (A search whose state was never set up -- the pool filled before the root was expanded -- falls back to
+ * pick_move.)  The resign check, the recorded q and the re-rooting are unchanged.
+ * TARGET.  Over legal a: x(a) = logit(a) + sigma(a); pi[a] = (float)(agz_exp(x(a) - max x) / sum), the Float64 sum in
+ * ascending index order; illegal actions get 0; no 0.98 squash.
+ * WHERE.  Self-play full searches only: every search with the playout cap off; with it on the searches the coin made
+ * full (the bench stagger's shortened first search counts as full).  Fast searches, the arena, analysis and review are
+ * as before, and so are the single-tree calls: a host-driven MCTSPlayer loop does not reproduce Gumbel self-play;
+ * agz_tree_gumbel_pi gives the target row of any node.
+ * One draw site is added (AGZ_SITE_GUMBEL = 12: move = n_root, idx = action), none moves; records, agz_game_header,
+ * agz_config and agz_stats do not change.
+ * Synchronises.  Refused (AGZ_BAD_ARGUMENT, the setting in force kept): an arena_mode engine; m outside {0, 2..16};
+ * c_visit negative or NaN; c_scale zero, negative or NaN; forced playouts on (agz_selfplay_set_forced_playouts with
+ * k > 0 is refused in turn while m > 0: the two rules answer the same question and are not composed); games of a run
+ * still being played (as agz_selfplay_set_playout_cap). */
+agz_status agz_selfplay_set_gumbel(agz_engine* e, int32_t m, double c_visit, double c_scale);
+/* out[0] = Gumbel searches begun, out[1] = halvings made, since agz_selfplay_start.  Synchronises. */
+agz_status agz_selfplay_gumbel_counts(agz_engine* e, int64_t out[2]);
 agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out);
 /* out[B], child_N / child_W / prior [B][A] (the root's rows when the search ended); any of them may be NULL */
 agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N, float* child_W, float* prior);

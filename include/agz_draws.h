@@ -58,6 +58,9 @@
 #define AGZ_SITE_PLAYOUT_CAP 11u   /* agz_selfplay_set_playout_cap: move = position.n of the
                                     * root about to be searched, idx = 0; a full search
                                     * iff agz_u01(draw) < full_prob                    */
+#define AGZ_SITE_GUMBEL 12u        /* agz_selfplay_set_gumbel: move = position.n of the root
+                                    * searched, idx = action; the Gumbel variable
+                                    * g = -agz_log(-agz_log(agz_u01(draw)))           */
 
 static inline AGZ_HD uint64_t agz_mix64(uint64_t z) {
   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
