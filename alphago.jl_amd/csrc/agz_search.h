@@ -632,36 +632,30 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
   return cur;
 }
 
+// select_leaf_rows<R, Mode> for the board's row width R = ceil(AP / 64); kNoRowsForm when there is no instantiation
+// for it (a leaf is never negative)
+constexpr int kNoRowsForm = -2;
+template <int Mode, class W>
+AGZ_FN int select_leaf_rows_of(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer,
+                               int root_pick) {
+  switch ((V.AP + 63) >> 6) {
+    case 1: return select_leaf_rows<1, Mode>(w, V, S, g, from, plen_out, defer, root_pick);
+    case 2: return select_leaf_rows<2, Mode>(w, V, S, g, from, plen_out, defer, root_pick);     // 9x9
+    case 3: return select_leaf_rows<3, Mode>(w, V, S, g, from, plen_out, defer, root_pick);     // 13x13
+    case 6: return select_leaf_rows<6, Mode>(w, V, S, g, from, plen_out, defer, root_pick);     // 19x19
+    default: return kNoRowsForm;
+  }
+}
+
 // select_leaf from `from`; the visited nodes are left in S.path[0..len).  Returns the leaf.
 template <class W>
 AGZ_FN int select_leaf(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer = false,
                        bool forced = false, int root_pick = -1) {
   if constexpr (W::kRegisterRows) {
-    if (root_pick >= 0) {
-      switch ((V.AP + 63) >> 6) {
-        case 1: return select_leaf_rows<1, kSelGiven>(w, V, S, g, from, plen_out, defer, root_pick);
-        case 2: return select_leaf_rows<2, kSelGiven>(w, V, S, g, from, plen_out, defer, root_pick);
-        case 3: return select_leaf_rows<3, kSelGiven>(w, V, S, g, from, plen_out, defer, root_pick);
-        case 6: return select_leaf_rows<6, kSelGiven>(w, V, S, g, from, plen_out, defer, root_pick);
-        default: break;
-      }
-    } else if (forced) {
-      switch ((V.AP + 63) >> 6) {
-        case 1: return select_leaf_rows<1, kSelForced>(w, V, S, g, from, plen_out, defer, -1);
-        case 2: return select_leaf_rows<2, kSelForced>(w, V, S, g, from, plen_out, defer, -1);
-        case 3: return select_leaf_rows<3, kSelForced>(w, V, S, g, from, plen_out, defer, -1);
-        case 6: return select_leaf_rows<6, kSelForced>(w, V, S, g, from, plen_out, defer, -1);
-        default: break;
-      }
-    } else {
-      switch ((V.AP + 63) >> 6) {
-        case 1: return select_leaf_rows<1, kSelPlain>(w, V, S, g, from, plen_out, defer, -1);
-        case 2: return select_leaf_rows<2, kSelPlain>(w, V, S, g, from, plen_out, defer, -1);     // 9x9
-        case 3: return select_leaf_rows<3, kSelPlain>(w, V, S, g, from, plen_out, defer, -1);     // 13x13
-        case 6: return select_leaf_rows<6, kSelPlain>(w, V, S, g, from, plen_out, defer, -1);     // 19x19
-        default: break;
-      }
-    }
+    const int leaf = root_pick >= 0 ? select_leaf_rows_of<kSelGiven>(w, V, S, g, from, plen_out, defer, root_pick)
+                     : forced       ? select_leaf_rows_of<kSelForced>(w, V, S, g, from, plen_out, defer, -1)
+                                    : select_leaf_rows_of<kSelPlain>(w, V, S, g, from, plen_out, defer, -1);
+    if (leaf != kNoRowsForm) return leaf;
   }
   GameState& G = V.gs[g];
   const int A = V.A, pass = V.P;
@@ -1201,10 +1195,16 @@ AGZ_FN bool playout_cap_full(const View& V, uint64_t game_id, int n) {
   return agz_u01(agz_draw_u64(V.seed, game_id, (uint32_t)n, AGZ_SITE_PLAYOUT_CAP, 0)) < V.cap_full_prob;
 }
 
+// Is the search of self-play game G's root of ply root_n a full one?  The bench stagger's short first search keeps its
+// own budget and counts as full, whatever its coin.
+AGZ_FN bool full_search(const View& V, const GameState& G, int root_n) {
+  return G.short_first || playout_cap_full(V, G.game_id, root_n);
+}
+
 AGZ_FN bool forced_search(const View& V, const GameState& G, int root_n) {
   if (!(V.forced_k > 0.0) || V.arena || V.analysis) return false;
   if (G.phase == G_MANUAL) return true;
-  return G.short_first || playout_cap_full(V, G.game_id, root_n);
+  return full_search(V, G, root_n);
 }
 
 
@@ -1234,7 +1234,7 @@ constexpr double kGumbelNoLogit = -1.0e30;
 // with the playout cap off); fast searches, the arena, analysis, review and single trees (G_MANUAL) never.
 AGZ_FN bool gumbel_search(const View& V, const GameState& G, int root_n) {
   if (V.gumbel_m <= 0 || V.arena || V.analysis || G.phase == G_MANUAL) return false;
-  return G.short_first || playout_cap_full(V, G.game_id, root_n);
+  return full_search(V, G, root_n);
 }
 
 AGZ_FN double gumbel_logit(float p) { return p > 0.0f ? agz_log((double)p) : kGumbelNoLogit; }
@@ -1424,6 +1424,15 @@ AGZ_FN void gumbel_pi(W& w, const View& V, Scratch& S, long ri, float* out) {
   w.sync();
 }
 
+// Begin the search of self-play game g's root `node`: Dirichlet noise (selfplay.jl:23) unless the search is fast or a
+// Gumbel search, which gets none, and the budget: R more root visits, cap_fast for a fast search.
+template <class W>
+AGZ_FN void search_begin(W& w, const View& V, Scratch& S, int g, int node, bool full) {
+  GameState& G = V.gs[g];
+  if (full && V.gumbel_m <= 0) inject_noise(w, V, S, g, node);
+  if (w.leader()) G.target = G.rootN + (float)(full ? V.R : V.cap_fast);
+}
+
 // The selfplay.jl:22-43 loop body between two readout phases, for a game whose budget is spent:
 // resign check -> pick -> play (record pi and Q, re-root) -> done check -> noise for the next move.
 template <class W>
@@ -1447,9 +1456,8 @@ AGZ_FN void game_move_phase(W& w, const View& V, Scratch& S, int g) {
     return;
   }
   AGZ_STAMP_BEGIN(w);
-  // a fast search (playout cap) leaves no policy target: its row is all zero; the bench stagger's short first search
-  // keeps its own budget and counts as full
-  const bool fast = !G.short_first && !playout_cap_full(V, G.game_id, rm.n);
+  // a fast search (playout cap) leaves no policy target: its row is all zero
+  const bool fast = !full_search(V, G, rm.n);
   const bool gumbel = V.gumbel_m > 0 && !fast;       // the search that ends here was a Gumbel search
   int a = V.P;
   if (gumbel && V.gumbel[g].n == rm.n) {             // (state never set up: the pool filled before the root was expanded)
@@ -1496,9 +1504,7 @@ AGZ_FN void game_move_phase(W& w, const View& V, Scratch& S, int g) {
     game_finish(w, V, S, g, result_of(sc), 0, sc);
     return;
   }
-  const bool next_full = playout_cap_full(V, G.game_id, V.meta[node_index(V, g, child)].n);
-  if (next_full && V.gumbel_m <= 0) inject_noise(w, V, S, g, child);     // a Gumbel search gets no noise
-  if (w.leader()) G.target = G.rootN + (float)(next_full ? V.R : V.cap_fast);
+  search_begin(w, V, S, g, child, playout_cap_full(V, G.game_id, V.meta[node_index(V, g, child)].n));
   w.sync();
   AGZ_STAMP(w, V, CT_T_NOISE);
 }
@@ -2193,15 +2199,12 @@ AGZ_FN void game_post(W& w, const View& V, Scratch& S, int g) {
   }
   (void)n_before;
   if (G.phase == G_INIT_WAIT) {
-    const bool full = G.short_first || playout_cap_full(V, G.game_id, V.meta[node_index(V, g, G.root)].n);
-    if (full && V.gumbel_m <= 0) inject_noise(w, V, S, g, G.root);       // a Gumbel search gets no noise
+    search_begin(w, V, S, g, G.root, full_search(V, G, V.meta[node_index(V, g, G.root)].n));
     if (w.leader()) {
-      float budget = (float)(full ? V.R : V.cap_fast);
-      if (G.short_first) {
+      if (G.short_first) {          // the bench stagger: a short first search of its own budget
         const double u = agz_u01(agz_draw_u64(V.seed, G.game_id, 0, AGZ_SITE_STAGGER, 1000000u));
-        budget = (float)(1 + (int)(u * (double)(V.R - 1)));
+        G.target = G.rootN + (float)(1 + (int)(u * (double)(V.R - 1)));
       }
-      G.target = G.rootN + budget;
       G.phase = G_SEARCH;
     }
   }

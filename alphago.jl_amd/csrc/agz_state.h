@@ -98,7 +98,7 @@ enum Counter : int {
   CT_PEAK_NODES,   // max over games of nodes_used at the moment of a move
   CT_CAP_FULL, CT_CAP_FAST,   // playout cap on (View::cap_fast > 0): moves played after a full / a fast search
   // forced playouts on (View::forced_k > 0): root descents the forced rule decided / recorded pi rows that policy target
-  // pruning changed (appended here: tests/cap_twin.py pins CT_PEAK_NODES's place)
+  // pruning changed (appended here: tests/hs.py pins CT_PEAK_NODES's place)
   CT_FORCED_SEL, CT_PRUNED_ROWS,
   CT_COUNT
 };

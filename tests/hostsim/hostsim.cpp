@@ -273,4 +273,135 @@ void hs_node_legal(void* h, int g, int node, int8_t* out) {
   for (int a = 0; a < s->V.A; ++a) out[a] = agz::legal_bit(s->V, ni, a);
 }
 
+// ---- the settings of self-play (agz_selfplay_set_*) and single-node entries of what they add
+// the table of start positions (View::st_*, agz_selfplay_set_starts):
+// boards int8[S][P], info[S], history int8[S][7][P] or NULL; S = 0 clears.  The copies live as long as the Sim.
+void hs_set_starts(void* h, const int8_t* boards, const agz_position_info* info, const int8_t* history, int S) {
+  Sim* s = (Sim*)h;
+  agz::View& V = s->V;
+  V.st_count = 0;
+  V.st_board = nullptr;
+  V.st_hist = nullptr;
+  V.st_info = nullptr;
+  if (S <= 0) return;
+  const size_t P = (size_t)V.P;
+  int8_t *b = nullptr, *hh = nullptr;
+  agz_position_info* f = nullptr;
+  alloc_one(s, b, (size_t)S * P);
+  alloc_one(s, hh, (size_t)S * 7 * P);
+  alloc_one(s, f, (size_t)S);
+  memcpy(b, boards, (size_t)S * P);
+  if (history) memcpy(hh, history, (size_t)S * 7 * P);
+  memcpy(f, info, sizeof(agz_position_info) * (size_t)S);
+  V.st_count = S;
+  V.st_board = b;
+  V.st_hist = hh;
+  V.st_info = f;
+}
+
+int hs_starts_count(void* h) { return ((Sim*)h)->V.st_count; }
+
+// root_board_valid of one candidate entry (what k_starts_valid runs per entry on the device)
+int hs_start_board_valid(void* h, const int8_t* board, int ko) {
+  Sim* s = (Sim*)h;
+  SimWave w;
+  return agz::root_board_valid(w, s->V, s->S, board, ko) ? 1 : 0;
+}
+
+// the playout cap (View::cap_fast / cap_full_prob, agz_selfplay_set_playout_cap):
+// fast_readouts = 0 switches the cap off
+void hs_set_playout_cap(void* h, int fast_readouts, double full_prob) {
+  agz::View& V = ((Sim*)h)->V;
+  V.cap_fast = fast_readouts > 0 ? fast_readouts : 0;
+  V.cap_full_prob = fast_readouts > 0 ? full_prob : 1.0;
+}
+
+// forced playouts and policy target pruning (View::forced_k / forced_prune, agz_selfplay_set_forced_playouts):
+// k = 0 switches both rules off
+void hs_set_forced_playouts(void* h, double k, int prune) {
+  agz::View& V = ((Sim*)h)->V;
+  V.forced_k = k > 0.0 ? k : 0.0;
+  V.forced_prune = (k > 0.0 && prune) ? 1 : 0;
+}
+
+// pruned_pi of node `node` of game slot g under k, whatever the setting: the scale of the node's own N, the squash of
+// its own n <= tau.  out float[A]; returns whether pruning changed the row.
+int hs_pruned_pi(void* h, int g, int node, double k, float* out) {
+  Sim* s = (Sim*)h;
+  SimWave w;
+  agz::View V = s->V;
+  V.forced_k = k;
+  const long ni = agz::node_index(V, g, node);
+  return agz::pruned_pi(w, V, s->S, ni, *agz::slotN(V, g, node), V.meta[ni].n <= V.tau, out) ? 1 : 0;
+}
+
+// the Gumbel root search (View::gumbel_m / gumbel_cvisit / gumbel_cscale, agz_selfplay_set_gumbel):
+// m = 0 switches the rule off.  The two counters restart here (hs_start clears the enum's counters only).
+void hs_set_gumbel(void* h, int m, double c_visit, double c_scale) {
+  agz::View& V = ((Sim*)h)->V;
+  V.gumbel_m = m > 0 ? m : 0;
+  V.gumbel_cvisit = m > 0 ? c_visit : 0.0;
+  V.gumbel_cscale = m > 0 ? c_scale : 0.0;
+  V.counters[agz::CT_GUMBEL_BEGUN] = 0;
+  V.counters[agz::CT_GUMBEL_HALVED] = 0;
+}
+
+// out[0] = Gumbel searches begun, out[1] = halvings made
+void hs_gumbel_counts(void* h, unsigned long long* out) {
+  const agz::View& V = ((Sim*)h)->V;
+  out[0] = V.counters[agz::CT_GUMBEL_BEGUN];
+  out[1] = V.counters[agz::CT_GUMBEL_HALVED];
+}
+
+void hs_gumbel_state(void* h, int g, agz::GumbelState* out) { *out = ((Sim*)h)->V.gumbel[g]; }
+
+// gumbel_pi of node `node` of game slot g under the constants given, whatever the setting.  out float[A].
+void hs_gumbel_pi(void* h, int g, int node, double c_visit, double c_scale, float* out) {
+  Sim* s = (Sim*)h;
+  SimWave w;
+  agz::View V = s->V;
+  V.gumbel_cvisit = c_visit;
+  V.gumbel_cscale = c_scale;
+  agz::gumbel_pi(w, V, s->S, agz::node_index(V, g, node), out);
+}
+
+// The root level of a Gumbel descent on a single tree (hand rows): slot g's state becomes the `cnt` survivors `act` of
+// its root, in that order, and one select_leaf runs from the root with gumbel_root_pick's action.  Returns the leaf.
+int hs_gumbel_descend(void* h, int g, const int16_t* act, int cnt) {
+  Sim* s = (Sim*)h;
+  SimWave w;
+  agz::View& V = s->V;
+  agz::GumbelState& T = V.gumbel[g];
+  T.n = V.meta[agz::node_index(V, g, V.gs[g].root)].n;
+  T.cnt = cnt;
+  for (int i = 0; i < cnt; ++i) T.act[i] = act[i];
+  int plen = 0;
+  return agz::select_leaf(w, V, s->S, g, V.gs[g].root, &plen, false, false, agz::gumbel_root_pick(V, g));
+}
+
+// the schedule of a search of budget n with m0 survivors: (m_p, Q_p) pairs into out, from the functions the search uses
+int hs_gumbel_schedule(int n, int m0, int32_t* out, int cap) {
+  int P = 1;
+  while ((1 << P) < m0) ++P;
+  int m = m0, left = n, k = 0;
+  while (left > 0 && k < cap) {
+    int q = agz::gumbel_quota(n, P, m);
+    if (q > left) q = left;
+    out[2 * k] = m;
+    out[2 * k + 1] = q;
+    ++k;
+    left -= q;
+    m = m == 1 ? 1 : (m / 2 > 2 ? m / 2 : 2);
+  }
+  return k;
+}
+
+// ---- analysis lines
+// node_lines on `node` of slot g: out [K], pv [K][D], pv_N [K][D]
+void hs_node_lines(void* h, int g, int node, int K, int D, int min_visits, agz_line* out, int16_t* pv, float* pv_N) {
+  Sim* s = (Sim*)h;
+  SimWave w;
+  agz::node_lines(w, s->V, s->S, g, node, K, D, min_visits, out, pv, pv_N);
+}
+
 }  // extern "C"

@@ -2,9 +2,12 @@
 search templates (TEST INFRASTRUCTURE; see tests/hostsim/hostsim.cpp)."""
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
+
+import alphago_jl_amd as ag
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CT = ["steps", "positions", "started", "finished", "evals", "dup", "terminal", "rootvisits",
@@ -84,6 +87,11 @@ class TreeArgs(C.Structure):
                 ("dout", C.POINTER(C.c_double))]
 
 
+class GumbelStateC(C.Structure):
+    _fields_ = [("n", C.c_int32), ("cnt", C.c_int32), ("budget", C.c_int32), ("P", C.c_int32), ("end", C.c_float),
+                ("pad", C.c_int32), ("act", C.c_int16 * 16)]
+
+
 (TOP_INIT, TOP_SELECT, TOP_ADD_CHILD, TOP_VLOSS_ADD, TOP_VLOSS_REVERT, TOP_INCORPORATE, TOP_NOISE,
  TOP_SEARCH_SELECT, TOP_SEARCH_POST, TOP_PICK, TOP_PLAY, TOP_RESIGN, TOP_SCORES, TOP_PENDING) = range(14)
 
@@ -101,7 +109,7 @@ def lib():
         if not os.path.exists(os.path.join(d, "libhostsim.so")):
             raise
     L = C.CDLL(os.path.join(d, "libhostsim.so"))
-    vp, i, f = C.c_void_p, C.c_int, C.c_float
+    vp, i, f, dbl = C.c_void_p, C.c_int, C.c_float, C.c_double
     P = C.POINTER
     sig = {
         "hs_create": (vp, [P(AgzConfig)]), "hs_destroy": (None, [vp]), "hs_dims": (None, [vp, P(C.c_int32)]),
@@ -123,6 +131,15 @@ def lib():
         "hs_node_N": (f, [vp, i, i]), "hs_node_W": (f, [vp, i, i]), "hs_node_set_N": (None, [vp, i, i, f]),
         "hs_node_row": (P(f), [vp, i, i, i]), "hs_node_children": (P(C.c_int32), [vp, i, i]),
         "hs_node_board": (P(C.c_int8), [vp, i, i]), "hs_node_legal": (None, [vp, i, i, P(C.c_int8)]),
+        # the settings of self-play and what the tests read back of them
+        "hs_set_starts": (None, [vp, P(C.c_int8), P(ag._lib.PositionInfo), P(C.c_int8), i]),
+        "hs_starts_count": (i, [vp]), "hs_start_board_valid": (i, [vp, P(C.c_int8), i]),
+        "hs_set_playout_cap": (None, [vp, i, dbl]),
+        "hs_set_forced_playouts": (None, [vp, dbl, i]), "hs_pruned_pi": (i, [vp, i, i, dbl, P(f)]),
+        "hs_set_gumbel": (None, [vp, i, dbl, dbl]), "hs_gumbel_counts": (None, [vp, P(C.c_ulonglong)]),
+        "hs_gumbel_state": (None, [vp, i, P(GumbelStateC)]), "hs_gumbel_pi": (None, [vp, i, i, dbl, dbl, P(f)]),
+        "hs_gumbel_descend": (i, [vp, i, P(C.c_int16), i]), "hs_gumbel_schedule": (i, [i, i, P(C.c_int32), i]),
+        "hs_node_lines": (None, [vp, i, i, i, i, i, P(ag._lib.Line), P(C.c_int16), P(f)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -130,6 +147,16 @@ def lib():
         fn.argtypes = args
     _lib = L
     return L
+
+
+def counter_names():
+    """enum Counter of agz_state.h, in order (without CT_COUNT)"""
+    src = open(os.path.join(os.path.dirname(HERE), "alphago.jl_amd", "csrc", "agz_state.h")).read()
+    body = re.search(r"enum Counter : int \{(.*?)\};", src, flags=re.S).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    names = re.findall(r"\bCT_\w+", body)
+    assert names[-1] == "CT_COUNT" and len(names) - 1 <= 64
+    return names[:-1]
 
 
 def p8(a):
@@ -201,6 +228,12 @@ class Sim:
         self.L.hs_counters(self.h, out)
         return dict(zip(CT, list(out)))
 
+    def all_counters(self):
+        """every counter of enum Counter by its name"""
+        out = (C.c_ulonglong * 64)()
+        self.L.hs_counters(self.h, out)
+        return dict(zip(counter_names(), list(out)))
+
     def records(self):
         out = []
         for k in range(self.L.hs_records_count(self.h)):
@@ -215,6 +248,56 @@ class Sim:
                             resign_disabled=hd.resign_disabled, final_score=hd.final_score,
                             short_searches=hd.short_searches, moves=moves[:nm].copy(), pis=pis[:nm].copy(), qs=qs[:nm].copy()))
         return sorted(out, key=lambda r: r["game_id"])
+
+    # ---- the settings of self-play (agz_selfplay_set_*)
+    def set_starts(self, positions):
+        """the table of start positions, from oracle positions; an empty list clears it"""
+        if not positions:
+            self.L.hs_set_starts(self.h, None, None, None, 0)
+            return
+        from selfplay_twin import opos_arrays          # (the twin module imports this one)
+        boards, infos, hist = opos_arrays(positions)
+        self.L.hs_set_starts(self.h, p8(boards), infos, p8(hist), len(positions))
+
+    def board_valid(self, board, ko=-1):
+        b = np.ascontiguousarray(board, np.int8)
+        return bool(self.L.hs_start_board_valid(self.h, p8(b), ko))
+
+    def set_playout_cap(self, r, p):
+        self.L.hs_set_playout_cap(self.h, int(r), float(p))
+
+    def cap_counts(self):
+        c, names = self.all_counters(), counter_names()
+        assert names.index("CT_CAP_FAST") == names.index("CT_CAP_FULL") + 1
+        assert names.index("CT_PEAK_NODES") == len(CT) - 1
+        return int(c["CT_CAP_FULL"]), int(c["CT_CAP_FAST"])
+
+    def set_forced_playouts(self, k, prune=True):
+        self.L.hs_set_forced_playouts(self.h, float(k), 1 if prune else 0)
+
+    def forced_counts(self):
+        c, names = self.all_counters(), counter_names()
+        assert names.index("CT_PRUNED_ROWS") == names.index("CT_FORCED_SEL") + 1 == names.index("CT_CAP_FAST") + 2
+        return int(c["CT_FORCED_SEL"]), int(c["CT_PRUNED_ROWS"])
+
+    def set_gumbel(self, m=0, c_visit=50.0, c_scale=1.0):
+        self.L.hs_set_gumbel(self.h, int(m), float(c_visit), float(c_scale))
+
+    def gumbel_counts(self):
+        out = (C.c_ulonglong * 2)()
+        self.L.hs_gumbel_counts(self.h, out)
+        return int(out[0]), int(out[1])
+
+    def gumbel_state(self, g):
+        st = GumbelStateC()
+        self.L.hs_gumbel_state(self.h, g, C.byref(st))
+        return st
+
+    def schedule(self, n, m0):
+        """the Sequential Halving schedule [(m_p, Q_p)] of a search of budget n with m0 survivors"""
+        out = (C.c_int32 * 128)()
+        k = self.L.hs_gumbel_schedule(int(n), int(m0), out, 64)
+        return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(k)]
 
     # ---- Go rules
     def go_play(self, boards, to_play, ko, moves):
@@ -281,6 +364,33 @@ class Sim:
         st, root = self.op(TOP_INIT, g=g, board=board, info=info, history=history)
         assert st == 0
         return root
+
+    def pruned_pi(self, g, node, k):
+        """agz_tree_pruned_pi: (row float32[A], whether pruning changed it)"""
+        out = np.zeros(self.A, np.float32)
+        ch = self.L.hs_pruned_pi(self.h, g, node, float(k), pf(out))
+        return out, bool(ch)
+
+    def gumbel_pi(self, g, node, c_visit, c_scale):
+        out = np.zeros(self.A, np.float32)
+        self.L.hs_gumbel_pi(self.h, g, node, float(c_visit), float(c_scale), pf(out))
+        return out
+
+    def gumbel_descend(self, g, survivors):
+        """one descent from the root of slot g with `survivors` as its Gumbel state -> the leaf"""
+        act = (C.c_int16 * len(survivors))(*survivors)
+        return int(self.L.hs_gumbel_descend(self.h, g, act, len(survivors)))
+
+    def lines(self, node, K, D, mv, g=0):
+        """node_lines on `node`: the fields of the K lines, pv [K][D] and pv_N [K][D]"""
+        ln = (ag._lib.Line * K)()
+        pv = np.full((K, D), 7, np.int16)               # (junk: every entry has to be written)
+        pvn = np.full((K, D), 7, np.float32)
+        self.L.hs_node_lines(self.h, g, node, K, D, mv, ln, pv.ctypes.data_as(C.POINTER(C.c_int16)), pf(pvn))
+        out = {f: np.array([getattr(x, f) for x in ln], np.int32 if f in ("move", "pv_len") else np.float32)
+               for f in ("move", "pv_len", "N", "W", "prior", "end_W")}
+        out.update(pv=pv, pv_N=pvn)
+        return out
 
     def game(self, g):
         s = GameState()

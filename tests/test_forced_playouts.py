@@ -1,6 +1,6 @@
 """Forced playouts and policy target pruning (agz_selfplay_set_forced_playouts) on the host simulator.
-The twin of tests/forced_twin.py restates the descent and the pruned target; with k = 0 it is held to the cap twin
-before anything rests on it.  Then: the worked example of the rules on a single tree, whole games against the twin bit
+tests/selfplay_twin.py restates the descent and the pruned target; with k = 0 the restated descent is held to the
+oracle's own before anything rests on it.  Then: the worked example of the rules on a single tree, whole games against the twin bit
 for bit, the off path against the cap simulator byte for byte, and the properties of the pruned rows.  CPU only."""
 import ctypes as C
 import inspect
@@ -12,12 +12,10 @@ import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
-import cap_twin as ct
-import forced_twin as ft
 import hs
 import orc
-import starts_twin as tw
-from test_hostsim_selfplay import OracleNet, bits_equal
+import selfplay_twin as tw
+from test_hostsim_selfplay import OracleNet, bits_equal, oracle_game
 from test_playout_cap import run_cap_sim
 
 L = orc.lib()
@@ -29,15 +27,17 @@ NO_RESIGN = dict(resign_threshold=-2.0, resign_disable_fraction=0.0)
 
 @pytest.mark.parametrize("N,R,games,r,p", [(5, 16, 3, 4, 0.4), (5, 16, 2, 4, 1.0), (9, 16, 1, 4, 0.3)])
 def test_twin_at_k_0_is_the_cap_twin(N, R, games, r, p):
-    """p < 1: the cap on; p = 1: every search full, which is the cap off (the twin's r = 0 form as well)"""
+    """forced = (0, .) plays the whole game on the restated descent under no rule; without the option every descent is
+    or_select_leaf.  p < 1: the cap on; p = 1: every search full, which is the cap off (the twin's r = 0 form as well),
+    and there the game from the empty board is or_selfplay_ex's, the C loop's, too"""
     net = OracleNet(N, 1, seed=0)
     starts = tw.random_starts(N, (4, 7, 1), seed=0)
     for gid in range(games):
         st = starts[gid % 3] if gid % 2 else None
-        want = ct.twin_selfplay_cap(N, net.cb, R, r, p, 3, gid, st, -0.1, 0.0)
+        want = tw.twin_selfplay(N, net.cb, R, 3, gid, st, -0.1, 0.0, cap=(r, p))
         forms = [(r, p)] + ([(0, 1.0)] if p == 1.0 else [])
         for rr, pp in forms:
-            got = ft.twin_selfplay_forced(N, net.cb, R, rr, pp, 0.0, True, 3, gid, st, -0.1, 0.0)
+            got = tw.twin_selfplay(N, net.cb, R, 3, gid, st, -0.1, 0.0, cap=(rr, pp), forced=(0.0, True))
             assert got["num_moves"] == want["num_moves"] and (got["moves"] == want["moves"]).all()
             assert got["result"] == want["result"] and got["was_resign"] == want["was_resign"]
             assert got["evals"] == want["evals"] and (got["full"] == want["full"]).all()
@@ -45,6 +45,14 @@ def test_twin_at_k_0_is_the_cap_twin(N, R, games, r, p):
             assert bits_equal(got["pis"], want["pis"]) and bits_equal(got["qs"], want["qs"])
             assert bits_equal(got["raw_pis"], want["pis"])
             assert got["forced_sel"] == 0 and not got["pruned_rows"].any()
+            if pp == 1.0 and st is None:
+                o = oracle_game(N, net, R, 3, gid, -0.1, 0.0)
+                assert got["full"].all() and got["searched_full"].all()
+                assert got["num_moves"] == o["num_moves"] and (got["moves"] == o["moves"][: got["num_moves"]]).all()
+                assert got["result"] == o["result"] and got["evals"] == o["evals"]
+                assert got["was_resign"] == (o["result_string"] in (b"B+R", b"W+R"))
+                assert bits_equal(got["pis"], o["pis"]) and bits_equal(got["qs"], o["qs"])
+                assert bits_equal(got["raw_pis"], o["pis"])
     net.close()
 
 
@@ -59,7 +67,7 @@ EX_TABLE = [60, 13.707, 8.882, 0, 6]          # N' as the rules' table prints it
 def example_tree(k, rows=(EX_N, EX_W, EX_P), at=(0, 1, 2, 3, 4), rootN=99.0, n=None, last_move=-1, N=5, prune=True):
     """a single tree on the simulator whose expanded root has the given child rows at actions `at` (zero elsewhere),
     c_puct = 1, N(root) = rootN, position.n = n (default: past tau, no squash); the engine's setting is (k, prune)"""
-    sim = ft.ForcedSim(board_size=N, games=1, num_readouts=8, seed=1, c_puct=1.0)
+    sim = hs.Sim(board_size=N, games=1, num_readouts=8, seed=1, c_puct=1.0)
     sim.set_forced_playouts(k, prune)
     root = sim.tree_init(0, np.zeros(N * N, np.int8), n=sim.tau + 1 if n is None else n, last_move=last_move)
     st, leaf = sim.op(hs.TOP_SELECT, node=root)
@@ -111,7 +119,7 @@ def test_example_forced_pick_and_k_0_pick():
     assert sim.row(0, root, 0)[3] == 2.0
     sim.close()
     sim, root = example_tree(0.0, rootN=98.0)
-    score, _, scale = ft.action_scores(EX_N, EX_W, EX_P, 1, 99.0, 1.0)
+    score, _, scale = tw.action_scores(EX_N, EX_W, EX_P, 1, 99.0, 1.0)
     assert scale == 10.0 and abs(score[0] - 0.58197) < 5e-6
     best = int(np.argmax(score))
     assert best == 4                                    # the example: a4's score is above S*
@@ -119,7 +127,7 @@ def test_example_forced_pick_and_k_0_pick():
     assert sim.forced_counts() == (0, 0)
     sim.close()
     # the twin's descent rule on the same rows
-    uf = ft.under_forced(2.0, EX_N, EX_P, 99.0)
+    uf = tw.under_forced(2.0, EX_N, EX_P, 99.0)
     assert list(uf) == [False, False, False, True, False]
 
 
@@ -157,7 +165,7 @@ def test_example_pass_hack_keeps_its_precedence():
 def test_example_pruned_row():
     sim, root = example_tree(0.0)                       # agz_tree_pruned_pi does not look at the setting
     got, changed = sim.pruned_pi(0, root, 2.0)
-    want, wch = ft.pruned_pi(*rows_of(sim, root), 1, 99.0, 1.0, 2.0, False)
+    want, wch = tw.pruned_pi(*rows_of(sim, root), 1, 99.0, 1.0, 2.0, False)
     assert changed and wch and bits_equal(got, want)
     visits, s_star = table_visits()
     assert abs(s_star - 0.58197) < 5e-6
@@ -178,7 +186,7 @@ def test_example_pruned_row_squashed():
     sim, root = example_tree(0.0, n=0)                  # position.n = 0 <= tau: the squash
     assert sim.meta(0, root).n <= sim.tau
     got, changed = sim.pruned_pi(0, root, 2.0)
-    want, _ = ft.pruned_pi(*rows_of(sim, root), 1, 99.0, 1.0, 2.0, True)
+    want, _ = tw.pruned_pi(*rows_of(sim, root), 1, 99.0, 1.0, 2.0, True)
     assert changed and bits_equal(got, want)
     visits, _ = table_visits()
     sq = np.array([v ** 0.98 for v in visits])
@@ -186,7 +194,7 @@ def test_example_pruned_row_squashed():
     plain, ch0 = sim.pruned_pi(0, root, 0.0)
     cn = sim.row(0, root, 0).astype(np.float64)
     # children_as_pi with the squash, from the oracle's own pow
-    pw = np.array([ft.L.or_det_pow(float(x), 0.98) for x in cn])
+    pw = np.array([tw.L.or_det_pow(float(x), 0.98) for x in cn])
     s = 0.0
     for x in pw:
         s += x
@@ -201,9 +209,9 @@ def test_example_tied_most_visited_child():
         sim, root = example_tree(0.0, rows=(Nv, Wv, Pv), at=at, rootN=79.0)
         got, changed = sim.pruned_pi(0, root, 2.0)
         Nr, Wr, Pr = rows_of(sim, root)
-        want, _ = ft.pruned_pi(Nr, Wr, Pr, 1, 79.0, 1.0, 2.0, False)
+        want, _ = tw.pruned_pi(Nr, Wr, Pr, 1, 79.0, 1.0, 2.0, False)
         assert changed and bits_equal(got, want)
-        vis = ft.pruned_visits(Nr, Wr, Pr, 1, 79.0, 1.0, 2.0)
+        vis = tw.pruned_visits(Nr, Wr, Pr, 1, 79.0, 1.0, 2.0)
         cs = min(a for a in at if Nr[a] == 30)
         other = max(a for a in at if Nr[a] == 30)
         assert vis[cs] == 30.0 and vis[other] < 30.0
@@ -214,8 +222,8 @@ def test_example_tied_most_visited_child():
 # ---------------------------------------------------------------- 3. whole games against the twin
 
 def run_forced_sim(N, net, R, cap, k, prune, seed, games, slots, starts=None, reset=False, max_steps=400000, **cfg):
-    sim = ft.ForcedSim(board_size=N, games=slots, num_readouts=R, seed=seed, game_id_base=0, game_id_stride=1,
-                       record_capacity_games=games + 8, **cfg)
+    sim = hs.Sim(board_size=N, games=slots, num_readouts=R, seed=seed, game_id_base=0, game_id_stride=1,
+                 record_capacity_games=games + 8, **cfg)
     if starts:
         sim.set_starts(starts)
     if cap:
@@ -254,8 +262,8 @@ def game_set(i):
         starts = tw.random_starts(N, (4, 7, 1), seed=0)
         recs, cnt, allc = run_forced_sim(N, net, R, CAP, k, True, seed, games, slots, starts=starts,
                                          resign_threshold=THR, resign_disable_fraction=0.0)
-        twins = [ft.twin_selfplay_forced(N, net.cb, R, CAP[0], CAP[1], k, True, seed, int(r["game_id"]),
-                                         starts[int(r["game_id"]) % len(starts)], THR, 0.0) for r in recs]
+        twins = [tw.twin_selfplay(N, net.cb, R, seed, int(r["game_id"]), starts[int(r["game_id"]) % len(starts)], THR, 0.0,
+                                  cap=CAP, forced=(k, True)) for r in recs]
         net.close()
         _games[i] = (recs, twins, cnt, allc)
     return _games[i]
@@ -298,7 +306,7 @@ def test_forcing_without_pruning_records_the_raw_rows():
                                      resign_disable_fraction=0.0)
     for rec in recs:
         gid = int(rec["game_id"])
-        o = ft.twin_selfplay_forced(N, net.cb, R, CAP[0], CAP[1], k, False, seed, gid, starts[gid % 3], THR, 0.0)
+        o = tw.twin_selfplay(N, net.cb, R, seed, gid, starts[gid % 3], THR, 0.0, cap=CAP, forced=(k, False))
         assert (rec["moves"] == o["moves"]).all() and bits_equal(rec["pis"], o["raw_pis"]) and bits_equal(rec["qs"], o["qs"])
         assert o["forced_sel"] >= 1 and not o["pruned_rows"].any()
     assert allc["CT_PRUNED_ROWS"] == 0 and allc["CT_FORCED_SEL"] >= 2
@@ -379,5 +387,5 @@ def test_header_declares_the_new_calls_and_keeps_the_abi():
     jl = open(os.path.join(ROOT, "alphago.jl_amd", "julia", "AlphaGoMI.jl")).read()
     for name in NEW_CALLS:
         assert ":%s" % name in jl, name
-    names = ct.counter_names()
+    names = hs.counter_names()
     assert names[-2:] == ["CT_FORCED_SEL", "CT_PRUNED_ROWS"] and names.index("CT_PEAK_NODES") == len(hs.CT) - 1

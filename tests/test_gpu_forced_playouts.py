@@ -1,7 +1,7 @@
 """Forced playouts and policy target pruning on the device (agz_selfplay_set_forced_playouts, agz_tree_pruned_pi,
 DESIGN.md §5i).
 
-Every self-play game must be, bit for bit, the twin's game (tests/forced_twin.py: the reference's loop with the forced
+Every self-play game must be, bit for bit, the twin's game (tests/selfplay_twin.py: the reference's loop with the forced
 root descent in its full searches and the pruned target in their pi rows) on the engine's own forward -- under the
 playout cap, from a table of starts, with drawn symmetries.  The single-tree calls reach the rule with hand-made rows at
 the four register-row widths of the descent.  Off is the engine that never made the call, byte for byte; analysis never
@@ -10,9 +10,8 @@ import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
-import forced_twin as ft
 import orc
-import starts_twin as tw
+import selfplay_twin as tw
 from alphago_jl_amd import symmetry as sy
 from gpu_common import GpuNetForOracle
 from test_hostsim_selfplay import bits_equal
@@ -89,8 +88,8 @@ def test_games_equal_the_twin(N, tower, R, k, games, slots, seed, plies):
     fwd = ag.Engine(board_size=N, tower_height=tower, games=1, num_readouts=8, max_nodes_per_game=16)
     fwd.init_synthetic(0)
     cb = GpuNetForOracle(fwd).cb
-    twins = [ft.twin_selfplay_forced(N, cb, R, CAP[0], CAP[1], k, True, seed, int(r["game_id"]),
-                                     starts[int(r["game_id"]) % len(starts)], THR, 0.0) for r in recs]
+    twins = [tw.twin_selfplay(N, cb, R, seed, int(r["game_id"]), starts[int(r["game_id"]) % len(starts)], THR, 0.0,
+                              cap=CAP, forced=(k, True)) for r in recs]
     check_set(eng, recs, st, twins)
     eng.close()
     fwd.close()
@@ -113,7 +112,7 @@ def test_games_with_random_symmetry_equal_the_twin():
     for r in recs:
         gid = int(r["game_id"])
         net = SymNetForOracle(fwd, seed, gid, sy.RANDOM)
-        twins.append(ft.twin_selfplay_forced(N, net.cb, R, CAP[0], CAP[1], k, True, seed, gid, starts[gid % 3], THR, 0.0))
+        twins.append(tw.twin_selfplay(N, net.cb, R, seed, gid, starts[gid % 3], THR, 0.0, cap=CAP, forced=(k, True)))
     check_set(eng, recs, st, twins)
     eng.close()
     fwd.close()
@@ -157,16 +156,16 @@ def test_single_tree_known_answers(N):
             root, rows = set_rows(eng, N, at, 99.0, n)
             for k in (2.0, 0.0, 16.0):
                 got = eng.tree_pruned_pi(0, root, k)
-                want, changed = ft.pruned_pi(*rows, 1, 99.0, 1.0, k, n <= tau)
+                want, changed = tw.pruned_pi(*rows, 1, 99.0, 1.0, k, n <= tau)
                 assert changed == (k > 0) and bits_equal(got, want), (N, u, n, k)
-            want2, _ = ft.pruned_pi(*rows, 1, 99.0, 1.0, 2.0, n <= tau)
+            want2, _ = tw.pruned_pi(*rows, 1, 99.0, 1.0, 2.0, n <= tau)
             assert want2[u] == 0.0 and abs(float(want2.astype(np.float64).sum()) - 1.0) < 1e-6
         # the forced pick, and the PUCT arg-max with the setting off
-        score, _, scale = ft.action_scores(rows[0], rows[1], rows[2], 1, 99.0, 1.0)
+        score, _, scale = tw.action_scores(rows[0], rows[1], rows[2], 1, 99.0, 1.0)
         assert scale == 10.0
         best = int(np.argmax(score))
         assert best == at[4]
-        assert list(np.flatnonzero(ft.under_forced(2.0, rows[0], rows[2], 99.0))) == [u]
+        assert list(np.flatnonzero(tw.under_forced(2.0, rows[0], rows[2], 99.0))) == [u]
         for k, want_pick, counted in ((2.0, u, 1), (0.0, best, 0)):
             eng.set_forced_playouts(k)
             root, rows = set_rows(eng, N, at, 98.0, tau + 1)
@@ -188,9 +187,9 @@ def test_node_view_pruned_pi():
     for _ in range(5):
         pl.tree_search(8)
     cn = pl.root.child_N
-    want, _ = ft.pruned_pi(cn, pl.root.child_W, pl.root.child_prior, 1, pl.root.N, pl.engine.cfg.c_puct, 2.0, True)
+    want, _ = tw.pruned_pi(cn, pl.root.child_W, pl.root.child_prior, 1, pl.root.N, pl.engine.cfg.c_puct, 2.0, True)
     assert bits_equal(pl.root.pruned_pi(2.0), want)
-    assert bits_equal(pl.root.pruned_pi(0.0), ft.pi_of(cn.astype(np.float64), True))
+    assert bits_equal(pl.root.pruned_pi(0.0), tw.pi_of(cn.astype(np.float64), True))
 
 
 # ---------------------------------------------------------------- off is off
@@ -290,7 +289,6 @@ def host_schedule(nn0):
     weights after every training kept (the method of tests/test_gpu_playout_cap.py::host_schedule)"""
     from test_gpu_playout_cap import arena_pis
     from test_gpu_train_batched import _weights
-    import cap_twin as ct
     c = TRAIN
     num_games, slots = c["num_games"], c["slots"]
     eng = ag.Engine(board_size=c["N"], tower_height=c["TOWER"], games=slots, num_readouts=c["R"], seed=c["SEED"],
@@ -320,7 +318,7 @@ def host_schedule(nn0):
             assert live == min(c["memory"], targets)
             loss = None
             if live >= c["start_after"]:
-                pairs, _ = ct.sample_targets(c["SEED"], i, c["B"], arena_pis(eng), window=live)
+                pairs, _ = tw.sample_targets(c["SEED"], i, c["B"], arena_pis(eng), window=live)
                 g = np.array([a for a, _ in pairs], np.int64)
                 q = np.array([b for _, b in pairs], np.int32)
                 f, pi, z = eng.replay_batch(g, q)
@@ -362,7 +360,7 @@ def test_train_with_forced_playouts_plays_the_twins_games():
                     chk.set_weights(layer, kind, w)
                 loaded[0] = t
 
-        o = ft.twin_selfplay_forced(N, cb, R, CAP[0], CAP[1], k, True, SEED, gid, None, -0.9, 0.05, on_round=on_round)
+        o = tw.twin_selfplay(N, cb, R, SEED, gid, None, -0.9, 0.05, on_round=on_round, cap=CAP, forced=(k, True))
         assert_game_equal(rec, o, gid)
         twins.append(o)
         first = sum(1 for h in ref if h["step"] < start_step[gid] and h["loss"] is not None)
@@ -394,7 +392,7 @@ def test_selfplay_takes_the_keywords():
     for prune in (True, False):
         players = ag.selfplay(env, nn, R, forced_playouts=k, prune_targets=prune, **kw)
         for gid, pl in enumerate(players):
-            o = ft.twin_selfplay_forced(N, cb, R, CAP[0], CAP[1], k, prune, 2, gid, None, -2.0, 0.0)
+            o = tw.twin_selfplay(N, cb, R, 2, gid, None, -2.0, 0.0, cap=CAP, forced=(k, prune))
             assert [ag.to_flat(m, env) for m in pl.moves] == list(o["moves"]) and pl.result == o["result"]
             assert pl.full_search == list(o["full"])
             assert bits_equal(np.stack(pl.searches_pi), o["pis"])

@@ -1,6 +1,6 @@
 """The Gumbel root search on the device (agz_selfplay_set_gumbel, agz_tree_gumbel_pi).
 
-Every self-play game must be, bit for bit, the twin's game (tests/gumbel_twin.py: the reference's loop with Gumbel-top-k
+Every self-play game must be, bit for bit, the twin's game (tests/selfplay_twin.py: the reference's loop with Gumbel-top-k
 candidates, Sequential Halving, the best-s move and the softmax(logit + sigma(q)) row in its full searches) on the
 engine's own forward -- with the playout cap on and off, from a table of starts, with drawn symmetries.  The
 single-tree row call is held to the worked example at the four register-row widths.  Off is the engine that never made
@@ -10,9 +10,8 @@ import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
-import gumbel_twin as gt
 import orc
-import starts_twin as tw
+import selfplay_twin as tw
 from alphago_jl_amd import symmetry as sy
 from gpu_common import GpuNetForOracle
 from test_hostsim_selfplay import bits_equal
@@ -92,8 +91,8 @@ def test_games_equal_the_twin(N, tower, R, m, cap, games, slots, seed, plies):
     fwd.init_synthetic(0)
     cb = GpuNetForOracle(fwd).cb
     r, p = cap if cap else (0, 1.0)
-    twins = [gt.twin_selfplay_gumbel(N, cb, R, r, p, m, 50.0, 1.0, seed, int(rec["game_id"]),
-                                     starts[int(rec["game_id"]) % len(starts)], THR, 0.0) for rec in recs]
+    twins = [tw.twin_selfplay(N, cb, R, seed, int(rec["game_id"]), starts[int(rec["game_id"]) % len(starts)], THR, 0.0,
+                              cap=(r, p), gumbel=(m, 50.0, 1.0)) for rec in recs]
     check_set(eng, recs, st, twins, cap)
     eng.close()
     fwd.close()
@@ -116,8 +115,7 @@ def test_games_with_random_symmetry_equal_the_twin():
     for r in recs:
         gid = int(r["game_id"])
         net = SymNetForOracle(fwd, seed, gid, sy.RANDOM)
-        twins.append(gt.twin_selfplay_gumbel(N, net.cb, R, CAP[0], CAP[1], m, 50.0, 0.5, seed, gid, starts[gid % 3],
-                                             THR, 0.0))
+        twins.append(tw.twin_selfplay(N, net.cb, R, seed, gid, starts[gid % 3], THR, 0.0, cap=CAP, gumbel=(m, 50.0, 0.5)))
     check_set(eng, recs, st, twins, CAP)
     eng.close()
     fwd.close()
@@ -163,7 +161,7 @@ def test_single_tree_worked_row(N):
         root, rows = set_rows(eng, N, at)
         for cs, table in ((0.1, EX_PI), (1.0, None)):
             got = eng.tree_gumbel_pi(0, root, 50.0, cs)
-            want, _ = gt.gumbel_pi(*rows, legal, 1, 50.0, cs)
+            want, _ = tw.gumbel_pi(*rows, legal, 1, 50.0, cs)
             assert bits_equal(got, want), (N, hi, cs)
             if table:
                 assert np.abs(got[list(at)].astype(np.float64) - table).max() < 1e-6
@@ -173,7 +171,7 @@ def test_single_tree_worked_row(N):
             assert (got[rest] == 0).all() and abs(float(got.astype(np.float64).sum()) - 1.0) < 1e-6
         root, rows = set_rows(eng, N, at, to_play=-1)
         got = eng.tree_gumbel_pi(0, root, 50.0, 0.1)
-        want, _ = gt.gumbel_pi(*rows, legal, -1, 50.0, 0.1)
+        want, _ = tw.gumbel_pi(*rows, legal, -1, 50.0, 0.1)
         assert bits_equal(got, want)
         assert np.abs(got[list(at)].astype(np.float64) - EX_PI_MINUS).max() < 1e-6
         # an occupied point is illegal: no mass there, the rest renormalised
@@ -182,7 +180,7 @@ def test_single_tree_worked_row(N):
         legal[1] = 0
         root, rows = set_rows(eng, N, at, board=board)
         got = eng.tree_gumbel_pi(0, root, 50.0, 0.1)
-        want, _ = gt.gumbel_pi(*rows, legal, 1, 50.0, 0.1)
+        want, _ = tw.gumbel_pi(*rows, legal, 1, 50.0, 0.1)
         assert bits_equal(got, want) and got[1] == 0.0 and got[hi] > EX_PI[0]
     assert eng.gumbel_counts() == (0, 0)
     eng.close()
@@ -200,9 +198,9 @@ def test_node_view_gumbel_pi_and_single_trees_do_not_follow_the_setting():
             pl.tree_search(8)
         root = pl.root
         legal = np.ones(26, np.int8)
-        want, _ = gt.gumbel_pi(root.child_N, root.child_W, root.child_prior, legal, 1, 50.0, 1.0)
+        want, _ = tw.gumbel_pi(root.child_N, root.child_W, root.child_prior, legal, 1, 50.0, 1.0)
         assert bits_equal(root.gumbel_pi(), want)
-        want, _ = gt.gumbel_pi(root.child_N, root.child_W, root.child_prior, legal, 1, 20.0, 0.25)
+        want, _ = tw.gumbel_pi(root.child_N, root.child_W, root.child_prior, legal, 1, 20.0, 0.25)
         assert bits_equal(root.gumbel_pi(20.0, 0.25), want)
         out.append((root.child_N.copy(), root.child_W.copy(), pl.engine.gumbel_counts()))
     assert bits_equal(out[0][0], out[1][0]) and bits_equal(out[0][1], out[1][1])     # a single tree is plain PUCT
@@ -322,7 +320,6 @@ def host_schedule(nn0):
     the weights after every training kept (the method of tests/test_gpu_playout_cap.py::host_schedule)"""
     from test_gpu_playout_cap import arena_pis
     from test_gpu_train_batched import _weights
-    import cap_twin as ct
     c = TRAIN
     num_games, slots = c["num_games"], c["slots"]
     eng = ag.Engine(board_size=c["N"], tower_height=c["TOWER"], games=slots, num_readouts=c["R"], seed=c["SEED"],
@@ -352,7 +349,7 @@ def host_schedule(nn0):
             assert live == min(c["memory"], targets)
             loss = None
             if live >= c["start_after"]:
-                pairs, _ = ct.sample_targets(c["SEED"], i, c["B"], arena_pis(eng), window=live)
+                pairs, _ = tw.sample_targets(c["SEED"], i, c["B"], arena_pis(eng), window=live)
                 g = np.array([a for a, _ in pairs], np.int64)
                 q = np.array([b for _, b in pairs], np.int32)
                 f, pi, z = eng.replay_batch(g, q)
@@ -394,8 +391,7 @@ def test_train_with_gumbel_plays_the_twins_games():
                     chk.set_weights(layer, kind, w)
                 loaded[0] = t
 
-        o = gt.twin_selfplay_gumbel(N, cb, R, CAP[0], CAP[1], m, 50.0, 1.0, SEED, gid, None, -0.9, 0.05,
-                                    on_round=on_round)
+        o = tw.twin_selfplay(N, cb, R, SEED, gid, None, -0.9, 0.05, on_round=on_round, cap=CAP, gumbel=(m, 50.0, 1.0))
         assert_game_equal(rec, o, gid)
         twins.append(o)
         first = sum(1 for h in ref if h["step"] < start_step[gid] and h["loss"] is not None)
@@ -426,7 +422,7 @@ def test_selfplay_takes_the_keywords():
     cb = GpuNetForOracle(nn.engine).cb
     players = ag.selfplay(env, nn, R, gumbel=m, gumbel_c_visit=20.0, gumbel_c_scale=0.5, **kw)
     for gid, pl in enumerate(players):
-        o = gt.twin_selfplay_gumbel(N, cb, R, CAP[0], CAP[1], m, 20.0, 0.5, 2, gid, None, -2.0, 0.0)
+        o = tw.twin_selfplay(N, cb, R, 2, gid, None, -2.0, 0.0, cap=CAP, gumbel=(m, 20.0, 0.5))
         assert [ag.to_flat(mv, env) for mv in pl.moves] == list(o["moves"]) and pl.result == o["result"]
         assert pl.full_search == list(o["full"])
         assert bits_equal(np.stack(pl.searches_pi), o["pis"])

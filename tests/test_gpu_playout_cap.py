@@ -1,7 +1,7 @@
 """Playout cap randomization on the device (agz_selfplay_set_playout_cap, agz_replay_set_targets_only).
 
-With the cap on, every self-play game must be, bit for bit, the twin's game (tests/cap_twin.py: the reference's loop with
-the coin u01(draw(seed, game, n, site 11, 0)) < p before each search) on the engine's own forward: full plies with noise,
+With the cap on, every self-play game must be, bit for bit, the twin's game (tests/selfplay_twin.py: the reference's loop
+with the coin u01(draw(seed, game, n, site 11, 0)) < p before each search) on the engine's own forward: full plies with noise,
 R readouts and their pi, fast plies without noise, r readouts and an all-zero pi row.  Off -- r = 0, or every search
 full -- is today's engine byte for byte.  A targets-only arena counts, keeps and samples the non-zero rows only, as the
 numpy restatement of the sampler says; train(..., playout_cap=...) is that schedule."""
@@ -9,9 +9,8 @@ import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
-import cap_twin as ct
 import orc
-import starts_twin as tw
+import selfplay_twin as tw
 from alphago_jl_amd import symmetry as sy
 from gpu_common import GpuNetForOracle, pos_soa
 from test_hostsim_selfplay import bits_equal
@@ -65,7 +64,7 @@ def check_against_twins(eng, recs, st, twin_of, seed, p, starts=None):
         o = twin_of(gid)
         assert_cap_game_equal(r, o, gid)
         n0 = starts[gid % len(starts)].n if starts else 0
-        assert (o["full"] == ct.pattern(seed, gid, n0, o["num_moves"], p)).all()
+        assert (o["full"] == tw.pattern(seed, gid, n0, o["num_moves"], p)).all()
         twins.append(o)
     assert_mixed(twins)
     nfull, nfast = sum(int(o["full"].sum()) for o in twins), sum(int((~o["full"]).sum()) for o in twins)
@@ -114,7 +113,7 @@ def test_games_with_the_cap_equal_the_twin(N, tower, R, r, p, games, slots, seed
     fwd = ag.Engine(board_size=N, tower_height=tower, games=1, num_readouts=8, max_nodes_per_game=16)
     fwd.init_synthetic(0)
     cb = GpuNetForOracle(fwd).cb
-    check_against_twins(eng, recs, st, lambda gid: ct.twin_selfplay_cap(N, cb, R, r, p, seed, gid, None, *resign), seed, p)
+    check_against_twins(eng, recs, st, lambda gid: tw.twin_selfplay(N, cb, R, seed, gid, None, *resign, cap=(r, p)), seed, p)
     eng.close()
     fwd.close()
 
@@ -132,8 +131,8 @@ def test_games_with_the_cap_from_a_starts_table_equal_the_twin():
     fwd = ag.Engine(board_size=N, tower_height=tower, games=1, num_readouts=8, max_nodes_per_game=16)
     fwd.init_synthetic(0)
     cb = GpuNetForOracle(fwd).cb
-    check_against_twins(eng, recs, st, lambda gid: ct.twin_selfplay_cap(N, cb, R, r, p, seed, gid, starts[gid % 6],
-                                                                       -2.0, 0.0), seed, p, starts)
+    check_against_twins(eng, recs, st, lambda gid: tw.twin_selfplay(N, cb, R, seed, gid, starts[gid % 6], -2.0, 0.0,
+                                                                   cap=(r, p)), seed, p, starts)
     eng.close()
     fwd.close()
 
@@ -150,7 +149,7 @@ def test_games_with_the_cap_and_random_symmetry_equal_the_twin():
 
     def twin_of(gid):
         net = SymNetForOracle(fwd, seed, gid, sy.RANDOM)
-        o = ct.twin_selfplay_cap(N, net.cb, R, r, p, seed, gid, None, -0.9, 0.05)
+        o = tw.twin_selfplay(N, net.cb, R, seed, gid, None, -0.9, 0.05, cap=(r, p))
         seen.update(net.syms)
         return o
 
@@ -190,7 +189,7 @@ def test_noise_only_on_full_searches():
             root = eng.tree_root(0)
             got = eng.node_floats(0, root, 2)
             want, _ = fwd.forward(*pos_soa([pos]))
-            full = bool(ct.coin_full(seed, gid, n, p))
+            full = bool(tw.coin_full(seed, gid, n, p))
             seen[n].add(full)
             print(f"game {gid}, n = {n}: {'full' if full else 'fast'}, max |prior - net| "
                   f"{float(np.abs(got - want[0]).max()):.3e}")
@@ -265,7 +264,7 @@ def check_samples(e, live_want, calls_and_B):
         feats, pi, z, game, ply = e.replay_sample(B, call, sym)
         torch.cuda.synchronize()
         e.sync()
-        want, Lw = ct.sample_targets(e.cfg.seed, call, B, pis, window=live_want)
+        want, Lw = tw.sample_targets(e.cfg.seed, call, B, pis, window=live_want)
         assert Lw == live_want
         g = np.array([a for a, _ in want], np.int64)
         q = np.array([b for _, b in want], np.int32)
@@ -382,7 +381,7 @@ def host_schedule(nn0):
             assert live == min(c["memory"], targets)
             loss = None
             if live >= c["start_after"]:
-                pairs, _ = ct.sample_targets(c["SEED"], i, c["B"], arena_pis(eng), window=live)
+                pairs, _ = tw.sample_targets(c["SEED"], i, c["B"], arena_pis(eng), window=live)
                 g = np.array([a for a, _ in pairs], np.int64)
                 q = np.array([b for _, b in pairs], np.int32)
                 f, pi, z = eng.replay_batch(g, q)
@@ -424,7 +423,7 @@ def test_train_with_the_cap_plays_the_twins_games_and_counts_targets():
                     chk.set_weights(layer, kind, w)
                 loaded[0] = t
 
-        o = ct.twin_selfplay_cap(N, cb, R, c["r"], c["p"], SEED, gid, None, -0.9, 0.05, on_round=on_round)
+        o = tw.twin_selfplay(N, cb, R, SEED, gid, None, -0.9, 0.05, on_round=on_round, cap=(c["r"], c["p"]))
         assert_cap_game_equal(rec, o, gid)
         twins.append(o)
         first = sum(1 for h in ref if h["step"] < start_step[gid] and h["loss"] is not None)
@@ -459,7 +458,7 @@ def test_selfplay_takes_the_cap_and_extract_data_drops_fast_plies():
                           resign_disable_fraction=0.0)
     cb = GpuNetForOracle(nn.engine).cb
     for gid, pl in enumerate(players):
-        o = ct.twin_selfplay_cap(N, cb, R, r, p, 2, gid, None, -2.0, 0.0)
+        o = tw.twin_selfplay(N, cb, R, 2, gid, None, -2.0, 0.0, cap=(r, p))
         assert [ag.to_flat(m, env) for m in pl.moves] == list(o["moves"]) and pl.result == o["result"]
         assert pl.full_search == list(o["full"])
         pos, pis, res = ag.extract_data(pl)

@@ -1,6 +1,6 @@
 """Start positions for self-play, the arena and replay on the device (agz_selfplay_set_starts).
 
-Game gid of a run with a table of S entries must be, bit for bit, the twin's game (tests/starts_twin.py: the reference's
+Game gid of a run with a table of S entries must be, bit for bit, the twin's game (tests/selfplay_twin.py: the reference's
 loops with initialize_game!(player, start)) from entry gid mod S -- arena game g from entry g mod S -- and every
 consumer of its record must rebuild or_get_feats of the twin's positions.  Refusals leave the table in force."""
 import numpy as np
@@ -8,7 +8,7 @@ import pytest
 
 import alphago_jl_amd as ag
 import orc
-import starts_twin as tw
+import selfplay_twin as tw
 from alphago_jl_amd import symmetry
 from gpu_common import GpuNetForOracle
 from test_hostsim_selfplay import OracleNet, bits_equal

@@ -1,6 +1,6 @@
 """The Gumbel root search (agz_selfplay_set_gumbel) on the host simulator: Gumbel-top-k candidates at the
 root of a full self-play search, Sequential Halving over them, the survivor with the largest s(a) as the move and
-softmax(logit + sigma(q)) as the recorded row.  tests/gumbel_twin.py restates all of it over the oracle's primitives.
+softmax(logit + sigma(q)) as the recorded row.  tests/selfplay_twin.py restates all of it over the oracle's primitives.
 Here: off is the cap simulator byte for byte, the schedules, the worked row, hand rows for the root pick, whole games
 against the twin bit for bit, and the properties of the rows.  CPU only."""
 import ctypes as C
@@ -12,12 +12,9 @@ import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
-import cap_twin as ct
-import forced_twin as ft
-import gumbel_twin as gt
 import hs
 import orc
-import starts_twin as tw
+import selfplay_twin as tw
 from test_hostsim_selfplay import OracleNet, bits_equal
 from test_playout_cap import run_cap_sim
 
@@ -29,8 +26,8 @@ THR = -0.1
 
 def run_gumbel_sim(N, net, R, cap, m, seed, games, slots, starts=None, reset=False, c_visit=50.0, c_scale=1.0,
                    max_steps=400000, **cfg):
-    sim = gt.GumbelSim(board_size=N, games=slots, num_readouts=R, seed=seed, game_id_base=0, game_id_stride=1,
-                       record_capacity_games=games + 8, **cfg)
+    sim = hs.Sim(board_size=N, games=slots, num_readouts=R, seed=seed, game_id_base=0, game_id_stride=1,
+                 record_capacity_games=games + 8, **cfg)
     if starts:
         sim.set_starts(starts)
     if cap:
@@ -74,7 +71,7 @@ def test_off_and_reset_are_the_cap_twin_and_simulator(cap):
         assert allc == ran[0][2] and gc == (0, 0)
     for rec in want:                                    # ... and the cap twin's
         gid = int(rec["game_id"])
-        o = ct.twin_selfplay_cap(N, net.cb, R, r if cap else 4, p, seed, gid, starts[gid % 3], THR, 0.0)
+        o = tw.twin_selfplay(N, net.cb, R, seed, gid, starts[gid % 3], THR, 0.0, cap=(r if cap else 4, p))
         assert (rec["moves"] == o["moves"]).all() and bits_equal(rec["qs"], o["qs"])
         assert bits_equal(np.ascontiguousarray(rec["pis"], np.float32).reshape(-1, N * N + 1), o["pis"])
     net.close()
@@ -92,19 +89,19 @@ SCHEDULES = [
 
 @pytest.mark.parametrize("n,m0,want", SCHEDULES)
 def test_schedules(n, m0, want):
-    sim = gt.GumbelSim(board_size=5, games=1, num_readouts=8, seed=1)
-    assert sim.schedule(n, m0) == want == gt.schedule(n, m0)
+    sim = hs.Sim(board_size=5, games=1, num_readouts=8, seed=1)
+    assert sim.schedule(n, m0) == want == tw.schedule(n, m0)
     assert sum(q for _, q in want) == n
     sim.close()
 
 
 def test_schedule_of_one_candidate_and_small_budgets():
-    sim = gt.GumbelSim(board_size=5, games=1, num_readouts=8, seed=1)
-    assert sim.schedule(16, 1) == [(1, 16)] == gt.schedule(16, 1)
+    sim = hs.Sim(board_size=5, games=1, num_readouts=8, seed=1)
+    assert sim.schedule(16, 1) == [(1, 16)] == tw.schedule(16, 1)
     for n in (1, 2, 3, 7, 16, 33):
         for m0 in range(1, 17):
             s = sim.schedule(n, m0)
-            assert s == gt.schedule(n, m0) and sum(q for _, q in s) == n
+            assert s == tw.schedule(n, m0) and sum(q for _, q in s) == n
     sim.close()
 
 
@@ -113,7 +110,7 @@ def test_schedule_of_a_running_search(R, m):
     """the phase ends and survivor counts the slot's state goes through in the first search of a game"""
     N = 5
     net = OracleNet(N, 1, seed=0)
-    sim = gt.GumbelSim(board_size=N, games=1, num_readouts=R, seed=4, resign_threshold=-2.0, resign_disable_fraction=0.0)
+    sim = hs.Sim(board_size=N, games=1, num_readouts=R, seed=4, resign_threshold=-2.0, resign_disable_fraction=0.0)
     sim.set_gumbel(m)
     sim.start(1)
     seen = []
@@ -125,7 +122,7 @@ def test_schedule_of_a_running_search(R, m):
         if st.n > 0:
             break
     want, end = [], 1.0                                  # the pre-expansion is the root's first visit
-    for mp, q in gt.schedule(R, m):
+    for mp, q in tw.schedule(R, m):
         end += q
         want.append((mp, end))
     assert seen == want
@@ -146,7 +143,7 @@ EX_PI_MINUS = [0.106663, 0.667399, 0.023713, 0.166850, 0.021333, 0.014043]
 
 def example_tree(rows=(EX_N, EX_W, EX_P), at=(0, 1, 2, 3, 4, 5), to_play=1, board=None, last_move=-1, N=5, sim=None):
     """a single tree on the simulator whose expanded root has the given child rows at actions `at`, zero elsewhere"""
-    sim = sim or gt.GumbelSim(board_size=N, games=1, num_readouts=8, seed=1, c_puct=1.0)
+    sim = sim or hs.Sim(board_size=N, games=1, num_readouts=8, seed=1, c_puct=1.0)
     b = np.zeros(N * N, np.int8) if board is None else board
     root = sim.tree_init(0, b, n=sim.tau + 1, to_play=to_play, last_move=last_move)
     st, leaf = sim.op(hs.TOP_SELECT, node=root)
@@ -173,7 +170,7 @@ def test_worked_row(at):
     sim, root = example_tree(at=at)
     at = list(at)
     got = sim.gumbel_pi(0, root, 50.0, 0.1)
-    want, x = gt.gumbel_pi(*rows_of(sim, root), legal_of(sim, root), 1, 50.0, 0.1)
+    want, x = tw.gumbel_pi(*rows_of(sim, root), legal_of(sim, root), 1, 50.0, 0.1)
     assert bits_equal(got, want)
     assert np.abs(x[at] - EX_X).max() < 1e-6
     assert np.abs(got[at].astype(np.float64) - EX_PI).max() < 1e-6
@@ -182,7 +179,7 @@ def test_worked_row(at):
     assert abs(float(got.astype(np.float64).sum()) - 1.0) < 1e-6
     # c_scale = 1.0
     got1 = sim.gumbel_pi(0, root, 50.0, 1.0)
-    want1, _ = gt.gumbel_pi(*rows_of(sim, root), legal_of(sim, root), 1, 50.0, 1.0)
+    want1, _ = tw.gumbel_pi(*rows_of(sim, root), legal_of(sim, root), 1, 50.0, 1.0)
     assert bits_equal(got1, want1)
     assert abs(float(got1[at[0]]) - 0.783795) < 1e-6 and abs(float(got1[at[5]]) - 0.00501063) < 1e-6
     sim.close()
@@ -191,7 +188,7 @@ def test_worked_row(at):
 def test_worked_row_white_to_play():
     sim, root = example_tree(to_play=-1)
     got = sim.gumbel_pi(0, root, 50.0, 0.1)
-    want, _ = gt.gumbel_pi(*rows_of(sim, root), legal_of(sim, root), -1, 50.0, 0.1)
+    want, _ = tw.gumbel_pi(*rows_of(sim, root), legal_of(sim, root), -1, 50.0, 0.1)
     assert bits_equal(got, want)
     assert np.abs(got[:6].astype(np.float64) - EX_PI_MINUS).max() < 1e-6
     sim.close()
@@ -204,7 +201,7 @@ def test_worked_row_illegal_action_and_zero_prior():
     lg = legal_of(sim, root)
     assert lg[2] == 0 and lg[[0, 1, 3, 4, 5]].all()
     got = sim.gumbel_pi(0, root, 50.0, 0.1)
-    want, _ = gt.gumbel_pi(*rows_of(sim, root), lg, 1, 50.0, 0.1)
+    want, _ = tw.gumbel_pi(*rows_of(sim, root), lg, 1, 50.0, 0.1)
     assert bits_equal(got, want) and got[2] == 0.0
     keep = [0, 1, 3, 4, 5]
     renorm = np.array(EX_PI)[keep] / np.array(EX_PI)[keep].sum()
@@ -215,7 +212,7 @@ def test_worked_row_illegal_action_and_zero_prior():
     P0[1] = 0.0
     sim, root = example_tree(rows=(EX_N, EX_W, P0))
     got = sim.gumbel_pi(0, root, 50.0, 0.1)
-    want, _ = gt.gumbel_pi(*rows_of(sim, root), legal_of(sim, root), 1, 50.0, 0.1)
+    want, _ = tw.gumbel_pi(*rows_of(sim, root), legal_of(sim, root), 1, 50.0, 0.1)
     assert bits_equal(got, want) and got[1] == 0.0
     keep = [0, 2, 3, 4, 5]
     renorm = np.array(EX_PI)[keep] / np.array(EX_PI)[keep].sum()
@@ -281,7 +278,7 @@ def test_below_the_root_is_puct():
     pick = int(np.flatnonzero(sim.children(0, child) == leaf)[0])
     Nc, Wc, Pc = [sim.row(0, child, f).copy() for f in range(3)]
     Nc[pick] -= 1                                                  # the rows the descent saw
-    score, _, scale = ft.action_scores(Nc, Wc, Pc, sim.meta(0, child).to_play, 99.0, 1.0)
+    score, _, scale = tw.action_scores(Nc, Wc, Pc, sim.meta(0, child).to_play, 99.0, 1.0)
     lg = sim.legal(0, child) != 0
     assert not lg[3] and scale == 10.0
     best = np.flatnonzero(lg & (score == score[lg].max()))
@@ -314,8 +311,8 @@ def game_set(i):
         recs, cnt, allc, gc = run_gumbel_sim(N, net, R, cap, m, seed, games, slots, starts=starts,
                                              resign_threshold=THR, resign_disable_fraction=0.0)
         r, p = cap if cap else (0, 1.0)
-        twins = [gt.twin_selfplay_gumbel(N, net.cb, R, r, p, m, 50.0, 1.0, seed, int(rec["game_id"]),
-                                         starts[int(rec["game_id"]) % len(starts)], THR, 0.0) for rec in recs]
+        twins = [tw.twin_selfplay(N, net.cb, R, seed, int(rec["game_id"]), starts[int(rec["game_id"]) % len(starts)], THR,
+                                  0.0, cap=(r, p), gumbel=(m, 50.0, 1.0)) for rec in recs]
         net.close()
         _games[i] = (recs, twins, cnt, allc, gc)
     return _games[i]
@@ -400,7 +397,7 @@ def test_header_declares_the_new_calls_and_keeps_the_abi():
     draws = open(os.path.join(ROOT, "include", "agz_draws.h")).read()
     assert re.search(r"#define AGZ_SITE_GUMBEL 12u", draws) and re.search(r"#define AGZ_SITE_PLAYOUT_CAP 11u", draws)
     assert C.sizeof(ag._lib.Config) == 112 and C.sizeof(ag._lib.GameHeader) == 32 and C.sizeof(hs.GameState) == 112
-    assert C.sizeof(gt.GumbelStateC) == 56
+    assert C.sizeof(hs.GumbelStateC) == 56
     lib = ag.load()
     assert lib.agz_version() == 103
     for name in NEW_CALLS:

@@ -5,9 +5,6 @@ the bits of every float."""
 import ctypes as C
 import os
 import re
-import shlex
-import subprocess
-import tempfile
 import zlib
 
 import numpy as np
@@ -69,67 +66,9 @@ def test_lines_off_is_the_plain_call():
 
 # ---------------------------------------------------------------- 3. the wave templates on the host simulator
 
-_hl = None
-
-
-def lines_lib():
-    """tests/hostsim/hostsim_lines.cpp (hostsim.cpp + an entry for node_lines), built with the flags of the Makefile
-    next to it"""
-    global _hl
-    if _hl is not None:
-        return _hl
-    d = os.path.join(ROOT, "tests", "hostsim")
-    recipe = [ln for ln in open(os.path.join(d, "Makefile")).read().split("\n") if ln.startswith("\tg++")]
-    assert len(recipe) == 1
-    flags = [t for t in shlex.split(recipe[0])[1:] if t not in ("$<", "-o", "$@")]
-    src = os.path.join(d, "hostsim_lines.cpp")
-    deps = [src, os.path.join(d, "hostsim.cpp")] + [os.path.join(ROOT, "alphago.jl_amd", "csrc", h) for h in
-                                                    ("agz_search.h", "agz_state.h", "agz_layout.h")]
-    deps += [os.path.join(ROOT, "include", h) for h in ("agz.h", "agz_draws.h")]
-    out = os.path.join(d, "libhostsim_lines.so")
-    if not os.access(d, os.W_OK):
-        out = os.path.join(tempfile.mkdtemp(prefix="hostsim_lines_"), "libhostsim_lines.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in deps):
-        subprocess.run(["g++"] + flags + [src, "-o", out], check=True)
-    L = C.CDLL(out)
-    L.hs_node_lines.restype = None
-    L.hs_node_lines.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ag._lib.Line),
-                                C.POINTER(C.c_int16), C.POINTER(C.c_float)]
-    _hl = L
-    return L
-
-
-class LinesSim(hs.Sim):
-    """hs.Sim on the library that also has hs_node_lines"""
-
-    def __init__(self, **cfg):
-        hs.lib()                                        # the prototypes of the simulator's own entries
-        super().__init__(**cfg)
-        self.close()
-        self.L = self._with_prototypes(lines_lib())
-        self.h = self.L.hs_create(C.byref(self.cfg))
-
-    @staticmethod
-    def _with_prototypes(L):
-        base = hs.lib()
-        for name in dir(base):
-            if name.startswith("hs_") and name != "hs_node_lines":
-                fn, src = getattr(L, name), getattr(base, name)
-                fn.restype, fn.argtypes = src.restype, src.argtypes
-        return L
-
-    def lines(self, node, K, D, mv, g=0):
-        ln = (ag._lib.Line * K)()
-        pv = np.full((K, D), 7, np.int16)               # (junk: every entry has to be written)
-        pvn = np.full((K, D), 7, np.float32)
-        self.L.hs_node_lines(self.h, g, node, K, D, mv, ln, pv.ctypes.data_as(C.POINTER(C.c_int16)), hs.pf(pvn))
-        out = {f: np.array([getattr(x, f) for x in ln], np.int32 if f in ("move", "pv_len") else np.float32)
-               for f in ("move", "pv_len", "N", "W", "prior", "end_W")}
-        out.update(pv=pv, pv_N=pvn)
-        return out
-
-    def twin(self, node, K, D, mv, g=0):
-        return lines_twin.walk(lambda n, f: self.row(g, n, f).copy(), lambda n: self.children(g, n).copy(), node, K, D, mv)
+def twin(sim, node, K, D, mv, g=0):
+    """lines_twin.walk over the rows of the simulator's tree"""
+    return lines_twin.walk(lambda n, f: sim.row(g, n, f).copy(), lambda n: sim.children(g, n).copy(), node, K, D, mv)
 
 
 def crc_net(A):
@@ -168,7 +107,7 @@ def test_node_lines_on_searched_trees_equal_the_twin():
     roots = first_pv = ties = 0
     full_d4, full_d16, longest = 0, 0, 0
     for seed in range(6):
-        sim = LinesSim(board_size=9, num_readouts=200, two_player_mode=1, seed=seed, games=1)
+        sim = hs.Sim(board_size=9, num_readouts=200, two_player_mode=1, seed=seed, games=1)
         net = crc_net(sim.A)
         sim.tree_init(0, np.zeros(sim.P, np.int8))
         sim.L.hs_game_set(sim.h, 0, 0, float(seed))
@@ -178,11 +117,11 @@ def test_node_lines_on_searched_trees_equal_the_twin():
             t16 = None
             for D in (16, 4):
                 for mv in (1, 2):
-                    got, want = sim.lines(root, K, D, mv), sim.twin(root, K, D, mv)
+                    got, want = sim.lines(root, K, D, mv), twin(sim, root, K, D, mv)
                     assert lines_twin.same(got, want) is None, (seed, ply, D, mv, lines_twin.same(got, want))
                     child = int(sim.children(0, root)[want["move"][0]])
                     assert child >= 0
-                    g2, w2 = sim.lines(child, K, D, mv), sim.twin(child, K, D, mv)
+                    g2, w2 = sim.lines(child, K, D, mv), twin(sim, child, K, D, mv)
                     assert lines_twin.same(g2, w2) is None, (seed, ply, D, mv, "child", lines_twin.same(g2, w2))
                     if mv == 1 and D == 16:
                         t16 = want
@@ -210,7 +149,7 @@ def test_node_lines_on_searched_trees_equal_the_twin():
 
 def hand_tree():
     """a 5x5 root with real child nodes under actions 3, 7, 11 and 20, and a grandchild under (7, 2); every row zero"""
-    sim = LinesSim(board_size=5, num_readouts=8, two_player_mode=1, seed=0, games=1)
+    sim = hs.Sim(board_size=5, num_readouts=8, two_player_mode=1, seed=0, games=1)
     root = sim.tree_init(0, np.zeros(sim.P, np.int8))
     kids = {}
     for a in (3, 7, 11, 20):
@@ -226,7 +165,7 @@ def hand_tree():
 
 
 def both(sim, node, K, D, mv):
-    got, want = sim.lines(node, K, D, mv), sim.twin(node, K, D, mv)
+    got, want = sim.lines(node, K, D, mv), twin(sim, node, K, D, mv)
     assert lines_twin.same(got, want) is None, lines_twin.same(got, want)
     return got
 
@@ -286,7 +225,7 @@ def test_node_lines_on_hand_written_rows():
 def test_node_lines_on_every_row_width(N):
     """R = ceil(A / 64) entries per lane slot is a template parameter: 1 (5x5), 3 (13x13) and 6 (19x19) besides the 2 of
     9x9, on random rows over real child nodes"""
-    sim = LinesSim(board_size=N, num_readouts=8, two_player_mode=1, seed=0, games=1, max_nodes_per_game=64)
+    sim = hs.Sim(board_size=N, num_readouts=8, two_player_mode=1, seed=0, games=1, max_nodes_per_game=64)
     root = sim.tree_init(0, np.zeros(sim.P, np.int8))
     rng = np.random.RandomState(N)
     nodes = [root]

@@ -1,7 +1,7 @@
 """Playout cap randomization (agz_selfplay_set_playout_cap) on the host simulator: before the search of the root of ply
 n a self-play game draws full = u01(draw(seed, game, n, site 11, 0)) < p; a full move is today's move (noise, R readouts,
 pi recorded), a fast one has no noise, r readouts and an all-zero pi row.  Games are held bit for bit to the twin of
-tests/cap_twin.py; the numpy restatement of the targets-only replay sampler is held to a brute-force enumeration.
+tests/selfplay_twin.py; the numpy restatement of the targets-only replay sampler is held to a brute-force enumeration.
 CPU only."""
 import ctypes as C
 import inspect
@@ -12,9 +12,9 @@ import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
-import cap_twin as ct
+import hs
 import orc
-import starts_twin as tw
+import selfplay_twin as tw
 from test_hostsim_selfplay import OracleNet, bits_equal, oracle_game, run_engine
 
 L = orc.lib()
@@ -23,8 +23,8 @@ NO_RESIGN = dict(resign_threshold=-2.0, resign_disable_fraction=0.0)     # every
 
 
 def run_cap_sim(N, net, R, r, p, seed, games, slots, starts=None, max_steps=400000, **cfg):
-    sim = ct.CapSim(board_size=N, games=slots, num_readouts=R, seed=seed, game_id_base=0, game_id_stride=1,
-                    record_capacity_games=games + 8, **cfg)
+    sim = hs.Sim(board_size=N, games=slots, num_readouts=R, seed=seed, game_id_base=0, game_id_stride=1,
+                 record_capacity_games=games + 8, **cfg)
     if starts:
         sim.set_starts(starts)
     sim.set_playout_cap(r, p)
@@ -70,7 +70,7 @@ def test_twin_at_p_1_is_or_selfplay_ex(N, R, games):
     net = OracleNet(N, 1, seed=0)
     for gid in range(games):
         o = oracle_game(N, net, R, 3, gid, -0.9, 0.05)
-        t = ct.twin_selfplay_cap(N, net.cb, R, 4, 1.0, 3, gid, None, -0.9, 0.05)
+        t = tw.twin_selfplay(N, net.cb, R, 3, gid, None, -0.9, 0.05, cap=(4, 1.0))
         assert t["full"].all() and t["searched_full"].all()
         assert t["num_moves"] == o["num_moves"] and (t["moves"] == o["moves"][: t["num_moves"]]).all()
         assert t["result"] == o["result"] and t["evals"] == o["evals"]
@@ -84,12 +84,12 @@ def test_twin_coin_is_the_stated_draw():
     hdr = open(os.path.join(ROOT, "include", "agz_draws.h")).read()
     assert re.search(r"#define AGZ_SITE_PLAYOUT_CAP 11u\b", hdr)
     for seed, game, n in ((0, 0, 0), (5, 17, 33), (2 ** 40 + 3, 2 ** 33, 80)):
-        bits = L.or_draw_u64(seed, game, n, ct.SITE_PLAYOUT_CAP, 0)
+        bits = L.or_draw_u64(seed, game, n, tw.SITE_PLAYOUT_CAP, 0)
         u = ((bits >> 11) + 0.5) / 9007199254740992.0
         for p in (0.0, 0.25, 0.5, 1.0):
-            assert ct.coin_full(seed, game, n, p) == (u < p)
-    assert not any(ct.coin_full(1, g, n, 0.0) for g in range(4) for n in range(20))
-    assert all(ct.coin_full(1, g, n, 1.0) for g in range(4) for n in range(20))
+            assert tw.coin_full(seed, game, n, p) == (u < p)
+    assert not any(tw.coin_full(1, g, n, 0.0) for g in range(4) for n in range(20))
+    assert all(tw.coin_full(1, g, n, 1.0) for g in range(4) for n in range(20))
 
 
 # ---------------------------------------------------------------- the simulator under the cap is the twin
@@ -109,10 +109,10 @@ def test_sim_with_the_cap_equals_the_twin(N, R, r, p, seed, games, slots):
     twins, evals = [], 0
     for rec in recs:
         gid = int(rec["game_id"])
-        o = ct.twin_selfplay_cap(N, net.cb, R, r, p, seed, gid, None, -2.0, 0.0)
+        o = tw.twin_selfplay(N, net.cb, R, seed, gid, None, -2.0, 0.0, cap=(r, p))
         assert_cap_game_equal(rec, o, gid)
-        assert (o["full"] == ct.pattern(seed, gid, 0, o["num_moves"], p)).all()
-        assert ((np.asarray(rec["pis"]) != 0).any(axis=1) == ct.pattern(seed, gid, 0, rec["num_moves"], p)).all()
+        assert (o["full"] == tw.pattern(seed, gid, 0, o["num_moves"], p)).all()
+        assert ((np.asarray(rec["pis"]) != 0).any(axis=1) == tw.pattern(seed, gid, 0, rec["num_moves"], p)).all()
         twins.append(o)
         evals += o["evals"]
     assert_mixed(twins)
@@ -133,11 +133,11 @@ def test_sim_with_the_cap_from_a_start_and_with_resignation():
     for rec in recs:
         gid = int(rec["game_id"])
         st = starts[gid % len(starts)]
-        o = ct.twin_selfplay_cap(N, net.cb, R, r, p, seed, gid, st, thr, 0.0)
+        o = tw.twin_selfplay(N, net.cb, R, seed, gid, st, thr, 0.0, cap=(r, p))
         assert o["start_n"] == st.n
         assert len(o["searched_full"]) == o["num_moves"] + o["was_resign"]
         assert_cap_game_equal(rec, o, gid)
-        assert (o["full"] == ct.pattern(seed, gid, st.n, o["num_moves"], p)).all()
+        assert (o["full"] == tw.pattern(seed, gid, st.n, o["num_moves"], p)).all()
         twins.append(o)
     assert_mixed(twins)
     assert {o["was_resign"] for o in twins} == {0, 1}, "games end both ways"
@@ -180,20 +180,20 @@ def test_sampler_restatement_against_brute_force():
         games.append(pis)
     games[3][:] = 0.0
     brute = [(g, k) for g, pis in enumerate(games) for k in range(len(pis)) if pis[k].any()]
-    assert ct.target_entries(games) == brute and 3 <= len(brute) < sum(len(g) for g in games)
+    assert tw.target_entries(games) == brute and 3 <= len(brute) < sum(len(g) for g in games)
     assert all(g != 3 and g != 1 for g, _ in brute)
     for window in (None, len(brute), len(brute) - 2, 2, 1):
         live = brute if window is None else brute[len(brute) - window:]
         seen = set()
         for call in range(200):
             for B in (1, min(2, len(live)), len(live)):
-                got, Lw = ct.sample_targets(7, call, B, games, window)
+                got, Lw = tw.sample_targets(7, call, B, games, window)
                 assert Lw == len(live) and len(got) == B and len(set(got)) == B
                 assert set(got) <= set(live)
                 if B == len(live):
                     assert set(got) == set(live)
                 # entry e is the e-th live target: recompute the map from the raw Floyd entries
-                ent = ct.floyd_entries(7, call, B, len(live))
+                ent = tw.floyd_entries(7, call, B, len(live))
                 assert got == [live[e] for e in ent]
                 seen |= set(got)
         assert seen == set(live)
@@ -205,7 +205,7 @@ def test_sampler_restatement_against_brute_force():
             bits = L.or_draw_u64(7, call, 0, 9, j)
             t = ((bits >> 32) * (j + 1)) >> 32
             out.append(j if t in out else t)
-        assert out == ct.floyd_entries(7, call, B, Lw) and len(set(out)) == B and max(out) < Lw
+        assert out == tw.floyd_entries(7, call, B, Lw) and len(set(out)) == B and max(out) < Lw
 
 
 # ---------------------------------------------------------------- the ABI

@@ -1,6 +1,6 @@
 """Start positions for self-play and the arena (agz_selfplay_set_starts), on the host simulator: game `gid` begins at entry
 gid mod S of the table (arena game g at g mod S) and is, from there, the reference's game -- bit for bit the twins of
-tests/starts_twin.py in moves, pi, q, result, resign flag and final score.  CPU only."""
+tests/selfplay_twin.py in moves, pi, q, result, resign flag and final score.  CPU only."""
 import ctypes as C
 import inspect
 import os
@@ -10,8 +10,9 @@ import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
+import hs
 import orc
-import starts_twin as tw
+import selfplay_twin as tw
 from test_hostsim_arena import oracle_eval_game
 from test_hostsim_selfplay import OracleNet, bits_equal, oracle_game, run_engine
 
@@ -26,8 +27,8 @@ def starts_5x5():
 
 
 def run_sim(N, net, R, seed, games, slots, starts, arena=False, white=None, max_steps=400000, **cfg):
-    sim = tw.StartsSim(board_size=N, games=slots, num_readouts=R, seed=seed, game_id_base=0, game_id_stride=1,
-                       record_capacity_games=games + 8, arena_mode=1 if arena else 0, **cfg)
+    sim = hs.Sim(board_size=N, games=slots, num_readouts=R, seed=seed, game_id_base=0, game_id_stride=1,
+                 record_capacity_games=games + 8, arena_mode=1 if arena else 0, **cfg)
     sim.set_starts(starts)
     sim.start(games)
     steps = 0
@@ -142,8 +143,8 @@ def test_game_to_start_follows_the_index_rule():
         assert_selfplay_equal(r, o, r["game_id"])
         assert starts[3].n + r["num_moves"] <= tw.max_game_length(N)
     # with base / stride (a rank of a multi-GPU run) the index is still the GLOBAL id mod S
-    sim = tw.StartsSim(board_size=N, games=2, num_readouts=R, seed=seed, game_id_base=3, game_id_stride=4,
-                       record_capacity_games=16, **THRESHOLD)
+    sim = hs.Sim(board_size=N, games=2, num_readouts=R, seed=seed, game_id_base=3, game_id_stride=4,
+                 record_capacity_games=16, **THRESHOLD)
     sim.set_starts(starts)
     sim.start(5)
     while sim.counters()["finished"] < 5:
@@ -231,7 +232,7 @@ def test_without_a_table_the_records_are_todays():
     want, wct, _ = run_engine(N, net, R, seed, games, 3)
     for starts in ([], None):
         if starts is None:          # a table set and cleared again
-            sim = tw.StartsSim(board_size=N, games=3, num_readouts=R, seed=seed, record_capacity_games=games + 8)
+            sim = hs.Sim(board_size=N, games=3, num_readouts=R, seed=seed, record_capacity_games=games + 8)
             sim.set_starts(starts_5x5())
             assert sim.L.hs_starts_count(sim.h) == 6
             sim.set_starts([])
@@ -256,7 +257,7 @@ def test_without_a_table_the_records_are_todays():
 def test_board_check_of_the_table():
     """root_board_valid, the check k_starts_valid runs over a table: a point outside {-1, 0, 1}, a group without a
     liberty, a stone on the ko point"""
-    sim = tw.StartsSim(board_size=5, games=1, num_readouts=4)
+    sim = hs.Sim(board_size=5, games=1, num_readouts=4)
     good = tw.ko_start(5)
     assert sim.board_valid(good.board_np(), good.ko)
     b = good.board_np()
