@@ -666,6 +666,27 @@ class SelfPlayPlayer:
 _stream = {"seed": 0, "next_game": 0}
 
 
+def _refuse_two_root_rules(gumbel, forced_playouts):      # before selfplay() / train() create anything
+    if gumbel and forced_playouts:
+        raise ValueError("gumbel and forced_playouts are two rules for the same decision: ask for one")
+
+
+def _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit, gumbel_c_scale,
+                          targets_only_arena=False):
+    """selfplay()'s and train()'s search options on a fresh engine (train(): a targets-only arena under the cap)"""
+    _refuse_two_root_rules(gumbel, forced_playouts)
+    if starts:
+        eng.set_starts(starts)
+    if playout_cap is not None:
+        eng.set_playout_cap(*playout_cap)
+        if targets_only_arena:
+            eng.replay_set_targets_only(playout_cap[0] > 0)
+    if forced_playouts:
+        eng.set_forced_playouts(forced_playouts, prune_targets)
+    if gumbel:
+        eng.set_gumbel(gumbel, gumbel_c_visit, gumbel_c_scale)
+
+
 def seed(s):
     """Random.seed!(s) for selfplay(): restarts the game-id stream at 0 under draw-stream seed `s`"""
     _stream["seed"], _stream["next_game"] = int(s), 0
@@ -690,8 +711,7 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     gumbel (ours): m -- the Gumbel root search (Engine.set_gumbel) in the full searches: up to m root candidates by
     Gumbel-top-k, Sequential Halving, the searches_pi row is softmax(log prior + sigma(q)); gumbel_c_visit and
     gumbel_c_scale are sigma's constants.  It composes with playout_cap, starts and symmetry, not with forced_playouts."""
-    if gumbel and forced_playouts:
-        raise ValueError("gumbel and forced_playouts are two rules for the same decision: ask for one")
+    _refuse_two_root_rules(gumbel, forced_playouts)
     single = games is None
     games = 1 if single else int(games)
     if seed is None:
@@ -708,14 +728,7 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     eng.set_precision(precision)
     if symmetry is not None:
         eng.set_symmetry(symmetry)
-    if starts:
-        eng.set_starts(starts)
-    if playout_cap is not None:
-        eng.set_playout_cap(*playout_cap)
-    if forced_playouts:
-        eng.set_forced_playouts(forced_playouts, prune_targets)
-    if gumbel:
-        eng.set_gumbel(gumbel, gumbel_c_visit, gumbel_c_scale)
+    _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit, gumbel_c_scale)
     eng.start(games)
     while eng.records_count() < games:
         eng.step(16)
@@ -1102,8 +1115,7 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
     num_games, batch_size, epochs = int(num_games), int(batch_size), int(epochs)
     if num_games < 1 or batch_size < 2 or epochs < 1 or int(ckp_freq) < 1:
         raise ValueError("num_games, epochs, ckp_freq >= 1 and batch_size >= 2 (BatchNorm needs two positions)")
-    if gumbel and forced_playouts:
-        raise ValueError("gumbel and forced_playouts are two rules for the same decision: ask for one")
+    _refuse_two_root_rules(gumbel, forced_playouts)
     cur_nn = NeuralNet(env, tower_height=tower_height) if model is None else model       # train.jl:43
     slots = min(num_games, 1024) if slots is None else int(slots)
     if slots < 1:
@@ -1123,15 +1135,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
         pi = torch.empty((batch_size, eng.A), dtype=torch.float32, device=dev)
         z = torch.empty(batch_size, dtype=torch.float32, device=dev)
         cuts = _minibatch_cuts(batch_size)
-        if starts:
-            eng.set_starts(starts)
-        if playout_cap is not None:
-            eng.set_playout_cap(*playout_cap)
-            eng.replay_set_targets_only(playout_cap[0] > 0)
-        if forced_playouts:
-            eng.set_forced_playouts(forced_playouts, prune_targets)
-        if gumbel:
-            eng.set_gumbel(gumbel, gumbel_c_visit, gumbel_c_scale)
+        _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit,
+                              gumbel_c_scale, targets_only_arena=True)
         eng.set_hold(True)
         eng.start(num_games)
         eng.release()

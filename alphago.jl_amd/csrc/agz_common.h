@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <stdexcept>
 #include <string>
+#include <utility>
 
 #include "../../include/agz.h"
 #include "../../include/agz_debug.h"
@@ -61,6 +62,7 @@ struct DevBuf {
   void ensure(size_t count) {
     if (count > n) alloc(count);
   }
+  void swap(DevBuf& o) { std::swap(p, o.p), std::swap(n, o.n); }
   void zero(hipStream_t s) {
     if (p) AGZ_HIP(hipMemsetAsync(p, 0, n * sizeof(T), s));
   }

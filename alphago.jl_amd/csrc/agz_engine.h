@@ -176,6 +176,13 @@ class Engine {
   void fill_synthetic_inputs(int B);
   void check_game(int g) const;
   void check_node(int g, int node) const;
+  // shared by the option setters and their readers (`what` is the error text's prefix)
+  void require_selfplay_engine(const char* what) const;
+  void require_between_games(const char* what);
+  void read_counter_pair(int first, int64_t out[2]);
+  template <class Launch>
+  void read_tree_pi_row(float* out, Launch launch);
+  void idle_all_slots();
 
   agz_config cfg_;
   View V_{};
@@ -223,6 +230,8 @@ class Engine {
   DevBuf<uint8_t> s_lines_;     // agz_tree_lines: lines, pv_N, pv of one node behind one another
   void check_positions(const char* mode, const char* item, const agz_position_info* info, const int8_t* history,
                        int64_t B);
+  void upload_position_table(DevBuf<int8_t>& board, DevBuf<int8_t>& hist, DevBuf<agz_position_info>& inf,
+                             const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B);
   void upload_positions(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,
                         int64_t rows);
   void begin_analysis_run(int64_t B, int64_t rows, uint64_t game_id_base);

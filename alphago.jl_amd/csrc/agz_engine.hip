@@ -727,6 +727,11 @@ void Engine::start(int64_t total_games) {
   if (hold_rel_.p) hold_rel_.zero(stream_);     // with the hold on, the fresh slots wait for a first release
   AGZ_HIP(hipMemsetAsync(V_.counters, 0, sizeof(unsigned long long) * kCounterSlots, stream_));
   AGZ_HIP(hipMemsetAsync(V_.ar_hdr, 0, sizeof(int32_t) * 5 * (V_.games / 2 + 1), stream_));
+  idle_all_slots();
+}
+
+// every slot idle and zeroed, as a run finds them; returns with the stream idle
+void Engine::idle_all_slots() {
   std::vector<GameState> gs(V_.games);
   std::memset(gs.data(), 0, sizeof(GameState) * gs.size());
   for (auto& g : gs) g.phase = G_IDLE;
@@ -776,7 +781,7 @@ void Engine::step(int nsteps) {
 
 void Engine::analyze_start(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,
                            uint64_t game_id_base) {
-  AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "analysis: an arena_mode engine plays evaluate() games only");
+  require_selfplay_engine("analysis");
   AGZ_REQUIRE(boards && info && B >= 1, AGZ_BAD_ARGUMENT, "analysis: boards and info of B >= 1 positions");
   check_positions("analysis", "position", info, history, B);
   AGZ_HIP(hipStreamSynchronize(stream_));     // nothing in flight may still read the tables that are replaced here
@@ -787,115 +792,108 @@ void Engine::analyze_start(const int8_t* boards, const agz_position_info* info, 
   begin_analysis_run(B, B, game_id_base);
 }
 
-// ---- playout cap randomization (agz_selfplay_set_playout_cap)
+// ---- the search options of self-play: playout cap, forced playouts with target pruning, Gumbel root search
+// (agz_selfplay_set_playout_cap / _set_forced_playouts / _set_gumbel).  `what` is the prefix of the error text
+
+void Engine::require_selfplay_engine(const char* what) const {
+  AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "%s: an arena_mode engine plays evaluate() games only", what);
+}
+
+// a game keeps its options from its first descent to its last move, and its record is rebuilt under them: they change
+// only between games (a run that has not stepped yet has claimed none)
+void Engine::require_between_games(const char* what) {
+  if (V_.analysis || !stepped_) return;
+  agz_stats st;
+  stats(&st);
+  AGZ_REQUIRE(st.live_games == 0, AGZ_BAD_ARGUMENT, "%s: %lld games of the current run are still being played", what,
+              (long long)st.live_games);
+}
+
+// the range checks a setter shares with its single-tree call (NaN fails each)
+static void check_forced_k(const char* what, const char* range, double k) {
+  AGZ_REQUIRE(k >= 0.0 && k <= 1024.0, AGZ_BAD_ARGUMENT, "%s: k = %g, not in %s", what, k, range);
+}
+static void check_gumbel_c(const char* what, double c_visit, double c_scale) {
+  AGZ_REQUIRE(c_visit >= 0.0 && c_visit <= 1.0e9, AGZ_BAD_ARGUMENT, "%s: c_visit = %g, not in 0 .. 1e9", what, c_visit);
+  AGZ_REQUIRE(c_scale > 0.0 && c_scale <= 1.0e9, AGZ_BAD_ARGUMENT, "%s: c_scale = %g, not in (0, 1e9]", what, c_scale);
+}
+static void check_lines(int K, int K_min, int D, int min_visits) {
+  AGZ_REQUIRE(K >= K_min && K <= 16, AGZ_BAD_ARGUMENT, "lines: K = %d, not in %d..16", K, K_min);
+  AGZ_REQUIRE(D >= 1 && D <= 64, AGZ_BAD_ARGUMENT, "lines: D = %d, not in 1..64", D);
+  AGZ_REQUIRE(min_visits >= 1, AGZ_BAD_ARGUMENT, "lines: min_visits = %d, not >= 1", min_visits);
+}
+
+// counters[first] and counters[first + 1]: {full, fast} moves, {forced descents, pruned rows}, {begun, halved}
+void Engine::read_counter_pair(int first, int64_t out[2]) {
+  unsigned long long c[2];
+  AGZ_HIP(hipMemcpyAsync(c, V_.counters + first, sizeof(c), hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+  out[0] = (int64_t)c[0];
+  out[1] = (int64_t)c[1];
+}
+static_assert(CT_CAP_FAST == CT_CAP_FULL + 1 && CT_PRUNED_ROWS == CT_FORCED_SEL + 1 && CT_GUMBEL_HALVED == CT_GUMBEL_BEGUN + 1,
+              "the counters of an option are read as one pair");
+void Engine::playout_cap_counts(int64_t out[2]) { read_counter_pair(CT_CAP_FULL, out); }
+void Engine::forced_counts(int64_t out[2]) { read_counter_pair(CT_FORCED_SEL, out); }
+void Engine::gumbel_counts(int64_t out[2]) { read_counter_pair(CT_GUMBEL_BEGUN, out); }
+
+// one pi row [A] of a single tree's node: `launch` writes it to the device row it is given
+template <class Launch>
+void Engine::read_tree_pi_row(float* out, Launch launch) {
+  AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+  s_f32a_.ensure(V_.A);
+  launch(s_f32a_.p);
+  AGZ_HIP(hipGetLastError());
+  AGZ_HIP(hipMemcpyAsync(out, s_f32a_.p, sizeof(float) * V_.A, hipMemcpyDeviceToHost, stream_));
+  AGZ_HIP(hipStreamSynchronize(stream_));
+}
 
 void Engine::set_playout_cap(int fast_readouts, double full_prob) {
-  AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "playout cap: an arena_mode engine plays evaluate() games only");
+  require_selfplay_engine("playout cap");
   AGZ_REQUIRE(fast_readouts >= 0 && fast_readouts <= V_.R, AGZ_BAD_ARGUMENT,
               "playout cap: %d fast readouts, 0 (off) or 1..num_readouts = %d", fast_readouts, V_.R);
   AGZ_REQUIRE(fast_readouts == 0 || (full_prob >= 0.0 && full_prob <= 1.0), AGZ_BAD_ARGUMENT,
               "playout cap: full_prob %g not in [0, 1]", full_prob);
-  // a game asks the coin again when it plays the move: the setting changes only between games
-  if (!V_.analysis && stepped_) {
-    agz_stats st;
-    stats(&st);
-    AGZ_REQUIRE(st.live_games == 0, AGZ_BAD_ARGUMENT, "playout cap: %lld games of the current run are still being played",
-                (long long)st.live_games);
-  }
+  require_between_games("playout cap");
   AGZ_HIP(hipStreamSynchronize(stream_));
-  V_.cap_fast = fast_readouts;
-  V_.cap_full_prob = fast_readouts > 0 ? full_prob : 1.0;
+  view_set_playout_cap(V_, fast_readouts, full_prob);
 }
-
-// ---- forced playouts and policy target pruning (agz_selfplay_set_forced_playouts)
 
 void Engine::set_forced_playouts(double k, int prune) {
-  AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "forced playouts: an arena_mode engine plays evaluate() games only");
-  AGZ_REQUIRE(k >= 0.0 && k <= 1024.0, AGZ_BAD_ARGUMENT, "forced playouts: k = %g, not in 0 (off) .. 1024", k);   // NaN fails
+  require_selfplay_engine("forced playouts");
+  check_forced_k("forced playouts", "0 (off) .. 1024", k);
   AGZ_REQUIRE(prune == 0 || k > 0.0, AGZ_BAD_ARGUMENT, "forced playouts: pruning needs k > 0");
   AGZ_REQUIRE(!(k > 0.0) || V_.gumbel_m == 0, AGZ_BAD_ARGUMENT, "forced playouts: the Gumbel root search is on (m = %d)", V_.gumbel_m);
-  // a search forced from its first descent and a target pruned by the same k: the setting changes only between games
-  if (!V_.analysis && stepped_) {
-    agz_stats st;
-    stats(&st);
-    AGZ_REQUIRE(st.live_games == 0, AGZ_BAD_ARGUMENT,
-                "forced playouts: %lld games of the current run are still being played", (long long)st.live_games);
-  }
+  require_between_games("forced playouts");
   AGZ_HIP(hipStreamSynchronize(stream_));
-  V_.forced_k = k;
-  V_.forced_prune = prune != 0;
-}
-
-// ---- Gumbel root search (agz_selfplay_set_gumbel)
-
-void Engine::set_gumbel(int m, double c_visit, double c_scale) {
-  AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "gumbel: an arena_mode engine plays evaluate() games only");
-  AGZ_REQUIRE(m == 0 || (m >= 2 && m <= kGumbelMax), AGZ_BAD_ARGUMENT, "gumbel: m = %d, not 0 (off) or in 2..%d", m,
-              kGumbelMax);
-  AGZ_REQUIRE(c_visit >= 0.0 && c_visit <= 1.0e9, AGZ_BAD_ARGUMENT, "gumbel: c_visit = %g, not in 0 .. 1e9", c_visit);   // NaN fails
-  AGZ_REQUIRE(c_scale > 0.0 && c_scale <= 1.0e9, AGZ_BAD_ARGUMENT, "gumbel: c_scale = %g, not in (0, 1e9]", c_scale);
-  AGZ_REQUIRE(m == 0 || !(V_.forced_k > 0.0), AGZ_BAD_ARGUMENT, "gumbel: forced playouts are on (k = %g)", V_.forced_k);
-  // a search keeps one rule from its first descent to its move: the setting changes only between games
-  if (!V_.analysis && stepped_) {
-    agz_stats st;
-    stats(&st);
-    AGZ_REQUIRE(st.live_games == 0, AGZ_BAD_ARGUMENT, "gumbel: %lld games of the current run are still being played",
-                (long long)st.live_games);
-  }
-  AGZ_HIP(hipStreamSynchronize(stream_));
-  V_.gumbel_m = m;
-  V_.gumbel_cvisit = m > 0 ? c_visit : 0.0;
-  V_.gumbel_cscale = m > 0 ? c_scale : 0.0;
-}
-
-void Engine::gumbel_counts(int64_t out[2]) {
-  unsigned long long c[2];
-  static_assert(CT_GUMBEL_HALVED == CT_GUMBEL_BEGUN + 1, "the two counters are read as one pair");
-  AGZ_HIP(hipMemcpyAsync(c, V_.counters + CT_GUMBEL_BEGUN, sizeof(c), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
-  out[0] = (int64_t)c[0];
-  out[1] = (int64_t)c[1];
-}
-
-void Engine::tree_gumbel_pi(int g, int node, double c_visit, double c_scale, float* out) {
-  check_node(g, node);
-  AGZ_REQUIRE(c_visit >= 0.0 && c_visit <= 1.0e9, AGZ_BAD_ARGUMENT, "gumbel pi: c_visit = %g, not in 0 .. 1e9", c_visit);
-  AGZ_REQUIRE(c_scale > 0.0 && c_scale <= 1.0e9, AGZ_BAD_ARGUMENT, "gumbel pi: c_scale = %g, not in (0, 1e9]", c_scale);
-  AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
-  s_f32a_.ensure(V_.A);
-  hipLaunchKernelGGL(k_tree_gumbel_pi, dim3(1), dim3(kWave), 0, stream_, V_, g, node, c_visit, c_scale, s_f32a_.p);
-  AGZ_HIP(hipGetLastError());
-  AGZ_HIP(hipMemcpyAsync(out, s_f32a_.p, sizeof(float) * V_.A, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
-}
-
-void Engine::forced_counts(int64_t out[2]) {
-  unsigned long long c[2];
-  static_assert(CT_PRUNED_ROWS == CT_FORCED_SEL + 1, "the two counters are read as one pair");
-  AGZ_HIP(hipMemcpyAsync(c, V_.counters + CT_FORCED_SEL, sizeof(c), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
-  out[0] = (int64_t)c[0];
-  out[1] = (int64_t)c[1];
+  view_set_forced_playouts(V_, k, prune);
 }
 
 void Engine::tree_pruned_pi(int g, int node, double k, float* out) {
   check_node(g, node);
-  AGZ_REQUIRE(k >= 0.0 && k <= 1024.0, AGZ_BAD_ARGUMENT, "pruned pi: k = %g, not in 0..1024", k);
-  AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
-  s_f32a_.ensure(V_.A);
-  hipLaunchKernelGGL(k_tree_pruned_pi, dim3(1), dim3(kWave), 0, stream_, V_, g, node, k, s_f32a_.p);
-  AGZ_HIP(hipGetLastError());
-  AGZ_HIP(hipMemcpyAsync(out, s_f32a_.p, sizeof(float) * V_.A, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  check_forced_k("pruned pi", "0..1024", k);
+  read_tree_pi_row(out, [&](float* row) {
+    hipLaunchKernelGGL(k_tree_pruned_pi, dim3(1), dim3(kWave), 0, stream_, V_, g, node, k, row);
+  });
 }
 
-void Engine::playout_cap_counts(int64_t out[2]) {
-  unsigned long long c[2];
-  static_assert(CT_CAP_FAST == CT_CAP_FULL + 1, "the two counters are read as one pair");
-  AGZ_HIP(hipMemcpyAsync(c, V_.counters + CT_CAP_FULL, sizeof(c), hipMemcpyDeviceToHost, stream_));
+void Engine::set_gumbel(int m, double c_visit, double c_scale) {
+  require_selfplay_engine("gumbel");
+  AGZ_REQUIRE(m == 0 || (m >= 2 && m <= kGumbelMax), AGZ_BAD_ARGUMENT, "gumbel: m = %d, not 0 (off) or in 2..%d", m,
+              kGumbelMax);
+  check_gumbel_c("gumbel", c_visit, c_scale);
+  AGZ_REQUIRE(m == 0 || !(V_.forced_k > 0.0), AGZ_BAD_ARGUMENT, "gumbel: forced playouts are on (k = %g)", V_.forced_k);
+  require_between_games("gumbel");
   AGZ_HIP(hipStreamSynchronize(stream_));
-  out[0] = (int64_t)c[0];
-  out[1] = (int64_t)c[1];
+  view_set_gumbel(V_, m, c_visit, c_scale);
+}
+
+void Engine::tree_gumbel_pi(int g, int node, double c_visit, double c_scale, float* out) {
+  check_node(g, node);
+  check_gumbel_c("gumbel pi", c_visit, c_scale);
+  read_tree_pi_row(out, [&](float* row) {
+    hipLaunchKernelGGL(k_tree_gumbel_pi, dim3(1), dim3(kWave), 0, stream_, V_, g, node, c_visit, c_scale, row);
+  });
 }
 
 // ---- start positions of self-play and arena games (agz_selfplay_set_starts)
@@ -910,14 +908,8 @@ void Engine::set_starts(const int8_t* boards, const agz_position_info* info, con
   AGZ_REQUIRE(held == 0 && rp_hdr_.empty(), AGZ_BAD_ARGUMENT,
               "starts: the record ring holds %lld games and the replay arena %lld; clear both first", (long long)held,
               (long long)rp_hdr_.size());
-  // ... and while no game is on its way into the ring (a run that has not stepped yet has claimed none: the table set
-  // there is that run's)
-  if (!V_.analysis && stepped_) {
-    agz_stats st;
-    stats(&st);
-    AGZ_REQUIRE(st.live_games == 0, AGZ_BAD_ARGUMENT, "starts: %lld games of the current run are still being played",
-                (long long)st.live_games);
-  }
+  // ... and while no game is on its way into the ring (the table set before a run's first step is that run's)
+  require_between_games("starts");
   const int P = V_.P, mgl = V_.max_game_length;
   if (S > 0) {
     check_positions("starts", "entry", info, history, S);
@@ -940,14 +932,8 @@ void Engine::set_starts(const int8_t* boards, const agz_position_info* info, con
   DevBuf<int8_t> nb, nh;
   DevBuf<agz_position_info> ni;
   DevBuf<int32_t> ok;
-  nb.alloc((size_t)S * P);
-  nh.alloc((size_t)S * 7 * P);
-  ni.alloc((size_t)S);
   ok.alloc((size_t)S);
-  AGZ_HIP(hipMemcpyAsync(nb.p, boards, (size_t)S * P, hipMemcpyHostToDevice, stream_));
-  if (history) AGZ_HIP(hipMemcpyAsync(nh.p, history, (size_t)S * 7 * P, hipMemcpyHostToDevice, stream_));
-  else AGZ_HIP(hipMemsetAsync(nh.p, 0, (size_t)S * 7 * P, stream_));
-  AGZ_HIP(hipMemcpyAsync(ni.p, info, sizeof(agz_position_info) * (size_t)S, hipMemcpyHostToDevice, stream_));
+  upload_position_table(nb, nh, ni, boards, info, history, S);
   hipLaunchKernelGGL(k_starts_valid, dim3((unsigned)S), dim3(kWave), 0, stream_, V_, (const int8_t*)nb.p,
                      (const agz_position_info*)ni.p, ok.p);
   AGZ_HIP(hipGetLastError());
@@ -958,9 +944,9 @@ void Engine::set_starts(const int8_t* boards, const agz_position_info* info, con
     AGZ_REQUIRE(good[(size_t)i], AGZ_BAD_ARGUMENT,
                 "starts: entry %lld: bad board (a point outside -1..1, a group without liberty or a stone on the ko point)",
                 (long long)i);
-  std::swap(st_board_.p, nb.p); std::swap(st_board_.n, nb.n);
-  std::swap(st_hist_.p, nh.p); std::swap(st_hist_.n, nh.n);
-  std::swap(st_info_.p, ni.p); std::swap(st_info_.n, ni.n);
+  st_board_.swap(nb);
+  st_hist_.swap(nh);
+  st_info_.swap(ni);
   V_.st_count = (int32_t)S;
   V_.st_board = st_board_.p;
   V_.st_hist = st_hist_.p;
@@ -988,20 +974,26 @@ void Engine::check_positions(const char* mode, const char* item, const agz_posit
   }
 }
 
+// B positions (boards, info, history or zeros) into a table of three device buffers, grown as needed
+void Engine::upload_position_table(DevBuf<int8_t>& board, DevBuf<int8_t>& hist, DevBuf<agz_position_info>& inf,
+                                   const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B) {
+  const size_t nb = (size_t)B * V_.P;
+  board.ensure(nb);
+  hist.ensure(7 * nb);
+  inf.ensure((size_t)B);
+  AGZ_HIP(hipMemcpyAsync(board.p, boards, nb, hipMemcpyHostToDevice, stream_));
+  if (history) AGZ_HIP(hipMemcpyAsync(hist.p, history, 7 * nb, hipMemcpyHostToDevice, stream_));
+  else AGZ_HIP(hipMemsetAsync(hist.p, 0, 7 * nb, stream_));
+  AGZ_HIP(hipMemcpyAsync(inf.p, info, sizeof(agz_position_info) * (size_t)B, hipMemcpyHostToDevice, stream_));
+}
+
 // B positions into the an_* tables, result tables of `rows` rows cleared (the stream is idle)
 void Engine::upload_positions(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,
                               int64_t rows) {
-  const int P = V_.P, A = V_.A;
-  const size_t R = (size_t)(rows > 0 ? rows : 1);
-  an_board_.ensure((size_t)B * P);
-  an_hist_.ensure((size_t)B * 7 * P);
-  an_info_.ensure((size_t)B);
+  const size_t R = (size_t)(rows > 0 ? rows : 1), A = (size_t)V_.A;
+  upload_position_table(an_board_, an_hist_, an_info_, boards, info, history, B);
   an_res_.ensure(R);
-  an_rows_.ensure((size_t)3 * R * A);
-  AGZ_HIP(hipMemcpyAsync(an_board_.p, boards, (size_t)B * P, hipMemcpyHostToDevice, stream_));
-  if (history) AGZ_HIP(hipMemcpyAsync(an_hist_.p, history, (size_t)B * 7 * P, hipMemcpyHostToDevice, stream_));
-  else AGZ_HIP(hipMemsetAsync(an_hist_.p, 0, (size_t)B * 7 * P, stream_));
-  AGZ_HIP(hipMemcpyAsync(an_info_.p, info, sizeof(agz_position_info) * B, hipMemcpyHostToDevice, stream_));
+  an_rows_.ensure(3 * R * A);
   AGZ_HIP(hipMemsetAsync(an_res_.p, 0, sizeof(agz_analysis) * R, stream_));
   AGZ_HIP(hipMemsetAsync(an_rows_.p, 0, sizeof(float) * 3 * R * A, stream_));
 }
@@ -1012,11 +1004,7 @@ void Engine::begin_analysis_run(int64_t B, int64_t rows, uint64_t game_id_base) 
   const size_t R = (size_t)(rows > 0 ? rows : 1);
   AGZ_HIP(hipMemsetAsync(V_.an_ctr, 0, sizeof(unsigned long long) * 2, stream_));
   // every slot idle, as agz_selfplay_start leaves them; the counters and the records ring keep their self-play content
-  std::vector<GameState> gs(V_.games);
-  std::memset(gs.data(), 0, sizeof(GameState) * gs.size());
-  for (auto& g : gs) g.phase = G_IDLE;
-  AGZ_HIP(hipMemcpyAsync(V_.gs, gs.data(), sizeof(GameState) * gs.size(), hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  idle_all_slots();
   an_count_ = rows;
   V_.analysis = 1;
   V_.an_count = B;
@@ -1056,9 +1044,7 @@ void Engine::begin_analysis_run(int64_t B, int64_t rows, uint64_t game_id_base) 
 }
 
 void Engine::analyze_set_lines(int K, int D, int min_visits) {
-  AGZ_REQUIRE(K >= 0 && K <= 16, AGZ_BAD_ARGUMENT, "lines: K = %d, not in 0..16", K);
-  AGZ_REQUIRE(D >= 1 && D <= 64, AGZ_BAD_ARGUMENT, "lines: D = %d, not in 1..64", D);
-  AGZ_REQUIRE(min_visits >= 1, AGZ_BAD_ARGUMENT, "lines: min_visits = %d, not >= 1", min_visits);
+  check_lines(K, 0, D, min_visits);
   lines_k_ = K;
   lines_d_ = D;
   lines_min_ = min_visits;
@@ -1078,9 +1064,7 @@ void Engine::analyze_lines(agz_line* lines, int16_t* pv, float* pv_N) {
 // the lines of any node of single tree g: one launch, one copy (the three tables lie behind one another in s_lines_)
 void Engine::tree_lines(int g, int node, int K, int D, int min_visits, agz_line* lines, int16_t* pv, float* pv_N) {
   check_node(g, node);
-  AGZ_REQUIRE(K >= 1 && K <= 16, AGZ_BAD_ARGUMENT, "lines: K = %d, not in 1..16", K);
-  AGZ_REQUIRE(D >= 1 && D <= 64, AGZ_BAD_ARGUMENT, "lines: D = %d, not in 1..64", D);
-  AGZ_REQUIRE(min_visits >= 1, AGZ_BAD_ARGUMENT, "lines: min_visits = %d, not >= 1", min_visits);
+  check_lines(K, 1, D, min_visits);
   const size_t kd = (size_t)K * D;
   const size_t off_n = sizeof(agz_line) * K, off_pv = off_n + sizeof(float) * kd, total = off_pv + sizeof(int16_t) * kd;
   s_lines_.ensure(total);
@@ -1099,7 +1083,7 @@ void Engine::tree_lines(int g, int node, int K, int D, int min_visits, agz_line*
 
 void Engine::review_start(const int16_t* moves, const int64_t* game_offset, const int8_t* boards,
                           const agz_position_info* info, const int8_t* history, int64_t G, uint64_t game_id_base) {
-  AGZ_REQUIRE(!cfg_.arena_mode, AGZ_BAD_ARGUMENT, "review: an arena_mode engine plays evaluate() games only");
+  require_selfplay_engine("review");
   AGZ_REQUIRE(game_offset && G >= 1, AGZ_BAD_ARGUMENT, "review: game_offset of G + 1 entries, G >= 1");
   AGZ_REQUIRE((boards == nullptr) == (info == nullptr), AGZ_BAD_ARGUMENT,
               "review: start boards and info are given together or not at all");
@@ -1120,11 +1104,7 @@ void Engine::review_start(const int16_t* moves, const int64_t* game_offset, cons
   std::vector<agz_position_info> dinfo;
   if (!boards) {       // the empty board with agz_config.komi, Black to play
     dboards.assign((size_t)G * P, 0);
-    agz_position_info f;
-    std::memset(&f, 0, sizeof(f));
-    f.n = 0; f.to_play = 1; f.ko = -1; f.caps_black = 0; f.caps_white = 0; f.last_move = -1; f.prev_move = -1;
-    f.history_len = 0; f.komi = V_.komi;
-    dinfo.assign((size_t)G, f);
+    dinfo.assign((size_t)G, empty_position_info(V_.komi));
     boards = dboards.data();
     info = dinfo.data();
   }

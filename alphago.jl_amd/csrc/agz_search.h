@@ -1012,44 +1012,21 @@ AGZ_FN void game_resign_coin(const View& V, GameState& G, uint64_t game_id) {
 template <class W>
 AGZ_FN void game_start(W& w, const View& V, Scratch& S, int g, uint64_t game_id, uint64_t start_key) {
   GameState& G = V.gs[g];
-  if (V.st_count > 0) {
-    const long s = (long)(start_key % (uint64_t)V.st_count);
-    const agz_position_info info = V.st_info[s];
-    root_install(w, V, S, g, V.st_board + s * V.P, V.st_hist + s * 7 * V.P, info, G_INIT, false);
-    if (w.leader()) {
-      G.game_id = game_id;
-      game_resign_coin(V, G, game_id);
-      G.short_first = 0;
-      V.gumbel[g].n = -1;
-    }
-    w.sync();
-    w.count(&V.counters[CT_STARTED], 1);
-    return;
-  }
-  w.for_each(V.cap, [&](int i) { V.freelist[(long)g * V.cap + i] = V.cap - 1 - i; });
-  w.sync();
+  const bool table = V.st_count > 0;
+  const long s = table ? (long)(start_key % (uint64_t)V.st_count) : 0;
+  const agz_position_info info = table ? V.st_info[s] : empty_position_info(V.komi);
+  // one install: the empty board is a null `board` and `hist` (no history, S.sb all zero)
+  root_install(w, V, S, g, table ? V.st_board + s * V.P : nullptr, table ? V.st_hist + s * 7 * V.P : nullptr, info, G_INIT,
+               false);
   if (w.leader()) {
     G.game_id = game_id;
     game_resign_coin(V, G, game_id);
-    G.rootN = 0.f; G.rootW = 0.f; G.target = 0.f; G.komi = V.komi;
-    G.sel = 0; G.move_count = 0; G.nqs = 0; G.hist_len = 0;
-    G.free_top = V.cap; G.garbage = 0; G.nleaves = 0; G.err = 0; G.result = 0; G.was_resign = 0; G.nodes_used = 0;
-    G.short_first = 0; G.short_searches = 0;
-    G.phase = G_INIT;
-    V.eval_ord[g] = 0;
+    G.short_first = 0;
     V.gumbel[g].n = -1;
   }
   w.sync();
-  const int id = pool_alloc(w, V, S, g);
-  w.for_each(V.P, [&](int p) { S.sb[p] = 0; });
-  w.sync();
-  NodeMeta m;
-  m.parent = -1; m.n = 0; m.ko = -1; m.caps_b = 0; m.caps_w = 0; m.fmove = -1; m.last_move = -1;
-  m.losses = 0; m.to_play = 1; m.flags = 0; m.pad = 0;
-  node_init_from_scratch(w, V, S, g, id, m);
-  if (w.leader()) G.root = id;
-  w.sync();
   w.count(&V.counters[CT_STARTED], 1);
+  if (table) return;
   // bench-only: a random opening prefix so that concurrent games are at mixed stages, and a
   // shortened first search so that they are also at mixed phases of their readout budget
   if (V.stagger > 0) {
@@ -1102,7 +1079,7 @@ AGZ_FN bool root_board_valid(W& w, const View& V, Scratch& S, const int8_t* boar
   return dead == 0;
 }
 
-// initialize_game!(player, pos) (mcts_play.jl:110-118) on slot g: an empty pool, `board` [P] as the root, the
+// initialize_game!(player, pos) (mcts_play.jl:110-118) on slot g: an empty pool, `board` [P] (null: empty) as the root, the
 // info.history_len boards of `hist` ([.][P], newest first) as the history ring, the slot in `phase`.  The one install of
 // agz_tree_init (TOP_INIT, analysis = false, unchanged) and of the analysis mode (analysis = true): there an invalid
 // board returns false before the slot is touched, and a position whose last two moves were passes is a finished root
@@ -1128,7 +1105,7 @@ AGZ_FN bool root_install(W& w, const View& V, Scratch& S, int g, const int8_t* b
   for (int h = 0; hist && h < info.history_len && h < 7; ++h)
     w.for_each(V.P, [&](int p) { V.hist[((long)g * 7 + h) * V.PP + p] = hist[(long)h * V.P + p]; });
   const int id = pool_alloc(w, V, S, g);
-  w.for_each(V.P, [&](int p) { S.sb[p] = board[p]; });
+  w.for_each(V.P, [&](int p) { S.sb[p] = board ? board[p] : (int8_t)0; });
   w.sync();
   NodeMeta m;
   m.parent = -1; m.n = info.n; m.ko = info.ko; m.caps_b = info.caps_black; m.caps_w = info.caps_white;

@@ -11,6 +11,7 @@
 #include <cstdint>
 
 #include "../../include/agz.h"
+#include "../../include/agz_draws.h"
 
 namespace agz {
 
@@ -21,6 +22,13 @@ enum GamePhase : int32_t {
   G_IDLE = 0, G_INIT = 1, G_INIT_WAIT = 2, G_SEARCH = 3, G_MANUAL = 4, G_RETIRED = 5,
   G_ARENA_WAIT = 6    // arena: the partner slot (other colour, other network) is to move
 };
+
+// the position every game without a start table begins at: the empty board, Black to play, komi as given
+AGZ_HD inline agz_position_info empty_position_info(float komi) {
+  agz_position_info f{};
+  f.to_play = 1; f.ko = -1; f.last_move = -1; f.prev_move = -1; f.komi = komi;   // n, caps and history_len stay 0
+  return f;
+}
 
 enum NodeFlags : uint8_t { NF_EXPANDED = 1, NF_DONE = 2, NF_ALLOC = 4 };
 
@@ -216,5 +224,20 @@ struct View {
   double gumbel_cvisit, gumbel_cscale;
   GumbelState* gumbel;                // [games]
 };
+
+// option values -> View fields, for the engine's setters (which check the arguments first) and the host simulator's
+inline void view_set_playout_cap(View& V, int fast_readouts, double full_prob) {
+  V.cap_fast = fast_readouts > 0 ? fast_readouts : 0;
+  V.cap_full_prob = fast_readouts > 0 ? full_prob : 1.0;
+}
+inline void view_set_forced_playouts(View& V, double k, int prune) {
+  V.forced_k = k > 0.0 ? k : 0.0;
+  V.forced_prune = (k > 0.0 && prune) ? 1 : 0;
+}
+inline void view_set_gumbel(View& V, int m, double c_visit, double c_scale) {
+  V.gumbel_m = m > 0 ? m : 0;
+  V.gumbel_cvisit = m > 0 ? c_visit : 0.0;
+  V.gumbel_cscale = m > 0 ? c_scale : 0.0;
+}
 
 }  // namespace agz

@@ -1,0 +1,191 @@
+"""What the GPU tests of the self-play search options share (test_gpu_starts.py, test_gpu_playout_cap.py,
+test_gpu_forced_playouts.py, test_gpu_gumbel.py; test_gpu_train_batched.py takes the arena helpers): playing a run to its
+records, a record against the twin's game (tests/selfplay_twin.py), and train() against the same schedule composed of
+single calls, whose games are the twin's on the weights in force round by round.  Test infrastructure only."""
+import numpy as np
+
+import alphago_jl_amd as ag
+import selfplay_twin as tw
+from gpu_common import GpuNetForOracle
+from test_hostsim_selfplay import bits_equal
+from test_train_loop_batched import sample_entries, window_pairs
+
+
+def play(eng, games, network=None, white=None, chunk=8, sort=True):
+    """a run of `games` games to its records (sort: by game id, else in the ring's order) and stats; network / white:
+    the callbacks of an external_network engine (white: an arena's second network)"""
+    eng.start(games)
+    for _ in range(400000):
+        if network is None:
+            eng.step(chunk)
+        elif white is None:
+            eng.step_external(network)
+        else:
+            eng.step_external(network, white)
+        if eng.records_count() >= games:
+            break
+    recs, st = eng.records(), eng.stats()
+    assert len(recs) == games and st["pool_exhausted"] == 0 and st["pool_short_searches"] == 0
+    return (sorted(recs, key=lambda r: r["game_id"]) if sort else recs), st
+
+
+def assert_game_equals_twin(r, o, what, full=None):
+    """record r is the twin's game o, bit for bit.  full (the twin's mask of fully searched plies, under the playout
+    cap): the pi row of a fast ply is all-zero bits, the full rows are the twin's and none of them is all zero"""
+    extra = {k: o[k] for k in ("forced_sel", "begun", "halved", "off_max", "dups", "cuts") if k in o}
+    print(f"game {what}: start {r.get('start')}, {r['num_moves']} moves{'' if full is None else f' ({int(full.sum())} full)'}, "
+          f"result {r['result']}, resign {r['was_resign']}, score {r['final_score']}; twin {o['num_moves']} / {o['result']} / "
+          f"{o['was_resign']} / {o['final_score']}, evals {o['evals']} {extra}")
+    assert r["num_moves"] == o["num_moves"], what
+    assert (r["moves"] == o["moves"]).all(), what
+    assert r["result"] == o["result"] and r["was_resign"] == o["was_resign"], what
+    assert r["resign_disabled"] == o["resign_disabled"], what
+    assert np.float32(r["final_score"]) == np.float32(o["final_score"]), what
+    assert bits_equal(r["qs"], o["qs"]), what
+    if full is None:
+        assert bits_equal(r["pis"], o["pis"]), what
+    elif r["num_moves"]:
+        got = np.ascontiguousarray(r["pis"], np.float32)
+        assert (got[~full].view(np.uint32) == 0).all(), (what, "a fast row is not all zero")
+        assert bits_equal(got[full], o["pis"][full]), what
+        assert (got[full] != 0).any(axis=1).all(), what
+    assert r["short_searches"] == 0, what
+
+
+def weight_mismatches(engine, want):
+    """the (layer, kind) arrays of `engine` that are not bit for bit `want`, with the largest difference of each"""
+    out = []
+    for lk, v in want.items():
+        got = engine.get_weights(*lk)
+        if not bits_equal(got, v):
+            out.append((lk, int((got != v).sum()), float(np.abs(got.astype(np.float64) - v).max())))
+    return out
+
+
+def _weights(eng):
+    return {lk: eng.get_weights(*lk) for lk in eng.layers()}
+
+
+def _lengths(e):
+    return [e.replay_record(k)["num_moves"] for k in range(e.replay_count())]
+
+
+def _twin_pairs(e, call, B):
+    """what agz_replay_sample must draw: the twin's entries mapped through the arena's current window"""
+    lengths = _lengths(e)
+    live = e.replay_live_positions()
+    first = sum(lengths) - live
+    cum = np.concatenate([[0], np.cumsum(lengths)])
+    fg = int(np.searchsorted(cum, first, side="right") - 1)
+    return window_pairs(lengths, fg, first - int(cum[fg]), sample_entries(e.cfg.seed, call, live, B))
+
+
+def arena_pis(e):
+    return [e.replay_record(k)["pis"][: e.replay_record(k)["num_moves"]] for k in range(e.replay_count())]
+
+
+def count_targets(pis):
+    return int(sum((np.asarray(x) != 0).any(axis=1).sum() for x in pis if len(x)))
+
+
+def host_schedule(nn0, cfg, configure, targets_only):
+    """train()'s schedule composed of single calls (the method of tests/test_gpu_train_batched.py) on an engine that
+    configure(eng) set the options of, with the weights after every training kept; targets_only: the arena train()
+    keeps under the playout cap.  cfg: N, TOWER, R, SEED, num_games, slots, memory, B, start_after
+    -> (per game: record, loss, step, live entries; the snapshots; the step each game was claimed in; the option
+    counters of the run)"""
+    c = cfg
+    num_games, slots = c["num_games"], c["slots"]
+    eng = ag.Engine(board_size=c["N"], tower_height=c["TOWER"], games=slots, num_readouts=c["R"], seed=c["SEED"],
+                    record_capacity_games=slots + 8)
+    nn0.engine.copy_weights_to(eng)
+    configure(eng)
+    if targets_only:
+        eng.replay_set_targets_only(True)
+    eng.set_hold(True)
+    eng.start(num_games)
+    eng.release()
+    snaps = [_weights(eng)]
+    i, claimed, pending, ref, steps, start_step, targets = 0, 0, min(slots, num_games), [], 0, {}, 0
+    while i < num_games:
+        for k in range(claimed, claimed + pending):
+            start_step[k] = steps + 1
+        claimed += pending
+        eng.step(1)
+        steps += 1
+        n = eng.records_count()
+        for r in sorted(eng.records(), key=lambda r: r["game_id"]):
+            assert eng.replay_ingest_records(r["index"], 1) == 1
+            eng.replay_set_window(c["memory"])
+            i += 1
+            live = eng.replay_live_positions()
+            if targets_only:
+                targets += count_targets([r["pis"][: r["num_moves"]]])
+                assert live == min(c["memory"], targets)
+            loss = None
+            if live >= c["start_after"]:
+                if targets_only:
+                    pairs, _ = tw.sample_targets(c["SEED"], i, c["B"], arena_pis(eng), window=live)
+                    g, p = np.array([a for a, _ in pairs], np.int64), np.array([b for _, b in pairs], np.int32)
+                else:
+                    g, p = _twin_pairs(eng, i, c["B"])
+                f, pi, z = eng.replay_batch(g, p)
+                assert not targets_only or (pi != 0).any(axis=1).all()
+                loss = float(eng.train_step(f, pi, z, eta=np.float32(0.02), rho=0.9)[0])
+                snaps.append(_weights(eng))
+            ref.append(dict(i=i, record=r, loss=loss, step=steps, live=live))
+        eng.records_clear()
+        eng.release()
+        pending = min(n, num_games - claimed)
+    counts = dict(cap=eng.playout_cap_counts(), forced=eng.forced_counts(), gumbel=eng.gumbel_counts())
+    eng.close()
+    return ref, snaps, start_step, counts
+
+
+def assert_train_equals_twin(env, nn0, cfg, schedule, twin_of, masked, **train_kw):
+    """schedule = host_schedule(...)[:3].  Every game of it is the twin's game twin_of(cb, gid, on_round) on the weights
+    in force round by round: with several slots games overlap training, so round r of a game (engine step start_step +
+    r) runs on the weights left by the trainings of the steps before it.  And ag.train(..., **train_kw) is that
+    schedule: records, losses, live entries (targets-only arenas) and final weights.  -> (the twins, train()'s log)"""
+    c = cfg
+    ref, snaps, start_step = schedule
+    assert sum(g["loss"] is not None for g in ref) >= 4
+    chk = ag.Engine(board_size=c["N"], tower_height=c["TOWER"], games=1, num_readouts=8, max_nodes_per_game=16)
+    cb = GpuNetForOracle(chk).cb
+    loaded = [None]
+    switched = 0
+    twins = []
+    for gme in ref:
+        gid = int(gme["record"]["game_id"])
+        rnd = [0]
+
+        def on_round():
+            step = start_step[gid] + rnd[0]
+            rnd[0] += 1
+            t = sum(1 for h in ref if h["step"] < step and h["loss"] is not None)
+            if loaded[0] != t:
+                for (layer, kind), w in snaps[t].items():
+                    chk.set_weights(layer, kind, w)
+                loaded[0] = t
+
+        o = twin_of(cb, gid, on_round)
+        assert_game_equals_twin(gme["record"], o, gid, o["full"] if masked else None)
+        twins.append(o)
+        first = sum(1 for h in ref if h["step"] < start_step[gid] and h["loss"] is not None)
+        switched += loaded[0] != first
+    assert switched > 0, "some game was in flight across a training step"
+
+    nn, log = ag.train(env, num_games=c["num_games"], memory_size=c["memory"], batch_size=c["B"], readouts=c["R"],
+                       model=nn0, start_training_after=c["start_after"], slots=c["slots"], seed=c["SEED"], callback=None,
+                       return_log=True, epochs=1, **train_kw)
+    assert len(log) == len(ref) == c["num_games"]
+    for x, y in zip(log, ref):
+        a, b = x["record"], y["record"]
+        assert a["game_id"] == b["game_id"] and a["num_moves"] == b["num_moves"] and a["result"] == b["result"]
+        assert (a["moves"] == b["moves"]).all() and bits_equal(a["pis"], b["pis"]) and bits_equal(a["qs"], b["qs"])
+        assert x["loss"] == y["loss"]
+        assert not masked or x["live"] == y["live"]
+    bad = weight_mismatches(nn.engine, snaps[-1])
+    assert not bad, bad
+    chk.close()
+    return twins, log

@@ -311,17 +311,13 @@ int hs_start_board_valid(void* h, const int8_t* board, int ko) {
 // the playout cap (View::cap_fast / cap_full_prob, agz_selfplay_set_playout_cap):
 // fast_readouts = 0 switches the cap off
 void hs_set_playout_cap(void* h, int fast_readouts, double full_prob) {
-  agz::View& V = ((Sim*)h)->V;
-  V.cap_fast = fast_readouts > 0 ? fast_readouts : 0;
-  V.cap_full_prob = fast_readouts > 0 ? full_prob : 1.0;
+  agz::view_set_playout_cap(((Sim*)h)->V, fast_readouts, full_prob);
 }
 
 // forced playouts and policy target pruning (View::forced_k / forced_prune, agz_selfplay_set_forced_playouts):
 // k = 0 switches both rules off
 void hs_set_forced_playouts(void* h, double k, int prune) {
-  agz::View& V = ((Sim*)h)->V;
-  V.forced_k = k > 0.0 ? k : 0.0;
-  V.forced_prune = (k > 0.0 && prune) ? 1 : 0;
+  agz::view_set_forced_playouts(((Sim*)h)->V, k, prune);
 }
 
 // pruned_pi of node `node` of game slot g under k, whatever the setting: the scale of the node's own N, the squash of
@@ -339,9 +335,7 @@ int hs_pruned_pi(void* h, int g, int node, double k, float* out) {
 // m = 0 switches the rule off.  The two counters restart here (hs_start clears the enum's counters only).
 void hs_set_gumbel(void* h, int m, double c_visit, double c_scale) {
   agz::View& V = ((Sim*)h)->V;
-  V.gumbel_m = m > 0 ? m : 0;
-  V.gumbel_cvisit = m > 0 ? c_visit : 0.0;
-  V.gumbel_cscale = m > 0 ? c_scale : 0.0;
+  agz::view_set_gumbel(V, m, c_visit, c_scale);
   V.counters[agz::CT_GUMBEL_BEGUN] = 0;
   V.counters[agz::CT_GUMBEL_HALVED] = 0;
 }

@@ -14,6 +14,7 @@ import orc
 import selfplay_twin as tw
 from alphago_jl_amd import symmetry as sy
 from gpu_common import GpuNetForOracle
+from gpu_options import assert_game_equals_twin, assert_train_equals_twin, host_schedule, play
 from test_hostsim_selfplay import bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -23,38 +24,9 @@ CAP = (8, 0.5)
 THR = -0.1
 
 
-def play(eng, games, chunk=8):
-    eng.start(games)
-    for _ in range(400000):
-        eng.step(chunk)
-        if eng.records_count() >= games:
-            break
-    recs, st = eng.records(), eng.stats()
-    assert len(recs) == games and st["pool_exhausted"] == 0 and st["pool_short_searches"] == 0
-    return sorted(recs, key=lambda r: r["game_id"]), st
-
-
-def assert_game_equal(r, o, what):
-    full = o["full"]
-    print(f"game {what}: {r['num_moves']} moves ({int(full.sum())} full), result {r['result']}, resign {r['was_resign']}; "
-          f"twin {o['num_moves']} / {o['result']} / {o['was_resign']}, evals {o['evals']}, forced {o['forced_sel']}, "
-          f"rows changed {int(o['pruned_rows'].sum())}")
-    assert r["num_moves"] == o["num_moves"], what
-    assert (r["moves"] == o["moves"]).all(), what
-    assert r["result"] == o["result"] and r["was_resign"] == o["was_resign"], what
-    assert r["resign_disabled"] == o["resign_disabled"], what
-    assert np.float32(r["final_score"]) == np.float32(o["final_score"]), what
-    assert bits_equal(r["qs"], o["qs"]), what
-    if r["num_moves"]:
-        got = np.ascontiguousarray(r["pis"], np.float32)
-        assert (got[~full].view(np.uint32) == 0).all(), (what, "a fast row is not all zero")
-        assert bits_equal(got[full], o["pis"][full]), what
-    assert r["short_searches"] == 0, what
-
-
 def check_set(eng, recs, st, twins):
     for r, o in zip(recs, twins):
-        assert_game_equal(r, o, int(r["game_id"]))
+        assert_game_equals_twin(r, o, int(r["game_id"]), o["full"])
     for o in twins:           # the condition of the comparison set
         assert o["forced_sel"] >= 1, "a game of the set has no forced selection"
         assert o["pruned_rows"].any(), "a game of the set has no row that pruning changed"
@@ -284,103 +256,23 @@ def test_analysis_is_untouched():
 TRAIN = dict(N=5, TOWER=1, R=16, k=2.0, SEED=3, num_games=8, slots=4, memory=40, B=8, start_after=8)
 
 
-def host_schedule(nn0):
-    """train()'s schedule with the cap, a targets-only arena and forced playouts, composed of single calls, with the
-    weights after every training kept (the method of tests/test_gpu_playout_cap.py::host_schedule)"""
-    from test_gpu_playout_cap import arena_pis
-    from test_gpu_train_batched import _weights
-    c = TRAIN
-    num_games, slots = c["num_games"], c["slots"]
-    eng = ag.Engine(board_size=c["N"], tower_height=c["TOWER"], games=slots, num_readouts=c["R"], seed=c["SEED"],
-                    record_capacity_games=slots + 8)
-    nn0.engine.copy_weights_to(eng)
+def configure_train(eng):
     eng.set_playout_cap(*CAP)
-    eng.replay_set_targets_only(True)
-    eng.set_forced_playouts(c["k"], True)
-    eng.set_hold(True)
-    eng.start(num_games)
-    eng.release()
-    snaps = [_weights(eng)]
-    i, claimed, pending, ref, steps, start_step, targets = 0, 0, min(slots, num_games), [], 0, {}, 0
-    while i < num_games:
-        for g in range(claimed, claimed + pending):
-            start_step[g] = steps + 1
-        claimed += pending
-        eng.step(1)
-        steps += 1
-        n = eng.records_count()
-        for r in sorted(eng.records(), key=lambda r: r["game_id"]):
-            assert eng.replay_ingest_records(r["index"], 1) == 1
-            eng.replay_set_window(c["memory"])
-            i += 1
-            targets += int((r["pis"] != 0).any(axis=1).sum()) if r["num_moves"] else 0
-            live = eng.replay_live_positions()
-            assert live == min(c["memory"], targets)
-            loss = None
-            if live >= c["start_after"]:
-                pairs, _ = tw.sample_targets(c["SEED"], i, c["B"], arena_pis(eng), window=live)
-                g = np.array([a for a, _ in pairs], np.int64)
-                q = np.array([b for _, b in pairs], np.int32)
-                f, pi, z = eng.replay_batch(g, q)
-                loss = float(eng.train_step(f, pi, z, eta=np.float32(0.02), rho=0.9)[0])
-                snaps.append(_weights(eng))
-            ref.append(dict(i=i, record=r, loss=loss, step=steps, live=live))
-        eng.records_clear()
-        eng.release()
-        pending = min(n, num_games - claimed)
-    counts = eng.forced_counts()
-    eng.close()
-    return ref, snaps, start_step, counts
+    eng.set_forced_playouts(TRAIN["k"], True)
 
 
 def test_train_with_forced_playouts_plays_the_twins_games():
-    from test_gpu_starts import weight_mismatches
     c = TRAIN
-    N, TOWER, R, SEED, k = c["N"], c["TOWER"], c["R"], c["SEED"], c["k"]
-    env = ag.GoEnv(N)
-    nn0 = ag.NeuralNet(env, tower_height=TOWER, seed=1)
-    ref, snaps, start_step, counts = host_schedule(nn0)
-    assert sum(g["loss"] is not None for g in ref) >= 4
-    chk = ag.Engine(board_size=N, tower_height=TOWER, games=1, num_readouts=8, max_nodes_per_game=16)
-    cb = GpuNetForOracle(chk).cb
-    loaded = [None]
-    switched = 0
-    twins = []
-    for gme in ref:
-        rec = gme["record"]
-        gid = int(rec["game_id"])
-        rnd = [0]
-
-        def on_round():
-            step = start_step[gid] + rnd[0]
-            rnd[0] += 1
-            t = sum(1 for h in ref if h["step"] < step and h["loss"] is not None)
-            if loaded[0] != t:
-                for (layer, kind), w in snaps[t].items():
-                    chk.set_weights(layer, kind, w)
-                loaded[0] = t
-
-        o = tw.twin_selfplay(N, cb, R, SEED, gid, None, -0.9, 0.05, on_round=on_round, cap=CAP, forced=(k, True))
-        assert_game_equal(rec, o, gid)
-        twins.append(o)
-        first = sum(1 for h in ref if h["step"] < start_step[gid] and h["loss"] is not None)
-        switched += loaded[0] != first
-    assert switched > 0, "some game was in flight across a training step"
+    env = ag.GoEnv(c["N"])
+    nn0 = ag.NeuralNet(env, tower_height=c["TOWER"], seed=1)
+    ref, snaps, start_step, counts = host_schedule(nn0, c, configure_train, targets_only=True)
+    twins, _ = assert_train_equals_twin(
+        env, nn0, c, (ref, snaps, start_step),
+        lambda cb, gid, on_round: tw.twin_selfplay(c["N"], cb, c["R"], c["SEED"], gid, None, -0.9, 0.05, on_round=on_round,
+                                                   cap=CAP, forced=(c["k"], True)),
+        masked=True, playout_cap=CAP, forced_playouts=c["k"])
     nforced, nrows = sum(o["forced_sel"] for o in twins), sum(int(o["pruned_rows"].sum()) for o in twins)
-    assert nforced >= 3 and nrows >= 3 and counts == (nforced, nrows)
-
-    nn, log = ag.train(env, num_games=c["num_games"], memory_size=c["memory"], batch_size=c["B"], readouts=R, model=nn0,
-                       start_training_after=c["start_after"], slots=c["slots"], seed=SEED, callback=None, return_log=True,
-                       epochs=1, playout_cap=CAP, forced_playouts=k)
-    assert len(log) == len(ref) == c["num_games"]
-    for x, y in zip(log, ref):
-        a, b = x["record"], y["record"]
-        assert a["game_id"] == b["game_id"] and a["num_moves"] == b["num_moves"] and a["result"] == b["result"]
-        assert (a["moves"] == b["moves"]).all() and bits_equal(a["pis"], b["pis"]) and bits_equal(a["qs"], b["qs"])
-        assert x["loss"] == y["loss"] and x["live"] == y["live"]
-    bad = weight_mismatches(nn.engine, snaps[-1])
-    assert not bad, bad
-    chk.close()
+    assert nforced >= 3 and nrows >= 3 and counts["forced"] == (nforced, nrows)
 
 
 def test_selfplay_takes_the_keywords():

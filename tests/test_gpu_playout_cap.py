@@ -13,6 +13,9 @@ import orc
 import selfplay_twin as tw
 from alphago_jl_amd import symmetry as sy
 from gpu_common import GpuNetForOracle, pos_soa
+from gpu_options import (_twin_pairs, arena_pis, assert_game_equals_twin, assert_train_equals_twin, count_targets,
+                         host_schedule)
+from gpu_options import play as play_sorted
 from test_hostsim_selfplay import bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -20,32 +23,12 @@ L = orc.lib()
 BAD_ARGUMENT = ag._lib.BAD_ARGUMENT
 
 
-def play(eng, games, chunk=8):
-    eng.start(games)
-    for _ in range(400000):
-        eng.step(chunk)
-        if eng.records_count() >= games:
-            break
-    recs, st = eng.records(), eng.stats()
-    assert len(recs) == games and st["pool_exhausted"] == 0 and st["pool_short_searches"] == 0
-    return recs, st
+def play(eng, games):
+    return play_sorted(eng, games, sort=False)
 
 
 def assert_cap_game_equal(r, o, what):
-    full = o["full"]
-    print(f"game {what}: {r['num_moves']} moves ({int(full.sum())} full, {int((~full).sum())} fast), result {r['result']}, "
-          f"resign {r['was_resign']}; twin {o['num_moves']} / {o['result']} / {o['was_resign']}, evals {o['evals']}")
-    assert r["num_moves"] == o["num_moves"], what
-    assert (r["moves"] == o["moves"]).all(), what
-    assert r["result"] == o["result"] and r["was_resign"] == o["was_resign"], what
-    assert r["resign_disabled"] == o["resign_disabled"], what
-    assert np.float32(r["final_score"]) == np.float32(o["final_score"]), what
-    assert bits_equal(r["qs"], o["qs"]), what
-    got = np.ascontiguousarray(r["pis"], np.float32)
-    assert (got[~full].view(np.uint32) == 0).all(), (what, "a fast row is not all zero")
-    assert bits_equal(got[full], o["pis"][full]), what
-    assert (got[full] != 0).any(axis=1).all(), what
-    assert r["short_searches"] == 0, what
+    assert_game_equals_twin(r, o, what, o["full"])
 
 
 def assert_mixed(twins):
@@ -247,14 +230,6 @@ def test_refusals():
 
 # ---------------------------------------------------------------- the targets-only arena
 
-def arena_pis(e):
-    return [e.replay_record(k)["pis"][: e.replay_record(k)["num_moves"]] for k in range(e.replay_count())]
-
-
-def count_targets(pis):
-    return int(sum((np.asarray(x) != 0).any(axis=1).sum() for x in pis if len(x)))
-
-
 def check_samples(e, live_want, calls_and_B):
     import torch
     from test_train_loop_batched import sample_syms
@@ -280,7 +255,6 @@ def check_samples(e, live_want, calls_and_B):
 
 
 def test_targets_only_arena_counts_and_samples_the_nonzero_rows():
-    from test_gpu_train_batched import _twin_pairs
     import torch
     N, tower, R, r, p, games, seed = 9, 1, 8, 2, 0.4, 128, 5       # about 25 targets a game: 2048 need more than 84
     eng = ag.Engine(board_size=N, tower_height=tower, games=games, num_readouts=R, seed=seed,
@@ -349,105 +323,23 @@ def test_targets_only_arena_counts_and_samples_the_nonzero_rows():
 TRAIN = dict(N=5, TOWER=1, R=16, r=4, p=0.4, SEED=3, num_games=8, slots=4, memory=40, B=8, start_after=8)
 
 
-def host_schedule(nn0):
-    """train()'s schedule with the cap and a targets-only arena, composed of single calls, with the weights after every
-    training kept (the method of tests/test_gpu_starts.py::host_schedule)"""
-    from test_gpu_train_batched import _weights
-    c = TRAIN
-    num_games, slots = c["num_games"], c["slots"]
-    eng = ag.Engine(board_size=c["N"], tower_height=c["TOWER"], games=slots, num_readouts=c["R"], seed=c["SEED"],
-                    record_capacity_games=slots + 8)
-    nn0.engine.copy_weights_to(eng)
-    eng.set_playout_cap(c["r"], c["p"])
-    eng.replay_set_targets_only(True)
-    eng.set_hold(True)
-    eng.start(num_games)
-    eng.release()
-    snaps = [_weights(eng)]
-    i, claimed, pending, ref, steps, start_step, targets = 0, 0, min(slots, num_games), [], 0, {}, 0
-    while i < num_games:
-        for k in range(claimed, claimed + pending):
-            start_step[k] = steps + 1
-        claimed += pending
-        eng.step(1)
-        steps += 1
-        n = eng.records_count()
-        for r in sorted(eng.records(), key=lambda r: r["game_id"]):
-            assert eng.replay_ingest_records(r["index"], 1) == 1
-            eng.replay_set_window(c["memory"])
-            i += 1
-            targets += int((r["pis"] != 0).any(axis=1).sum()) if r["num_moves"] else 0
-            live = eng.replay_live_positions()
-            assert live == min(c["memory"], targets)
-            loss = None
-            if live >= c["start_after"]:
-                pairs, _ = tw.sample_targets(c["SEED"], i, c["B"], arena_pis(eng), window=live)
-                g = np.array([a for a, _ in pairs], np.int64)
-                q = np.array([b for _, b in pairs], np.int32)
-                f, pi, z = eng.replay_batch(g, q)
-                assert (pi != 0).any(axis=1).all()
-                loss = float(eng.train_step(f, pi, z, eta=np.float32(0.02), rho=0.9)[0])
-                snaps.append(_weights(eng))
-            ref.append(dict(i=i, record=r, loss=loss, step=steps, live=live))
-        eng.records_clear()
-        eng.release()
-        pending = min(n, num_games - claimed)
-    eng.close()
-    return ref, snaps, start_step
-
-
 def test_train_with_the_cap_plays_the_twins_games_and_counts_targets():
-    from test_gpu_starts import weight_mismatches
     c = TRAIN
-    N, TOWER, R, SEED = c["N"], c["TOWER"], c["R"], c["SEED"]
-    env = ag.GoEnv(N)
-    nn0 = ag.NeuralNet(env, tower_height=TOWER, seed=1)
-    ref, snaps, start_step = host_schedule(nn0)
-    assert sum(g["loss"] is not None for g in ref) >= 4
-    chk = ag.Engine(board_size=N, tower_height=TOWER, games=1, num_readouts=8, max_nodes_per_game=16)
-    cb = GpuNetForOracle(chk).cb
-    loaded = [None]
-    switched = 0
-    twins = []
-    for gme in ref:
-        rec = gme["record"]
-        gid = int(rec["game_id"])
-        rnd = [0]
-
-        def on_round():
-            step = start_step[gid] + rnd[0]
-            rnd[0] += 1
-            t = sum(1 for h in ref if h["step"] < step and h["loss"] is not None)
-            if loaded[0] != t:
-                for (layer, kind), w in snaps[t].items():
-                    chk.set_weights(layer, kind, w)
-                loaded[0] = t
-
-        o = tw.twin_selfplay(N, cb, R, SEED, gid, None, -0.9, 0.05, on_round=on_round, cap=(c["r"], c["p"]))
-        assert_cap_game_equal(rec, o, gid)
-        twins.append(o)
-        first = sum(1 for h in ref if h["step"] < start_step[gid] and h["loss"] is not None)
-        switched += loaded[0] != first
-    assert switched > 0, "some game was in flight across a training step"
+    env = ag.GoEnv(c["N"])
+    nn0 = ag.NeuralNet(env, tower_height=c["TOWER"], seed=1)
+    ref, snaps, start_step, _ = host_schedule(nn0, c, lambda eng: eng.set_playout_cap(c["r"], c["p"]), targets_only=True)
+    twins, log = assert_train_equals_twin(
+        env, nn0, c, (ref, snaps, start_step),
+        lambda cb, gid, on_round: tw.twin_selfplay(c["N"], cb, c["R"], c["SEED"], gid, None, -0.9, 0.05, on_round=on_round,
+                                                   cap=(c["r"], c["p"])),
+        masked=True, playout_cap=(c["r"], c["p"]))
     nfull, nfast = sum(int(o["full"].sum()) for o in twins), sum(int((~o["full"]).sum()) for o in twins)
     assert nfull >= 3 and nfast >= 3, (nfull, nfast)          # (a game that resigns early may hold one kind only)
-
-    nn, log = ag.train(env, num_games=c["num_games"], memory_size=c["memory"], batch_size=c["B"], readouts=R, model=nn0,
-                       start_training_after=c["start_after"], slots=c["slots"], seed=SEED, callback=None, return_log=True,
-                       epochs=1, playout_cap=(c["r"], c["p"]))
-    assert len(log) == len(ref) == c["num_games"]
     targets = 0
     for x, y in zip(log, ref):
-        a, b = x["record"], y["record"]
-        assert a["game_id"] == b["game_id"] and a["num_moves"] == b["num_moves"] and a["result"] == b["result"]
-        assert (a["moves"] == b["moves"]).all() and bits_equal(a["pis"], b["pis"]) and bits_equal(a["qs"], b["qs"])
-        assert x["loss"] == y["loss"]
-        targets += int((a["pis"] != 0).any(axis=1).sum()) if a["num_moves"] else 0
+        targets += count_targets([x["record"]["pis"][: x["record"]["num_moves"]]])
         assert x["live"] == y["live"] == min(c["memory"], targets)
     assert targets < sum(int(x["record"]["num_moves"]) for x in log)
-    bad = weight_mismatches(nn.engine, snaps[-1])
-    assert not bad, bad
-    chk.close()
 
 
 def test_selfplay_takes_the_cap_and_extract_data_drops_fast_plies():

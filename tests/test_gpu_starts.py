@@ -11,6 +11,8 @@ import orc
 import selfplay_twin as tw
 from alphago_jl_amd import symmetry
 from gpu_common import GpuNetForOracle
+from gpu_options import assert_game_equals_twin as assert_selfplay_equal, assert_train_equals_twin, host_schedule
+from gpu_options import play as play_sorted
 from test_hostsim_selfplay import OracleNet, bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -31,32 +33,8 @@ def set_table(eng, starts):
     eng.set_starts(boards=b, info=i, history=h)
 
 
-def play(eng, games, network=None, white=None, chunk=8):
-    eng.start(games)
-    for _ in range(400000):
-        if network is None:
-            eng.step(chunk)
-        elif white is None:
-            eng.step_external(network)
-        else:
-            eng.step_external(network, white)
-        if eng.records_count() >= games:
-            break
-    recs, st = eng.records(), eng.stats()
-    assert len(recs) == games and st["pool_exhausted"] == 0 and st["pool_short_searches"] == 0
-    return recs, st
-
-
-def assert_selfplay_equal(r, o, what):
-    print(f"game {what}: start {r['start']}, {r['num_moves']} moves, result {r['result']}, resign {r['was_resign']}, "
-          f"score {r['final_score']}; twin {o['num_moves']} / {o['result']} / {o['was_resign']} / {o['final_score']}")
-    assert r["num_moves"] == o["num_moves"], what
-    assert (r["moves"] == o["moves"]).all(), what
-    assert r["result"] == o["result"] and r["was_resign"] == o["was_resign"], what
-    assert r["resign_disabled"] == o["resign_disabled"], what
-    assert np.float32(r["final_score"]) == np.float32(o["final_score"]), what
-    assert bits_equal(r["qs"], o["qs"]) and bits_equal(r["pis"], o["pis"]), what
-    assert r["short_searches"] == 0, what
+def play(eng, games, network=None, white=None):
+    return play_sorted(eng, games, network, white, sort=False)          # the order of the record ring is asserted here
 
 
 def assert_arena_equal(r, o, what):
@@ -150,6 +128,27 @@ def test_one_entry_and_slot_count_is_invisible():
         assert r["start"] == 0
         assert_selfplay_equal(r, tw.twin_selfplay(N, cb, R, seed, int(r["game_id"]), starts[3], -0.9, 0.0), r["game_id"])
     fwd.close()
+
+
+def test_the_empty_board_is_the_one_entry_table_of_the_empty_position():
+    """what lets game_start make one root_install call: no table and a table of the empty position alone are one run"""
+    N, R, seed, games = 5, 16, 2, 5
+    out = []
+    for tbl in (None, [tw.random_start(N, 0, 0)]):
+        eng = ag.Engine(board_size=N, tower_height=1, games=3, num_readouts=R, seed=seed, record_capacity_games=games + 8)
+        eng.init_synthetic(0)
+        if tbl:
+            set_table(eng, tbl)
+        assert eng.starts_count() == (1 if tbl else 0)
+        out.append(play_sorted(eng, games))
+        eng.close()
+    (want, wst), (got, gst) = out
+    assert gst["positions"] == wst["positions"] and gst["evals"] == wst["evals"]
+    for x, y in zip(got, want):
+        for k in ("game_id", "num_moves", "result", "was_resign", "resign_disabled", "short_searches"):
+            assert x[k] == y[k], k
+        assert np.float32(x["final_score"]) == np.float32(y["final_score"])
+        assert (x["moves"] == y["moves"]).all() and bits_equal(x["pis"], y["pis"]) and bits_equal(x["qs"], y["qs"])
 
 
 # ---------------------------------------------------------------- the arena
@@ -455,106 +454,20 @@ def test_selfplay_and_evaluate_take_positions():
 TRAIN = dict(N=5, TOWER=1, R=16, SEED=3, num_games=8, slots=4, memory=60, B=8, start_after=8)
 
 
-def host_schedule(nn0, starts):
-    """train()'s schedule composed of single calls (the method of tests/test_gpu_train_batched.py), with the weights
-    after every training kept -> (per game: record, loss, step; the snapshots; the step each game was claimed in)"""
-    from test_gpu_train_batched import _twin_pairs, _weights
-    c = TRAIN
-    num_games, slots = c["num_games"], c["slots"]
-    eng = ag.Engine(board_size=c["N"], tower_height=c["TOWER"], games=slots, num_readouts=c["R"], seed=c["SEED"],
-                    record_capacity_games=slots + 8)
-    nn0.engine.copy_weights_to(eng)
-    eng.set_starts(starts)
-    eng.set_hold(True)
-    eng.start(num_games)
-    eng.release()
-    snaps = [_weights(eng)]
-    i, claimed, pending, ref, steps, start_step = 0, 0, min(slots, num_games), [], 0, {}
-    while i < num_games:
-        for k in range(claimed, claimed + pending):
-            start_step[k] = steps + 1
-        claimed += pending
-        eng.step(1)
-        steps += 1
-        n = eng.records_count()
-        for r in sorted(eng.records(), key=lambda r: r["game_id"]):
-            assert eng.replay_ingest_records(r["index"], 1) == 1
-            eng.replay_set_window(c["memory"])
-            i += 1
-            loss = None
-            if eng.replay_live_positions() >= c["start_after"]:
-                g, p = _twin_pairs(eng, i, c["B"])
-                f, pi, z = eng.replay_batch(g, p)
-                loss = float(eng.train_step(f, pi, z, eta=np.float32(0.02), rho=0.9)[0])
-                snaps.append(_weights(eng))
-            ref.append(dict(i=i, record=r, loss=loss, step=steps))
-        eng.records_clear()
-        eng.release()
-        pending = min(n, num_games - claimed)
-    eng.close()
-    return ref, snaps, start_step
-
-
-def weight_mismatches(engine, want):
-    """the (layer, kind) arrays of `engine` that are not bit for bit `want`, with the largest difference of each"""
-    out = []
-    for lk, v in want.items():
-        got = engine.get_weights(*lk)
-        if not bits_equal(got, v):
-            out.append((lk, int((got != v).sum()), float(np.abs(got.astype(np.float64) - v).max())))
-    return out
-
-
 def test_train_with_starts_plays_the_twins_games():
     """train(..., starts=..., slots=4): every logged record is the twin's game from its start on the weights in force
     round by round -- games overlap training with 4 slots, so round r of a game (engine step start_step + r) runs on
     the weights left by the trainings of the steps before it.  The weights after each training come from the same
     schedule composed of single calls (the method of tests/test_gpu_train_batched.py), which train() must equal."""
-    N, TOWER, R, SEED = TRAIN["N"], TRAIN["TOWER"], TRAIN["R"], TRAIN["SEED"]
-    num_games, slots, memory, B, start_after = (TRAIN[k] for k in ("num_games", "slots", "memory", "B", "start_after"))
+    N, R, SEED = TRAIN["N"], TRAIN["R"], TRAIN["SEED"]
     env = ag.GoEnv(N)
     ostarts = tw.random_starts(N, PLIES, seed=0)
     starts = [api_position(env, p) for p in ostarts]
-    nn0 = ag.NeuralNet(env, tower_height=TOWER, seed=1)
-    ref, snaps, start_step = host_schedule(nn0, starts)
-    assert sum(g["loss"] is not None for g in ref) >= 4
-
-    # every game of that schedule is the twin's game on the weights of each of its rounds
-    chk = ag.Engine(board_size=N, tower_height=TOWER, games=1, num_readouts=8, max_nodes_per_game=16)
-    cb = GpuNetForOracle(chk).cb
-    loaded = [None]
-    switched = 0
-    for gme in ref:
-        r = gme["record"]
-        gid = int(r["game_id"])
-        rnd = [0]
-
-        def on_round():
-            step = start_step[gid] + rnd[0]
-            rnd[0] += 1
-            t = sum(1 for h in ref if h["step"] < step and h["loss"] is not None)
-            if loaded[0] != t:
-                for (layer, kind), w in snaps[t].items():
-                    chk.set_weights(layer, kind, w)
-                loaded[0] = t
-
-        o = tw.twin_selfplay(N, cb, R, SEED, gid, ostarts[gid % 6], -0.9, 0.05, on_round=on_round)
-        assert_selfplay_equal(r, o, gid)
-        first = sum(1 for h in ref if h["step"] < start_step[gid] and h["loss"] is not None)
-        switched += loaded[0] != first
-    assert switched > 0, "some game was in flight across a training step"
-
-    # train() is that schedule
-    nn, log = ag.train(env, num_games=num_games, memory_size=memory, batch_size=B, readouts=R, model=nn0,
-                       start_training_after=start_after, slots=slots, seed=SEED, starts=starts, callback=None,
-                       return_log=True)
-    assert len(log) == len(ref) == num_games
+    nn0 = ag.NeuralNet(env, tower_height=TRAIN["TOWER"], seed=1)
+    ref, snaps, start_step, _ = host_schedule(nn0, TRAIN, lambda eng: eng.set_starts(starts), targets_only=False)
+    _, log = assert_train_equals_twin(
+        env, nn0, TRAIN, (ref, snaps, start_step),
+        lambda cb, gid, on_round: tw.twin_selfplay(N, cb, R, SEED, gid, ostarts[gid % 6], -0.9, 0.05, on_round=on_round),
+        masked=False, starts=starts)
     for x, y in zip(log, ref):
-        a, b = x["record"], y["record"]
-        assert a["game_id"] == b["game_id"] and a["num_moves"] == b["num_moves"] and a["result"] == b["result"]
-        assert a["start"] == b["start"] == int(a["game_id"]) % 6
-        assert (a["moves"] == b["moves"]).all() and bits_equal(a["pis"], b["pis"]) and bits_equal(a["qs"], b["qs"])
-        assert x["loss"] == y["loss"]
-    bad = weight_mismatches(nn.engine, snaps[-1])
-    assert not bad, bad
-    chk.close()
+        assert x["record"]["start"] == y["record"]["start"] == int(x["record"]["game_id"]) % 6

@@ -8,8 +8,9 @@ import pytest
 import alphago_jl_amd as ag
 from alphago_jl_amd import Engine, GoEnv, NeuralNet, load_model, train
 from gpu_common import GpuNetForOracle
+from gpu_options import _lengths, _twin_pairs, _weights
 from test_hostsim_selfplay import bits_equal, oracle_game
-from test_train_loop_batched import sample_entries, sample_syms, window_pairs
+from test_train_loop_batched import sample_syms
 
 pytestmark = pytest.mark.gpu
 N, TOWER, R, SEED = 5, 1, 16, 3
@@ -23,20 +24,6 @@ def _arena(N, games, slots, R, tower=1, seed=1):
         e.step(16)
     assert e.replay_ingest_records(0, games) == games
     return e
-
-
-def _lengths(e):
-    return [e.replay_record(k)["num_moves"] for k in range(e.replay_count())]
-
-
-def _twin_pairs(e, call, B):
-    """what agz_replay_sample must draw: the twin's entries mapped through the arena's current window"""
-    lengths = _lengths(e)
-    live = e.replay_live_positions()
-    first = sum(lengths) - live
-    cum = np.concatenate([[0], np.cumsum(lengths)])
-    fg = int(np.searchsorted(cum, first, side="right") - 1)
-    return window_pairs(lengths, fg, first - int(cum[fg]), sample_entries(e.cfg.seed, call, live, B))
 
 
 @pytest.mark.parametrize("N,games,slots,R,memory,B", [(5, 3, 3, 8, None, 8), (5, 3, 3, 8, "cut", 16),
@@ -65,10 +52,6 @@ def test_sample_equals_twin_and_replay_batch(N, games, slots, R, memory, B):
             wf, wp, wz = e.replay_batch_sym(g, p, s)
         assert bits_equal(feats.cpu().numpy(), wf) and bits_equal(pi.cpu().numpy(), wp) and bits_equal(z.cpu().numpy(), wz)
     e.close()
-
-
-def _weights(eng):
-    return {lk: eng.get_weights(*lk) for lk in eng.layers()}
 
 
 def host_loop(env, nn0, num_games, slots, memory, B, start_after, epochs=1, augment=False, on_start=None, on_game=None):

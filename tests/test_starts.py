@@ -53,6 +53,15 @@ def assert_selfplay_equal(r, o, what):
     assert r["short_searches"] == 0, what
 
 
+def assert_records_identical(got, want):
+    assert len(got) == len(want)
+    for x, y in zip(got, want):
+        for k in ("game_id", "num_moves", "result", "was_resign", "resign_disabled", "short_searches"):
+            assert x[k] == y[k], k
+        assert np.float32(x["final_score"]) == np.float32(y["final_score"])
+        assert (x["moves"] == y["moves"]).all() and bits_equal(x["pis"], y["pis"]) and bits_equal(x["qs"], y["qs"])
+
+
 def assert_arena_equal(r, o, what):
     assert r["num_moves"] == o["num_moves"], (what, r["num_moves"], o["num_moves"])
     assert (r["moves"] == o["moves"]).all(), what
@@ -244,14 +253,22 @@ def test_without_a_table_the_records_are_todays():
             sim.close()
         else:
             got, gct = run_sim(N, net, R, seed, games, 3, starts)
-        assert len(got) == len(want) == games
-        for x, y in zip(got, want):
-            for k in ("game_id", "num_moves", "result", "was_resign", "resign_disabled", "short_searches"):
-                assert x[k] == y[k], k
-            assert np.float32(x["final_score"]) == np.float32(y["final_score"])
-            assert (x["moves"] == y["moves"]).all() and bits_equal(x["pis"], y["pis"]) and bits_equal(x["qs"], y["qs"])
+        assert len(got) == games
+        assert_records_identical(got, want)
         assert gct == wct
     net.close()
+
+
+def test_the_empty_board_is_the_one_entry_table_of_the_empty_position():
+    """what lets game_start make one root_install call: no table and a table of the empty position alone are one run"""
+    for N, R, seed, games, slots in ((5, 16, 2, 5, 3), (9, 16, 4, 2, 2)):
+        net = OracleNet(N, 1, seed=0)
+        want, wct, _ = run_engine(N, net, R, seed, games, slots)
+        got, gct = run_sim(N, net, R, seed, games, slots, [tw.random_start(N, 0, 0)])
+        net.close()
+        assert len(want) == games
+        assert_records_identical(got, want)
+        assert gct == wct
 
 
 def test_board_check_of_the_table():

@@ -14,68 +14,11 @@ off against on in alternating windows of the same process on the same box (the m
           position the mass moved, half the L1 distance of the two rows.
 
 Prints one JSON object."""
-import argparse
 import json
-import os
-import statistics
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def windows_of(eng, args, R):
-    modes = ("off", "on")
-    out = {m: [] for m in modes}
-    live = False
-    for k in range(args.pairs):
-        for mode in (modes if k % 2 == 0 else modes[::-1]):
-            if live:
-                for g in range(args.games):
-                    eng.slot_abandon(g)
-            eng.records_clear()
-            eng.start(0)                      # a run without a step yet: stagger and setting may change here
-            eng._ck(eng.L.agz_debug_set_stagger(eng.h, args.stagger))
-            eng.set_forced_playouts(args.k if mode == "on" else 0.0, True)
-            eng.start(0)
-            live = True
-            eng.step(((R + 7) // 8 + 5 if args.stagger > 0 else 0) + args.warmup)
-            eng.sync()
-            s0, c0 = eng.stats(), eng.forced_counts()
-            eng.profile_search(True)
-            t0 = time.perf_counter()
-            eng.step(args.steps)
-            eng.sync()
-            dt = time.perf_counter() - t0
-            search_ms, search_steps = eng.profile_search_read()
-            eng.profile_search(False)
-            s1, c1 = eng.stats(), eng.forced_counts()
-            moves = s1["positions"] - s0["positions"]
-            evals = s1["evals"] - s0["evals"]
-            forced, rows = c1[0] - c0[0], c1[1] - c0[1]
-            out[mode].append(dict(
-                ms_per_step=round(1e3 * dt / args.steps, 4), moves_per_s=round(moves / dt, 1),
-                evals_per_move=round(evals / max(moves, 1), 2), moves=moves, forced_selections=forced, rows_changed=rows,
-                # every search is full here (no cap); the stagger's shortened first moves are not in `positions`, so
-                # both ratios are slightly high while such games are still about
-                forced_per_full_search=round(forced / max(moves, 1), 3), rows_changed_share=round(rows / max(moves, 1), 4),
-                search_kernels_ms_per_step=round(float(sum(search_ms.values())) / max(search_steps, 1), 4),
-                pool_short_searches=s1["pool_short_searches"] - s0["pool_short_searches"]))
-    return out
-
-
-def summary(windows):
-    res = {}
-    for mode, ws in windows.items():
-        res[mode] = {}
-        for key in ("ms_per_step", "moves_per_s", "evals_per_move", "search_kernels_ms_per_step", "forced_per_full_search",
-                    "rows_changed_share"):
-            v = [w[key] for w in ws]
-            res[mode][key] = dict(median=round(statistics.median(v), 4), spread=round(max(v) - min(v), 4))
-    return res
+import rate_windows as rw
 
 
 def mass_part(args):
@@ -113,39 +56,35 @@ def mass_part(args):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--board", type=int, default=9)
-    ap.add_argument("--tower", type=int, default=10)
-    ap.add_argument("--readouts", type=int, default=400)
+    ap = rw.parser()
     ap.add_argument("--k", type=float, default=2.0, help="forced playouts coefficient (KataGo: 2)")
-    ap.add_argument("--games", type=int, default=1024)
-    ap.add_argument("--stagger", type=int, default=60)
-    ap.add_argument("--steps", type=int, default=100, help="timed steps per window")
-    ap.add_argument("--pairs", type=int, default=3, help="rounds of the windows (the order reverses every round)")
-    ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--mass-plies", type=int, default=40, help="positions of the single-tree game of the mass part")
     args = ap.parse_args()
 
-    import alphago_jl_amd as ag
+    def configure(eng, mode):
+        rw.set_stagger(eng, args.stagger)
+        eng.set_forced_playouts(args.k if mode == "on" else 0.0, True)
 
-    N, R = args.board, args.readouts
-    eng = ag.Engine(board_size=N, tower_height=args.tower, games=args.games, num_readouts=R, parallel_readouts=8, seed=1,
-                    record_capacity_games=2 * args.games + 64)
-    eng.init_synthetic(0)
-    windows = windows_of(eng, args, R)
+    def collect(s0, s1, c0, c1, dt):
+        moves = s1["positions"] - s0["positions"]
+        forced, rows = c1[0] - c0[0], c1[1] - c0[1]
+        # every search is full here (no cap); the stagger's shortened first moves are not in `positions`, so both ratios
+        # are slightly high while such games are still about
+        return dict(forced_selections=forced, rows_changed=rows, forced_per_full_search=round(forced / max(moves, 1), 3),
+                    rows_changed_share=round(rows / max(moves, 1), 4))
+
+    eng = rw.engine(args)
+    windows = rw.windows_of(eng, args, ("off", "on"), configure, collect,
+                            rw.first_search_steps(args) if args.stagger > 0 else 0, lambda e: e.forced_counts())
     eng.close()
-    res = summary(windows)
+    res = rw.summary(windows, ("ms_per_step", "moves_per_s", "evals_per_move", "search_kernels_ms_per_step",
+                               "forced_per_full_search", "rows_changed_share"))
     print(json.dumps(dict(
-        shape=dict(board=N, tower=args.tower, readouts=R, k=args.k, prune=True, games=args.games, stagger=args.stagger),
+        shape=dict(board=args.board, tower=args.tower, readouts=args.readouts, k=args.k, prune=True, games=args.games,
+                   stagger=args.stagger),
         steps_per_window=args.steps, windows=windows, summary=res,
-        measured=dict(
-            ms_per_step_on_minus_off=round(res["on"]["ms_per_step"]["median"] - res["off"]["ms_per_step"]["median"], 4),
-            search_kernels_on_minus_off=round(res["on"]["search_kernels_ms_per_step"]["median"]
-                                              - res["off"]["search_kernels_ms_per_step"]["median"], 4),
-            off_spread_ms_per_step=res["off"]["ms_per_step"]["spread"],
-            off_spread_search_kernels=res["off"]["search_kernels_ms_per_step"]["spread"],
-            forced_per_full_search=res["on"]["forced_per_full_search"]["median"],
-            rows_changed_share=res["on"]["rows_changed_share"]["median"]),
+        measured=dict(rw.measured(res), forced_per_full_search=res["on"]["forced_per_full_search"]["median"],
+                      rows_changed_share=res["on"]["rows_changed_share"]["median"]),
         mass=mass_part(args))))
 
 

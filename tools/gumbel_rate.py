@@ -14,67 +14,11 @@ alternating windows of the same process on the same box (the method of tools/for
           entropy of the Gumbel target row against that of children_as_pi on the same visits.
 
 Prints one JSON object."""
-import argparse
 import json
-import os
-import statistics
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def windows_of(eng, args, R):
-    modes = ("off", "on")
-    out = {m: [] for m in modes}
-    live = False
-    for k in range(args.pairs):
-        for mode in (modes if k % 2 == 0 else modes[::-1]):
-            if live:
-                for g in range(args.games):
-                    eng.slot_abandon(g)
-            eng.records_clear()
-            eng.start(0)                      # a run without a step yet: stagger and setting may change here
-            eng._ck(eng.L.agz_debug_set_stagger(eng.h, args.stagger))
-            eng.set_gumbel(args.m if mode == "on" else 0, args.c_visit, args.c_scale)
-            eng.start(0)
-            live = True
-            eng.step(((R + 7) // 8 + 5 if args.stagger > 0 else 0) + args.warmup)
-            eng.sync()
-            s0, c0 = eng.stats(), eng.gumbel_counts()
-            eng.profile_search(True)
-            t0 = time.perf_counter()
-            eng.step(args.steps)
-            eng.sync()
-            dt = time.perf_counter() - t0
-            search_ms, search_steps = eng.profile_search_read()
-            eng.profile_search(False)
-            s1, c1 = eng.stats(), eng.gumbel_counts()
-            moves = s1["positions"] - s0["positions"]
-            evals = s1["evals"] - s0["evals"]
-            begun, halved = c1[0] - c0[0], c1[1] - c0[1]
-            out[mode].append(dict(
-                ms_per_step=round(1e3 * dt / args.steps, 4), moves_per_s=round(moves / dt, 1),
-                evals_per_move=round(evals / max(moves, 1), 2), moves=moves,
-                leaves_per_select_phase=round(evals / (args.games * args.steps), 3),
-                searches_begun=begun, halvings=halved, halvings_per_search=round(halved / max(begun, 1), 3),
-                search_kernels_ms_per_step=round(float(sum(search_ms.values())) / max(search_steps, 1), 4),
-                pool_short_searches=s1["pool_short_searches"] - s0["pool_short_searches"]))
-    return out
-
-
-def summary(windows):
-    res = {}
-    for mode, ws in windows.items():
-        res[mode] = {}
-        for key in ("ms_per_step", "moves_per_s", "evals_per_move", "leaves_per_select_phase",
-                    "search_kernels_ms_per_step", "halvings_per_search"):
-            v = [w[key] for w in ws]
-            res[mode][key] = dict(median=round(statistics.median(v), 4), spread=round(max(v) - min(v), 4))
-    return res
+import rate_windows as rw
 
 
 def entropy(row):
@@ -124,42 +68,36 @@ def rows_part(args):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--board", type=int, default=9)
-    ap.add_argument("--tower", type=int, default=10)
-    ap.add_argument("--readouts", type=int, default=400)
+    ap = rw.parser()
     ap.add_argument("--m", type=int, default=16, help="root candidates of the Gumbel search")
     ap.add_argument("--c-visit", type=float, default=50.0)
     ap.add_argument("--c-scale", type=float, default=1.0)
-    ap.add_argument("--games", type=int, default=1024)
-    ap.add_argument("--stagger", type=int, default=60)
-    ap.add_argument("--steps", type=int, default=100, help="timed steps per window")
-    ap.add_argument("--pairs", type=int, default=3, help="rounds of the windows (the order reverses every round)")
-    ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--rows-slots", type=int, default=8, help="slots of the engine of the rows part")
     ap.add_argument("--rows-steps", type=int, default=400, help="most steps of the rows part")
     ap.add_argument("--rows-samples", type=int, default=100, help="moves the rows part stops at")
     args = ap.parse_args()
 
-    import alphago_jl_amd as ag
+    def configure(eng, mode):
+        rw.set_stagger(eng, args.stagger)
+        eng.set_gumbel(args.m if mode == "on" else 0, args.c_visit, args.c_scale)
 
-    N, R = args.board, args.readouts
-    eng = ag.Engine(board_size=N, tower_height=args.tower, games=args.games, num_readouts=R, parallel_readouts=8, seed=1,
-                    record_capacity_games=2 * args.games + 64)
-    eng.init_synthetic(0)
-    windows = windows_of(eng, args, R)
+    def collect(s0, s1, c0, c1, dt):
+        begun, halved = c1[0] - c0[0], c1[1] - c0[1]
+        return dict(leaves_per_select_phase=round((s1["evals"] - s0["evals"]) / (args.games * args.steps), 3),
+                    searches_begun=begun, halvings=halved, halvings_per_search=round(halved / max(begun, 1), 3))
+
+    eng = rw.engine(args)
+    windows = rw.windows_of(eng, args, ("off", "on"), configure, collect,
+                            rw.first_search_steps(args) if args.stagger > 0 else 0, lambda e: e.gumbel_counts())
     eng.close()
-    res = summary(windows)
+    res = rw.summary(windows, ("ms_per_step", "moves_per_s", "evals_per_move", "leaves_per_select_phase",
+                               "search_kernels_ms_per_step", "halvings_per_search"))
     print(json.dumps(dict(
-        shape=dict(board=N, tower=args.tower, readouts=R, m=args.m, c_visit=args.c_visit, c_scale=args.c_scale,
-                   games=args.games, stagger=args.stagger),
+        shape=dict(board=args.board, tower=args.tower, readouts=args.readouts, m=args.m, c_visit=args.c_visit,
+                   c_scale=args.c_scale, games=args.games, stagger=args.stagger),
         steps_per_window=args.steps, windows=windows, summary=res,
         measured=dict(
-            ms_per_step_on_minus_off=round(res["on"]["ms_per_step"]["median"] - res["off"]["ms_per_step"]["median"], 4),
-            search_kernels_on_minus_off=round(res["on"]["search_kernels_ms_per_step"]["median"]
-                                              - res["off"]["search_kernels_ms_per_step"]["median"], 4),
-            off_spread_ms_per_step=res["off"]["ms_per_step"]["spread"],
-            off_spread_search_kernels=res["off"]["search_kernels_ms_per_step"]["spread"],
+            rw.measured(res),
             evals_per_move=dict(off=res["off"]["evals_per_move"]["median"], on=res["on"]["evals_per_move"]["median"]),
             leaves_per_select_phase=dict(off=res["off"]["leaves_per_select_phase"]["median"],
                                          on=res["on"]["leaves_per_select_phase"]["median"]),

@@ -12,66 +12,11 @@ against cap on in alternating windows of the same process on the same box.
           arena (the difference is the scan kernel and its read-back) and agz_replay_sample from both, ms per call.
 
 Prints one JSON object."""
-import argparse
 import json
-import os
 import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def windows_of(eng, args, R):
-    modes = ("off", "on")
-    out = {m: [] for m in modes}
-    live = False
-    for k in range(args.pairs):
-        for mode in (modes if k % 2 == 0 else modes[::-1]):
-            if live:
-                for g in range(args.games):
-                    eng.slot_abandon(g)
-            eng.records_clear()
-            eng.start(0)                      # a run without a step yet: stagger and cap may change here
-            eng._ck(eng.L.agz_debug_set_stagger(eng.h, args.stagger))
-            eng.set_playout_cap(args.fast if mode == "on" else 0, args.prob)
-            eng.start(0)
-            live = True
-            eng.step(((R + 7) // 8 + 5 if args.stagger > 0 else 0) + args.warmup)
-            eng.sync()
-            s0, c0 = eng.stats(), eng.playout_cap_counts()
-            eng.profile_search(True)
-            t0 = time.perf_counter()
-            eng.step(args.steps)
-            eng.sync()
-            dt = time.perf_counter() - t0
-            search_ms, search_steps = eng.profile_search_read()
-            eng.profile_search(False)
-            s1, c1 = eng.stats(), eng.playout_cap_counts()
-            moves = s1["positions"] - s0["positions"]
-            evals = s1["evals"] - s0["evals"]
-            full, fast = c1[0] - c0[0], c1[1] - c0[1]
-            # both modes from the same counter: agz_stats.positions leaves out the stagger's shortened first moves, which
-            # the cap counts as full, so the on-mode targets are the counted moves that were not fast
-            targets = moves - fast
-            out[mode].append(dict(
-                ms_per_step=round(1e3 * dt / args.steps, 4), moves_per_s=round(moves / dt, 1),
-                target_positions_per_s=round(targets / dt, 1), evals_per_move=round(evals / max(moves, 1), 2),
-                evals_per_step=round(evals / args.steps, 1), moves=moves, full=full, fast=fast,
-                search_kernels_ms_per_step=round(float(sum(search_ms.values())) / max(search_steps, 1), 4),
-                pool_short_searches=s1["pool_short_searches"] - s0["pool_short_searches"]))
-    return out
-
-
-def summary(windows):
-    res = {}
-    for mode, ws in windows.items():
-        res[mode] = {}
-        for key in ("ms_per_step", "moves_per_s", "target_positions_per_s", "evals_per_move", "search_kernels_ms_per_step"):
-            v = [w[key] for w in ws]
-            res[mode][key] = dict(median=round(statistics.median(v), 4), spread=round(max(v) - min(v), 4))
-    return res
+import rate_windows as rw
 
 
 def arena_part(args):
@@ -125,32 +70,34 @@ def arena_part(args):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--board", type=int, default=9)
-    ap.add_argument("--tower", type=int, default=10)
-    ap.add_argument("--readouts", type=int, default=400)
+    ap = rw.parser()
     ap.add_argument("--fast", type=int, default=64, help="readouts of a fast search (r)")
     ap.add_argument("--prob", type=float, default=0.25, help="probability of a full search (p)")
-    ap.add_argument("--games", type=int, default=1024)
-    ap.add_argument("--stagger", type=int, default=60)
-    ap.add_argument("--steps", type=int, default=100, help="timed steps per window")
-    ap.add_argument("--pairs", type=int, default=3, help="rounds of the windows (the order reverses every round)")
-    ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--arena-games", type=int, default=512)
     ap.add_argument("--arena-batch", type=int, default=2048)
     ap.add_argument("--arena-calls", type=int, default=20)
     ap.add_argument("--arena-rounds", type=int, default=3, help="timed ingest rounds per arena mode, behind one warm-up")
     args = ap.parse_args()
-
-    import alphago_jl_amd as ag
-
     N, R = args.board, args.readouts
-    eng = ag.Engine(board_size=N, tower_height=args.tower, games=args.games, num_readouts=R, parallel_readouts=8, seed=1,
-                    record_capacity_games=2 * args.games + 64)
-    eng.init_synthetic(0)
-    windows = windows_of(eng, args, R)
+
+    def configure(eng, mode):
+        rw.set_stagger(eng, args.stagger)
+        eng.set_playout_cap(args.fast if mode == "on" else 0, args.prob)
+
+    def collect(s0, s1, c0, c1, dt):
+        moves = s1["positions"] - s0["positions"]
+        full, fast = c1[0] - c0[0], c1[1] - c0[1]
+        # both modes from the same counter: agz_stats.positions leaves out the stagger's shortened first moves, which
+        # the cap counts as full, so the on-mode targets are the counted moves that were not fast
+        return dict(target_positions_per_s=round((moves - fast) / dt, 1), full=full, fast=fast,
+                    evals_per_step=round((s1["evals"] - s0["evals"]) / args.steps, 1))
+
+    eng = rw.engine(args)
+    windows = rw.windows_of(eng, args, ("off", "on"), configure, collect,
+                            rw.first_search_steps(args) if args.stagger > 0 else 0, lambda e: e.playout_cap_counts())
     eng.close()
-    res = summary(windows)
+    res = rw.summary(windows, ("ms_per_step", "moves_per_s", "target_positions_per_s", "evals_per_move",
+                               "search_kernels_ms_per_step"))
     mean_readouts = args.prob * R + (1 - args.prob) * args.fast
     print(json.dumps(dict(
         shape=dict(board=N, tower=args.tower, readouts=R, fast_readouts=args.fast, full_prob=args.prob, games=args.games,
@@ -161,7 +108,7 @@ def main():
             moves_per_s_ratio=round(res["on"]["moves_per_s"]["median"] / max(res["off"]["moves_per_s"]["median"], 1e-9), 3),
             target_positions_per_s_ratio=round(res["on"]["target_positions_per_s"]["median"]
                                                / max(res["off"]["target_positions_per_s"]["median"], 1e-9), 3),
-            ms_per_step_on_minus_off=round(res["on"]["ms_per_step"]["median"] - res["off"]["ms_per_step"]["median"], 4)),
+            ms_per_step_on_minus_off=rw.on_minus_off(res, "ms_per_step")),
         arena=arena_part(args))))
 
 

@@ -21,17 +21,13 @@ Three parts, each on one engine:
 A table can be set only while no game is being played and the bench stagger excludes it, so every window is a run of
 its own: the slots of the previous window are given up (agz_slot_abandon), the mode is set, the run is started,
 stepped through its first search plus a warm-up, and then K steps are timed.  Prints one JSON object."""
-import argparse
 import json
-import os
 import statistics
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import rate_windows as rw
 
 
 def midgame_starts(eng, S, lo, hi, seed, komi=7.5):
@@ -84,47 +80,30 @@ def midgame_starts(eng, S, lo, hi, seed, komi=7.5):
     return boards, info, hist
 
 
-def windows_of(eng, args, modes, tables, R):
-    """alternating timed windows of `modes` on one engine -> (ms per step, games started inside each window)"""
-    windows = {m: [] for m in modes}
-    started = {m: [] for m in modes}
+def windows_of(eng, args, modes, tables):
+    """alternating timed windows of `modes` on one engine -> (ms per step, games started inside each window, ms of
+    each set_starts call)"""
     set_ms = []
-    live = False
 
-    def stagger(n):
-        eng._ck(eng.L.agz_debug_set_stagger(eng.h, n))
+    def configure(eng, mode):
+        if mode == "off_stagger":
+            eng.set_starts(None)
+            rw.set_stagger(eng, args.stagger)
+            return
+        rw.set_stagger(eng, 0)
+        t0 = time.perf_counter()
+        if mode == "off":
+            eng.set_starts(None)
+        else:
+            tb = tables[mode]
+            eng.set_starts(boards=tb[0], info=tb[1], history=tb[2])
+        set_ms.append(round(1e3 * (time.perf_counter() - t0), 3))
 
-    for k in range(args.pairs):
-        order = modes if k % 2 == 0 else modes[::-1]
-        for mode in order:
-            if live:                          # give the previous window's games up: a table changes between runs only
-                for g in range(args.games):
-                    eng.slot_abandon(g)
-            eng.records_clear()
-            eng.start(0)                      # a run without a step yet: the stagger may change here
-            if mode == "off_stagger":
-                eng.set_starts(None)
-                stagger(args.stagger)
-            else:
-                stagger(0)
-                t0 = time.perf_counter()
-                if mode == "off":
-                    eng.set_starts(None)
-                else:
-                    tb = tables[mode]
-                    eng.set_starts(boards=tb[0], info=tb[1], history=tb[2])
-                set_ms.append(round(1e3 * (time.perf_counter() - t0), 3))
-            eng.start(0)
-            live = True
-            eng.step((R + 7) // 8 + 5 + args.warmup)
-            eng.sync()
-            s0 = eng.stats()["games_started"]
-            t0 = time.perf_counter()
-            eng.step(args.steps)
-            eng.sync()
-            windows[mode].append(round(1e3 * (time.perf_counter() - t0) / args.steps, 4))
-            started[mode].append(eng.stats()["games_started"] - s0)
-    return windows, started, set_ms
+    ws = rw.windows_of(eng, args, modes, configure,
+                       lambda s0, s1, c0, c1, dt: dict(games_started=s1["games_started"] - s0["games_started"]),
+                       rw.first_search_steps(args), profile=False)
+    return ({m: [w["ms_per_step"] for w in v] for m, v in ws.items()},
+            {m: [w["games_started"] for w in v] for m, v in ws.items()}, set_ms)
 
 
 def summary(windows):
@@ -170,39 +149,25 @@ def replay_part(args, tables):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--board", type=int, default=9)
-    ap.add_argument("--tower", type=int, default=10)
-    ap.add_argument("--readouts", type=int, default=400)
-    ap.add_argument("--games", type=int, default=1024)
+    ap = rw.parser()          # --stagger is the off_stagger windows' alone
     ap.add_argument("--starts", type=int, default=1024)
-    ap.add_argument("--stagger", type=int, default=60, help="the bench stagger of the off_stagger windows")
-    ap.add_argument("--steps", type=int, default=100, help="timed steps per window (two searches of 400 readouts)")
-    ap.add_argument("--pairs", type=int, default=3, help="rounds of the windows (the order reverses every round)")
-    ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--replay-games", type=int, default=512)
     ap.add_argument("--replay-batch", type=int, default=2048)
     ap.add_argument("--replay-calls", type=int, default=20)
     args = ap.parse_args()
 
-    import alphago_jl_amd as ag
-
     N, R = args.board, args.readouts
-    cfg = dict(board_size=N, tower_height=args.tower, games=args.games, num_readouts=R, parallel_readouts=8, seed=1,
-               record_capacity_games=2 * args.games + 64)
-    eng = ag.Engine(**cfg)
-    eng.init_synthetic(0)
+    eng = rw.engine(args)
     t0 = time.perf_counter()
     tables = dict(on=midgame_starts(eng, args.starts, N * N // 4, N * N // 2, seed=7))
     t_gen = time.perf_counter() - t0
     tables["on_empty"] = midgame_starts(eng, args.starts, 0, 0, seed=7)
-    search, search_started, set_ms = windows_of(eng, args, ("off", "on_empty", "on", "off_stagger"), tables, R)
+    search, search_started, set_ms = windows_of(eng, args, ("off", "on_empty", "on", "off_stagger"), tables)
     short = eng.stats()["pool_short_searches"]
     eng.close()
     # no game survives its first move phase: Q_perspective(root) < 2 always (mcts_play.jl:124)
-    eng = ag.Engine(resign_threshold=2.0, resign_disable_fraction=0.0, **cfg)
-    eng.init_synthetic(0)
-    turn, turn_started, _ = windows_of(eng, args, ("off", "on_empty", "on"), tables, R)
+    eng = rw.engine(args, resign_threshold=2.0, resign_disable_fraction=0.0)
+    turn, turn_started, _ = windows_of(eng, args, ("off", "on_empty", "on"), tables)
     eng.close()
     rp = replay_part(args, tables)
     med, spread = summary(search)
