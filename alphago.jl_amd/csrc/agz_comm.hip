@@ -169,10 +169,10 @@ int64_t comm_allgather_records(Engine& E, Comm* c) {
     my_error = x.what();
   }
   // 2. counts
-  AGZ_HIP(hipMemcpyAsync(c->d_counts.p, mine, sizeof(mine), hipMemcpyHostToDevice, s));
+  upload(c->d_counts.p, mine, 2, s);
   AGZ_RCCL(rccl().AllGather(c->d_counts.p, c->d_counts.p + 2, 2, ncclInt64, c->comm, s));
   std::vector<int64_t> counts((size_t)2 * W);
-  AGZ_HIP(hipMemcpyAsync(counts.data(), c->d_counts.p + 2, sizeof(int64_t) * counts.size(), hipMemcpyDeviceToHost, s));
+  download(counts.data(), c->d_counts.p + 2, counts.size(), s);
   AGZ_HIP(hipStreamSynchronize(s));
   int64_t total = 0;
   // (a rank that failed reports AGZ_RCCL_ERROR like its peers -- the plan names it -- with its own reason appended)

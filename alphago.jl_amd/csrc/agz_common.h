@@ -68,6 +68,44 @@ struct DevBuf {
   }
 };
 
+// ---- host <-> device staging, written once.  Every copy is asynchronous on the caller's stream and counts ELEMENTS of
+// T: the byte count comes from the type, and host and device pointers must agree on it.  The rules the callers keep:
+//  * a copy from or into host memory that the caller owns on its stack or in a vector is followed by a
+//    hipStreamSynchronize before that memory dies (fetch / put do it themselves);
+//  * several downloads of one entry point share one synchronise: download() never waits;
+//  * stage() grows the buffer first, so within one call every pointer into a staging buffer is taken after the last
+//    ensure()/stage() of that buffer; a buffer that plays several roles in one call is ensure()d once for all of them
+//    and filled with upload() at offsets;
+//  * n == 0 copies nothing, and download() into a NULL host pointer is a no-op (an output the caller does not want).
+template <class T>
+void upload(T* dev, const T* host, size_t n, hipStream_t s) {
+  if (n) AGZ_HIP(hipMemcpyAsync(dev, host, sizeof(T) * n, hipMemcpyHostToDevice, s));
+}
+template <class T>
+void download(T* host, const T* dev, size_t n, hipStream_t s) {
+  if (host && n) AGZ_HIP(hipMemcpyAsync(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost, s));
+}
+// n elements into a staging buffer, grown as needed; the device pointer to use from here on
+template <class T>
+T* stage(DevBuf<T>& buf, const T* host, size_t n, hipStream_t s) {
+  buf.ensure(n);
+  upload(buf.p, host, n, s);
+  return buf.p;
+}
+// one object down (or up) and the synchronise: the accessors that read or write exactly one thing
+template <class T>
+T fetch(const T* dev, hipStream_t s) {
+  T v;
+  download(&v, dev, 1, s);
+  AGZ_HIP(hipStreamSynchronize(s));
+  return v;
+}
+template <class T>
+void put(T* dev, const T& v, hipStream_t s) {
+  upload(dev, &v, 1, s);
+  AGZ_HIP(hipStreamSynchronize(s));
+}
+
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace agz

@@ -182,7 +182,25 @@ class Engine {
   void read_counter_pair(int first, int64_t out[2]);
   template <class Launch>
   void read_tree_pi_row(float* out, Launch launch);
+  void set_all_slots(int phase);
   void idle_all_slots();
+  // host <-> device staging on stream_ (the primitives and their rules: agz_common.h)
+  template <class T> T* stage(DevBuf<T>& b, const T* host, size_t n) { return agz::stage(b, host, n, stream_); }
+  template <class T> void up(T* dev, const T* host, size_t n) { agz::upload(dev, host, n, stream_); }
+  template <class T> void down(T* host, const T* dev, size_t n) { agz::download(host, dev, n, stream_); }
+  template <class T> T fetch(const T* dev) { return agz::fetch(dev, stream_); }
+  template <class T> void put(T* dev, const T& v) { agz::put(dev, v, stream_); }
+  void wait() { AGZ_HIP(hipStreamSynchronize(stream_)); }
+  // the shared steps of the ABI calls (agz_engine.hip)
+  void stage_positions(const int8_t* boards, const int8_t* deltas, const int32_t* ndeltas, const int8_t* to_play, int B);
+  float* stage_forward(const int& B);
+  void forward_x32(int B);
+  void forward_staged(int B, const int32_t* d_sym, float* pi_out, float* v_out);
+  template <class Launch>
+  float time_launches(int iters, Launch launch);
+  void emit_replay_batch(int B, const int64_t* off, const int32_t* ply, const int32_t* sym, int8_t* boards, float* feats,
+                         float* pi, float* z);
+  size_t packed_layout(int64_t first, int64_t last, std::vector<int64_t>& off);
 
   agz_config cfg_;
   View V_{};
@@ -258,7 +276,6 @@ class Engine {
   DevBuf<int64_t> smp_off_, smp_game_;
   DevBuf<int32_t> smp_ply_, smp_sym_;
   DevBuf<int8_t> smp_boards_;
-  DevBuf<float> smp_f_, smp_p_;
   DevBuf<int32_t> hold_rel_;        // View::released
   DevBuf<int8_t> st_board_, st_hist_;       // the start-position table in force (View::st_*)
   DevBuf<agz_position_info> st_info_;

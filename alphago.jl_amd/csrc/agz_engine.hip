@@ -682,12 +682,7 @@ Engine::Engine(const agz_config& cfg) : cfg_(cfg) {
   s_iout_.alloc(4);
   net_.reset(new Net(V_.N, cfg.tower_height, stream_));
   if (cfg.arena_mode) net2_.reset(new Net(V_.N, cfg.tower_height, stream_));
-  // every slot idle-retired until start()
-  std::vector<GameState> gs(V_.games);
-  std::memset(gs.data(), 0, sizeof(GameState) * gs.size());
-  for (auto& g : gs) g.phase = G_RETIRED;
-  AGZ_HIP(hipMemcpyAsync(V_.gs, gs.data(), sizeof(GameState) * gs.size(), hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  set_all_slots(G_RETIRED);      // every slot idle-retired until start()
 }
 
 Engine::~Engine() {
@@ -704,7 +699,7 @@ Engine::~Engine() {
 }
 
 void Engine::sync() {
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
   // an error word a persistent tower launch raised is reported by the first synchronising call behind it, not only by
   // the next persistent forward
   net_->check_async_error();
@@ -730,14 +725,16 @@ void Engine::start(int64_t total_games) {
   idle_all_slots();
 }
 
-// every slot idle and zeroed, as a run finds them; returns with the stream idle
-void Engine::idle_all_slots() {
+// every slot zeroed and in `phase`; returns with the stream idle
+void Engine::set_all_slots(int phase) {
   std::vector<GameState> gs(V_.games);
   std::memset(gs.data(), 0, sizeof(GameState) * gs.size());
-  for (auto& g : gs) g.phase = G_IDLE;
-  AGZ_HIP(hipMemcpyAsync(V_.gs, gs.data(), sizeof(GameState) * gs.size(), hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  for (auto& g : gs) g.phase = phase;
+  up(V_.gs, gs.data(), gs.size());
+  wait();
 }
+// every slot idle and zeroed, as a run finds them
+void Engine::idle_all_slots() { set_all_slots(G_IDLE); }
 
 void Engine::step(int nsteps) {
   AGZ_REQUIRE(!cfg_.external_network, AGZ_BAD_ARGUMENT,
@@ -784,7 +781,7 @@ void Engine::analyze_start(const int8_t* boards, const agz_position_info* info, 
   require_selfplay_engine("analysis");
   AGZ_REQUIRE(boards && info && B >= 1, AGZ_BAD_ARGUMENT, "analysis: boards and info of B >= 1 positions");
   check_positions("analysis", "position", info, history, B);
-  AGZ_HIP(hipStreamSynchronize(stream_));     // nothing in flight may still read the tables that are replaced here
+  wait();     // nothing in flight may still read the tables that are replaced here
   upload_positions(boards, info, history, B, B);
   V_.review = 0;
   V_.rv_moves = nullptr;
@@ -826,8 +823,8 @@ static void check_lines(int K, int K_min, int D, int min_visits) {
 // counters[first] and counters[first + 1]: {full, fast} moves, {forced descents, pruned rows}, {begun, halved}
 void Engine::read_counter_pair(int first, int64_t out[2]) {
   unsigned long long c[2];
-  AGZ_HIP(hipMemcpyAsync(c, V_.counters + first, sizeof(c), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(c, V_.counters + first, 2);
+  wait();
   out[0] = (int64_t)c[0];
   out[1] = (int64_t)c[1];
 }
@@ -844,8 +841,8 @@ void Engine::read_tree_pi_row(float* out, Launch launch) {
   s_f32a_.ensure(V_.A);
   launch(s_f32a_.p);
   AGZ_HIP(hipGetLastError());
-  AGZ_HIP(hipMemcpyAsync(out, s_f32a_.p, sizeof(float) * V_.A, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(out, s_f32a_.p, (size_t)V_.A);
+  wait();
 }
 
 void Engine::set_playout_cap(int fast_readouts, double full_prob) {
@@ -855,7 +852,7 @@ void Engine::set_playout_cap(int fast_readouts, double full_prob) {
   AGZ_REQUIRE(fast_readouts == 0 || (full_prob >= 0.0 && full_prob <= 1.0), AGZ_BAD_ARGUMENT,
               "playout cap: full_prob %g not in [0, 1]", full_prob);
   require_between_games("playout cap");
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
   view_set_playout_cap(V_, fast_readouts, full_prob);
 }
 
@@ -865,7 +862,7 @@ void Engine::set_forced_playouts(double k, int prune) {
   AGZ_REQUIRE(prune == 0 || k > 0.0, AGZ_BAD_ARGUMENT, "forced playouts: pruning needs k > 0");
   AGZ_REQUIRE(!(k > 0.0) || V_.gumbel_m == 0, AGZ_BAD_ARGUMENT, "forced playouts: the Gumbel root search is on (m = %d)", V_.gumbel_m);
   require_between_games("forced playouts");
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
   view_set_forced_playouts(V_, k, prune);
 }
 
@@ -884,7 +881,7 @@ void Engine::set_gumbel(int m, double c_visit, double c_scale) {
   check_gumbel_c("gumbel", c_visit, c_scale);
   AGZ_REQUIRE(m == 0 || !(V_.forced_k > 0.0), AGZ_BAD_ARGUMENT, "gumbel: forced playouts are on (k = %g)", V_.forced_k);
   require_between_games("gumbel");
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
   view_set_gumbel(V_, m, c_visit, c_scale);
 }
 
@@ -920,7 +917,7 @@ void Engine::set_starts(const int8_t* boards, const agz_position_info* info, con
                   (long long)i, info[i].n, mgl);
     }
   }
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
   if (S == 0) {
     V_.st_count = 0;
     V_.st_board = nullptr;
@@ -938,8 +935,8 @@ void Engine::set_starts(const int8_t* boards, const agz_position_info* info, con
                      (const agz_position_info*)ni.p, ok.p);
   AGZ_HIP(hipGetLastError());
   std::vector<int32_t> good((size_t)S);
-  AGZ_HIP(hipMemcpyAsync(good.data(), ok.p, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(good.data(), ok.p, (size_t)S);
+  wait();
   for (int64_t i = 0; i < S; ++i)
     AGZ_REQUIRE(good[(size_t)i], AGZ_BAD_ARGUMENT,
                 "starts: entry %lld: bad board (a point outside -1..1, a group without liberty or a stone on the ko point)",
@@ -978,13 +975,11 @@ void Engine::check_positions(const char* mode, const char* item, const agz_posit
 void Engine::upload_position_table(DevBuf<int8_t>& board, DevBuf<int8_t>& hist, DevBuf<agz_position_info>& inf,
                                    const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B) {
   const size_t nb = (size_t)B * V_.P;
-  board.ensure(nb);
+  stage(board, boards, nb);
   hist.ensure(7 * nb);
-  inf.ensure((size_t)B);
-  AGZ_HIP(hipMemcpyAsync(board.p, boards, nb, hipMemcpyHostToDevice, stream_));
-  if (history) AGZ_HIP(hipMemcpyAsync(hist.p, history, 7 * nb, hipMemcpyHostToDevice, stream_));
+  if (history) up(hist.p, history, 7 * nb);
   else AGZ_HIP(hipMemsetAsync(hist.p, 0, 7 * nb, stream_));
-  AGZ_HIP(hipMemcpyAsync(inf.p, info, sizeof(agz_position_info) * (size_t)B, hipMemcpyHostToDevice, stream_));
+  stage(inf, info, (size_t)B);
 }
 
 // B positions into the an_* tables, result tables of `rows` rows cleared (the stream is idle)
@@ -1026,16 +1021,15 @@ void Engine::begin_analysis_run(int64_t B, int64_t rows, uint64_t game_id_base) 
   V_.an_pvN = nullptr;
   if (lines_k_ > 0) {
     const size_t nl = R * (size_t)lines_k_, np = nl * (size_t)lines_d_;
-    an_line_.ensure(nl);
     an_pv_.ensure(np);
     an_pvN_.ensure(np);
     agz_line unused;
     unused.move = -1; unused.pv_len = 0; unused.N = 0.f; unused.W = 0.f; unused.prior = 0.f; unused.end_W = 0.f;
     const std::vector<agz_line> fill(nl, unused);
-    AGZ_HIP(hipMemcpyAsync(an_line_.p, fill.data(), sizeof(agz_line) * nl, hipMemcpyHostToDevice, stream_));
+    stage(an_line_, fill.data(), nl);
     AGZ_HIP(hipMemsetAsync(an_pv_.p, 0xff, sizeof(int16_t) * np, stream_));
     AGZ_HIP(hipMemsetAsync(an_pvN_.p, 0, sizeof(float) * np, stream_));
-    AGZ_HIP(hipStreamSynchronize(stream_));
+    wait();                      // `fill` dies here
     V_.an_line = an_line_.p;
     V_.an_pv = an_pv_.p;
     V_.an_pvN = an_pvN_.p;
@@ -1055,10 +1049,10 @@ void Engine::analyze_lines(agz_line* lines, int16_t* pv, float* pv_N) {
   AGZ_REQUIRE(V_.an_lines > 0, AGZ_BAD_ARGUMENT, "lines: the run was started with lines off (agz_analyze_set_lines)");
   AGZ_REQUIRE(done >= B, AGZ_NOT_READY, "analysis: %lld of %lld rows finished", (long long)done, (long long)B);
   const size_t nl = (size_t)B * V_.an_lines, np = nl * V_.an_pv_depth;
-  if (lines && nl) AGZ_HIP(hipMemcpyAsync(lines, an_line_.p, sizeof(agz_line) * nl, hipMemcpyDeviceToHost, stream_));
-  if (pv && np) AGZ_HIP(hipMemcpyAsync(pv, an_pv_.p, sizeof(int16_t) * np, hipMemcpyDeviceToHost, stream_));
-  if (pv_N && np) AGZ_HIP(hipMemcpyAsync(pv_N, an_pvN_.p, sizeof(float) * np, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(lines, an_line_.p, nl);
+  down(pv, an_pv_.p, np);
+  down(pv_N, an_pvN_.p, np);
+  wait();
 }
 
 // the lines of any node of single tree g: one launch, one copy (the three tables lie behind one another in s_lines_)
@@ -1072,8 +1066,8 @@ void Engine::tree_lines(int g, int node, int K, int D, int min_visits, agz_line*
   hipLaunchKernelGGL(k_tree_lines, dim3(1), dim3(kWave), 0, stream_, V_, g, node, K, D, min_visits, (agz_line*)d,
                      (int16_t*)(d + off_pv), (float*)(d + off_n));
   std::vector<uint8_t> h(total);
-  AGZ_HIP(hipMemcpyAsync(h.data(), d, total, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(h.data(), d, total);
+  wait();
   if (lines) std::memcpy(lines, h.data(), off_n);
   if (pv_N) std::memcpy(pv_N, h.data() + off_n, sizeof(float) * kd);
   if (pv) std::memcpy(pv, h.data() + off_pv, sizeof(int16_t) * kd);
@@ -1109,12 +1103,11 @@ void Engine::review_start(const int16_t* moves, const int64_t* game_offset, cons
     info = dinfo.data();
   }
   check_positions("review", "game", info, history, G);
-  AGZ_HIP(hipStreamSynchronize(stream_));     // nothing in flight may still read the tables that are replaced here
+  wait();     // nothing in flight may still read the tables that are replaced here
   upload_positions(boards, info, history, G, total);
   rv_moves_.ensure((size_t)(total > 0 ? total : 1));
-  rv_off_.ensure((size_t)G + 1);
-  if (total > 0) AGZ_HIP(hipMemcpyAsync(rv_moves_.p, moves, sizeof(int16_t) * total, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(rv_off_.p, game_offset, sizeof(int64_t) * (G + 1), hipMemcpyHostToDevice, stream_));
+  up(rv_moves_.p, moves, (size_t)total);
+  stage(rv_off_, game_offset, (size_t)G + 1);
   rv_off_host_.assign(game_offset, game_offset + G + 1);
   V_.review = 1;
   V_.rv_moves = rv_moves_.p;
@@ -1124,9 +1117,7 @@ void Engine::review_start(const int16_t* moves, const int64_t* game_offset, cons
 
 int64_t Engine::analyze_progress() {
   AGZ_REQUIRE(V_.an_res != nullptr, AGZ_BAD_ARGUMENT, "analysis: no agz_analyze_start on this engine");
-  unsigned long long done = 0;
-  AGZ_HIP(hipMemcpyAsync(&done, V_.an_ctr + 1, sizeof(done), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  const unsigned long long done = fetch(V_.an_ctr + 1);
   net_->check_async_error();
   return (int64_t)done;
 }
@@ -1135,11 +1126,11 @@ void Engine::analyze_results(agz_analysis* out, float* child_N, float* child_W, 
   const int64_t done = analyze_progress(), B = an_count_;
   AGZ_REQUIRE(done >= B, AGZ_NOT_READY, "analysis: %lld of %lld rows finished", (long long)done, (long long)B);
   const size_t rows = (size_t)B * V_.A;
-  if (out) AGZ_HIP(hipMemcpyAsync(out, an_res_.p, sizeof(agz_analysis) * B, hipMemcpyDeviceToHost, stream_));
-  if (child_N) AGZ_HIP(hipMemcpyAsync(child_N, an_rows_.p, sizeof(float) * rows, hipMemcpyDeviceToHost, stream_));
-  if (child_W) AGZ_HIP(hipMemcpyAsync(child_W, an_rows_.p + rows, sizeof(float) * rows, hipMemcpyDeviceToHost, stream_));
-  if (prior) AGZ_HIP(hipMemcpyAsync(prior, an_rows_.p + 2 * rows, sizeof(float) * rows, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(out, an_res_.p, (size_t)B);
+  down(child_N, an_rows_.p, rows);
+  down(child_W, an_rows_.p + rows, rows);
+  down(prior, an_rows_.p + 2 * rows, rows);
+  wait();
 }
 
 void Engine::profile_search_enable(bool on) {
@@ -1153,7 +1144,7 @@ void Engine::profile_search_enable(bool on) {
 
 // ms5: summed milliseconds of k_pre, k_expand, k_scan, k_leaf_features, k_post over the timed steps
 void Engine::profile_search_read(double* ms5, int64_t* steps) {
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
   for (int k = 0; k < 5; ++k) ms5[k] = 0.0;
   static const int a[5] = {0, 1, 2, 3, 5}, b[5] = {1, 2, 3, 4, 6};
   for (int i = 0; i < sprof_n_; ++i)
@@ -1171,8 +1162,8 @@ int Engine::select_external() {
   hipLaunchKernelGGL(k_expand, dim3(V_.games * (kMaxPend / 2)), dim3(kWave), 0, stream_, V_);
   hipLaunchKernelGGL(cfg_.arena_mode ? k_scan_arena : k_scan, dim3(1), dim3(256), 0, stream_, V_);
   int32_t n[2] = {0, 0};
-  AGZ_HIP(hipMemcpyAsync(n, V_.batch_count, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(n, V_.batch_count, 2);
+  wait();
   external_batch_ = n[0];
   external_batch2_ = cfg_.arena_mode ? n[1] : 0;
   return external_batch_ + external_batch2_;
@@ -1189,27 +1180,25 @@ void Engine::leaf_features_external(float* feats_out) {
   const size_t per = (size_t)17 * V_.P;
   d_whcn_.ensure((size_t)bcap_ * per);
   hipLaunchKernelGGL(k_leaf_features, dim3(bcap_), dim3(kWavesPerLeaf * kWave), 0, stream_, V_, 0, bcap_, (float*)nullptr, d_whcn_.p);
-  if (B) AGZ_HIP(hipMemcpyAsync(feats_out, d_whcn_.p, sizeof(float) * (size_t)B * per, hipMemcpyDeviceToHost, stream_));
+  down(feats_out, d_whcn_.p, (size_t)B * per);
   // arena: the White players' rows follow the Black players' rows in the host buffer
-  if (B2) AGZ_HIP(hipMemcpyAsync(feats_out + (size_t)B * per, d_whcn_.p + (size_t)(bcap_ / 2) * per,
-                                 sizeof(float) * (size_t)B2 * per, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(feats_out + (size_t)B * per, d_whcn_.p + (size_t)(bcap_ / 2) * per, (size_t)B2 * per);
+  wait();
 }
 
 void Engine::incorporate_external(const float* pi, const float* v) {
   const int B = external_batch_, B2 = external_batch2_;
+  const size_t A = V_.A, half = (size_t)bcap_ / 2;
   if (B > 0) {
-    AGZ_HIP(hipMemcpyAsync(d_pi_.p, pi, sizeof(float) * (size_t)B * V_.A, hipMemcpyHostToDevice, stream_));
-    AGZ_HIP(hipMemcpyAsync(d_v_.p, v, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, stream_));
+    up(d_pi_.p, pi, (size_t)B * A);
+    up(d_v_.p, v, (size_t)B);
   }
   if (B2 > 0) {
-    const size_t half = (size_t)bcap_ / 2;
-    AGZ_HIP(hipMemcpyAsync(d_pi_.p + half * V_.A, pi + (size_t)B * V_.A, sizeof(float) * (size_t)B2 * V_.A,
-                           hipMemcpyHostToDevice, stream_));
-    AGZ_HIP(hipMemcpyAsync(d_v_.p + half, v + B, sizeof(float) * (size_t)B2, hipMemcpyHostToDevice, stream_));
+    up(d_pi_.p + half * A, pi + (size_t)B * A, (size_t)B2 * A);
+    up(d_v_.p + half, v + B, (size_t)B2);
   }
   hipLaunchKernelGGL(k_post, dim3(V_.games), dim3(kWave), 0, stream_, V_);
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
   external_batch_ = 0;
   external_batch2_ = 0;
 }
@@ -1224,38 +1213,34 @@ void Engine::debug_set_stagger(int moves) {
 
 void Engine::debug_live_record(int g, int k, uint64_t* game_id, int32_t* num_moves, int32_t* move, float* pi, float* q) {
   AGZ_REQUIRE(g >= 0 && g < V_.games, AGZ_BAD_ARGUMENT, "slot %d of %d", g, V_.games);
-  GameState G;
-  AGZ_HIP(hipMemcpyAsync(&G, V_.gs + g, sizeof(G), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  const GameState G = fetch(V_.gs + g);
   if (game_id) *game_id = G.game_id;
   if (num_moves) *num_moves = G.nqs;
   if (k < 0) return;
   AGZ_REQUIRE(k < G.nqs, AGZ_BAD_ARGUMENT, "slot %d has recorded %d moves", g, G.nqs);
   const long at = (long)g * V_.max_game_length + k;
   int16_t m = 0;
-  AGZ_HIP(hipMemcpyAsync(&m, V_.rec_moves + at, sizeof(m), hipMemcpyDeviceToHost, stream_));
-  if (q) AGZ_HIP(hipMemcpyAsync(q, V_.rec_q + at, sizeof(float), hipMemcpyDeviceToHost, stream_));
-  if (pi) AGZ_HIP(hipMemcpyAsync(pi, V_.rec_pi + at * V_.A, sizeof(float) * V_.A, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(&m, V_.rec_moves + at, 1);
+  down(q, V_.rec_q + at, 1);
+  down(pi, V_.rec_pi + at * V_.A, (size_t)V_.A);
+  wait();
   if (move) *move = m;
 }
 
 int Engine::debug_counters(uint64_t* out, int cap) {
   unsigned long long c[CT_COUNT];
-  AGZ_HIP(hipMemcpyAsync(c, V_.counters, sizeof(c), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(c, V_.counters, CT_COUNT);
+  wait();
   for (int i = 0; i < CT_COUNT && i < cap; ++i) out[i] = c[i];
   return CT_COUNT;
 }
 
 void Engine::stats(agz_stats* out) {
   unsigned long long c[CT_COUNT];
-  AGZ_HIP(hipMemcpyAsync(c, V_.counters, sizeof(c), hipMemcpyDeviceToHost, stream_));
   std::vector<GameState> gs(V_.games);
-  AGZ_HIP(hipMemcpyAsync(gs.data(), V_.gs, sizeof(GameState) * gs.size(), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
-  net_->check_async_error();
-  if (net2_) net2_->check_async_error();
+  down(c, V_.counters, CT_COUNT);
+  down(gs.data(), V_.gs, gs.size());
+  sync();
   std::memset(out, 0, sizeof(*out));
   out->steps = (int64_t)c[CT_STEPS];
   out->positions = (int64_t)c[CT_POSITIONS];
@@ -1285,8 +1270,8 @@ void Engine::stats(agz_stats* out) {
 // agz_slot_abandon the games it gives up on -- or let AGZ_POOL_MOVE_EARLY (the default) keep them moving.
 void Engine::slot_status(int32_t* status, int32_t* nodes, int32_t* moves) {
   std::vector<GameState> gs(V_.games);
-  AGZ_HIP(hipMemcpyAsync(gs.data(), V_.gs, sizeof(GameState) * gs.size(), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(gs.data(), V_.gs, gs.size());
+  wait();
   for (int g = 0; g < V_.games; ++g) {
     if (status) status[g] = (gs[g].stalled && gs[g].phase == G_SEARCH) ? AGZ_POOL_EXHAUSTED : (gs[g].err == AGZ_POOL_EXHAUSTED ? AGZ_OK : gs[g].err);
     if (nodes) nodes[g] = gs[g].nodes_used;
@@ -1299,9 +1284,9 @@ void Engine::slot_status(int32_t* status, int32_t* nodes, int32_t* moves) {
 void Engine::slot_abandon(int g) {
   AGZ_REQUIRE(g >= 0 && g < V_.games, AGZ_BAD_ARGUMENT, "slot %d of %d", g, V_.games);
   AGZ_REQUIRE(!V_.arena, AGZ_BAD_ARGUMENT, "arena slots come in pairs: not abandonable one by one");
-  GameState G;
-  AGZ_HIP(hipMemcpyAsync(&G, V_.gs + g, sizeof(G), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  GameState G = fetch(V_.gs + g);
+  std::vector<agz_analysis> rs;      // uploaded below: both live until put() at the end has synchronised
+  unsigned long long done = 0;
   AGZ_REQUIRE(G.phase == G_SEARCH || G.phase == G_INIT || G.phase == G_INIT_WAIT, AGZ_BAD_ARGUMENT,
               "slot %d is not playing a self-play game (phase %d)", g, G.phase);
   if (V_.analysis) {
@@ -1310,40 +1295,36 @@ void Engine::slot_abandon(int g) {
     // (review mode: the rest of the game is given up -- the current ply's row as above, the later rows move -1 and
     // nothing searched, all AGZ_POOL_EXHAUSTED)
     int64_t i = 0;
-    unsigned long long done = 0;
-    AGZ_HIP(hipMemcpyAsync(&i, V_.an_slot + g, sizeof(i), hipMemcpyDeviceToHost, stream_));
-    AGZ_HIP(hipMemcpyAsync(&done, V_.an_ctr + 1, sizeof(done), hipMemcpyDeviceToHost, stream_));
-    AGZ_HIP(hipStreamSynchronize(stream_));
+    down(&i, V_.an_slot + g, 1);
+    down(&done, V_.an_ctr + 1, 1);
+    wait();
     int64_t row = i, nrows = 1;
     if (V_.review) {
       row = rv_off_host_[i] + G.move_count;
       nrows = rv_off_host_[i + 1] - row;
     }
-    std::vector<agz_analysis> rs((size_t)nrows);
+    rs.resize((size_t)nrows);
     for (auto& r : rs) { r.move = -1; r.status = AGZ_POOL_EXHAUSTED; r.N = 0.f; r.W = 0.f; r.Q = 0.f; r.nodes_used = 0; }
     agz_analysis& r = rs[0];
     r.N = G.rootN; r.W = G.rootW; r.Q = G.rootW / (1.0f + G.rootN);
     r.nodes_used = G.nodes_used;
     done += (unsigned long long)nrows;
-    AGZ_HIP(hipMemcpyAsync(V_.an_res + row, rs.data(), sizeof(agz_analysis) * nrows, hipMemcpyHostToDevice, stream_));
-    AGZ_HIP(hipMemcpyAsync(V_.an_ctr + 1, &done, sizeof(done), hipMemcpyHostToDevice, stream_));
+    up(V_.an_res + row, rs.data(), (size_t)nrows);
+    up(V_.an_ctr + 1, &done, 1);
   }
   G.phase = G_IDLE;
   G.nleaves = 0;
   G.npend = 0;
   G.err = 0;
   G.stalled = 0;
-  AGZ_HIP(hipMemcpyAsync(V_.gs + g, &G, sizeof(G), hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  put(V_.gs + g, G);
   if (!V_.analysis) ++abandoned_;
 }
 
 // ---- records
 
 int64_t Engine::records_count() {
-  unsigned long long f = 0;
-  AGZ_HIP(hipMemcpyAsync(&f, V_.counters + CT_RECORDED, sizeof(f), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  const unsigned long long f = fetch(V_.counters + CT_RECORDED);
   net_->check_async_error();
   if (net2_) net2_->check_async_error();
   return (int64_t)std::min<unsigned long long>(f, (unsigned long long)V_.fin_cap);
@@ -1351,8 +1332,7 @@ int64_t Engine::records_count() {
 
 void Engine::record_header(int64_t k, agz_game_header* out) {
   AGZ_REQUIRE(k >= 0 && k < records_count(), AGZ_BAD_ARGUMENT, "record %lld out of range", (long long)k);
-  AGZ_HIP(hipMemcpyAsync(out, V_.fin_hdr + k, sizeof(*out), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  *out = fetch(V_.fin_hdr + k);
 }
 
 void Engine::record_game(int64_t k, int16_t* moves, float* pis, float* qs) {
@@ -1360,46 +1340,51 @@ void Engine::record_game(int64_t k, int16_t* moves, float* pis, float* qs) {
   record_header(k, &h);
   const size_t mgl = V_.max_game_length, nm = (size_t)h.num_moves;
   if (nm == 0) return;
-  if (moves) AGZ_HIP(hipMemcpyAsync(moves, V_.fin_moves + k * mgl, sizeof(int16_t) * nm, hipMemcpyDeviceToHost, stream_));
-  if (qs) AGZ_HIP(hipMemcpyAsync(qs, V_.fin_q + k * mgl, sizeof(float) * nm, hipMemcpyDeviceToHost, stream_));
-  if (pis) AGZ_HIP(hipMemcpyAsync(pis, V_.fin_pi + k * mgl * V_.A, sizeof(float) * nm * V_.A, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(moves, V_.fin_moves + k * mgl, nm);
+  down(qs, V_.fin_q + k * mgl, nm);
+  down(pis, V_.fin_pi + k * mgl * V_.A, nm * V_.A);
+  wait();
 }
 
-static size_t packed_record_bytes(const View& V, int nm) { return packed_bytes(V.A, nm); }
+// the packed form of records [first, last) (last < 0: records_count()): off[k] = where record first + k begins, one
+// entry per record; returns the bytes of all of them.  The headers come over stream_ and are waited for.  (The size
+// call used to fetch them with a blocking hipMemcpy on the null stream, which stream_ -- hipStreamNonBlocking -- does not
+// order itself against; every caller had come through records_count(), which leaves stream_ idle, so that copy read
+// what this one reads.)
+size_t Engine::packed_layout(int64_t first, int64_t last, std::vector<int64_t>& off) {
+  const int64_t n = (last < 0 ? records_count() : last) - first;
+  off.clear();
+  if (n <= 0) return 0;
+  std::vector<agz_game_header> h((size_t)n);
+  down(h.data(), V_.fin_hdr + first, (size_t)n);
+  wait();
+  size_t total = 0;
+  for (auto& x : h) {
+    off.push_back((int64_t)total);
+    total += packed_bytes(V_.A, x.num_moves);
+  }
+  return total;
+}
 
 // bytes of the packed form of records [first, count)
 int64_t Engine::records_packed_size(int64_t first, int64_t last) {
-  const int64_t n = (last < 0 ? records_count() : last) - first;
-  if (n <= 0) return 0;
-  std::vector<agz_game_header> h((size_t)n);
-  AGZ_HIP(hipMemcpy(h.data(), V_.fin_hdr + first, sizeof(agz_game_header) * (size_t)n, hipMemcpyDeviceToHost));
-  size_t total = 0;
-  for (auto& x : h) total += packed_record_bytes(V_, x.num_moves);
-  return (int64_t)total;
+  std::vector<int64_t> off;
+  return (int64_t)packed_layout(first, last, off);
 }
 
 // pack the finished records [first, count) into `dst` (device memory, >= records_packed_size(first) bytes): one D2H
 // of the headers to lay the records out, one kernel to move them.  Returns the number of records packed.
 int64_t Engine::pack_records_device(uint8_t* dst, int64_t capacity, int64_t* nbytes, int64_t first, int64_t last) {
-  const int64_t n = (last < 0 ? records_count() : last) - first;
   *nbytes = 0;
+  std::vector<int64_t> off;
+  const size_t total = packed_layout(first, last, off);
+  const int64_t n = (int64_t)off.size();
   if (n <= 0) return 0;
-  std::vector<agz_game_header> h((size_t)n);
-  AGZ_HIP(hipMemcpyAsync(h.data(), V_.fin_hdr + first, sizeof(agz_game_header) * (size_t)n, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
-  std::vector<int64_t> off((size_t)n);
-  size_t total = 0;
-  for (int64_t k = 0; k < n; ++k) {
-    off[k] = (int64_t)total;
-    total += packed_record_bytes(V_, h[k].num_moves);
-  }
   AGZ_REQUIRE((int64_t)total <= capacity, AGZ_BAD_ARGUMENT, "export buffer too small");
-  s_i64a_.ensure((size_t)n);
-  AGZ_HIP(hipMemcpyAsync(s_i64a_.p, off.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_pack_records, dim3((unsigned)n), dim3(256), 0, stream_, V_, (const int64_t*)s_i64a_.p, dst, (long)first);
+  const int64_t* d_off = stage(s_i64a_, off.data(), off.size());
+  hipLaunchKernelGGL(k_pack_records, dim3((unsigned)n), dim3(256), 0, stream_, V_, d_off, dst, (long)first);
   AGZ_HIP(hipGetLastError());
-  AGZ_HIP(hipStreamSynchronize(stream_));      // `off` is stack-owned
+  wait();      // `off` is stack-owned
   *nbytes = (int64_t)total;
   return n;
 }
@@ -1415,8 +1400,8 @@ void Engine::records_export_packed(void* dst, int64_t capacity, bool is_device) 
   if (need == 0) return;
   s_pack_.ensure((size_t)need);
   pack_records_device(s_pack_.p, need, &nb);
-  AGZ_HIP(hipMemcpyAsync(dst, s_pack_.p, (size_t)nb, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down((uint8_t*)dst, s_pack_.p, (size_t)nb);
+  wait();
 }
 
 // ---- device replay arena
@@ -1427,7 +1412,7 @@ void Engine::replay_reserve(size_t bytes) {
   DevBuf<uint8_t> nb;
   nb.alloc(cap);
   if (rp_used_) AGZ_HIP(hipMemcpyAsync(nb.p, rp_buf_.p, rp_used_, hipMemcpyDeviceToDevice, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
   std::swap(nb.p, rp_buf_.p);
   std::swap(nb.n, rp_buf_.n);
 }
@@ -1462,7 +1447,7 @@ int64_t Engine::replay_ingest_chunks(const uint8_t* dbuf, const std::vector<int6
   meta.insert(meta.end(), nrec.begin(), nrec.end());
   meta.insert(meta.end(), first.begin(), first.end());
   meta.resize((size_t)5 * nc, 0);
-  AGZ_HIP(hipMemcpyAsync(d_meta.p, meta.data(), sizeof(int64_t) * meta.size(), hipMemcpyHostToDevice, stream_));
+  up(d_meta.p, meta.data(), meta.size());
   AGZ_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(int32_t), stream_));
   hipLaunchKernelGGL(k_index_records, dim3(nc), dim3(kWave), 0, stream_, dbuf, (const int64_t*)d_meta.p,
                      (const int64_t*)(d_meta.p + nc), (const int64_t*)(d_meta.p + 2 * nc),
@@ -1472,11 +1457,11 @@ int64_t Engine::replay_ingest_chunks(const uint8_t* dbuf, const std::vector<int6
   std::vector<int64_t> off((size_t)total_rec), found((size_t)nc);
   std::vector<agz_game_header> hdr((size_t)total_rec);
   int32_t bad = 0;
-  AGZ_HIP(hipMemcpyAsync(off.data(), d_off.p, sizeof(int64_t) * off.size(), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipMemcpyAsync(hdr.data(), d_hdr.p, sizeof(agz_game_header) * hdr.size(), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipMemcpyAsync(found.data(), d_meta.p + 4 * nc, sizeof(int64_t) * nc, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipMemcpyAsync(&bad, d_flag.p, sizeof(bad), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(off.data(), d_off.p, off.size());
+  down(hdr.data(), d_hdr.p, hdr.size());
+  down(found.data(), d_meta.p + 4 * nc, (size_t)nc);
+  down(&bad, d_flag.p, 1);
+  wait();
   AGZ_REQUIRE(bad == 0, AGZ_BAD_ARGUMENT, "packed records are malformed (a record runs past its chunk or a count does not match)");
   replay_reserve(rp_used_ + (size_t)total_bytes);
   const size_t first_new = rp_hdr_.size();
@@ -1494,7 +1479,7 @@ int64_t Engine::replay_ingest_chunks(const uint8_t* dbuf, const std::vector<int6
     rp_used_ += (size_t)cbytes[c];
   }
   if (rp_targets_only_ && added > 0) replay_scan_targets(first_new);
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
   return added;
 }
 
@@ -1503,11 +1488,7 @@ int64_t Engine::replay_ingest(const void* packed, int64_t nbytes, bool is_device
   AGZ_REQUIRE(nbytes % 8 == 0, AGZ_BAD_ARGUMENT, "packed records are a multiple of 8 bytes");
   if (nbytes == 0) return 0;
   const uint8_t* d = (const uint8_t*)packed;
-  if (!is_device) {
-    s_pack_.ensure((size_t)nbytes);
-    AGZ_HIP(hipMemcpyAsync(s_pack_.p, packed, (size_t)nbytes, hipMemcpyHostToDevice, stream_));
-    d = s_pack_.p;
-  }
+  if (!is_device) d = stage(s_pack_, d, (size_t)nbytes);
   return replay_ingest_chunks(d, {0}, {nbytes}, {-1});
 }
 
@@ -1516,7 +1497,7 @@ int64_t Engine::replay_ingest_gathered(const void* buf, bool is_device, size_t n
   const uint8_t* d = (const uint8_t*)buf;
   if (!is_device) {
     s_pack_.ensure(std::max<size_t>(nbytes, 8));
-    AGZ_HIP(hipMemcpyAsync(s_pack_.p, buf, nbytes, hipMemcpyHostToDevice, stream_));
+    up(s_pack_.p, d, nbytes);
     d = s_pack_.p;
   }
   return replay_ingest_chunks(d, coff, cbytes, cnrec);
@@ -1561,10 +1542,11 @@ void Engine::replay_game(int64_t k, int16_t* moves, float* pis, float* qs) {
   if (nm == 0) return;
   const uint8_t* r = rp_buf_.p + rp_off_[(size_t)k];
   const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * nm + 3) & ~(size_t)3;
-  if (moves) AGZ_HIP(hipMemcpyAsync(moves, r + sizeof(agz_game_header), sizeof(int16_t) * nm, hipMemcpyDeviceToHost, stream_));
-  if (pis) AGZ_HIP(hipMemcpyAsync(pis, r + o_pi, sizeof(float) * nm * V_.A, hipMemcpyDeviceToHost, stream_));
-  if (qs) AGZ_HIP(hipMemcpyAsync(qs, r + o_pi + sizeof(float) * nm * V_.A, sizeof(float) * nm, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  const float* r_pi = (const float*)(r + o_pi);
+  down(moves, (const int16_t*)(r + sizeof(agz_game_header)), nm);
+  down(pis, r_pi, nm * V_.A);
+  down(qs, r_pi + nm * V_.A, nm);
+  wait();
 }
 
 // the FIFO window of train() (`shrink`, train.jl:52): forget the oldest games until at most max_positions remain
@@ -1585,7 +1567,7 @@ void Engine::replay_drop_front(size_t drop) {
   DevBuf<uint8_t> nb;
   nb.alloc(std::max(keep, (size_t)1 << 20));
   AGZ_HIP(hipMemcpyAsync(nb.p, rp_buf_.p + cut, keep, hipMemcpyDeviceToDevice, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
   std::swap(nb.p, rp_buf_.p);
   std::swap(nb.n, rp_buf_.n);
   if (rp_targets_only_) {           // the target lists lie by position prefix: they move up with it
@@ -1594,7 +1576,7 @@ void Engine::replay_drop_front(size_t drop) {
     if (pos > 0)
       AGZ_HIP(hipMemcpyAsync(nt.p, d_rp_tply_.p + rp_cum_[drop], sizeof(int16_t) * (size_t)pos, hipMemcpyDeviceToDevice,
                              stream_));
-    AGZ_HIP(hipStreamSynchronize(stream_));
+    wait();
     std::swap(nt.p, d_rp_tply_.p);
     std::swap(nt.n, d_rp_tply_.n);
     const int64_t t0 = rp_tcum_[drop];
@@ -1670,7 +1652,7 @@ void Engine::replay_scan_targets(size_t first_new) {
     nt.alloc(std::max<size_t>(2 * (size_t)rp_positions_, (size_t)1 << 16));
     const size_t have = (size_t)rp_cum_[first_new];
     if (have) AGZ_HIP(hipMemcpyAsync(nt.p, d_rp_tply_.p, sizeof(int16_t) * have, hipMemcpyDeviceToDevice, stream_));
-    AGZ_HIP(hipStreamSynchronize(stream_));
+    wait();
     std::swap(nt.p, d_rp_tply_.p);
     std::swap(nt.n, d_rp_tply_.n);
   }
@@ -1678,14 +1660,14 @@ void Engine::replay_scan_targets(size_t first_new) {
   DevBuf<int32_t>& d_cnt = tgt_cnt_;
   d_idx.ensure(2 * m);
   d_cnt.ensure(m);
-  AGZ_HIP(hipMemcpyAsync(d_idx.p, rp_off_.data() + first_new, sizeof(int64_t) * m, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(d_idx.p + m, rp_cum_.data() + first_new, sizeof(int64_t) * m, hipMemcpyHostToDevice, stream_));
+  up(d_idx.p, rp_off_.data() + first_new, m);
+  up(d_idx.p + m, rp_cum_.data() + first_new, m);
   hipLaunchKernelGGL(k_replay_targets, dim3((unsigned)m), dim3(kWave), 0, stream_, (const uint8_t*)rp_buf_.p,
                      (const int64_t*)d_idx.p, (const int64_t*)(d_idx.p + m), V_.A, d_rp_tply_.p, d_cnt.p);
   AGZ_HIP(hipGetLastError());
   std::vector<int32_t> cnt(m);
-  AGZ_HIP(hipMemcpyAsync(cnt.data(), d_cnt.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(cnt.data(), d_cnt.p, m);
+  wait();
   rp_tcum_.resize(first_new + 1);
   for (size_t i = 0; i < m; ++i) rp_tcum_.push_back(rp_tcum_.back() + cnt[i]);
 }
@@ -1712,17 +1694,13 @@ void Engine::replay_sample(int B, uint64_t call, int sym_mode, float* feats, flo
     rp_dev_n_ = 0;
   }
   if (rp_dev_n_ < n) {
-    AGZ_HIP(hipMemcpyAsync(d_rp_off_.p + rp_dev_n_, rp_off_.data() + rp_dev_n_, sizeof(int64_t) * (size_t)(n - rp_dev_n_),
-                           hipMemcpyHostToDevice, stream_));
-    AGZ_HIP(hipMemcpyAsync(d_rp_cum_.p + rp_dev_n_, rp_cum_.data() + rp_dev_n_,
-                           sizeof(int64_t) * (size_t)(n + 1 - rp_dev_n_), hipMemcpyHostToDevice, stream_));
-    if (rp_targets_only_)
-      AGZ_HIP(hipMemcpyAsync(d_rp_tcum_.p + rp_dev_n_, rp_tcum_.data() + rp_dev_n_,
-                             sizeof(int64_t) * (size_t)(n + 1 - rp_dev_n_), hipMemcpyHostToDevice, stream_));
-    AGZ_HIP(hipStreamSynchronize(stream_));      // the host vectors may move with the next ingest
+    const size_t at = (size_t)rp_dev_n_, fresh = (size_t)n - at;
+    up(d_rp_off_.p + at, rp_off_.data() + at, fresh);
+    up(d_rp_cum_.p + at, rp_cum_.data() + at, fresh + 1);
+    if (rp_targets_only_) up(d_rp_tcum_.p + at, rp_tcum_.data() + at, fresh + 1);
+    wait();      // the host vectors may move with the next ingest
     rp_dev_n_ = n;
   }
-  const size_t per = (size_t)17 * V_.P;
   smp_off_.ensure(kSampleMax);
   smp_ply_.ensure(kSampleMax);
   smp_sym_.ensure(kSampleMax);
@@ -1734,20 +1712,28 @@ void Engine::replay_sample(int B, uint64_t call, int sym_mode, float* feats, flo
                      (const int64_t*)d_rp_cum_.p, (const int16_t*)(rp_targets_only_ ? d_rp_tply_.p : nullptr), n, sym_mode,
                      smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, game_out, ply_out);
   AGZ_HIP(hipGetLastError());
-  if (with_sym) {
-    smp_f_.ensure(per * (size_t)B);
-    smp_p_.ensure((size_t)B * V_.A);
-    hipLaunchKernelGGL(k_replay_arena_batch, dim3(B), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
-                       (const int64_t*)smp_off_.p, (const int32_t*)smp_ply_.p, smp_boards_.p, smp_f_.p,
-                       pi ? smp_p_.p : nullptr, z);
-    hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)smp_f_.p, feats,
-                       (const int32_t*)smp_sym_.p, V_.N, 17, 0, 0);
-    if (pi)
-      hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)smp_p_.p, pi,
-                         (const int32_t*)smp_sym_.p, V_.N, 1, 1, 0);
-  } else {
-    hipLaunchKernelGGL(k_replay_arena_batch, dim3(B), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
-                       (const int64_t*)smp_off_.p, (const int32_t*)smp_ply_.p, smp_boards_.p, feats, pi, z);
+  emit_replay_batch(B, smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, smp_boards_.p, feats, pi, z);
+}
+
+// B samples given on the device as (record offset, ply) -> feats [B][17 P], pi [B][A] (or NULL) and z [B] (or NULL) in
+// device memory; `boards` is replay scratch of B * 8 * PP.  With `sym` (device, [B]) the samples are written as they are
+// into s_symf_ / s_symp_ and sample b goes under T_sym[b] into the outputs.  The sampler and agz_replay_batch share that
+// pair: both enqueue on stream_ only, so the later call's kernels start after the earlier call's have read it, and a
+// regrow goes through hipFree, which waits for the device.  Nothing here waits: agz_replay_sample stays asynchronous.
+void Engine::emit_replay_batch(int B, const int64_t* off, const int32_t* ply, const int32_t* sym, int8_t* boards,
+                               float* feats, float* pi, float* z) {
+  float *f = feats, *p = pi;
+  if (sym) {
+    s_symf_.ensure((size_t)B * 17 * V_.P);
+    s_symp_.ensure((size_t)B * V_.A);
+    f = s_symf_.p;
+    p = pi ? s_symp_.p : nullptr;
+  }
+  hipLaunchKernelGGL(k_replay_arena_batch, dim3(B), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p, off, ply,
+                     boards, f, p, z);
+  if (sym) {
+    hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)f, feats, sym, V_.N, 17, 0, 0);
+    if (pi) hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)p, pi, sym, V_.N, 1, 1, 0);
   }
   AGZ_HIP(hipGetLastError());
 }
@@ -1805,51 +1791,32 @@ void Engine::replay_batch(const int64_t* game, const int32_t* ply, int B, float*
                 "sample %d: ply outside the game (searches_pi has one entry per move played)", b);
     off[b] = rp_off_[(size_t)game[b]];
   }
-  const size_t per = (size_t)17 * V_.P;
-  s_i64a_.ensure((size_t)B);
-  s_i32a_.ensure((size_t)B);
-  s_boards_.ensure((size_t)B * 8 * V_.PP);
+  const size_t n = (size_t)B, per = (size_t)17 * V_.P, A = V_.A;
+  s_boards_.ensure(n * 8 * V_.PP);
   float *df = feats, *dp = pi, *dz = z;
   if (!out_is_device) {
-    s_f32a_.ensure(per * (size_t)B);
-    s_f32b_.ensure((size_t)B * (V_.A + 1));
+    s_f32a_.ensure(per * n);
+    s_f32b_.ensure(n * (A + 1));
     df = s_f32a_.p;
     dp = pi ? s_f32b_.p : nullptr;
-    dz = z ? s_f32b_.p + (size_t)B * V_.A : nullptr;
+    dz = z ? s_f32b_.p + n * A : nullptr;
   }
-  AGZ_HIP(hipMemcpyAsync(s_i64a_.p, off.data(), sizeof(int64_t) * (size_t)B, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_i32a_.p, ply, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, stream_));
-  if (sym) {
-    // agz_replay_batch_sym: the samples as they are into scratch, then sample b under T_sym[b] into the outputs
-    s_sym_.ensure((size_t)B);
-    s_symf_.ensure(per * (size_t)B);
-    s_symp_.ensure((size_t)B * V_.A);
-    AGZ_HIP(hipMemcpyAsync(s_sym_.p, sym, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, stream_));
-    hipLaunchKernelGGL(k_replay_arena_batch, dim3(B), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
-                       (const int64_t*)s_i64a_.p, (const int32_t*)s_i32a_.p, s_boards_.p, s_symf_.p,
-                       dp ? s_symp_.p : nullptr, dz);
-    hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)s_symf_.p, df, (const int32_t*)s_sym_.p,
-                       V_.N, 17, 0, 0);
-    if (dp)
-      hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)s_symp_.p, dp,
-                         (const int32_t*)s_sym_.p, V_.N, 1, 1, 0);
-  } else {
-    hipLaunchKernelGGL(k_replay_arena_batch, dim3(B), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
-                       (const int64_t*)s_i64a_.p, (const int32_t*)s_i32a_.p, s_boards_.p, df, dp, dz);
-  }
-  AGZ_HIP(hipGetLastError());
+  const int64_t* d_off = stage(s_i64a_, off.data(), n);
+  const int32_t* d_ply = stage(s_i32a_, ply, n);
+  const int32_t* d_sym = sym ? stage(s_sym_, sym, n) : nullptr;      // agz_replay_batch_sym
+  emit_replay_batch(B, d_off, d_ply, d_sym, s_boards_.p, df, dp, dz);
   if (!out_is_device) {
-    AGZ_HIP(hipMemcpyAsync(feats, df, sizeof(float) * per * (size_t)B, hipMemcpyDeviceToHost, stream_));
-    if (pi) AGZ_HIP(hipMemcpyAsync(pi, dp, sizeof(float) * (size_t)B * V_.A, hipMemcpyDeviceToHost, stream_));
-    if (z) AGZ_HIP(hipMemcpyAsync(z, dz, sizeof(float) * (size_t)B, hipMemcpyDeviceToHost, stream_));
+    down(feats, df, per * n);
+    down(pi, dp, n * A);
+    down(z, dz, n);
   }
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();      // `off` is stack-owned
 }
 
 void Engine::records_clear() {
   rec_sent_ = 0;
   AGZ_HIP(hipMemsetAsync(V_.counters + CT_RECORDED, 0, sizeof(unsigned long long), stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
 }
 
 void Engine::record_features(int64_t k, float* out) {
@@ -1859,17 +1826,15 @@ void Engine::record_features(int64_t k, float* out) {
   const size_t per = (size_t)17 * V_.P;
   s_f32a_.ensure(per * (size_t)h.num_moves);
   s_boards_.ensure((size_t)8 * V_.PP);
-  s_i32a_.ensure(4);
-  s_i64a_.ensure(1);
   const int32_t args[4] = {0, h.num_moves, 0, (int32_t)record_start(V_, h.game_id)};
   const int64_t zero = 0;
-  AGZ_HIP(hipMemcpyAsync(s_i32a_.p, args, sizeof(args), hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_i64a_.p, &zero, sizeof(zero), hipMemcpyHostToDevice, stream_));
+  int32_t* a = stage(s_i32a_, args, 4);
+  int64_t* d_off = stage(s_i64a_, &zero, 1);
   hipLaunchKernelGGL(k_replay_features, dim3(1), dim3(kWave), 0, stream_, V_,
-                     (const int16_t*)(V_.fin_moves + k * V_.max_game_length), s_i32a_.p, s_i32a_.p + 1, s_i32a_.p + 2,
-                     s_i64a_.p, s_boards_.p, s_f32a_.p, (const int32_t*)(s_i32a_.p + 3));
-  AGZ_HIP(hipMemcpyAsync(out, s_f32a_.p, sizeof(float) * per * (size_t)h.num_moves, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+                     (const int16_t*)(V_.fin_moves + k * V_.max_game_length), a, a + 1, a + 2, d_off, s_boards_.p,
+                     s_f32a_.p, (const int32_t*)(a + 3));
+  down(out, s_f32a_.p, per * (size_t)h.num_moves);
+  wait();
 }
 
 // get_replay_batch (train.jl:4-12), feature side: B sampled (game, ply) pairs -> [B][17*P].
@@ -1897,87 +1862,94 @@ void Engine::replay_batch_features(const int16_t* moves, int64_t nmoves, const i
   for (int64_t i = 0; i < nmoves; ++i)
     AGZ_REQUIRE(moves[i] >= 0 && moves[i] <= V_.P, AGZ_BAD_ARGUMENT, "move outside 0..N*N");
   s_i16a_.ensure((size_t)std::max<int64_t>(nmoves, 1));
-  s_i32a_.ensure((size_t)4 * B);
-  s_i64a_.ensure(B);
   s_boards_.ensure((size_t)B * 8 * V_.PP);
   float* dst = out;
   if (!out_is_device) {
     s_f32a_.ensure(per * (size_t)B);
     dst = s_f32a_.p;
   }
-  if (nmoves) AGZ_HIP(hipMemcpyAsync(s_i16a_.p, moves, sizeof(int16_t) * nmoves, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_i32a_.p, h32.data(), sizeof(int32_t) * h32.size(), hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_i64a_.p, h64.data(), sizeof(int64_t) * h64.size(), hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_replay_features, dim3(B), dim3(kWave), 0, stream_, V_, (const int16_t*)s_i16a_.p, s_i32a_.p,
-                     s_i32a_.p + B, s_i32a_.p + 2 * B, s_i64a_.p, s_boards_.p, dst, (const int32_t*)(s_i32a_.p + 3 * B));
+  up(s_i16a_.p, moves, (size_t)nmoves);
+  int32_t* a = stage(s_i32a_, h32.data(), h32.size());      // [off | ply + 1 | ply | start] x B
+  int64_t* d_off = stage(s_i64a_, h64.data(), h64.size());
+  hipLaunchKernelGGL(k_replay_features, dim3(B), dim3(kWave), 0, stream_, V_, (const int16_t*)s_i16a_.p, a, a + B,
+                     a + 2 * B, d_off, s_boards_.p, dst, (const int32_t*)(a + 3 * B));
   AGZ_HIP(hipGetLastError());
-  if (!out_is_device)
-    AGZ_HIP(hipMemcpyAsync(out, dst, sizeof(float) * per * (size_t)B, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));     // the staging vectors above are stack-owned
+  if (!out_is_device) down(out, dst, per * (size_t)B);
+  wait();     // the staging vectors above are stack-owned
 }
 
 // ---- network entry points
+
+// B caller positions into the staging buffers launch_features_from_deltas reads: s_boards_, s_deltas_, s_i32a_ (the
+// delta counts) and s_tp_
+void Engine::stage_positions(const int8_t* boards, const int8_t* deltas, const int32_t* ndeltas, const int8_t* to_play,
+                             int B) {
+  const size_t n = (size_t)B, P = V_.P;
+  stage(s_boards_, boards, n * P);
+  stage(s_deltas_, deltas, n * 7 * P);
+  stage(s_i32a_, ndeltas, n);
+  stage(s_tp_, to_play, n);
+}
+
+// what a forward of B rows from the ABI needs before its launch: the batch count on the device, room for [pi | v] in
+// s_f32b_ and for the x32 rows in s_f32a_.  Returns where the caller writes the x32 rows.  The count is uploaded from
+// the caller's `B`, which must live until the caller's next wait() (forward_staged's, fill_synthetic_inputs' own).
+float* Engine::stage_forward(const int& B) {
+  stage(d_count_, &B, 1);
+  s_f32b_.ensure((size_t)B * (V_.A + 1));
+  s_f32a_.ensure((size_t)B * V_.P * 32);
+  return s_f32a_.p;
+}
+
+// the selected network on the rows stage_forward() made room for: pi [B][A] at s_f32b_, v [B] behind it
+void Engine::forward_x32(int B) {
+  net().forward(s_f32a_.p, d_count_.p, B, s_f32b_.p, s_f32b_.p + (size_t)B * V_.A);
+}
+
+// forward_x32 and pi / v back to the host; with d_sym (device, [B]) pi row b goes back to board orientation first
+void Engine::forward_staged(int B, const int32_t* d_sym, float* pi_out, float* v_out) {
+  const size_t nA = (size_t)B * V_.A;
+  const float* pi = s_f32b_.p;
+  forward_x32(B);
+  if (d_sym) {      // s_symp_: sized by the caller, next to s_symf_
+    hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)s_f32b_.p, s_symp_.p, d_sym, V_.N, 1, 1, 1);
+    AGZ_HIP(hipGetLastError());
+    pi = s_symp_.p;
+  }
+  down(pi_out, pi, nA);
+  down(v_out, s_f32b_.p + nA, (size_t)B);
+  wait();
+  net().check_async_error();      // a persistent tower launch that gave up: these outputs are garbage, say so now
+}
 
 void Engine::features(const int8_t* boards, const int8_t* deltas, const int32_t* ndeltas, const int8_t* to_play,
                       int B, float* out) {
   AGZ_REQUIRE(B >= 0, AGZ_BAD_ARGUMENT, "B < 0");
   if (B == 0) return;
-  const size_t P = V_.P;
-  s_boards_.ensure((size_t)B * P);
-  s_deltas_.ensure((size_t)B * 7 * P);
-  s_i32a_.ensure(B);
-  s_tp_.ensure(B);
-  s_f32a_.ensure((size_t)B * 17 * P);
-  AGZ_HIP(hipMemcpyAsync(s_boards_.p, boards, (size_t)B * P, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_deltas_.p, deltas, (size_t)B * 7 * P, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_i32a_.p, ndeltas, sizeof(int32_t) * B, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_tp_.p, to_play, (size_t)B, hipMemcpyHostToDevice, stream_));
+  const size_t n = (size_t)B * 17 * V_.P;
+  stage_positions(boards, deltas, ndeltas, to_play, B);
+  s_f32a_.ensure(n);
   launch_features_from_deltas(s_boards_.p, s_deltas_.p, s_i32a_.p, s_tp_.p, B, V_.N, nullptr, s_f32a_.p, stream_);
-  AGZ_HIP(hipMemcpyAsync(out, s_f32a_.p, sizeof(float) * (size_t)B * 17 * P, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(out, s_f32a_.p, n);
+  wait();
 }
 
 void Engine::net_forward_positions(const int8_t* boards, const int8_t* deltas, const int32_t* ndeltas,
                                    const int8_t* to_play, int B, float* pi_out, float* v_out) {
   AGZ_REQUIRE(B >= 0, AGZ_BAD_ARGUMENT, "B < 0");
   if (B == 0) return;
-  const size_t P = V_.P;
-  s_boards_.ensure((size_t)B * P);
-  s_deltas_.ensure((size_t)B * 7 * P);
-  s_i32a_.ensure(B);
-  s_tp_.ensure(B);
-  d_count_.ensure(1);
-  s_f32a_.ensure((size_t)B * P * 32);
-  s_f32b_.ensure((size_t)B * (V_.A + 1));
-  AGZ_HIP(hipMemcpyAsync(s_boards_.p, boards, (size_t)B * P, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_deltas_.p, deltas, (size_t)B * 7 * P, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_i32a_.p, ndeltas, sizeof(int32_t) * B, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_tp_.p, to_play, (size_t)B, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(d_count_.p, &B, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  launch_features_from_deltas(s_boards_.p, s_deltas_.p, s_i32a_.p, s_tp_.p, B, V_.N, s_f32a_.p, nullptr, stream_);
-  net().forward(s_f32a_.p, d_count_.p, B, s_f32b_.p, s_f32b_.p + (size_t)B * V_.A);
-  AGZ_HIP(hipMemcpyAsync(pi_out, s_f32b_.p, sizeof(float) * (size_t)B * V_.A, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipMemcpyAsync(v_out, s_f32b_.p + (size_t)B * V_.A, sizeof(float) * B, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
-  net().check_async_error();      // a persistent tower launch that gave up: these outputs are garbage, say so now
+  stage_positions(boards, deltas, ndeltas, to_play, B);
+  float* x32 = stage_forward(B);
+  launch_features_from_deltas(s_boards_.p, s_deltas_.p, s_i32a_.p, s_tp_.p, B, V_.N, x32, nullptr, stream_);
+  forward_staged(B, nullptr, pi_out, v_out);
 }
 
 void Engine::net_forward_features(const float* feats, int B, float* pi_out, float* v_out) {
   AGZ_REQUIRE(B >= 0, AGZ_BAD_ARGUMENT, "B < 0");
   if (B == 0) return;
-  const size_t P = V_.P;
-  d_whcn_.ensure((size_t)B * 17 * P);
-  d_count_.ensure(1);
-  s_f32a_.ensure((size_t)B * P * 32);
-  s_f32b_.ensure((size_t)B * (V_.A + 1));
-  AGZ_HIP(hipMemcpyAsync(d_whcn_.p, feats, sizeof(float) * (size_t)B * 17 * P, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(d_count_.p, &B, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  launch_whcn_to_x32(d_whcn_.p, B, V_.N, s_f32a_.p, stream_);
-  net().forward(s_f32a_.p, d_count_.p, B, s_f32b_.p, s_f32b_.p + (size_t)B * V_.A);
-  AGZ_HIP(hipMemcpyAsync(pi_out, s_f32b_.p, sizeof(float) * (size_t)B * V_.A, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipMemcpyAsync(v_out, s_f32b_.p + (size_t)B * V_.A, sizeof(float) * B, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
-  net().check_async_error();      // a persistent tower launch that gave up: these outputs are garbage, say so now
+  const float* whcn = stage(d_whcn_, feats, (size_t)B * 17 * V_.P);
+  launch_whcn_to_x32(whcn, B, V_.N, stage_forward(B), stream_);
+  forward_staged(B, nullptr, pi_out, v_out);
 }
 
 // agz_net_forward_features_sym: row b under T_sym[b] (k_sym_rows), the plain forward, pi back to board orientation
@@ -1986,28 +1958,14 @@ void Engine::net_forward_features_sym(const float* feats, const int32_t* sym, in
   if (B == 0) return;
   AGZ_REQUIRE(feats && sym && pi_out && v_out, AGZ_BAD_ARGUMENT, "null pointer");
   for (int b = 0; b < B; ++b) AGZ_REQUIRE(sym[b] >= 0 && sym[b] < 8, AGZ_BAD_ARGUMENT, "sym[%d] = %d: 0..7", b, sym[b]);
-  const size_t P = V_.P;
-  d_whcn_.ensure((size_t)B * 17 * P);
-  d_count_.ensure(1);
-  s_sym_.ensure((size_t)B);
-  s_symf_.ensure((size_t)B * 17 * P);
+  const size_t n = (size_t)B * 17 * V_.P;
+  const float* whcn = stage(d_whcn_, feats, n);
+  const int32_t* d_sym = stage(s_sym_, sym, (size_t)B);
+  s_symf_.ensure(n);
   s_symp_.ensure((size_t)B * V_.A);
-  s_f32a_.ensure((size_t)B * P * 32);
-  s_f32b_.ensure((size_t)B * (V_.A + 1));
-  AGZ_HIP(hipMemcpyAsync(d_whcn_.p, feats, sizeof(float) * (size_t)B * 17 * P, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_sym_.p, sym, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(d_count_.p, &B, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)d_whcn_.p, s_symf_.p,
-                     (const int32_t*)s_sym_.p, V_.N, 17, 0, 0);
-  launch_whcn_to_x32(s_symf_.p, B, V_.N, s_f32a_.p, stream_);
-  net().forward(s_f32a_.p, d_count_.p, B, s_f32b_.p, s_f32b_.p + (size_t)B * V_.A);
-  hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)s_f32b_.p, s_symp_.p,
-                     (const int32_t*)s_sym_.p, V_.N, 1, 1, 1);
-  AGZ_HIP(hipGetLastError());
-  AGZ_HIP(hipMemcpyAsync(pi_out, s_symp_.p, sizeof(float) * (size_t)B * V_.A, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipMemcpyAsync(v_out, s_f32b_.p + (size_t)B * V_.A, sizeof(float) * B, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
-  net().check_async_error();
+  hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, whcn, s_symf_.p, d_sym, V_.N, 17, 0, 0);
+  launch_whcn_to_x32(s_symf_.p, B, V_.N, stage_forward(B), stream_);
+  forward_staged(B, d_sym, pi_out, v_out);
 }
 
 void Engine::set_hold(bool on) {
@@ -2016,7 +1974,7 @@ void Engine::set_hold(bool on) {
   if (hold_rel_.p) hold_rel_.zero(stream_);     // pending releases go: a parked slot waits for the next release
   V_.hold = on ? 1 : 0;                         // by value into the kernels: effective from the next step
   V_.released = hold_rel_.p;
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  wait();
 }
 
 void Engine::release() {
@@ -2047,77 +2005,63 @@ void Engine::fill_synthetic_inputs(int B) {
     x = (int8_t)(r == 2 ? -1 : r);
   }
   for (int b = 0; b < B; ++b) tp[b] = (b & 1) ? -1 : 1;
-  s_boards_.ensure(boards.size());
-  s_deltas_.ensure(deltas.size());
-  s_i32a_.ensure(B);
-  s_tp_.ensure(B);
-  d_count_.ensure(1);
-  s_f32a_.ensure((size_t)B * P * 32);
-  s_f32b_.ensure((size_t)B * (V_.A + 1));
-  AGZ_HIP(hipMemcpyAsync(s_boards_.p, boards.data(), boards.size(), hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_deltas_.p, deltas.data(), deltas.size(), hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_i32a_.p, nd.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_tp_.p, tp.data(), (size_t)B, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(d_count_.p, &B, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  launch_features_from_deltas(s_boards_.p, s_deltas_.p, s_i32a_.p, s_tp_.p, B, V_.N, s_f32a_.p, nullptr, stream_);
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  stage_positions(boards.data(), deltas.data(), nd.data(), tp.data(), B);
+  float* x32 = stage_forward(B);
+  launch_features_from_deltas(s_boards_.p, s_deltas_.p, s_i32a_.p, s_tp_.p, B, V_.N, x32, nullptr, stream_);
+  wait();      // the vectors above are stack-owned
+}
+
+// milliseconds per launch over `iters` launches, by two events on stream_
+template <class Launch>
+float Engine::time_launches(int iters, Launch launch) {
+  hipEvent_t e0, e1;
+  AGZ_HIP(hipEventCreate(&e0));
+  AGZ_HIP(hipEventCreate(&e1));
+  AGZ_HIP(hipEventRecord(e0, stream_));
+  for (int i = 0; i < iters; ++i) launch();
+  AGZ_HIP(hipEventRecord(e1, stream_));
+  AGZ_HIP(hipEventSynchronize(e1));
+  float ms = 0.f;
+  AGZ_HIP(hipEventElapsedTime(&ms, e0, e1));
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return ms / (float)iters;
 }
 
 float Engine::time_forward(int B, int iters) {
   AGZ_REQUIRE(B > 0 && iters > 0, AGZ_BAD_ARGUMENT, "B and iters must be positive");
   fill_synthetic_inputs(B);
-  net().forward(s_f32a_.p, d_count_.p, B, s_f32b_.p, s_f32b_.p + (size_t)B * V_.A);   // warm-up
-  hipEvent_t e0, e1;
-  AGZ_HIP(hipEventCreate(&e0));
-  AGZ_HIP(hipEventCreate(&e1));
-  AGZ_HIP(hipEventRecord(e0, stream_));
-  for (int i = 0; i < iters; ++i) net().forward(s_f32a_.p, d_count_.p, B, s_f32b_.p, s_f32b_.p + (size_t)B * V_.A);
-  AGZ_HIP(hipEventRecord(e1, stream_));
-  AGZ_HIP(hipEventSynchronize(e1));
-  float ms = 0.f;
-  AGZ_HIP(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return ms / (float)iters;
+  forward_x32(B);   // warm-up
+  return time_launches(iters, [&] { forward_x32(B); });
 }
 
 float Engine::time_conv(int B, int iters) {
   AGZ_REQUIRE(B > 0 && iters > 0, AGZ_BAD_ARGUMENT, "B and iters must be positive");
   fill_synthetic_inputs(B);
-  // one forward leaves real (post-ReLU, mixed-sign-weight) activations in the tower buffers
-  net().forward(s_f32a_.p, d_count_.p, B, s_f32b_.p, s_f32b_.p + (size_t)B * V_.A);
+  forward_x32(B);   // one forward leaves real (post-ReLU, mixed-sign-weight) activations in the tower buffers
   net_->launch_tower_conv_once(d_count_.p, B);
-  hipEvent_t e0, e1;
-  AGZ_HIP(hipEventCreate(&e0));
-  AGZ_HIP(hipEventCreate(&e1));
-  AGZ_HIP(hipEventRecord(e0, stream_));
-  for (int i = 0; i < iters; ++i) net_->launch_tower_conv_once(d_count_.p, B);
-  AGZ_HIP(hipEventRecord(e1, stream_));
-  AGZ_HIP(hipEventSynchronize(e1));
-  float ms = 0.f;
-  AGZ_HIP(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return ms / (float)iters;
+  return time_launches(iters, [&] { net_->launch_tower_conv_once(d_count_.p, B); });
 }
 
 void Engine::debug_draws(uint64_t seed, uint64_t game, uint32_t move, int n, double alpha, double* out) {
   if (n <= 0) return;
   s_f64_.ensure(n);
   hipLaunchKernelGGL(k_debug_draws, dim3(ceil_div(n, 64)), dim3(64), 0, stream_, seed, game, move, n, alpha, s_f64_.p);
-  AGZ_HIP(hipMemcpyAsync(out, s_f64_.p, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(out, s_f64_.p, (size_t)n);
+  wait();
 }
 
 void Engine::debug_math(int op, const double* x, const double* y, int n, double* out) {
   if (n <= 0) return;
-  s_f64_.ensure((size_t)3 * n);
-  AGZ_HIP(hipMemcpyAsync(s_f64_.p, x, sizeof(double) * n, hipMemcpyHostToDevice, stream_));
-  if (y) AGZ_HIP(hipMemcpyAsync(s_f64_.p + n, y, sizeof(double) * n, hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_debug_math, dim3(ceil_div(n, 64)), dim3(64), 0, stream_, V_, op, (const double*)s_f64_.p,
-                     (const double*)(s_f64_.p + n), n, s_f64_.p + 2 * (size_t)n);
-  AGZ_HIP(hipMemcpyAsync(out, s_f64_.p + 2 * (size_t)n, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  const size_t m = (size_t)n;
+  s_f64_.ensure(3 * m);
+  double* d = s_f64_.p;      // [x | y | out]
+  up(d, x, m);
+  if (y) up(d + m, y, m);
+  hipLaunchKernelGGL(k_debug_math, dim3(ceil_div(n, 64)), dim3(64), 0, stream_, V_, op, (const double*)d,
+                     (const double*)(d + m), n, d + 2 * m);
+  down(out, d + 2 * m, m);
+  wait();
 }
 
 // ---- Go rules
@@ -2125,52 +2069,42 @@ void Engine::debug_math(int op, const double* x, const double* y, int n, double*
 void Engine::go_play(const int8_t* boards, const int8_t* to_play, const int32_t* ko, const int32_t* moves, int B,
                      int8_t* boards_out, int32_t* ko_out, int32_t* ncap_out, int32_t* status_out) {
   if (B <= 0) return;
-  const size_t P = V_.P;
-  s_boards_.ensure((size_t)B * P);
-  s_boards_out_.ensure((size_t)B * P);
-  s_tp_.ensure(B);
-  s_i32a_.ensure(B); s_i32b_.ensure(B); s_i32c_.ensure((size_t)3 * B);
-  AGZ_HIP(hipMemcpyAsync(s_boards_.p, boards, (size_t)B * P, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_tp_.p, to_play, (size_t)B, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_i32a_.p, ko, sizeof(int32_t) * B, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_i32b_.p, moves, sizeof(int32_t) * B, hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_go_play, dim3(B), dim3(kWave), 0, stream_, V_, (const int8_t*)s_boards_.p,
-                     (const int8_t*)s_tp_.p, (const int32_t*)s_i32a_.p, (const int32_t*)s_i32b_.p, B,
-                     s_boards_out_.p, s_i32c_.p, s_i32c_.p + B, s_i32c_.p + 2 * (size_t)B);
-  AGZ_HIP(hipMemcpyAsync(boards_out, s_boards_out_.p, (size_t)B * P, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipMemcpyAsync(ko_out, s_i32c_.p, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipMemcpyAsync(ncap_out, s_i32c_.p + B, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipMemcpyAsync(status_out, s_i32c_.p + 2 * (size_t)B, sizeof(int32_t) * B, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  const size_t n = (size_t)B, P = V_.P;
+  const int8_t *d_boards = stage(s_boards_, boards, n * P), *d_tp = stage(s_tp_, to_play, n);
+  const int32_t *d_ko = stage(s_i32a_, ko, n), *d_moves = stage(s_i32b_, moves, n);
+  s_boards_out_.ensure(n * P);
+  s_i32c_.ensure(3 * n);
+  int32_t* o = s_i32c_.p;      // [ko | captures | status]
+  hipLaunchKernelGGL(k_go_play, dim3(B), dim3(kWave), 0, stream_, V_, d_boards, d_tp, d_ko, d_moves, B, s_boards_out_.p,
+                     o, o + n, o + 2 * n);
+  down(boards_out, s_boards_out_.p, n * P);
+  down(ko_out, o, n);
+  down(ncap_out, o + n, n);
+  down(status_out, o + 2 * n, n);
+  wait();
 }
 
 void Engine::go_legal(const int8_t* boards, const int8_t* to_play, const int32_t* ko, int B, int8_t* out) {
   if (B <= 0) return;
-  const size_t P = V_.P;
-  s_boards_.ensure((size_t)B * P);
-  s_tp_.ensure(B);
-  s_i32a_.ensure(B);
-  s_legal_.ensure((size_t)B * V_.A);
-  AGZ_HIP(hipMemcpyAsync(s_boards_.p, boards, (size_t)B * P, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_tp_.p, to_play, (size_t)B, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_i32a_.p, ko, sizeof(int32_t) * B, hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_go_legal, dim3(B), dim3(kWave), 0, stream_, V_, (const int8_t*)s_boards_.p,
-                     (const int8_t*)s_tp_.p, (const int32_t*)s_i32a_.p, B, s_legal_.p);
-  AGZ_HIP(hipMemcpyAsync(out, s_legal_.p, (size_t)B * V_.A, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  const size_t n = (size_t)B;
+  const int8_t *d_boards = stage(s_boards_, boards, n * V_.P), *d_tp = stage(s_tp_, to_play, n);
+  const int32_t* d_ko = stage(s_i32a_, ko, n);
+  s_legal_.ensure(n * V_.A);
+  hipLaunchKernelGGL(k_go_legal, dim3(B), dim3(kWave), 0, stream_, V_, d_boards, d_tp, d_ko, B, s_legal_.p);
+  down(out, s_legal_.p, n * V_.A);
+  wait();
 }
 
 void Engine::go_score(const int8_t* boards, const float* komi, int B, float* out) {
   if (B <= 0) return;
-  const size_t P = V_.P;
-  s_boards_.ensure((size_t)B * P);
-  s_f32a_.ensure((size_t)2 * B);
-  AGZ_HIP(hipMemcpyAsync(s_boards_.p, boards, (size_t)B * P, hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipMemcpyAsync(s_f32a_.p, komi, sizeof(float) * B, hipMemcpyHostToDevice, stream_));
-  hipLaunchKernelGGL(k_go_score, dim3(B), dim3(kWave), 0, stream_, V_, (const int8_t*)s_boards_.p,
-                     (const float*)s_f32a_.p, B, s_f32a_.p + B);
-  AGZ_HIP(hipMemcpyAsync(out, s_f32a_.p + B, sizeof(float) * B, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  const size_t n = (size_t)B;
+  const int8_t* d_boards = stage(s_boards_, boards, n * V_.P);
+  s_f32a_.ensure(2 * n);
+  float* d = s_f32a_.p;      // [komi | score]
+  up(d, komi, n);
+  hipLaunchKernelGGL(k_go_score, dim3(B), dim3(kWave), 0, stream_, V_, d_boards, (const float*)d, B, d + n);
+  down(out, d + n, n);
+  wait();
 }
 
 // ---- single-tree compat
@@ -2186,20 +2120,11 @@ void Engine::check_node(int g, int node) const {
 int Engine::tree_op(TreeArgs& T, int32_t* r0) {
   check_game(T.g);
   // stage host-side inputs
-  if (T.probs) {
-    s_f32a_.ensure(V_.A);
-    AGZ_HIP(hipMemcpyAsync(s_f32a_.p, T.probs, sizeof(float) * V_.A, hipMemcpyHostToDevice, stream_));
-    T.probs = s_f32a_.p;
-  }
-  if (T.board) {
-    s_boards_.ensure(V_.P);
-    AGZ_HIP(hipMemcpyAsync(s_boards_.p, T.board, (size_t)V_.P, hipMemcpyHostToDevice, stream_));
-    T.board = s_boards_.p;
-  }
+  if (T.probs) T.probs = stage(s_f32a_, T.probs, (size_t)V_.A);
+  if (T.board) T.board = stage(s_boards_, T.board, (size_t)V_.P);
   if (T.history && T.info.history_len > 0) {
     s_deltas_.ensure((size_t)7 * V_.P);
-    AGZ_HIP(hipMemcpyAsync(s_deltas_.p, T.history, (size_t)std::min(T.info.history_len, 7) * V_.P,
-                           hipMemcpyHostToDevice, stream_));
+    up(s_deltas_.p, T.history, (size_t)std::min(T.info.history_len, 7) * V_.P);
     T.history = s_deltas_.p;
   }
   double* host_dout = T.dout;
@@ -2210,9 +2135,9 @@ int Engine::tree_op(TreeArgs& T, int32_t* r0) {
   T.iout = s_iout_.p;
   hipLaunchKernelGGL(k_tree_op, dim3(1), dim3(kWave), 0, stream_, V_, T);
   int32_t iout[4] = {0, 0, 0, 0};
-  AGZ_HIP(hipMemcpyAsync(iout, s_iout_.p, sizeof(iout), hipMemcpyDeviceToHost, stream_));
-  if (host_dout) AGZ_HIP(hipMemcpyAsync(host_dout, s_f64_.p, sizeof(double) * V_.A, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(iout, s_iout_.p, 4);
+  down(host_dout, s_f64_.p, (size_t)V_.A);
+  wait();
   if (r0) *r0 = iout[1];
   return iout[0];
 }
@@ -2238,9 +2163,8 @@ void Engine::tree_leaf_features(int g, float* feats_out) {
   if (tree_batch_ <= 0) return;
   d_whcn_.ensure((size_t)bcap_ * 17 * V_.P);
   hipLaunchKernelGGL(k_leaf_features, dim3(V_.par), dim3(kWavesPerLeaf * kWave), 0, stream_, V_, g, V_.par, (float*)nullptr, d_whcn_.p);
-  AGZ_HIP(hipMemcpyAsync(feats_out, d_whcn_.p, sizeof(float) * (size_t)tree_batch_ * 17 * V_.P,
-                         hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(feats_out, d_whcn_.p, (size_t)tree_batch_ * 17 * V_.P);
+  wait();
 }
 
 // agz_tree_leaf_positions: the leaves of the last tree_search_select as the reference's GoPosition fields
@@ -2258,10 +2182,10 @@ void Engine::tree_leaf_positions(int g, int32_t* nodes, int8_t* boards, int8_t* 
   std::vector<int8_t> b8((size_t)n * 8 * P);
   std::vector<LeafPosRow> rows(n);
   GameState gs;
-  AGZ_HIP(hipMemcpyAsync(b8.data(), s_leafb_.p, b8.size(), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipMemcpyAsync(rows.data(), s_leafrows_.p, sizeof(LeafPosRow) * n, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipMemcpyAsync(&gs, V_.gs + g, sizeof(GameState), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(b8.data(), s_leafb_.p, b8.size());
+  down(rows.data(), (const LeafPosRow*)s_leafrows_.p, (size_t)n);
+  down(&gs, V_.gs + g, 1);
+  wait();
   for (int k = 0; k < n; ++k) {
     const LeafPosRow& r = rows[k];
     const int avail = std::min(7, (r.plen - 1) + gs.hist_len);   // older boards that exist (record_leaf)
@@ -2289,19 +2213,14 @@ int Engine::tree_search_incorporate(int g, const float* pi, const float* v) {
   const int n = tree_batch_;
   if (n > 0) {
     if (pi && v) {
-      AGZ_HIP(hipMemcpyAsync(d_pi_.p, pi, sizeof(float) * (size_t)n * V_.A, hipMemcpyHostToDevice, stream_));
-      AGZ_HIP(hipMemcpyAsync(d_v_.p, v, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, stream_));
-    } else {
-      d_count_.ensure(1);
-      AGZ_HIP(hipMemcpyAsync(d_count_.p, &n, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-      if (V_.symmetry) {
-        hipLaunchKernelGGL(k_leaf_features_sym, dim3(V_.par), dim3(kWavesPerLeaf * kWave), 0, stream_, V_, g, V_.par, d_x32_.p, (float*)nullptr);
-        net_->forward(d_x32_.p, d_count_.p, std::min(bcap_, V_.par), d_pi_.p, d_v_.p);
-        hipLaunchKernelGGL(k_pi_unpermute, dim3(V_.par), dim3(kWave), 0, stream_, V_, g, V_.par, d_pi_.p);
-      } else {
-        hipLaunchKernelGGL(k_leaf_features, dim3(V_.par), dim3(kWavesPerLeaf * kWave), 0, stream_, V_, g, V_.par, d_x32_.p, (float*)nullptr);
-        net_->forward(d_x32_.p, d_count_.p, std::min(bcap_, V_.par), d_pi_.p, d_v_.p);
-      }
+      up(d_pi_.p, pi, (size_t)n * V_.A);
+      up(d_v_.p, v, (size_t)n);
+    } else {      // the engine's own network, under the symmetry in force (`n` lives until tree_op below has synchronised)
+      stage(d_count_, &n, 1);
+      hipLaunchKernelGGL(V_.symmetry ? k_leaf_features_sym : k_leaf_features, dim3(V_.par), dim3(kWavesPerLeaf * kWave), 0,
+                         stream_, V_, g, V_.par, d_x32_.p, (float*)nullptr);
+      net_->forward(d_x32_.p, d_count_.p, std::min(bcap_, V_.par), d_pi_.p, d_v_.p);
+      if (V_.symmetry) hipLaunchKernelGGL(k_pi_unpermute, dim3(V_.par), dim3(kWave), 0, stream_, V_, g, V_.par, d_pi_.p);
     }
   }
   TreeArgs T;
@@ -2313,23 +2232,19 @@ int Engine::tree_search_incorporate(int g, const float* pi, const float* v) {
 
 void Engine::game_state(int g, GameState* out) {
   check_game(g);
-  AGZ_HIP(hipMemcpyAsync(out, V_.gs + g, sizeof(GameState), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  *out = fetch(V_.gs + g);
 }
 void Engine::game_patch(int g, const GameState& s) {
   check_game(g);
-  AGZ_HIP(hipMemcpyAsync(V_.gs + g, &s, sizeof(GameState), hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  put(V_.gs + g, s);
 }
 void Engine::node_meta(int g, int node, NodeMeta* out) {
   check_node(g, node);
-  AGZ_HIP(hipMemcpyAsync(out, V_.meta + node_index(V_, g, node), sizeof(NodeMeta), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  *out = fetch(V_.meta + node_index(V_, g, node));
 }
 void Engine::node_meta_set(int g, int node, const NodeMeta& m) {
   check_node(g, node);
-  AGZ_HIP(hipMemcpyAsync(V_.meta + node_index(V_, g, node), &m, sizeof(NodeMeta), hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  put(V_.meta + node_index(V_, g, node), m);
 }
 static float* row_base(const View& V, int field) {
   return field == AGZ_F_CHILD_N ? V.childN : field == AGZ_F_CHILD_W ? V.childW : V.childP;
@@ -2337,48 +2252,41 @@ static float* row_base(const View& V, int field) {
 void Engine::node_row_get(int g, int node, int field, float* out) {
   check_node(g, node);
   AGZ_REQUIRE(field >= 0 && field <= 2, AGZ_BAD_ARGUMENT, "field %d", field);
-  AGZ_HIP(hipMemcpyAsync(out, row_base(V_, field) + node_index(V_, g, node) * V_.AP, sizeof(float) * V_.A,
-                         hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(out, row_base(V_, field) + node_index(V_, g, node) * V_.AP, (size_t)V_.A);
+  wait();
 }
 void Engine::node_row_set(int g, int node, int field, const float* in) {
   check_node(g, node);
   AGZ_REQUIRE(field >= 0 && field <= 2, AGZ_BAD_ARGUMENT, "field %d", field);
-  AGZ_HIP(hipMemcpyAsync(row_base(V_, field) + node_index(V_, g, node) * V_.AP, in, sizeof(float) * V_.A,
-                         hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  up(row_base(V_, field) + node_index(V_, g, node) * V_.AP, in, (size_t)V_.A);
+  wait();
 }
 void Engine::node_children(int g, int node, int32_t* out) {
   check_node(g, node);
-  AGZ_HIP(hipMemcpyAsync(out, V_.child + node_index(V_, g, node) * V_.AP, sizeof(int32_t) * V_.A,
-                         hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(out, V_.child + node_index(V_, g, node) * V_.AP, (size_t)V_.A);
+  wait();
 }
 void Engine::node_board(int g, int node, int8_t* out) {
   check_node(g, node);
-  AGZ_HIP(hipMemcpyAsync(out, V_.board + node_index(V_, g, node) * V_.PP, (size_t)V_.P, hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  down(out, V_.board + node_index(V_, g, node) * V_.PP, (size_t)V_.P);
+  wait();
 }
 float Engine::node_stat(int g, int node, int which) {
   NodeMeta m;
   node_meta(g, node, &m);
-  float v = 0.f;
   const float* src;
   if (m.parent < 0) {
     src = which == 0 ? &V_.gs[g].rootN : &V_.gs[g].rootW;
   } else {
     src = (which == 0 ? V_.childN : V_.childW) + node_index(V_, g, m.parent) * V_.AP + m.fmove;
   }
-  AGZ_HIP(hipMemcpyAsync(&v, src, sizeof(float), hipMemcpyDeviceToHost, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
-  return v;
+  return fetch(src);
 }
 void Engine::node_set_N(int g, int node, float v) {
   NodeMeta m;
   node_meta(g, node, &m);
   float* dst = m.parent < 0 ? &V_.gs[g].rootN : V_.childN + node_index(V_, g, m.parent) * V_.AP + m.fmove;
-  AGZ_HIP(hipMemcpyAsync(dst, &v, sizeof(float), hipMemcpyHostToDevice, stream_));
-  AGZ_HIP(hipStreamSynchronize(stream_));
+  put(dst, v);
 }
 
 }  // namespace agz

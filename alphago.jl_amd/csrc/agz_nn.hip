@@ -386,12 +386,12 @@ const float* Net::host_slot(const FluxSlot& sl) const {
 
 // host vector -> its place in the device master (the host vectors never move: an enqueued copy may read them later)
 void Net::upload_slot(const FluxSlot& sl) {
-  AGZ_HIP(hipMemcpyAsync(d_flux_.p + sl.off, host_slot(sl), sizeof(float) * sl.n, hipMemcpyHostToDevice, stream_));
+  upload(d_flux_.p + sl.off, host_slot(sl), (size_t)sl.n, stream_);
 }
 void Net::upload_host_all() {
   std::vector<float> flat(flux_n_);
   for (const auto& sl : slots_) std::memcpy(flat.data() + sl.off, host_slot(sl), sizeof(float) * sl.n);
-  AGZ_HIP(hipMemcpyAsync(d_flux_.p, flat.data(), sizeof(float) * flux_n_, hipMemcpyHostToDevice, stream_));
+  upload(d_flux_.p, flat.data(), (size_t)flux_n_, stream_);
   AGZ_HIP(hipStreamSynchronize(stream_));
   derived_dirty_ = true;
   host_stale_ = false;
@@ -401,7 +401,7 @@ void Net::upload_host_all() {
 void Net::sync_host() const {
   if (!host_stale_) return;
   std::vector<float> flat(flux_n_);
-  AGZ_HIP(hipMemcpyAsync(flat.data(), d_flux_.p, sizeof(float) * flux_n_, hipMemcpyDeviceToHost, stream_));
+  download(flat.data(), d_flux_.p, (size_t)flux_n_, stream_);
   AGZ_HIP(hipStreamSynchronize(stream_));
   for (const auto& sl : slots_) std::memcpy(const_cast<float*>(host_slot(sl)), flat.data() + sl.off, sizeof(float) * sl.n);
   host_stale_ = false;
