@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <functional>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "agz_common.h"
@@ -15,6 +16,7 @@ namespace agz {
 constexpr int kC = 256;        // tower width, neural_net.jl:16
 constexpr int kCinStem = 17;   // 2*planes + 1, neural_net.jl:19
 constexpr int kCinStemPad = 32;
+constexpr int kWinoStages = 64, kWinoStemStages = 8;   // K-loop stages (padded input channels / 4) of a tower layer / the stem
 
 struct ConvHost {
   int k = 3, cin = 0, cout = 0;
@@ -25,6 +27,21 @@ struct DenseHost {
   int in = 0, out = 0;
   std::vector<float> w, b;
 };
+
+// One family of inference weight images derived from a layer's Flux tensor [3][3][cin][256]: what Net and
+// the trainer need of it.  ns: K-loop stages = padded input channels / 4 (kWinoStages for a tower layer, kWinoStemStages for
+// the stem).  Each is image_family<trait>() of agz_pack.h, defined next to the kernel that reads the image.
+struct ImageFamily {
+  const char* name;
+  size_t (*bytes)(int ns);                                       // of one layer's image
+  void (*host_pack)(const ConvHost& c, void* out, int ns);       // host restatement (test reference)
+  // the product: `layers` tensors on the device, wstride floats apart -> `layers` images
+  void (*device_pack)(const float* d_w, long wstride, int cin, int layers, void* d_out, int ns, hipStream_t s);
+};
+extern const ImageFamily kDirectImage;                     // Wt[cout][tap][cin_pad]: the direct kernel's and the trainer's layout
+extern const ImageFamily kWinoImage, kWinoSplitImage;      // F(3x3,3x3) U; its split-half form (AGZ_PRECISION_F32S)
+extern const ImageFamily kWino4Image, kWino5Image;         // F(4x4,3x3) U; the five-pass form's U
+extern const ImageFamily kConv16Image;                     // fp16 fragments in MFMA operand order
 
 bool wino4_applies(int N);      // agz_wino4.hip (declared with the rest of its interface below)
 bool wino_fusable(int N);       // agz_wino.hip
@@ -58,7 +75,7 @@ class Net {
   float* flux_device() { return d_flux_.p; }
   size_t flux_count() const { return flux_n_; }
   size_t flux_offset(int layer, int kind) const;
-  void device_master_written() { host_stale_ = true; derived_dirty_ = true; ++param_version_; }
+  void device_master_written() { host_stale_ = true; ++param_version_; }
   // (test hook) words of the device images that differ from the host restatement of the same packs; -1 if `which` is unknown
   long debug_pack_diff(int which);
 
@@ -130,6 +147,39 @@ class Net {
 
  private:
   void pack();
+  // The built images: which family, of the stem or of the tower's layers, under which settings it is read, where, and the
+  // param_version_ it was built from.  `which`: its id for agz_debug_pack_diff (include/agz_debug.h).  pack() builds the
+  // ones the current settings read: the base images (direct, F(3x3,3x3)) always, the optional ones while their mode is selected.
+  enum ImageId { kDirectStem, kDirectTower, kWinoStem, kWinoTower, kSplitStem, kSplitTower, kWino4Tower, kWino5Tower, kF16Tower, kImages };
+  struct BuiltImage {
+    const ImageFamily* family;
+    bool stem;
+    int which;
+    bool (*needed)(const Net&);
+    DevBuf<uint32_t> buf;          // (every image is a whole number of 32-bit words, the unit agz_debug_pack_diff counts)
+    uint64_t version = ~0ull;      // never built
+  };
+  static bool always(const Net&) { return true; }
+  static bool with_tower(const Net& n) { return n.tower_ > 0; }
+  static bool split_selected(const Net& n) { return n.tower_ > 0 && n.precision_ == 2; }
+  template <TowerForm F> static bool form_is(const Net& n) { return n.tower_form() == F; }      // (no tower: Direct)
+  BuiltImage images_[kImages] = {{&kDirectImage, true, 0, always},
+                                 {&kDirectImage, false, 0, with_tower},
+                                 {&kWinoImage, true, 1, with_tower},
+                                 {&kWinoImage, false, 1, with_tower},
+                                 {&kWinoSplitImage, true, 4, split_selected},
+                                 {&kWinoSplitImage, false, 4, split_selected},
+                                 {&kWino4Image, false, 2, form_is<TowerForm::Wino4>},
+                                 {&kWino5Image, false, 6, form_is<TowerForm::Wino5>},
+                                 {&kConv16Image, false, 3, form_is<TowerForm::F16>}};
+  uint64_t affines_version_ = ~0ull;      // the folded affines and the head block: built whenever the master changed
+  int image_stages(const BuiltImage& im) const { return im.stem ? kWinoStemStages : kWinoStages; }
+  // layer l of image `id`, as the kernels read it
+  template <class T>
+  const T* image(ImageId id, int l = 0) const {
+    const BuiltImage& im = images_[id];
+    return reinterpret_cast<const T*>(im.buf.p + im.family->bytes(image_stages(im)) / 4 * l);
+  }
   // forward() = stem -> tower (one of these, by form) -> heads
   void stem(TowerForm form, const float* d_x32, const int* d_count, int bcap);
   void direct_tower(const int* d_count, int bcap);
@@ -153,7 +203,6 @@ class Net {
   std::vector<FluxSlot> slots_;
   size_t flux_n_ = 0;
   DevBuf<float> d_flux_;
-  bool derived_dirty_ = true;          // the inference images are older than the device master
   mutable bool host_stale_ = false;    // the host vectors are older than the device master
   uint64_t param_version_ = 0;
   void upload_slot(const FluxSlot& s);
@@ -161,7 +210,6 @@ class Net {
   const float* host_slot(const FluxSlot& s) const;
 
   // device-resident packed parameters
-  DevBuf<float> d_wstem_, d_wtower_;      // [cout][9*cin_pad] per layer
   DevBuf<float> d_scale_, d_shift_;       // (1 + 2*tower) x 256
   DevBuf<float> d_head_;                  // head conv weights + affine
   const float *d_vfc1w_ = nullptr, *d_vfc1b_ = nullptr, *d_vfc2w_ = nullptr, *d_vfc2b_ = nullptr, *d_pfcw_ = nullptr,
@@ -170,21 +218,13 @@ class Net {
   int bcap_ = 0;
   DevBuf<float> d_a_, d_b_, d_t_, d_vh_, d_ph_;
   int winograd_ = 1;                           // set_winograd's mode
-  DevBuf<float> d_uwino5_;                     // five-pass F(3x3,3x3) weights (agz_wino5.hip), packed when first used
-  bool packed5_ = false;
-  DevBuf<float> d_uwino4_;                     // F(4x4,3x3) transformed weights (agz_wino4.hip), packed when first used
-  bool packed4_ = false;
   static constexpr int kMaxTowerStreams = 4;
   int tower_streams_ = 2;
   hipStream_t streamx_[kMaxTowerStreams - 1] = {nullptr, nullptr, nullptr};      // chains 1.. (chain 0 runs on stream_)
   hipEvent_t ev_fork_ = nullptr, ev_join_[kMaxTowerStreams - 1] = {nullptr, nullptr, nullptr};
-  DevBuf<float> d_uwino_s_, d_scale_s_;        // split form: weights as halves, scale x 1 / (operand scales)
-  bool packed_split_ = false;
-  DevBuf<float> d_uwino_, d_vimg_, d_vimg2_;   // transformed weights (stage images) / transformed activations (ping-pong)
-  DevBuf<float> d_ustem_, d_ustem_s_;          // the stem's transformed weights (8 stages), f32 / split form
+  DevBuf<float> d_scale_s_;                    // split form: scale x 1 / (operand scales)
+  DevBuf<float> d_vimg_, d_vimg2_;             // transformed activations (ping-pong)
   int precision_ = 0;
-  bool packed16_ = false;
-  DevBuf<uint16_t> d_wi16_;               // fp16 tower weights as padded LDS tile images [layer][stage 72][256][40]
   DevBuf<uint16_t> d_ha_, d_hb_, d_ht_;   // fp16 tower activations [rows][256]
   // persistent tower launch
   bool tower_persistent_ = false;
@@ -229,9 +269,6 @@ class Trainer {
   int n_optw_ = 0;
 };
 
-// `layers` Flux tensors [3][3][cin][256] on the device, wstride floats apart -> Wt[cout][tap][cin_pad] images (the direct
-// kernel's and the trainer's layout)
-void launch_pack_direct(const float* d_w, long wstride, int cin, int cin_pad, int layers, float* d_out, hipStream_t s);
 // the direct implicit-GEMM 3x3 convolution of agz_nn.hip (y = act(scale * conv + shift (+ res))), cin_pad = 32 or 256
 void launch_conv3x3_direct_taps(const float* x, const float* wt, const float* ones, const float* zeros, const float* shift,
                                 float* y, float* part, const int* d_count, int bcap, int N, int cin_pad, hipStream_t s);
@@ -240,11 +277,6 @@ void launch_conv3x3_direct(const float* x, const float* wt, const float* scale, 
                            float* y, const int* d_count, int bcap, int N, int relu, int cin_pad, hipStream_t s);
 
 // Winograd F(3x3,3x3) tower convolution (agz_wino.hip)
-constexpr int kWinoStages = 64, kWinoStemStages = 8;   // K-loop stages (input channels / 4) of a tower layer / the stem
-void wino_pack_weights(const ConvHost& c, float* out, int ns = kWinoStages);          // host restatement (test reference)
-// the product: `layers` Flux tensors [3][3][cin][256] on the device, wstride floats apart -> `layers` U images
-void launch_wino_pack(const float* d_w, long wstride, int cin, int layers, float* d_out, int ns, bool split, hipStream_t s);
-size_t wino_weight_floats(int ns = kWinoStages);
 size_t wino_v_floats(int bcap, int T);
 long wino_blocks(int bcap, int T);           // tile blocks of a batch (64 rows; whole boards where they fit: 63 at 9x9)
 // The part-th of `parts` equal ranges [tb0, tb1) of `blocks` tile blocks (`pairs`: of whole block pairs).  Ranges that hold
@@ -283,15 +315,26 @@ size_t wino_tower_sched_ints(int layers, int bcap, int N);
 bool wino_tower_supported(hipStream_t s);
 void launch_wino_tower(const void* d_layers, int layers, int* d_sched, const int* d_count, int bcap, int N, bool split, hipStream_t s);
 constexpr int kWinoTowerErrWord = 8;         // int offset of the scheduler's error word in d_sched
-// split-operand form (AGZ_PRECISION_F32S): weights as (hi, lo) halves of 2^10 u; 1 / (operand scales) for the epilogue
-void wino_pack_weights_split(const ConvHost& c, float* out, int ns = kWinoStages);
+// split-operand form (AGZ_PRECISION_F32S): weights as (hi, lo) halves of 2^10 u (kWinoSplitImage); 1 / (operand scales) for
+// the epilogue
 float wino_split_descale();
 
+// launch(std::integral_constant<int, MODE>) for what a fused GEMM launch writes and reads -- MODE bit 0: y, bit 1: the next
+// layer's V, bit 2: a residual -- over the six combinations that write something (the F(4x4,3x3) and five-pass kernels)
+template <class Launch>
+void dispatch_mode(const void* y, const void* vnext, const void* res, Launch&& launch) {
+  switch ((y ? 1 : 0) | (vnext ? 2 : 0) | (res ? 4 : 0)) {
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 3: launch(std::integral_constant<int, 3>{}); break;
+    case 5: launch(std::integral_constant<int, 5>{}); break;
+    case 6: launch(std::integral_constant<int, 6>{}); break;
+    default: launch(std::integral_constant<int, 7>{}); break;
+  }
+}
+
 // Winograd F(3x3,3x3) tower layer in five one-row passes over a 64-tile x 128-cout workgroup tile (agz_wino5.hip): reads the
-// V images of agz_wino.hip's kernels, its own U image; whole-board tile blocks (N <= 12), exact f32
-void wino5_pack_weights(const ConvHost& c, float* out);                              // host restatement (test reference)
-void launch_wino5_pack(const float* d_w, long wstride, int layers, float* d_out, hipStream_t s);
-size_t wino5_weight_floats();
+// V images of agz_wino.hip's kernels, its own U image (kWino5Image); whole-board tile blocks (N <= 12), exact f32
 void launch_wino5_gemm(const float* vimg, const float* uimg, const float* scale, const float* shift, const float* res,
                        float* y, float* vnext, const int* d_count, int bcap, int N, int relu, hipStream_t s, int part = 0,
                        int parts = 1);
@@ -301,9 +344,6 @@ void launch_wino5_gemm(const float* vimg, const float* uimg, const float* scale,
 constexpr int kWino4Stages = 96;             // K-loop stages of a layer: six passes (transform rows) x 16 stages of 6 planes x 16 cin
 bool wino4_applies(int N);                   // N >= 13: fewer multiplies per output point than F(3x3,3x3)
 bool wino4_whole_boards(int N);              // tile blocks hold whole boards (N = 13..16); else dense blocks + fix-up transform
-void wino4_pack_weights(const ConvHost& c, float* out);                              // host restatement (test reference)
-void launch_wino4_pack(const float* d_w, long wstride, int layers, float* d_out, hipStream_t s);
-size_t wino4_weight_floats();
 size_t wino4_v_floats(int bcap, int N);
 // x -> V (all tiles), or with fixup only the tiles the previous GEMM's epilogue could not emit (dense blocks)
 void launch_wino4_in(const float* x, float* vimg, const int* d_count, int bcap, int N, hipStream_t s, bool fixup, int part = 0,
@@ -317,10 +357,7 @@ bool wino4_paired(int N);                    // five boards per two tile blocks 
 void wino4_validate(int bcap, int N);        // throws if the batch's tile index / byte offsets leave 32 bits (before any launch)
 // (part / parts: the part-th of `parts` ranges of tile blocks, cut at board boundaries: ranges are independent layer chains)
 
-// fp16-operand tower convolution (agz_conv16.hip); x is half, res / y are float* or half* as flagged
-void conv16_pack_images(const ConvHost& c, uint16_t* out);                           // host restatement (test reference)
-void launch_conv16_pack(const float* d_w, long wstride, int layers, uint16_t* d_out, hipStream_t s);
-size_t conv16_image_halves();
+// fp16-operand tower convolution (agz_conv16.hip); x is half, res / y are float* or half* as flagged; wi: kConv16Image
 void launch_conv16_dma(const uint16_t* x, const uint16_t* wi, const float* scale, const float* shift, const void* res,
                        int res_f32, void* y, int out_f32, const int* d_count, int bcap, int N, int relu, hipStream_t s);
 void launch_f32_to_f16(const float* x, uint16_t* y, const int* d_count, int bcap, int N, hipStream_t s);

@@ -16,6 +16,7 @@
 // chunk; weights are pre-packed once to Wt[cout][tap][cin] with the true-convolution kernel
 // flip of NNlib applied at pack time, so the B-tile has the same shape as the A-tile.
 #include "agz_nn.h"
+#include "agz_pack.h"
 
 #include <cmath>
 #include <algorithm>
@@ -393,7 +394,6 @@ void Net::upload_host_all() {
   for (const auto& sl : slots_) std::memcpy(flat.data() + sl.off, host_slot(sl), sizeof(float) * sl.n);
   upload(d_flux_.p, flat.data(), (size_t)flux_n_, stream_);
   AGZ_HIP(hipStreamSynchronize(stream_));
-  derived_dirty_ = true;
   host_stale_ = false;
 }
 
@@ -468,7 +468,6 @@ void Net::set(int layer, int kind, const float* data, int64_t count) {
   // the copy reads a pageable host vector: drain it before anything (init_synthetic, conv_init, ~Net) may reassign or
   // free that vector.  ~20 us per parameter; bulk device-side paths (train step, broadcast) do not come here.
   AGZ_HIP(hipStreamSynchronize(stream_));
-  derived_dirty_ = true;
 }
 
 void Net::get(int layer, int kind, float* out, int64_t count) const {
@@ -521,32 +520,21 @@ void Net::init_synthetic(uint64_t seed) {
   upload_host_all();
 }
 
-// Flux [kw,kh,cin,cout] column-major -> Wt[cout][tap][cin_pad].  NNlib's conv is a TRUE
-// convolution: Flux index (a,b) multiplies x[i + 1 - a, j + 1 - b], i.e. tap offset
-// (da,db) = (1-a, 1-b); tap = (da+1) + 3*(db+1).  Element idx of the image (0 in the channel padding):
-__host__ __device__ inline float direct_image_element(const float* w, int cin, int cin_pad, size_t idx) {
-  const int ci = (int)(idx % cin_pad), tap = (int)((idx / cin_pad) % 9), o = (int)(idx / ((size_t)9 * cin_pad));
-  const int a = 2 - tap % 3, b = 2 - tap / 3;
-  return ci < cin ? w[a + 3 * (b + 3 * (ci + (size_t)cin * o))] : 0.f;
-}
-static void pack_conv3(const ConvHost& c, int cin_pad, float* out) {          // host restatement (test reference)
-  const size_t n = (size_t)c.cout * 9 * cin_pad;
-  for (size_t i = 0; i < n; ++i) out[i] = direct_image_element(c.w.data(), c.cin, cin_pad, i);
-}
-__global__ __launch_bounds__(256) void k_pack_direct(const float* __restrict__ w, long wstride, int cin, int cin_pad, int layers,
-                                                     float* __restrict__ out) {
-  const long per = (long)kC * 9 * cin_pad, n = per * layers;
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long)gridDim.x * 256) {
-    const long l = t / per;
-    out[t] = direct_image_element(w + l * wstride, cin, cin_pad, (size_t)(t - l * per));
+// Flux [kw,kh,cin,cout] column-major -> Wt[cout][tap][cin_pad], cin_pad = 4 ns, with the true-convolution flip (flux_tap):
+// tap = (da+1) + 3*(db+1) reads x[i + da, j + db].  One unit = element idx of the image (0 in the channel padding).
+struct DirectImage : ImageDefaults {
+  using word = float;
+  static constexpr const char* name = "direct";
+  static constexpr int grid_cap = 8192;
+  __host__ __device__ static size_t words(int ns) { return (size_t)kC * 9 * 4 * ns; }
+  __host__ __device__ static long units(int, int ns) { return (long)words(ns); }
+  __host__ __device__ static void put(const float* w, int cin, long idx, int ns, float* out) {
+    const int cin_pad = 4 * ns;
+    const int ci = (int)(idx % cin_pad), tap = (int)((idx / cin_pad) % 9), o = (int)(idx / ((long)9 * cin_pad));
+    out[idx] = ci < cin ? flux_tap(w, cin, tap % 3, tap / 3, ci, o) : 0.f;
   }
-}
-
-void launch_pack_direct(const float* d_w, long wstride, int cin, int cin_pad, int layers, float* d_out, hipStream_t s) {
-  const long n = (long)kC * 9 * cin_pad * layers;
-  hipLaunchKernelGGL(k_pack_direct, dim3((int)std::min<long>((n + 255) / 256, 8192)), dim3(256), 0, s, d_w, wstride, cin, cin_pad,
-                     layers, d_out);
-}
+};
+const ImageFamily kDirectImage = image_family<DirectImage>();
 
 // inference BatchNorm folded into the convolution: y = scale * conv + shift, in float64, rounded once
 __host__ __device__ inline void bn_affine_one(float gamma, float var, float eps, float beta, float b, float mean, float* scale,
@@ -592,155 +580,98 @@ __global__ void k_pack_head(const float* __restrict__ vw, const float* __restric
   }
 }
 
-// Every inference image from the device master, by kernels on stream_: no host work, no synchronisation.  The optional
-// images (F(4x4,3x3), fp16, split) are built when the mode that reads them is first used, and again whenever the master changes.
+// Every inference image from the device master, by kernels on stream_: no host work, no synchronisation.  An image is built
+// when the settings read it and it is not of this master version: the base images whenever the master changed, the optional
+// ones on the first forward that selects them, and again after every change while selected.
 void Net::pack() {
   const int L = 1 + 2 * tower_;
   const float* F = d_flux_.p;
-  const size_t w0 = flux_offset(0, AGZ_K_WEIGHT);
-  const size_t w1 = tower_ > 0 ? flux_offset(1, AGZ_K_WEIGHT) : 0;
-  const long tstride = tower_ > 0 ? (long)(flux_offset(2, AGZ_K_WEIGHT) - w1) : 0;      // tower layers (2 per block) are equally spaced
-  const TowerForm form = tower_form();
-  if (derived_dirty_) { packed4_ = packed5_ = packed16_ = packed_split_ = false; }
-  if (form == TowerForm::Wino5 && !packed5_) {
-    d_uwino5_.ensure(wino5_weight_floats() * 2 * tower_);
-    launch_wino5_pack(F + w1, tstride, 2 * tower_, d_uwino5_.p, stream_);
-    packed5_ = true;
+  // tower layers (2 per block) are equally spaced in the master
+  auto tstride = [&] { return (long)(flux_offset(2, AGZ_K_WEIGHT) - flux_offset(1, AGZ_K_WEIGHT)); };
+  bool launched = false;
+  for (BuiltImage& im : images_) {
+    if (im.version == param_version_ || !im.needed(*this)) continue;
+    const int layers = im.stem ? 1 : 2 * tower_, ns = image_stages(im);
+    const size_t bytes = im.family->bytes(ns);
+    AGZ_REQUIRE(bytes % 4 == 0, AGZ_BAD_ARGUMENT, "%s image: %zu bytes per layer are not whole 32-bit words", im.family->name, bytes);
+    im.buf.ensure(bytes / 4 * layers);
+    im.family->device_pack(F + flux_offset(im.stem ? 0 : 1, AGZ_K_WEIGHT), im.stem ? 0 : tstride(), im.stem ? kCinStem : kC, layers,
+                           im.buf.p, ns, stream_);
+    im.version = param_version_;
+    launched = true;
   }
-  if (precision_ == 2 && tower_ > 0 && !packed_split_) {
-    d_uwino_s_.ensure(wino_weight_floats() * 2 * tower_);
-    launch_wino_pack(F + w1, tstride, kC, 2 * tower_, d_uwino_s_.p, kWinoStages, true, stream_);
-    d_ustem_s_.ensure(wino_weight_floats(kWinoStemStages));
-    launch_wino_pack(F + w0, 0, kCinStem, 1, d_ustem_s_.p, kWinoStemStages, true, stream_);
-    packed_split_ = true;
+  if (affines_version_ != param_version_) {
+    d_scale_.ensure((size_t)L * kC);
+    d_shift_.ensure((size_t)L * kC);
+    d_scale_s_.ensure((size_t)L * kC);
+    // affines: stem row 0, tower layer l row l; the split form's scales (x 1 / (operand scales)) tower first, the stem's last
+    hipLaunchKernelGGL(k_bn_affine, dim3(1), dim3(256), 0, stream_, F + flux_offset(0, AGZ_K_BIAS), 0L, 1, kC, d_scale_.p, d_shift_.p,
+                       d_scale_s_.p + (size_t)2 * tower_ * kC, wino_split_descale());
+    if (tower_ > 0)
+      hipLaunchKernelGGL(k_bn_affine, dim3(2 * tower_), dim3(256), 0, stream_, F + flux_offset(1, AGZ_K_BIAS), tstride(), 2 * tower_, kC,
+                         d_scale_.p + kC, d_shift_.p + kC, d_scale_s_.p, wino_split_descale());
+    d_head_.ensure(776);
+    hipLaunchKernelGGL(k_pack_head, dim3(1), dim3(256), 0, stream_, F + flux_offset(AGZ_L_VALUE_CONV, AGZ_K_WEIGHT),
+                       F + flux_offset(AGZ_L_POLICY_CONV, AGZ_K_WEIGHT), d_head_.p);
+    // the dense layers are read where they are
+    d_vfc1w_ = F + flux_offset(AGZ_L_VALUE_FC1, AGZ_K_WEIGHT); d_vfc1b_ = F + flux_offset(AGZ_L_VALUE_FC1, AGZ_K_BIAS);
+    d_vfc2w_ = F + flux_offset(AGZ_L_VALUE_FC2, AGZ_K_WEIGHT); d_vfc2b_ = F + flux_offset(AGZ_L_VALUE_FC2, AGZ_K_BIAS);
+    d_pfcw_ = F + flux_offset(AGZ_L_POLICY_FC, AGZ_K_WEIGHT); d_pfcb_ = F + flux_offset(AGZ_L_POLICY_FC, AGZ_K_BIAS);
+    affines_version_ = param_version_;
+    launched = true;
   }
-  if (form == TowerForm::Wino4 && !packed4_) {
-    d_uwino4_.ensure(wino4_weight_floats() * 2 * tower_);
-    launch_wino4_pack(F + w1, tstride, 2 * tower_, d_uwino4_.p, stream_);
-    packed4_ = true;
-  }
-  if (form == TowerForm::F16 && !packed16_) {
-    d_wi16_.ensure(conv16_image_halves() * 2 * tower_);
-    launch_conv16_pack(F + w1, tstride, 2 * tower_, d_wi16_.p, stream_);
-    packed16_ = true;
-  }
-  if (!derived_dirty_) return;
-  d_wstem_.ensure((size_t)kC * 9 * kCinStemPad);
-  launch_pack_direct(F + w0, 0, kCinStem, kCinStemPad, 1, d_wstem_.p, stream_);
-  d_scale_.ensure((size_t)L * kC);
-  d_shift_.ensure((size_t)L * kC);
-  d_scale_s_.ensure((size_t)L * kC);
-  // affines: stem row 0, tower layer l row l; the split form's scales (x 1 / (operand scales)) tower first, the stem's last
-  hipLaunchKernelGGL(k_bn_affine, dim3(1), dim3(256), 0, stream_, F + flux_offset(0, AGZ_K_BIAS), 0L, 1, kC, d_scale_.p, d_shift_.p,
-                     d_scale_s_.p + (size_t)2 * tower_ * kC, wino_split_descale());
-  if (tower_ > 0) {
-    hipLaunchKernelGGL(k_bn_affine, dim3(2 * tower_), dim3(256), 0, stream_, F + flux_offset(1, AGZ_K_BIAS), tstride, 2 * tower_, kC,
-                       d_scale_.p + kC, d_shift_.p + kC, d_scale_s_.p, wino_split_descale());
-    d_wtower_.ensure((size_t)kC * 9 * kC * 2 * tower_);
-    launch_pack_direct(F + w1, tstride, kC, kC, 2 * tower_, d_wtower_.p, stream_);
-    d_uwino_.ensure(wino_weight_floats() * 2 * tower_);
-    launch_wino_pack(F + w1, tstride, kC, 2 * tower_, d_uwino_.p, kWinoStages, false, stream_);
-    d_ustem_.ensure(wino_weight_floats(kWinoStemStages));
-    launch_wino_pack(F + w0, 0, kCinStem, 1, d_ustem_.p, kWinoStemStages, false, stream_);
-  }
-  d_head_.ensure(776);
-  hipLaunchKernelGGL(k_pack_head, dim3(1), dim3(256), 0, stream_, F + flux_offset(AGZ_L_VALUE_CONV, AGZ_K_WEIGHT),
-                     F + flux_offset(AGZ_L_POLICY_CONV, AGZ_K_WEIGHT), d_head_.p);
-  // the dense layers are read where they are
-  d_vfc1w_ = F + flux_offset(AGZ_L_VALUE_FC1, AGZ_K_WEIGHT); d_vfc1b_ = F + flux_offset(AGZ_L_VALUE_FC1, AGZ_K_BIAS);
-  d_vfc2w_ = F + flux_offset(AGZ_L_VALUE_FC2, AGZ_K_WEIGHT); d_vfc2b_ = F + flux_offset(AGZ_L_VALUE_FC2, AGZ_K_BIAS);
-  d_pfcw_ = F + flux_offset(AGZ_L_POLICY_FC, AGZ_K_WEIGHT); d_pfcb_ = F + flux_offset(AGZ_L_POLICY_FC, AGZ_K_BIAS);
-  AGZ_HIP(hipGetLastError());
-  derived_dirty_ = false;
+  if (launched) AGZ_HIP(hipGetLastError());
 }
 
-// (test hook, agz_debug_pack_diff) the device images against the host restatement of the same packs, word for word
+// (test hook, agz_debug_pack_diff) the device images against the host restatement of the same packs, word for word: the
+// images of family `which` that the current settings read (none: 0), layer by layer; the split form's scales with family 4;
+// the folded affines and the head block are family 5
 long Net::debug_pack_diff(int which) {
   pack();
   sync_host();
+  if (which < 0 || which > 6) return -1;
   const int L = 1 + 2 * tower_;
-  auto diff = [&](const void* dev, const void* host, size_t bytes) {
-    std::vector<uint32_t> got((bytes + 3) / 4, 0);
-    AGZ_HIP(hipMemcpyAsync(got.data(), dev, bytes, hipMemcpyDeviceToHost, stream_));
+  auto diff = [&](const auto* dev, const auto& host) {      // host: a vector of 32-bit words, float or raw
+    static_assert(sizeof(host[0]) == 4, "debug_pack_diff counts 32-bit words");
+    auto got = host;
+    download(got.data(), dev, got.size(), stream_);
     AGZ_HIP(hipStreamSynchronize(stream_));
-    const uint32_t* want = static_cast<const uint32_t*>(host);
     long bad = 0;
-    for (size_t i = 0; i < bytes / 4; ++i) bad += got[i] != want[i];
+    for (size_t i = 0; i < got.size(); ++i) bad += std::memcmp(&got[i], &host[i], 4) != 0;
     return bad;
   };
-  switch (which) {
-    case 0: {      // direct images (stem + tower)
-      std::vector<float> w((size_t)kC * 9 * kCinStemPad);
-      pack_conv3(stem_, kCinStemPad, w.data());
-      long bad = diff(d_wstem_.p, w.data(), w.size() * 4);
-      const size_t per = (size_t)kC * 9 * kC;
-      w.resize(per);
-      for (int l = 0; l < 2 * tower_; ++l) { pack_conv3(tconv_[l], kC, w.data()); bad += diff(d_wtower_.p + per * l, w.data(), per * 4); }
-      return bad;
+  long bad = 0;
+  for (const BuiltImage& im : images_) {
+    if (im.which != which || !im.needed(*this)) continue;
+    std::vector<uint32_t> img(im.family->bytes(image_stages(im)) / 4);
+    for (int l = 0; l < (im.stem ? 1 : 2 * tower_); ++l) {
+      im.family->host_pack(im.stem ? stem_ : tconv_[l], img.data(), image_stages(im));
+      bad += diff(im.buf.p + img.size() * l, img);
     }
-    case 1: {      // F(3x3,3x3) images (tower + stem)
-      long bad = 0;
-      std::vector<float> u(wino_weight_floats());
-      for (int l = 0; l < 2 * tower_; ++l) { wino_pack_weights(tconv_[l], u.data()); bad += diff(d_uwino_.p + u.size() * l, u.data(), u.size() * 4); }
-      if (tower_ > 0) {
-        std::vector<float> us(wino_weight_floats(kWinoStemStages));
-        wino_pack_weights(stem_, us.data(), kWinoStemStages);
-        bad += diff(d_ustem_.p, us.data(), us.size() * 4);
-      }
-      return bad;
-    }
-    case 2: {      // F(4x4,3x3) images
-      if (tower_form() != TowerForm::Wino4) return 0;
-      long bad = 0;
-      std::vector<float> u(wino4_weight_floats());
-      for (int l = 0; l < 2 * tower_; ++l) { wino4_pack_weights(tconv_[l], u.data()); bad += diff(d_uwino4_.p + u.size() * l, u.data(), u.size() * 4); }
-      return bad;
-    }
-    case 3: {      // fp16 images (precision f16 selected)
-      if (tower_form() != TowerForm::F16) return 0;
-      long bad = 0;
-      std::vector<uint16_t> wi(conv16_image_halves());
-      for (int l = 0; l < 2 * tower_; ++l) { conv16_pack_images(tconv_[l], wi.data()); bad += diff(d_wi16_.p + wi.size() * l, wi.data(), wi.size() * 2); }
-      return bad;
-    }
-    case 4: {      // split images + scales (precision f32s selected)
-      if (precision_ != 2 || tower_ == 0) return 0;
-      long bad = 0;
-      std::vector<float> u(wino_weight_floats());
-      for (int l = 0; l < 2 * tower_; ++l) { wino_pack_weights_split(tconv_[l], u.data()); bad += diff(d_uwino_s_.p + u.size() * l, u.data(), u.size() * 4); }
-      std::vector<float> us(wino_weight_floats(kWinoStemStages));
-      wino_pack_weights_split(stem_, us.data(), kWinoStemStages);
-      bad += diff(d_ustem_s_.p, us.data(), us.size() * 4);
-      std::vector<float> sc((size_t)L * kC), tmp(kC);
-      for (int l = 0; l <= 2 * tower_; ++l) {
-        bn_affine(l < 2 * tower_ ? tconv_[l] : stem_, sc.data() + (size_t)l * kC, tmp.data());
-        for (int o = 0; o < kC; ++o) sc[(size_t)l * kC + o] *= wino_split_descale();
-      }
-      return bad + diff(d_scale_s_.p, sc.data(), sc.size() * 4);
-    }
-    case 6: {      // five-pass F(3x3,3x3) images (agz_net_set_winograd(3))
-      if (tower_form() != TowerForm::Wino5) return 0;
-      long bad = 0;
-      std::vector<float> u(wino5_weight_floats());
-      for (int l = 0; l < 2 * tower_; ++l) { wino5_pack_weights(tconv_[l], u.data()); bad += diff(d_uwino5_.p + u.size() * l, u.data(), u.size() * 4); }
-      return bad;
-    }
-    case 5: {      // folded affines + head block
-      std::vector<float> scale((size_t)L * kC), shift((size_t)L * kC);
-      bn_affine(stem_, scale.data(), shift.data());
-      for (int l = 0; l < 2 * tower_; ++l) bn_affine(tconv_[l], scale.data() + (size_t)(l + 1) * kC, shift.data() + (size_t)(l + 1) * kC);
-      long bad = diff(d_scale_.p, scale.data(), scale.size() * 4) + diff(d_shift_.p, shift.data(), shift.size() * 4);
-      std::vector<float> hp(776, 0.f);
-      for (int c = 0; c < kC; ++c) { hp[c] = vconv_.w[c]; hp[256 + c] = pconv_.w[c]; hp[512 + c] = pconv_.w[kC + c]; }
-      float s[2], t[2];
-      bn_affine(vconv_, s, t);
-      hp[768] = s[0]; hp[769] = t[0];
-      bn_affine(pconv_, s, t);
-      hp[770] = s[0]; hp[771] = t[0]; hp[772] = s[1]; hp[773] = t[1];
-      return bad + diff(d_head_.p, hp.data(), hp.size() * 4);
-    }
-    default: return -1;
   }
+  if (which == 4 && images_[kSplitTower].needed(*this)) {
+    std::vector<float> sc((size_t)L * kC), tmp(kC);
+    for (int l = 0; l <= 2 * tower_; ++l) {
+      bn_affine(l < 2 * tower_ ? tconv_[l] : stem_, sc.data() + (size_t)l * kC, tmp.data());
+      for (int o = 0; o < kC; ++o) sc[(size_t)l * kC + o] *= wino_split_descale();
+    }
+    bad += diff(d_scale_s_.p, sc);
+  }
+  if (which == 5) {
+    std::vector<float> scale((size_t)L * kC), shift((size_t)L * kC);
+    bn_affine(stem_, scale.data(), shift.data());
+    for (int l = 0; l < 2 * tower_; ++l) bn_affine(tconv_[l], scale.data() + (size_t)(l + 1) * kC, shift.data() + (size_t)(l + 1) * kC);
+    bad += diff(d_scale_.p, scale) + diff(d_shift_.p, shift);
+    std::vector<float> hp(776, 0.f);
+    for (int c = 0; c < kC; ++c) { hp[c] = vconv_.w[c]; hp[256 + c] = pconv_.w[c]; hp[512 + c] = pconv_.w[kC + c]; }
+    float s[2], t[2];
+    bn_affine(vconv_, s, t);
+    hp[768] = s[0]; hp[769] = t[0];
+    bn_affine(pconv_, s, t);
+    hp[770] = s[0]; hp[771] = t[0]; hp[772] = s[1]; hp[773] = t[1];
+    bad += diff(d_head_.p, hp);
+  }
+  return bad;
 }
 
 void Net::reserve(int bcap) {
@@ -884,17 +815,17 @@ void Net::check_async_error() {
 void Net::stem(TowerForm form, const float* d_x32, const int* d_count, int bcap) {
   float* a = d_a_.p;
   if (winograd_ == 0 || tower_ == 0) {
-    launch_conv3x3_direct(d_x32, d_wstem_.p, d_scale_.p, d_shift_.p, nullptr, a, d_count, bcap, N_, 1, kCinStemPad, stream_);
+    launch_conv3x3_direct(d_x32, image<float>(kDirectStem), d_scale_.p, d_shift_.p, nullptr, a, d_count, bcap, N_, 1, kCinStemPad, stream_);
   } else if (form == TowerForm::F16 || form == TowerForm::Wino4) {
     float* v = form == TowerForm::F16 ? d_vimg_.p : d_vimg2_.p;
     launch_wino_in(d_x32, v, d_count, bcap, N_, false, stream_, kWinoStemStages);
-    launch_wino_gemm(v, d_ustem_.p, d_scale_.p, d_shift_.p, nullptr, a, nullptr, d_count, bcap, N_, 1, false, stream_,
+    launch_wino_gemm(v, image<float>(kWinoStem), d_scale_.p, d_shift_.p, nullptr, a, nullptr, d_count, bcap, N_, 1, false, stream_,
                      kWinoStemStages);
     if (form == TowerForm::Wino4) launch_wino4_in(a, d_vimg_.p, d_count, bcap, N_, stream_, false);
   } else {
     const bool split = precision_ == 2;
     launch_wino_in(d_x32, d_vimg2_.p, d_count, bcap, N_, split, stream_, kWinoStemStages);
-    launch_wino_gemm(d_vimg2_.p, split ? d_ustem_s_.p : d_ustem_.p, split ? d_scale_s_.p + (size_t)2 * tower_ * kC : d_scale_.p,
+    launch_wino_gemm(d_vimg2_.p, image<float>(split ? kSplitStem : kWinoStem), split ? d_scale_s_.p + (size_t)2 * tower_ * kC : d_scale_.p,
                      d_shift_.p, nullptr, a, d_vimg_.p, d_count, bcap, N_, 1, split, stream_, kWinoStemStages);
     if (!wino_fusable(N_)) launch_wino_in(a, d_vimg_.p, d_count, bcap, N_, split, stream_, kWinoStages, true);
   }
@@ -903,18 +834,17 @@ void Net::stem(TowerForm form, const float* d_x32, const int* d_count, int bcap)
 // relu(BN2(conv2(relu(BN1(conv1(x))))) + x), resnet.jl:26-32, as the direct implicit GEMM (agz_net_set_winograd(0)).  The
 // affine of tower layer l is row l + 1 of d_scale_ / d_shift_ (row 0: the stem's).
 void Net::direct_tower(const int* d_count, int bcap) {
-  const size_t per = (size_t)kC * 9 * kC;
   const float* sc = d_scale_.p + kC;
   const float* sh = d_shift_.p + kC;
   float *a = d_a_.p, *b = d_b_.p, *t = d_t_.p;
   for (int blk = 0; blk < tower_; ++blk) {
     const int l1 = 2 * blk, l2 = 2 * blk + 1;
     timed(1, [&] {
-      launch_conv3x3_direct(a, d_wtower_.p + per * l1, sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, nullptr, t, d_count, bcap,
+      launch_conv3x3_direct(a, image<float>(kDirectTower, l1), sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, nullptr, t, d_count, bcap,
                             N_, 1, kC, stream_);
     });
     timed(1, [&] {
-      launch_conv3x3_direct(t, d_wtower_.p + per * l2, sc + (size_t)l2 * kC, sh + (size_t)l2 * kC, a, b, d_count, bcap, N_, 1,
+      launch_conv3x3_direct(t, image<float>(kDirectTower, l2), sc + (size_t)l2 * kC, sh + (size_t)l2 * kC, a, b, d_count, bcap, N_, 1,
                             kC, stream_);
     });
     std::swap(a, b);
@@ -924,7 +854,6 @@ void Net::direct_tower(const int* d_count, int bcap) {
 // fp16 tower (agz_conv16.hip): half activations between the f32 stem output and the f32 input of the heads (d_b_); the
 // residual of block 0 is the unrounded f32 stem output
 void Net::f16_tower(const int* d_count, int bcap) {
-  const size_t iper = conv16_image_halves();
   const float* sc = d_scale_.p + kC;
   const float* sh = d_shift_.p + kC;
   const float* a = d_a_.p;
@@ -934,11 +863,11 @@ void Net::f16_tower(const int* d_count, int bcap) {
     const int l1 = 2 * blk, l2 = 2 * blk + 1;
     const bool first = blk == 0, last = blk + 1 == tower_;
     timed(1, [&] {
-      launch_conv16_dma(cur, d_wi16_.p + iper * l1, sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, nullptr, 0, d_ht_.p, 0,
+      launch_conv16_dma(cur, image<uint16_t>(kF16Tower, l1), sc + (size_t)l1 * kC, sh + (size_t)l1 * kC, nullptr, 0, d_ht_.p, 0,
                         d_count, bcap, N_, 1, stream_);
     });
     timed(1, [&] {
-      launch_conv16_dma(d_ht_.p, d_wi16_.p + iper * l2, sc + (size_t)l2 * kC, sh + (size_t)l2 * kC,
+      launch_conv16_dma(d_ht_.p, image<uint16_t>(kF16Tower, l2), sc + (size_t)l2 * kC, sh + (size_t)l2 * kC,
                         first ? (const void*)a : (const void*)cur, first ? 1 : 0, last ? (void*)d_b_.p : (void*)nxt,
                         last ? 1 : 0, d_count, bcap, N_, 1, stream_);
     });
@@ -962,15 +891,15 @@ void Net::wino_layer(TowerForm form, int l, const LayerIO& io, const int* d_coun
   const float* sh = d_shift_.p + (size_t)(l + 1) * kC;
   if (form == TowerForm::Wino4) {
     // (a y without residual -- conv1's -- is read by the fix-up transform only: with paired packing it is stored only there)
-    launch_wino4_gemm(io.vin, d_uwino4_.p + wino4_weight_floats() * l, sc, sh, io.res, io.y, io.vout, d_count, bcap, N_, 1, st,
+    launch_wino4_gemm(io.vin, image<float>(kWino4Tower, l), sc, sh, io.res, io.y, io.vout, d_count, bcap, N_, 1, st,
                       part, parts, io.y && !io.res && wino4_paired(N_));
     if (io.vout && !wino4_whole_boards(N_)) launch_wino4_in(io.y, io.vout, d_count, bcap, N_, st, true, part, parts);
   } else if (form == TowerForm::Wino5) {
-    launch_wino5_gemm(io.vin, d_uwino5_.p + wino5_weight_floats() * l, sc, sh, io.res, io.y, io.vout, d_count, bcap, N_, 1, st,
+    launch_wino5_gemm(io.vin, image<float>(kWino5Tower, l), sc, sh, io.res, io.y, io.vout, d_count, bcap, N_, 1, st,
                       part, parts);
   } else {
     const bool split = precision_ == 2;      // (the split form's scales: tower layer l in row l)
-    const float* u = (split ? d_uwino_s_.p : d_uwino_.p) + wino_weight_floats() * l;
+    const float* u = image<float>(split ? kSplitTower : kWinoTower, l);
     launch_wino_gemm(io.vin, u, split ? d_scale_s_.p + (size_t)l * kC : sc, sh, io.res, io.y, io.vout, d_count, bcap, N_, 1, split,
                      st, kWinoStages, part, parts);
     if (io.vout && !wino_fusable(N_)) launch_wino_in(io.y, io.vout, d_count, bcap, N_, split, st, kWinoStages, true);
@@ -1001,14 +930,14 @@ void Net::wino_tower(TowerForm form, const int* d_count, int bcap) {
 // the same layers as wino_tower's (Wino3, whole-board tile blocks), as a table for ONE persistent launch (k_wino_tower)
 void Net::persistent_tower(const int* d_count, int bcap) {
   const bool split = precision_ == 2;
-  const float* usrc = split ? d_uwino_s_.p : d_uwino_.p;
+  const ImageId u = split ? kSplitTower : kWinoTower;
   const float* sc = split ? d_scale_s_.p : d_scale_.p + kC;
   const float* sh = d_shift_.p + kC;
   const int nl = 2 * tower_;
   std::vector<WinoTowerLayer> tab(nl);
   for (int l = 0; l < nl; ++l) {
     const LayerIO io = layer_io(l, false);
-    tab[l] = {io.vin, usrc + wino_weight_floats() * l, sc + (size_t)l * kC, sh + (size_t)l * kC, io.res, io.y, io.vout,
+    tab[l] = {io.vin, image<float>(u, l), sc + (size_t)l * kC, sh + (size_t)l * kC, io.res, io.y, io.vout,
               (io.y ? 1 : 0) | (io.vout ? 2 : 0), 1};
   }
   const size_t tbytes = sizeof(WinoTowerLayer) * tab.size();
@@ -1199,10 +1128,10 @@ void Net::launch_tower_conv_once(const int* d_count, int bcap) {
   AGZ_REQUIRE(tower_ > 0, AGZ_BAD_ARGUMENT, "no tower conv in a tower_height=0 network");
   const TowerForm form = tower_form();
   if (form == TowerForm::F16)
-    launch_conv16_dma(d_ha_.p, d_wi16_.p, d_scale_.p + kC, d_shift_.p + kC, nullptr, 0, d_ht_.p, 0, d_count, bcap, N_, 1,
+    launch_conv16_dma(d_ha_.p, image<uint16_t>(kF16Tower), d_scale_.p + kC, d_shift_.p + kC, nullptr, 0, d_ht_.p, 0, d_count, bcap, N_, 1,
                       stream_);
   else if (form == TowerForm::Direct)
-    launch_conv3x3_direct(d_a_.p, d_wtower_.p, d_scale_.p + kC, d_shift_.p + kC, nullptr, d_t_.p, d_count, bcap, N_, 1, kC,
+    launch_conv3x3_direct(d_a_.p, image<float>(kDirectTower), d_scale_.p + kC, d_shift_.p + kC, nullptr, d_t_.p, d_count, bcap, N_, 1, kC,
                           stream_);
   else      // a steady-state Winograd layer: residual in, y and the next V out (+ the fix-up transform of dense blocks)
     wino_layer(form, 0, {d_vimg_.p, d_a_.p, d_t_.p, d_vimg2_.p}, d_count, bcap, stream_);

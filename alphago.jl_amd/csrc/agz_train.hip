@@ -434,7 +434,7 @@ static inline float train_eps(float eps) { return eps > 1e-5f ? eps : 1e-5f; }
 
 void Trainer::reset() { have_vel_ = false; }
 
-// Flux [3][3][cin][256] <- Wt[cout][tap][cin_pad]: the inverse of the direct image (agz_nn.hip: direct_image_element)
+// Flux [3][3][cin][256] <- Wt[cout][tap][cin_pad]: the inverse of the direct image (agz_nn.hip: DirectImage)
 __global__ __launch_bounds__(256) void k_unpack_direct(const float* __restrict__ wt, int cin, int cin_pad, float* __restrict__ w) {
   const long n = (long)9 * cin * kC;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
@@ -480,7 +480,7 @@ void Trainer::upload() {
   for (int l = 0; l < L; ++l) {
     const int cin = l == 0 ? kCinStem : kC, cinp = l == 0 ? kCinStemPad : kC;
     size(*params_[4 * l + 0], (size_t)kC * 9 * cinp);
-    launch_pack_direct(F + net_.flux_offset(l, AGZ_K_WEIGHT), 0, cin, cinp, 1, params_[4 * l + 0]->theta.p, stream_);
+    kDirectImage.device_pack(F + net_.flux_offset(l, AGZ_K_WEIGHT), 0, cin, 1, params_[4 * l + 0]->theta.p, cinp / 4, stream_);
     put(*params_[4 * l + 1], l, AGZ_K_BIAS);
     put(*params_[4 * l + 2], l, AGZ_K_BN_GAMMA);
     put(*params_[4 * l + 3], l, AGZ_K_BN_BETA);

@@ -30,6 +30,7 @@
 // direct global->LDS DMA (global_load_lds_dwordx4), which is why V and U are stored in HBM as ready-made,
 // bank-swizzled stage images.  64x64 per workgroup gives 16 flop per DMA byte.
 #include "agz_nn.h"
+#include "agz_pack.h"
 #include "agz_glds.h"
 
 #include <algorithm>
@@ -818,26 +819,21 @@ __global__ void k_xcd_census(int* out) {
 
 // ------------------------------------------------------------------ host side
 
-// Flux [kw,kh,cin,cout] column-major -> stage images U[cout block][stage][plane][cout 64][8] with
-// U_xi = G k G^T computed in float64.  k is the CORRELATION kernel: NNlib's conv is a true
-// convolution, so tap (a', b') reading x[i + a' - 1, j + b' - 1] carries w[2 - a', 2 - b'].
-// One (cout, cin) pair = one call of wino_pack_pair: the host loop below (test reference, agz_debug_pack_diff) and the
-// device kernel (the product: weights never leave the GPU between a training step / a broadcast and the next forward)
-// run the same source with FP contraction off, and produce the same bits.
+// Flux [kw,kh,cin,cout] column-major -> stage images U[cout block][stage][plane][cout 64][8] with U_xi = G k G^T
+// (agz_pack.h: winograd_u, and the driver that runs put() on the host and on the device).  One unit = one (cout, cin) pair.
+// The stem's 17 channels fill 5 of its 8 stages' rows: the image is cleared first.
 template <bool SPLIT>
-__host__ __device__ inline void wino_pack_pair(const float* w, int cin, int o, int ci, int ns, float* out) {
-#pragma clang fp contract(off)
-  constexpr double G[5][3] = {{0.5, 0.0, 0.0}, {0.5, 0.5, 0.5}, {1.0 / 6, -1.0 / 6, 1.0 / 6},
-                              {1.0 / 6, 1.0 / 3, 2.0 / 3}, {0.0, 0.0, 1.0}};
-  double k[3][3];
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) k[a][b] = w[(2 - a) + 3 * ((2 - b) + 3 * (ci + (size_t)cin * o))];
-  const int cb = o / WC, ol = o % WC, st = ci / WK, cl = ci % WK;
-  for (int i = 0; i < 5; ++i)
-    for (int j = 0; j < 5; ++j) {
-      double u = 0.0;
-      for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) u += G[i][a] * k[a][b] * G[j][b];
+struct WinoImage : ImageDefaults {
+  using word = float;
+  static constexpr const char* name = SPLIT ? "split F(3x3,3x3)" : "F(3x3,3x3)";
+  static constexpr bool zeroed = true;
+  __host__ __device__ static size_t words(int ns) { return (size_t)(kC / WC) * ns * B_STAGE; }
+  __host__ __device__ static long units(int cin, int) { return (long)kC * cin; }
+  __host__ __device__ static void put(const float* w, int cin, long unit, int ns, float* out) {
+#pragma clang fp contract(off)      // (also keeps the split form's two roundings, double -> float -> half, as written)
+    const int o = (int)(unit / cin), ci = (int)(unit % cin);
+    const int cb = o / WC, ol = o % WC, st = ci / WK, cl = ci % WK;
+    winograd_u<5>(w, cin, o, ci, [&](int i, int j, double u) {
       const int xi = i * 5 + j;
       if (SPLIT) {          // u' = 2^10 u as (hi, lo) halves, rows laid out by wino_v_off (block h = 0: hi, 1: lo)
         _Float16* o16 = reinterpret_cast<_Float16*>(out);
@@ -852,41 +848,12 @@ __host__ __device__ inline void wino_pack_pair(const float* w, int cin, int o, i
         // rounds 1-5 interleaved the two planes of a pair in 32-byte rows rotated by the row: 0.2 of the LDS cycles in conflicts)
         out[((size_t)cb * ns + st) * B_STAGE + wino_v_off(xi, ol, cl >> 1) + (cl & 1)] = (float)u;
       }
-    }
-}
-
-void wino_pack_weights(const ConvHost& c, float* out, int ns) {
-  std::memset(out, 0, sizeof(float) * wino_weight_floats(ns));
-  for (int o = 0; o < c.cout; ++o)
-    for (int ci = 0; ci < c.cin; ++ci) wino_pack_pair<false>(c.w.data(), c.cin, o, ci, ns, out);
-}
-void wino_pack_weights_split(const ConvHost& c, float* out, int ns) {
-  std::memset(out, 0, sizeof(float) * wino_weight_floats(ns));
-  for (int o = 0; o < c.cout; ++o)
-    for (int ci = 0; ci < c.cin; ++ci) wino_pack_pair<true>(c.w.data(), c.cin, o, ci, ns, out);
-}
-
-// the same images from Flux-layout weights that are already on the device (Net's master copy): `layers` consecutive
-// [3][3][cin][256] tensors, `wstride` floats apart, into `layers` images.  One thread per (layer, cout, cin).
-template <bool SPLIT>
-__global__ __launch_bounds__(256) void k_wino_pack(const float* __restrict__ w, long wstride, int cin, int layers, int ns,
-                                                   float* __restrict__ out, long per) {
-  const long n = (long)layers * kC * cin;
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long)gridDim.x * 256) {
-    const int ci = (int)(t % cin), o = (int)((t / cin) % kC), l = (int)(t / ((long)cin * kC));
-    wino_pack_pair<SPLIT>(w + l * wstride, cin, o, ci, ns, out + l * per);
+    });
   }
-}
-void launch_wino_pack(const float* d_w, long wstride, int cin, int layers, float* d_out, int ns, bool split, hipStream_t s) {
-  const long per = (long)wino_weight_floats(ns);
-  AGZ_HIP(hipMemsetAsync(d_out, 0, sizeof(float) * (size_t)per * layers, s));      // (the stem's 17 channels fill 5 of 8 stages' rows)
-  const int grid = (int)std::min<long>(((long)layers * kC * cin + 255) / 256, 65536);
-  if (split) hipLaunchKernelGGL(k_wino_pack<true>, dim3(grid), dim3(256), 0, s, d_w, wstride, cin, layers, ns, d_out, per);
-  else hipLaunchKernelGGL(k_wino_pack<false>, dim3(grid), dim3(256), 0, s, d_w, wstride, cin, layers, ns, d_out, per);
-}
+};
+const ImageFamily kWinoImage = image_family<WinoImage<false>>(), kWinoSplitImage = image_family<WinoImage<true>>();
 float wino_split_descale() { return 1.f / (kSplitV * kSplitU); }
 
-size_t wino_weight_floats(int ns) { return (size_t)(kC / WC) * ns * B_STAGE; }
 long wino_blocks(int bcap, int T) {
   const long rpb = wino_rows_per_block(T);
   return ((long)bcap * T * T + rpb - 1) / rpb;

@@ -42,6 +42,7 @@
 // stores) for every tile whose patch lies in this tile block (whole-board blocks for N = 13..16: 16 tiles per board, 4
 // boards per block; five boards per block pair above, where k_wino4_in<FIXUP> does the ends of the one board a pair cuts).
 #include "agz_nn.h"
+#include "agz_pack.h"
 #include "agz_glds.h"
 
 #include <cmath>
@@ -627,52 +628,29 @@ __global__ __launch_bounds__(256, 1) void k_wino4_gemm(
 
 // ------------------------------------------------------------------ host side
 
-// Flux [kw,kh,cin,cout] column-major -> U stage images [cout block 4][stage 96][unit 24][row 64][4], U = G k G^T in
-// float64.  k is the CORRELATION kernel (NNlib's conv is a true convolution: tap (a', b') carries w[2 - a', 2 - b']).
-// One (cout, cin) pair per call, same source on the host (test reference) and in the device kernel (the product).
-__host__ __device__ inline void wino4_pack_pair(const float* w, int o, int ci, float* out) {
-#pragma clang fp contract(off)
-  constexpr double G[6][3] = {{0.25, 0.0, 0.0},         {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                              {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
-  double k[3][3];
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) k[a][b] = w[(2 - a) + 3 * ((2 - b) + 3 * (ci + (size_t)kC * o))];
-  int r = 0;                                          // the U row that holds this cout: the inverse of w4_cout_of_urow
-  for (int q = 0; q < W4C; ++q)
-    if (w4_cout_of_urow(q) == o % W4C) r = q;
-  const int cb = o / W4C, cg = ci / 4, cl = ci % 4;
-  for (int i = 0; i < 6; ++i)
-    for (int j = 0; j < 6; ++j) {
-      double u = 0.0;
-      for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) u += G[i][a] * k[a][b] * G[j][b];
-      int stage, unit;
-      w4_slot(i, j, cg, stage, unit);
-      out[(size_t)cb * W4BLOCK + (size_t)stage * W4HALF + (size_t)unit * W4UNIT + w4_off(r, cl >> 1) + (cl & 1)] = (float)u;
-    }
-}
-void wino4_pack_weights(const ConvHost& c, float* out) {
-  AGZ_REQUIRE(c.cin == kC && c.cout == kC, AGZ_BAD_ARGUMENT, "F(4x4,3x3) pack: tower layers only (%d -> %d)", c.cin, c.cout);
-  std::memset(out, 0, sizeof(float) * wino4_weight_floats());
-  for (int o = 0; o < kC; ++o)
-    for (int ci = 0; ci < kC; ++ci) wino4_pack_pair(c.w.data(), o, ci, out);
-}
-__global__ __launch_bounds__(256) void k_wino4_pack(const float* __restrict__ w, long wstride, int layers, float* __restrict__ out,
-                                                    long per) {
-  const long n = (long)layers * kC * kC;
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long)gridDim.x * 256) {
-    const int ci = (int)(t % kC), o = (int)((t / kC) % kC), l = (int)(t / ((long)kC * kC));
-    wino4_pack_pair(w + l * wstride, o, ci, out + l * per);
+// Flux [kw,kh,cin,cout] column-major -> U stage images [cout block 4][stage 96][unit 24][row 64][4], U = G k G^T (agz_pack.h).
+// One unit = one (cout, cin) pair; every word of an image is written.
+struct Wino4Image : ImageDefaults {
+  using word = float;
+  static constexpr const char* name = "F(4x4,3x3)";
+  static constexpr bool tower_only = true;
+  __host__ __device__ static size_t words(int) { return (size_t)(kC / W4C) * W4BLOCK; }
+  __host__ __device__ static long units(int, int) { return (long)kC * kC; }
+  __host__ __device__ static void put(const float* w, int, long unit, int, float* out) {
+    const int o = (int)(unit / kC), ci = (int)(unit % kC);
+    int r = 0;                                          // the U row that holds this cout: the inverse of w4_cout_of_urow
+    for (int q = 0; q < W4C; ++q)
+      if (w4_cout_of_urow(q) == o % W4C) r = q;
+    const int cb = o / W4C, cg = ci / 4, cl = ci % 4;
+    winograd_u<6>(w, kC, o, ci, [&](int i, int j, double u) {
+      int stage, unit4;
+      w4_slot(i, j, cg, stage, unit4);
+      out[(size_t)cb * W4BLOCK + (size_t)stage * W4HALF + (size_t)unit4 * W4UNIT + w4_off(r, cl >> 1) + (cl & 1)] = (float)u;
+    });
   }
-}
-// `layers` consecutive Flux-layout tower tensors on the device (wstride floats apart) -> `layers` U images
-void launch_wino4_pack(const float* d_w, long wstride, int layers, float* d_out, hipStream_t s) {
-  const long per = (long)wino4_weight_floats();
-  const int grid = (int)std::min<long>(((long)layers * kC * kC + 255) / 256, 65536);
-  hipLaunchKernelGGL(k_wino4_pack, dim3(grid), dim3(256), 0, s, d_w, wstride, layers, d_out, per);     // (every word of an image is written)
-}
+};
+const ImageFamily kWino4Image = image_family<Wino4Image>();
 
-size_t wino4_weight_floats() { return (size_t)(kC / W4C) * W4BLOCK; }
 static long wino4_blocks(int bcap, int T) {
   if (w4_paired(T)) {      // five boards per block pair; the last pair's second block exists only if it has a tile
     const long pairs = bcap / 5, rest = (long)(bcap % 5) * 25;
@@ -729,17 +707,10 @@ void launch_wino4_gemm(const float* vimg, const float* uimg, const float* scale,
   // kernel's last argument
   AGZ_REQUIRE(!ypart || (w4_paired(T) && y && !res && tb1 < (1 << 30)), AGZ_BAD_ARGUMENT, "F(4x4,3x3) GEMM: partial y needs paired packing and no residual");
   const int tb1y = tb1 | (ypart ? 1 << 30 : 0);
-#define W4_LAUNCH(MODE_) hipLaunchKernelGGL((k_wino4_gemm<MODE_>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1y)
-  const int mode = (y ? 1 : 0) | (vnext ? 2 : 0) | (res ? 4 : 0);
-  switch (mode) {
-    case 1: W4_LAUNCH(1); break;
-    case 2: W4_LAUNCH(2); break;
-    case 3: W4_LAUNCH(3); break;
-    case 5: W4_LAUNCH(5); break;
-    case 6: W4_LAUNCH(6); break;
-    default: W4_LAUNCH(7); break;
-  }
-#undef W4_LAUNCH
+  dispatch_mode(y, vnext, res, [&](auto mode) {
+    hipLaunchKernelGGL((k_wino4_gemm<decltype(mode)::value>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T,
+                       relu, tb0, tb1y);
+  });
 }
 
 }  // namespace agz

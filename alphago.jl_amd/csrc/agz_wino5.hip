@@ -25,6 +25,7 @@
 // input transform for the half's 16 stages (the last two are k_wino_gemm4's phases 1b / 2, operation for operation: bt5p
 // is THE arithmetic of B^T d B, so a tile's V does not depend on which kernel emitted it).
 #include "agz_nn.h"
+#include "agz_pack.h"
 #include "agz_glds.h"
 
 #include <algorithm>
@@ -544,47 +545,26 @@ __global__ __launch_bounds__(256, 1) void k_wino5_gemm(
 
 // ------------------------------------------------------------------ host side
 
-// Flux [kw,kh,cin,cout] column-major -> U images [cout block 2][pass 5][super-stage 32][unit 10][row 128][4], U = G k G^T in
-// float64 (agz_wino.hip's G; k is the CORRELATION kernel: NNlib's conv is a true convolution).  One (cout, cin) pair per
-// call, the same source on the host (test reference, agz_debug_pack_diff) and in the device kernel (the product).
-__host__ __device__ inline void wino5_pack_pair(const float* w, int o, int ci, float* out) {
-#pragma clang fp contract(off)
-  constexpr double G[5][3] = {{0.5, 0.0, 0.0}, {0.5, 0.5, 0.5}, {1.0 / 6, -1.0 / 6, 1.0 / 6},
-                              {1.0 / 6, 1.0 / 3, 2.0 / 3}, {0.0, 0.0, 1.0}};
-  double k[3][3];
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) k[a][b] = w[(2 - a) + 3 * ((2 - b) + 3 * (ci + (size_t)kC * o))];
-  const int cb = o / W5C, r = o % W5C, c4 = ci / 4, cl = ci % 4;
-  const int ss = c4 / W5G, cg = c4 % W5G;
-  for (int i = 0; i < 5; ++i)
-    for (int j = 0; j < 5; ++j) {
-      double u = 0.0;
-      for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) u += G[i][a] * k[a][b] * G[j][b];
+// Flux [kw,kh,cin,cout] column-major -> U images [cout block 2][pass 5][super-stage 32][unit 10][row 128][4], U = G k G^T
+// with agz_wino.hip's G (agz_pack.h).  One unit = one (cout, cin) pair; every word of an image is written.
+struct Wino5Image : ImageDefaults {
+  using word = float;
+  static constexpr const char* name = "five-pass F(3x3,3x3)";
+  static constexpr bool tower_only = true;
+  __host__ __device__ static size_t words(int) { return (size_t)(kC / W5C) * W5UBLOCK; }
+  __host__ __device__ static long units(int, int) { return (long)kC * kC; }
+  __host__ __device__ static void put(const float* w, int, long unit, int, float* out) {
+    const int o = (int)(unit / kC), ci = (int)(unit % kC);
+    const int cb = o / W5C, r = o % W5C, c4 = ci / 4, cl = ci % 4;
+    const int ss = c4 / W5G, cg = c4 % W5G;
+    winograd_u<5>(w, kC, o, ci, [&](int i, int j, double u) {
       out[(size_t)cb * W5UBLOCK + (size_t)(i * W5SSP + ss) * W5SU + (size_t)(cg * 5 + j) * W5UU + w5_off(r, cl >> 1) + (cl & 1)] = (float)u;
-    }
-}
-void wino5_pack_weights(const ConvHost& c, float* out) {
-  AGZ_REQUIRE(c.cin == kC && c.cout == kC, AGZ_BAD_ARGUMENT, "five-pass F(3x3,3x3) pack: tower layers only (%d -> %d)", c.cin, c.cout);
-  for (int o = 0; o < kC; ++o)
-    for (int ci = 0; ci < kC; ++ci) wino5_pack_pair(c.w.data(), o, ci, out);
-}
-__global__ __launch_bounds__(256) void k_wino5_pack(const float* __restrict__ w, long wstride, int layers, float* __restrict__ out,
-                                                    long per) {
-  const long n = (long)layers * kC * kC;
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long)gridDim.x * 256) {
-    const int ci = (int)(t % kC), o = (int)((t / kC) % kC), l = (int)(t / ((long)kC * kC));
-    wino5_pack_pair(w + l * wstride, o, ci, out + l * per);
+    });
   }
-}
-void launch_wino5_pack(const float* d_w, long wstride, int layers, float* d_out, hipStream_t s) {
-  const long per = (long)wino5_weight_floats();
-  const int grid = (int)std::min<long>(((long)layers * kC * kC + 255) / 256, 65536);
-  hipLaunchKernelGGL(k_wino5_pack, dim3(grid), dim3(256), 0, s, d_w, wstride, layers, d_out, per);     // (every word of an image is written)
-}
-size_t wino5_weight_floats() { return (size_t)(kC / W5C) * W5UBLOCK; }
+};
+const ImageFamily kWino5Image = image_family<Wino5Image>();
 
-// the arguments of launch_wino_gemm (agz_wino.hip) for a tower layer in exact f32; uimg: launch_wino5_pack's image
+// the arguments of launch_wino_gemm (agz_wino.hip) for a tower layer in exact f32; uimg: the kWino5Image of the layer
 void launch_wino5_gemm(const float* vimg, const float* uimg, const float* scale, const float* shift, const float* res,
                        float* y, float* vnext, const int* d_count, int bcap, int N, int relu, hipStream_t s, int part, int parts) {
   const int T = (N + 2) / 3;
@@ -597,11 +577,14 @@ void launch_wino5_gemm(const float* vimg, const float* uimg, const float* scale,
   const int blocks = tb1 - tb0;
   const dim3 grid(8 * 2 * ((blocks + 7) / 8)), block(256);
   wino_check_32bit(all_blocks, W5T, bcap, N);
-#define W5_LAUNCH(MODE_) hipLaunchKernelGGL((k_wino5_gemm<MODE_>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T, relu, tb0, tb1)
+  auto launch = [&](auto mode) {
+    hipLaunchKernelGGL((k_wino5_gemm<decltype(mode)::value>), grid, block, 0, s, vimg, uimg, scale, shift, res, y, vnext, d_count, N, T,
+                       relu, tb0, tb1);
+  };
 #ifdef AGZ_TIMING_EXPERIMENTS
   static int traced = 0;
   if (getenv("AGZ_WINO5_TRACE") && y && vnext && res && ++traced == 3) {      // third steady-state conv2-form launch
-    W5_LAUNCH(7);
+    launch(std::integral_constant<int, 7>{});
     (void)hipStreamSynchronize(s);
     static unsigned long long host[4096][24];
     (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(w5_trace), sizeof(host));
@@ -612,16 +595,7 @@ void launch_wino5_gemm(const float* vimg, const float* uimg, const float* scale,
     return;
   }
 #endif
-  const int mode = (y ? 1 : 0) | (vnext ? 2 : 0) | (res ? 4 : 0);
-  switch (mode) {
-    case 1: W5_LAUNCH(1); break;
-    case 2: W5_LAUNCH(2); break;
-    case 3: W5_LAUNCH(3); break;
-    case 5: W5_LAUNCH(5); break;
-    case 6: W5_LAUNCH(6); break;
-    default: W5_LAUNCH(7); break;
-  }
-#undef W5_LAUNCH
+  dispatch_mode(y, vnext, res, launch);
 }
 
 }  // namespace agz

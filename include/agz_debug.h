@@ -52,7 +52,8 @@ agz_status agz_debug_mfma_sustained_data(agz_engine* e, int32_t millis, int32_t 
  * This hook rebuilds image family `which` on the HOST from the host copies (the round-1..4 pack code, kept as the
  * reference) and counts the 32-bit words in which the device image differs: 0 = direct Wt, 1 = F(3x3,3x3) U (+ stem),
  * 2 = F(4x4,3x3) U, 3 = fp16 images (precision f16 selected), 4 = split-operand U + scales (precision f32s selected),
- * 5 = folded BatchNorm affines + head block.  -1 for an unknown family. */
+ * 5 = folded BatchNorm affines + head block, 6 = five-pass F(3x3,3x3) U (agz_net_set_winograd(3), N <= 12).  -1 for an
+ * unknown family, 0 for one that the current settings do not read. */
 agz_status agz_debug_pack_diff(agz_engine* e, int32_t which, int64_t* mismatches_out);
 
 #ifdef __cplusplus

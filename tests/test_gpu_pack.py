@@ -10,7 +10,7 @@ import alphago_jl_amd as ag
 from test_gpu_train import batch
 
 pytestmark = pytest.mark.gpu
-FAMILIES = {0: "direct Wt", 1: "F(3x3,3x3) U", 2: "F(4x4,3x3) U", 3: "fp16 images", 4: "split U + scales", 5: "affines + heads"}
+FAMILIES = {0: "direct Wt", 1: "F(3x3,3x3) U", 2: "F(4x4,3x3) U", 3: "fp16 images", 4: "split U + scales", 5: "affines + heads"}      # (6, the five-pass U, needs its own mode: below)
 
 
 def randomize(eng, tower, seed):
@@ -31,6 +31,9 @@ def all_families_identical(eng):
         for which, name in FAMILIES.items():
             assert eng.debug_pack_diff(which) == 0, f"{name} differs from the host pack ({precision})"
     eng.set_precision("f32")
+    eng.set_winograd(3)          # family 6: the five-pass U, built where that form is selected (N <= 12)
+    assert eng.debug_pack_diff(6) == 0, "five-pass F(3x3,3x3) U differs from the host pack"
+    eng.set_winograd(1)
     assert eng.debug_pack_diff(99) == -1
 
 
@@ -92,6 +95,49 @@ def test_set_weights_writes_through_to_the_device_master():
     p2, _ = eng.forward_features(feats)
     assert p2.tobytes() == p0.tobytes()
     eng.close()
+
+
+# (board size, select the mode, deselect it): every optional image family, and the direct tower as the base case.  F(4x4,3x3)
+# is the default at 13x13, so selecting it on the fresh engine B changes nothing, and the direct tower reads base images: in
+# those two legs B only shows that copied parameters reach the images; what they add is steps 4-5 (stale image, reselected).
+MODES = {
+    "f16": (9, lambda e: e.set_precision("f16"), lambda e: e.set_precision("f32")),
+    "f32s": (9, lambda e: e.set_precision("f32s"), lambda e: e.set_precision("f32")),
+    "five-pass": (9, lambda e: e.set_winograd(3), lambda e: e.set_winograd(1)),
+    "F(4x4,3x3)": (13, lambda e: e.set_winograd(1), lambda e: e.set_winograd(2)),
+    "direct": (9, lambda e: e.set_winograd(0), lambda e: e.set_winograd(1)),
+}
+
+
+@pytest.mark.parametrize("mode", list(MODES))
+def test_optional_images_follow_the_master(mode):
+    """An optional image is built on the first forward that selects its mode and again after every change of the master
+    while selected -- and an image that was built, then left unselected across a change of the master, is rebuilt when its
+    mode is selected again (it must not be taken for current).  Bit for bit throughout."""
+    N, select, deselect = MODES[mode]
+    kw = dict(board_size=N, games=1, tower_height=1, num_readouts=8, max_nodes_per_game=16)
+    feats = np.random.RandomState(1).randint(0, 2, (3, 17 * N * N)).astype(np.float32)
+    a = ag.Engine(**kw)
+    a.init_synthetic(4)
+    select(a)
+    p0, v0 = a.forward_features(feats)
+    w = a.get_weights(2, 0)
+    a.set_weights(2, 0, (w * 1.5).astype(np.float32))
+    p1, v1 = a.forward_features(feats)
+    assert np.abs(p1 - p0).max() > 0
+    b = ag.Engine(**kw)                  # the mode first, the parameters after
+    select(b)
+    a.copy_weights_to(b)
+    p2, v2 = b.forward_features(feats)
+    assert p2.tobytes() == p1.tobytes() and v2.tobytes() == v1.tobytes()
+    deselect(a)
+    a.set_weights(2, 0, w)               # the master changes while the image is not in use
+    a.forward_features(feats)
+    select(a)
+    p3, v3 = a.forward_features(feats)
+    assert p3.tobytes() == p0.tobytes() and v3.tobytes() == v0.tobytes()
+    a.close()
+    b.close()
 
 
 def test_mfma_sustained_microbenchmarks_run_and_are_ordered_as_the_hardware_says():

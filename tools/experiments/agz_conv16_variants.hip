@@ -26,6 +26,7 @@
 // AGZ_C16_DEBUG / _RB / _PACE (results WRONG: parts of the loop compiled out), and -DAGZ_C16_WL=true (weights through a
 // wave-private LDS ring, round 4).
 #include "agz_nn.h"
+#include "agz_pack.h"
 
 #include <hip/hip_fp16.h>
 
@@ -43,7 +44,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int HK = 32;             // channels per chunk
 constexpr int HCH = kC / HK;       // 8 chunks
 
-static size_t conv16_weight_halves() { return (size_t)HCH * 9 * kC * HK; }
+__host__ __device__ static size_t conv16_weight_halves() { return (size_t)HCH * 9 * kC * HK; }
 
 // tap reads x[row + da, col + db] with da = tap % 3 - 1, db = tap / 3 - 1 and multiplies Flux's w[a = 1 - da, b = 1 - db]
 // (NNlib true convolution), as in pack_conv3 (agz_nn.hip)
@@ -96,8 +97,6 @@ constexpr int W2_RB_PRODUCT = 7;                    // row blocks per tile of th
 constexpr int W2_KS = HCH * 18;                     // k-steps per tile
 constexpr int W2_RR = 2;                            // epilogue passes of residual in flight (f32 residual: 1)
 
-size_t conv16_image_halves() { return conv16_weight_halves(); }
-
 // Wf[k-step 144][cout block 8][lane 64][8 halves]: the A operand of D = W . X^T in register order.  Element `idx` of the
 // image straight from the Flux tensor (same source for the host reference and the device kernel).
 __host__ __device__ inline uint16_t conv16_image_element(const float* w, size_t idx) {
@@ -108,23 +107,16 @@ __host__ __device__ inline uint16_t conv16_image_element(const float* w, size_t 
   const _Float16 h = (_Float16)w[a + 3 * (b + 3 * (ci + (size_t)kC * o))];          // round to nearest even, as __float2half_rn
   return *reinterpret_cast<const uint16_t*>(&h);
 }
-void conv16_pack_images(const ConvHost& c, uint16_t* out) {
-  const size_t n = conv16_weight_halves();
-  for (size_t i = 0; i < n; ++i) out[i] = conv16_image_element(c.w.data(), i);
-}
-__global__ __launch_bounds__(256) void k_conv16_pack(const float* __restrict__ w, long wstride, int layers, uint16_t* __restrict__ out,
-                                                     long per) {
-  const long n = (long)layers * per;
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long)gridDim.x * 256) {
-    const long l = t / per;
-    out[t] = conv16_image_element(w + l * wstride, (size_t)(t - l * per));
-  }
-}
-void launch_conv16_pack(const float* d_w, long wstride, int layers, uint16_t* d_out, hipStream_t s) {
-  const long per = (long)conv16_weight_halves();
-  const int grid = (int)std::min<long>((layers * per + 255) / 256, 65536);
-  hipLaunchKernelGGL(k_conv16_pack, dim3(grid), dim3(256), 0, s, d_w, wstride, layers, d_out, per);
-}
+// (the product's pack driver, agz_pack.h, over this frozen file's own pair / element function and layout)
+struct Conv16Image : ImageDefaults {
+  using word = uint16_t;
+  static constexpr const char* name = "fp16";
+  static constexpr bool tower_only = true;
+  __host__ __device__ static size_t words(int) { return conv16_weight_halves(); }
+  __host__ __device__ static long units(int, int) { return (long)words(0); }
+  __host__ __device__ static void put(const float* w, int, long idx, int, uint16_t* out) { out[idx] = conv16_image_element(w, (size_t)idx); }
+};
+const ImageFamily kConv16Image = image_family<Conv16Image>();
 
 #ifdef AGZ_TIMING_EXPERIMENTS
 // pacing experiment: bit i set = the waves sleep 64 clocks in k-step i of every channel chunk (AGZ_C16_PACE, 18 bits)

@@ -42,6 +42,7 @@
 // stores) for every tile whose patch lies in this tile block (whole-board blocks for N = 13..16: 16 tiles per board, 4
 // boards per block; five boards per block pair above, where k_wino4_in<FIXUP> does the ends of the one board a pair cuts).
 #include "agz_nn.h"
+#include "agz_pack.h"
 #include "agz_glds.h"
 
 #include <cmath>
@@ -701,28 +702,19 @@ __host__ __device__ inline void wino4_pack_pair(const float* w, int o, int ci, f
       out[(size_t)cb * W4BLOCK + (size_t)stage * W4HALF + (size_t)unit * W4UNIT + w4_off(r, cl >> 1) + (cl & 1)] = (float)u;
     }
 }
-void wino4_pack_weights(const ConvHost& c, float* out) {
-  AGZ_REQUIRE(c.cin == kC && c.cout == kC, AGZ_BAD_ARGUMENT, "F(4x4,3x3) pack: tower layers only (%d -> %d)", c.cin, c.cout);
-  std::memset(out, 0, sizeof(float) * wino4_weight_floats());
-  for (int o = 0; o < kC; ++o)
-    for (int ci = 0; ci < kC; ++ci) wino4_pack_pair(c.w.data(), o, ci, out);
-}
-__global__ __launch_bounds__(256) void k_wino4_pack(const float* __restrict__ w, long wstride, int layers, float* __restrict__ out,
-                                                    long per) {
-  const long n = (long)layers * kC * kC;
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long)gridDim.x * 256) {
-    const int ci = (int)(t % kC), o = (int)((t / kC) % kC), l = (int)(t / ((long)kC * kC));
-    wino4_pack_pair(w + l * wstride, o, ci, out + l * per);
+// (the product's pack driver, agz_pack.h, over this frozen file's own pair / element function and layout)
+struct Wino4Image : ImageDefaults {
+  using word = float;
+  static constexpr const char* name = "F(4x4,3x3)";
+  static constexpr bool tower_only = true;      // (every word of an image is written)
+  __host__ __device__ static size_t words(int) { return (size_t)(kC / W4C) * W4BLOCK; }
+  __host__ __device__ static long units(int, int) { return (long)kC * kC; }
+  __host__ __device__ static void put(const float* w, int, long unit, int, float* out) {
+    wino4_pack_pair(w, (int)(unit / kC), (int)(unit % kC), out);
   }
-}
-// `layers` consecutive Flux-layout tower tensors on the device (wstride floats apart) -> `layers` U images
-void launch_wino4_pack(const float* d_w, long wstride, int layers, float* d_out, hipStream_t s) {
-  const long per = (long)wino4_weight_floats();
-  const int grid = (int)std::min<long>(((long)layers * kC * kC + 255) / 256, 65536);
-  hipLaunchKernelGGL(k_wino4_pack, dim3(grid), dim3(256), 0, s, d_w, wstride, layers, d_out, per);     // (every word of an image is written)
-}
+};
+const ImageFamily kWino4Image = image_family<Wino4Image>();
 
-size_t wino4_weight_floats() { return (size_t)(kC / W4C) * W4BLOCK; }
 static long wino4_blocks(int bcap, int T) {
   if (w4_paired(T)) {      // five boards per block pair; the last pair's second block exists only if it has a tile
     const long pairs = bcap / 5, rest = (long)(bcap % 5) * 25;

@@ -34,6 +34,7 @@
 // direct global->LDS DMA (global_load_lds_dwordx4), which is why V and U are stored in HBM as ready-made,
 // bank-swizzled stage images.  64x64 per workgroup gives 16 flop per DMA byte.
 #include "agz_nn.h"
+#include "agz_pack.h"
 #include "agz_glds.h"
 
 #include <algorithm>
@@ -980,38 +981,21 @@ __host__ __device__ inline void wino_pack_pair(const float* w, int cin, int o, i
     }
 }
 
-void wino_pack_weights(const ConvHost& c, float* out, int ns) {
-  std::memset(out, 0, sizeof(float) * wino_weight_floats(ns));
-  for (int o = 0; o < c.cout; ++o)
-    for (int ci = 0; ci < c.cin; ++ci) wino_pack_pair<false>(c.w.data(), c.cin, o, ci, ns, out);
-}
-void wino_pack_weights_split(const ConvHost& c, float* out, int ns) {
-  std::memset(out, 0, sizeof(float) * wino_weight_floats(ns));
-  for (int o = 0; o < c.cout; ++o)
-    for (int ci = 0; ci < c.cin; ++ci) wino_pack_pair<true>(c.w.data(), c.cin, o, ci, ns, out);
-}
-
-// the same images from Flux-layout weights that are already on the device (Net's master copy): `layers` consecutive
-// [3][3][cin][256] tensors, `wstride` floats apart, into `layers` images.  One thread per (layer, cout, cin).
+// (the product's pack driver, agz_pack.h, over this frozen file's own pair / element function and layout)
 template <bool SPLIT>
-__global__ __launch_bounds__(256) void k_wino_pack(const float* __restrict__ w, long wstride, int cin, int layers, int ns,
-                                                   float* __restrict__ out, long per) {
-  const long n = (long)layers * kC * cin;
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < n; t += (long)gridDim.x * 256) {
-    const int ci = (int)(t % cin), o = (int)((t / cin) % kC), l = (int)(t / ((long)cin * kC));
-    wino_pack_pair<SPLIT>(w + l * wstride, cin, o, ci, ns, out + l * per);
+struct WinoImage : ImageDefaults {
+  using word = float;
+  static constexpr const char* name = SPLIT ? "split F(3x3,3x3)" : "F(3x3,3x3)";
+  static constexpr bool zeroed = true;      // (the stem's 17 channels fill 5 of 8 stages' rows)
+  __host__ __device__ static size_t words(int ns) { return (size_t)(kC / WC) * ns * B_STAGE; }
+  __host__ __device__ static long units(int cin, int) { return (long)kC * cin; }
+  __host__ __device__ static void put(const float* w, int cin, long unit, int ns, float* out) {
+    wino_pack_pair<SPLIT>(w, cin, (int)(unit / cin), (int)(unit % cin), ns, out);
   }
-}
-void launch_wino_pack(const float* d_w, long wstride, int cin, int layers, float* d_out, int ns, bool split, hipStream_t s) {
-  const long per = (long)wino_weight_floats(ns);
-  AGZ_HIP(hipMemsetAsync(d_out, 0, sizeof(float) * (size_t)per * layers, s));      // (the stem's 17 channels fill 5 of 8 stages' rows)
-  const int grid = (int)std::min<long>(((long)layers * kC * cin + 255) / 256, 65536);
-  if (split) hipLaunchKernelGGL(k_wino_pack<true>, dim3(grid), dim3(256), 0, s, d_w, wstride, cin, layers, ns, d_out, per);
-  else hipLaunchKernelGGL(k_wino_pack<false>, dim3(grid), dim3(256), 0, s, d_w, wstride, cin, layers, ns, d_out, per);
-}
+};
+const ImageFamily kWinoImage = image_family<WinoImage<false>>(), kWinoSplitImage = image_family<WinoImage<true>>();
 float wino_split_descale() { return 1.f / (kSplitV * kSplitU); }
 
-size_t wino_weight_floats(int ns) { return (size_t)(kC / WC) * ns * B_STAGE; }
 long wino_blocks(int bcap, int T) {
   const long rpb = wino_rows_per_block(T);
   return ((long)bcap * T * T + rpb - 1) / rpb;
