@@ -155,6 +155,9 @@ def load():
         "agz_selfplay_set_playout_cap": (i32, [E, i32, C.c_double]),
         "agz_selfplay_playout_cap_counts": (i32, [E, P(i64)]),
         "agz_replay_set_targets_only": (i32, [E, i32]),
+        "agz_replay_set_value_target": (i32, [E, C.c_double, C.c_double]),
+        "agz_records_value_targets": (i32, [E, i64, C.c_double, C.c_double, f32p]),
+        "agz_value_targets": (i32, [f32p, i32, i32, C.c_double, C.c_double, f32p]),
         "agz_selfplay_set_forced_playouts": (i32, [E, C.c_double, i32]),
         "agz_selfplay_forced_counts": (i32, [E, P(i64)]),
         "agz_tree_pruned_pi": (i32, [E, i32, i32, C.c_double, f32p]),

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import IllegalMove
-from .engine import Engine
+from .engine import Engine, value_targets
 
 BLACK, WHITE, EMPTY = 1, -1, 0
 _KGS = "ABCDEFGHJKLMNOPQRST"
@@ -566,14 +566,14 @@ class MCTSPlayer:
         self.result = winner
         self.result_string = ("B+R" if winner == BLACK else "W+R") if was_resign else self.root.position.result_string()
 
-    def extract_data(self):                   # mcts_play.jl:126-139
+    def extract_data(self, value_target=None):                   # mcts_play.jl:126-139
         assert len(self.searches_pi) == self.root._info.pos.n, "GoPosition history is incomplete"
         pos = Position(self.env, komi=self._start.komi)
         positions = []
         for c in self._moves:
             positions.append(pos)
             pos = pos.play_move(c)
-        return positions, [p.copy() for p in self.searches_pi], [self.result] * len(positions)
+        return positions, [p.copy() for p in self.searches_pi], _results(self, len(positions), value_target)
 
 
 # A bare finished-game tuple (what records look like before they are wrapped; tests and the replay buffer build them by
@@ -652,12 +652,24 @@ class SelfPlayPlayer:
     def is_done(self):                         # mcts_play.jl:120
         return True
 
-    def extract_data(self, targets_only=False):                    # mcts_play.jl:126-139
+    def extract_data(self, targets_only=False, value_target=None):                    # mcts_play.jl:126-139
         start_n = 0 if self.start is None else self.start.n
         assert len(self.searches_pi) == self.root.position.n - start_n, "GoPosition history is incomplete"
         before, _ = self._replay()
         keep = [k for k in range(len(before)) if self.full_search[k] or not targets_only]
-        return [before[k] for k in keep], [self.searches_pi[k].copy() for k in keep], [self.result] * len(keep)
+        results = _results(self, len(before), value_target)       # over every ply: a target sums the fast plies behind it
+        return [before[k] for k in keep], [self.searches_pi[k].copy() for k in keep], [results[k] for k in keep]
+
+
+def _results(player, n, value_target):
+    """the results list of extract_data: the constant fill of mcts_play.jl:138, or with value_target = (alpha, lam) the
+    per-ply value targets of the player's qs and result (value_targets, include/agz_value_target.h) as float32"""
+    if value_target is None:
+        return [player.result] * n
+    alpha, lam = value_target
+    y = value_targets(np.asarray(player.qs, np.float32), player.result, alpha, lam)
+    assert len(y) == n, "one recorded q per position"
+    return list(y)
 
 
 # The reference draws from Julia's global RNG (selfplay.jl:9, mcts.jl:133,235, mcts_play.jl:61,66): successive selfplay
@@ -1012,13 +1024,17 @@ def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, se
     return ok
 
 
-def extract_data(player, record=None, targets_only=False):
+def extract_data(player, record=None, targets_only=False, value_target=None):
     """extract_data(player) -> (positions, pis, results), mcts_play.jl:126-139: one argument, the player selfplay()
     returned or a live MCTSPlayer (train.jl:58).  The round <= 5 form extract_data(env, record) for a bare GameRecord
     is still accepted.  targets_only=True (ours, for selfplay(..., playout_cap=...) players) drops the plies of fast
-    searches -- the all-zero pi rows -- from all three lists; the default keeps every ply, zero rows included."""
+    searches -- the all-zero pi rows -- from all three lists; the default keeps every ply, zero rows included.
+    value_target=(alpha, lam) (ours): `results` is the per-ply vector of value targets y_t (float32) -- the result blended
+    with the TD(lam) return of the player's recorded qs from that ply on (Engine.replay_set_value_target; a kept ply sums
+    the qs of the dropped plies behind it) -- instead of the constant fill; None: the result, as the reference."""
     if record is None:
-        return player.extract_data(targets_only=True) if targets_only else player.extract_data()
+        kw = {} if value_target is None else dict(value_target=value_target)
+        return player.extract_data(targets_only=True, **kw) if targets_only else player.extract_data(**kw)
     env, pos, positions = player, Position(player), []
     for c in record.moves:
         positions.append(pos)
@@ -1087,7 +1103,7 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
           tower_height=19, model=None, start_training_after=50000, slots=None, seed=0, game_id_base=0, symmetry=None,
           augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, starts=None,
           playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
-          gumbel_c_scale=1.0, **cfg):
+          gumbel_c_scale=1.0, value_target=None, **cfg):
     """train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model,
     start_training_after) (src/train.jl:38-92) with `slots` games in flight on the device.  One engine
     plays, keeps the replay arena and trains; per step: agz_selfplay_step(1), one read of how many games finished, and
@@ -1106,7 +1122,9 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
     playout_cap ((r, p): playout cap randomization as in selfplay, with a targets-only arena -- memory_size and
     start_training_after then count target entries, the plies of full searches, and only those are sampled),
     forced_playouts (k) and prune_targets (forced playouts and policy target pruning in the full searches, as in selfplay),
-    gumbel (m), gumbel_c_visit and gumbel_c_scale (the Gumbel root search in the full searches, as in selfplay).
+    gumbel (m), gumbel_c_visit and gumbel_c_scale (the Gumbel root search in the full searches, as in selfplay),
+    value_target ((alpha, lam): the z of every training batch is (1 - alpha) * result + alpha * TD(lam) of the game's
+    recorded root values from the sampled ply on, Engine.replay_set_value_target; None: the result, as the reference).
     Returns the trained NeuralNet (model itself when given)."""
     import time
     import torch
@@ -1137,6 +1155,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
         cuts = _minibatch_cuts(batch_size)
         _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit,
                               gumbel_c_scale, targets_only_arena=True)
+        if value_target is not None:
+            eng.replay_set_value_target(*value_target)
         eng.set_hold(True)
         eng.start(num_games)
         eng.release()

@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/agz_value_target.h"
 #include "agz_engine.h"
 #include "agz_search.h"
 
@@ -248,6 +249,18 @@ agz_status agz_slot_abandon(agz_engine* e, int32_t slot) {
 agz_status agz_records_features(agz_engine* e, int64_t k, float* out) {
   return guard(e, [&](agz::Engine& E) { E.record_features(k, out); });
 }
+agz_status agz_records_value_targets(agz_engine* e, int64_t k, double alpha, double lambda, float* out) {
+  return guard(e, [&](agz::Engine& E) { E.record_value_targets(k, alpha, lambda, out); });
+}
+// engine-free: the host loop over agz_value_target for a record the caller holds
+agz_status agz_value_targets(const float* qs, int32_t T, int32_t result, double alpha, double lambda, float* out) {
+  if (T < 0 || (T > 0 && (!qs || !out)) || !agz_value_target_params_ok(alpha, lambda)) {
+    g_create_error = "value targets: T >= 0 entries of qs and out, alpha and lambda both 0..1";
+    return AGZ_BAD_ARGUMENT;
+  }
+  for (int32_t t = 0; t < T; ++t) out[t] = agz_value_target(qs, T, t, result, alpha, lambda);
+  return AGZ_OK;
+}
 agz_status agz_replay_ingest_packed(agz_engine* e, const void* packed, int64_t nbytes, int32_t is_device,
                                     int64_t* added_out) {
   return guard(e, [&](agz::Engine& E) {
@@ -349,6 +362,9 @@ agz_status agz_tree_gumbel_pi(agz_engine* e, int32_t g, int32_t node, double c_v
 }
 agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on) {
   return guard(e, [&](agz::Engine& E) { E.replay_set_targets_only(on != 0); });
+}
+agz_status agz_replay_set_value_target(agz_engine* e, double alpha, double lambda) {
+  return guard(e, [&](agz::Engine& E) { E.replay_set_value_target(alpha, lambda); });
 }
 agz_status agz_device_alloc(agz_engine* e, int64_t bytes, void** out) {
   return guard(e, [&](agz::Engine& E) {

@@ -75,6 +75,8 @@ class Engine {
   int64_t records_exchanged() const { return rec_sent_; }
   void records_mark_exchanged(int64_t upto) { rec_sent_ = upto; }
   void record_features(int64_t k, float* out);
+  // the value targets y_t of ring record k under (alpha, lambda) (agz_records_value_targets, include/agz_value_target.h)
+  void record_value_targets(int64_t k, double alpha, double lambda, float* out);
 
   // device replay arena: finished games of every rank, packed, resident in HBM
   int64_t replay_ingest(const void* packed, int64_t nbytes, bool is_device);
@@ -99,6 +101,8 @@ class Engine {
   }
   // targets-only arena (agz_replay_set_targets_only): an entry is a ply whose pi row is not all zero
   void replay_set_targets_only(bool on);
+  // the z of the batch calls is y_t under (alpha, lambda) (agz_replay_set_value_target); alpha = 0 (the default) is off
+  void replay_set_value_target(double alpha, double lambda);
   // get_replay_batch without the host: B distinct live entries drawn on the device (agz_replay_sample)
   void replay_sample(int B, uint64_t call, int sym_mode, float* feats, float* pi, float* z, int64_t* game_out,
                      int32_t* ply_out);
@@ -273,6 +277,7 @@ class Engine {
   DevBuf<int16_t> d_rp_tply_;
   DevBuf<int64_t> tgt_idx_;         // replay_scan_targets: offsets and position prefix of the games just filed
   DevBuf<int32_t> tgt_cnt_;         // ... and their target counts
+  double vt_alpha_ = 0.0, vt_lambda_ = 1.0;   // agz_replay_set_value_target; alpha = 0: off, z stays the result
   DevBuf<int64_t> smp_off_, smp_game_;
   DevBuf<int32_t> smp_ply_, smp_sym_;
   DevBuf<int8_t> smp_boards_;

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "../../include/agz_value_target.h"
 #include "agz_search.h"
 
 namespace agz {
@@ -502,6 +503,21 @@ __global__ __launch_bounds__(kWave) void k_replay_arena_batch(View V, const uint
               record_start(V, h.game_id));
   if (pi_out) w.for_each(A, [&](int i) { pi_out[(long)b * A + i] = pi[i]; });
   if (z_out && w.leader()) z_out[b] = (float)h.result;
+}
+
+// agz_replay_set_value_target with alpha > 0: z of sample b = y_ply[b] of its record (include/agz_value_target.h), written
+// over the result k_replay_arena_batch left there.  One lane per sample walks the record's qs from its last ply down to
+// the sampled one: at most max_game_length dependent f64 steps.
+__global__ __launch_bounds__(kWave) void k_replay_value_targets(const uint8_t* arena, const int64_t* rec_off,
+                                                                 const int32_t* ply, int B, int A, double alpha,
+                                                                 double lambda, float* z_out) {
+  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (b >= B) return;
+  const uint8_t* r = arena + rec_off[b];
+  const agz_game_header h = *reinterpret_cast<const agz_game_header*>(r);
+  const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * (size_t)h.num_moves + 3) & ~(size_t)3;
+  const float* qs = reinterpret_cast<const float*>(r + o_pi) + (size_t)h.num_moves * A;
+  z_out[b] = agz_value_target(qs, h.num_moves, ply[b], h.result, alpha, lambda);
 }
 
 // agz_replay_set_targets_only, the index: one wave per newly filed game scans its pi rows; a ply whose row is not all
@@ -1346,6 +1362,19 @@ void Engine::record_game(int64_t k, int16_t* moves, float* pis, float* qs) {
   wait();
 }
 
+void Engine::record_value_targets(int64_t k, double alpha, double lambda, float* out) {
+  AGZ_REQUIRE(agz_value_target_params_ok(alpha, lambda), AGZ_BAD_ARGUMENT, "value target: alpha %g, lambda %g: both 0..1",
+              alpha, lambda);
+  agz_game_header h;
+  record_header(k, &h);
+  const size_t nm = (size_t)h.num_moves;
+  if (nm == 0) return;
+  std::vector<float> qs(nm);
+  down(qs.data(), V_.fin_q + k * (size_t)V_.max_game_length, nm);
+  wait();
+  for (size_t t = 0; t < nm; ++t) out[t] = agz_value_target(qs.data(), h.num_moves, (int32_t)t, h.result, alpha, lambda);
+}
+
 // the packed form of records [first, last) (last < 0: records_count()): off[k] = where record first + k begins, one
 // entry per record; returns the bytes of all of them.  The headers come over stream_ and are waited for.  (The size
 // call used to fetch them with a blocking hipMemcpy on the null stream, which stream_ -- hipStreamNonBlocking -- does not
@@ -1643,6 +1672,15 @@ void Engine::replay_set_targets_only(bool on) {
   rp_first_ply_ = 0;
 }
 
+// The value target of the batch calls (agz_replay_set_value_target).  A host-side pair read at the next batch call: the
+// arena and its index do not depend on it, so it may change at any time, and agz_replay_clear leaves it alone.
+void Engine::replay_set_value_target(double alpha, double lambda) {
+  AGZ_REQUIRE(agz_value_target_params_ok(alpha, lambda), AGZ_BAD_ARGUMENT, "value target: alpha %g, lambda %g: both 0..1",
+              alpha, lambda);
+  vt_alpha_ = alpha;
+  vt_lambda_ = lambda;
+}
+
 // games [first_new, count) have just been filed: k_replay_targets writes their target lists, the host extends the
 // target prefix by their counts
 void Engine::replay_scan_targets(size_t first_new) {
@@ -1735,6 +1773,9 @@ void Engine::emit_replay_batch(int B, const int64_t* off, const int32_t* ply, co
     hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)f, feats, sym, V_.N, 17, 0, 0);
     if (pi) hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)p, pi, sym, V_.N, 1, 1, 0);
   }
+  if (z && vt_alpha_ > 0.0)         // agz_replay_set_value_target: z becomes y (a symmetry does not touch it)
+    hipLaunchKernelGGL(k_replay_value_targets, dim3((unsigned)((B + kWave - 1) / kWave)), dim3(kWave), 0, stream_,
+                       (const uint8_t*)rp_buf_.p, off, ply, B, V_.A, vt_alpha_, vt_lambda_, z);
   AGZ_HIP(hipGetLastError());
 }
 

@@ -23,7 +23,7 @@ using Random
 export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, train, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
-       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, set_starts!, set_playout_cap!, playout_cap_counts, set_forced_playouts!, forced_counts, pruned_pi, set_gumbel!, gumbel_counts, gumbel_pi, extract_targets, node_lines, most_visited_path, mvp_gg,
+       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, set_starts!, set_playout_cap!, playout_cap_counts, set_forced_playouts!, forced_counts, pruned_pi, set_gumbel!, gumbel_counts, gumbel_pi, extract_targets, value_targets, extract_value_targets, node_lines, most_visited_path, mvp_gg,
        # the node-level surface test/test_mcts.jl:2-5 and test/test_mcts_player.jl:3-6 import
        MCTSNode, select_leaf, maybe_add_child!, add_virtual_loss!, revert_virtual_loss!,
        incorporate_results!, inject_noise!, child_action_score, child_Q, child_U, child_N, child_W,
@@ -793,6 +793,38 @@ function replay_set_targets_only!(e::Engine, on::Bool = true)
   check(e, ccall((:agz_replay_set_targets_only, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, on ? 1 : 0))
 end
 
+# Search-value targets (ours; include/agz.h agz_replay_set_value_target, include/agz_value_target.h): the z of the arena's
+# batch calls becomes y_t = (1 - alpha) * result + alpha * G_t, G_t the TD(lam) return of the record's qs from ply t on
+# (backward Horner in Float64, every product and sum rounded on its own).  alpha = 0 (the default) is off.
+function replay_set_value_target!(e::Engine, alpha::Real = 0.0, lam::Real = 1.0)
+  check(e, ccall((:agz_replay_set_value_target, libagz), Int32, (Ptr{Cvoid}, Float64, Float64), e.handle, alpha, lam))
+end
+# y [num_moves] of ring record k (0-based, agz_records_game's numbering)
+function records_value_targets(e::Engine, k::Integer, alpha::Real, lam::Real)
+  h = Ref{AgzGameHeader}()
+  check(e, ccall((:agz_records_header, libagz), Int32, (Ptr{Cvoid}, Int64, Ref{AgzGameHeader}), e.handle, k, h))
+  out = zeros(Float32, max(Int(h[].num_moves), 1))
+  check(e, ccall((:agz_records_value_targets, libagz), Int32, (Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float32}),
+                 e.handle, k, alpha, lam, out))
+  out[1:h[].num_moves]
+end
+# the same for a record held on the host (no engine): qs the recorded root values, result the outcome
+function value_targets(qs::Vector{Float32}, result::Integer, alpha::Real, lam::Real)
+  out = zeros(Float32, length(qs))
+  st = ccall((:agz_value_targets, libagz), Int32, (Ptr{Float32}, Int32, Int32, Float64, Float64, Ptr{Float32}),
+             qs, length(qs), result, alpha, lam, out)
+  st == 0 || throw(ArgumentError("value targets: alpha $alpha and lam $lam must both lie in 0..1"))
+  out
+end
+# extract_data with the per-ply value targets as `results` instead of the constant fill; value_target = (alpha, lam).
+# (extract_data itself keeps the reference's one-argument form, as extract_targets does for the playout cap.)
+function extract_value_targets(p::Union{MCTSPlayer, SelfPlayPlayer}, value_target; targets_only::Bool = false)
+  positions, pis, _ = extract_data(p)
+  y = value_targets(Vector{Float32}(p.qs), p.result, value_target[1], value_target[2])
+  keep = (targets_only && p isa SelfPlayPlayer) ? findall(p.full_search) : collect(1:length(positions))
+  positions[keep], pis[keep], y[keep]        # a kept ply sums the qs of the dropped plies behind it
+end
+
 # Forced playouts and policy target pruning (ours; include/agz.h agz_selfplay_set_forced_playouts): in a full self-play
 # search a visited root child a with N_a^2 < k P_a sum(N) is selected ahead of the PUCT arg-max; with prune the recorded π
 # row leaves out the forced visits the search did not agree with.  k = 0 switches both off; KataGo plays k = 2.
@@ -1273,7 +1305,7 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
                augment::Bool = false, callback::Function = println,
                starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing,
                forced_playouts = nothing, prune_targets::Bool = true,
-               gumbel = nothing, gumbel_c_visit::Real = 50.0, gumbel_c_scale::Real = 1.0)
+               gumbel = nothing, gumbel_c_visit::Real = 50.0, gumbel_c_scale::Real = 1.0, value_target = nothing)
   (gumbel !== nothing && gumbel != 0 && forced_playouts !== nothing && forced_playouts != 0) &&
     throw(ArgumentError("gumbel and forced_playouts are two rules for the same decision: ask for one"))
   cur_nn = model === nothing ? NeuralNet(env; tower_height = tower_height) : model                       # train.jl:43
@@ -1297,6 +1329,7 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
   end
   forced_playouts === nothing || set_forced_playouts!(e, forced_playouts, prune_targets)   # k, as in selfplay
   gumbel === nothing || set_gumbel!(e, gumbel, gumbel_c_visit, gumbel_c_scale)             # m, as in selfplay
+  value_target === nothing || replay_set_value_target!(e, value_target[1], value_target[2])   # (alpha, lam): z of the batches
   check(e, ccall((:agz_selfplay_set_hold, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 1))
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, num_games))
   check(e, ccall((:agz_selfplay_release, libagz), Int32, (Ptr{Cvoid},), e.handle))

@@ -298,6 +298,13 @@ agz_status agz_records_game(agz_engine* e, int64_t k, int16_t* moves, float* pis
 agz_status agz_records_packed_size(agz_engine* e, int64_t* nbytes_out);
 agz_status agz_records_export_packed(agz_engine* e, void* dst, int64_t capacity, int32_t is_device);
 agz_status agz_records_clear(agz_engine* e);
+/* the value targets y_0 .. y_{num_moves-1} of ring record k under (alpha, lambda) (agz_replay_set_value_target states
+ * the rule): out float[num_moves].  Numbering and refusals of agz_records_game; AGZ_BAD_ARGUMENT also for alpha or
+ * lambda outside [0, 1] or NaN.  alpha = 0: every entry is (float)result. */
+agz_status agz_records_value_targets(agz_engine* e, int64_t k, double alpha, double lambda, float* out);
+/* the same for a record the caller holds (no engine, no device): qs float[T], out float[T]; the host loop over
+ * agz_value_target of include/agz_value_target.h that the Python and Julia mirrors call */
+agz_status agz_value_targets(const float* qs, int32_t T, int32_t result, double alpha, double lambda, float* out);
 /* arena_mode with external_network: after agz_selfplay_select, counts_out[0] leaves belong to Black
  * players (network 0) and counts_out[1] to White players (network 1); agz_selfplay_leaf_features
  * and agz_selfplay_incorporate order the rows [Black players' | White players'].  A finished
@@ -390,6 +397,22 @@ agz_status agz_replay_sample(agz_engine* e, int32_t B, uint64_t call, int32_t sy
  * agz_replay_clear empties the arena and leaves the mode as it is.  Off (the default): every call is what it is without
  * this one. */
 agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on);
+/* Search-value targets (include/agz_value_target.h holds the arithmetic): the z of agz_replay_batch,
+ * agz_replay_batch_sym and agz_replay_sample becomes the outcome blended with the TD(lambda) return of the root values
+ * the search recorded.  For a record of T = num_moves plies with q_k = qs[k] (Black-absolute, as result is) and
+ * z = (double)result, the sample at ply t gets, all in double with every multiply and add rounded on its own:
+ *     acc = z;  for k = T-1 down to t:  acc = ((1.0 - lambda) * (double)q_k) + (lambda * acc);      G_t = acc
+ *     y_t = (float)(((1.0 - alpha) * z) + (alpha * G_t))
+ * lambda = 0: G_t = q_t; lambda = 1: G_t = z; alpha = 1, lambda = 0: y_t = q_t bit for bit (returned as it stands: the
+ * arithmetic would turn a q_t of -0.0 into +0.0).  alpha = 0 (the default)
+ * is OFF: z = (float)result by the code that runs without this call, and no further kernel is launched.  With
+ * alpha > 0 one small kernel (one lane per sample) follows the batch kernel on the engine's stream and overwrites z;
+ * feats, pi, game_out, ply_out and the draw are untouched, a symmetry does not touch y, and y stays Black-absolute.
+ * In a targets-only arena a sampled target ply sums the q of the fast plies behind it; with a window that starts inside
+ * a game the sum reads later plies of the same record only.  The pair is kept on the host and read at the next batch
+ * call: it may be set at any time, and agz_replay_clear leaves it as it is.  AGZ_BAD_ARGUMENT, with the setting in
+ * force kept, when alpha or lambda is a NaN or outside [0, 1]. */
+agz_status agz_replay_set_value_target(agz_engine* e, double alpha, double lambda);
 /* device memory on the engine's GPU for a host without its own allocator (the Julia stub's train): agz_replay_sample's
  * outputs, agz_train_step's device inputs.  Freed by agz_device_free (after the engine's stream has used it). */
 agz_status agz_device_alloc(agz_engine* e, int64_t bytes, void** out);
