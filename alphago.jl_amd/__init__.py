@@ -8,7 +8,7 @@ from . import _lib
 from ._lib import AgzError, IllegalMove, load
 from .engine import Engine, comm_unique_id, value_targets
 from .api import (BLACK, EMPTY, WHITE, Analysis, AnalysisLines, Line, GameRecord, GoEnv, LeafPosition, MCTSPlayer, Momentum, NeuralNet, PlayerMove,
-                  Position, SelfPlayPlayer, _train, analyze, evaluate, extract_data, get_replay_batch, seed, from_flat, from_kgs, from_sgf, get_feats, load_model, position_arrays, review, review_arrays, save_model, selfplay, to_flat, train,
+                  Position, SelfPlayPlayer, _train, analyze, evaluate, extract_data, get_replay_batch, seed, from_flat, from_kgs, from_sgf, get_feats, load_model, position_arrays, reanalyze, review, review_arrays, save_model, selfplay, to_flat, train,
                   to_kgs, to_sgf)
 from . import bson_weights
 from . import distributed
@@ -18,4 +18,4 @@ __all__ = ["Engine", "comm_unique_id", "value_targets", "AgzError", "IllegalMove
            "MCTSPlayer", "selfplay", "extract_data", "GameRecord", "SelfPlayPlayer", "LeafPosition", "get_replay_batch",
            "Momentum", "_train", "seed", "get_feats", "to_flat", "from_flat",
            "from_kgs", "to_kgs", "from_sgf", "to_sgf", "BLACK", "WHITE", "EMPTY", "load_model", "save_model", "evaluate",
-           "bson_weights", "ReplayBuffer", "analyze", "Analysis", "AnalysisLines", "Line", "position_arrays", "review", "review_arrays", "train"]
+           "bson_weights", "ReplayBuffer", "analyze", "Analysis", "AnalysisLines", "Line", "position_arrays", "review", "review_arrays", "reanalyze", "train"]

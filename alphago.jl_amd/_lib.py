@@ -166,6 +166,8 @@ def load():
         "agz_tree_gumbel_pi": (i32, [E, i32, i32, C.c_double, C.c_double, f32p]),
         "agz_analyze_start": (i32, [E, i8p, P(PositionInfo), i8p, i64, u64]),
         "agz_review_start": (i32, [E, P(C.c_int16), P(i64), i8p, P(PositionInfo), i8p, i64, u64]),
+        "agz_replay_reanalyze_start": (i32, [E, i64, i64, u64]),
+        "agz_replay_reanalyze_commit": (i32, [E, P(i64)]),
         "agz_analyze_progress": (i32, [E, P(i64)]),
         "agz_analyze_results": (i32, [E, P(Analysis), f32p, f32p, f32p]),
         "agz_analyze_set_lines": (i32, [E, i32, i32, i32]),

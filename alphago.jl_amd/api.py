@@ -952,27 +952,54 @@ def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, 
         if lines:
             eng.analyze_set_lines(lines, pv_depth, pv_min_visits)
         eng.review_start(moves, off, boards, infos, hist, game_id_base)
-        total = int(off[-1])
-        while eng.review_progress() < total:
-            eng.step(16)
-            if eng.stats()["stalled_games"]:      # pool_policy = AGZ_POOL_STALL: a slot waits on its full pool
-                raise _lib.AgzError(_lib.POOL_EXHAUSTED, "a search is waiting on a full node pool (pool_policy = "
-                                                         "stall): raise max_nodes_per_game or use the default policy")
-        r = eng.review_results()
-        t = eng.analyze_lines() if lines else None
+        return _review_rows(env, eng, off, [int(game_id_base) + j for j in range(G)], lines)
     finally:
         eng.close()
+
+
+def _review_rows(env, eng, off, game_ids, lines):
+    """The loop behind review() and reanalyze(): step the review run on `eng` until its off[-1] rows are finished, then
+    read them as one list of Analysis (AnalysisLines with lines on) per game: game j's rows off[j] .. off[j + 1] - 1."""
+    total = int(off[-1])
+    while eng.review_progress() < total:
+        eng.step(16)
+        if eng.stats()["stalled_games"]:      # pool_policy = AGZ_POOL_STALL: a slot waits on its full pool
+            raise _lib.AgzError(_lib.POOL_EXHAUSTED, "a search is waiting on a full node pool (pool_policy = "
+                                                     "stall): raise max_nodes_per_game or use the default policy")
+    r = eng.review_results()
+    t = eng.analyze_lines() if lines else None
     out = []
-    for j in range(G):
+    for j, gid in enumerate(game_ids):
         rows = []
         for i in range(int(off[j]), int(off[j + 1])):
             cn, cw = r["child_N"][i], r["child_W"][i]
             a = Analysis(None if r["move"][i] < 0 else from_flat(int(r["move"][i]), env), r["N"][i], r["W"][i],
                          r["Q"][i], cn, cw, cw / (np.float32(1) + cn), r["prior"][i], int(r["status"][i]),
-                         int(r["nodes_used"][i]), int(game_id_base) + j)
+                         int(r["nodes_used"][i]), gid)
             rows.append(AnalysisLines(*a, _line_rows(env, {f: v[i] for f, v in t.items()})) if lines else a)
         out.append(rows)
     return out
+
+
+def reanalyze(engine, first=0, count=None, game_id_base=0, commit=True, lines=0, pv_depth=0, pv_min_visits=1):
+    """Reanalyse (ours; MuZero's): search games first .. first + count - 1 of `engine`'s replay arena
+    again on its current network and write the new targets over the records.  The search is review()'s, on the engine's
+    own num_readouts, network and pool, with the games gathered on the device: game j from its entry of the start table,
+    draw-stream game id game_id_base + its record's game_id, so the rows of a game depend neither on its place in the
+    arena nor on the range.  commit: every row with status OK writes qs[k] = Q and -- unless the record's row is all
+    zero, which means "no policy target" and stays so -- its pi row children_as_pi(root, n <= tau_threshold); short,
+    invalid and given-up rows leave the record alone.  Moves, results, the arena's order and its window stay.  The run
+    takes over the engine's slots: self-play games in flight are dropped.  lines > 0: AnalysisLines rows, as in review()
+    (pv_depth 0: review()'s default of 16); the call leaves the engine's analyze_set_lines setting at these values.
+    Returns (counts, rows): counts = dict(committed, pi_rows, skipped) in rows (None with commit=False), rows = one list
+    of Analysis per game as review() gives them."""
+    pv_depth = pv_depth or 16
+    _check_lines(lines, pv_depth, pv_min_visits)
+    engine.analyze_set_lines(lines, pv_depth, pv_min_visits)
+    engine.reanalyze_start(first, count, game_id_base)
+    ids = [int(game_id_base) + int(g) for g in engine.reanalyze_game_ids()]
+    rows = _review_rows(GoEnv(engine.N), engine, engine.reanalyze_offsets(), ids, lines)
+    return (engine.reanalyze_commit() if commit else None), rows
 
 
 EvalStats = namedtuple("EvalStats", "games_won num_games win_rate resigned moves records")

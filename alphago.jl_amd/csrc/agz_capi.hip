@@ -401,6 +401,12 @@ agz_status agz_review_start(agz_engine* e, const int16_t* moves, const int64_t* 
                             const agz_position_info* info, const int8_t* history, int64_t G, uint64_t game_id_base) {
   return guard(e, [&](agz::Engine& E) { E.review_start(moves, game_offset, boards, info, history, G, game_id_base); });
 }
+agz_status agz_replay_reanalyze_start(agz_engine* e, int64_t first, int64_t count, uint64_t game_id_base) {
+  return guard(e, [&](agz::Engine& E) { E.replay_reanalyze_start(first, count, game_id_base); });
+}
+agz_status agz_replay_reanalyze_commit(agz_engine* e, int64_t counts_out[3]) {
+  return guard(e, [&](agz::Engine& E) { E.replay_reanalyze_commit(counts_out); });
+}
 agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out) {
   return guard(e, [&](agz::Engine& E) {
     const int64_t d = E.analyze_progress();

@@ -40,6 +40,10 @@ class Engine {
   // batched game review (agz_review_start): play() over G recorded games on reused trees, rows read as in analysis
   void review_start(const int16_t* moves, const int64_t* game_offset, const int8_t* boards, const agz_position_info* info,
                     const int8_t* history, int64_t G, uint64_t game_id_base);
+  // reanalysis (agz_replay_reanalyze_start / _commit): a review run over arena games [first, first + count) gathered on
+  // the device, then its finished rows written over the records' pi and q targets
+  void replay_reanalyze_start(int64_t first, int64_t count, uint64_t game_id_base);
+  void replay_reanalyze_commit(int64_t counts_out[3]);
   // start positions of self-play / arena games and of everything that replays their records (agz_selfplay_set_starts)
   void set_starts(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t S);
   int64_t starts_count() const { return V_.st_count; }
@@ -174,6 +178,7 @@ class Engine {
   void replay_reserve(size_t bytes);
   void replay_drop_front(size_t drop);
   void replay_scan_targets(size_t first_new);
+  void replay_index_to_device();
   // the prefix the window and the sampler count entries by: every ply, or target plies only
   const std::vector<int64_t>& rp_entry_cum() const { return rp_targets_only_ ? rp_tcum_ : rp_cum_; }
   void upload_view_outputs();
@@ -256,7 +261,16 @@ class Engine {
                              const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B);
   void upload_positions(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,
                         int64_t rows);
+  void clear_result_tables(int64_t rows);
   void begin_analysis_run(int64_t B, int64_t rows, uint64_t game_id_base);
+  // reanalysis: the run in force (begin_analysis_run ends it), its first arena game and the arena's change counter at
+  // its start; the per-game draw ids and the pi rows of the run (View::an_gid / an_pi); the commit's three counts
+  bool ra_on_ = false, ra_committed_ = false;
+  int64_t ra_first_ = 0;
+  uint64_t ra_stamp_ = 0;
+  DevBuf<uint64_t> an_gid_;
+  DevBuf<float> an_pi_;
+  DevBuf<unsigned long long> ra_counts_;
   // replay arena
   DevBuf<uint8_t> rp_buf_, s_pack_;
   size_t rp_used_ = 0;
@@ -268,6 +282,7 @@ class Engine {
   int64_t rp_first_ply_ = 0;        // rp_first_game_ are dead
   DevBuf<int64_t> d_rp_cum_, d_rp_off_;   // device copies of rp_cum_ / rp_off_ for the sampler
   int64_t rp_dev_n_ = 0;            // games whose rp_cum_ / rp_off_ entries are on the device
+  uint64_t rp_change_ = 0;          // bumped by every ingest, trim, clear, window and targets-only call (reanalysis commit)
   // targets-only mode: rp_tcum_[k] = target plies of the games before game k (next to rp_cum_; the window's
   // rp_first_ply_ is then an index into rp_first_game_'s target list); d_rp_tply_[rp_cum_[k] + i] = the i-th target ply
   // of game k, written by k_replay_targets at ingest

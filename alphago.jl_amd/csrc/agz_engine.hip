@@ -545,6 +545,69 @@ __global__ __launch_bounds__(kWave) void k_replay_targets(const uint8_t* arena, 
   if (w.leader()) count[g] = n;
 }
 
+// ---- reanalysis (agz_replay_reanalyze_start / _commit): a review run whose games are arena records
+
+// the gather in front of the search: one wave per game j = arena game first + j (rec_off is the arena's offset table from
+// `first` on).  Its moves go record to review table in coalesced int16 copies, its start is the table entry every
+// kernel that rebuilds a record begins at (record_start; none: the empty board with agz_config.komi), and its draw-stream
+// game id is id_base + header.game_id
+__global__ __launch_bounds__(kWave) void k_reanalyze_gather(View V, const uint8_t* arena, const int64_t* rec_off,
+                                                             const int64_t* rv_off, uint64_t id_base, int16_t* rv_moves,
+                                                             int8_t* an_board, int8_t* an_hist,
+                                                             agz_position_info* an_info, uint64_t* an_gid) {
+  HipWave w;
+  const long j = blockIdx.x;
+  const int P = V.P;
+  const uint8_t* r = arena + rec_off[j];
+  const agz_game_header h = *reinterpret_cast<const agz_game_header*>(r);
+  const int16_t* mv = reinterpret_cast<const int16_t*>(r + sizeof(agz_game_header));
+  int16_t* out = rv_moves + rv_off[j];
+  w.for_each(h.num_moves, [&](int i) { out[i] = mv[i]; });
+  const long s = record_start(V, h.game_id);
+  w.for_each(P, [&](int p) { an_board[j * P + p] = s >= 0 ? V.st_board[s * P + p] : (int8_t)0; });
+  w.for_each(7 * P, [&](int i) { an_hist[j * 7 * P + i] = s >= 0 ? V.st_hist[s * 7 * P + i] : (int8_t)0; });
+  if (w.leader()) {
+    an_info[j] = s >= 0 ? V.st_info[s] : empty_position_info(V.komi);
+    an_gid[j] = id_base + h.game_id;
+  }
+}
+
+// the commit behind it: one wave per result row = (game j, ply k) of the run, j found in the row prefix rv_off.  A row
+// whose search finished in full (status AGZ_OK) writes qs[k] = Q, and its pi row over the record's unless that one is all
+// zero -- "no policy target" (k_replay_targets) stays that, so the targets-only index, the window and the sampler's entry
+// numbering hold.  Every other row leaves the record alone.  counts = {rows committed, pi rows overwritten, rows skipped}
+__global__ __launch_bounds__(kWave) void k_replay_refresh(uint8_t* arena, const int64_t* rec_off, const int64_t* rv_off,
+                                                           int64_t G, int A, const agz_analysis* res, const float* an_pi,
+                                                           unsigned long long* counts) {
+  HipWave w;
+  const int64_t row = blockIdx.x;
+  int64_t lo = 0, hi = G;                                         // rv_off[lo] <= row < rv_off[hi]
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (rv_off[mid] <= row) lo = mid; else hi = mid;
+  }
+  const agz_analysis a = res[row];
+  if (a.status != AGZ_OK) {
+    if (w.leader()) atomicAdd(&counts[2], 1ull);
+    return;
+  }
+  const size_t k = (size_t)(row - rv_off[lo]);
+  uint8_t* r = arena + rec_off[lo];
+  const agz_game_header h = *reinterpret_cast<const agz_game_header*>(r);
+  const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * (size_t)h.num_moves + 3) & ~(size_t)3;
+  float* pi = reinterpret_cast<float*>(r + o_pi) + k * A;
+  float* qs = reinterpret_cast<float*>(r + o_pi) + (size_t)h.num_moves * A;
+  bool nz = false;
+  w.for_each(A, [&](int i) { nz = nz || pi[i] != 0.f; });
+  const bool target = w.any(nz);
+  if (target) w.for_each(A, [&](int i) { pi[i] = an_pi[row * A + i]; });
+  if (w.leader()) {
+    qs[k] = a.Q;
+    atomicAdd(&counts[0], 1ull);
+    if (target) atomicAdd(&counts[1], 1ull);
+  }
+}
+
 // agz_selfplay_release: every slot parked in G_IDLE may claim its next game at the next k_pre
 __global__ void k_release(View V) {
   const int g = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -731,6 +794,7 @@ void Engine::net_select(int which) {
 void Engine::start(int64_t total_games) {
   V_.analysis = 0;              // back to self-play (the analysis tables stay readable through analyze_results)
   V_.review = 0;
+  ra_on_ = false;
   V_.total_games = total_games;
   rec_sent_ = 0;
   abandoned_ = 0;
@@ -1001,8 +1065,12 @@ void Engine::upload_position_table(DevBuf<int8_t>& board, DevBuf<int8_t>& hist, 
 // B positions into the an_* tables, result tables of `rows` rows cleared (the stream is idle)
 void Engine::upload_positions(const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,
                               int64_t rows) {
-  const size_t R = (size_t)(rows > 0 ? rows : 1), A = (size_t)V_.A;
   upload_position_table(an_board_, an_hist_, an_info_, boards, info, history, B);
+  clear_result_tables(rows);
+}
+
+void Engine::clear_result_tables(int64_t rows) {
+  const size_t R = (size_t)(rows > 0 ? rows : 1), A = (size_t)V_.A;
   an_res_.ensure(R);
   an_rows_.ensure(3 * R * A);
   AGZ_HIP(hipMemsetAsync(an_res_.p, 0, sizeof(agz_analysis) * R, stream_));
@@ -1027,6 +1095,9 @@ void Engine::begin_analysis_run(int64_t B, int64_t rows, uint64_t game_id_base) 
   V_.an_childN = an_rows_.p;
   V_.an_childW = an_rows_.p + R * A;
   V_.an_prior = an_rows_.p + 2 * R * A;
+  V_.an_gid = nullptr;           // agz_replay_reanalyze_start sets the two behind this call
+  V_.an_pi = nullptr;
+  ra_on_ = false;
   // analysis lines (agz_analyze_set_lines): every slot of the three tables starts unused, which is what a row that is
   // never searched keeps
   V_.an_lines = lines_k_;
@@ -1129,6 +1200,73 @@ void Engine::review_start(const int16_t* moves, const int64_t* game_offset, cons
   V_.rv_moves = rv_moves_.p;
   V_.rv_off = rv_off_.p;
   begin_analysis_run(G, total, game_id_base);
+}
+
+// ---- reanalysis: a review run over arena games [first, first + count), and the commit of its rows into their records
+
+void Engine::replay_reanalyze_start(int64_t first, int64_t count, uint64_t game_id_base) {
+  require_selfplay_engine("reanalyze");
+  const int64_t n = (int64_t)rp_hdr_.size();
+  AGZ_REQUIRE(n > 0, AGZ_BAD_ARGUMENT, "reanalyze: the replay arena is empty");
+  AGZ_REQUIRE(first >= 0 && count >= 1 && count <= n && first <= n - count, AGZ_BAD_ARGUMENT,
+              "reanalyze: games %lld .. %lld + %lld: the replay arena holds %lld", (long long)first, (long long)first,
+              (long long)count, (long long)n);
+  std::vector<int64_t> off((size_t)count + 1, 0);
+  for (int64_t j = 0; j < count; ++j) off[(size_t)j + 1] = off[(size_t)j] + rp_hdr_[(size_t)(first + j)].num_moves;
+  const int64_t total = off[(size_t)count];
+  AGZ_REQUIRE(total <= 0x7fffffffLL, AGZ_BAD_ARGUMENT, "reanalyze: %lld rows in one run: at most 2^31 - 1",
+              (long long)total);
+  wait();     // nothing in flight may still read the tables that are replaced here
+  replay_index_to_device();
+  const size_t G = (size_t)count, P = (size_t)V_.P, A = (size_t)V_.A, R = (size_t)(total > 0 ? total : 1);
+  an_board_.ensure(G * P);
+  an_hist_.ensure(7 * G * P);
+  an_info_.ensure(G);
+  an_gid_.ensure(G);
+  an_pi_.ensure(R * A);
+  AGZ_HIP(hipMemsetAsync(an_pi_.p, 0, sizeof(float) * R * A, stream_));
+  clear_result_tables(total);
+  rv_moves_.ensure(R);
+  stage(rv_off_, off.data(), G + 1);
+  hipLaunchKernelGGL(k_reanalyze_gather, dim3((unsigned)G), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
+                     (const int64_t*)(d_rp_off_.p + first), (const int64_t*)rv_off_.p, game_id_base, rv_moves_.p,
+                     an_board_.p, an_hist_.p, an_info_.p, an_gid_.p);
+  AGZ_HIP(hipGetLastError());
+  rv_off_host_.swap(off);
+  V_.review = 1;
+  V_.rv_moves = rv_moves_.p;
+  V_.rv_off = rv_off_.p;
+  begin_analysis_run(count, total, game_id_base);       // (waits: `off` has been read)
+  V_.an_gid = an_gid_.p;
+  V_.an_pi = an_pi_.p;
+  ra_on_ = true;
+  ra_committed_ = false;
+  ra_first_ = first;
+  ra_stamp_ = rp_change_;
+}
+
+void Engine::replay_reanalyze_commit(int64_t counts_out[3]) {
+  AGZ_REQUIRE(ra_on_, AGZ_BAD_ARGUMENT,
+              "reanalyze commit: no reanalysis run in force (a later analysis, review or self-play start ends one)");
+  AGZ_REQUIRE(!ra_committed_, AGZ_BAD_ARGUMENT, "reanalyze commit: the run has been committed already");
+  AGZ_REQUIRE(ra_stamp_ == rp_change_, AGZ_BAD_ARGUMENT,
+              "reanalyze commit: the replay arena changed since the run started (ingest, trim, clear, window or targets-only)");
+  const int64_t done = analyze_progress(), rows = an_count_;
+  AGZ_REQUIRE(done >= rows, AGZ_BAD_ARGUMENT, "reanalyze commit: %lld of %lld rows finished", (long long)done,
+              (long long)rows);
+  ra_counts_.ensure(3);
+  ra_counts_.zero(stream_);
+  if (rows > 0)
+    hipLaunchKernelGGL(k_replay_refresh, dim3((unsigned)rows), dim3(kWave), 0, stream_, rp_buf_.p,
+                       (const int64_t*)(d_rp_off_.p + ra_first_), (const int64_t*)rv_off_.p, (int64_t)V_.an_count, V_.A,
+                       (const agz_analysis*)an_res_.p, (const float*)an_pi_.p, ra_counts_.p);
+  AGZ_HIP(hipGetLastError());
+  unsigned long long c[3];
+  down(c, ra_counts_.p, 3);
+  wait();
+  ra_committed_ = true;
+  if (counts_out)
+    for (int i = 0; i < 3; ++i) counts_out[i] = (int64_t)c[i];
 }
 
 int64_t Engine::analyze_progress() {
@@ -1462,6 +1600,7 @@ int64_t Engine::replay_ingest_chunks(const uint8_t* dbuf, const std::vector<int6
     total_bytes += cbytes[c];
   }
   if (total_rec == 0 || total_bytes == 0) return 0;
+  ++rp_change_;
   // device scratch: [coff | cbytes | nrec | first] int64 x nc, then offsets, found counts, bad flag, headers
   DevBuf<int64_t> d_meta, d_off;
   DevBuf<agz_game_header> d_hdr;
@@ -1581,6 +1720,7 @@ void Engine::replay_game(int64_t k, int16_t* moves, float* pis, float* qs) {
 // the FIFO window of train() (`shrink`, train.jl:52): forget the oldest games until at most max_positions remain
 void Engine::replay_trim(int64_t max_positions) {
   AGZ_REQUIRE(max_positions >= 0, AGZ_BAD_ARGUMENT, "negative window");
+  ++rp_change_;
   size_t drop = 0;
   int64_t pos = rp_positions_;
   while (drop < rp_hdr_.size() && pos > max_positions) pos -= rp_hdr_[drop++].num_moves;
@@ -1631,6 +1771,7 @@ void Engine::replay_drop_front(size_t drop) {
 
 // (the targets-only mode is a setting of the arena, not part of its contents: it stays as it is)
 void Engine::replay_clear() {
+  ++rp_change_;
   rp_off_.clear();
   rp_hdr_.clear();
   rp_cum_.assign(1, 0);
@@ -1646,6 +1787,7 @@ void Engine::replay_clear() {
 // start never moves back.  Dead games are dropped physically only once they hold more than half of the arena's bytes,
 // so the copy is amortised over many calls.  max_entries < 0: every entry live again (nothing dropped comes back).
 void Engine::replay_set_window(int64_t max_entries) {
+  ++rp_change_;
   if (max_entries < 0) { rp_first_game_ = 0; rp_first_ply_ = 0; return; }
   const std::vector<int64_t>& ec = rp_entry_cum();       // every ply, or (targets-only) the target plies
   const int64_t cur = ec[(size_t)rp_first_game_] + rp_first_ply_;
@@ -1668,6 +1810,7 @@ void Engine::replay_set_targets_only(bool on) {
   AGZ_REQUIRE(rp_hdr_.empty(), AGZ_BAD_ARGUMENT, "targets only: the replay arena holds %lld games; clear it first",
               (long long)rp_hdr_.size());
   rp_targets_only_ = on;
+  ++rp_change_;
   rp_first_game_ = 0;
   rp_first_ply_ = 0;
 }
@@ -1724,6 +1867,24 @@ void Engine::replay_sample(int B, uint64_t call, int sym_mode, float* feats, flo
               "sym_mode %d: -1 (none), 0..7 (fixed T_s) or 8 (drawn)", sym_mode);
   AGZ_REQUIRE(feats, AGZ_BAD_ARGUMENT, "feats is NULL");
   const int64_t n = (int64_t)rp_hdr_.size();
+  replay_index_to_device();
+  smp_off_.ensure(kSampleMax);
+  smp_ply_.ensure(kSampleMax);
+  smp_sym_.ensure(kSampleMax);
+  smp_boards_.ensure((size_t)B * 8 * V_.PP);
+  const bool with_sym = sym_mode != AGZ_SYMMETRY_NONE;
+  hipLaunchKernelGGL(k_replay_sample, dim3(1), dim3(kSampleThreads), 0, stream_, (uint64_t)V_.seed, call, B, L,
+                     rp_entry_cum()[(size_t)rp_first_game_] + rp_first_ply_,
+                     (const int64_t*)(rp_targets_only_ ? d_rp_tcum_.p : d_rp_cum_.p), (const int64_t*)d_rp_off_.p,
+                     (const int64_t*)d_rp_cum_.p, (const int16_t*)(rp_targets_only_ ? d_rp_tply_.p : nullptr), n, sym_mode,
+                     smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, game_out, ply_out);
+  AGZ_HIP(hipGetLastError());
+  emit_replay_batch(B, smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, smp_boards_.p, feats, pi, z);
+}
+
+// the arena's index (rp_off_, rp_cum_ and, targets-only, rp_tcum_) on the device: only what changed since the last call
+void Engine::replay_index_to_device() {
+  const int64_t n = (int64_t)rp_hdr_.size();
   if (d_rp_cum_.n < (size_t)n + 1 || d_rp_off_.n < (size_t)n || (rp_targets_only_ && d_rp_tcum_.n < (size_t)n + 1)) {
     const size_t cap = std::max<size_t>(2 * (size_t)n + 1, 1024);
     d_rp_cum_.alloc(cap);
@@ -1739,18 +1900,6 @@ void Engine::replay_sample(int B, uint64_t call, int sym_mode, float* feats, flo
     wait();      // the host vectors may move with the next ingest
     rp_dev_n_ = n;
   }
-  smp_off_.ensure(kSampleMax);
-  smp_ply_.ensure(kSampleMax);
-  smp_sym_.ensure(kSampleMax);
-  smp_boards_.ensure((size_t)B * 8 * V_.PP);
-  const bool with_sym = sym_mode != AGZ_SYMMETRY_NONE;
-  hipLaunchKernelGGL(k_replay_sample, dim3(1), dim3(kSampleThreads), 0, stream_, (uint64_t)V_.seed, call, B, L,
-                     rp_entry_cum()[(size_t)rp_first_game_] + rp_first_ply_,
-                     (const int64_t*)(rp_targets_only_ ? d_rp_tcum_.p : d_rp_cum_.p), (const int64_t*)d_rp_off_.p,
-                     (const int64_t*)d_rp_cum_.p, (const int16_t*)(rp_targets_only_ ? d_rp_tply_.p : nullptr), n, sym_mode,
-                     smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, game_out, ply_out);
-  AGZ_HIP(hipGetLastError());
-  emit_replay_batch(B, smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, smp_boards_.p, feats, pi, z);
 }
 
 // B samples given on the device as (record offset, ply) -> feats [B][17 P], pi [B][A] (or NULL) and z [B] (or NULL) in

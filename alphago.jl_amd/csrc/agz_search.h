@@ -1906,6 +1906,8 @@ AGZ_FN void analysis_finish(W& w, const View& V, Scratch& S, int g) {
     V.an_childW[i * A + k] = V.childW[ri * V.AP + k];
     V.an_prior[i * A + k] = V.childP[ri * V.AP + k];
   });
+  // reanalysis: the pi row the self-play move phase records at this root, under the same squash rule
+  if (V.an_pi) children_as_pi(w, V, S, ri, V.meta[ri].n <= V.tau, V.an_pi + i * A);
   if (V.an_lines > 0) {                                 // (review mode: before review_play re-roots)
     const long long kd = (long long)V.an_lines * V.an_pv_depth;
     node_lines(w, V, S, g, G.root, V.an_lines, V.an_pv_depth, V.an_pv_min, V.an_line + i * V.an_lines, V.an_pv + i * kd,
@@ -1958,7 +1960,7 @@ AGZ_FN void review_next_ply(W& w, const View& V, int g) {
   }
   const int a = V.rv_moves[off + G.move_count];
   const long ri = node_index(V, g, G.root);
-  if (node_is_done(V, g, G.root) || !legal_bit(V, ri, a)) {
+  if (node_is_done(V, g, G.root) || a < 0 || a > V.P || !legal_bit(V, ri, a)) {   // (arena records: no host check)
     review_give_up(w, V, g, AGZ_BAD_ARGUMENT);
     return;
   }
@@ -2017,7 +2019,7 @@ AGZ_FN void review_claim(W& w, const View& V, Scratch& S, int g, long long j) {
   const bool ok = root_install(w, V, S, g, V.an_board + j * V.P, V.an_hist + j * 7 * V.P, info, G_SEARCH, true);
   if (w.leader()) {
     G.move_count = 0;
-    if (ok) { G.game_id = V.an_id_base + (uint64_t)j; G.short_first = 0; }
+    if (ok) { G.game_id = V.an_gid ? V.an_gid[j] : V.an_id_base + (uint64_t)j; G.short_first = 0; }
   }
   w.sync();
   if (!ok) { review_give_up(w, V, g, AGZ_BAD_ARGUMENT); return; }

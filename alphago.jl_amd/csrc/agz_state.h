@@ -223,6 +223,11 @@ struct View {
   int32_t gumbel_m;                   // m
   double gumbel_cvisit, gumbel_cscale;
   GumbelState* gumbel;                // [games]
+  // reanalysis (agz_replay_reanalyze_start; NULL = off, the View{} of the host simulator): a review run whose games are
+  // records of the replay arena.  an_gid[j] is game j's draw-stream game id (NULL: an_id_base + j); with an_pi set,
+  // analysis_finish also writes the root's children_as_pi row, the policy target self-play records
+  const uint64_t* an_gid;             // [an_count]
+  float* an_pi;                       // [rows][A]
 };
 
 // option values -> View fields, for the engine's setters (which check the arguments first) and the host simulator's

@@ -23,7 +23,7 @@ using Random
 export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, train, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
-       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, set_starts!, set_playout_cap!, playout_cap_counts, set_forced_playouts!, forced_counts, pruned_pi, set_gumbel!, gumbel_counts, gumbel_pi, extract_targets, value_targets, extract_value_targets, node_lines, most_visited_path, mvp_gg,
+       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, reanalyze!, set_starts!, set_playout_cap!, playout_cap_counts, set_forced_playouts!, forced_counts, pruned_pi, set_gumbel!, gumbel_counts, gumbel_pi, extract_targets, value_targets, extract_value_targets, node_lines, most_visited_path, mvp_gg,
        # the node-level surface test/test_mcts.jl:2-5 and test/test_mcts_player.jl:3-6 import
        MCTSNode, select_leaf, maybe_add_child!, add_virtual_loss!, revert_virtual_loss!,
        incorporate_results!, inject_noise!, child_action_score, child_Q, child_U, child_N, child_W,
@@ -1037,7 +1037,13 @@ function review(env::GoEnv, nn::NeuralNet, games::Vector; num_readouts::Int = 80
   check(e, ccall((:agz_review_start, libagz), Int32,
                  (Ptr{Cvoid}, Ptr{Int16}, Ptr{Int64}, Ptr{Int8}, Ptr{AgzPositionInfo}, Ptr{Int8}, Int64, UInt64),
                  e.handle, moves, off, boards, info, hist, G, game_id_base))
-  total = off[end]
+  review_rows(e, env, off, UInt64[UInt64(game_id_base + j - 1) for j in 1:G], lines, pv_depth)
+end
+
+# the loop behind review and reanalyze!: step the review run on `e` until its off[end] rows are finished, then read them
+# as one vector of NamedTuples per game (game j's rows off[j]+1 .. off[j+1], its game id ids[j])
+function review_rows(e::Engine, env::GoEnv, off::Vector{Int64}, ids::Vector{UInt64}, lines::Int, pv_depth::Int)
+  G, A, total = length(ids), env.action_space, off[end]
   done = Ref{Int64}(0)
   while true
     check(e, ccall((:agz_analyze_progress, libagz), Int32, (Ptr{Cvoid}, Ref{Int64}), e.handle, done))
@@ -1049,16 +1055,42 @@ function review(env::GoEnv, nn::NeuralNet, games::Vector; num_readouts::Int = 80
   cn, cw, pr = zeros(Float32, A, total), zeros(Float32, A, total), zeros(Float32, A, total)
   check(e, ccall((:agz_analyze_results, libagz), Int32, (Ptr{Cvoid}, Ptr{AgzAnalysis}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
                  e.handle, res, cn, cw, pr))
-  row(i, j0) = (r = res[i]; (move = r.move < 0 ? nothing : from_flat(r.move + 1, env), N = r.N, W = r.W, Q = r.Q,
+  row(i, id) = (r = res[i]; (move = r.move < 0 ? nothing : from_flat(r.move + 1, env), N = r.N, W = r.W, Q = r.Q,
             child_N = cn[:, i], child_W = cw[:, i], child_Q = cw[:, i] ./ (1f0 .+ cn[:, i]), child_prior = pr[:, i],
-            status = Int(r.status), nodes_used = Int(r.nodes_used), game_id = UInt64(game_id_base + j0)))
+            status = Int(r.status), nodes_used = Int(r.nodes_used), game_id = id))
   ln, pv, pvn = lines > 0 ? read_lines(e, total, lines, pv_depth) : (nothing, nothing, nothing)
   withlines(i, r) = lines > 0 ? merge(r, (lines = line_rows(env, ln[:, i], pv[:, :, i], pvn[:, :, i]),)) : r
   out = Vector{Vector{NamedTuple}}(undef, G)
   for j in 1:G
-    out[j] = [withlines(i, row(i, j - 1)) for i in off[j]+1:off[j+1]]
+    out[j] = [withlines(i, row(i, ids[j])) for i in off[j]+1:off[j+1]]
   end
   out
+end
+
+# reanalyze!(e, env; first, count) (ours; MuZero's Reanalyse, include/agz.h agz_replay_reanalyze_start / _commit): search
+# the replay-arena games first .. first + count - 1 (0-based, count = nothing: all from `first`) of engine `e` again on
+# its current network -- a review run gathered on the device, game id game_id_base + the record's -- and, with commit,
+# write every finished row over its record: qs[k] = Q, and the new π row unless the old one is all zero.  Moves, results
+# and the arena's order stay.  Returns ((committed, pi_rows, skipped) or nothing, the rows per game as review gives them).
+function reanalyze!(e::Engine, env::GoEnv; first::Integer = 0, count::Union{Nothing, Integer} = nothing, game_id_base = 0,
+                    commit::Bool = true, lines::Int = 0, pv_depth::Int = 16, pv_min_visits::Int = 1)
+  check_lines(lines, pv_depth, pv_min_visits)
+  G = count === nothing ? replay_games(e) - first : count
+  check(e, ccall((:agz_analyze_set_lines, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Int32),
+                 e.handle, lines, pv_depth, pv_min_visits))
+  check(e, ccall((:agz_replay_reanalyze_start, libagz), Int32, (Ptr{Cvoid}, Int64, Int64, UInt64),
+                 e.handle, first, G, game_id_base))
+  h = Ref{AgzGameHeader}()
+  off = Int64[0]; ids = UInt64[]
+  for k in first:first+G-1
+    check(e, ccall((:agz_replay_header, libagz), Int32, (Ptr{Cvoid}, Int64, Ref{AgzGameHeader}), e.handle, k, h))
+    push!(off, off[end] + h[].num_moves); push!(ids, UInt64(game_id_base) + h[].game_id)
+  end
+  rows = review_rows(e, env, off, ids, lines, pv_depth)
+  commit || return nothing, rows
+  counts = zeros(Int64, 3)
+  check(e, ccall((:agz_replay_reanalyze_commit, libagz), Int32, (Ptr{Cvoid}, Ptr{Int64}), e.handle, counts))
+  (committed = counts[1], pi_rows = counts[2], skipped = counts[3]), rows
 end
 
 # get_replay_batch(pos_buffer, π_buffer, res_buffer; batch_size), src/train.jl:4-12: batch_size distinct entries,

@@ -2,13 +2,15 @@
 """One generation of the reference's train() loop (src/train.jl:38-92) on the MI355X:
 self-play -> replay arena -> training batches -> optimiser step -> arena match -> checkpoint.
 
-    python examples/generation_loop.py [--board 9] [--tower 2] [--games 32] [--readouts 64]
+    python examples/generation_loop.py [--board 9] [--tower 2] [--games 32] [--readouts 64] [--reanalyze]
 
 What runs where:
   selfplay          G concurrent games on the device (one wave per tree, one network batch per step)
   extract_data      finished games come back as (moves, pi, result); multi-GPU: all-gathered over RCCL
   get_replay_batch  (game, ply) pairs are sampled on the host; the device replays the move lists of the replay
                     arena and emits the N x N x 17 x B feature tensor, pi and z (agz_replay_batch)
+  reanalyze         (--reanalyze) the arena's games are searched again on the current weights and their pi / q
+                    targets overwritten in place, moves and results as played (agz_replay_reanalyze_start / _commit)
   _train            agz_train_step: training-mode forward, 0.01 CE + 0.01 MSE + 1e-4 L2, backward, Momentum(0.02)
   evaluate          candidate vs incumbent, both networks resident in one arena engine
   save_model        BSON parameter lists readable by Flux.loadparams!
@@ -34,6 +36,7 @@ def main(argv=None):
     ap.add_argument("--readouts", type=int, default=64)
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--eval-games", type=int, default=8)
+    ap.add_argument("--reanalyze", action="store_true", help="refresh the arena's targets before the training batches")
     args = ap.parse_args(argv)
 
     env = ag.GoEnv(args.board)
@@ -52,9 +55,16 @@ def main(argv=None):
     _, pi, z = buf.sample(B, np.random.default_rng(0), cur.engine, out=feats)       # host-side buffer, device replay
     # the same through the device replay arena + the training step (train.jl:56-70)
     eng = cur.engine
+    if args.reanalyze:      # a search needs slots, readouts and a node pool: an engine of that shape holds the arena
+        eng = ag.Engine(board_size=env.N, tower_height=args.tower, games=min(args.games, 1024),
+                        num_readouts=args.readouts, seed=1)
+        cur.engine.copy_weights_to(eng)
     eng.replay_ingest(ag.distributed.pack_records(
         [dict(game_id=r.game_id, result=r.result, was_resign=r.was_resign, moves=[ag.to_flat(c, env) for c in r.moves],
               pis=r.searches_pi, qs=r.qs) for r in records], env.action_space))
+    if args.reanalyze:
+        counts, _ = ag.reanalyze(eng)
+        print(f"reanalyse: {counts['committed']} rows refreshed ({counts['pi_rows']} pi rows), {counts['skipped']} skipped")
     rng = np.random.default_rng(1)
     lens = np.array([eng.replay_record(k)["num_moves"] for k in range(eng.replay_count())])
     losses = []
@@ -65,6 +75,9 @@ def main(argv=None):
         f, p, zz = eng.replay_batch(game, ply)
         losses.append(eng.train_step(f, p, zz)[0])
     print("training: loss", " -> ".join(f"{x:.5f}" for x in losses))
+    if args.reanalyze:      # the trained weights go back to the network the match and the checkpoint use
+        eng.copy_weights_to(cur.engine)
+        eng.close()
 
     ok, st = ag.evaluate(env, cur, prev, num_games=args.eval_games, ro=args.readouts, seed=2, return_stats=True)
     print(f"evaluate: Black (candidate) won {st.games_won}/{st.num_games} -> {'keep' if ok else 'revert'}")

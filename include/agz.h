@@ -730,6 +730,47 @@ agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N,
 agz_status agz_review_start(agz_engine* e, const int16_t* moves, const int64_t* game_offset, const int8_t* boards,
                             const agz_position_info* info, const int8_t* history, int64_t G, uint64_t game_id_base);
 
+/* ---------------------------------------------------------------- reanalysis ------------ */
+/* Refresh the targets of games already in the replay arena with the engine's current network (ours; MuZero's
+ * Reanalyse): the stored positions are searched again and the records' pi rows and qs overwritten; the moves, the
+ * outcome, the headers, the arena's order and its window stay as played.  Off unless called.
+ *
+ * agz_replay_reanalyze_start starts a review run (see agz_review_start) whose games are arena games first ..
+ * first + count - 1, indexed as agz_replay_game indexes them.  Nothing of a record visits the host: a kernel copies its
+ * moves into the review tables, takes its start from the start-position table (entry header.game_id mod S by the index
+ * rule of agz_selfplay_set_starts; no table: the empty board with agz_config.komi), and keys its draws by game id
+ * game_id_base + header.game_id -- so a row depends neither on the arena index of its game nor on first and count, and
+ * runs over disjoint ranges, or over the same games ingested in another order, give the same rows per game_id.
+ * Everything else is agz_review_start's contract: row k of a game is suggest_move at ply k of
+ *   p = MCTSPlayer(env, nn; num_readouts) with draw-stream seed agz_config.seed and that game id;
+ *   initialize_game!(p, start);  for k: suggest_move(p), then play_move!(p, m_k)
+ * on the selected network (agz_net_select) and the engine's own num_readouts and pool: plain PUCT without noise,
+ * resignation or record, whatever playout cap, forced playouts or Gumbel setting self-play has;
+ * agz_selfplay_set_symmetry applies.  It takes over the slots (self-play games in flight are dropped; a later
+ * agz_selfplay_start plays as a fresh engine does), is stepped with agz_selfplay_step and read with
+ * agz_analyze_progress / agz_analyze_results / agz_slot_status, with agz_analyze_set_lines on also agz_analyze_lines;
+ * game j's ply k is row (moves of the run's games before j) + k.  Besides the tables of a review run every finished
+ * search keeps the row children_as_pi(root, n <= tau_threshold) -- what play_move! appends to searches_pi
+ * (mcts_play.jl:26-50), taken before the recorded move re-roots the tree.  A record whose move cannot be played (or is
+ * outside 0..N*N) gives AGZ_BAD_ARGUMENT rows from that ply on, as in a review run.
+ * Refused (AGZ_BAD_ARGUMENT, nothing changed): first < 0, count < 1, first + count > agz_replay_count, an empty arena,
+ * an arena_mode engine.
+ *
+ * agz_replay_reanalyze_commit writes the run into the arena, one wave per row, on the engine's stream.  A row is
+ * committed iff its agz_analysis.status is AGZ_OK: qs[k] = Q (= W / (1 + N) of the root, Black-absolute, the expression
+ * self-play records), and the pi row replaces the record's unless that one is all zero.  An all-zero row means "no
+ * policy target" (a fast search of agz_selfplay_set_playout_cap, an arena record) and stays all zero, so the
+ * targets-only index, the window and the entry numbering of agz_replay_sample hold.  Short rows
+ * (AGZ_POOL_EXHAUSTED), invalid rows (AGZ_BAD_ARGUMENT), failed soft picks and given-up rows leave their plies as they
+ * were.  counts_out (may be NULL) = {rows committed, pi rows overwritten, rows skipped}.  agz_replay_game, _batch,
+ * _batch_sym, _sample and the value targets of agz_replay_set_value_target read the new rows from then on.
+ * Synchronises.  The arena is unchanged until commit.  Refused (AGZ_BAD_ARGUMENT, the arena unchanged): no reanalysis
+ * run in force (agz_analyze_start, agz_review_start and agz_selfplay_start end one); the run not complete
+ * (agz_analyze_progress below its rows); a second commit of one run; any agz_replay_ingest*, agz_replay_trim, _clear,
+ * _set_window or _set_targets_only call since the start. */
+agz_status agz_replay_reanalyze_start(agz_engine* e, int64_t first, int64_t count, uint64_t game_id_base);
+agz_status agz_replay_reanalyze_commit(agz_engine* e, int64_t counts_out[3]);
+
 /* ---------------------------------------------------------------- analysis lines -------- */
 /* The top-K candidate moves of a searched node and the principal variation (PV) the search expects behind each: what
  * most_visited_path, mvp_gg and describe of src/mcts.jl:255-327 define (commented out there; their text is the
