@@ -460,7 +460,7 @@ class MCTSPlayer:
     plain arrays or Tracker-style objects carrying `.data` (mcts_play.jl:90)."""
 
     def __init__(self, env, network, num_readouts=800, two_player_mode=False, resign_threshold=-0.9, seed=0,
-                 game_id=0, symmetry=None):
+                 game_id=0, symmetry=None, fpu=None, c_base=0.0):
         self.env = env
         self.network = network
         self.num_readouts = num_readouts
@@ -478,6 +478,7 @@ class MCTSPlayer:
             if not internal:
                 raise ValueError("symmetry needs a NeuralNet of this package: a caller's network receives Positions")
             self.engine.set_symmetry(symmetry)
+        _apply_puct(self.engine, fpu, c_base)      # (ours) the PUCT rule options of Engine.set_puct
         self._game_id = game_id
         self.qs, self.searches_pi = [], []
         self.result, self.result_string = 0, ""
@@ -683,10 +684,17 @@ def _refuse_two_root_rules(gumbel, forced_playouts):      # before selfplay() / 
         raise ValueError("gumbel and forced_playouts are two rules for the same decision: ask for one")
 
 
+def _apply_puct(eng, fpu, c_base):
+    """the PUCT rule options (Engine.set_puct) on a fresh engine; nothing asked for, nothing set"""
+    if fpu is not None or c_base:
+        eng.set_puct(fpu, c_base)
+
+
 def _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit, gumbel_c_scale,
-                          targets_only_arena=False):
+                          targets_only_arena=False, fpu=None, c_base=0.0):
     """selfplay()'s and train()'s search options on a fresh engine (train(): a targets-only arena under the cap)"""
     _refuse_two_root_rules(gumbel, forced_playouts)
+    _apply_puct(eng, fpu, c_base)
     if starts:
         eng.set_starts(starts)
     if playout_cap is not None:
@@ -706,7 +714,7 @@ def seed(s):
 
 def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="f32", game_id_base=None, symmetry=None,
              starts=None, playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
-             gumbel_c_scale=1.0, **cfg):
+             gumbel_c_scale=1.0, fpu=None, c_base=0.0, **cfg):
     """selfplay(env, nn, num_ro) (src/selfplay.jl:1-45) -> the finished game's player (SelfPlayPlayer), exactly the
     call train() makes (train.jl:57).  `games=G` (ours) plays G games concurrently on the device and returns a list of
     G such players ordered by game id.  Game ids continue from the previous call (module stream, `seed()`), unless
@@ -722,7 +730,9 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     row with the forced visits the search did not agree with left out.
     gumbel (ours): m -- the Gumbel root search (Engine.set_gumbel) in the full searches: up to m root candidates by
     Gumbel-top-k, Sequential Halving, the searches_pi row is softmax(log prior + sigma(q)); gumbel_c_visit and
-    gumbel_c_scale are sigma's constants.  It composes with playout_cap, starts and symmetry, not with forced_playouts."""
+    gumbel_c_scale are sigma's constants.  It composes with playout_cap, starts and symmetry, not with forced_playouts.
+    fpu and c_base (ours): the PUCT rule options of Engine.set_puct -- first-play urgency reduction, r or (r, r_root),
+    and the c_puct growth constant -- at every level of every search; they compose with all of the above."""
     _refuse_two_root_rules(gumbel, forced_playouts)
     single = games is None
     games = 1 if single else int(games)
@@ -740,7 +750,8 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     eng.set_precision(precision)
     if symmetry is not None:
         eng.set_symmetry(symmetry)
-    _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit, gumbel_c_scale)
+    _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit, gumbel_c_scale,
+                          fpu=fpu, c_base=c_base)
     eng.start(games)
     while eng.records_count() < games:
         eng.step(16)
@@ -795,7 +806,7 @@ def _line_rows(env, t):
 
 
 def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=None, two_player_mode=False,
-            symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, **cfg):
+            symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, fpu=None, c_base=0.0, **cfg):
     """suggest_move over many positions in one device run (ours).  Record i is what
     `MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + i, symmetry=symmetry)`,
     `initialize_game(positions[i])`, `suggest_move()` computes (mcts_play.jl:110-118,144-151), bit for bit, except that
@@ -838,6 +849,7 @@ def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=
         eng.set_precision(precision)
         if symmetry is not None:
             eng.set_symmetry(symmetry)
+        _apply_puct(eng, fpu, c_base)      # the PUCT rule options of Engine.set_puct, as MCTSPlayer(fpu=, c_base=)
         if lines:
             eng.analyze_set_lines(lines, pv_depth, pv_min_visits)
         eng.analyze_start(boards, infos, hist, game_id_base)
@@ -897,7 +909,7 @@ def review_arrays(env, games):
 
 
 def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, seed=0, game_id_base=0, slots=None,
-           symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, **cfg):
+           symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, fpu=None, c_base=0.0, **cfg):
     """Batched game review (ours; the loop of play(), src/play.jl:25-77, over recorded games): for game j, what
     `p = MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + j, symmetry=symmetry)`,
     `p.initialize_game(starts[j])`, then for every recorded move m_k `p.suggest_move()` and `p.play_move(m_k)` compute,
@@ -949,6 +961,7 @@ def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, 
         eng.set_precision(precision)
         if symmetry is not None:
             eng.set_symmetry(symmetry)
+        _apply_puct(eng, fpu, c_base)      # the PUCT rule options of Engine.set_puct, as MCTSPlayer(fpu=, c_base=)
         if lines:
             eng.analyze_set_lines(lines, pv_depth, pv_min_visits)
         eng.review_start(moves, off, boards, infos, hist, game_id_base)
@@ -1006,7 +1019,7 @@ EvalStats = namedtuple("EvalStats", "games_won num_games win_rate resigned moves
 
 
 def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, seed=0, slots=None,
-             return_stats=False, symmetry=None, starts=None, **cfg):
+             return_stats=False, symmetry=None, starts=None, fpu=None, c_base=0.0, **cfg):
     """evaluate(env, black_net, white_net; num_games, ro) (src/neural_net.jl:103-158): black_net plays
     Black and white_net White in `num_games` games of two two_player_mode MCTSPlayers (arg-max moves,
     no noise, resign at -0.9); True iff Black's win rate reaches 0.55.  All games run concurrently on
@@ -1015,7 +1028,8 @@ def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, se
     by the Tromp-Taylor score of the final position, also after a resignation (:147).  symmetry (ours): as for
     selfplay(), applied to both networks' evaluations.  starts (ours): an opening suite -- game g begins at the Position
     starts[g % len(starts)] with komi, stones and side to move as given there; the player of the colour to move searches
-    first, black_net still plays Black.  The records (return_stats) carry the entry as `start`."""
+    first, black_net still plays Black.  The records (return_stats) carry the entry as `start`.  fpu and c_base (ours):
+    the PUCT rule options of Engine.set_puct, for both players."""
     if black_net.tower_height != white_net.tower_height:
         raise ValueError("the arena keeps both networks in one engine: tower heights must match")
     pairs = min(num_games, 512) if slots is None else slots
@@ -1027,6 +1041,7 @@ def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, se
     eng.net_select(0)
     if symmetry is not None:
         eng.set_symmetry(symmetry)
+    _apply_puct(eng, fpu, c_base)
     if starts:
         eng.set_starts(starts)
     eng.start(num_games)
@@ -1130,7 +1145,7 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
           tower_height=19, model=None, start_training_after=50000, slots=None, seed=0, game_id_base=0, symmetry=None,
           augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, starts=None,
           playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
-          gumbel_c_scale=1.0, value_target=None, **cfg):
+          gumbel_c_scale=1.0, value_target=None, fpu=None, c_base=0.0, **cfg):
     """train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model,
     start_training_after) (src/train.jl:38-92) with `slots` games in flight on the device.  One engine
     plays, keeps the replay arena and trains; per step: agz_selfplay_step(1), one read of how many games finished, and
@@ -1151,7 +1166,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
     forced_playouts (k) and prune_targets (forced playouts and policy target pruning in the full searches, as in selfplay),
     gumbel (m), gumbel_c_visit and gumbel_c_scale (the Gumbel root search in the full searches, as in selfplay),
     value_target ((alpha, lam): the z of every training batch is (1 - alpha) * result + alpha * TD(lam) of the game's
-    recorded root values from the sampled ply on, Engine.replay_set_value_target; None: the result, as the reference).
+    recorded root values from the sampled ply on, Engine.replay_set_value_target; None: the result, as the reference),
+    fpu and c_base (the PUCT rule options of Engine.set_puct, as in selfplay).
     Returns the trained NeuralNet (model itself when given)."""
     import time
     import torch
@@ -1181,7 +1197,7 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
         z = torch.empty(batch_size, dtype=torch.float32, device=dev)
         cuts = _minibatch_cuts(batch_size)
         _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit,
-                              gumbel_c_scale, targets_only_arena=True)
+                              gumbel_c_scale, targets_only_arena=True, fpu=fpu, c_base=c_base)
         if value_target is not None:
             eng.replay_set_value_target(*value_target)
         eng.set_hold(True)

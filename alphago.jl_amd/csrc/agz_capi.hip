@@ -360,6 +360,19 @@ agz_status agz_selfplay_gumbel_counts(agz_engine* e, int64_t out[2]) {
 agz_status agz_tree_gumbel_pi(agz_engine* e, int32_t g, int32_t node, double c_visit, double c_scale, float* out) {
   return guard(e, [&](agz::Engine& E) { E.tree_gumbel_pi(g, node, c_visit, c_scale, out); });
 }
+agz_status agz_search_set_puct(agz_engine* e, int32_t fpu_on, double fpu_reduction, double fpu_reduction_root,
+                               double c_base) {
+  return guard(e, [&](agz::Engine& E) { E.set_puct(fpu_on, fpu_reduction, fpu_reduction_root, c_base); });
+}
+agz_status agz_search_puct_counts(agz_engine* e, uint64_t* out) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+    int64_t c[2];
+    E.puct_counts(c);
+    out[0] = (uint64_t)c[0];
+    out[1] = (uint64_t)c[1];
+  });
+}
 agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on) {
   return guard(e, [&](agz::Engine& E) { E.replay_set_targets_only(on != 0); });
 }

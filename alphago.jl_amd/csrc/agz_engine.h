@@ -58,6 +58,9 @@ class Engine {
   void set_gumbel(int m, double c_visit, double c_scale);
   void gumbel_counts(int64_t out[2]);
   void tree_gumbel_pi(int g, int node, double c_visit, double c_scale, float* out);
+  // PUCT rule options of every search (agz_search_set_puct): (0, 0, 0, 0) is off
+  void set_puct(int fpu_on, double r, double r_root, double c_base);
+  void puct_counts(int64_t out[2]);
   int64_t analyze_progress();
   void analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior);
   // analysis lines (agz_analyze_set_lines / agz_analyze_lines / agz_tree_lines): top-K candidates with their PVs

@@ -908,11 +908,13 @@ void Engine::read_counter_pair(int first, int64_t out[2]) {
   out[0] = (int64_t)c[0];
   out[1] = (int64_t)c[1];
 }
-static_assert(CT_CAP_FAST == CT_CAP_FULL + 1 && CT_PRUNED_ROWS == CT_FORCED_SEL + 1 && CT_GUMBEL_HALVED == CT_GUMBEL_BEGUN + 1,
+static_assert(CT_CAP_FAST == CT_CAP_FULL + 1 && CT_PRUNED_ROWS == CT_FORCED_SEL + 1 && CT_GUMBEL_HALVED == CT_GUMBEL_BEGUN + 1 &&
+                  CT_PUCT_UNVISITED == CT_PUCT_LEVELS + 1,
               "the counters of an option are read as one pair");
 void Engine::playout_cap_counts(int64_t out[2]) { read_counter_pair(CT_CAP_FULL, out); }
 void Engine::forced_counts(int64_t out[2]) { read_counter_pair(CT_FORCED_SEL, out); }
 void Engine::gumbel_counts(int64_t out[2]) { read_counter_pair(CT_GUMBEL_BEGUN, out); }
+void Engine::puct_counts(int64_t out[2]) { read_counter_pair(CT_PUCT_LEVELS, out); }
 
 // one pi row [A] of a single tree's node: `launch` writes it to the device row it is given
 template <class Launch>
@@ -963,6 +965,23 @@ void Engine::set_gumbel(int m, double c_visit, double c_scale) {
   require_between_games("gumbel");
   wait();
   view_set_gumbel(V_, m, c_visit, c_scale);
+}
+
+// ---- the PUCT rule options (agz_search_set_puct): every search of every engine, so no require_selfplay_engine
+
+void Engine::set_puct(int fpu_on, double r, double r_root, double c_base) {
+  AGZ_REQUIRE(fpu_on == 0 || fpu_on == 1, AGZ_BAD_ARGUMENT, "puct: fpu_on = %d, not 0 or 1", fpu_on);
+  AGZ_REQUIRE(r >= 0.0 && r <= 4.0, AGZ_BAD_ARGUMENT, "puct: fpu_reduction = %g, not in 0 .. 4", r);
+  AGZ_REQUIRE(r_root >= 0.0 && r_root <= 4.0, AGZ_BAD_ARGUMENT, "puct: fpu_reduction_root = %g, not in 0 .. 4", r_root);
+  AGZ_REQUIRE(c_base == 0.0 || (c_base >= 1.0 && c_base <= 1.0e9), AGZ_BAD_ARGUMENT,
+              "puct: c_base = %g, not 0 (off) or in 1 .. 1e9", c_base);
+  AGZ_REQUIRE(tree_batch_ == 0, AGZ_BAD_ARGUMENT,
+              "puct: not between agz_tree_search_select and agz_tree_search_incorporate");
+  require_between_games("puct");
+  wait();
+  view_set_puct(V_, fpu_on, r, r_root, c_base);
+  AGZ_HIP(hipMemsetAsync(V_.counters + CT_PUCT_LEVELS, 0, sizeof(unsigned long long) * 2, stream_));
+  wait();
 }
 
 void Engine::tree_gumbel_pi(int g, int node, double c_visit, double c_scale, float* out) {

@@ -74,6 +74,10 @@ inline void fill_dims(View& V, const agz_config& c) {
   V.gumbel_m = 0;                // agz_selfplay_set_gumbel
   V.gumbel_cvisit = 0.0;
   V.gumbel_cscale = 0.0;
+  V.fpu_on = 0;                  // agz_search_set_puct
+  V.fpu_r = 0.0;
+  V.fpu_r_root = 0.0;
+  V.c_base = 0.0;
 }
 
 // visits every buffer of the View: f(pointer-reference, element count)

@@ -477,9 +477,42 @@ AGZ_FN double action_score(const View& V, long ni, int a, float to_play, double 
   return (double)qs + u;
 }
 
+// c_base > 0 (agz_search_set_puct): c_puct grows with the logarithm of the node's visits
 AGZ_FN double puct_scale(const View& V, float n_node) {
   const float one_plus_n = 1.0f + n_node;
+  if (V.c_base > 0.0) {
+    const double c = V.c_puct + agz_log(((double)one_plus_n + V.c_base) / V.c_base);
+    return c * (double)sqrtf(one_plus_n);
+  }
   return V.c_puct * (double)sqrtf(one_plus_n);
+}
+
+// PUCT rule options (View::fpu_on / c_base, agz_search_set_puct): is either part on?
+AGZ_FN bool puct_rule_on(const View& V) { return V.fpu_on != 0 || V.c_base > 0.0; }
+
+// First-play urgency.  A lane's share of M, the policy mass of the node's visited children in units of 2^-30: an
+// integer sum, so order-free and exact
+AGZ_FN long long fpu_mass(float n, float p) { return n > 0.0f ? (long long)((double)p * 1073741824.0) : 0ll; }
+// the sum of a wave's shares, through the int reductions every wave has (the low 24 bits and the rest apart)
+template <class W>
+AGZ_FN long long reduce_sum_i64(W& w, long long v) {
+  const int lo = w.reduce_sum((int)(v & 0xffffffll));
+  const int hi = w.reduce_sum((int)(v >> 24));
+  return (long long)hi * 16777216ll + (long long)lo;
+}
+// f, the Q of every unvisited child of a node with own statistics (n_s, w_s): the node's value from the side to move,
+// less rho * sqrt(m); rho = fpu_r_root at the game's root
+AGZ_FN float fpu_value(const View& V, bool is_root, float n_s, float w_s, float to_play, long long M) {
+  const double m = (double)M * (1.0 / 1073741824.0);
+  const float q_s = w_s / (1.0f + n_s);
+  const float qp = q_s * to_play;
+  const double rho = is_root ? V.fpu_r_root : V.fpu_r;
+  return (float)((double)qp - rho * agz_sqrt(m));
+}
+// the score of an unvisited child under the FPU: f for its Q, its U as action_score writes it with N_a = 0
+AGZ_FN double fpu_score(float f, float p, double scale) {
+  const double u = (scale * (double)p) / (double)1.0f;
+  return (double)f + u;
 }
 
 // k-th (0-based) set flag in ascending index order; every lane scans (LDS broadcast reads)
@@ -529,10 +562,16 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
   const int A = V.A, AP = V.AP, pass = V.P;
   const uint32_t move_key = (uint32_t)V.meta[node_index(V, g, G.root)].n;
   const uint32_t sel = (uint32_t)G.sel;
+  // the PUCT rule options (agz_search_set_puct): uniform branches on the View, so that off nothing below is new work
+  const bool rule = puct_rule_on(V), fpu = V.fpu_on != 0;
+  const int root = G.root;
   int cur = from, depth = 0, plen = 0;
+  int levels = 0, unvisited = 0;                               // CT_PUCT_LEVELS / CT_PUCT_UNVISITED of this descent
   w.sync();
   float* np = slotN(V, g, cur);
   float n_cur = *np;
+  float w_cur = 0.f;                                           // the node's own W: its parent's row, like n_cur
+  if (fpu) w_cur = *slotW(V, g, cur);
   for (;;) {
     const long ni = node_index(V, g, cur);
     const NodeMeta m = V.meta[ni];
@@ -563,7 +602,7 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
       return x;
     };
     int pick;
-    bool given = false;
+    bool given = false, scored = false;
     if constexpr (Mode == kSelGiven) given = depth == 0;
     if (m.last_move == pass && row_f(cn, pass) == 0.0f) {
       pick = pass;    // HACK of mcts.jl:119-126: look at the double pass first
@@ -583,9 +622,18 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
           total = w.reduce_sum_f(total);   // visit counts are integers: order-free and exact
         }
       }
+      float f = 0.f;
+      if (fpu) {
+        long long M = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) M += w.lane + 64 * r < A ? fpu_mass(cn[r], cp[r]) : 0ll;
+        f = fpu_value(V, cur == root, n_new, w_cur, tp, reduce_sum_i64(w, M));
+      }
+      scored = rule;
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         sc[r] = action_score_v(cn[r], cw[r], cp[r], tp, scale);
+        if (fpu && cn[r] == 0.0f) sc[r] = fpu_score(f, cp[r], scale);
         if constexpr (Forced) {
           if (depth == 0 && under_forced(V.forced_k, cn[r], cp[r], total)) sc[r] = kForcedScore;
         }
@@ -619,6 +667,8 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
 #pragma unroll
     for (int r = 0; r < R; ++r) { const int t = w.shfl(cc[r], pick & 63); if (r == (pick >> 6)) nx = t; }
     const float n_next = row_f(cn, pick);
+    if (scored) { levels++; unvisited += n_next == 0.0f; }
+    if (fpu) w_cur = row_f(cw, pick);
     if (nx < 0) nx = node_create_child(w, V, S, g, cur, pick, defer);
     if (nx < 0) break;   // pool exhausted: hand back the current node (flagged in the counters)
     np = &V.childN[ni * AP + pick];      // the child's own N lives in this row (slotN)
@@ -627,6 +677,10 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
     depth++;
   }
   if (w.leader()) G.sel = (int32_t)(sel + 1);
+  if (rule) {
+    w.count(&V.counters[CT_PUCT_LEVELS], (unsigned long long)levels);
+    w.count(&V.counters[CT_PUCT_UNVISITED], (unsigned long long)unvisited);
+  }
   w.sync();
   *plen_out = plen < V.maxd ? plen : V.maxd;
   return cur;
@@ -661,7 +715,9 @@ AGZ_FN int select_leaf(W& w, const View& V, Scratch& S, int g, int from, int* pl
   const int A = V.A, pass = V.P;
   const uint32_t move_key = (uint32_t)V.meta[node_index(V, g, G.root)].n;
   const uint32_t sel = (uint32_t)G.sel;
+  const bool rule = puct_rule_on(V), fpu = V.fpu_on != 0;
   int cur = from, depth = 0, plen = 0;
+  int levels = 0, unvisited = 0;                               // CT_PUCT_LEVELS / CT_PUCT_UNVISITED of this descent
   w.sync();
   for (;;) {
     const long ni = node_index(V, g, cur);
@@ -687,8 +743,15 @@ AGZ_FN int select_leaf(W& w, const View& V, Scratch& S, int g, int from, int* pl
         w.for_each(A, [&](int a) { total += V.childN[ni * V.AP + a]; });
         total = w.reduce_sum_f(total);   // visit counts are integers: order-free and exact
       }
+      float f = 0.f;
+      if (fpu) {
+        long long M = 0;
+        w.for_each(A, [&](int a) { M += fpu_mass(V.childN[ni * V.AP + a], V.childP[ni * V.AP + a]); });
+        f = fpu_value(V, cur == G.root, n_new, *slotW(V, g, cur), tp, reduce_sum_i64(w, M));
+      }
       auto score = [&](int a) {
         if (fr && under_forced(V.forced_k, V.childN[ni * V.AP + a], V.childP[ni * V.AP + a], total)) return kForcedScore;
+        if (fpu && V.childN[ni * V.AP + a] == 0.0f) return fpu_score(f, V.childP[ni * V.AP + a], scale);
         return action_score(V, ni, a, tp, scale);
       };
       double best = -1.0e300;
@@ -716,6 +779,7 @@ AGZ_FN int select_leaf(W& w, const View& V, Scratch& S, int g, int from, int* pl
       }
       if (cnt == 0) idx = pass;   // cannot happen: pass is always legal
       pick = idx;
+      if (rule) { levels++; unvisited += V.childN[ni * V.AP + pick] == 0.0f; }
       w.sync();
     }
     int nx = V.child[ni * V.AP + pick];
@@ -725,6 +789,10 @@ AGZ_FN int select_leaf(W& w, const View& V, Scratch& S, int g, int from, int* pl
     depth++;
   }
   if (w.leader()) G.sel = (int32_t)(sel + 1);
+  if (rule) {
+    w.count(&V.counters[CT_PUCT_LEVELS], (unsigned long long)levels);
+    w.count(&V.counters[CT_PUCT_UNVISITED], (unsigned long long)unvisited);
+  }
   w.sync();
   *plen_out = plen < V.maxd ? plen : V.maxd;
   return cur;
@@ -2396,8 +2464,18 @@ AGZ_FN void tree_op(W& w, const View& V, Scratch& S, const TreeArgs& T) {
     case TOP_SCORES: {
       const long ni = node_index(V, g, T.node);
       const NodeMeta m = V.meta[ni];
-      const double scale = puct_scale(V, *slotN(V, g, T.node));
-      w.for_each(V.A, [&](int a) { T.dout[a] = action_score(V, ni, a, (float)m.to_play, scale); });
+      const float n_s = *slotN(V, g, T.node), tp = (float)m.to_play;
+      const double scale = puct_scale(V, n_s);
+      float f = 0.f;
+      if (V.fpu_on) {
+        long long M = 0;
+        w.for_each(V.A, [&](int a) { M += fpu_mass(V.childN[ni * V.AP + a], V.childP[ni * V.AP + a]); });
+        f = fpu_value(V, T.node == G.root, n_s, *slotW(V, g, T.node), tp, reduce_sum_i64(w, M));
+      }
+      w.for_each(V.A, [&](int a) {
+        T.dout[a] = V.fpu_on && V.childN[ni * V.AP + a] == 0.0f ? fpu_score(f, V.childP[ni * V.AP + a], scale)
+                                                                : action_score(V, ni, a, tp, scale);
+      });
       w.sync();
     } break;
     case TOP_PENDING: {

@@ -113,7 +113,10 @@ enum Counter : int {
 // Gumbel root search on (View::gumbel_m > 0): searches begun (gumbel_begin) / halvings made (gumbel_halve).  The two
 // slots after CT_PRUNED_ROWS, named outside the enum: tests/test_forced_playouts.py pins the enum's last two names.
 constexpr int CT_GUMBEL_BEGUN = CT_COUNT, CT_GUMBEL_HALVED = CT_COUNT + 1;
-constexpr int kCounterSlots = CT_COUNT + 2;     // what View::counters holds
+// PUCT rule options on (puct_rule_on): tree levels a descent scored under the rule / those of them that picked an
+// unvisited child.  The two slots after the Gumbel ones, outside the enum for the same reason.
+constexpr int CT_PUCT_LEVELS = CT_COUNT + 2, CT_PUCT_UNVISITED = CT_COUNT + 3;
+constexpr int kCounterSlots = CT_COUNT + 4;     // what View::counters holds
 
 struct View {
   // dimensions
@@ -228,6 +231,13 @@ struct View {
   // analysis_finish also writes the root's children_as_pi row, the policy target self-play records
   const uint64_t* an_gid;             // [an_count]
   float* an_pi;                       // [rows][A]
+  // PUCT rule options (agz_search_set_puct; zero = off, the View{} of the host simulator and of fill_dims), for every
+  // level of every descent the engine makes: fpu_on -- an unvisited child's Q is its parent's value less
+  // fpu_r * sqrt(visited policy mass) (fpu_r_root at the game's root) instead of 0; c_base > 0 -- c_puct grows with the
+  // logarithm of the node's visits (include/agz.h states both operation for operation)
+  int32_t fpu_on;
+  double fpu_r, fpu_r_root;           // r, r_root
+  double c_base;
 };
 
 // option values -> View fields, for the engine's setters (which check the arguments first) and the host simulator's
@@ -243,6 +253,12 @@ inline void view_set_gumbel(View& V, int m, double c_visit, double c_scale) {
   V.gumbel_m = m > 0 ? m : 0;
   V.gumbel_cvisit = m > 0 ? c_visit : 0.0;
   V.gumbel_cscale = m > 0 ? c_scale : 0.0;
+}
+inline void view_set_puct(View& V, int fpu_on, double r, double r_root, double c_base) {
+  V.fpu_on = fpu_on ? 1 : 0;
+  V.fpu_r = fpu_on ? r : 0.0;
+  V.fpu_r_root = fpu_on ? r_root : 0.0;
+  V.c_base = c_base > 0.0 ? c_base : 0.0;
 }
 
 }  // namespace agz

@@ -23,7 +23,7 @@ using Random
 export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, train, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
-       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, reanalyze!, set_starts!, set_playout_cap!, playout_cap_counts, set_forced_playouts!, forced_counts, pruned_pi, set_gumbel!, gumbel_counts, gumbel_pi, extract_targets, value_targets, extract_value_targets, node_lines, most_visited_path, mvp_gg,
+       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, reanalyze!, set_starts!, set_playout_cap!, playout_cap_counts, set_forced_playouts!, forced_counts, pruned_pi, set_gumbel!, gumbel_counts, gumbel_pi, set_puct!, puct_counts, extract_targets, value_targets, extract_value_targets, node_lines, most_visited_path, mvp_gg,
        # the node-level surface test/test_mcts.jl:2-5 and test/test_mcts_player.jl:3-6 import
        MCTSNode, select_leaf, maybe_add_child!, add_virtual_loss!, revert_virtual_loss!,
        incorporate_results!, inject_noise!, child_action_score, child_Q, child_U, child_N, child_W,
@@ -328,13 +328,14 @@ mutable struct MCTSPlayer
   recent::Vector{PlayerMove}            # start.recent + every move played since: root.position.recent (board.jl:299)
 end
 function MCTSPlayer(env::GoEnv, network; num_readouts = 800, two_player_mode = false,
-                    resign_threshold = -0.9, seed = 0, symmetry = nothing)
+                    resign_threshold = -0.9, seed = 0, symmetry = nothing, fpu = nothing, c_base::Real = 0.0)
   τ = two_player_mode ? -1 : (env.N * env.N ÷ 12) ÷ 2 * 2
   th = network isa NeuralNet ? network.tower_height : 0
   e = Engine(board_size = env.N, tower_height = th, games = 1, num_readouts = num_readouts,
              parallel_readouts = 64, two_player_mode = two_player_mode,
              resign_threshold = resign_threshold, seed = seed, external_network = !(network isa NeuralNet))
   symmetry === nothing || set_symmetry!(e, symmetry)
+  apply_puct!(e, fpu, c_base)
   MCTSPlayer(env, network, num_readouts, two_player_mode, τ, Float32[], Vector{Float32}[], 0, "",
              resign_threshold, e, nothing, PlayerMove[])
 end
@@ -867,6 +868,26 @@ function gumbel_pi(e::Engine, g::Integer, node::Integer, c_visit::Real, c_scale:
   out
 end
 
+# PUCT rule options (ours; include/agz.h agz_search_set_puct), for every search the engine runs.  fpu = nothing (off: an
+# unvisited child's Q is 0), r, or (r, r_root): first-play urgency reduction -- an unvisited child's Q is its parent's
+# value less r * sqrt(policy mass of the visited children), r_root at the game's root; fpu = 0.0 is not off.
+# c_base > 0: c_puct grows by log((1 + N + c_base) / c_base) with the node's visits (AlphaZero: 19652); 0 is off.
+function set_puct!(e::Engine, fpu = nothing, c_base::Real = 0.0)
+  on = fpu === nothing ? 0 : 1
+  r, r_root = fpu === nothing ? (0.0, 0.0) : fpu isa Tuple ? (fpu[1], fpu[2]) : (fpu, fpu)
+  check(e, ccall((:agz_search_set_puct, libagz), Int32, (Ptr{Cvoid}, Int32, Float64, Float64, Float64), e.handle, on, r,
+                 r_root, c_base))
+end
+# (tree levels scored under an active rule, those of them that picked an unvisited child) since the later of
+# set_puct! and agz_selfplay_start
+function puct_counts(e::Engine)
+  out = zeros(UInt64, 2)
+  check(e, ccall((:agz_search_puct_counts, libagz), Int32, (Ptr{Cvoid}, Ptr{UInt64}), e.handle, out))
+  Int(out[1]), Int(out[2])
+end
+# the keywords fpu = / c_base = of selfplay, train, analyze, review, evaluate and MCTSPlayer: nothing asked, nothing set
+apply_puct!(e::Engine, fpu, c_base) = (fpu === nothing && c_base == 0) || set_puct!(e, fpu, c_base)
+
 # replay_position (board.jl:557-578) from a start position: the position before each move and the final one
 function replay_positions_from(start::Position, moves)
   positions = Position[]
@@ -882,7 +903,8 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
                   slots::Union{Nothing, Int} = nothing, seed = nothing, game_id_base = nothing, symmetry = nothing,
                   starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing,
                   forced_playouts = nothing, prune_targets::Bool = true,
-                  gumbel = nothing, gumbel_c_visit::Real = 50.0, gumbel_c_scale::Real = 1.0)
+                  gumbel = nothing, gumbel_c_visit::Real = 50.0, gumbel_c_scale::Real = 1.0,
+                  fpu = nothing, c_base::Real = 0.0)
   (gumbel !== nothing && gumbel != 0 && forced_playouts !== nothing && forced_playouts != 0) &&
     throw(ArgumentError("gumbel and forced_playouts are two rules for the same decision: ask for one"))
   G = games === nothing ? 1 : games
@@ -902,6 +924,7 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
   playout_cap === nothing || set_playout_cap!(e, playout_cap[1], playout_cap[2])      # (r, p)
   forced_playouts === nothing || set_forced_playouts!(e, forced_playouts, prune_targets)   # k
   gumbel === nothing || set_gumbel!(e, gumbel, gumbel_c_visit, gumbel_c_scale)             # m
+  apply_puct!(e, fpu, c_base)                                                              # the PUCT rule options
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, G))
   while ccall((:agz_records_count, libagz), Int64, (Ptr{Cvoid},), e.handle) < G
     check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 16))
@@ -943,7 +966,7 @@ end
 # AGZ_POOL_EXHAUSTED, AGZ_ASSERT_SOFTPICK) and nodes_used.
 function analyze(env::GoEnv, nn::NeuralNet, positions::Vector{Position}; num_readouts::Int = 800, seed = 0,
                  game_id_base = 0, slots::Union{Nothing, Int} = nothing, two_player_mode = false, symmetry = nothing,
-                 lines::Int = 0, pv_depth::Int = 16, pv_min_visits::Int = 1)
+                 lines::Int = 0, pv_depth::Int = 16, pv_min_visits::Int = 1, fpu = nothing, c_base::Real = 0.0)
   check_lines(lines, pv_depth, pv_min_visits)
   B, P, A = length(positions), env.N * env.N, env.action_space
   B == 0 && return NamedTuple[]
@@ -958,6 +981,7 @@ function analyze(env::GoEnv, nn::NeuralNet, positions::Vector{Position}; num_rea
              max_nodes_per_game = 2 * num_readouts + 256)
   copy_weights!(e, nn.engine)
   symmetry === nothing || set_symmetry!(e, symmetry)
+  apply_puct!(e, fpu, c_base)
   lines > 0 && check(e, ccall((:agz_analyze_set_lines, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Int32),
                               e.handle, lines, pv_depth, pv_min_visits))
   check(e, ccall((:agz_analyze_start, libagz), Int32, (Ptr{Cvoid}, Ptr{Int8}, Ptr{AgzPositionInfo}, Ptr{Int8}, Int64, UInt64),
@@ -1003,7 +1027,8 @@ end
 # the later ones of that game status AGZ_BAD_ARGUMENT.
 function review(env::GoEnv, nn::NeuralNet, games::Vector; num_readouts::Int = 800, starts = nothing,
                 two_player_mode = true, seed = 0, game_id_base = 0, slots::Union{Nothing, Int} = nothing,
-                symmetry = nothing, lines::Int = 0, pv_depth::Int = 16, pv_min_visits::Int = 1)
+                symmetry = nothing, lines::Int = 0, pv_depth::Int = 16, pv_min_visits::Int = 1, fpu = nothing,
+                c_base::Real = 0.0)
   check_lines(lines, pv_depth, pv_min_visits)
   G, P, A = length(games), env.N * env.N, env.action_space
   G == 0 && return Vector{NamedTuple}[]
@@ -1032,6 +1057,7 @@ function review(env::GoEnv, nn::NeuralNet, games::Vector; num_readouts::Int = 80
              num_readouts = num_readouts, seed = seed, two_player_mode = two_player_mode)
   copy_weights!(e, nn.engine)
   symmetry === nothing || set_symmetry!(e, symmetry)
+  apply_puct!(e, fpu, c_base)
   lines > 0 && check(e, ccall((:agz_analyze_set_lines, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Int32),
                               e.handle, lines, pv_depth, pv_min_visits))
   check(e, ccall((:agz_review_start, libagz), Int32,
@@ -1176,7 +1202,7 @@ set_precision!(e::Engine, p::Symbol) =      # :f32 (default, exact), :f16 (fp16 
 # final_score > 0, also for resigned games.
 function evaluate(env::GoEnv, black_net::NeuralNet, white_net::NeuralNet; num_games = 400, ro = 800,
                   verbose::Bool = false, seed = 0, pairs::Int = min(num_games, 512), symmetry = nothing,
-                  starts::Union{Nothing, Vector{Position}} = nothing)
+                  starts::Union{Nothing, Vector{Position}} = nothing, fpu = nothing, c_base::Real = 0.0)
   @assert black_net.tower_height == white_net.tower_height
   e = Engine(board_size = env.N, tower_height = black_net.tower_height, games = 2 * pairs, num_readouts = ro,
              seed = seed, record_capacity_games = num_games + 8, arena_mode = true)
@@ -1185,6 +1211,7 @@ function evaluate(env::GoEnv, black_net::NeuralNet, white_net::NeuralNet; num_ga
   copy_weights!(e, white_net.engine)
   check(e, ccall((:agz_net_select, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 0))
   symmetry === nothing || set_symmetry!(e, symmetry)
+  apply_puct!(e, fpu, c_base)                            # both players
   starts === nothing || set_starts!(e, env, starts)      # an opening suite: game g begins at starts[g % S + 1]
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, num_games))
   while ccall((:agz_records_count, libagz), Int64, (Ptr{Cvoid},), e.handle) < num_games
@@ -1337,7 +1364,8 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
                augment::Bool = false, callback::Function = println,
                starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing,
                forced_playouts = nothing, prune_targets::Bool = true,
-               gumbel = nothing, gumbel_c_visit::Real = 50.0, gumbel_c_scale::Real = 1.0, value_target = nothing)
+               gumbel = nothing, gumbel_c_visit::Real = 50.0, gumbel_c_scale::Real = 1.0, value_target = nothing,
+               fpu = nothing, c_base::Real = 0.0)
   (gumbel !== nothing && gumbel != 0 && forced_playouts !== nothing && forced_playouts != 0) &&
     throw(ArgumentError("gumbel and forced_playouts are two rules for the same decision: ask for one"))
   cur_nn = model === nothing ? NeuralNet(env; tower_height = tower_height) : model                       # train.jl:43
@@ -1361,6 +1389,7 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
   end
   forced_playouts === nothing || set_forced_playouts!(e, forced_playouts, prune_targets)   # k, as in selfplay
   gumbel === nothing || set_gumbel!(e, gumbel, gumbel_c_visit, gumbel_c_scale)             # m, as in selfplay
+  apply_puct!(e, fpu, c_base)                                                              # as in selfplay
   value_target === nothing || replay_set_value_target!(e, value_target[1], value_target[2])   # (alpha, lam): z of the batches
   check(e, ccall((:agz_selfplay_set_hold, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 1))
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, num_games))

@@ -699,6 +699,39 @@ agz_status agz_selfplay_forced_counts(agz_engine* e, int64_t out[2]);
 agz_status agz_selfplay_set_gumbel(agz_engine* e, int32_t m, double c_visit, double c_scale);
 /* out[0] = Gumbel searches begun, out[1] = halvings made, since agz_selfplay_start.  Synchronises. */
 agz_status agz_selfplay_gumbel_counts(agz_engine* e, int64_t out[2]);
+/* PUCT rule options (ours): first-play urgency (FPU) reduction as in KataGo / Leela Zero, and the c_puct
+ * growth of AlphaZero (2018).  The setting is (fpu_on, r = fpu_reduction, r_root = fpu_reduction_root, c_base); the
+ * default (0, 0, 0, 0) is off: the rule of mcts.jl:86-92, an unvisited child's Q = 0 and one constant c_puct.
+ * THE RULE.  Where a node s scores its children (rows N, W, P over the A actions): n = the node's own stored N at that
+ * moment (what the scale of mcts.jl:91 receives), N_s = n and W_s = the node's own stored W at that moment (virtual
+ * losses of other descents in flight included), tp = (float)to_play.
+ *   GROWTH (c_base > 0):   c     = c_puct + agz_log(((double)(1.0f + n) + c_base) / c_base)
+ *                          scale = c * (double)sqrtf(1.0f + n)           (c_base == 0: scale = c_puct * (double)sqrtf(1.0f + n))
+ *   FPU (fpu_on), for a child a whose row value N_a == 0.0f:
+ *     M   = sum over b < A with N_b > 0 of (int64)((double)P_b * 1073741824.0)      (integers: order-free and exact)
+ *     m   = (double)M * (1.0 / 1073741824.0)                                         (exact)
+ *     q_s = W_s / (1.0f + N_s);  qp = q_s * tp                                       (Float32)
+ *     f   = (float)((double)qp - rho * agz_sqrt(m)),  rho = r_root when s is the game's root, else r
+ *     score_a = (double)f + (scale * (double)P_a) / (double)1.0f
+ *   P_b is the row as stored: Dirichlet noise included at a noised root.  (fpu_on, 0, 0, .) is not off: an unvisited
+ *   child then has its parent's value.  A visited child's score keeps the arithmetic of mcts.jl:86-92 under `scale`.
+ * Everything else keeps its place and precedence: the pass-first rule of mcts.jl:119-126, the arg-max, the tie rule with
+ * its draw and key, the forced-playout score (it replaces scores of visited children only) and the given root action
+ * of the Gumbel root search.  The scale of the pruned policy target (agz_selfplay_set_forced_playouts) is `scale` too.
+ * WHERE.  Every level of every descent of every search the engine runs: self-play (full and fast searches), the arena
+ * (both players), analysis, review and reanalysis, and the single-tree calls agz_tree_select_leaf, agz_tree_search and
+ * agz_tree_search_select / _incorporate; agz_tree_node_scores reports the scores under the setting.
+ * No draw site is added and none moves; records, agz_game_header, agz_config and agz_stats do not change.
+ * Synchronises; the two counters of agz_search_puct_counts restart.  Refused (AGZ_BAD_ARGUMENT, the setting in force
+ * kept): fpu_on outside {0, 1}; a reduction outside [0, 4] or NaN; c_base neither 0 nor in [1, 1e9], or NaN; games of a
+ * run still being played (as agz_selfplay_set_playout_cap); between agz_tree_search_select and
+ * agz_tree_search_incorporate.  An arena_mode engine takes it. */
+agz_status agz_search_set_puct(agz_engine* e, int32_t fpu_on, double fpu_reduction, double fpu_reduction_root,
+                               double c_base);
+/* out[0] = tree levels that a descent scored under an active rule (pass-first and given root actions do not count),
+ * out[1] = those of them that picked an unvisited child, since the later of agz_search_set_puct and
+ * agz_selfplay_start.  Synchronises. */
+agz_status agz_search_puct_counts(agz_engine* e, uint64_t* out /* [2] */);
 agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out);
 /* out[B], child_N / child_W / prior [B][A] (the root's rows when the search ended); any of them may be NULL */
 agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N, float* child_W, float* prior);
