@@ -23,7 +23,7 @@ namespace agz {
 // ------------------------------------------------------------------ the wave primitives on gfx950
 
 struct HipWave {
-  static constexpr bool kRegisterRows = true;     // select_leaf_rows (agz_search.h)
+  static constexpr int kLanes = kWave;
   int lane;
   __device__ HipWave() : lane((int)threadIdx.x) {}
   __device__ explicit HipWave(int l) : lane(l) {}      // (a wave of a multi-wave workgroup: kernels that never call sync())
@@ -96,8 +96,6 @@ struct HipWave {
     return ((unsigned long long)hi << 32) | lo;
   }
 };
-
-constexpr int kPPMax = 368, kAPMax = 368, kMaxdMax = 528;
 
 #define AGZ_SCRATCH(S)                                                        \
   __shared__ int8_t s_sb[kPPMax];                                             \

@@ -11,7 +11,8 @@
 //
 // Discipline that makes the two agree: data-parallel work goes through w.for_each (pure per-index
 // bodies), every cross-lane flow through memory is separated by w.sync(), per-lane partials are
-// combined with w.reduce_*, and all other control flow is wave-uniform.
+// combined with w.reduce_*, and all other control flow is wave-uniform.  The descent keeps rows in registers across the
+// W::kLanes lanes (64; the simulator is a wave of one) and reads single elements by shuffle: both run that one form.
 //
 // Reference semantics restated here (file:line under /root/reference):
 //   select_leaf mcts.jl:108-138 | maybe_add_child! :140-147 | virtual loss :149-171 |
@@ -26,6 +27,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/agz_draws.h"
 #include "agz_state.h"
@@ -58,6 +60,39 @@
 #endif
 
 namespace agz {
+
+// the largest board the scratch is sized for (19x19): bounds on View::PP, AP and maxd
+constexpr int kPPMax = 368, kAPMax = 368, kMaxdMax = 528;
+
+// The widths R (row elements per lane of a 64-lane wave) that the register-row templates -- the descent and the lines
+// walk -- are instantiated at; f gets R as a std::integral_constant.  A row of n elements with no width of its own (4 or
+// 5 per lane, N = 14..17) takes the next one up: the templates mask what lies past the row's end.
+template <class F>
+AGZ_FN auto with_row_width(int n, F f) {
+  static_assert(6 * kWave >= kAPMax, "the widest instantiation covers the largest row");
+  switch ((n + kWave - 1) / kWave) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});     // 9x9
+    case 3: return f(std::integral_constant<int, 3>{});     // 13x13
+    default: return f(std::integral_constant<int, 6>{});    // 19x19, and N = 14..17 rounded up
+  }
+}
+
+// The width of a wave type: W::kLanes lanes (HipWave: 64; the host simulator: 1).  A wave type that states none is taken
+// as lane-serial, a wave of one lane.  That one lane is lane 0 and holds whole rows, so it reads an element out of its
+// own registers and is asked for neither w.lane nor w.shfl: wave_lane and wave_shfl are those two for any wave.
+template <class W, class = void>
+struct wave_lanes : std::integral_constant<int, 1> {};
+template <class W>
+struct wave_lanes<W, std::void_t<decltype(W::kLanes)>> : std::integral_constant<int, W::kLanes> {};
+template <class W>
+AGZ_FN int wave_lane(const W& w) {
+  if constexpr (wave_lanes<W>::value > 1) return w.lane; else return 0;
+}
+template <class W, class T>
+AGZ_FN T wave_shfl(const W& w, T v, int src) {
+  if constexpr (wave_lanes<W>::value > 1) return w.shfl(v, src); else return v;
+}
 
 struct Scratch {
   int8_t* sb;        // [PP] working board
@@ -468,13 +503,17 @@ AGZ_FN void game_expand(W& w, const View& V, Scratch& S, int g, int i) {
 
 // ------------------------------------------------------------------ PUCT and select_leaf
 
-// child_action_score[a] (mcts.jl:86-92): Float32 Q times to_play, plus Float64 U
-AGZ_FN double action_score(const View& V, long ni, int a, float to_play, double scale) {
-  const float denom = 1.0f + V.childN[ni * V.AP + a];
-  const float q = V.childW[ni * V.AP + a] / denom;
-  const float qs = q * to_play;
-  const double u = (scale * (double)V.childP[ni * V.AP + a]) / (double)denom;
-  return (double)qs + u;
+// child_Q[a] from the side to move (mcts.jl:86-92): Float32
+AGZ_FN float action_q(float n, float wv, float to_play) {
+  const float denom = 1.0f + n;
+  const float q = wv / denom;
+  return q * to_play;
+}
+// child_action_score[a] (mcts.jl:86-92) of a child's N, W and prior: Float32 Q times to_play, plus Float64 U
+AGZ_FN double action_score(float n, float wv, float p, float to_play, double scale) {
+  const float denom = 1.0f + n;
+  const double u = (scale * (double)p) / (double)denom;
+  return (double)action_q(n, wv, to_play) + u;
 }
 
 // c_base > 0 (agz_search_set_puct): c_puct grows with the logarithm of the node's visits
@@ -514,21 +553,17 @@ AGZ_FN double fpu_score(float f, float p, double scale) {
   const double u = (scale * (double)p) / (double)1.0f;
   return (double)f + u;
 }
+// the score of a child under the current rule: with the FPU on an unvisited child has f for its Q
+AGZ_FN double child_score(bool fpu, float f, float n, float wv, float p, float to_play, double scale) {
+  const double s = action_score(n, wv, p, to_play, scale);
+  return fpu && n == 0.0f ? fpu_score(f, p, scale) : s;
+}
 
 // k-th (0-based) set flag in ascending index order; every lane scans (LDS broadcast reads)
 AGZ_FN int kth_flag(const int8_t* flag, int n, int k) {
   for (int a = 0; a < n; ++a)
     if (flag[a]) { if (k == 0) return a; --k; }
   return -1;
-}
-
-// PUCT score from register operands: the arithmetic of action_score, operation for operation
-AGZ_FN double action_score_v(float n, float wv, float p, float to_play, double scale) {
-  const float denom = 1.0f + n;
-  const float q = wv / denom;
-  const float qs = q * to_play;
-  const double u = (scale * (double)p) / (double)denom;
-  return (double)qs + u;
 }
 
 // Forced playouts (View::forced_k = k > 0).  At the root level of a descent a legal child that has been
@@ -545,19 +580,23 @@ AGZ_FN bool under_forced(double k, float n, float p, float total) {
 // setting.  root_n = position.n of the root about to be searched.
 AGZ_FN bool forced_search(const View& V, const GameState& G, int root_n);
 
-// select_leaf for waves that keep a node's child rows in registers (W::kRegisterRows, the GPU): R = ceil(AP / 64)
-// row elements per lane.  The generic form below walks FOUR dependent global round trips per tree level (meta ->
-// the node's own N in its parent's row -> its child rows for the scores -> the chosen child's id); here everything
-// that depends only on the node id -- meta, N / W / P / child-id rows, the legal words -- is requested at once, the
-// node's own N comes along from the parent's row of the level above, and the chosen child's id and N come out of the
-// registers by shuffle: one round trip per level.  Same arithmetic, same tie-break draws: the tree is bit-identical.
+// select_leaf (mcts.jl:108-138), the one descent of the device and the host simulator.  A wave of W::kLanes lanes keeps
+// a node's child rows in registers, R >= ceil(AP / kLanes) elements a = lane + kLanes * r per lane; what lies past AP or
+// A is loaded from a clamped index and masked out of every sum, arg-max and flag.  Everything that depends only on the
+// node id -- meta, N / W / P / child-id rows, the legal words -- is requested at once, the node's own N comes along from
+// the parent's row of the level above, and the chosen child's id and N come out of the registers by shuffle: one memory
+// round trip per level.
 // Mode, the root level (depth 0) of the descent alone: kSelForced -- the descent starts at the root of a search under the
 // forced rule; kSelGiven -- the caller chose the root action (root_pick, the Gumbel root search); the pass-first rule
 // keeps its precedence, nothing is scored and no tie draw is made there.
 constexpr int kSelPlain = 0, kSelForced = 1, kSelGiven = 2;
 template <int R, int Mode, class W>
-AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer, int root_pick) {
+AGZ_FN int descend(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer, int root_pick) {
   constexpr bool Forced = Mode == kSelForced;
+  constexpr int L = wave_lanes<W>::value;
+  // element a >= 0 of a row sits in lane a % L, row a / L: unsigned, so that at L = 64 these are a & 63 and a >> 6
+  auto lane_of = [](int a) { return (int)((unsigned)a % (unsigned)L); };
+  auto row_of = [](int a) { return (int)((unsigned)a / (unsigned)L); };
   GameState& G = V.gs[g];
   const int A = V.A, AP = V.AP, pass = V.P;
   const uint32_t move_key = (uint32_t)V.meta[node_index(V, g, G.root)].n;
@@ -580,7 +619,7 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
     bool lg[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      const int a = w.lane + 64 * r;
+      const int a = wave_lane(w) + L * r;
       const bool in = a < AP;
       const long o = ni * AP + (in ? a : 0);
       cn[r] = V.childN[o];
@@ -598,7 +637,7 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
     auto row_f = [&](const float* v, int a) {              // element a of a row held across the lanes
       float x = 0.f;
 #pragma unroll
-      for (int r = 0; r < R; ++r) { const float t = w.shfl(v[r], a & 63); if (r == (a >> 6)) x = t; }
+      for (int r = 0; r < R; ++r) { const float t = wave_shfl(w, v[r], lane_of(a)); if (r == row_of(a)) x = t; }
       return x;
     };
     int pick;
@@ -618,7 +657,7 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
       if constexpr (Forced) {
         if (depth == 0) {
 #pragma unroll
-          for (int r = 0; r < R; ++r) total += w.lane + 64 * r < A ? cn[r] : 0.f;
+          for (int r = 0; r < R; ++r) total += wave_lane(w) + L * r < A ? cn[r] : 0.f;
           total = w.reduce_sum_f(total);   // visit counts are integers: order-free and exact
         }
       }
@@ -626,14 +665,13 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
       if (fpu) {
         long long M = 0;
 #pragma unroll
-        for (int r = 0; r < R; ++r) M += w.lane + 64 * r < A ? fpu_mass(cn[r], cp[r]) : 0ll;
+        for (int r = 0; r < R; ++r) M += wave_lane(w) + L * r < A ? fpu_mass(cn[r], cp[r]) : 0ll;
         f = fpu_value(V, cur == root, n_new, w_cur, tp, reduce_sum_i64(w, M));
       }
       scored = rule;
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        sc[r] = action_score_v(cn[r], cw[r], cp[r], tp, scale);
-        if (fpu && cn[r] == 0.0f) sc[r] = fpu_score(f, cp[r], scale);
+        sc[r] = child_score(fpu, f, cn[r], cw[r], cp[r], tp, scale);
         if constexpr (Forced) {
           if (depth == 0 && under_forced(V.forced_k, cn[r], cp[r], total)) sc[r] = kForcedScore;
         }
@@ -646,7 +684,7 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
       int cnt = 0, idx = kIntMax;
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        const int a = w.lane + 64 * r;
+        const int a = wave_lane(w) + L * r;
         const bool f = lg[r] && sc[r] == best;
         if (a < AP) S.flag[a] = f;
         if (f) { cnt++; idx = a < idx ? a : idx; }
@@ -665,7 +703,7 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
     }
     int nx = -1;
 #pragma unroll
-    for (int r = 0; r < R; ++r) { const int t = w.shfl(cc[r], pick & 63); if (r == (pick >> 6)) nx = t; }
+    for (int r = 0; r < R; ++r) { const int t = wave_shfl(w, cc[r], lane_of(pick)); if (r == row_of(pick)) nx = t; }
     const float n_next = row_f(cn, pick);
     if (scored) { levels++; unvisited += n_next == 0.0f; }
     if (fpu) w_cur = row_f(cw, pick);
@@ -686,18 +724,17 @@ AGZ_FN int select_leaf_rows(W& w, const View& V, Scratch& S, int g, int from, in
   return cur;
 }
 
-// select_leaf_rows<R, Mode> for the board's row width R = ceil(AP / 64); kNoRowsForm when there is no instantiation
-// for it (a leaf is never negative)
-constexpr int kNoRowsForm = -2;
+// descend<R, Mode> at the wave's row width for this board: a 64-lane wave takes one of the instantiated widths, any
+// other wave (the host simulator's single lane) the one width that covers the largest board
 template <int Mode, class W>
-AGZ_FN int select_leaf_rows_of(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer,
-                               int root_pick) {
-  switch ((V.AP + 63) >> 6) {
-    case 1: return select_leaf_rows<1, Mode>(w, V, S, g, from, plen_out, defer, root_pick);
-    case 2: return select_leaf_rows<2, Mode>(w, V, S, g, from, plen_out, defer, root_pick);     // 9x9
-    case 3: return select_leaf_rows<3, Mode>(w, V, S, g, from, plen_out, defer, root_pick);     // 13x13
-    case 6: return select_leaf_rows<6, Mode>(w, V, S, g, from, plen_out, defer, root_pick);     // 19x19
-    default: return kNoRowsForm;
+AGZ_FN int descend_of(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer, int root_pick) {
+  constexpr int L = wave_lanes<W>::value;
+  if constexpr (L == kWave) {
+    return with_row_width(V.AP, [&](auto r) {
+      return descend<decltype(r)::value, Mode>(w, V, S, g, from, plen_out, defer, root_pick);
+    });
+  } else {
+    return descend<(kAPMax + L - 1) / L, Mode>(w, V, S, g, from, plen_out, defer, root_pick);
   }
 }
 
@@ -705,97 +742,9 @@ AGZ_FN int select_leaf_rows_of(W& w, const View& V, Scratch& S, int g, int from,
 template <class W>
 AGZ_FN int select_leaf(W& w, const View& V, Scratch& S, int g, int from, int* plen_out, bool defer = false,
                        bool forced = false, int root_pick = -1) {
-  if constexpr (W::kRegisterRows) {
-    const int leaf = root_pick >= 0 ? select_leaf_rows_of<kSelGiven>(w, V, S, g, from, plen_out, defer, root_pick)
-                     : forced       ? select_leaf_rows_of<kSelForced>(w, V, S, g, from, plen_out, defer, -1)
-                                    : select_leaf_rows_of<kSelPlain>(w, V, S, g, from, plen_out, defer, -1);
-    if (leaf != kNoRowsForm) return leaf;
-  }
-  GameState& G = V.gs[g];
-  const int A = V.A, pass = V.P;
-  const uint32_t move_key = (uint32_t)V.meta[node_index(V, g, G.root)].n;
-  const uint32_t sel = (uint32_t)G.sel;
-  const bool rule = puct_rule_on(V), fpu = V.fpu_on != 0;
-  int cur = from, depth = 0, plen = 0;
-  int levels = 0, unvisited = 0;                               // CT_PUCT_LEVELS / CT_PUCT_UNVISITED of this descent
-  w.sync();
-  for (;;) {
-    const long ni = node_index(V, g, cur);
-    const NodeMeta m = V.meta[ni];
-    float* np = slotN(V, g, cur);
-    const float n_new = *np + 1.0f;
-    w.sync();
-    if (w.leader()) { *np = n_new; if (plen < V.maxd) S.path[plen] = cur; }
-    plen++;
-    w.sync();
-    if (!(m.flags & NF_EXPANDED)) break;
-    int pick;
-    if (m.last_move == pass && V.childN[ni * V.AP + pass] == 0.0f) {
-      pick = pass;    // HACK of mcts.jl:119-126: look at the double pass first
-    } else if (root_pick >= 0 && depth == 0) {
-      pick = root_pick;   // the Gumbel root search chose the root action
-    } else {
-      const double scale = puct_scale(V, n_new);
-      const float tp = (float)m.to_play;
-      const bool fr = forced && depth == 0;         // the forced rule: the root level only
-      float total = 0.f;
-      if (fr) {
-        w.for_each(A, [&](int a) { total += V.childN[ni * V.AP + a]; });
-        total = w.reduce_sum_f(total);   // visit counts are integers: order-free and exact
-      }
-      float f = 0.f;
-      if (fpu) {
-        long long M = 0;
-        w.for_each(A, [&](int a) { M += fpu_mass(V.childN[ni * V.AP + a], V.childP[ni * V.AP + a]); });
-        f = fpu_value(V, cur == G.root, n_new, *slotW(V, g, cur), tp, reduce_sum_i64(w, M));
-      }
-      auto score = [&](int a) {
-        if (fr && under_forced(V.forced_k, V.childN[ni * V.AP + a], V.childP[ni * V.AP + a], total)) return kForcedScore;
-        if (fpu && V.childN[ni * V.AP + a] == 0.0f) return fpu_score(f, V.childP[ni * V.AP + a], scale);
-        return action_score(V, ni, a, tp, scale);
-      };
-      double best = -1.0e300;
-      bool have = false;
-      w.for_each(A, [&](int a) {
-        if (!legal_bit(V, ni, a)) return;
-        const double s = score(a);
-        if (!have || s > best) { best = s; have = true; }
-      });
-      best = w.reduce_max(have ? best : -1.0e300);
-      if (fr && best == kForcedScore) w.count(&V.counters[CT_FORCED_SEL], 1);
-      int cnt = 0, idx = kIntMax;
-      w.for_each(V.AP, [&](int a) {
-        const bool f = a < A && legal_bit(V, ni, a) && score(a) == best;
-        S.flag[a] = f;
-        if (f) { cnt++; idx = a < idx ? a : idx; }
-      });
-      cnt = w.reduce_sum(cnt);
-      idx = w.reduce_min(idx);
-      w.sync();
-      if (cnt > 1) {
-        const uint64_t bits = agz_draw_u64(V.seed, G.game_id, move_key, AGZ_SITE_PUCT_TIE,
-                                           (uint64_t)sel * 1024u + (uint64_t)depth);
-        idx = kth_flag(S.flag, A, (int)agz_index(bits, (uint32_t)cnt));
-      }
-      if (cnt == 0) idx = pass;   // cannot happen: pass is always legal
-      pick = idx;
-      if (rule) { levels++; unvisited += V.childN[ni * V.AP + pick] == 0.0f; }
-      w.sync();
-    }
-    int nx = V.child[ni * V.AP + pick];
-    if (nx < 0) nx = node_create_child(w, V, S, g, cur, pick, defer);
-    if (nx < 0) break;   // pool exhausted: hand back the current node (flagged in the counters)
-    cur = nx;
-    depth++;
-  }
-  if (w.leader()) G.sel = (int32_t)(sel + 1);
-  if (rule) {
-    w.count(&V.counters[CT_PUCT_LEVELS], (unsigned long long)levels);
-    w.count(&V.counters[CT_PUCT_UNVISITED], (unsigned long long)unvisited);
-  }
-  w.sync();
-  *plen_out = plen < V.maxd ? plen : V.maxd;
-  return cur;
+  return root_pick >= 0 ? descend_of<kSelGiven>(w, V, S, g, from, plen_out, defer, root_pick)
+         : forced       ? descend_of<kSelForced>(w, V, S, g, from, plen_out, defer, -1)
+                        : descend_of<kSelPlain>(w, V, S, g, from, plen_out, defer, -1);
 }
 
 // walk parents from `node` up to and including `up_to` (or the root); path[0] = topmost
@@ -922,7 +871,7 @@ AGZ_FN void children_as_pi(W& w, const View& V, Scratch& S, long ni, bool squash
 // under scale = puct_scale(rootN).  Every other visited child a keeps
 //   N'_a = min(N_a, max(N_a - sqrt(k P_a T), N_min, 0)),   N_min = scale P_a / (S* - q_a) - 1  (N_a when S* <= q_a),
 // the visits at which its score would still not pass S*, and none at all when what is left of a reduced child is <= 1.
-// All f64 but q_a, which is action_score's f32.  The row is N' (squash: N'^0.98) over its f64 sum in ascending index
+// All f64 but q_a, which is action_q's f32.  The row is N' (squash: N'^0.98) over its f64 sum in ascending index
 // order, narrowed to f32 last -- for an unchanged row bit for bit children_as_pi's.  Returns whether some N'_a < N_a.
 template <class W>
 AGZ_FN bool pruned_pi(W& w, const View& V, Scratch& S, long ni, float rootN, bool squash, float* out) {
@@ -937,7 +886,9 @@ AGZ_FN bool pruned_pi(W& w, const View& V, Scratch& S, long ni, float rootN, boo
   cs = w.reduce_min(cs);
   const float tp = (float)V.meta[ni].to_play;
   const double scale = puct_scale(V, rootN);
-  const double s_star = action_score(V, ni, cs, tp, scale);
+  const float* cW = V.childW + ni * V.AP;
+  const float* cP = V.childP + ni * V.AP;
+  const double s_star = action_score(cN[cs], cW[cs], cP[cs], tp, scale);
   const double k = V.forced_k;
   bool changed = false;
   w.sync();
@@ -945,12 +896,9 @@ AGZ_FN bool pruned_pi(W& w, const View& V, Scratch& S, long ni, float rootN, boo
     const float n = cN[a];
     double keep = (double)n;
     if (a != cs && n > 0.0f) {
-      const double p = (double)V.childP[ni * V.AP + a];
+      const double p = (double)cP[a];
       const double nf = sqrt((k * p) * (double)total);
-      const float denom = 1.0f + n;
-      const float q = V.childW[ni * V.AP + a] / denom;
-      const float qs = q * tp;
-      const double gap = s_star - (double)qs;
+      const double gap = s_star - (double)action_q(n, cW[a], tp);
       const double n_min = gap <= 0.0 ? (double)n : (scale * p) / gap - 1.0;
       double m = (double)n - nf;
       m = n_min > m ? n_min : m;
@@ -1938,12 +1886,9 @@ AGZ_FN void node_lines_rows(W& w, const View& V, Scratch& S, int g, int node, in
 template <class W>
 AGZ_FN void node_lines(W& w, const View& V, Scratch& S, int g, int node, int K, int D, int min_visits, agz_line* out,
                        int16_t* pv, float* pv_N) {
-  switch ((V.A + kWave - 1) / kWave) {
-    case 1: node_lines_rows<1>(w, V, S, g, node, K, D, min_visits, out, pv, pv_N); break;
-    case 2: node_lines_rows<2>(w, V, S, g, node, K, D, min_visits, out, pv, pv_N); break;     // 9x9
-    case 3: node_lines_rows<3>(w, V, S, g, node, K, D, min_visits, out, pv, pv_N); break;     // 13x13
-    default: node_lines_rows<6>(w, V, S, g, node, K, D, min_visits, out, pv, pv_N);           // 19x19 (A <= 384)
-  }
+  with_row_width(V.A, [&](auto r) {
+    node_lines_rows<decltype(r)::value>(w, V, S, g, node, K, D, min_visits, out, pv, pv_N);
+  });
 }
 
 // ---------------------------------------------------------------- batched analysis ----
@@ -2473,8 +2418,8 @@ AGZ_FN void tree_op(W& w, const View& V, Scratch& S, const TreeArgs& T) {
         f = fpu_value(V, T.node == G.root, n_s, *slotW(V, g, T.node), tp, reduce_sum_i64(w, M));
       }
       w.for_each(V.A, [&](int a) {
-        T.dout[a] = V.fpu_on && V.childN[ni * V.AP + a] == 0.0f ? fpu_score(f, V.childP[ni * V.AP + a], scale)
-                                                                : action_score(V, ni, a, tp, scale);
+        const long o = ni * V.AP + a;
+        T.dout[a] = child_score(V.fpu_on != 0, f, V.childN[o], V.childW[o], V.childP[o], tp, scale);
       });
       w.sync();
     } break;

@@ -4,9 +4,11 @@
 // instantiates them with agz::HipWave inside HIP kernels (agz_engine.hip).  This file
 // instantiates the very same source with a lane-serial SimWave so that, in a container without
 // a GPU, the tree / rules / lifecycle logic can be diffed bit-for-bit against the CPU oracle
-// (tests/test_hostsim_*.py).  It is built into tests/hostsim/libhostsim.so, is loaded only by
-// tests, and is never linked into or loaded by libagz.so.  It contains no network: pi/v always
-// come from the caller.
+// (tests/test_hostsim_*.py).  That includes select_leaf: there is one descent, the register-row
+// form the kernels run, and SimWave runs it as a wave of one lane (kLanes = 1, which needs no
+// shuffle) at the one row width that covers the largest board.  It is built into
+// tests/hostsim/libhostsim.so, is loaded only by tests, and is never linked into or loaded by
+// libagz.so.  It contains no network: pi/v always come from the caller.
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -17,7 +19,7 @@
 namespace {
 
 struct SimWave {
-  static constexpr bool kRegisterRows = false;    // the generic select_leaf (agz_search.h)
+  static constexpr int kLanes = 1;                // a wave of one lane: the descent keeps a whole row in that lane
   template <class F>
   void for_each(int n, F f) const { for (int i = 0; i < n; ++i) f(i); }
   void sync() const {}

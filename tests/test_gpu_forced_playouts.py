@@ -4,7 +4,7 @@ DESIGN.md §5i).
 Every self-play game must be, bit for bit, the twin's game (tests/selfplay_twin.py: the reference's loop with the forced
 root descent in its full searches and the pruned target in their pi rows) on the engine's own forward -- under the
 playout cap, from a table of starts, with drawn symmetries.  The single-tree calls reach the rule with hand-made rows at
-the four register-row widths of the descent.  Off is the engine that never made the call, byte for byte; analysis never
+the four register-row widths of the descent and at the two boards the widest one runs rounded up.  Off is the engine that never made the call, byte for byte; analysis never
 forces; train(..., forced_playouts=...) plays the twin's games on the weights of each round."""
 import numpy as np
 import pytest
@@ -113,10 +113,11 @@ def set_rows(eng, N, at, rootN, n):
     return root, rows
 
 
-@pytest.mark.parametrize("N", [5, 9, 13, 19])
+@pytest.mark.parametrize("N", [5, 9, 13, 15, 17, 19])
 def test_single_tree_known_answers(N):
-    """N = 5, 9, 13, 19: select_leaf_rows<1|2|3|6>.  The under-forced child sits at action A - 2 (the last point) and,
-    separately, at the pass: the last register row and its lane mapping"""
+    """N = 5, 9, 13, 19: the descent at its row widths 1, 2, 3, 6; N = 15, 17 (4 and 5 row elements per lane): the
+    width 6 rounded up, whose last rows lie past AP.  The under-forced child sits at action A - 2 (the last point) and,
+    separately, at the pass: the last register row in use and its lane mapping"""
     A = N * N + 1
     tau = ((N * N // 12) // 2) * 2
     eng = ag.Engine(board_size=N, tower_height=1, games=1, num_readouts=8, max_nodes_per_game=64, c_puct=1.0, seed=1)

@@ -3,9 +3,9 @@
 Every self-play game must be, bit for bit, the twin's game (tests/selfplay_twin.py: the reference's loop with Gumbel-top-k
 candidates, Sequential Halving, the best-s move and the softmax(logit + sigma(q)) row in its full searches) on the
 engine's own forward -- with the playout cap on and off, from a table of starts, with drawn symmetries.  The
-single-tree row call is held to the worked example at the four register-row widths.  Off is the engine that never made
-the call, byte for byte; every refusal; analysis is unchanged; train(..., gumbel=...) plays the twin's games on the
-weights of each round."""
+single-tree row call is held to the worked example at the four register-row widths and at the two boards the widest
+one runs rounded up.  Off is the engine that never made the call, byte for byte; every refusal; analysis is unchanged;
+train(..., gumbel=...) plays the twin's games on the weights of each round."""
 import numpy as np
 import pytest
 
@@ -118,10 +118,11 @@ def set_rows(eng, N, at, to_play=1, board=None):
     return root, rows
 
 
-@pytest.mark.parametrize("N", [5, 9, 13, 19])
+@pytest.mark.parametrize("N", [5, 9, 13, 15, 17, 19])
 def test_single_tree_worked_row(N):
-    """N = 5, 9, 13, 19: row widths 1, 2, 3, 6.  The example's a0 (the largest entry) and a5 (the unvisited child) sit
-    at action A - 2 (the last point) and at the pass, and the other way round"""
+    """N = 5, 9, 13, 19: row widths 1, 2, 3, 6; N = 15, 17: 4 and 5 row elements per lane, run at width 6.  The example's
+    a0 (the largest entry) and a5 (the unvisited child) sit at action A - 2 (the last point) and at the pass, and the
+    other way round"""
     A = N * N + 1
     eng = ag.Engine(board_size=N, tower_height=1, games=1, num_readouts=8, max_nodes_per_game=64, c_puct=1.0, seed=1)
     eng.init_synthetic(0)

@@ -1,5 +1,6 @@
 """PUCT rule options on the device (agz_search_set_puct): the scores of searched trees against the
-numpy restatement and whole trees against the host simulator at the four register-row widths of select_leaf_rows;
+numpy restatement and whole trees against the host simulator at the four register-row widths of the descent and at the
+two boards (15x15, 17x17: 4 and 5 row elements per lane) that the widest one runs, rounded up;
 self-play games with every other search option against the simulator, counters included; analyze, review and evaluate
 under the rule against their single-tree / per-game forms; off is the engine that never made the call; every refusal
 keeps the setting in force.  The simulator runs on the engine's own forward.  Tower 1 everywhere."""
@@ -23,7 +24,7 @@ BOTH = (1, 0.2, 0.05, 19652.0)
 FPU, CB = (0.2, 0.05), 19652.0
 BAD_ARGUMENT = ag._lib.BAD_ARGUMENT
 F_N, F_W, F_P = ag._lib.F_CHILD_N, ag._lib.F_CHILD_W, ag._lib.F_CHILD_PRIOR
-BOARDS = [5, 9, 13, 19]          # register-row widths R = 1, 2, 3, 6
+BOARDS = [5, 9, 13, 15, 17, 19]  # register-row widths R = 1, 2, 3, 6; 15 and 17 (4 and 5 per lane) are run by R = 6
 
 
 def forward_engine(N, peaked=False):
@@ -127,7 +128,7 @@ def tree_case(N, readouts, external):
     sim.close()
 
 
-@pytest.mark.parametrize("N,readouts", [(5, 64), (9, 64), (13, 24), (19, 24)])
+@pytest.mark.parametrize("N,readouts", [(5, 64), (9, 64), (13, 24), (15, 24), (17, 24), (19, 24)])
 def test_trees_equal_the_simulator(N, readouts):
     tree_case(N, readouts, external=False)
 
