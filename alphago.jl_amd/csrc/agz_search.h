@@ -42,16 +42,19 @@
 #ifdef AGZ_TIMING_EXPERIMENTS
 #define AGZ_STAMP_BEGIN(w) unsigned long long agz_t_prev = (w).clock()
 #define AGZ_STAMP_BEGIN_AGAIN(w) agz_t_prev = (w).clock()
-#define AGZ_STAMP(w, V, slot)                                   \
+#define AGZ_STAMP_TO(w, V, slot, t)                             \
   do {                                                          \
     const unsigned long long agz_t_now = (w).clock();           \
-    (w).count(&(V).counters[slot], agz_t_now - agz_t_prev);      \
-    agz_t_prev = agz_t_now;                                     \
+    (w).count(&(V).counters[slot], agz_t_now - (t));             \
+    (t) = agz_t_now;                                            \
   } while (0)
+#define AGZ_STAMP(w, V, slot) AGZ_STAMP_TO(w, V, slot, agz_t_prev)
+#define AGZ_STAMP_AT(w, V, slot, clk) do { if (clk) AGZ_STAMP_TO(w, V, slot, *(clk)); } while (0)   // a caller's clock, if any
 #else
 #define AGZ_STAMP_BEGIN(w) unsigned long long agz_t_prev = 0
 #define AGZ_STAMP_BEGIN_AGAIN(w) (void)agz_t_prev
 #define AGZ_STAMP(w, V, slot) (void)agz_t_prev
+#define AGZ_STAMP_AT(w, V, slot, clk) (void)(clk)
 #endif
 
 
@@ -408,6 +411,13 @@ template <class W>
 AGZ_FN void load_board(W& w, const View& V, Scratch& S, long ni) {
   w.for_each(V.P, [&](int p) { S.sb[p] = V.board[ni * V.PP + p]; });
   w.sync();
+}
+
+// The Tromp-Taylor score of `node`'s board under the game's komi; result_of gives its sign (`result`, board.jl:535-545)
+template <class W>
+AGZ_FN float position_score(W& w, const View& V, Scratch& S, int g, int node) {
+  load_board(w, V, S, node_index(V, g, node));
+  return area_score(w, V, S, V.gs[g].komi);
 }
 
 // Initialise node `id` from the board currently in S.sb (rows zeroed, legal mask for `tp`).
@@ -1417,13 +1427,94 @@ AGZ_FN void gumbel_pi(W& w, const View& V, Scratch& S, long ri, float* out) {
   w.sync();
 }
 
+// ------------------------------------------------------------------ the player's methods, once for every driver
+// MCTSPlayer's play_move!, should_resign, suggest_move and is_done (mcts_play.jl:26-50, :124, :144-151, :120): self-play
+// (game_*), the evaluate() arena (arena_*), analysis / review (analysis_* / review_*) and tree_op are loops over these.
+
+// Q(root) (mcts.jl:96-102 on the DummyNode entries): Float32
+AGZ_FN float root_q(const GameState& G) { return G.rootW / (1.0f + G.rootN); }
+
+// should_resign: Q_perspective(root) < resign_threshold (mcts_play.jl:124) -- the Float32 Q from the side to move,
+// widened for the comparison with the Float64 threshold
+AGZ_FN bool should_resign(const View& V, int g) {
+  const GameState& G = V.gs[g];
+  const float qp = root_q(G) * (float)V.meta[node_index(V, g, G.root)].to_play;
+  return (double)qp < G.resign_threshold;
+}
+
+// suggest_move's budget (mcts_play.jl:145-146): `budget` more visits of the root, and the slot searches
+template <class W>
+AGZ_FN void search_budget(W& w, GameState& G, int budget) {
+  if (w.leader()) { G.target = G.rootN + (float)budget; G.phase = G_SEARCH; }
+}
+
 // Begin the search of self-play game g's root `node`: Dirichlet noise (selfplay.jl:23) unless the search is fast or a
 // Gumbel search, which gets none, and the budget: R more root visits, cap_fast for a fast search.
 template <class W>
 AGZ_FN void search_begin(W& w, const View& V, Scratch& S, int g, int node, bool full) {
-  GameState& G = V.gs[g];
   if (full && V.gumbel_m <= 0) inject_noise(w, V, S, g, node);
-  if (w.leader()) G.target = G.rootN + (float)(full ? V.R : V.cap_fast);
+  search_budget(w, V.gs[g], full ? V.R : V.cap_fast);
+}
+
+// Is the search of slot g over: its budget spent, or the pool full and the game able to move early?  Sets G.stalled,
+// what agz_stats.stalled_games / agz_slot_status report: the pool is full and the slot cannot move (AGZ_POOL_STALL: it
+// waits for agz_slot_abandon).  (The arena asks in game_post and looks at the target alone: it never moves early.)
+template <class W>
+AGZ_FN bool search_over(W& w, const View& V, int g) {
+  GameState& G = V.gs[g];
+  const bool full = G.err == AGZ_POOL_EXHAUSTED;
+  const bool over = !(G.rootN < G.target) || pool_full_can_move(w, V, g);
+  if (w.leader()) G.stalled = full && !over;
+  w.sync();
+  return over;
+}
+
+// the pi row a ply's record gets (play_move): none; all zero (a fast search, the arena); children_as_pi of the visits;
+// pruned_pi (counts CT_PRUNED_ROWS where pruning changed the row); gumbel_pi
+enum PiRow : int { kPiNone = 0, kPiZero, kPiVisits, kPiPruned, kPiGumbel };
+
+// play_move!(player, a) (mcts_play.jl:26-50), in the reference's order: record the ply -- the pi row `kind` at index
+// G.move_count (length(searches_pi)), with `qs` the move and q at index G.nqs (length(qs)) -- then find or create the
+// root's child for `a`, re-root on it (the dropped siblings go to the garbage stack) and advance move_count with `plies`,
+// nqs with `qs`.  Returns the child, or what node_create_child returned (-2 too for an action out of range, before
+// anything is written).  A failed play leaves both counts where they were, so the row it stored lies past the end of the
+// record (the reference's push!, catch, pop!) until the slot's next play overwrites it; what follows is the caller's.
+// clk: the phase clock of self-play's move phase (timing builds).
+template <class W>
+AGZ_FN int play_move(W& w, const View& V, Scratch& S, int g, int a, float q, int kind, bool plies, bool qs,
+                     unsigned long long* clk = nullptr) {
+  GameState& G = V.gs[g];
+  if (a < 0 || a >= V.A) return -2;
+  const int root = G.root, mgl = V.max_game_length;
+  const long ri = node_index(V, g, root);
+  const int k = G.move_count, kq = G.nqs;
+  if (kind != kPiNone && k < mgl) {
+    float* row = V.rec_pi + ((long)g * mgl + k) * V.A;
+    const bool squash = V.meta[ri].n <= V.tau;
+    if (kind == kPiZero) {
+      w.for_each(V.A, [&](int i) { row[i] = 0.f; });
+    } else if (kind == kPiGumbel) {
+      gumbel_pi(w, V, S, ri, row);
+    } else if (kind == kPiPruned) {                          // the forced playouts do not belong in the target
+      if (pruned_pi(w, V, S, ri, G.rootN, squash, row)) w.count(&V.counters[CT_PRUNED_ROWS], 1);
+    } else {
+      children_as_pi(w, V, S, ri, squash, row);
+    }
+  }
+  if (qs && kq < mgl && w.leader()) {
+    V.rec_moves[(long)g * mgl + kq] = (int16_t)a;
+    V.rec_q[(long)g * mgl + kq] = q;
+  }
+  w.sync();
+  AGZ_STAMP_AT(w, V, CT_T_PICK, clk);
+  int child = V.child[ri * V.AP + a];
+  if (child < 0) child = node_create_child(w, V, S, g, root, a);
+  if (child < 0) return child;
+  AGZ_STAMP_AT(w, V, CT_T_CHILD, clk);
+  reroot(w, V, S, g, a, child);
+  if (w.leader()) { if (plies) G.move_count = k + 1; if (qs) G.nqs = kq + 1; }
+  w.sync();
+  return child;
 }
 
 // The selfplay.jl:22-43 loop body between two readout phases, for a game whose budget is spent:
@@ -1431,12 +1522,7 @@ AGZ_FN void search_begin(W& w, const View& V, Scratch& S, int g, int node, bool 
 template <class W>
 AGZ_FN void game_move_phase(W& w, const View& V, Scratch& S, int g) {
   GameState& G = V.gs[g];
-  const int root = G.root;
-  const long ri = node_index(V, g, root);
-  const NodeMeta rm = V.meta[ri];
-  // should_resign: Q_perspective(root) < resign_threshold (mcts_play.jl:124)
-  const float q = G.rootW / (1.0f + G.rootN);
-  const float qp = q * (float)rm.to_play;
+  const NodeMeta rm = V.meta[node_index(V, g, G.root)];
   w.count_max(&V.counters[CT_PEAK_NODES], (unsigned long long)G.nodes_used);
   const bool early = G.rootN < G.target;          // only game_pre's full-pool rule sends a game here before its budget is spent
   if (early) {
@@ -1444,10 +1530,7 @@ AGZ_FN void game_move_phase(W& w, const View& V, Scratch& S, int g) {
     if (w.leader()) { G.short_searches = G.short_searches + 1; G.err = 0; }
     w.sync();
   }
-  if ((double)qp < G.resign_threshold) {
-    game_finish(w, V, S, g, -rm.to_play, 1, 0.f);
-    return;
-  }
+  if (should_resign(V, g)) { game_finish(w, V, S, g, -rm.to_play, 1, 0.f); return; }
   AGZ_STAMP_BEGIN(w);
   // a fast search (playout cap) leaves no policy target: its row is all zero
   const bool fast = !full_search(V, G, rm.n);
@@ -1458,42 +1541,17 @@ AGZ_FN void game_move_phase(W& w, const View& V, Scratch& S, int g) {
   } else if (pick_move(w, V, S, g, &a) != AGZ_OK) {
     a = V.P;  // the reference dies on its assertion; we pass
   }
-  // play_move!(player, c): record pi and Q, then re-root (mcts_play.jl:26-50)
-  const int k = G.move_count;
-  if (k < V.max_game_length) {
-    float* row = V.rec_pi + ((long)g * V.max_game_length + k) * V.A;
-    if (fast) {
-      w.for_each(V.A, [&](int i) { row[i] = 0.f; });
-    } else if (gumbel) {
-      gumbel_pi(w, V, S, ri, row);
-    } else if (V.forced_prune && V.forced_k > 0.0) {     // the forced playouts do not belong in the target
-      if (pruned_pi(w, V, S, ri, G.rootN, rm.n <= V.tau, row)) w.count(&V.counters[CT_PRUNED_ROWS], 1);
-    } else {
-      children_as_pi(w, V, S, ri, rm.n <= V.tau, row);
-    }
-    if (w.leader()) {
-      V.rec_moves[(long)g * V.max_game_length + k] = (int16_t)a;
-      V.rec_q[(long)g * V.max_game_length + k] = q;
-    }
-  }
-  w.sync();
   if (V.cap_fast > 0) w.count(&V.counters[fast ? CT_CAP_FAST : CT_CAP_FULL], 1);
-  AGZ_STAMP(w, V, CT_T_PICK);
-  int child = V.child[ri * V.AP + a];
-  if (child < 0) child = node_create_child(w, V, S, g, root, a);
-  if (child < 0) { game_finish(w, V, S, g, 0, 0, 0.f); return; }
-  AGZ_STAMP(w, V, CT_T_CHILD);
-  reroot(w, V, S, g, a, child);
-  if (w.leader()) { G.move_count = k + 1; G.nqs = k + 1; }
-  w.sync();
+  const int kind = fast ? kPiZero : gumbel ? kPiGumbel : (V.forced_prune && V.forced_k > 0.0) ? kPiPruned : kPiVisits;
+  const int child = play_move(w, V, S, g, a, root_q(G), kind, true, true, &agz_t_prev);
+  if (child < 0) { game_finish(w, V, S, g, 0, 0, 0.f); return; }      // the pool cannot hold the child: the game is void
   if (!G.short_first) w.count(&V.counters[CT_POSITIONS], 1);
   w.sync();
   if (w.leader()) G.short_first = 0;
   w.sync();
   AGZ_STAMP(w, V, CT_T_REROOT);
   if (node_is_done(V, g, child)) {
-    load_board(w, V, S, node_index(V, g, child));
-    const float sc = area_score(w, V, S, G.komi);
+    const float sc = position_score(w, V, S, g, child);
     game_finish(w, V, S, g, result_of(sc), 0, sc);
     return;
   }
@@ -1554,8 +1612,7 @@ AGZ_FN void game_select_phase(W& w, const View& V, Scratch& S, int g, int par, b
     int plen = 0;
     const int leaf = select_leaf(w, V, S, g, G.root, &plen, defer, forced, gumbel ? gumbel_root_pick(V, g) : -1);
     if (node_is_done(V, g, leaf)) {
-      load_board(w, V, S, node_index(V, g, leaf));
-      const float value = (float)result_of(area_score(w, V, S, G.komi));
+      const float value = (float)result_of(position_score(w, V, S, g, leaf));
       path_backup(w, V, g, S.path, plen, value);
       terminal++;
       continue;
@@ -1588,12 +1645,8 @@ AGZ_FN int32_t* arena_abort_word(const View& V, int pair) { return V.ar_hdr + 4 
 template <class W>
 AGZ_FN void arena_finish(W& w, const View& V, Scratch& S, int g, bool emit, int winner, int was_resign) {
   GameState& G = V.gs[g];
-  if (emit) {
-    // `result(black.root.position)` (:147) is the Tromp-Taylor result of the final position
-    load_board(w, V, S, node_index(V, g, G.root));
-    const float sc = area_score(w, V, S, G.komi);
-    game_finish(w, V, S, g, winner, was_resign, sc);
-  }
+  // `result(black.root.position)` (:147) is the Tromp-Taylor result of the final position
+  if (emit) game_finish(w, V, S, g, winner, was_resign, position_score(w, V, S, g, G.root));
   if (w.leader()) { G.phase = G_IDLE; G.arena_k = G.arena_k + 1; G.nleaves = 0; }
   w.sync();
 }
@@ -1612,32 +1665,25 @@ AGZ_FN void arena_start(W& w, const View& V, Scratch& S, int g, uint64_t index) 
     G.resign_disabled = 0;
     G.resign_threshold = V.resign_threshold;     // MCTSPlayer default, evaluate passes none (:110-111)
     if (waits) G.phase = G_ARENA_WAIT;
-    else { G.target = G.rootN + (float)V.R; G.phase = G_SEARCH; }     // :121-126, root not pre-expanded
   }
+  if (!waits) search_budget(w, G, V.R);            // :121-126, root not pre-expanded
   w.sync();
 }
 
-// play the partner's move on this slot's tree: play_move!(inactive, move) (:137)
+// play_move!(active, move) (:138) and, with the partner's move, play_move!(inactive, move) (:139) on this slot's tree:
+// two_player_mode records no pi, so the ply's row is all zero
 template <class W>
 AGZ_FN bool arena_apply(W& w, const View& V, Scratch& S, int g, int a, float q) {
-  GameState& G = V.gs[g];
-  const long ri = node_index(V, g, G.root);
-  const int k = G.move_count;
-  if (k < V.max_game_length) {
-    w.for_each(V.A, [&](int i) { V.rec_pi[((long)g * V.max_game_length + k) * V.A + i] = 0.f; });
-    if (w.leader()) {
-      V.rec_moves[(long)g * V.max_game_length + k] = (int16_t)a;
-      V.rec_q[(long)g * V.max_game_length + k] = q;
-    }
-  }
+  return play_move(w, V, S, g, a, q, kPiZero, true, true) >= 0;
+}
+
+// the pair's mailbox: this slot's game, its plies played, whether the game is over and how (arena_pre reads it)
+template <class W>
+AGZ_FN void arena_publish(W& w, const View& V, int g, int done, int result) {
+  const GameState& G = V.gs[g];
+  int32_t* hdr = V.ar_hdr + 4 * (g >> 1);
+  if (w.leader()) { hdr[0] = G.arena_k; hdr[1] = G.move_count; hdr[2] = done; hdr[3] = result; }
   w.sync();
-  int child = V.child[ri * V.AP + a];
-  if (child < 0) child = node_create_child(w, V, S, g, G.root, a);
-  if (child < 0) return false;
-  reroot(w, V, S, g, a, child);
-  if (w.leader()) { G.move_count = k + 1; G.nqs = k + 1; }
-  w.sync();
-  return true;
 }
 
 template <class W>
@@ -1688,7 +1734,7 @@ AGZ_FN void arena_pre(W& w, const View& V, Scratch& S, int g) {
       arena_finish(w, V, S, g, false, 0, 0);
       return;
     }
-    if (w.leader()) { G.target = G.rootN + (float)V.R; G.phase = G_SEARCH; }     // :121-126
+    search_budget(w, G, V.R);                               // :121-126
     w.sync();
   }
   if (G.phase == G_SEARCH) game_select_phase(w, V, S, g, V.par, V.defer_expand != 0);
@@ -1698,38 +1744,28 @@ AGZ_FN void arena_pre(W& w, const View& V, Scratch& S, int g) {
 template <class W>
 AGZ_FN void arena_move_phase(W& w, const View& V, Scratch& S, int g) {
   GameState& G = V.gs[g];
-  const int pair = g >> 1;
-  int32_t* hdr = V.ar_hdr + 4 * pair;
-  const long ri = node_index(V, g, G.root);
-  const NodeMeta rm = V.meta[ri];
-  const float q = G.rootW / (1.0f + G.rootN);
-  const float qp = q * (float)rm.to_play;
-  if ((double)qp < G.resign_threshold) {                    // should_resign(active) (:129-133)
-    const int winner = -rm.to_play;
-    if (w.leader()) { hdr[0] = G.arena_k; hdr[1] = G.move_count; hdr[2] = 1; hdr[3] = (winner + 1) | 4; }
-    w.sync();
+  if (should_resign(V, g)) {                                // should_resign(active) (:129-133)
+    const int winner = -V.meta[node_index(V, g, G.root)].to_play;
+    arena_publish(w, V, g, 1, (winner + 1) | 4);
     arena_finish(w, V, S, g, true, winner, 1);
     return;
   }
   int a = V.P;
   if (pick_move(w, V, S, g, &a) != AGZ_OK) a = V.P;
-  if (!arena_apply(w, V, S, g, a, q)) {
-    if (w.leader()) { hdr[0] = G.arena_k; hdr[1] = G.move_count; hdr[2] = 1; hdr[3] = 1; }
-    w.sync();
+  if (!arena_apply(w, V, S, g, a, root_q(G))) {             // the pool cannot hold the child: the game is void
+    arena_publish(w, V, g, 1, 1);
     arena_finish(w, V, S, g, true, 0, 0);
     return;
   }
   w.count(&V.counters[CT_POSITIONS], 1);
   if (node_is_done(V, g, G.root)) {                         // :140-145
-    load_board(w, V, S, node_index(V, g, G.root));
-    const int winner = result_of(area_score(w, V, S, G.komi));
-    if (w.leader()) { hdr[0] = G.arena_k; hdr[1] = G.move_count; hdr[2] = 1; hdr[3] = winner + 1; }
-    w.sync();
+    const int winner = result_of(position_score(w, V, S, g, G.root));
+    arena_publish(w, V, g, 1, winner + 1);
     arena_finish(w, V, S, g, true, winner, 0);
     return;
   }
-  if (w.leader()) { hdr[0] = G.arena_k; hdr[1] = G.move_count; hdr[2] = 0; hdr[3] = 0; G.phase = G_ARENA_WAIT; }
-  w.sync();
+  if (w.leader()) G.phase = G_ARENA_WAIT;
+  arena_publish(w, V, g, 0, 0);
 }
 
 // ---------------------------------------------------------------- analysis lines ----
@@ -1904,6 +1940,16 @@ AGZ_FN long long analysis_row(const View& V, int g) {
   return V.review ? V.rv_off[j] + V.gs[g].move_count : j;
 }
 
+// the row of a position or ply that was not searched: no move, `status`
+AGZ_FN agz_analysis unsearched_row(int status) { return agz_analysis{-1, status, 0.f, 0.f, 0.f, 0}; }
+
+// the slot is done with its position or game: idle, to claim the next one in analysis_pre
+template <class W>
+AGZ_FN void slot_idle(W& w, GameState& G) {
+  if (w.leader()) { G.phase = G_IDLE; G.nleaves = 0; G.err = 0; G.stalled = 0; }
+  w.sync();
+}
+
 // the slot's row of the result tables: the header, and the root's three A-wide rows in consecutive stores
 template <class W>
 AGZ_FN void analysis_finish(W& w, const View& V, Scratch& S, int g) {
@@ -1928,12 +1974,11 @@ AGZ_FN void analysis_finish(W& w, const View& V, Scratch& S, int g) {
   }
   if (w.leader()) {
     agz_analysis r;
-    r.move = a; r.status = status; r.N = G.rootN; r.W = G.rootW; r.Q = G.rootW / (1.0f + G.rootN);
+    r.move = a; r.status = status; r.N = G.rootN; r.W = G.rootW; r.Q = root_q(G);
     r.nodes_used = G.nodes_used;
     V.an_res[i] = r;
-    G.phase = G_IDLE; G.nleaves = 0; G.err = 0; G.stalled = 0;
   }
-  w.sync();
+  slot_idle(w, G);
   w.count(&V.an_ctr[1], 1);
 }
 
@@ -1947,14 +1992,9 @@ AGZ_FN void review_give_up(W& w, const View& V, int g, int status) {
   GameState& G = V.gs[g];
   const long long j = V.an_slot[g];
   const long long r0 = V.rv_off[j] + G.move_count, r1 = V.rv_off[j + 1];
-  w.for_each((int)(r1 - r0), [&](int t) {
-    agz_analysis r;
-    r.move = -1; r.status = status; r.N = 0.f; r.W = 0.f; r.Q = 0.f; r.nodes_used = 0;
-    V.an_res[r0 + t] = r;
-  });
+  w.for_each((int)(r1 - r0), [&](int t) { V.an_res[r0 + t] = unsearched_row(status); });
   w.sync();
-  if (w.leader()) { G.phase = G_IDLE; G.nleaves = 0; G.err = 0; G.stalled = 0; }
-  w.sync();
+  slot_idle(w, G);
   w.count(&V.an_ctr[1], (unsigned long long)(r1 - r0));
 }
 
@@ -1966,34 +2006,28 @@ AGZ_FN void review_next_ply(W& w, const View& V, int g) {
   GameState& G = V.gs[g];
   const long long j = V.an_slot[g];
   const long long off = V.rv_off[j], n = V.rv_off[j + 1] - off;
-  if (G.move_count >= n) {
-    if (w.leader()) { G.phase = G_IDLE; G.nleaves = 0; G.err = 0; G.stalled = 0; }
-    w.sync();
-    return;
-  }
+  if (G.move_count >= n) { slot_idle(w, G); return; }
   const int a = V.rv_moves[off + G.move_count];
   const long ri = node_index(V, g, G.root);
   if (node_is_done(V, g, G.root) || a < 0 || a > V.P || !legal_bit(V, ri, a)) {   // (arena records: no host check)
     review_give_up(w, V, g, AGZ_BAD_ARGUMENT);
     return;
   }
-  if (w.leader()) { G.phase = G_SEARCH; G.target = G.rootN + (float)V.R; G.stalled = 0; }   // N(root) >= N0 + R
+  search_budget(w, G, V.R);                                 // N(root) >= N0 + R
+  if (w.leader()) G.stalled = 0;
   w.sync();
 }
 
-// play_move!(player, m_k) (mcts_play.jl:26-50) without the record: find or create the child, re-root (the dropped
-// siblings go to the garbage stack game_pre drains), then the next ply.  A child the full pool cannot hold is made room
-// for by discarding the root's other subtrees first: the re-root drops them anyway, so the result is the unbounded
-// tree's.
+// play_move!(player, m_k) without the record -- the ply count alone advances -- then the next ply (the dropped siblings
+// go to the garbage stack game_pre drains).  A child the full pool cannot hold is made room for by discarding the
+// root's other subtrees first: the re-root drops them anyway, so the result is the unbounded tree's.
 template <class W>
 AGZ_FN void review_play(W& w, const View& V, Scratch& S, int g) {
   GameState& G = V.gs[g];
   const long long j = V.an_slot[g];
   const int a = V.rv_moves[V.rv_off[j] + G.move_count];
-  const int root = G.root;
-  const long ri = node_index(V, g, root);
-  int child = V.child[ri * V.AP + a];
-  if (child < 0) child = node_create_child(w, V, S, g, root, a);
+  const long ri = node_index(V, g, G.root);
+  int child = play_move(w, V, S, g, a, 0.f, kPiNone, true, false);
   if (child == -1) {
     if (w.leader()) {
       for (int b = 0; b < V.A; ++b) {
@@ -2007,7 +2041,7 @@ AGZ_FN void review_play(W& w, const View& V, Scratch& S, int g) {
     }
     w.sync();
     free_pending(w, V, S, g, V.cap);
-    child = node_create_child(w, V, S, g, root, a);
+    child = play_move(w, V, S, g, a, 0.f, kPiNone, true, false);
   }
   if (child < 0) {                                      // (a pool of fewer than two nodes)
     if (w.leader()) G.move_count = G.move_count + 1;
@@ -2015,8 +2049,7 @@ AGZ_FN void review_play(W& w, const View& V, Scratch& S, int g) {
     review_give_up(w, V, g, AGZ_POOL_EXHAUSTED);
     return;
   }
-  reroot(w, V, S, g, a, child);
-  if (w.leader()) { G.move_count = G.move_count + 1; G.err = 0; }
+  if (w.leader()) G.err = 0;
   w.sync();
   review_next_ply(w, V, g);
 }
@@ -2047,15 +2080,9 @@ AGZ_FN void analysis_pre(W& w, const View& V, Scratch& S, int g) {
     w.sync();
     return;
   }
-  if (G.phase == G_SEARCH) {
-    const bool full = G.err == AGZ_POOL_EXHAUSTED;
-    const bool finish = !(G.rootN < G.target) || pool_full_can_move(w, V, g);
-    if (w.leader()) G.stalled = full && !finish;        // AGZ_POOL_STALL: the slot waits for agz_slot_abandon
-    w.sync();
-    if (finish) {
-      analysis_finish(w, V, S, g);
-      if (V.review) review_play(w, V, S, g);
-    }
+  if (G.phase == G_SEARCH && search_over(w, V, g)) {
+    analysis_finish(w, V, S, g);
+    if (V.review) review_play(w, V, S, g);
   }
   while (G.phase == G_IDLE) {
     if (w.leader()) G.nleaves = 0;
@@ -2072,11 +2099,7 @@ AGZ_FN void analysis_pre(W& w, const View& V, Scratch& S, int g) {
     }
     const agz_position_info info = V.an_info[i];
     if (!root_install(w, V, S, g, V.an_board + i * V.P, V.an_hist + i * 7 * V.P, info, G_SEARCH, true)) {
-      if (w.leader()) {
-        agz_analysis r;
-        r.move = -1; r.status = AGZ_BAD_ARGUMENT; r.N = 0.f; r.W = 0.f; r.Q = 0.f; r.nodes_used = 0;
-        V.an_res[i] = r;
-      }
+      if (w.leader()) V.an_res[i] = unsearched_row(AGZ_BAD_ARGUMENT);
       w.sync();
       w.count(&V.an_ctr[1], 1);
       continue;                                         // nothing searched: claim the next position in this k_pre
@@ -2084,9 +2107,9 @@ AGZ_FN void analysis_pre(W& w, const View& V, Scratch& S, int g) {
     if (w.leader()) {
       V.an_slot[g] = i;
       G.game_id = V.an_id_base + (uint64_t)i;
-      G.target = G.rootN + (float)V.R;                  // suggest_move: N(root) >= N0 + num_readouts
       G.short_first = 0; G.stalled = 0;
     }
+    search_budget(w, G, V.R);                           // suggest_move: N(root) >= N0 + num_readouts
     w.sync();
   }
   if (G.phase == G_SEARCH) game_select_phase(w, V, S, g, V.par, V.defer_expand != 0);
@@ -2111,11 +2134,7 @@ AGZ_FN void game_pre(W& w, const View& V, Scratch& S, int g) {
   }
   bool agz_moved = false;
   if (G.phase == G_SEARCH) {
-    const bool full = G.err == AGZ_POOL_EXHAUSTED;
-    const bool can_move = !(G.rootN < G.target) || pool_full_can_move(w, V, g);
-    if (w.leader()) G.stalled = full && !can_move;      // what agz_stats.stalled_games / agz_slot_status report
-    w.sync();
-    if (can_move) { game_move_phase(w, V, S, g); agz_moved = true; }
+    if (search_over(w, V, g)) { game_move_phase(w, V, S, g); agz_moved = true; }
   } else if (G.stalled) {
     if (w.leader()) G.stalled = 0;
     w.sync();
@@ -2180,7 +2199,6 @@ AGZ_FN void game_post(W& w, const View& V, Scratch& S, int g) {
     return;
   }
   if (nl <= 0 || (G.phase != G_SEARCH && G.phase != G_INIT_WAIT && G.phase != G_MANUAL)) return;
-  const float n_before = G.rootN;
   for (int k = 0; k < nl; ++k) {
     const long li = (long)g * V.par + k;
     const int leaf = V.leaf_node[li], plen = V.leaf_plen[li];
@@ -2189,19 +2207,16 @@ AGZ_FN void game_post(W& w, const View& V, Scratch& S, int g) {
     if (G.phase != G_INIT_WAIT) path_virtual_loss(w, V, g, path, plen, -1);
     incorporate(w, V, g, leaf, V.pi + b * V.A, V.v[b], path, plen);
   }
-  (void)n_before;
   if (G.phase == G_INIT_WAIT) {
     search_begin(w, V, S, g, G.root, full_search(V, G, V.meta[node_index(V, g, G.root)].n));
-    if (w.leader()) {
-      if (G.short_first) {          // the bench stagger: a short first search of its own budget
-        const double u = agz_u01(agz_draw_u64(V.seed, G.game_id, 0, AGZ_SITE_STAGGER, 1000000u));
-        G.target = G.rootN + (float)(1 + (int)(u * (double)(V.R - 1)));
-      }
-      G.phase = G_SEARCH;
+    if (G.short_first) {            // the bench stagger: a short first search of its own budget
+      const double u = agz_u01(agz_draw_u64(V.seed, G.game_id, 0, AGZ_SITE_STAGGER, 1000000u));
+      search_budget(w, G, 1 + (int)(u * (double)(V.R - 1)));
     }
   }
   if (w.leader()) G.nleaves = 0;
   w.sync();
+  // (the arena's "search over" is the target alone, here and above: search_over's full-pool rule is game_pre's)
   if (V.arena && G.phase == G_SEARCH && !(G.rootN < G.target)) arena_move_phase(w, V, S, g);
 }
 
@@ -2380,32 +2395,14 @@ AGZ_FN void tree_op(W& w, const View& V, Scratch& S, const TreeArgs& T) {
     case TOP_SEARCH_POST: game_post(w, V, S, g); break;
     case TOP_PICK: status = pick_move(w, V, S, g, &r0); break;
     case TOP_PLAY: {
-      // play_move!(player, c), mcts_play.jl:26-50
-      const int root = G.root;
-      const long ri = node_index(V, g, root);
-      int c = (T.a >= 0 && T.a < V.A) ? V.child[ri * V.AP + T.a] : -2;
-      if (c == -1) c = node_create_child(w, V, S, g, root, T.a);
+      // play_move!(player, c), mcts_play.jl:26-50: two_player_mode keeps qs and no searches_pi.  An illegal move is
+      // the reference's "Illegal move ... return false": AGZ_OK with r0 = 0
+      const int c = play_move(w, V, S, g, T.a, root_q(G), V.two_player ? kPiNone : kPiVisits, !V.two_player, true);
       if (c < 0) { r0 = 0; status = c == -2 ? AGZ_OK : AGZ_POOL_EXHAUSTED; break; }
-      const int k = G.move_count;
-      const float q = G.rootW / (1.0f + G.rootN);
-      if (!V.two_player && k < V.max_game_length)
-        children_as_pi(w, V, S, ri, V.meta[ri].n <= V.tau, V.rec_pi + ((long)g * V.max_game_length + k) * V.A);
-      if (w.leader() && G.nqs < V.max_game_length) {
-        V.rec_moves[(long)g * V.max_game_length + G.nqs] = (int16_t)T.a;
-        V.rec_q[(long)g * V.max_game_length + G.nqs] = q;
-      }
-      w.sync();
-      reroot(w, V, S, g, T.a, c);
       free_pending(w, V, S, g, V.cap);      // single-tree API: release the dropped siblings right away
-      if (w.leader()) { if (!V.two_player) G.move_count = k + 1; G.nqs = G.nqs + 1; }
-      w.sync();
       r0 = 1;
     } break;
-    case TOP_RESIGN: {
-      const float q = G.rootW / (1.0f + G.rootN);
-      const float qp = q * (float)V.meta[node_index(V, g, G.root)].to_play;
-      r0 = (double)qp < G.resign_threshold;
-    } break;
+    case TOP_RESIGN: r0 = should_resign(V, g); break;
     case TOP_SCORES: {
       const long ni = node_index(V, g, T.node);
       const NodeMeta m = V.meta[ni];

@@ -62,6 +62,7 @@ struct Sim {
   std::vector<float> pi, v;
   agz::Scratch S{};
   int batch = 0;
+  long long an_rows = 0;               // result rows of the analysis / review run (hs_analysis_start)
 };
 
 template <class T>
@@ -106,6 +107,7 @@ void hs_dims(void* h, int32_t* out /*N,P,A,AP,cap,games,par,mgl,tau,maxd*/) {
 void hs_start(void* h, int64_t total_games) {
   Sim* s = (Sim*)h;
   s->V.total_games = total_games;
+  s->V.analysis = 0;                   // back to self-play, as Engine::start
   memset(s->V.counters, 0, sizeof(unsigned long long) * agz::CT_COUNT);
   memset(s->V.ar_hdr, 0, sizeof(int32_t) * 5 * (s->V.games / 2 + 1));
   for (int g = 0; g < s->V.games; ++g) {
@@ -390,6 +392,78 @@ int hs_gumbel_schedule(int n, int m0, int32_t* out, int cap) {
     m = m == 1 ? 1 : (m / 2 > 2 ? m / 2 : 2);
   }
   return k;
+}
+
+// ---- batched analysis and game review (agz_analyze_start / agz_review_start; no lines, no reanalysis)
+// B claimable items: positions -- or, with `moves` and `game_offset` [B + 1], the start positions of B recorded games.
+// The View is set up as Engine::begin_analysis_run and Engine::review_start set it: the an_* / rv_* tables (host arrays
+// here; the copies live as long as the Sim), the claim and progress counters cleared, every slot idle.  history may be
+// NULL (every history_len 0).  hs_pre / hs_post step the run through game_pre / game_post.
+void hs_analysis_start(void* h, const int8_t* boards, const agz_position_info* info, const int8_t* history, int64_t B,
+                       const int16_t* moves, const int64_t* game_offset, uint64_t game_id_base) {
+  Sim* s = (Sim*)h;
+  agz::View& V = s->V;
+  const size_t P = (size_t)V.P, A = (size_t)V.A, nb = (size_t)B;
+  const size_t rows = game_offset ? (size_t)game_offset[B] : nb, R = rows ? rows : 1;
+  int8_t *b = nullptr, *hh = nullptr;
+  agz_position_info* f = nullptr;
+  agz_analysis* res = nullptr;
+  float* tab = nullptr;
+  int16_t* mv = nullptr;
+  int64_t* off = nullptr;
+  alloc_one(s, b, nb * P);
+  alloc_one(s, hh, nb * 7 * P);
+  alloc_one(s, f, nb);
+  alloc_one(s, res, R);                 // (zeroed, as clear_result_tables leaves them)
+  alloc_one(s, tab, 3 * R * A);
+  memcpy(b, boards, nb * P);
+  if (history) memcpy(hh, history, nb * 7 * P);
+  memcpy(f, info, sizeof(agz_position_info) * nb);
+  V.review = game_offset ? 1 : 0;
+  V.rv_moves = nullptr;
+  V.rv_off = nullptr;
+  if (game_offset) {
+    alloc_one(s, mv, rows);
+    alloc_one(s, off, nb + 1);
+    memcpy(mv, moves, sizeof(int16_t) * rows);
+    memcpy(off, game_offset, sizeof(int64_t) * (nb + 1));
+    V.rv_moves = mv;
+    V.rv_off = off;
+  }
+  V.analysis = 1;
+  V.an_count = B;
+  V.an_id_base = game_id_base;
+  V.an_board = b;
+  V.an_hist = hh;
+  V.an_info = f;
+  V.an_res = res;
+  V.an_childN = tab;
+  V.an_childW = tab + R * A;
+  V.an_prior = tab + 2 * R * A;
+  V.an_gid = nullptr;
+  V.an_pi = nullptr;
+  V.an_lines = V.an_pv_depth = V.an_pv_min = 0;
+  V.an_line = nullptr;
+  V.an_pv = nullptr;
+  V.an_pvN = nullptr;
+  V.an_ctr[0] = V.an_ctr[1] = 0;
+  s->an_rows = (long long)rows;
+  for (int g = 0; g < V.games; ++g) {
+    memset(&V.gs[g], 0, sizeof(agz::GameState));
+    V.gs[g].phase = agz::G_IDLE;
+  }
+}
+
+// the run's result rows: res [rows], child N / W / prior [rows][A] each; returns an_ctr[1], the rows finished so far
+long long hs_analysis_results(void* h, agz_analysis* res, float* child_N, float* child_W, float* prior) {
+  Sim* s = (Sim*)h;
+  const agz::View& V = s->V;
+  const size_t n = (size_t)s->an_rows, A = (size_t)V.A;
+  memcpy(res, V.an_res, sizeof(agz_analysis) * n);
+  memcpy(child_N, V.an_childN, sizeof(float) * n * A);
+  memcpy(child_W, V.an_childW, sizeof(float) * n * A);
+  memcpy(prior, V.an_prior, sizeof(float) * n * A);
+  return (long long)V.an_ctr[1];
 }
 
 // ---- analysis lines

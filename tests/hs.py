@@ -140,6 +140,9 @@ def lib():
         "hs_gumbel_state": (None, [vp, i, P(GumbelStateC)]), "hs_gumbel_pi": (None, [vp, i, i, dbl, dbl, P(f)]),
         "hs_gumbel_descend": (i, [vp, i, P(C.c_int16), i]), "hs_gumbel_schedule": (i, [i, i, P(C.c_int32), i]),
         "hs_node_lines": (None, [vp, i, i, i, i, i, P(ag._lib.Line), P(C.c_int16), P(f)]),
+        "hs_analysis_start": (None, [vp, P(C.c_int8), P(ag._lib.PositionInfo), P(C.c_int8), C.c_int64, P(C.c_int16),
+                                     P(C.c_int64), C.c_uint64]),
+        "hs_analysis_results": (C.c_longlong, [vp, P(ag._lib.Analysis), P(f), P(f), P(f)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -298,6 +301,35 @@ class Sim:
         out = (C.c_int32 * 128)()
         k = self.L.hs_gumbel_schedule(int(n), int(m0), out, 64)
         return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(k)]
+
+    # ---- batched analysis and game review
+    def analysis_start(self, positions, games=None, game_id_base=0):
+        """agz_analyze_start on oracle positions (or their opos_arrays, which a caller may have spoilt); with `games` (one
+        list of flat moves per position) agz_review_start: the positions are the games' starts, and ply k of game j is
+        row offsets[j] + k.  Step the run with step()."""
+        from selfplay_twin import opos_arrays          # (the twin module imports this one)
+        boards, infos, hist = positions if isinstance(positions, tuple) else opos_arrays(positions)
+        B = len(infos)
+        moves = off = None
+        self.an_rows = B
+        if games is not None:
+            assert len(games) == B
+            mv = np.array([m for g in games for m in g] + [0], np.int16)        # (never empty)
+            of = np.concatenate([[0], np.cumsum([len(g) for g in games])]).astype(np.int64)
+            moves, off = mv.ctypes.data_as(C.POINTER(C.c_int16)), of.ctypes.data_as(C.POINTER(C.c_int64))
+            self.an_rows = int(of[-1])
+        self.L.hs_analysis_start(self.h, p8(boards), infos, p8(hist), B, moves, off, game_id_base)
+
+    def analysis_results(self):
+        """(rows finished, the fields of the run's rows: move, status, N, W, Q, nodes_used, child_N / child_W / prior)"""
+        n = self.an_rows
+        res = (ag._lib.Analysis * max(n, 1))()
+        rows = [np.zeros((max(n, 1), self.A), np.float32) for _ in range(3)]
+        done = self.L.hs_analysis_results(self.h, res, *(pf(r) for r in rows))
+        out = {f: np.array([getattr(res[k], f) for k in range(n)], np.int32 if t is C.c_int32 else np.float32)
+               for f, t in ag._lib.Analysis._fields_}
+        out.update(child_N=rows[0][:n], child_W=rows[1][:n], prior=rows[2][:n])
+        return int(done), out
 
     # ---- Go rules
     def go_play(self, boards, to_play, ko, moves):
