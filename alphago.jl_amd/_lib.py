@@ -158,6 +158,11 @@ def load():
         "agz_replay_set_value_target": (i32, [E, C.c_double, C.c_double]),
         "agz_records_value_targets": (i32, [E, i64, C.c_double, C.c_double, f32p]),
         "agz_value_targets": (i32, [f32p, i32, i32, C.c_double, C.c_double, f32p]),
+        "agz_replay_score": (i32, [E, i64, i64, P(i64)]),
+        "agz_replay_set_surprise": (i32, [E, C.c_double]),
+        "agz_replay_surprise": (i32, [E, i64, f64p, P(C.c_uint32), i32p]),
+        "agz_surprise_weights": (i32, [f32p, f32p, i32, i32, C.c_double, f64p, P(C.c_uint32)]),
+        "agz_surprise_pick": (i64, [P(u64), i64, u64]),
         "agz_selfplay_set_forced_playouts": (i32, [E, C.c_double, i32]),
         "agz_selfplay_forced_counts": (i32, [E, P(i64)]),
         "agz_tree_pruned_pi": (i32, [E, i32, i32, C.c_double, f32p]),

@@ -1145,7 +1145,7 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
           tower_height=19, model=None, start_training_after=50000, slots=None, seed=0, game_id_base=0, symmetry=None,
           augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, starts=None,
           playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
-          gumbel_c_scale=1.0, value_target=None, fpu=None, c_base=0.0, **cfg):
+          gumbel_c_scale=1.0, value_target=None, fpu=None, c_base=0.0, surprise=0.0, **cfg):
     """train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model,
     start_training_after) (src/train.jl:38-92) with `slots` games in flight on the device.  One engine
     plays, keeps the replay arena and trains; per step: agz_selfplay_step(1), one read of how many games finished, and
@@ -1167,7 +1167,10 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
     gumbel (m), gumbel_c_visit and gumbel_c_scale (the Gumbel root search in the full searches, as in selfplay),
     value_target ((alpha, lam): the z of every training batch is (1 - alpha) * result + alpha * TD(lam) of the game's
     recorded root values from the sampled ply on, Engine.replay_set_value_target; None: the result, as the reference),
-    fpu and c_base (the PUCT rule options of Engine.set_puct, as in selfplay).
+    fpu and c_base (the PUCT rule options of Engine.set_puct, as in selfplay), surprise (rho: policy surprise weighting --
+    each game is scored right after it is filed, on the weights of that moment, and every training batch is drawn by
+    weight, with replacement: per game a share 1 - rho of the sampling mass evenly over its target plies and rho in
+    proportion to KL(pi || prior), Engine.replay_score / replay_set_surprise; 0: the uniform draw, as the reference).
     Returns the trained NeuralNet (model itself when given)."""
     import time
     import torch
@@ -1200,6 +1203,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
                               gumbel_c_scale, targets_only_arena=True, fpu=fpu, c_base=c_base)
         if value_target is not None:
             eng.replay_set_value_target(*value_target)
+        surprise = float(surprise)
+        eng.replay_set_surprise(surprise)
         eng.set_hold(True)
         eng.start(num_games)
         eng.release()
@@ -1228,6 +1233,9 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
             for h, k in heads:
                 n_pos += int(h["num_moves"])
                 eng.replay_ingest_records(k, 1)                                          # push_data, train.jl:60-61
+                if surprise > 0.0:
+                    eng.replay_score(eng.replay_count() - 1, 1)                          # on the weights of this moment
+                    syncs += 1
                 eng.replay_set_window(memory_size)                                       # shrink, train.jl:63-65
                 i += 1
                 loss = None

@@ -8,6 +8,7 @@
 #include "../../include/agz_value_target.h"
 #include "agz_engine.h"
 #include "agz_search.h"
+#include "../../include/agz_surprise.h"      // (behind the HIP runtime: the device side uses __umul64hi)
 
 struct agz_engine {
   agz::Engine* impl;
@@ -378,6 +379,48 @@ agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on) {
 }
 agz_status agz_replay_set_value_target(agz_engine* e, double alpha, double lambda) {
   return guard(e, [&](agz::Engine& E) { E.replay_set_value_target(alpha, lambda); });
+}
+// ---- policy surprise weighting (include/agz_surprise.h)
+agz_status agz_replay_score(agz_engine* e, int64_t first, int64_t count, int64_t* rows_out) {
+  return guard(e, [&](agz::Engine& E) {
+    const int64_t rows = E.replay_score(first, count);
+    if (rows_out) *rows_out = rows;
+  });
+}
+agz_status agz_replay_set_surprise(agz_engine* e, double rho) {
+  return guard(e, [&](agz::Engine& E) { E.replay_set_surprise(rho); });
+}
+agz_status agz_replay_surprise(agz_engine* e, int64_t k, double* kl_out, uint32_t* q_out, int32_t* scored_out) {
+  return guard(e, [&](agz::Engine& E) { E.replay_surprise(k, kl_out, q_out, scored_out); });
+}
+// engine-free: the host loops over include/agz_surprise.h for one game the caller holds
+agz_status agz_surprise_weights(const float* pis, const float* ps, int32_t T, int32_t A, double rho, double* kl_out,
+                                uint32_t* q_out) {
+  if (T < 0 || A < 1 || (T > 0 && (!pis || !ps)) || !agz_surprise_rho_ok(rho)) {
+    g_create_error = "surprise weights: T >= 0 rows of A >= 1 entries in pis and ps, rho 0..1";
+    return AGZ_BAD_ARGUMENT;
+  }
+  std::vector<double> kl((size_t)T, 0.0);
+  std::vector<uint8_t> tgt((size_t)T, 0);
+  double S = 0.0;
+  int32_t n = 0;
+  for (int32_t t = 0; t < T; ++t) {
+    const float* pi = pis + (size_t)t * A;
+    if (!agz_surprise_is_target(pi, A)) continue;
+    tgt[(size_t)t] = 1;
+    kl[(size_t)t] = agz_surprise_score(pi, ps + (size_t)t * A, A);
+    S = S + kl[(size_t)t];
+    ++n;
+  }
+  for (int32_t t = 0; t < T; ++t) {
+    if (kl_out) kl_out[t] = kl[(size_t)t];
+    if (q_out) q_out[t] = tgt[(size_t)t] ? agz_surprise_q(kl[(size_t)t], n, S, rho) : AGZ_SURPRISE_UNIT;
+  }
+  return AGZ_OK;
+}
+int64_t agz_surprise_pick(const uint64_t* cum, int64_t n, uint64_t u) {
+  if (!cum || n < 1 || cum[n - 1] == 0) return -1;
+  return agz_weighted_pick(u, cum, n);
 }
 agz_status agz_device_alloc(agz_engine* e, int64_t bytes, void** out) {
   return guard(e, [&](agz::Engine& E) {

@@ -110,6 +110,11 @@ class Engine {
   void replay_set_targets_only(bool on);
   // the z of the batch calls is y_t under (alpha, lambda) (agz_replay_set_value_target); alpha = 0 (the default) is off
   void replay_set_value_target(double alpha, double lambda);
+  // policy surprise weighting (agz_replay_score / _set_surprise / _surprise, include/agz_surprise.h): one KL(pi || p)
+  // per ply of arena games [first, first + count) on the selected network; rho = 0 (the default) is off
+  int64_t replay_score(int64_t first, int64_t count);
+  void replay_set_surprise(double rho);
+  void replay_surprise(int64_t k, double* kl_out, uint32_t* q_out, int32_t* scored_out);
   // get_replay_batch without the host: B distinct live entries drawn on the device (agz_replay_sample)
   void replay_sample(int B, uint64_t call, int sym_mode, float* feats, float* pi, float* z, int64_t* game_out,
                      int32_t* ply_out);
@@ -296,6 +301,25 @@ class Engine {
   DevBuf<int64_t> tgt_idx_;         // replay_scan_targets: offsets and position prefix of the games just filed
   DevBuf<int32_t> tgt_cnt_;         // ... and their target counts
   double vt_alpha_ = 0.0, vt_lambda_ = 1.0;   // agz_replay_set_value_target; alpha = 0: off, z stays the result
+  // policy surprise weighting: rp_scored_[k] = game k has scores; d_sp_kl_ / d_sp_tgt_[rp_cum_[k] + t] = the score and the
+  // target flag of ply t of a scored game (laid out by the position prefix, as d_rp_tply_ is; what lies under an unscored
+  // game is never read).  d_sp_q_ / d_sp_qcum_ = q and its inclusive prefix over all positions, rebuilt by
+  // replay_weights_to_device when the arena (rp_change_), the scores (sp_epoch_) or rho changed since they were built
+  double sp_rho_ = 0.0;
+  std::vector<uint8_t> rp_scored_;
+  DevBuf<double> d_sp_kl_;
+  DevBuf<uint8_t> d_sp_tgt_, d_sp_scored_;
+  DevBuf<uint32_t> d_sp_q_;
+  DevBuf<uint64_t> d_sp_qcum_, d_sp_tiles_;
+  DevBuf<int64_t> sp_off_;
+  DevBuf<int32_t> sp_ply_;
+  DevBuf<unsigned long long> sp_count_;
+  uint64_t sp_epoch_ = 0, sp_built_change_ = 0, sp_built_epoch_ = 0, sp_total_ = 0;
+  double sp_built_rho_ = 0.0;
+  bool sp_built_ = false;
+  void replay_scores_reserve();
+  void replay_scored_to_device();
+  void replay_weights_to_device();
   DevBuf<int64_t> smp_off_, smp_game_;
   DevBuf<int32_t> smp_ply_, smp_sym_;
   DevBuf<int8_t> smp_boards_;

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "../../include/agz_surprise.h"
 #include "../../include/agz_value_target.h"
 #include "agz_search.h"
 
@@ -679,6 +680,175 @@ __global__ __launch_bounds__(kSampleThreads) void k_replay_sample(uint64_t seed,
   }
 }
 
+// ---- policy surprise weighting (agz_replay_score / agz_replay_set_surprise, include/agz_surprise.h)
+
+// the scoring pass, behind the forward: one wave per row = (record at rec_off[b], ply[b]).  The row's pi is read from the
+// arena, p is row b of the forward's output.  Each lane computes whole terms into LDS; lane 0 adds them in ascending a,
+// the order the header's loop adds them in.  A row that is all zero is no target: score 0, flag 0.
+constexpr int kSurpriseMaxA = 19 * 19 + 1;
+__global__ __launch_bounds__(kWave) void k_replay_surprise(const uint8_t* arena, const int64_t* rec_off,
+                                                            const int32_t* ply, const float* p_all, int A, double* kl,
+                                                            uint8_t* tgt, unsigned long long* ntargets) {
+  __shared__ double s_term[kSurpriseMaxA];
+  HipWave w;
+  const long b = blockIdx.x;
+  const uint8_t* r = arena + rec_off[b];
+  const agz_game_header h = *reinterpret_cast<const agz_game_header*>(r);
+  const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * (size_t)h.num_moves + 3) & ~(size_t)3;
+  const float* pi = reinterpret_cast<const float*>(r + o_pi) + (size_t)ply[b] * A;
+  const float* p = p_all + b * A;
+  bool nz = false;
+  w.for_each(A, [&](int a) {
+    const float x = pi[a];
+    nz = nz || x != 0.f;
+    s_term[a] = x > 0.f ? agz_surprise_term(x, p[a]) : 0.0;
+  });
+  const bool target = w.any(nz);
+  w.sync();
+  if (!w.leader()) return;
+  double s = 0.0;
+  if (target) {
+    for (int a = 0; a < A; ++a)
+      if (pi[a] > 0.f) s = s + s_term[a];
+    s = s > 0.0 ? s : 0.0;
+    atomicAdd(ntargets, 1ull);
+  }
+  kl[b] = s;
+  tgt[b] = target ? 1 : 0;
+}
+
+// the weights: one wave per game g0 + blockIdx.x.  Every lane walks the game's plies in order for S and n (the same
+// loads in every lane), then the lanes share the plies out for q.  A game that has not been scored, and a ply that is no
+// target, weigh 1.  Two masks force q to 0: the plies in front of the window (first_game, first_ply -- counted in target
+// plies when the arena is targets-only) and, targets-only (tply != NULL), the plies that are no targets; those are looked
+// up in the game's ascending target list tply[cum[g] .. + tcum[g+1] - tcum[g]).  q goes to q_out[cum[g] - shift + ply].
+__global__ __launch_bounds__(kWave) void k_replay_weights(const int64_t* cum, int64_t g0, const uint8_t* scored,
+                                                           const double* kl, const uint8_t* tgt, double rho,
+                                                           int64_t first_game, int64_t first_ply, const int64_t* tcum,
+                                                           const int16_t* tply, uint32_t* q_out, int64_t shift) {
+  HipWave w;
+  const int64_t g = g0 + blockIdx.x;
+  const int64_t base = cum[g];
+  const int nm = (int)(cum[g + 1] - base);
+  uint32_t* q = q_out + (base - shift);
+  if (g < first_game) {
+    w.for_each(nm, [&](int t) { q[t] = 0u; });
+    return;
+  }
+  const bool sc = scored[g] != 0;
+  double S = 0.0;
+  int n = 0;
+  if (sc)
+    for (int t = 0; t < nm; ++t)
+      if (tgt[base + t]) { S = S + kl[base + t]; ++n; }
+  const int nt = tply ? (int)(tcum[g + 1] - tcum[g]) : 0;
+  const int16_t* tl = tply ? tply + base : nullptr;
+  const int64_t dead = g == first_game ? first_ply : 0;
+  w.for_each(nm, [&](int t) {
+    uint32_t v = AGZ_SURPRISE_UNIT;
+    if (sc && tgt[base + t]) v = agz_surprise_q(kl[base + t], n, S, rho);
+    if (tl) {
+      int lo = 0, hi = nt;                                         // the first i with tl[i] >= t
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (tl[mid] < t) lo = mid + 1; else hi = mid;
+      }
+      if (lo >= nt || tl[lo] != t || lo < dead) v = 0u;
+    } else if (t < dead) {
+      v = 0u;
+    }
+    q[t] = v;
+  });
+}
+
+// the inclusive prefix of q (u32 -> u64) over n positions in three launches: k_scan_reduce (one sum per tile of kScanTile
+// positions), k_scan_tiles (one workgroup turns the tile sums into their exclusive prefix) and k_scan_add (each tile scans
+// its own positions and adds its offset).  No workgroup waits for another: the order is the order of the launches.
+constexpr int kScanThreads = 256, kScanItems = 4, kScanTile = kScanThreads * kScanItems, kScanTop = 1024;
+
+// the block-wide inclusive scan of one value per thread (Hillis-Steele in LDS); s has blockDim.x entries
+__device__ __forceinline__ uint64_t block_scan_inclusive(uint64_t v, uint64_t* s) {
+  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  s[tid] = v;
+  __syncthreads();
+  for (int o = 1; o < nt; o <<= 1) {
+    const uint64_t add = tid >= o ? s[tid - o] : 0ull;
+    __syncthreads();
+    s[tid] += add;
+    __syncthreads();
+  }
+  return s[tid];
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_scan_reduce(const uint32_t* q, int64_t n, uint64_t* tile_sum) {
+  __shared__ uint64_t s[kScanThreads];
+  const int64_t at = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+  uint64_t v = 0;
+  for (int i = 0; i < kScanItems; ++i)
+    if (at + i < n) v += q[at + i];
+  const uint64_t incl = block_scan_inclusive(v, s);
+  if (threadIdx.x == kScanThreads - 1) tile_sum[blockIdx.x] = incl;
+}
+
+__global__ __launch_bounds__(kScanTop) void k_scan_tiles(uint64_t* tile_sum, int64_t ntiles) {
+  __shared__ uint64_t s[kScanTop];
+  const int64_t per = (ntiles + kScanTop - 1) / kScanTop;          // consecutive tiles per thread
+  const int64_t lo = (int64_t)threadIdx.x * per, hi = lo + per < ntiles ? lo + per : ntiles;
+  uint64_t v = 0;
+  for (int64_t i = lo; i < hi; ++i) v += tile_sum[i];
+  uint64_t run = block_scan_inclusive(v, s) - v;                  // the sum of every tile in front of `lo`
+  for (int64_t i = lo; i < hi; ++i) {
+    const uint64_t x = tile_sum[i];
+    tile_sum[i] = run;
+    run += x;
+  }
+}
+
+__global__ __launch_bounds__(kScanThreads) void k_scan_add(const uint32_t* q, int64_t n, const uint64_t* tile_off,
+                                                            uint64_t* out) {
+  __shared__ uint64_t s[kScanThreads];
+  const int64_t at = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+  uint32_t x[kScanItems];
+  uint64_t v = 0;
+  for (int i = 0; i < kScanItems; ++i) {
+    x[i] = at + i < n ? q[at + i] : 0u;
+    v += x[i];
+  }
+  uint64_t run = tile_off[blockIdx.x] + (block_scan_inclusive(v, s) - v);
+  for (int i = 0; i < kScanItems; ++i) {
+    run += x[i];
+    if (at + i < n) out[at + i] = run;
+  }
+}
+
+// agz_replay_sample under rho > 0: one lane per sample.  Sample b is the position agz_weighted_pick finds for its draw in
+// the prefix qcum of all npos arena positions (with replacement), mapped to (game, ply) by the binary search over the
+// position prefix pcum that k_replay_sample makes.  Everything behind the draw is k_replay_sample's.
+__global__ __launch_bounds__(kWave) void k_replay_sample_weighted(uint64_t seed, uint64_t call, int B,
+                                                                   const uint64_t* qcum, int64_t npos,
+                                                                   const int64_t* pcum, const int64_t* goff,
+                                                                   int64_t ngames, int sym_mode, int64_t* rec_off,
+                                                                   int32_t* ply, int32_t* sym, int64_t* game_out,
+                                                                   int32_t* ply_out) {
+  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (b >= B) return;
+  const int64_t a = agz_weighted_pick(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_WEIGHTED, (uint64_t)b), qcum, npos);
+  int64_t lo = 0, hi = ngames;                                    // pcum[lo] <= a < pcum[hi]
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (pcum[mid] <= a) lo = mid; else hi = mid;
+  }
+  const int32_t p = (int32_t)(a - pcum[lo]);
+  rec_off[b] = goff[lo];
+  ply[b] = p;
+  if (sym)
+    sym[b] = sym_mode == AGZ_SYMMETRY_RANDOM
+                 ? (int32_t)agz_index(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_SYM, (uint64_t)b), 8u)
+                 : sym_mode;
+  if (game_out) game_out[b] = lo;
+  if (ply_out) ply_out[b] = p;
+}
+
 __global__ void k_debug_draws(uint64_t seed, uint64_t game, uint32_t move, int n, double alpha, double* out) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a < n) out[a] = agz_dirichlet_gamma(seed, game, move, (uint32_t)a, alpha);
@@ -1282,6 +1452,9 @@ void Engine::replay_reanalyze_commit(int64_t counts_out[3]) {
   down(c, ra_counts_.p, 3);
   wait();
   ra_committed_ = true;
+  // the run's games carry new pi rows: their surprise scores are of the old ones (agz_replay_score scores them again)
+  for (size_t j = 0; j + 1 < rv_off_host_.size(); ++j) rp_scored_[(size_t)ra_first_ + j] = 0;
+  ++sp_epoch_;
   if (counts_out)
     for (int i = 0; i < 3; ++i) counts_out[i] = (int64_t)c[i];
 }
@@ -1657,6 +1830,7 @@ int64_t Engine::replay_ingest_chunks(const uint8_t* dbuf, const std::vector<int6
     for (int64_t i = 0; i < found[c]; ++i) {
       rp_off_.push_back((int64_t)rp_used_ + off[first[c] + i] - coff[c]);
       rp_hdr_.push_back(hdr[first[c] + i]);
+      rp_scored_.push_back(0);              // a new game has no surprise scores (agz_replay_score)
       rp_positions_ += hdr[first[c] + i].num_moves;
       rp_cum_.push_back(rp_positions_);
     }
@@ -1769,6 +1943,21 @@ void Engine::replay_drop_front(size_t drop) {
     rp_tcum_.erase(rp_tcum_.begin(), rp_tcum_.begin() + drop);
     for (auto& c : rp_tcum_) c -= t0;
   }
+  if (d_sp_kl_.p) {                 // so do the surprise scores and their target flags, as far as they were ever written
+    const size_t c0 = (size_t)rp_cum_[drop], have = d_sp_kl_.n > c0 ? std::min(d_sp_kl_.n - c0, (size_t)pos) : 0;
+    DevBuf<double> nk;
+    DevBuf<uint8_t> ng;
+    nk.alloc(std::max((size_t)pos, (size_t)1 << 16));
+    ng.alloc(nk.n);
+    if (have) {
+      AGZ_HIP(hipMemcpyAsync(nk.p, d_sp_kl_.p + c0, sizeof(double) * have, hipMemcpyDeviceToDevice, stream_));
+      AGZ_HIP(hipMemcpyAsync(ng.p, d_sp_tgt_.p + c0, have, hipMemcpyDeviceToDevice, stream_));
+    }
+    wait();
+    nk.swap(d_sp_kl_);
+    ng.swap(d_sp_tgt_);
+  }
+  rp_scored_.erase(rp_scored_.begin(), rp_scored_.begin() + drop);
   rp_off_.erase(rp_off_.begin(), rp_off_.begin() + drop);
   rp_hdr_.erase(rp_hdr_.begin(), rp_hdr_.begin() + drop);
   for (auto& o : rp_off_) o -= (int64_t)cut;
@@ -1791,6 +1980,7 @@ void Engine::replay_clear() {
   ++rp_change_;
   rp_off_.clear();
   rp_hdr_.clear();
+  rp_scored_.clear();               // (the surprise scores go with their games; rho is a setting and stays)
   rp_cum_.assign(1, 0);
   rp_tcum_.assign(1, 0);
   rp_used_ = 0;
@@ -1877,8 +2067,12 @@ void Engine::replay_sample(int B, uint64_t call, int sym_mode, float* feats, flo
                            int32_t* ply_out) {
   const int64_t L = replay_live_positions();
   AGZ_REQUIRE(B >= 1 && B <= kSampleMax, AGZ_BAD_ARGUMENT, "batch %d: 1..%d samples", B, kSampleMax);
-  AGZ_REQUIRE(B <= L, AGZ_BAD_ARGUMENT, "batch %d from a window of %lld entries (sampling without replacement)", B,
-              (long long)L);
+  const bool weighted = sp_rho_ > 0.0;      // agz_replay_set_surprise: drawn by weight, with replacement
+  if (weighted)
+    AGZ_REQUIRE(L >= 1, AGZ_BAD_ARGUMENT, "batch %d from an empty window", B);
+  else
+    AGZ_REQUIRE(B <= L, AGZ_BAD_ARGUMENT, "batch %d from a window of %lld entries (sampling without replacement)", B,
+                (long long)L);
   AGZ_REQUIRE(L <= 0x7fffffffLL, AGZ_BAD_ARGUMENT, "window of %lld entries: at most 2^31 - 1", (long long)L);
   AGZ_REQUIRE(sym_mode >= AGZ_SYMMETRY_NONE && sym_mode <= AGZ_SYMMETRY_RANDOM, AGZ_BAD_ARGUMENT,
               "sym_mode %d: -1 (none), 0..7 (fixed T_s) or 8 (drawn)", sym_mode);
@@ -1890,13 +2084,164 @@ void Engine::replay_sample(int B, uint64_t call, int sym_mode, float* feats, flo
   smp_sym_.ensure(kSampleMax);
   smp_boards_.ensure((size_t)B * 8 * V_.PP);
   const bool with_sym = sym_mode != AGZ_SYMMETRY_NONE;
-  hipLaunchKernelGGL(k_replay_sample, dim3(1), dim3(kSampleThreads), 0, stream_, (uint64_t)V_.seed, call, B, L,
-                     rp_entry_cum()[(size_t)rp_first_game_] + rp_first_ply_,
-                     (const int64_t*)(rp_targets_only_ ? d_rp_tcum_.p : d_rp_cum_.p), (const int64_t*)d_rp_off_.p,
-                     (const int64_t*)d_rp_cum_.p, (const int16_t*)(rp_targets_only_ ? d_rp_tply_.p : nullptr), n, sym_mode,
-                     smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, game_out, ply_out);
+  if (weighted) {
+    replay_weights_to_device();
+    AGZ_REQUIRE(sp_total_ > 0, AGZ_BAD_ARGUMENT, "every live entry has weight 0 (rho = %g)", sp_rho_);
+    hipLaunchKernelGGL(k_replay_sample_weighted, dim3((unsigned)((B + kWave - 1) / kWave)), dim3(kWave), 0, stream_,
+                       (uint64_t)V_.seed, call, B, (const uint64_t*)d_sp_qcum_.p, rp_positions_,
+                       (const int64_t*)d_rp_cum_.p, (const int64_t*)d_rp_off_.p, n, sym_mode, smp_off_.p, smp_ply_.p,
+                       with_sym ? smp_sym_.p : nullptr, game_out, ply_out);
+  } else {
+    hipLaunchKernelGGL(k_replay_sample, dim3(1), dim3(kSampleThreads), 0, stream_, (uint64_t)V_.seed, call, B, L,
+                       rp_entry_cum()[(size_t)rp_first_game_] + rp_first_ply_,
+                       (const int64_t*)(rp_targets_only_ ? d_rp_tcum_.p : d_rp_cum_.p), (const int64_t*)d_rp_off_.p,
+                       (const int64_t*)d_rp_cum_.p, (const int16_t*)(rp_targets_only_ ? d_rp_tply_.p : nullptr), n,
+                       sym_mode, smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, game_out, ply_out);
+  }
   AGZ_HIP(hipGetLastError());
   emit_replay_batch(B, smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, smp_boards_.p, feats, pi, z);
+}
+
+// ---- policy surprise weighting (include/agz_surprise.h)
+
+// room in d_sp_kl_ / d_sp_tgt_ for every arena position; what has been written stays where it is
+void Engine::replay_scores_reserve() {
+  const size_t need = (size_t)rp_positions_;
+  if (d_sp_kl_.n >= need && d_sp_kl_.p) return;
+  DevBuf<double> nk;
+  DevBuf<uint8_t> ng;
+  nk.alloc(std::max<size_t>(2 * need, (size_t)1 << 16));
+  ng.alloc(nk.n);
+  if (d_sp_kl_.n) {
+    AGZ_HIP(hipMemcpyAsync(nk.p, d_sp_kl_.p, sizeof(double) * d_sp_kl_.n, hipMemcpyDeviceToDevice, stream_));
+    AGZ_HIP(hipMemcpyAsync(ng.p, d_sp_tgt_.p, d_sp_tgt_.n, hipMemcpyDeviceToDevice, stream_));
+  }
+  wait();
+  nk.swap(d_sp_kl_);
+  ng.swap(d_sp_tgt_);
+}
+
+// the per-game scored flags on the device (a byte per game: all of them, every time)
+void Engine::replay_scored_to_device() {
+  const size_t n = rp_hdr_.size();
+  if (d_sp_scored_.n < n) d_sp_scored_.alloc(std::max<size_t>(2 * n, 1024));
+  up(d_sp_scored_.p, rp_scored_.data(), n);
+  wait();
+}
+
+// agz_replay_score: the games' plies in chunks of at most the engine's forward batch -- k_replay_arena_batch for the
+// features, the staged forward of the ABI calls (its buffers are not the ones the games in flight use), k_replay_surprise
+// for one score per row.  Everything runs on stream_, between steps.
+int64_t Engine::replay_score(int64_t first, int64_t count) {
+  AGZ_REQUIRE(!cfg_.external_network, AGZ_BAD_ARGUMENT,
+              "score: engine was created with external_network=1 and has no network to score on");
+  AGZ_REQUIRE(!(ra_on_ && !ra_committed_), AGZ_BAD_ARGUMENT, "score: a reanalysis run is open; commit it first");
+  const int64_t n = (int64_t)rp_hdr_.size();
+  AGZ_REQUIRE(first >= 0 && count >= 0 && count <= n && first <= n - count, AGZ_BAD_ARGUMENT,
+              "score: games %lld .. %lld + %lld: the replay arena holds %lld", (long long)first, (long long)first,
+              (long long)count, (long long)n);
+  if (count == 0) return 0;
+  const int64_t pos0 = rp_cum_[(size_t)first], rows = rp_cum_[(size_t)(first + count)] - pos0;
+  std::vector<int64_t> off((size_t)rows);
+  std::vector<int32_t> ply((size_t)rows);
+  for (int64_t k = first, r = 0; k < first + count; ++k)
+    for (int32_t t = 0; t < rp_hdr_[(size_t)k].num_moves; ++t, ++r) {
+      off[(size_t)r] = rp_off_[(size_t)k];
+      ply[(size_t)r] = t;
+    }
+  replay_scores_reserve();
+  sp_count_.ensure(1);
+  sp_count_.zero(stream_);
+  unsigned long long targets = 0;
+  if (rows > 0) {
+    sp_off_.ensure((size_t)rows);
+    sp_ply_.ensure((size_t)rows);
+    up(sp_off_.p, off.data(), (size_t)rows);
+    up(sp_ply_.p, ply.data(), (size_t)rows);
+    const int cap = bcap_;
+    s_boards_.ensure((size_t)cap * 8 * V_.PP);
+    d_whcn_.ensure((size_t)cap * 17 * V_.P);
+    for (int64_t r0 = 0; r0 < rows; r0 += cap) {
+      const int Bc = (int)std::min<int64_t>(cap, rows - r0);
+      hipLaunchKernelGGL(k_replay_arena_batch, dim3(Bc), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
+                         (const int64_t*)(sp_off_.p + r0), (const int32_t*)(sp_ply_.p + r0), s_boards_.p, d_whcn_.p,
+                         (float*)nullptr, (float*)nullptr);
+      launch_whcn_to_x32(d_whcn_.p, Bc, V_.N, stage_forward(Bc), stream_);
+      forward_x32(Bc);
+      hipLaunchKernelGGL(k_replay_surprise, dim3(Bc), dim3(kWave), 0, stream_, (const uint8_t*)rp_buf_.p,
+                         (const int64_t*)(sp_off_.p + r0), (const int32_t*)(sp_ply_.p + r0), (const float*)s_f32b_.p, V_.A,
+                         d_sp_kl_.p + pos0 + r0, d_sp_tgt_.p + pos0 + r0, sp_count_.p);
+      AGZ_HIP(hipGetLastError());
+      wait();                           // Bc was uploaded from this frame (stage_forward)
+      net().check_async_error();
+    }
+    down(&targets, sp_count_.p, 1);
+    wait();
+  }
+  for (int64_t k = first; k < first + count; ++k) rp_scored_[(size_t)k] = 1;
+  ++sp_epoch_;
+  return (int64_t)targets;
+}
+
+// rho of agz_replay_sample's draw.  A host-side value read at the next sample call: it may change at any time, and
+// agz_replay_clear leaves it alone.
+void Engine::replay_set_surprise(double rho) {
+  AGZ_REQUIRE(agz_surprise_rho_ok(rho), AGZ_BAD_ARGUMENT, "surprise: rho %g: 0..1", rho);
+  sp_rho_ = rho;
+}
+
+// game k's scores, its q under the rho in force (k_replay_weights on that game alone, without the sampler's masks) and
+// its scored flag
+void Engine::replay_surprise(int64_t k, double* kl_out, uint32_t* q_out, int32_t* scored_out) {
+  AGZ_REQUIRE(k >= 0 && k < (int64_t)rp_hdr_.size(), AGZ_BAD_ARGUMENT, "replay game %lld out of range", (long long)k);
+  const size_t nm = (size_t)rp_hdr_[(size_t)k].num_moves;
+  const bool sc = rp_scored_[(size_t)k] != 0;
+  if (scored_out) *scored_out = sc ? 1 : 0;
+  if (nm == 0) return;
+  if (kl_out) {
+    if (sc) down(kl_out, d_sp_kl_.p + rp_cum_[(size_t)k], nm);
+    else std::fill(kl_out, kl_out + nm, 0.0);
+  }
+  if (q_out) {
+    replay_index_to_device();
+    replay_scored_to_device();
+    d_sp_q_.ensure(std::max<size_t>((size_t)rp_positions_, (size_t)1 << 16));     // (the sampler reads d_sp_qcum_ only)
+    hipLaunchKernelGGL(k_replay_weights, dim3(1), dim3(kWave), 0, stream_, (const int64_t*)d_rp_cum_.p, k,
+                       (const uint8_t*)d_sp_scored_.p, (const double*)d_sp_kl_.p, (const uint8_t*)d_sp_tgt_.p, sp_rho_,
+                       (int64_t)0, (int64_t)0, (const int64_t*)nullptr, (const int16_t*)nullptr, d_sp_q_.p,
+                       rp_cum_[(size_t)k]);
+    AGZ_HIP(hipGetLastError());
+    down(q_out, d_sp_q_.p, nm);
+  }
+  wait();
+}
+
+// q of every arena position and its inclusive prefix on the device, if the arena, the scores or rho changed since they
+// were built: k_replay_weights, then the scan in three launches; the total comes back for the sampler's check
+void Engine::replay_weights_to_device() {
+  if (sp_built_ && sp_built_change_ == rp_change_ && sp_built_epoch_ == sp_epoch_ && sp_built_rho_ == sp_rho_) return;
+  const int64_t n = (int64_t)rp_hdr_.size(), npos = rp_positions_;
+  replay_index_to_device();
+  replay_scored_to_device();
+  const int64_t ntiles = (npos + kScanTile - 1) / kScanTile;
+  if (d_sp_q_.n < (size_t)npos) d_sp_q_.alloc(std::max<size_t>(2 * (size_t)npos, (size_t)1 << 16));
+  if (d_sp_qcum_.n < (size_t)npos) d_sp_qcum_.alloc(std::max<size_t>(2 * (size_t)npos, (size_t)1 << 16));
+  if (d_sp_tiles_.n < (size_t)ntiles) d_sp_tiles_.alloc(std::max<size_t>(2 * (size_t)ntiles, 1024));
+  hipLaunchKernelGGL(k_replay_weights, dim3((unsigned)n), dim3(kWave), 0, stream_, (const int64_t*)d_rp_cum_.p, (int64_t)0,
+                     (const uint8_t*)d_sp_scored_.p, (const double*)d_sp_kl_.p, (const uint8_t*)d_sp_tgt_.p, sp_rho_,
+                     rp_first_game_, rp_first_ply_, (const int64_t*)(rp_targets_only_ ? d_rp_tcum_.p : nullptr),
+                     (const int16_t*)(rp_targets_only_ ? d_rp_tply_.p : nullptr), d_sp_q_.p, (int64_t)0);
+  hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)ntiles), dim3(kScanThreads), 0, stream_, (const uint32_t*)d_sp_q_.p,
+                     npos, d_sp_tiles_.p);
+  hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kScanTop), 0, stream_, d_sp_tiles_.p, ntiles);
+  hipLaunchKernelGGL(k_scan_add, dim3((unsigned)ntiles), dim3(kScanThreads), 0, stream_, (const uint32_t*)d_sp_q_.p, npos,
+                     (const uint64_t*)d_sp_tiles_.p, d_sp_qcum_.p);
+  AGZ_HIP(hipGetLastError());
+  sp_total_ = fetch(d_sp_qcum_.p + (npos - 1));
+  sp_built_ = true;
+  sp_built_change_ = rp_change_;
+  sp_built_epoch_ = sp_epoch_;
+  sp_built_rho_ = sp_rho_;
 }
 
 // the arena's index (rp_off_, rp_cum_ and, targets-only, rp_tcum_) on the device: only what changed since the last call

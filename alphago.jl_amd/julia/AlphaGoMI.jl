@@ -826,6 +826,43 @@ function extract_value_targets(p::Union{MCTSPlayer, SelfPlayPlayer}, value_targe
   positions[keep], pis[keep], y[keep]        # a kept ply sums the qs of the dropped plies behind it
 end
 
+# Policy surprise weighting (ours; include/agz.h agz_replay_score, include/agz_surprise.h): one KL(π ‖ prior) per ply of
+# arena games first .. first+count-1 (0-based) on the selected network; under rho > 0 agz_replay_sample draws by weight,
+# with replacement -- per scored game a share 1 - rho of the mass evenly over its target plies, rho in proportion to the
+# scores.  rho = 0 (the default) is off.
+function replay_score!(e::Engine, first::Integer = 0, count::Union{Nothing, Integer} = nothing)
+  n = count === nothing ? ccall((:agz_replay_count, libagz), Int64, (Ptr{Cvoid},), e.handle) - first : count
+  rows = Ref{Int64}(0)
+  check(e, ccall((:agz_replay_score, libagz), Int32, (Ptr{Cvoid}, Int64, Int64, Ref{Int64}), e.handle, first, n, rows))
+  Int(rows[])
+end
+function replay_set_surprise!(e::Engine, rho::Real = 0.0)
+  check(e, ccall((:agz_replay_set_surprise, libagz), Int32, (Ptr{Cvoid}, Float64), e.handle, rho))
+end
+# (kl [num_moves], q [num_moves] under the rho in force, scored) of arena game k (0-based)
+function replay_surprise(e::Engine, k::Integer)
+  h = Ref{AgzGameHeader}()
+  check(e, ccall((:agz_replay_header, libagz), Int32, (Ptr{Cvoid}, Int64, Ref{AgzGameHeader}), e.handle, k, h))
+  n = Int(h[].num_moves)
+  kl, q, sc = zeros(Float64, max(n, 1)), zeros(UInt32, max(n, 1)), Ref{Int32}(0)
+  check(e, ccall((:agz_replay_surprise, libagz), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{UInt32}, Ref{Int32}),
+                 e.handle, k, kl, q, sc))
+  kl[1:n], q[1:n], sc[] != 0
+end
+# the same for one game held on the host (no engine): pis and ps are A x T (one column per ply, as the C rows lie)
+function surprise_weights(pis::Matrix{Float32}, ps::Matrix{Float32}, rho::Real)
+  A, T = size(pis)
+  size(ps) == (A, T) || throw(ArgumentError("surprise weights: pis and ps must have the same size"))
+  kl, q = zeros(Float64, T), zeros(UInt32, T)
+  st = ccall((:agz_surprise_weights, libagz), Int32,
+             (Ptr{Float32}, Ptr{Float32}, Int32, Int32, Float64, Ptr{Float64}, Ptr{UInt32}), pis, ps, T, A, rho, kl, q)
+  st == 0 || throw(ArgumentError("surprise weights: rho $rho must lie in 0..1"))
+  kl, q
+end
+# the index agz_replay_sample's weighted draw picks for the 64-bit draw u in the inclusive prefix cum (0-based; -1: no mass)
+surprise_pick(cum::Vector{UInt64}, u::UInt64) =
+  Int(ccall((:agz_surprise_pick, libagz), Int64, (Ptr{UInt64}, Int64, UInt64), cum, length(cum), u))
+
 # Forced playouts and policy target pruning (ours; include/agz.h agz_selfplay_set_forced_playouts): in a full self-play
 # search a visited root child a with N_a^2 < k P_a sum(N) is selected ahead of the PUCT arg-max; with prune the recorded π
 # row leaves out the forced visits the search did not agree with.  k = 0 switches both off; KataGo plays k = 2.
@@ -1365,7 +1402,7 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
                starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing,
                forced_playouts = nothing, prune_targets::Bool = true,
                gumbel = nothing, gumbel_c_visit::Real = 50.0, gumbel_c_scale::Real = 1.0, value_target = nothing,
-               fpu = nothing, c_base::Real = 0.0)
+               fpu = nothing, c_base::Real = 0.0, surprise::Real = 0.0)
   (gumbel !== nothing && gumbel != 0 && forced_playouts !== nothing && forced_playouts != 0) &&
     throw(ArgumentError("gumbel and forced_playouts are two rules for the same decision: ask for one"))
   cur_nn = model === nothing ? NeuralNet(env; tower_height = tower_height) : model                       # train.jl:43
@@ -1391,6 +1428,7 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
   gumbel === nothing || set_gumbel!(e, gumbel, gumbel_c_visit, gumbel_c_scale)             # m, as in selfplay
   apply_puct!(e, fpu, c_base)                                                              # as in selfplay
   value_target === nothing || replay_set_value_target!(e, value_target[1], value_target[2])   # (alpha, lam): z of the batches
+  replay_set_surprise!(e, surprise)       # rho: each game is scored as it is filed, the batches are drawn by weight
   check(e, ccall((:agz_selfplay_set_hold, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 1))
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, num_games))
   check(e, ccall((:agz_selfplay_release, libagz), Int32, (Ptr{Cvoid},), e.handle))
@@ -1409,6 +1447,7 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
     for (h, k) in heads
       check(e, ccall((:agz_replay_ingest_records, libagz), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}),
                      e.handle, k, 1, C_NULL))                                                          # train.jl:60-61
+      surprise > 0 && replay_score!(e, ccall((:agz_replay_count, libagz), Int64, (Ptr{Cvoid},), e.handle) - 1, 1)
       check(e, ccall((:agz_replay_set_window, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, memory_size))   # :63-65
       i += 1
       if ccall((:agz_replay_live_positions, libagz), Int64, (Ptr{Cvoid},), e.handle) >= start_training_after   # :67

@@ -3,6 +3,7 @@
 self-play -> replay arena -> training batches -> optimiser step -> arena match -> checkpoint.
 
     python examples/generation_loop.py [--board 9] [--tower 2] [--games 32] [--readouts 64] [--reanalyze]
+                                       [--surprise RHO]
 
 What runs where:
   selfplay          G concurrent games on the device (one wave per tree, one network batch per step)
@@ -11,6 +12,8 @@ What runs where:
                     arena and emits the N x N x 17 x B feature tensor, pi and z (agz_replay_batch)
   reanalyze         (--reanalyze) the arena's games are searched again on the current weights and their pi / q
                     targets overwritten in place, moves and results as played (agz_replay_reanalyze_start / _commit)
+  surprise          (--surprise RHO) every arena ply is scored by KL(pi || prior) on the current weights and the batches
+                    are drawn on the device by weight, with replacement (agz_replay_score / agz_replay_set_surprise)
   _train            agz_train_step: training-mode forward, 0.01 CE + 0.01 MSE + 1e-4 L2, backward, Momentum(0.02)
   evaluate          candidate vs incumbent, both networks resident in one arena engine
   save_model        BSON parameter lists readable by Flux.loadparams!
@@ -37,6 +40,9 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--eval-games", type=int, default=8)
     ap.add_argument("--reanalyze", action="store_true", help="refresh the arena's targets before the training batches")
+    ap.add_argument("--surprise", type=float, default=0.0, metavar="RHO",
+                    help="policy surprise weighting: draw the training batches by weight, this share of each game's "
+                         "sampling mass in proportion to KL(pi || prior)")
     args = ap.parse_args(argv)
 
     env = ag.GoEnv(args.board)
@@ -65,10 +71,17 @@ def main(argv=None):
     if args.reanalyze:
         counts, _ = ag.reanalyze(eng)
         print(f"reanalyse: {counts['committed']} rows refreshed ({counts['pi_rows']} pi rows), {counts['skipped']} skipped")
+    if args.surprise > 0:
+        eng.replay_set_surprise(args.surprise)
+        print(f"surprise: {eng.replay_score()} target plies scored, rho = {args.surprise}")
     rng = np.random.default_rng(1)
     lens = np.array([eng.replay_record(k)["num_moves"] for k in range(eng.replay_count())])
     losses = []
     for it in range(3):
+        if args.surprise > 0:                                                     # drawn on the device, by weight
+            f, p, zz, _, _ = eng.replay_sample(B, it)
+            losses.append(float(eng.train_step_device(f, p, zz, B)[0]))
+            continue
         flat = rng.choice(int(lens.sum()), size=B, replace=False)                 # sample(1:n, B, replace=false)
         game = np.searchsorted(np.cumsum(lens), flat, side="right")
         ply = flat - (np.cumsum(lens) - lens)[game]

@@ -413,6 +413,48 @@ agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on);
  * call: it may be set at any time, and agz_replay_clear leaves it as it is.  AGZ_BAD_ARGUMENT, with the setting in
  * force kept, when alpha or lambda is a NaN or outside [0, 1]. */
 agz_status agz_replay_set_value_target(agz_engine* e, double alpha, double lambda);
+/* Policy surprise weighting (include/agz_surprise.h holds the arithmetic): how often agz_replay_sample
+ * draws a ply.  The score of a target ply (pi row not all zero) is KL(pi || p) of its recorded pi from the prior p the
+ * network gives for its position, summed in double in ascending action order over pi[a] > 0, p floored at FLT_MIN, logs
+ * by agz_log.  Under rho a scored game's n target plies with scores s_t summing (in ply order) to S weigh
+ *     w_t = (1.0 - rho) + rho * ((s_t * (double)n) / S)   (S > 0; else 1.0),     q_t = (uint32_t)(w_t * 65536.0 + 0.5)
+ * and every other ply (no target, or a game without scores) weighs 1.0, q = 65536.
+ *
+ * agz_replay_score scores arena games first .. first + count - 1 on the network chosen by agz_net_select, at the
+ * precision in force: in chunks of at most the engine's forward batch it rebuilds the features of every ply of the games
+ * on the device, runs the forward and keeps one score per ply on the device, next to the arena, plus a "scored" flag per
+ * game; rows_out (may be NULL) = target plies scored.  A score is as of the network it was computed on: weight updates
+ * leave it alone, a second call replaces it.  It runs on the engine's stream between steps and leaves the games in
+ * flight as they are.  AGZ_BAD_ARGUMENT on an external_network engine, for a range outside the arena and while a
+ * reanalysis run is open (started, not committed).  Games filed later are unscored; agz_replay_trim and the window move
+ * the scores with their games; agz_replay_clear drops them; agz_replay_reanalyze_commit marks its games unscored (their
+ * pi changed).
+ *
+ * agz_replay_set_surprise: rho = 0 (the default) is OFF -- agz_replay_sample is the call stated above, the Floyd draw bit
+ * for bit, and nothing is launched or allocated for this feature.  With rho > 0 sample b of agz_replay_sample is position
+ *     agz_weighted_pick(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_WEIGHTED, b), C, positions)
+ * of the arena, C the inclusive prefix (uint64) of q over all arena positions in arena order with q forced to 0 for the
+ * plies in front of the window and, in a targets-only arena, for the plies that are no targets; the pick is
+ * r = floor(draw * C[last] / 2^64) and the smallest index with C[i] > r.  The draw is WITH replacement: 1 <= B <= 2048,
+ * L >= 1, B may exceed L (AGZ_BAD_ARGUMENT if every live q is 0).  The symmetry draw, the value target, game_out /
+ * ply_out and the batch kernels are the same.  C is rebuilt on the device (one wave per game, then a scan in three
+ * launches) at the first sample call after the arena, the scores or rho changed.  rho is kept on the host and read at
+ * the next sample call: it may be set at any time, and agz_replay_clear leaves it alone.  AGZ_BAD_ARGUMENT, with the
+ * setting in force kept, when rho is a NaN or outside [0, 1].
+ *
+ * agz_replay_surprise: for arena game k, kl_out double[num_moves] (0 for a ply that is no target and for a game without
+ * scores), q_out uint32[num_moves] under the rho in force (without the window and targets-only masks) and scored_out;
+ * each may be NULL.
+ *
+ * agz_surprise_weights (host only, no engine): the same score and q for one game the caller holds, pis and ps float[T][A]
+ * (the game counts as scored).  agz_surprise_pick (host only): agz_weighted_pick over cum[0..n-1], -1 when cum is NULL,
+ * n < 1 or cum[n-1] = 0. */
+agz_status agz_replay_score(agz_engine* e, int64_t first, int64_t count, int64_t* rows_out);
+agz_status agz_replay_set_surprise(agz_engine* e, double rho);
+agz_status agz_replay_surprise(agz_engine* e, int64_t k, double* kl_out, uint32_t* q_out, int32_t* scored_out);
+agz_status agz_surprise_weights(const float* pis, const float* ps, int32_t T, int32_t A, double rho, double* kl_out,
+                                uint32_t* q_out);
+int64_t agz_surprise_pick(const uint64_t* cum, int64_t n, uint64_t u);
 /* device memory on the engine's GPU for a host without its own allocator (the Julia stub's train): agz_replay_sample's
  * outputs, agz_train_step's device inputs.  Freed by agz_device_free (after the engine's stream has used it). */
 agz_status agz_device_alloc(agz_engine* e, int64_t bytes, void** out);

@@ -61,6 +61,9 @@
 #define AGZ_SITE_GUMBEL 12u        /* agz_selfplay_set_gumbel: move = position.n of the root
                                     * searched, idx = action; the Gumbel variable
                                     * g = -agz_log(-agz_log(agz_u01(draw)))           */
+#define AGZ_SITE_REPLAY_WEIGHTED 13u  /* agz_replay_sample under agz_replay_set_surprise: game = call,
+                                       * move = 0, idx = sample b; the position
+                                       * agz_weighted_pick(draw, prefix of q, positions)  */
 
 static inline AGZ_HD uint64_t agz_mix64(uint64_t z) {
   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
