@@ -1,6 +1,17 @@
 """HIP network (features + MFMA tower + heads, through the C ABI) against the oracle.
 Tolerance: |d pi|, |d v| <= 1e-4 versus the float64 oracle (BASELINE.json north_star); feature
-planes are integer-valued and must match exactly."""
+planes are integer-valued and must match exactly.
+
+What these cases see of the tower (float64 oracle, head planes read before their ReLU through tests/trunk_probe.py): on the
+`or_net_init_synthetic(3)` + `randomize_bn` networks below the value-conv plane is negative at every point of every board -- v
+is one constant, |dv| checks nothing of the tower, the value conv or value FC1 -- in test_forward_matches_oracle at (5, 1, 7),
+(9, 10, 16) and (19, 3, 5), and in test_every_tiling_class_of_the_winograd_tower at N = 3, 4, 6, 8, 12, 13, 16 and 18 (live on
+under a tenth of its entries at 10 and 17).  One or both policy-conv planes are dead, or live on under a tenth of their
+entries, in every case except that test's N = 3 and 10; at (5, 1, 7) and at N = 4 all three planes are dead and pi, v do not
+depend on the input at all.
+Where a plane is live it sits behind a softmax with pi max 0.004 .. 0.1.  These tests keep their meaning for layouts, batch
+rows and entry points (the bit-for-bit assertions); the arithmetic of every tower form is held against float64 on the trunk
+itself, and pi / v on networks with live heads, in tests/test_gpu_trunk.py."""
 import ctypes as C
 
 import numpy as np

@@ -33,30 +33,41 @@ def randomize_bn(net, layers, rng):
         L.or_net_set(net, l, orc.K_BIAS, orc.fptr(v), n)
 
 
+def torch_conv(net, l, k, cin, cout, inp):
+    dt = torch.float64
+    w = get_param(net, l, orc.K_WEIGHT).reshape(cout, cin, k, k)   # col-major [a,b,ci,o] -> [o,ci,b,a]
+    w = torch.tensor(w, dtype=dt).permute(0, 1, 3, 2)               # [o, ci, a, b]
+    w = torch.flip(w, dims=(2, 3))                                  # true convolution
+    b = torch.tensor(get_param(net, l, orc.K_BIAS), dtype=dt)
+    y = torch.nn.functional.conv2d(inp, w, b, padding=k // 2)
+    g = torch.tensor(get_param(net, l, orc.K_BN_GAMMA), dtype=dt)
+    be = torch.tensor(get_param(net, l, orc.K_BN_BETA), dtype=dt)
+    mu = torch.tensor(get_param(net, l, orc.K_BN_MEAN), dtype=dt)
+    var = torch.tensor(get_param(net, l, orc.K_BN_VAR), dtype=dt)
+    eps = float(get_param(net, l, orc.K_BN_EPS)[0])
+    return torch.nn.functional.batch_norm(y, mu, var, g, be, training=False, eps=eps)
+
+
+def torch_trunk(net, tower, x_bcij):
+    """stem + tower in float64: x [B, 17, i, j] -> h [B, 256, i, j], what both heads read"""
+    x = torch.tensor(x_bcij, dtype=torch.float64)
+    h = torch.relu(torch_conv(net, 0, 3, 17, 256, x))
+    for blk in range(tower):
+        t = torch.relu(torch_conv(net, 1 + 2 * blk, 3, 256, 256, h))
+        h = torch.relu(torch_conv(net, 2 + 2 * blk, 3, 256, 256, t) + h)
+    return h
+
+
 def torch_forward(net, N, tower, x_whcn):
     """x_whcn: (B, 17, N, N) indexed [b, c, j(col), i(row)] is awkward; build [b,c,i,j]."""
     P = N * N
     B = x_whcn.shape[0]
     dt = torch.float64
-    x = torch.tensor(x_whcn, dtype=dt)   # [B, 17, i, j]
 
     def conv(l, k, cin, cout, inp):
-        w = get_param(net, l, orc.K_WEIGHT).reshape(cout, cin, k, k)   # col-major [a,b,ci,o] -> [o,ci,b,a]
-        w = torch.tensor(w, dtype=dt).permute(0, 1, 3, 2)               # [o, ci, a, b]
-        w = torch.flip(w, dims=(2, 3))                                  # true convolution
-        b = torch.tensor(get_param(net, l, orc.K_BIAS), dtype=dt)
-        y = torch.nn.functional.conv2d(inp, w, b, padding=k // 2)
-        g = torch.tensor(get_param(net, l, orc.K_BN_GAMMA), dtype=dt)
-        be = torch.tensor(get_param(net, l, orc.K_BN_BETA), dtype=dt)
-        mu = torch.tensor(get_param(net, l, orc.K_BN_MEAN), dtype=dt)
-        var = torch.tensor(get_param(net, l, orc.K_BN_VAR), dtype=dt)
-        eps = float(get_param(net, l, orc.K_BN_EPS)[0])
-        return torch.nn.functional.batch_norm(y, mu, var, g, be, training=False, eps=eps)
+        return torch_conv(net, l, k, cin, cout, inp)
 
-    h = torch.relu(conv(0, 3, 17, 256, x))
-    for blk in range(tower):
-        t = torch.relu(conv(1 + 2 * blk, 3, 256, 256, h))
-        h = torch.relu(conv(2 + 2 * blk, 3, 256, 256, t) + h)
+    h = torch_trunk(net, tower, x_whcn)
     vh = torch.relu(conv(orc.L_VALUE_CONV, 1, 256, 1, h))     # [B,1,i,j]
     ph = torch.relu(conv(orc.L_POLICY_CONV, 1, 256, 2, h))    # [B,2,i,j]
     # Julia reshape of W x H x C x B (column-major) => index i + N*j + P*c
