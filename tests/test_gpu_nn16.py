@@ -8,6 +8,10 @@ Two bars, both written here:
     boundary (one half ulp = 4.9e-4 relative of that activation).
   * TOLMIX = 1e-2 against the exact f64 network: the price of half storage itself -- this mode does
     NOT meet the 1e-4 bar of the default f32 path and is not what bench.py measures.
+Both bars have to let through the half roundings that f32 and f64 sums place differently, and one such flip is as large as
+a small structural defect (a truncating store in one epilogue passes every test of this file).  Structural defects of the
+fp16 kernels -- a tap, a halo row, a tile edge, the late flush of the output image, a rounding mode -- are caught in
+tests/test_gpu_exact_tower.py, on networks whose every rounded value is an integer: there the trunk has to agree exactly.
 Integer/tree work stays bit-exact in this mode too: self-play games equal the oracle's when the
 oracle's network callable is this same HIP network."""
 import numpy as np

@@ -12,7 +12,9 @@ Bars, on e_gpu = max |l_gpu - l_f64| against e_ref = max |l_directf32oracle - l_
     weak point 1);
   * f32s (operands as two f16 halves: 22 significant bits against 24): e_gpu <= 32 e_ref;
   * f16: no closer to its restatement (oracle precision 16) than that restatement is to float64 -- reported, and asserted only
-    as e(gpu, restatement) <= e(restatement, f64);
+    as e(gpu, restatement) <= e(restatement, f64): on random weights f32 and f64 sums round to different halves now and then,
+    and no bar under such a flip exists.  What a flip would hide -- structural defects of the fp16 kernels -- is caught in
+    tests/test_gpu_exact_tower.py, where every rounded value is an integer and the trunk has to agree exactly;
   * every form: a row's read-out does not depend on its batch position, to the bit.
 tests/test_trunk_probe.py::test_defect_audit shows a dropped tap or tf32-class weight noise at >= 16 e_ref.  No bar here comes from
 a device measurement.  Then the ordinary heads, on live networks: |dpi|, |dv| <= 1e-4 against float64, the project's bar."""

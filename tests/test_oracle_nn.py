@@ -45,16 +45,22 @@ def torch_conv(net, l, k, cin, cout, inp):
     mu = torch.tensor(get_param(net, l, orc.K_BN_MEAN), dtype=dt)
     var = torch.tensor(get_param(net, l, orc.K_BN_VAR), dtype=dt)
     eps = float(get_param(net, l, orc.K_BN_EPS)[0])
-    return torch.nn.functional.batch_norm(y, mu, var, g, be, training=False, eps=eps)
+    # inference BatchNorm written out (torch's batch_norm refuses eps = 0, which tests/exact_nets.py needs)
+    c = (1, -1, 1, 1)
+    return (y - mu.view(c)) / torch.sqrt(var.view(c) + eps) * g.view(c) + be.view(c)
 
 
-def torch_trunk(net, tower, x_bcij):
-    """stem + tower in float64: x [B, 17, i, j] -> h [B, 256, i, j], what both heads read"""
+def torch_trunk(net, tower, x_bcij, store=None):
+    """stem + tower in float64: x [B, 17, i, j] -> h [B, 256, i, j], what both heads read.  store(kind, blk, a) -> a', if
+    given, stands at the points where the fp16 tower keeps an activation (agz_oracle_nn_impl.inc, forward_ex): "in", the block
+    input as the first convolution loads it (the residual keeps what was stored); "t"; "h", the block output, and "out", the
+    last block's, which that tower leaves in f32."""
+    store = store or (lambda kind, blk, a: a)
     x = torch.tensor(x_bcij, dtype=torch.float64)
     h = torch.relu(torch_conv(net, 0, 3, 17, 256, x))
     for blk in range(tower):
-        t = torch.relu(torch_conv(net, 1 + 2 * blk, 3, 256, 256, h))
-        h = torch.relu(torch_conv(net, 2 + 2 * blk, 3, 256, 256, t) + h)
+        t = store("t", blk, torch.relu(torch_conv(net, 1 + 2 * blk, 3, 256, 256, store("in", blk, h))))
+        h = store("h" if blk + 1 < tower else "out", blk, torch.relu(torch_conv(net, 2 + 2 * blk, 3, 256, 256, t) + h))
     return h
 
 
