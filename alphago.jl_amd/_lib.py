@@ -170,6 +170,12 @@ def load():
         "agz_selfplay_gumbel_counts": (i32, [E, P(i64)]),
         "agz_search_set_puct": (i32, [E, i32, C.c_double, C.c_double, C.c_double]),
         "agz_search_puct_counts": (i32, [E, P(u64)]),
+        "agz_selfplay_set_root_policy_temperature": (i32, [E, i32, C.c_double, C.c_double, C.c_double]),
+        "agz_selfplay_set_root_noise": (i32, [E, C.c_double, i32]),
+        "agz_search_set_move_temperature": (i32, [E, i32, C.c_double, C.c_double, C.c_double]),
+        "agz_search_explore_counts": (i32, [E, P(u64)]),
+        "agz_tree_explore_rows": (i32, [E, i32, i32, f32p, f64p, f32p]),
+        "agz_explore_temperature": (i32, [i32, C.c_double, C.c_double, C.c_double, f64p]),
         "agz_tree_gumbel_pi": (i32, [E, i32, i32, C.c_double, C.c_double, f32p]),
         "agz_analyze_start": (i32, [E, i8p, P(PositionInfo), i8p, i64, u64]),
         "agz_review_start": (i32, [E, P(C.c_int16), P(i64), i8p, P(PositionInfo), i8p, i64, u64]),

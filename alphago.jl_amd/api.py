@@ -460,7 +460,8 @@ class MCTSPlayer:
     plain arrays or Tracker-style objects carrying `.data` (mcts_play.jl:90)."""
 
     def __init__(self, env, network, num_readouts=800, two_player_mode=False, resign_threshold=-0.9, seed=0,
-                 game_id=0, symmetry=None, fpu=None, c_base=0.0):
+                 game_id=0, symmetry=None, fpu=None, c_base=0.0, root_policy_temperature=None, root_noise=None,
+                 move_temperature=None):
         self.env = env
         self.network = network
         self.num_readouts = num_readouts
@@ -479,6 +480,8 @@ class MCTSPlayer:
                 raise ValueError("symmetry needs a NeuralNet of this package: a caller's network receives Positions")
             self.engine.set_symmetry(symmetry)
         _apply_puct(self.engine, fpu, c_base)      # (ours) the PUCT rule options of Engine.set_puct
+        # (ours) root exploration in inject_noise and the move temperature in pick_move, as selfplay() takes them
+        _apply_explore(self.engine, root_policy_temperature, root_noise, move_temperature)
         self._game_id = game_id
         self.qs, self.searches_pi = [], []
         self.result, self.result_string = 0, ""
@@ -690,11 +693,25 @@ def _apply_puct(eng, fpu, c_base):
         eng.set_puct(fpu, c_base)
 
 
+def _apply_explore(eng, root_policy_temperature=None, root_noise=None, move_temperature=None):
+    """root exploration and the move temperature (Engine.set_root_policy_temperature / set_root_noise /
+    set_move_temperature) on a fresh engine; nothing asked for, nothing set"""
+    if root_policy_temperature is not None:
+        eng.set_root_policy_temperature(root_policy_temperature)
+    if root_noise is not None:
+        total_alpha, shaped = root_noise if isinstance(root_noise, (tuple, list)) else (root_noise, False)
+        eng.set_root_noise(total_alpha, shaped)
+    if move_temperature is not None:
+        eng.set_move_temperature(move_temperature)
+
+
 def _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit, gumbel_c_scale,
-                          targets_only_arena=False, fpu=None, c_base=0.0):
+                          targets_only_arena=False, fpu=None, c_base=0.0, root_policy_temperature=None, root_noise=None,
+                          move_temperature=None):
     """selfplay()'s and train()'s search options on a fresh engine (train(): a targets-only arena under the cap)"""
     _refuse_two_root_rules(gumbel, forced_playouts)
     _apply_puct(eng, fpu, c_base)
+    _apply_explore(eng, root_policy_temperature, root_noise, move_temperature)
     if starts:
         eng.set_starts(starts)
     if playout_cap is not None:
@@ -714,7 +731,8 @@ def seed(s):
 
 def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="f32", game_id_base=None, symmetry=None,
              starts=None, playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
-             gumbel_c_scale=1.0, fpu=None, c_base=0.0, **cfg):
+             gumbel_c_scale=1.0, fpu=None, c_base=0.0, root_policy_temperature=None, root_noise=None,
+             move_temperature=None, **cfg):
     """selfplay(env, nn, num_ro) (src/selfplay.jl:1-45) -> the finished game's player (SelfPlayPlayer), exactly the
     call train() makes (train.jl:57).  `games=G` (ours) plays G games concurrently on the device and returns a list of
     G such players ordered by game id.  Game ids continue from the previous call (module stream, `seed()`), unless
@@ -732,7 +750,11 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     Gumbel-top-k, Sequential Halving, the searches_pi row is softmax(log prior + sigma(q)); gumbel_c_visit and
     gumbel_c_scale are sigma's constants.  It composes with playout_cap, starts and symmetry, not with forced_playouts.
     fpu and c_base (ours): the PUCT rule options of Engine.set_puct -- first-play urgency reduction, r or (r, r_root),
-    and the c_puct growth constant -- at every level of every search; they compose with all of the above."""
+    and the c_puct growth constant -- at every level of every search; they compose with all of the above.
+    root_policy_temperature, root_noise, move_temperature (ours): T or (early, late, halflife) -- a softmax temperature on
+    the root prior of a full search; (total_alpha, shaped) -- its Dirichlet noise over the legal moves only, shaped by the
+    prior as in KataGo; T or (early, late, halflife) -- the move is sampled in proportion to N^(1/T(n)) (Engine.set_root_
+    policy_temperature / set_root_noise / set_move_temperature).  Gumbel and fast searches get no root rule."""
     _refuse_two_root_rules(gumbel, forced_playouts)
     single = games is None
     games = 1 if single else int(games)
@@ -751,7 +773,8 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     if symmetry is not None:
         eng.set_symmetry(symmetry)
     _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit, gumbel_c_scale,
-                          fpu=fpu, c_base=c_base)
+                          fpu=fpu, c_base=c_base, root_policy_temperature=root_policy_temperature, root_noise=root_noise,
+                          move_temperature=move_temperature)
     eng.start(games)
     while eng.records_count() < games:
         eng.step(16)
@@ -806,7 +829,8 @@ def _line_rows(env, t):
 
 
 def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=None, two_player_mode=False,
-            symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, fpu=None, c_base=0.0, **cfg):
+            symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, fpu=None, c_base=0.0,
+            move_temperature=None, **cfg):
     """suggest_move over many positions in one device run (ours).  Record i is what
     `MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + i, symmetry=symmetry)`,
     `initialize_game(positions[i])`, `suggest_move()` computes (mcts_play.jl:110-118,144-151), bit for bit, except that
@@ -816,7 +840,10 @@ def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=
     (parallel_readouts = tree_search!'s 8 by default, max_nodes_per_game, pool_policy, ...).
     lines > 0 (at most 16): the rows are AnalysisLines, i.e. Analysis plus `lines`, the root's top candidates with
     principal variations of at most pv_depth moves taken when the search ended (pv_min_visits 1 walks
-    like most_visited_path, 2 like mvp_gg); everything else in the row is what lines = 0 gives."""
+    like most_visited_path, 2 like mvp_gg); everything else in the row is what lines = 0 gives.
+    move_temperature (ours): T or (early, late, halflife), with two_player_mode off -- the suggested move is sampled in
+    proportion to N^(1/T(n)) as Engine.set_move_temperature states it; record i is then what the MCTSPlayer above computes
+    when it is given the same move_temperature.  The search and the rows do not change."""
     _check_lines(lines, pv_depth, pv_min_visits)
     positions = list(positions)
     for k, p in enumerate(positions):
@@ -850,6 +877,7 @@ def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=
         if symmetry is not None:
             eng.set_symmetry(symmetry)
         _apply_puct(eng, fpu, c_base)      # the PUCT rule options of Engine.set_puct, as MCTSPlayer(fpu=, c_base=)
+        _apply_explore(eng, move_temperature=move_temperature)      # pick_move's, as MCTSPlayer(move_temperature=)
         if lines:
             eng.analyze_set_lines(lines, pv_depth, pv_min_visits)
         eng.analyze_start(boards, infos, hist, game_id_base)
@@ -909,7 +937,8 @@ def review_arrays(env, games):
 
 
 def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, seed=0, game_id_base=0, slots=None,
-           symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, fpu=None, c_base=0.0, **cfg):
+           symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, fpu=None, c_base=0.0,
+           move_temperature=None, **cfg):
     """Batched game review (ours; the loop of play(), src/play.jl:25-77, over recorded games): for game j, what
     `p = MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + j, symmetry=symmetry)`,
     `p.initialize_game(starts[j])`, then for every recorded move m_k `p.suggest_move()` and `p.play_move(m_k)` compute,
@@ -921,7 +950,10 @@ def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, 
     plies and the other games are not affected.  `slots` trees search at once (default min(len(games),
     1024)).  `cfg`: further agz_config fields (parallel_readouts, max_nodes_per_game, pool_policy, komi, ...).
     lines > 0: the rows are AnalysisLines as in analyze(); the lines of ply k are taken when its search ended, before
-    the recorded move re-roots the tree."""
+    the recorded move re-roots the tree.
+    move_temperature (ours): T or (early, late, halflife); with two_player_mode=False the suggested move of every ply is
+    sampled in proportion to N^(1/T(n)) (Engine.set_move_temperature), as the MCTSPlayer above suggests it when it is
+    given the same move_temperature; under the default two_player_mode=True it changes nothing."""
     _check_lines(lines, pv_depth, pv_min_visits)
     games = list(games)
     moves, off = review_arrays(env, games)
@@ -962,6 +994,7 @@ def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, 
         if symmetry is not None:
             eng.set_symmetry(symmetry)
         _apply_puct(eng, fpu, c_base)      # the PUCT rule options of Engine.set_puct, as MCTSPlayer(fpu=, c_base=)
+        _apply_explore(eng, move_temperature=move_temperature)      # pick_move's, as MCTSPlayer(move_temperature=)
         if lines:
             eng.analyze_set_lines(lines, pv_depth, pv_min_visits)
         eng.review_start(moves, off, boards, infos, hist, game_id_base)
@@ -1145,7 +1178,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
           tower_height=19, model=None, start_training_after=50000, slots=None, seed=0, game_id_base=0, symmetry=None,
           augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, starts=None,
           playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
-          gumbel_c_scale=1.0, value_target=None, fpu=None, c_base=0.0, surprise=0.0, **cfg):
+          gumbel_c_scale=1.0, value_target=None, fpu=None, c_base=0.0, surprise=0.0, root_policy_temperature=None,
+          root_noise=None, move_temperature=None, **cfg):
     """train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model,
     start_training_after) (src/train.jl:38-92) with `slots` games in flight on the device.  One engine
     plays, keeps the replay arena and trains; per step: agz_selfplay_step(1), one read of how many games finished, and
@@ -1170,7 +1204,8 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
     fpu and c_base (the PUCT rule options of Engine.set_puct, as in selfplay), surprise (rho: policy surprise weighting --
     each game is scored right after it is filed, on the weights of that moment, and every training batch is drawn by
     weight, with replacement: per game a share 1 - rho of the sampling mass evenly over its target plies and rho in
-    proportion to KL(pi || prior), Engine.replay_score / replay_set_surprise; 0: the uniform draw, as the reference).
+    proportion to KL(pi || prior), Engine.replay_score / replay_set_surprise; 0: the uniform draw, as the reference),
+    root_policy_temperature, root_noise and move_temperature (root exploration and the move temperature, as in selfplay).
     Returns the trained NeuralNet (model itself when given)."""
     import time
     import torch
@@ -1200,7 +1235,9 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
         z = torch.empty(batch_size, dtype=torch.float32, device=dev)
         cuts = _minibatch_cuts(batch_size)
         _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit,
-                              gumbel_c_scale, targets_only_arena=True, fpu=fpu, c_base=c_base)
+                              gumbel_c_scale, targets_only_arena=True, fpu=fpu, c_base=c_base,
+                              root_policy_temperature=root_policy_temperature, root_noise=root_noise,
+                              move_temperature=move_temperature)
         if value_target is not None:
             eng.replay_set_value_target(*value_target)
         surprise = float(surprise)

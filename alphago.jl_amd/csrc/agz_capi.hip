@@ -374,6 +374,29 @@ agz_status agz_search_puct_counts(agz_engine* e, uint64_t* out) {
     out[1] = (uint64_t)c[1];
   });
 }
+agz_status agz_selfplay_set_root_policy_temperature(agz_engine* e, int32_t on, double early, double late, double halflife) {
+  return guard(e, [&](agz::Engine& E) { E.set_root_policy_temperature(on, early, late, halflife); });
+}
+agz_status agz_selfplay_set_root_noise(agz_engine* e, double total_alpha, int32_t shaped) {
+  return guard(e, [&](agz::Engine& E) { E.set_root_noise(total_alpha, shaped); });
+}
+agz_status agz_search_set_move_temperature(agz_engine* e, int32_t on, double early, double late, double halflife) {
+  return guard(e, [&](agz::Engine& E) { E.set_move_temperature(on, early, late, halflife); });
+}
+agz_status agz_search_explore_counts(agz_engine* e, uint64_t* out) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+    E.explore_counts(out);
+  });
+}
+agz_status agz_tree_explore_rows(agz_engine* e, int32_t g, int32_t node, float* tempered, double* alpha, float* noised) {
+  return guard(e, [&](agz::Engine& E) { E.tree_explore_rows(g, node, tempered, alpha, noised); });
+}
+agz_status agz_explore_temperature(int32_t n, double early, double late, double halflife, double* out) {
+  if (!out) return AGZ_BAD_ARGUMENT;
+  *out = agz_temperature(n, early, late, halflife);
+  return AGZ_OK;
+}
 agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on) {
   return guard(e, [&](agz::Engine& E) { E.replay_set_targets_only(on != 0); });
 }

@@ -61,6 +61,13 @@ class Engine {
   // PUCT rule options of every search (agz_search_set_puct): (0, 0, 0, 0) is off
   void set_puct(int fpu_on, double r, double r_root, double c_base);
   void puct_counts(int64_t out[2]);
+  // root exploration and the move temperature (agz_selfplay_set_root_policy_temperature / _set_root_noise,
+  // agz_search_set_move_temperature): off by default
+  void set_root_policy_temperature(int on, double early, double late, double halflife);
+  void set_root_noise(double total_alpha, int shaped);
+  void set_move_temperature(int on, double early, double late, double halflife);
+  void explore_counts(uint64_t out[4]);
+  void tree_explore_rows(int g, int node, float* tempered, double* alpha, float* noised);
   int64_t analyze_progress();
   void analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior);
   // analysis lines (agz_analyze_set_lines / agz_analyze_lines / agz_tree_lines): top-K candidates with their PVs
@@ -196,6 +203,8 @@ class Engine {
   // shared by the option setters and their readers (`what` is the error text's prefix)
   void require_selfplay_engine(const char* what) const;
   void require_between_games(const char* what);
+  void require_explore_settable(const char* what);
+  void explore_set_done();
   void read_counter_pair(int first, int64_t out[2]);
   template <class Launch>
   void read_tree_pi_row(float* out, Launch launch);

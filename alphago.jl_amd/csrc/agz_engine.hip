@@ -314,6 +314,18 @@ __global__ __launch_bounds__(kWave) void k_tree_gumbel_pi(View V, int g, int nod
   gumbel_pi(w, V, S, node_index(V, g, node), out);
 }
 
+// agz_tree_explore_rows: root_explore of one node of single tree g on a copy of its prior row, under the engine's
+// setting; row [AP] receives the noised row, tempered [A] and alpha [A] what lies between.  The tree is not written.
+__global__ __launch_bounds__(kWave) void k_tree_explore_rows(View V, int g, int node, float* row, float* tempered,
+                                                              double* alpha) {
+  AGZ_SCRATCH(S)
+  HipWave w;
+  const long ni = node_index(V, g, node);
+  w.for_each(V.AP, [&](int a) { row[a] = V.childP[ni * V.AP + a]; });
+  w.sync();
+  root_explore(w, V, S, g, node, row, tempered, alpha);
+}
+
 __global__ __launch_bounds__(kWave) void k_go_play(View V, const int8_t* boards, const int8_t* tp, const int32_t* ko,
                                                     const int32_t* moves, int B, int8_t* bo, int32_t* ko_o,
                                                     int32_t* nc, int32_t* st) {
@@ -1149,6 +1161,71 @@ void Engine::set_puct(int fpu_on, double r, double r_root, double c_base) {
   wait();
   view_set_puct(V_, fpu_on, r, r_root, c_base);
   AGZ_HIP(hipMemsetAsync(V_.counters + CT_PUCT_LEVELS, 0, sizeof(unsigned long long) * 2, stream_));
+  wait();
+}
+
+// ---- root exploration and the move temperature (agz_selfplay_set_root_policy_temperature / _set_root_noise,
+// agz_search_set_move_temperature)
+
+// the range checks are explore_*_refusal of agz_state.h, shared with the host simulator
+static void check_explore(const char* what, const char* why) {
+  AGZ_REQUIRE(!why, AGZ_BAD_ARGUMENT, "%s: %s", what, why ? why : "");
+}
+
+// what the three setters share after their own range checks; then the caller writes the View and calls explore_set_done
+void Engine::require_explore_settable(const char* what) {
+  require_selfplay_engine(what);
+  AGZ_REQUIRE(tree_batch_ == 0, AGZ_BAD_ARGUMENT,
+              "%s: not between agz_tree_search_select and agz_tree_search_incorporate", what);
+  require_between_games(what);
+  wait();
+}
+void Engine::explore_set_done() {
+  AGZ_HIP(hipMemsetAsync(V_.counters + CT_EXP_TEMPERED, 0, sizeof(unsigned long long) * 4, stream_));
+  wait();
+}
+static_assert(CT_EXP_NOISED == CT_EXP_TEMPERED + 1 && CT_EXP_SAMPLED == CT_EXP_TEMPERED + 2 &&
+                  CT_EXP_OFF_MAX == CT_EXP_TEMPERED + 3, "the four counters are cleared and read as one run");
+
+void Engine::set_root_policy_temperature(int on, double early, double late, double halflife) {
+  check_explore("root policy temperature", explore_schedule_refusal(V_, on, early, late, halflife, 0.1));
+  require_explore_settable("root policy temperature");
+  view_set_root_policy_temperature(V_, on, early, late, halflife);
+  explore_set_done();
+}
+
+void Engine::set_root_noise(double total_alpha, int shaped) {
+  check_explore("root noise", explore_noise_refusal(V_, total_alpha, shaped));
+  require_explore_settable("root noise");
+  view_set_root_noise(V_, total_alpha, shaped);
+  explore_set_done();
+}
+
+void Engine::set_move_temperature(int on, double early, double late, double halflife) {
+  check_explore("move temperature", explore_schedule_refusal(V_, on, early, late, halflife, 0.0));
+  require_explore_settable("move temperature");
+  view_set_move_temperature(V_, on, early, late, halflife);
+  explore_set_done();
+}
+
+void Engine::explore_counts(uint64_t out[4]) {
+  unsigned long long c[4];
+  down(c, V_.counters + CT_EXP_TEMPERED, 4);
+  wait();
+  for (int i = 0; i < 4; ++i) out[i] = (uint64_t)c[i];
+}
+
+void Engine::tree_explore_rows(int g, int node, float* tempered, double* alpha, float* noised) {
+  check_node(g, node);
+  const size_t A = (size_t)V_.A, AP = (size_t)V_.AP;
+  s_f32a_.ensure(AP + A);          // [noised row, AP | tempered, A]
+  s_f64_.ensure(A);
+  hipLaunchKernelGGL(k_tree_explore_rows, dim3(1), dim3(kWave), 0, stream_, V_, g, node, s_f32a_.p, s_f32a_.p + AP,
+                     s_f64_.p);
+  AGZ_HIP(hipGetLastError());
+  if (noised) down(noised, s_f32a_.p, A);
+  if (tempered) down(tempered, s_f32a_.p + AP, A);
+  if (alpha) down(alpha, s_f64_.p, A);
   wait();
 }
 

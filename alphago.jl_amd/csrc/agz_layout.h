@@ -78,6 +78,9 @@ inline void fill_dims(View& V, const agz_config& c) {
   V.fpu_r = 0.0;
   V.fpu_r_root = 0.0;
   V.c_base = 0.0;
+  view_set_root_policy_temperature(V, 0, 0.0, 0.0, 0.0);   // agz_selfplay_set_root_policy_temperature
+  view_set_root_noise(V, 0.0, 0);                          // agz_selfplay_set_root_noise
+  view_set_move_temperature(V, 0, 0.0, 0.0, 0.0);          // agz_search_set_move_temperature
 }
 
 // visits every buffer of the View: f(pointer-reference, element count)

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "../../include/agz_draws.h"
+#include "../../include/agz_explore.h"
 #include "agz_state.h"
 
 #if defined(__HIPCC__)
@@ -836,9 +837,10 @@ AGZ_FN int incorporate(W& w, const View& V, int g, int node, const float* probs,
   return AGZ_OK;
 }
 
-// inject_noise!(node) (mcts.jl:233-239): Dirichlet(alpha) over ALL actions from the draw stream
+// inject_noise!(node) (mcts.jl:233-239): Dirichlet(alpha) over ALL actions from the draw stream, mixed into `row` (the
+// node's prior row)
 template <class W>
-AGZ_FN void inject_noise(W& w, const View& V, Scratch& S, int g, int node) {
+AGZ_FN void inject_noise(W& w, const View& V, Scratch& S, int g, int node, float* row) {
   const GameState& G = V.gs[g];
   const long ni = node_index(V, g, node);
   const uint32_t move_key = (uint32_t)V.meta[ni].n;
@@ -851,10 +853,132 @@ AGZ_FN void inject_noise(W& w, const View& V, Scratch& S, int g, int node) {
   for (int a = 0; a < A; ++a) sum += S.dbuf[a];   // fixed ascending order on every lane
   w.for_each(A, [&](int a) {
     const double d = sum > 0.0 ? S.dbuf[a] / sum : 1.0 / (double)A;
-    const double mixed = (double)V.childP[ni * V.AP + a] * (1.0 - V.noise_w) + d * V.noise_w;
-    V.childP[ni * V.AP + a] = (float)mixed;
+    const double mixed = (double)row[a] * (1.0 - V.noise_w) + d * V.noise_w;
+    row[a] = (float)mixed;
   });
   w.sync();
+}
+
+// ------------------------------------------------------------------ root exploration
+// The root policy temperature and the noise over the legal moves (include/agz_explore.h states the arithmetic, include/agz.h
+// the rule).  The per-element values go through S.dbuf and every sum is taken over it in ascending action order on
+// every lane, as inject_noise sums.
+
+// the sum of S.dbuf over the flagged actions, ascending
+AGZ_FN double sum_flagged(const Scratch& S, int A) {
+  double s = 0.0;
+  for (int a = 0; a < A; ++a)
+    if (S.flag[a]) s += S.dbuf[a];
+  return s;
+}
+
+// Rule 1 on `row`: the legal, positive entries re-softmaxed at T and scaled to the mass they had.  Returns whether there
+// was such an entry (a row without one is left alone).
+template <class W>
+AGZ_FN bool temper_row(W& w, const View& V, Scratch& S, long ni, int n_root, float* row) {
+  const int A = V.A;
+  const double T = agz_temperature(n_root, V.pt_early, V.pt_late, V.pt_half);
+  int cnt = 0;
+  w.for_each(V.AP, [&](int a) {
+    const bool on = a < A && legal_bit(V, ni, a) && row[a] > 0.0f;
+    S.flag[a] = on;
+    S.dbuf[a] = on ? (double)row[a] : 0.0;
+    if (on) cnt++;
+  });
+  cnt = w.reduce_sum(cnt);
+  w.sync();
+  if (cnt == 0) return false;
+  const double mass = sum_flagged(S, A);
+  w.sync();
+  double mx = -__builtin_huge_val();
+  w.for_each(A, [&](int a) {
+    if (!S.flag[a]) return;
+    const double x = agz_explore_temper_x(row[a], T);
+    S.dbuf[a] = x;
+    if (x > mx) mx = x;
+  });
+  mx = w.reduce_max(mx);
+  w.for_each(A, [&](int a) { if (S.flag[a]) S.dbuf[a] = agz_exp(S.dbuf[a] - mx); });
+  w.sync();
+  const double E = sum_flagged(S, A);
+  w.for_each(A, [&](int a) { if (S.flag[a]) row[a] = agz_explore_temper_p(S.dbuf[a], E, mass); });
+  w.sync();
+  return true;
+}
+
+// Rule 2 on `row`: Dirichlet noise of total concentration V.noise_total over the legal actions, the concentration of
+// each shaped by the row under V.noise_shaped; alpha (may be null) receives alpha_a, 0 for an illegal action
+template <class W>
+AGZ_FN void legal_noise(W& w, const View& V, Scratch& S, int g, long ni, int n_root, float* row, double* alpha) {
+  const GameState& G = V.gs[g];
+  const int A = V.A;
+  const int shaped = V.noise_shaped;
+  int L = 0;
+  w.for_each(V.AP, [&](int a) {
+    const bool lg = a < A && legal_bit(V, ni, a);
+    S.flag[a] = lg;
+    if (lg) L++;
+  });
+  L = w.reduce_sum(L);
+  w.sync();
+  if (L == 0) return;   // cannot happen: pass is always legal
+  const double u = 1.0 / (double)L;
+  double ssum = 0.0;
+  if (shaped) {
+    w.for_each(A, [&](int a) { S.dbuf[a] = S.flag[a] ? agz_explore_shape_l(row[a]) : 0.0; });
+    w.sync();
+    const double mean = sum_flagged(S, A) / (double)L;
+    w.sync();
+    w.for_each(A, [&](int a) { S.dbuf[a] = S.flag[a] ? agz_explore_shape_s(S.dbuf[a], mean) : 0.0; });
+    w.sync();
+    ssum = sum_flagged(S, A);
+    w.sync();
+  }
+  w.for_each(A, [&](int a) {
+    double al = 0.0, gm = 0.0;
+    if (S.flag[a]) {
+      al = agz_explore_alpha(V.noise_total, u, shaped, shaped ? S.dbuf[a] : 0.0, ssum);
+      gm = agz_dirichlet_gamma(V.seed, G.game_id, (uint32_t)n_root, (uint32_t)a, al);
+    }
+    if (alpha) alpha[a] = al;
+    S.dbuf[a] = gm;
+  });
+  w.sync();
+  const double gsum = sum_flagged(S, A);
+  w.for_each(A, [&](int a) {
+    if (!S.flag[a]) return;
+    const double d = gsum > 0.0 ? S.dbuf[a] / gsum : u;
+    row[a] = agz_explore_mix(row[a], d, V.noise_w);
+  });
+  w.sync();
+}
+
+// What a search that gets noise does to its root's prior before it begins: the temperature first, the noise second.
+// With both rules off this is inject_noise.  row = null: the node's stored row, and the roots are counted; otherwise
+// a copy of it [AP] (agz_tree_explore_rows), with `tempered` [A] = the row between the two rules and `alpha` [A] = the
+// concentration of each action (either may be null).
+template <class W>
+AGZ_FN void root_explore(W& w, const View& V, Scratch& S, int g, int node, float* row = nullptr, float* tempered = nullptr,
+                         double* alpha = nullptr) {
+  const long ni = node_index(V, g, node);
+  const bool stored = row == nullptr;
+  if (stored) row = V.childP + ni * V.AP;
+  const int n_root = V.meta[ni].n;
+  if (V.pt_on) {
+    const bool did = temper_row(w, V, S, ni, n_root, row);
+    if (did && stored) w.count(&V.counters[CT_EXP_TEMPERED], 1);
+  }
+  if (tempered) {
+    w.for_each(V.A, [&](int a) { tempered[a] = row[a]; });
+    w.sync();
+  }
+  if (V.noise_total > 0.0) {
+    legal_noise(w, V, S, g, ni, n_root, row, alpha);
+    if (stored) w.count(&V.counters[CT_EXP_NOISED], 1);
+  } else {
+    if (alpha) w.for_each(V.A, [&](int a) { alpha[a] = V.alpha; });
+    inject_noise(w, V, S, g, node, row);
+  }
 }
 
 // children_as_pi(root, squash) into out[A] (mcts.jl:241-252)
@@ -938,7 +1062,10 @@ AGZ_FN int pick_move(W& w, const View& V, Scratch& S, int g, int* a_out) {
   const long ni = node_index(V, g, G.root);
   const int A = V.A, n = V.meta[ni].n;
   const int tau = V.two_player ? -1 : V.tau;
-  if (n >= tau) {
+  // the move temperature (agz_search_set_move_temperature, two_player off): at T <= 0.01 the arg-max branch, verbatim
+  const bool tempered = V.mt_on != 0 && !V.two_player;
+  const double T = tempered ? agz_temperature(n, V.mt_early, V.mt_late, V.mt_half) : 0.0;
+  if (tempered ? T <= AGZ_EXPLORE_ARGMAX_T : n >= tau) {
     float mx = -1.0f;
     w.for_each(A, [&](int a) { const float c = V.childN[ni * V.AP + a]; mx = c > mx ? c : mx; });
     mx = w.reduce_max_f(mx);
@@ -957,6 +1084,32 @@ AGZ_FN int pick_move(W& w, const View& V, Scratch& S, int g, int* a_out) {
     }
     w.sync();
     *a_out = idx;
+    return AGZ_OK;
+  }
+  if (tempered) {
+    // sample in proportion to (N_a / max N)^(1/T), pass included, with the soft pick's draw
+    float mx = 0.0f;
+    w.for_each(A, [&](int a) { const float c = V.childN[ni * V.AP + a]; mx = c > mx ? c : mx; });
+    mx = w.reduce_max_f(mx);
+    if (!(mx > 0.0f)) return AGZ_ASSERT_SOFTPICK;
+    w.for_each(A, [&](int a) { S.dbuf[a] = agz_explore_pick_weight(V.childN[ni * V.AP + a], mx, T); });
+    w.sync();
+    double sum = 0.0;
+    for (int a = 0; a < A; ++a) sum += S.dbuf[a];   // fixed ascending order on every lane
+    const double r = agz_u01(agz_draw_u64(V.seed, G.game_id, (uint32_t)n, AGZ_SITE_SOFTPICK, 0)) * sum;
+    int pick = -1, last = -1;
+    double acc = 0.0;
+    for (int a = 0; a < A && pick < 0; ++a) {
+      const double wa = S.dbuf[a];
+      acc += wa;
+      if (wa > 0.0) { last = a; if (acc > r) pick = a; }
+    }
+    if (pick < 0) pick = last;                      // rounding left r at or past the sum: the highest weighted action
+    const bool off_max = V.childN[ni * V.AP + pick] != mx;
+    w.sync();
+    w.count(&V.counters[CT_EXP_SAMPLED], 1);
+    w.count(&V.counters[CT_EXP_OFF_MAX], off_max ? 1 : 0);
+    *a_out = pick;
     return AGZ_OK;
   }
   // soft pick: cdf = cumsum(child_N) ./ cdf[end-1]; first index with !(cdf < u)
@@ -1186,7 +1339,8 @@ AGZ_FN bool pool_full_can_move(W& w, const View& V, int g) {
   float s = 0.f;
   w.for_each(V.P, [&](int a) { s += V.childN[ri * V.AP + a]; });
   s = w.reduce_sum_f(s);
-  const bool argmax = V.two_player || rm.n >= V.tau;
+  // (under the move temperature every visited child has a weight, pass included, in either branch)
+  const bool argmax = V.two_player || V.mt_on != 0 || rm.n >= V.tau;
   return s > 0.f || (argmax && V.childN[ri * V.AP + V.P] > 0.f);
 }
 
@@ -1448,11 +1602,11 @@ AGZ_FN void search_budget(W& w, GameState& G, int budget) {
   if (w.leader()) { G.target = G.rootN + (float)budget; G.phase = G_SEARCH; }
 }
 
-// Begin the search of self-play game g's root `node`: Dirichlet noise (selfplay.jl:23) unless the search is fast or a
+// Begin the search of self-play game g's root `node`: root_explore (Dirichlet noise, selfplay.jl:23) unless the search is fast or a
 // Gumbel search, which gets none, and the budget: R more root visits, cap_fast for a fast search.
 template <class W>
 AGZ_FN void search_begin(W& w, const View& V, Scratch& S, int g, int node, bool full) {
-  if (full && V.gumbel_m <= 0) inject_noise(w, V, S, g, node);
+  if (full && V.gumbel_m <= 0) root_explore(w, V, S, g, node);
   search_budget(w, V.gs[g], full ? V.R : V.cap_fast);
 }
 
@@ -2385,7 +2539,7 @@ AGZ_FN void tree_op(W& w, const View& V, Scratch& S, const TreeArgs& T) {
       const int len = walk_path(w, V, S, g, T.node, T.up_to);
       status = incorporate(w, V, g, T.node, T.probs, T.value, S.path, len);
     } break;
-    case TOP_NOISE: inject_noise(w, V, S, g, T.node); break;
+    case TOP_NOISE: root_explore(w, V, S, g, T.node); break;
     case TOP_SEARCH_SELECT: {
       game_select_phase(w, V, S, g, T.par);
       r0 = G.nleaves;

@@ -116,7 +116,12 @@ constexpr int CT_GUMBEL_BEGUN = CT_COUNT, CT_GUMBEL_HALVED = CT_COUNT + 1;
 // PUCT rule options on (puct_rule_on): tree levels a descent scored under the rule / those of them that picked an
 // unvisited child.  The two slots after the Gumbel ones, outside the enum for the same reason.
 constexpr int CT_PUCT_LEVELS = CT_COUNT + 2, CT_PUCT_UNVISITED = CT_COUNT + 3;
-constexpr int kCounterSlots = CT_COUNT + 4;     // what View::counters holds
+// Root exploration and the move temperature (agz_search.h root_explore / pick_move): roots tempered / roots
+// noised under total_alpha > 0 / moves picked by the sampling branch of the move temperature / those of them that are
+// not a most-visited child.  The four slots after the PUCT ones, outside the enum for the same reason.
+constexpr int CT_EXP_TEMPERED = CT_COUNT + 4, CT_EXP_NOISED = CT_COUNT + 5, CT_EXP_SAMPLED = CT_COUNT + 6,
+              CT_EXP_OFF_MAX = CT_COUNT + 7;
+constexpr int kCounterSlots = CT_COUNT + 8;     // what View::counters holds
 
 struct View {
   // dimensions
@@ -238,6 +243,15 @@ struct View {
   int32_t fpu_on;
   double fpu_r, fpu_r_root;           // r, r_root
   double c_base;
+  // Root exploration and the move temperature (agz_selfplay_set_root_policy_temperature / _set_root_noise,
+  // agz_search_set_move_temperature; zero = off, the View{} of the host simulator and of fill_dims; include/agz_explore.h
+  // states the arithmetic).  pt_on: the root prior is re-softmaxed at T(n) before the noise; noise_total >
+  // 0: Dirichlet noise over the legal actions only, of that total concentration, shaped by the prior with noise_shaped;
+  // mt_on: pick_move (two_player off) samples in proportion to N^(1/T(n)), and is the arg-max once T(n) <= 0.01
+  int32_t pt_on, mt_on, noise_shaped;
+  double pt_early, pt_late, pt_half;
+  double mt_early, mt_late, mt_half;
+  double noise_total;
 };
 
 // option values -> View fields, for the engine's setters (which check the arguments first) and the host simulator's
@@ -259,6 +273,41 @@ inline void view_set_puct(View& V, int fpu_on, double r, double r_root, double c
   V.fpu_r = fpu_on ? r : 0.0;
   V.fpu_r_root = fpu_on ? r_root : 0.0;
   V.c_base = c_base > 0.0 ? c_base : 0.0;
+}
+// The argument checks of those three setters, for the engine and the host simulator alike: null when the values are
+// taken, else why not (NaN fails every range).  t_min: 0.1 for the root policy temperature, 0 for the move temperature.
+// What only an engine knows -- games in flight, a select phase awaiting its incorporate -- is the engine's to add.
+inline const char* explore_schedule_refusal(const View& V, int on, double early, double late, double halflife,
+                                            double t_min) {
+  if (V.arena) return "an arena_mode engine plays evaluate() games only";
+  if (on != 0 && on != 1) return "on is not 0 or 1";
+  if (!(early >= t_min && early <= 10.0)) return "early is outside the temperature range";
+  if (!(late >= t_min && late <= 10.0)) return "late is outside the temperature range";
+  if (!(halflife > 0.0 && halflife <= 1.0e6)) return "halflife is not in (0, 1e6]";
+  return nullptr;
+}
+inline const char* explore_noise_refusal(const View& V, double total_alpha, int shaped) {
+  if (V.arena) return "an arena_mode engine plays evaluate() games only";
+  if (!(total_alpha >= 0.0 && total_alpha <= 1000.0)) return "total_alpha is not in 0 (off) .. 1000";
+  if (shaped != 0 && shaped != 1) return "shaped is not 0 or 1";
+  if (shaped && !(total_alpha > 0.0)) return "the shape needs total_alpha > 0";
+  return nullptr;
+}
+inline void view_set_root_policy_temperature(View& V, int on, double early, double late, double halflife) {
+  V.pt_on = on ? 1 : 0;
+  V.pt_early = on ? early : 0.0;
+  V.pt_late = on ? late : 0.0;
+  V.pt_half = on ? halflife : 0.0;
+}
+inline void view_set_root_noise(View& V, double total_alpha, int shaped) {
+  V.noise_total = total_alpha > 0.0 ? total_alpha : 0.0;
+  V.noise_shaped = (total_alpha > 0.0 && shaped) ? 1 : 0;
+}
+inline void view_set_move_temperature(View& V, int on, double early, double late, double halflife) {
+  V.mt_on = on ? 1 : 0;
+  V.mt_early = on ? early : 0.0;
+  V.mt_late = on ? late : 0.0;
+  V.mt_half = on ? halflife : 0.0;
 }
 
 }  // namespace agz

@@ -23,7 +23,7 @@ using Random
 export GoEnv, Position, NeuralNet, MCTSPlayer, selfplay, train, extract_data, initialize_game!,
        tree_search!, pick_move, play_move!, should_resign, is_done, set_result!, all_legal_moves,
        score, result, result_string, IllegalMove, to_flat, from_flat, PlayerMove, BLACK, WHITE,
-       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, reanalyze!, set_starts!, set_playout_cap!, playout_cap_counts, set_forced_playouts!, forced_counts, pruned_pi, set_gumbel!, gumbel_counts, gumbel_pi, set_puct!, puct_counts, extract_targets, value_targets, extract_value_targets, node_lines, most_visited_path, mvp_gg,
+       SelfPlayPlayer, get_replay_batch, Momentum, _train, seed!, analyze, review, reanalyze!, set_starts!, set_playout_cap!, playout_cap_counts, set_forced_playouts!, forced_counts, pruned_pi, set_gumbel!, gumbel_counts, gumbel_pi, set_puct!, puct_counts, set_root_policy_temperature!, set_root_noise!, set_move_temperature!, explore_counts, explore_rows, explore_temperature, extract_targets, value_targets, extract_value_targets, node_lines, most_visited_path, mvp_gg,
        # the node-level surface test/test_mcts.jl:2-5 and test/test_mcts_player.jl:3-6 import
        MCTSNode, select_leaf, maybe_add_child!, add_virtual_loss!, revert_virtual_loss!,
        incorporate_results!, inject_noise!, child_action_score, child_Q, child_U, child_N, child_W,
@@ -328,7 +328,8 @@ mutable struct MCTSPlayer
   recent::Vector{PlayerMove}            # start.recent + every move played since: root.position.recent (board.jl:299)
 end
 function MCTSPlayer(env::GoEnv, network; num_readouts = 800, two_player_mode = false,
-                    resign_threshold = -0.9, seed = 0, symmetry = nothing, fpu = nothing, c_base::Real = 0.0)
+                    resign_threshold = -0.9, seed = 0, symmetry = nothing, fpu = nothing, c_base::Real = 0.0,
+                    root_policy_temperature = nothing, root_noise = nothing, move_temperature = nothing)
   τ = two_player_mode ? -1 : (env.N * env.N ÷ 12) ÷ 2 * 2
   th = network isa NeuralNet ? network.tower_height : 0
   e = Engine(board_size = env.N, tower_height = th, games = 1, num_readouts = num_readouts,
@@ -336,6 +337,7 @@ function MCTSPlayer(env::GoEnv, network; num_readouts = 800, two_player_mode = f
              resign_threshold = resign_threshold, seed = seed, external_network = !(network isa NeuralNet))
   symmetry === nothing || set_symmetry!(e, symmetry)
   apply_puct!(e, fpu, c_base)
+  apply_explore!(e, root_policy_temperature, root_noise, move_temperature)
   MCTSPlayer(env, network, num_readouts, two_player_mode, τ, Float32[], Vector{Float32}[], 0, "",
              resign_threshold, e, nothing, PlayerMove[])
 end
@@ -925,6 +927,58 @@ end
 # the keywords fpu = / c_base = of selfplay, train, analyze, review, evaluate and MCTSPlayer: nothing asked, nothing set
 apply_puct!(e::Engine, fpu, c_base) = (fpu === nothing && c_base == 0) || set_puct!(e, fpu, c_base)
 
+# Root exploration and the move temperature (ours; include/agz.h agz_selfplay_set_root_policy_temperature and what follows
+# it, DESIGN.md 5t).  A temperature t is nothing (off), T, or (early, late, halflife): T(n) = late + (early - late) *
+# 2^(-n / halflife), n = position.n of the root.  root policy temperature: the root prior of a search that gets noise is
+# re-softmaxed at T(n) first; root noise: Dirichlet noise of total concentration total_alpha over the legal moves only
+# (0: off, the reference's one alpha over all actions), each move's share shaped by the prior with shaped = true
+# (KataGo); move temperature: pick_move (two_player_mode off) samples in proportion to N^(1 / T(n)), arg-max once
+# T(n) <= 0.01.
+schedule_args(t) = t === nothing ? (Int32(0), 1.0, 1.0, 1.0) :
+                   t isa Tuple ? (Int32(1), Float64(t[1]), Float64(t[2]), Float64(t[3])) : (Int32(1), Float64(t), Float64(t), 1.0)
+function set_root_policy_temperature!(e::Engine, t = nothing)
+  on, early, late, half = schedule_args(t)
+  check(e, ccall((:agz_selfplay_set_root_policy_temperature, libagz), Int32, (Ptr{Cvoid}, Int32, Float64, Float64, Float64),
+                 e.handle, on, early, late, half))
+end
+function set_root_noise!(e::Engine, total_alpha::Real = 0.0, shaped::Bool = false)
+  check(e, ccall((:agz_selfplay_set_root_noise, libagz), Int32, (Ptr{Cvoid}, Float64, Int32), e.handle, total_alpha,
+                 shaped ? 1 : 0))
+end
+function set_move_temperature!(e::Engine, t = nothing)
+  on, early, late, half = schedule_args(t)
+  check(e, ccall((:agz_search_set_move_temperature, libagz), Int32, (Ptr{Cvoid}, Int32, Float64, Float64, Float64),
+                 e.handle, on, early, late, half))
+end
+# (roots tempered, roots noised under total_alpha > 0, moves sampled, those of them off the most visited child) since the
+# later of a setter call and agz_selfplay_start
+function explore_counts(e::Engine)
+  out = zeros(UInt64, 4)
+  check(e, ccall((:agz_search_explore_counts, libagz), Int32, (Ptr{Cvoid}, Ptr{UInt64}), e.handle, out))
+  Tuple(Int.(out))
+end
+# what inject_noise! would do to `node` of single tree g under the engine's setting: (tempered, alpha, noised); the tree
+# is not modified
+function explore_rows(e::Engine, g::Integer, node::Integer, A::Integer)
+  t, al, nz = zeros(Float32, A), zeros(Float64, A), zeros(Float32, A)
+  check(e, ccall((:agz_tree_explore_rows, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Float32}, Ptr{Float64}, Ptr{Float32}),
+                 e.handle, g, node, t, al, nz))
+  t, al, nz
+end
+function explore_temperature(n::Integer, early::Real, late::Real, halflife::Real)
+  out = Ref{Float64}(0.0)
+  ccall((:agz_explore_temperature, libagz), Int32, (Int32, Float64, Float64, Float64, Ref{Float64}), n, early, late, halflife, out)
+  out[]
+end
+# the keywords root_policy_temperature = / root_noise = (total_alpha, shaped) / move_temperature = of selfplay, train and
+# MCTSPlayer (analyze and review take move_temperature): nothing asked, nothing set
+function apply_explore!(e::Engine, root_policy_temperature, root_noise, move_temperature)
+  root_policy_temperature === nothing || set_root_policy_temperature!(e, root_policy_temperature)
+  root_noise === nothing || (root_noise isa Tuple ? set_root_noise!(e, root_noise[1], root_noise[2]) : set_root_noise!(e, root_noise))
+  move_temperature === nothing || set_move_temperature!(e, move_temperature)
+  nothing
+end
+
 # replay_position (board.jl:557-578) from a start position: the position before each move and the final one
 function replay_positions_from(start::Position, moves)
   positions = Position[]
@@ -941,7 +995,8 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
                   starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing,
                   forced_playouts = nothing, prune_targets::Bool = true,
                   gumbel = nothing, gumbel_c_visit::Real = 50.0, gumbel_c_scale::Real = 1.0,
-                  fpu = nothing, c_base::Real = 0.0)
+                  fpu = nothing, c_base::Real = 0.0, root_policy_temperature = nothing, root_noise = nothing,
+                  move_temperature = nothing)
   (gumbel !== nothing && gumbel != 0 && forced_playouts !== nothing && forced_playouts != 0) &&
     throw(ArgumentError("gumbel and forced_playouts are two rules for the same decision: ask for one"))
   G = games === nothing ? 1 : games
@@ -962,6 +1017,7 @@ function selfplay(env::GoEnv, nn::NeuralNet, num_ro::Int = 800; games::Union{Not
   forced_playouts === nothing || set_forced_playouts!(e, forced_playouts, prune_targets)   # k
   gumbel === nothing || set_gumbel!(e, gumbel, gumbel_c_visit, gumbel_c_scale)             # m
   apply_puct!(e, fpu, c_base)                                                              # the PUCT rule options
+  apply_explore!(e, root_policy_temperature, root_noise, move_temperature)                 # root exploration, move temperature
   check(e, ccall((:agz_selfplay_start, libagz), Int32, (Ptr{Cvoid}, Int64), e.handle, G))
   while ccall((:agz_records_count, libagz), Int64, (Ptr{Cvoid},), e.handle) < G
     check(e, ccall((:agz_selfplay_step, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 16))
@@ -1003,7 +1059,8 @@ end
 # AGZ_POOL_EXHAUSTED, AGZ_ASSERT_SOFTPICK) and nodes_used.
 function analyze(env::GoEnv, nn::NeuralNet, positions::Vector{Position}; num_readouts::Int = 800, seed = 0,
                  game_id_base = 0, slots::Union{Nothing, Int} = nothing, two_player_mode = false, symmetry = nothing,
-                 lines::Int = 0, pv_depth::Int = 16, pv_min_visits::Int = 1, fpu = nothing, c_base::Real = 0.0)
+                 lines::Int = 0, pv_depth::Int = 16, pv_min_visits::Int = 1, fpu = nothing, c_base::Real = 0.0,
+                 move_temperature = nothing)
   check_lines(lines, pv_depth, pv_min_visits)
   B, P, A = length(positions), env.N * env.N, env.action_space
   B == 0 && return NamedTuple[]
@@ -1019,6 +1076,7 @@ function analyze(env::GoEnv, nn::NeuralNet, positions::Vector{Position}; num_rea
   copy_weights!(e, nn.engine)
   symmetry === nothing || set_symmetry!(e, symmetry)
   apply_puct!(e, fpu, c_base)
+  apply_explore!(e, nothing, nothing, move_temperature)      # pick_move's, as MCTSPlayer(move_temperature = )
   lines > 0 && check(e, ccall((:agz_analyze_set_lines, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Int32),
                               e.handle, lines, pv_depth, pv_min_visits))
   check(e, ccall((:agz_analyze_start, libagz), Int32, (Ptr{Cvoid}, Ptr{Int8}, Ptr{AgzPositionInfo}, Ptr{Int8}, Int64, UInt64),
@@ -1065,7 +1123,7 @@ end
 function review(env::GoEnv, nn::NeuralNet, games::Vector; num_readouts::Int = 800, starts = nothing,
                 two_player_mode = true, seed = 0, game_id_base = 0, slots::Union{Nothing, Int} = nothing,
                 symmetry = nothing, lines::Int = 0, pv_depth::Int = 16, pv_min_visits::Int = 1, fpu = nothing,
-                c_base::Real = 0.0)
+                c_base::Real = 0.0, move_temperature = nothing)
   check_lines(lines, pv_depth, pv_min_visits)
   G, P, A = length(games), env.N * env.N, env.action_space
   G == 0 && return Vector{NamedTuple}[]
@@ -1095,6 +1153,7 @@ function review(env::GoEnv, nn::NeuralNet, games::Vector; num_readouts::Int = 80
   copy_weights!(e, nn.engine)
   symmetry === nothing || set_symmetry!(e, symmetry)
   apply_puct!(e, fpu, c_base)
+  apply_explore!(e, nothing, nothing, move_temperature)      # pick_move's, as MCTSPlayer(move_temperature = )
   lines > 0 && check(e, ccall((:agz_analyze_set_lines, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Int32),
                               e.handle, lines, pv_depth, pv_min_visits))
   check(e, ccall((:agz_review_start, libagz), Int32,
@@ -1402,7 +1461,8 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
                starts::Union{Nothing, Vector{Position}} = nothing, playout_cap = nothing,
                forced_playouts = nothing, prune_targets::Bool = true,
                gumbel = nothing, gumbel_c_visit::Real = 50.0, gumbel_c_scale::Real = 1.0, value_target = nothing,
-               fpu = nothing, c_base::Real = 0.0, surprise::Real = 0.0)
+               fpu = nothing, c_base::Real = 0.0, surprise::Real = 0.0, root_policy_temperature = nothing,
+               root_noise = nothing, move_temperature = nothing)
   (gumbel !== nothing && gumbel != 0 && forced_playouts !== nothing && forced_playouts != 0) &&
     throw(ArgumentError("gumbel and forced_playouts are two rules for the same decision: ask for one"))
   cur_nn = model === nothing ? NeuralNet(env; tower_height = tower_height) : model                       # train.jl:43
@@ -1427,6 +1487,7 @@ function train(env::GoEnv; num_games::Int = 25000, memory_size::Int = 500000, ba
   forced_playouts === nothing || set_forced_playouts!(e, forced_playouts, prune_targets)   # k, as in selfplay
   gumbel === nothing || set_gumbel!(e, gumbel, gumbel_c_visit, gumbel_c_scale)             # m, as in selfplay
   apply_puct!(e, fpu, c_base)                                                              # as in selfplay
+  apply_explore!(e, root_policy_temperature, root_noise, move_temperature)                 # as in selfplay
   value_target === nothing || replay_set_value_target!(e, value_target[1], value_target[2])   # (alpha, lam): z of the batches
   replay_set_surprise!(e, surprise)       # rho: each game is scored as it is filed, the batches are drawn by weight
   check(e, ccall((:agz_selfplay_set_hold, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, 1))

@@ -3,13 +3,17 @@
 self-play -> replay arena -> training batches -> optimiser step -> arena match -> checkpoint.
 
     python examples/generation_loop.py [--board 9] [--tower 2] [--games 32] [--readouts 64] [--reanalyze]
-                                       [--surprise RHO]
+                                       [--surprise RHO] [--explore]
 
 What runs where:
   selfplay          G concurrent games on the device (one wave per tree, one network batch per step)
   extract_data      finished games come back as (moves, pi, result); multi-GPU: all-gathered over RCCL
   get_replay_batch  (game, ply) pairs are sampled on the host; the device replays the move lists of the replay
                     arena and emits the N x N x 17 x B feature tensor, pi and z (agz_replay_batch)
+  explore           (--explore) KataGo's root exploration in self-play: the root prior at temperature 1.25 -> 1.1, shaped
+                    Dirichlet noise of total concentration 10.83 over the legal moves, the move sampled at temperature
+                    0.75 -> 0.15, each with a halflife of the board size (agz_selfplay_set_root_policy_temperature /
+                    _set_root_noise, agz_search_set_move_temperature)
   reanalyze         (--reanalyze) the arena's games are searched again on the current weights and their pi / q
                     targets overwritten in place, moves and results as played (agz_replay_reanalyze_start / _commit)
   surprise          (--surprise RHO) every arena ply is scored by KL(pi || prior) on the current weights and the batches
@@ -43,13 +47,19 @@ def main(argv=None):
     ap.add_argument("--surprise", type=float, default=0.0, metavar="RHO",
                     help="policy surprise weighting: draw the training batches by weight, this share of each game's "
                          "sampling mass in proportion to KL(pi || prior)")
+    ap.add_argument("--explore", action="store_true",
+                    help="KataGo's root policy temperature, shaped root noise and move temperature in self-play")
     args = ap.parse_args(argv)
 
     env = ag.GoEnv(args.board)
     cur = ag.NeuralNet(env, tower_height=args.tower, seed=0)        # Flux-default-equivalent init
     prev = ag.NeuralNet(env, tower_height=args.tower, seed=1)
 
-    records = ag.selfplay(env, cur, args.readouts, games=args.games, seed=1)
+    explore = {}
+    if args.explore:        # KataGo's values; the halflife of both schedules is the board size
+        explore = dict(root_policy_temperature=(1.25, 1.1, args.board), root_noise=(10.83, True),
+                       move_temperature=(0.75, 0.15, args.board))
+    records = ag.selfplay(env, cur, args.readouts, games=args.games, seed=1, **explore)
     buf = ag.ReplayBuffer(env, memory_size=500000)
     buf.extend(records)
     print(f"self-play: {len(records)} games, {len(buf)} positions, "

@@ -774,6 +774,54 @@ agz_status agz_search_set_puct(agz_engine* e, int32_t fpu_on, double fpu_reducti
  * out[1] = those of them that picked an unvisited child, since the later of agz_search_set_puct and
  * agz_selfplay_start.  Synchronises. */
 agz_status agz_search_puct_counts(agz_engine* e, uint64_t* out /* [2] */);
+/* Root exploration and the move that is played (ours; the arithmetic is include/agz_explore.h): a softmax
+ * temperature on the root prior, Dirichlet noise over the legal moves with KataGo's policy-shaped concentration, and a
+ * move-selection temperature that decays with the move number.  All three are off by default: the reference's
+ * inject_noise! (one alpha for all A actions, mcts.jl:233-239) and pick_move (mcts_play.jl:52-71).
+ * Everything is Float64, every multiply, add and divide rounded on its own, unless cast; every sum runs in ascending
+ * action order.  n is position.n of the root, the key its draws use.
+ *   SCHEDULE  T(n) = late + ((early - late) * agz_exp(-(((double)n * 0.6931471805599453) / halflife)))
+ *   1. agz_selfplay_set_root_policy_temperature(on, early, late, halflife): over the root's stored prior row, over the
+ *      legal actions with P_a > 0 only:  x_a = agz_log((double)P_a) / T, M = max x_a, e_a = agz_exp(x_a - M), E = sum e_a,
+ *      mass = sum (double)P_a,  P_a <- (float)((e_a / E) * mass).  Illegal and zero entries stay; a row with no positive
+ *      legal entry is left alone.  (1, 1, 1, h) is not off: it runs the arithmetic.
+ *   2. agz_selfplay_set_root_noise(total_alpha, shaped), total_alpha = 0 off.  L = the legal actions of the root,
+ *      u = 1.0 / (double)L.  Unshaped: alpha_a = total_alpha * u.  Shaped (KataGo): l_a = agz_log(min(0.01, (double)P_a)
+ *      + 1e-20), mean = (sum l_a) / (double)L, s_a = max(0, l_a - mean), S = sum s_a, alpha_a = total_alpha * u when
+ *      S <= 0, else total_alpha * (0.5 * ((s_a / S) + u)).  Then gamma_a = agz_dirichlet_gamma(seed, game_id, n, a,
+ *      alpha_a) for legal a (no draw for an illegal one), G = sum gamma_a, d_a = G > 0 ? gamma_a / G : u,
+ *      P_a <- (float)(((double)P_a * (1.0 - w)) + (d_a * w)), w = dirichlet_noise_weight.  Illegal entries stay.  With
+ *      both rules on the shape reads the row after the temperature.
+ *   3. agz_search_set_move_temperature(on, early, late, halflife), in pick_move with two_player_mode off.  T <= 0.01: the
+ *      arg-max branch of pick_move with its AGZ_SITE_PICK_TIE draw.  Otherwise mx = max child_N over the A actions
+ *      (mx <= 0: AGZ_ASSERT_SOFTPICK), w_a = N_a > 0 ? agz_exp(agz_log((double)N_a / (double)mx) / T) : 0 (pass
+ *      included), S = sum w_a, r = agz_u01(agz_draw_u64(seed, game_id, n, AGZ_SITE_SOFTPICK, 0)) * S, and with acc += w_a
+ *      in ascending a the pick is the first a with w_a > 0 and acc > r, else the highest a with w_a > 0.  A full pool
+ *      under AGZ_POOL_MOVE_EARLY can then move on any visited child.  The recorded pi row (its n <= tau squash), q, the
+ *      resign check and the re-rooting do not change.
+ * WHERE.  Rules 1 and 2 run exactly where inject_noise! runs, the temperature first: the full self-play searches that are
+ * not Gumbel searches, and agz_tree_inject_noise on single trees (so a host-driven MCTSPlayer loop equals device
+ * self-play).  Fast searches, Gumbel searches, the arena, analysis, review and reanalysis get neither.  Rule 3 applies at
+ * every pick_move with two_player_mode off: self-play, analysis, review, reanalysis and agz_tree_pick_move.
+ * No draw site is added or moved; records, agz_game_header, agz_config and agz_stats do not change.
+ * The setters synchronise and restart the counters of agz_search_explore_counts.  Refused (AGZ_BAD_ARGUMENT, the setting
+ * in force kept): an arena_mode engine; `on` or `shaped` outside {0, 1}; shaped = 1 with total_alpha = 0; a temperature
+ * NaN or outside [0.1, 10] (root policy) / [0, 10] (move); halflife NaN, <= 0 or > 1e6; total_alpha NaN, negative or
+ * > 1000; games of a run still being played; between agz_tree_search_select and agz_tree_search_incorporate. */
+agz_status agz_selfplay_set_root_policy_temperature(agz_engine* e, int32_t on, double early, double late, double halflife);
+agz_status agz_selfplay_set_root_noise(agz_engine* e, double total_alpha, int32_t shaped);
+agz_status agz_search_set_move_temperature(agz_engine* e, int32_t on, double early, double late, double halflife);
+/* out[0] = roots tempered, out[1] = roots noised under total_alpha > 0, out[2] = moves picked by rule 3's sampling
+ * branch, out[3] = those of out[2] that are not a most-visited child; since the later of a setter call and
+ * agz_selfplay_start.  Synchronises. */
+agz_status agz_search_explore_counts(agz_engine* e, uint64_t* out /* [4] */);
+/* What agz_tree_inject_noise would do to `node` of single tree g under the engine's setting; the tree is not modified.
+ * tempered float[A]: the prior row after rule 1 (the stored row when rule 1 is off); alpha double[A]: alpha_a, 0 for an
+ * illegal action (rule 2 off: the reference's one alpha for all A); noised float[A]: the row agz_tree_inject_noise would
+ * store.  Any output may be NULL.  One small kernel; synchronises. */
+agz_status agz_tree_explore_rows(agz_engine* e, int32_t g, int32_t node, float* tempered, double* alpha, float* noised);
+/* *out = T(n) of the schedule above; host only, needs no engine.  AGZ_BAD_ARGUMENT: out is NULL. */
+agz_status agz_explore_temperature(int32_t n, double early, double late, double halflife, double* out);
 agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out);
 /* out[B], child_N / child_W / prior [B][A] (the root's rows when the search ended); any of them may be NULL */
 agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N, float* child_W, float* prior);

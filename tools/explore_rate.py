@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""Cost and data effect of root exploration and the move temperature (agz_selfplay_set_root_policy_temperature,
+agz_selfplay_set_root_noise, agz_search_set_move_temperature) at the BASELINE.json configs[1] shape, on
+rate_windows.py's alternating windows of one box.
+
+  parent  (--parent-tree DIR: a built checkout of the parent commit)  Everything off against the parent commit's library.
+          The two libraries cannot share a process, so every round runs one child process per tree -- this file, importing
+          the package from that tree -- in an order that reverses every round.  Accepted when the medians of ms per step
+          and of the k_pre microseconds lie no further apart than the parent's own max - min; otherwise the exit status is 1.
+  on      KataGo's values -- (1.25, 1.1, N), (10.83, shaped), (0.75, 0.15, N) -- against off in alternating windows of
+          the same process: ms per step, k_pre, the four counters per step.
+  data    the synthetic network has no strength to gain or lose, so this is a record of what the rules do to the data,
+          not a claim: finished self-play games at a small shape under off and on -- entropy of the recorded pi, the share
+          of moves off the most visited child, game length.
+
+Prints one JSON object."""
+import json
+import os
+import subprocess
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def katago(board):
+    return dict(pt=(1.25, 1.1, float(board)), noise=(10.83, True), mt=(0.75, 0.15, float(board)))
+
+
+def set_mode(eng, on, board):
+    k = katago(board)
+    eng.set_root_policy_temperature(k["pt"] if on else None)
+    eng.set_root_noise(*(k["noise"] if on else (0.0, False)))
+    eng.set_move_temperature(k["mt"] if on else None)
+
+
+def child(args):
+    """one tree's windows, in this process: the modes this tree's library knows"""
+    # the windows are this tree's rate_windows.py for both trees (it reports k_pre); the package is the tree's own: it is
+    # imported when the engine is made, with the tree in front of the path
+    sys.path.insert(0, HERE)
+    import rate_windows as rw
+    sys.path.insert(0, os.path.abspath(args.tree))
+    modes = tuple(args.modes.split(","))
+    has = "on" in modes                        # (the parent's library has no such calls)
+
+    def configure(eng, mode):
+        rw.set_stagger(eng, args.stagger)
+        if has:
+            set_mode(eng, mode == "on", args.board)
+
+    def collect(s0, s1, c0, c1, dt):
+        out = dict(steps_per_s=round(args.steps / dt, 3))
+        if c0 is not None:
+            out.update(counts_per_step=[round((b - a) / args.steps, 3) for a, b in zip(c0, c1)])
+        return out
+
+    eng = rw.engine(args)
+    windows = rw.windows_of(eng, args, modes, configure, collect, rw.first_search_steps(args) if args.stagger > 0 else 0,
+                            (lambda e: e.explore_counts()) if has else None)
+    eng.close()
+    print("EXPLORE_RATE_CHILD " + json.dumps(windows))
+
+
+def run_child(args, tree, modes):
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--tree", tree, "--modes", modes, "--pairs", "1"]
+    for k in ("board", "tower", "readouts", "games", "stagger", "steps", "warmup"):
+        cmd += ["--" + k, str(getattr(args, k))]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.child_timeout)
+    if r.returncode != 0:
+        raise RuntimeError(f"child on {tree} failed ({r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+    line = [x for x in r.stdout.splitlines() if x.startswith("EXPLORE_RATE_CHILD ")][-1]
+    print(f"windows of {tree} ({modes}) done", file=sys.stderr, flush=True)
+    return json.loads(line[len("EXPLORE_RATE_CHILD "):])
+
+
+def data_part(args):
+    import numpy as np
+    import alphago_jl_amd as ag
+    out = {}
+    for mode in ("off", "on"):
+        eng = ag.Engine(board_size=args.board, tower_height=args.data_tower, games=args.data_games,
+                        num_readouts=args.data_readouts, seed=1, record_capacity_games=args.data_games + 8)
+        eng.init_synthetic(0)
+        set_mode(eng, mode == "on", args.board)
+        eng.start(args.data_games)
+        while eng.records_count() < args.data_games:
+            eng.step(32)
+        recs, st, counts = eng.records(), eng.stats(), eng.explore_counts()
+        eng.close()
+        rows = np.concatenate([r["pis"][: r["num_moves"]] for r in recs if r["num_moves"]]).astype(np.float64)
+        moves = np.concatenate([r["moves"][: r["num_moves"]] for r in recs if r["num_moves"]]).astype(np.int64)
+        ent = -(np.where(rows > 0, rows * np.log(np.where(rows > 0, rows, 1.0)), 0.0)).sum(axis=1)
+        off_max = rows[np.arange(len(moves)), moves] < rows.max(axis=1)        # by the recorded pi, for both modes
+        out[mode] = dict(games=len(recs), positions=int(st["positions"]),
+                         pi_entropy_nats=round(float(ent.mean()), 4),
+                         moves_off_the_most_visited_child=round(float(off_max.mean()), 4),
+                         game_length=round(float(np.mean([r["num_moves"] for r in recs])), 2),
+                         resignation_share=round(float(np.mean([bool(r["was_resign"]) for r in recs])), 4),
+                         counters=list(counts), pool_short_searches=int(st["pool_short_searches"]))
+    return out
+
+
+def main():
+    sys.path[:0] = [os.path.dirname(HERE), HERE]
+    import rate_windows as rw
+    ap = rw.parser()
+    ap.add_argument("--child", action="store_true", help="(internal) time one tree's windows and print them")
+    ap.add_argument("--tree", default=os.path.dirname(HERE))
+    ap.add_argument("--modes", default="off,on")
+    ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit; none: no parent part")
+    ap.add_argument("--child-timeout", type=int, default=900)
+    ap.add_argument("--data-tower", type=int, default=2)
+    ap.add_argument("--data-readouts", type=int, default=100)
+    ap.add_argument("--data-games", type=int, default=256)
+    ap.add_argument("--no-data", action="store_true")
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+    this = os.path.dirname(HERE)
+    windows = dict(parent_off=[], off=[], on=[])
+    for k in range(args.pairs):
+        order = ["parent", "this"] if k % 2 == 0 else ["this", "parent"]
+        for which in order:
+            if which == "parent":
+                if args.parent_tree:
+                    windows["parent_off"] += run_child(args, args.parent_tree, "off")["off"]
+            else:
+                w = run_child(args, this, "off,on" if k % 2 == 0 else "on,off")
+                windows["off"] += w["off"]
+                windows["on"] += w["on"]
+    keys = ("ms_per_step", "steps_per_s", "moves_per_s", "evals_per_move", "search_kernels_ms_per_step", "k_pre_us_per_step")
+    res = rw.summary({m: w for m, w in windows.items() if w}, keys)
+    measured = dict(on_minus_off_ms_per_step=rw.on_minus_off(res, "ms_per_step"),
+                    on_minus_off_k_pre_us=rw.on_minus_off(res, "k_pre_us_per_step"),
+                    off_spread_ms_per_step=res["off"]["ms_per_step"]["spread"])
+    if windows["parent_off"]:
+        d = round(res["off"]["ms_per_step"]["median"] - res["parent_off"]["ms_per_step"]["median"], 4)
+        dk = round(res["off"]["k_pre_us_per_step"]["median"] - res["parent_off"]["k_pre_us_per_step"]["median"], 2)
+        measured.update(off_minus_parent_ms_per_step=d, off_minus_parent_k_pre_us=dk,
+                        parent_spread_ms_per_step=res["parent_off"]["ms_per_step"]["spread"],
+                        parent_spread_k_pre_us=res["parent_off"]["k_pre_us_per_step"]["spread"],
+                        off_within_parent_spread=bool(abs(d) <= res["parent_off"]["ms_per_step"]["spread"]
+                                                      and abs(dk) <= res["parent_off"]["k_pre_us_per_step"]["spread"]))
+    print(json.dumps(dict(
+        shape=dict(board=args.board, tower=args.tower, readouts=args.readouts, games=args.games, stagger=args.stagger),
+        setting={k: list(v) for k, v in katago(args.board).items()},
+        steps_per_window=args.steps, windows=windows, summary=res, measured=measured,
+        data=None if args.no_data else dict(
+            shape=dict(board=args.board, tower=args.data_tower, readouts=args.data_readouts, games=args.data_games),
+            note="synthetic network: what the rules do to the data, no strength claim", **data_part(args)))))
+
+    # the bar of the off path is part of the tool: outside the parent's own spread is a failure, not a figure
+    if windows["parent_off"] and not measured["off_within_parent_spread"]:
+        print("off against the parent lies outside the parent's own max - min", file=sys.stderr)
+        return 1
+    return 0
+
+if __name__ == "__main__":
+    sys.exit(main())
