@@ -203,9 +203,10 @@ class Engine {
   // shared by the option setters and their readers (`what` is the error text's prefix)
   void require_selfplay_engine(const char* what) const;
   void require_between_games(const char* what);
-  void require_explore_settable(const char* what);
-  void explore_set_done();
-  void read_counter_pair(int first, int64_t out[2]);
+  template <class Write>
+  void set_option(const char* what, bool single_trees, Write write, int first, int n);
+  template <class T>
+  void read_counters(int first, int n, T* out);
   template <class Launch>
   void read_tree_pi_row(float* out, Launch launch);
   void set_all_slots(int phase);

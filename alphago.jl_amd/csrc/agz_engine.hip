@@ -1080,21 +1080,40 @@ static void check_lines(int K, int K_min, int D, int min_visits) {
   AGZ_REQUIRE(min_visits >= 1, AGZ_BAD_ARGUMENT, "lines: min_visits = %d, not >= 1", min_visits);
 }
 
-// counters[first] and counters[first + 1]: {full, fast} moves, {forced descents, pruned rows}, {begun, halved}
-void Engine::read_counter_pair(int first, int64_t out[2]) {
-  unsigned long long c[2];
-  down(c, V_.counters + first, 2);
+// what follows a setter's own range checks: single_trees = the option also steers single-tree searches, so it does not
+// change inside a select / incorporate pair; write(V_) stores the setting; the counters [first, first + n) of the option
+// restart (n = 0: it has none that a setter clears)
+template <class Write>
+void Engine::set_option(const char* what, bool single_trees, Write write, int first, int n) {
+  AGZ_REQUIRE(!single_trees || tree_batch_ == 0, AGZ_BAD_ARGUMENT,
+              "%s: not between agz_tree_search_select and agz_tree_search_incorporate", what);
+  require_between_games(what);
   wait();
-  out[0] = (int64_t)c[0];
-  out[1] = (int64_t)c[1];
+  write(V_);
+  if (n == 0) return;
+  AGZ_HIP(hipMemsetAsync(V_.counters + first, 0, sizeof(unsigned long long) * n, stream_));
+  wait();
+}
+
+// counters[first .. first + n): {full, fast} moves, {forced descents, pruned rows}, {begun, halved}, {levels, unvisited},
+// {tempered, noised, sampled, off the most visited}
+template <class T>
+void Engine::read_counters(int first, int n, T* out) {
+  unsigned long long c[4];
+  down(c, V_.counters + first, (size_t)n);
+  wait();
+  for (int i = 0; i < n; ++i) out[i] = (T)c[i];
 }
 static_assert(CT_CAP_FAST == CT_CAP_FULL + 1 && CT_PRUNED_ROWS == CT_FORCED_SEL + 1 && CT_GUMBEL_HALVED == CT_GUMBEL_BEGUN + 1 &&
                   CT_PUCT_UNVISITED == CT_PUCT_LEVELS + 1,
               "the counters of an option are read as one pair");
-void Engine::playout_cap_counts(int64_t out[2]) { read_counter_pair(CT_CAP_FULL, out); }
-void Engine::forced_counts(int64_t out[2]) { read_counter_pair(CT_FORCED_SEL, out); }
-void Engine::gumbel_counts(int64_t out[2]) { read_counter_pair(CT_GUMBEL_BEGUN, out); }
-void Engine::puct_counts(int64_t out[2]) { read_counter_pair(CT_PUCT_LEVELS, out); }
+static_assert(CT_EXP_NOISED == CT_EXP_TEMPERED + 1 && CT_EXP_SAMPLED == CT_EXP_TEMPERED + 2 &&
+                  CT_EXP_OFF_MAX == CT_EXP_TEMPERED + 3, "the four counters are cleared and read as one run");
+void Engine::playout_cap_counts(int64_t out[2]) { read_counters(CT_CAP_FULL, 2, out); }
+void Engine::forced_counts(int64_t out[2]) { read_counters(CT_FORCED_SEL, 2, out); }
+void Engine::gumbel_counts(int64_t out[2]) { read_counters(CT_GUMBEL_BEGUN, 2, out); }
+void Engine::puct_counts(int64_t out[2]) { read_counters(CT_PUCT_LEVELS, 2, out); }
+void Engine::explore_counts(uint64_t out[4]) { read_counters(CT_EXP_TEMPERED, 4, out); }
 
 // one pi row [A] of a single tree's node: `launch` writes it to the device row it is given
 template <class Launch>
@@ -1113,9 +1132,7 @@ void Engine::set_playout_cap(int fast_readouts, double full_prob) {
               "playout cap: %d fast readouts, 0 (off) or 1..num_readouts = %d", fast_readouts, V_.R);
   AGZ_REQUIRE(fast_readouts == 0 || (full_prob >= 0.0 && full_prob <= 1.0), AGZ_BAD_ARGUMENT,
               "playout cap: full_prob %g not in [0, 1]", full_prob);
-  require_between_games("playout cap");
-  wait();
-  view_set_playout_cap(V_, fast_readouts, full_prob);
+  set_option("playout cap", false, [&](View& V) { view_set_playout_cap(V, fast_readouts, full_prob); }, 0, 0);
 }
 
 void Engine::set_forced_playouts(double k, int prune) {
@@ -1123,9 +1140,7 @@ void Engine::set_forced_playouts(double k, int prune) {
   check_forced_k("forced playouts", "0 (off) .. 1024", k);
   AGZ_REQUIRE(prune == 0 || k > 0.0, AGZ_BAD_ARGUMENT, "forced playouts: pruning needs k > 0");
   AGZ_REQUIRE(!(k > 0.0) || V_.gumbel_m == 0, AGZ_BAD_ARGUMENT, "forced playouts: the Gumbel root search is on (m = %d)", V_.gumbel_m);
-  require_between_games("forced playouts");
-  wait();
-  view_set_forced_playouts(V_, k, prune);
+  set_option("forced playouts", false, [&](View& V) { view_set_forced_playouts(V, k, prune); }, 0, 0);
 }
 
 void Engine::tree_pruned_pi(int g, int node, double k, float* out) {
@@ -1142,9 +1157,7 @@ void Engine::set_gumbel(int m, double c_visit, double c_scale) {
               kGumbelMax);
   check_gumbel_c("gumbel", c_visit, c_scale);
   AGZ_REQUIRE(m == 0 || !(V_.forced_k > 0.0), AGZ_BAD_ARGUMENT, "gumbel: forced playouts are on (k = %g)", V_.forced_k);
-  require_between_games("gumbel");
-  wait();
-  view_set_gumbel(V_, m, c_visit, c_scale);
+  set_option("gumbel", false, [&](View& V) { view_set_gumbel(V, m, c_visit, c_scale); }, 0, 0);
 }
 
 // ---- the PUCT rule options (agz_search_set_puct): every search of every engine, so no require_selfplay_engine
@@ -1155,13 +1168,7 @@ void Engine::set_puct(int fpu_on, double r, double r_root, double c_base) {
   AGZ_REQUIRE(r_root >= 0.0 && r_root <= 4.0, AGZ_BAD_ARGUMENT, "puct: fpu_reduction_root = %g, not in 0 .. 4", r_root);
   AGZ_REQUIRE(c_base == 0.0 || (c_base >= 1.0 && c_base <= 1.0e9), AGZ_BAD_ARGUMENT,
               "puct: c_base = %g, not 0 (off) or in 1 .. 1e9", c_base);
-  AGZ_REQUIRE(tree_batch_ == 0, AGZ_BAD_ARGUMENT,
-              "puct: not between agz_tree_search_select and agz_tree_search_incorporate");
-  require_between_games("puct");
-  wait();
-  view_set_puct(V_, fpu_on, r, r_root, c_base);
-  AGZ_HIP(hipMemsetAsync(V_.counters + CT_PUCT_LEVELS, 0, sizeof(unsigned long long) * 2, stream_));
-  wait();
+  set_option("puct", true, [&](View& V) { view_set_puct(V, fpu_on, r, r_root, c_base); }, CT_PUCT_LEVELS, 2);
 }
 
 // ---- root exploration and the move temperature (agz_selfplay_set_root_policy_temperature / _set_root_noise,
@@ -1172,47 +1179,25 @@ static void check_explore(const char* what, const char* why) {
   AGZ_REQUIRE(!why, AGZ_BAD_ARGUMENT, "%s: %s", what, why ? why : "");
 }
 
-// what the three setters share after their own range checks; then the caller writes the View and calls explore_set_done
-void Engine::require_explore_settable(const char* what) {
-  require_selfplay_engine(what);
-  AGZ_REQUIRE(tree_batch_ == 0, AGZ_BAD_ARGUMENT,
-              "%s: not between agz_tree_search_select and agz_tree_search_incorporate", what);
-  require_between_games(what);
-  wait();
-}
-void Engine::explore_set_done() {
-  AGZ_HIP(hipMemsetAsync(V_.counters + CT_EXP_TEMPERED, 0, sizeof(unsigned long long) * 4, stream_));
-  wait();
-}
-static_assert(CT_EXP_NOISED == CT_EXP_TEMPERED + 1 && CT_EXP_SAMPLED == CT_EXP_TEMPERED + 2 &&
-                  CT_EXP_OFF_MAX == CT_EXP_TEMPERED + 3, "the four counters are cleared and read as one run");
-
+// ... and an arena engine is refused after them; every taken setter restarts the four counters
 void Engine::set_root_policy_temperature(int on, double early, double late, double halflife) {
   check_explore("root policy temperature", explore_schedule_refusal(V_, on, early, late, halflife, 0.1));
-  require_explore_settable("root policy temperature");
-  view_set_root_policy_temperature(V_, on, early, late, halflife);
-  explore_set_done();
+  require_selfplay_engine("root policy temperature");
+  set_option("root policy temperature", true,
+             [&](View& V) { view_set_root_policy_temperature(V, on, early, late, halflife); }, CT_EXP_TEMPERED, 4);
 }
 
 void Engine::set_root_noise(double total_alpha, int shaped) {
   check_explore("root noise", explore_noise_refusal(V_, total_alpha, shaped));
-  require_explore_settable("root noise");
-  view_set_root_noise(V_, total_alpha, shaped);
-  explore_set_done();
+  require_selfplay_engine("root noise");
+  set_option("root noise", true, [&](View& V) { view_set_root_noise(V, total_alpha, shaped); }, CT_EXP_TEMPERED, 4);
 }
 
 void Engine::set_move_temperature(int on, double early, double late, double halflife) {
   check_explore("move temperature", explore_schedule_refusal(V_, on, early, late, halflife, 0.0));
-  require_explore_settable("move temperature");
-  view_set_move_temperature(V_, on, early, late, halflife);
-  explore_set_done();
-}
-
-void Engine::explore_counts(uint64_t out[4]) {
-  unsigned long long c[4];
-  down(c, V_.counters + CT_EXP_TEMPERED, 4);
-  wait();
-  for (int i = 0; i < 4; ++i) out[i] = (uint64_t)c[i];
+  require_selfplay_engine("move temperature");
+  set_option("move temperature", true, [&](View& V) { view_set_move_temperature(V, on, early, late, halflife); },
+             CT_EXP_TEMPERED, 4);
 }
 
 void Engine::tree_explore_rows(int g, int node, float* tempered, double* alpha, float* noised) {

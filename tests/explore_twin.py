@@ -7,23 +7,18 @@ or_det_log, or_det_exp, or_dirichlet_gamma, or_draw_u64 and or_draw_u01.  twin_s
 selfplay_twin.twin_selfplay with two steps replaced by the restatement: the noise of a full search, written into the
 oracle root's prior row in place, and the pick of the move.
 
-Also here: the host simulator with the setters -- tests/hostsim/hostsim_explore.cpp, built to a library of its own with
-the flags of the Makefile next to it and bound like hs.lib() -- and a callback that lets a network of feature rows (such
-as puct_twin.PeakedNet) answer the oracle's positions."""
+Also here: a callback that lets a network of feature rows (such as hs.PeakedNet) answer the oracle's positions, a run of
+the host simulator (hs.Sim: apply, explore_counts, explore_rows, set_pick_case) under a setting, and the settings, game
+sets, rows and positions that the CPU tests (tests/test_explore.py) and the device tests (tests/test_gpu_explore.py) share."""
 import ctypes as C
-import os
-import re
-import shlex
-import subprocess
 
 import numpy as np
 
 import hs
 import orc
 import selfplay_twin as tw
+from hs import bits32, bits64
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 L = tw.L
 L.or_dirichlet_gamma.restype = C.c_double
 L.or_dirichlet_gamma.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double]
@@ -180,18 +175,10 @@ def pick_move(Nrow, n, seed, game, mt, N):
     return True, int(pick), True, bool(Nrow[pick] != mx)
 
 
-def bits32(x):
-    return np.ascontiguousarray(x, f32).view(np.uint32)
-
-
-def bits64(x):
-    return np.ascontiguousarray(x, f64).view(np.uint64)
-
-
 # ---------------------------------------------------------------- a feature-row network in front of the oracle
 
 class FeatsNet:
-    """net(feats [B, 17 * P] float32) -> (pi, v), such as puct_twin.PeakedNet, as the oracle's network callback: the
+    """net(feats [B, 17 * P] float32) -> (pi, v), such as hs.PeakedNet, as the oracle's network callback: the
     positions go through or_get_feats, so the simulator (hs_leaf_features) and the oracle ask the same rows"""
 
     def __init__(self, net, N):
@@ -310,96 +297,12 @@ def tallies(twins):
     return tuple(int(sum(o[k] for o in twins)) for k in ("tempered", "noised", "sampled", "off_max"))
 
 
-# ---------------------------------------------------------------- the simulator with the setters
-
-_lib = None
-SRC = os.path.join(HERE, "hostsim", "hostsim_explore.cpp")
-
-
-def _sources():
-    c = os.path.join(ROOT, "alphago.jl_amd", "csrc")
-    return [SRC, os.path.join(HERE, "hostsim", "hostsim.cpp"),
-            os.path.join(c, "agz_search.h"), os.path.join(c, "agz_state.h"), os.path.join(c, "agz_layout.h"),
-            os.path.join(ROOT, "include", "agz_draws.h"), os.path.join(ROOT, "include", "agz_explore.h"),
-            os.path.join(ROOT, "include", "agz.h")]
-
-
-def compile_command(src, out, extra=()):
-    """the Makefile's g++ line next to hostsim.cpp, for another source and output"""
-    d = os.path.join(HERE, "hostsim")
-    mk = open(os.path.join(d, "Makefile")).read()
-    cmd = shlex.split(re.search(r"^\t(g\+\+ .*)$", mk, flags=re.M).group(1))
-    return [src if t == "$<" else out if t == "$@" else t for t in cmd] + ["-Wno-unknown-pragmas"] + list(extra)
-
-
-def lib():
-    """tests/hostsim/libhostsim_explore.so: hostsim.cpp + the setters, with hs.lib()'s prototypes"""
-    global _lib
-    if _lib is not None:
-        return _lib
-    base = hs.lib()
-    out = os.path.join(HERE, "hostsim", "libhostsim_explore.so")
-    if not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in _sources()):
-        subprocess.run(compile_command(SRC, out + ".tmp"), check=True)
-        os.replace(out + ".tmp", out)
-    Lx = C.CDLL(out)
-    for name, fn in list(vars(base).items()):
-        if name.startswith("hs_") and hasattr(fn, "argtypes"):
-            g = getattr(Lx, name)
-            g.restype, g.argtypes = fn.restype, fn.argtypes
-    vp, i, dbl = C.c_void_p, C.c_int, C.c_double
-    P = C.POINTER
-    for name, (res, args) in {"hs_set_root_policy_temperature": (i, [vp, i, dbl, dbl, dbl]),
-                              "hs_set_root_noise": (i, [vp, dbl, i]),
-                              "hs_set_move_temperature": (i, [vp, i, dbl, dbl, dbl]),
-                              "hs_explore_counts": (None, [vp, P(C.c_ulonglong)]),
-                              "hs_explore_rows": (None, [vp, i, i, P(C.c_float), P(dbl), P(C.c_float)]),
-                              "hs_temperature": (dbl, [i, dbl, dbl, dbl]),
-                              "hs_set_pick_case": (None, [vp, i, P(C.c_float), C.c_ulonglong, i])}.items():
-        g = getattr(Lx, name)
-        g.restype, g.argtypes = res, args
-    _lib = Lx
-    return Lx
-
-
-class Sim(hs.Sim):
-    """hs.Sim on the library with the setters"""
-
-    def __init__(self, **cfg):
-        self.L = lib()
-        self.cfg = hs.default_config(**cfg)
-        self.h = self.L.hs_create(C.byref(self.cfg))
-        d = (C.c_int32 * 10)()
-        self.L.hs_dims(self.h, d)
-        (self.N, self.P, self.A, self.AP, self.cap, self.games, self.par, self.mgl, self.tau, self.maxd) = list(d)
-
-    def apply(self, st):
-        """the three setters from a setting; an off part is set off"""
-        pt, (total, shaped), mt = st["pt"], st["noise"], st["mt"]
-        off = (0, 1.0, 1.0, 1.0)
-        assert self.L.hs_set_root_policy_temperature(self.h, *(off if pt is None else (1,) + schedule_of(pt, self.N))) == 0
-        assert self.L.hs_set_root_noise(self.h, float(total), 1 if shaped else 0) == 0
-        assert self.L.hs_set_move_temperature(self.h, *(off if mt is None else (1,) + schedule_of(mt, self.N))) == 0
-
-    def explore_counts(self):
-        out = (C.c_ulonglong * 4)()
-        self.L.hs_explore_counts(self.h, out)
-        return tuple(int(x) for x in out)
-
-    def explore_rows(self, node, g=0):
-        t, al, nz = np.zeros(self.A, f32), np.zeros(self.A, f64), np.zeros(self.A, f32)
-        self.L.hs_explore_rows(self.h, g, node, hs.pf(t), al.ctypes.data_as(C.POINTER(C.c_double)), hs.pf(nz))
-        return t, al, nz
-
-    def set_pick_case(self, Nrow, game_id, n, g=0):
-        row = np.ascontiguousarray(Nrow, f32)
-        self.L.hs_set_pick_case(self.h, g, hs.pf(row), int(game_id), int(n))
-
+# ---------------------------------------------------------------- the simulator under a setting
 
 def run_sim(N, net, R, seed, games, slots, st, cap=None, forced=None, starts=None, max_steps=400000, **cfg):
     """self-play of `games` games on the simulator under setting st (None: no setter is called) -> (records, counters,
     the four explore counters)"""
-    sim = Sim(board_size=N, games=slots, num_readouts=R, seed=seed, game_id_base=0, game_id_stride=1,
+    sim = hs.Sim(board_size=N, games=slots, num_readouts=R, seed=seed, game_id_base=0, game_id_stride=1,
               record_capacity_games=games + 8, **cfg)
     if starts:
         sim.set_starts(starts)
@@ -433,3 +336,61 @@ def prior_kinds(A, legal, seed):
     peaked = np.full(A, (1.0 - 0.6) / A, f32)
     peaked[lg[len(lg) // 2]] += f32(0.6)
     return {"random": rand, "constant": np.full(A, 1.0 / A, f32), "big_and_zero": big, "peaked": peaked}
+
+
+def ko_position(N):
+    """tw.ko_start(N); on the boards where seeded random play meets no ko early enough, the textbook shape played out"""
+    try:
+        return tw.ko_start(N)
+    except AssertionError:
+        pass
+    b = np.zeros(N * N, np.int8)
+    for (r, c), s in {(0, 1): 1, (1, 0): 1, (2, 1): 1, (1, 1): -1, (0, 2): -1, (2, 2): -1, (1, 3): -1}.items():
+        b[r + N * c] = s
+    rcode, pos = orc.play(orc.make_pos(N, board=b, n=8), 1 + N * 2)
+    assert rcode == orc.OK and pos.ko == 1 + N * 1
+    return pos.copy()
+
+
+def positions(N):
+    cap = tw.random_start(N, (N * N * 6) // 5, 40 + N)
+    assert cap.caps[0] + cap.caps[1] > 0, "the random start has captures"
+    return {"empty": orc.make_pos(N), "ko": ko_position(N), "captures": cap}
+
+
+def pick_rows(A, seed):
+    rng = np.random.RandomState(seed)
+    one = np.zeros(A, f32)
+    one[A // 3] = 5
+    ties = np.zeros(A, f32)
+    ties[[1, A // 2, A - 2]] = 7
+    ties[2] = 3
+    only_pass = np.zeros(A, f32)
+    only_pass[A - 1] = 4
+    big = np.zeros(A, f32)
+    idx = rng.choice(A, min(A, 12), replace=False)
+    big[idx] = rng.randint(1, 1601, len(idx))
+    big[idx[0]] = 1600
+    dense = rng.randint(0, 40, A).astype(f32)
+    ones = np.ones(A, f32)
+    return {"one": one, "ties": ties, "only_pass": only_pass, "big": big, "dense": dense, "ones": ones}
+
+
+# ---------------------------------------------------------------- settings and game sets
+
+GAME_SETTING = setting(pt=(1.25, 1.1, None), noise=(10.83, True), mt=(0.75, 0.0, 2.0))
+SETTINGS = {
+    "all": GAME_SETTING,
+    "katago": KATAGO,
+    "temper_only": setting(pt=(0.8, 1.3, 4.0)),
+    "unit_temper": setting(pt=(1.0, 1.0, 7.0)),
+    "unshaped": setting(noise=(3.0, False)),
+    "shaped": setting(noise=(10.83, True)),
+    "off": OFF,
+}
+GAME_SETS = {5: dict(R=24, seed=21, games=8, slots=4), 9: dict(R=32, seed=22, games=8, slots=4)}
+COMPOSE = {"plain": {}, "cap": dict(cap=(8, 0.5)), "forced": dict(forced=(2.0, True)), "starts": dict(starts=True)}
+
+
+def starts_of(N):
+    return tw.random_starts(N, (4, 7, 1), seed=0)

@@ -1,14 +1,115 @@
-"""What the GPU tests of the self-play search options share (test_gpu_starts.py, test_gpu_playout_cap.py,
-test_gpu_forced_playouts.py, test_gpu_gumbel.py; test_gpu_train_batched.py takes the arena helpers): playing a run to its
-records, a record against the twin's game (tests/selfplay_twin.py), and train() against the same schedule composed of
-single calls, whose games are the twin's on the weights in force round by round.  Test infrastructure only."""
+"""What the GPU tests of the search options share (test_gpu_starts.py, test_gpu_playout_cap.py,
+test_gpu_forced_playouts.py, test_gpu_gumbel.py, test_gpu_symmetry.py, test_gpu_puct.py, test_gpu_explore.py;
+test_gpu_train_batched.py takes the arena helpers): engines with a peaked policy, setting the options of an engine or a
+simulator from one dict, playing a run to its records, a record against another record or against the twin's game
+(tests/selfplay_twin.py), and train() against the same schedule composed of single calls, whose games are the twin's on
+the weights in force round by round.  Test infrastructure only."""
+import ctypes as C
+
 import numpy as np
 
 import alphago_jl_amd as ag
+import explore_twin as ex
+import hs
+import orc
 import selfplay_twin as tw
-from gpu_common import GpuNetForOracle
+from alphago_jl_amd import symmetry as sy
+from gpu_common import GpuNetForOracle, pos_soa
+from test_gpu_analysis import api_positions        # noqa: F401  (the API positions and games that the option files
+from test_gpu_review import api_game               # noqa: F401   give analyze and review)
 from test_hostsim_selfplay import bits_equal
 from test_train_loop_batched import sample_entries, window_pairs
+
+
+def sharpen(engine, N):
+    """scale the policy FC of the selected network by the smallest power of two k that makes pi max > 0.5 on random
+    positions (the synthetic FC bias is zero, so the logits scale by k): with the flat glorot policy a wrong remap
+    would hide in the noise"""
+    w = engine.get_weights(orc.L_POLICY_FC, 0)
+    pi0, _ = engine.forward_features(rand_feats(N, 8, seed=123))
+    logp = np.log(pi0.astype(np.float64))
+    for k in (2.0 ** i for i in range(1, 10)):
+        z = k * logp - (k * logp).max(axis=1, keepdims=True)
+        if (np.exp(z) / np.exp(z).sum(axis=1, keepdims=True)).max(axis=1).min() > 0.5:
+            break
+    engine.set_weights(orc.L_POLICY_FC, 0, (w * k).astype(np.float32))
+
+
+def peaked_engine(N, tower, **kw):
+    e = ag.Engine(board_size=N, tower_height=tower, **kw)
+    e.init_synthetic(0)
+    sharpen(e, N)
+    return e
+
+
+def rand_feats(N, B, seed=0):
+    x = (np.random.RandomState(seed).rand(B, 17 * N * N) < 0.3).astype(np.float32)
+    x[:, 16 * N * N:] = 1.0
+    return x
+
+
+class SymNetForOracle:
+    """an or_net_fn for ONE game (or one arena player): evaluation e of the game is made under T_s with s predicted by
+    the mirror of the draw key (or fixed): features of the oracle's positions, host transform, the plain GPU forward,
+    host un-permute"""
+
+    def __init__(self, engine, seed, game_id, mode, plain_first=0):
+        self.engine, self.seed, self.game_id, self.mode = engine, seed, game_id, mode
+        self.plain_first = plain_first      # evaluations made before the mode was switched on: T_0
+        self.e = 0
+        self.syms = []
+        N = engine.N
+
+        def _fn(ctx, positions, B, pi, v):
+            plist = [positions[b].contents for b in range(B)]
+            feats = engine.features(*pos_soa(plist))
+            sym = []
+            for _ in range(B):
+                if self.e < self.plain_first:
+                    sym.append(0)
+                else:
+                    sym.append(self.mode if self.mode != sy.RANDOM else sy.draw_symmetry(self.seed, self.game_id, self.e))
+                self.e += 1
+            self.syms += sym
+            tx = np.stack([sy.apply_features(feats[b], sym[b], N) for b in range(B)])
+            gpi, gv = engine.forward_features(tx)
+            gpi = np.ascontiguousarray(np.stack([sy.apply_policy(gpi[b], sy.inverse(sym[b]), N) for b in range(B)]),
+                                       np.float32)
+            C.memmove(pi, gpi.ctypes.data, 4 * B * engine.A)
+            C.memmove(v, np.ascontiguousarray(gv, np.float32).ctypes.data, 4 * B)
+
+        self.cb = orc.NET_FN(_fn)
+
+
+def apply(eng, st):
+    """the three exploration setters of an engine from a setting of explore_twin; an off part is set off"""
+    sched = lambda t: None if t is None else ex.schedule_of(t, eng.N)
+    eng.set_root_policy_temperature(sched(st["pt"]))
+    eng.set_root_noise(*st["noise"])
+    eng.set_move_temperature(sched(st["mt"]))
+
+
+def configure(x, opt):
+    """the options of ag.Engine or hs.Sim x from opt: starts (oracle positions), cap (fast readouts, full probability),
+    forced (k, prune), gumbel (m), symmetry (random), explore (a setting of explore_twin).  A key left out is a setter
+    not called."""
+    sim = isinstance(x, hs.Sim)
+    if opt.get("starts"):
+        if sim:
+            x.set_starts(opt["starts"])
+        else:
+            b, i, h = tw.opos_arrays(opt["starts"])
+            x.set_starts(boards=b, info=i, history=h)
+    if "cap" in opt:
+        x.set_playout_cap(*opt["cap"])
+    if "forced" in opt:
+        x.set_forced_playouts(*opt["forced"])
+    if "gumbel" in opt:
+        x.set_gumbel(opt["gumbel"], 50.0, 1.0)
+    if "symmetry" in opt:
+        x.set_symmetry(8 if sim else "random")
+    if opt.get("explore") is not None:
+        x.apply(opt["explore"]) if sim else apply(x, opt["explore"])
 
 
 def play(eng, games, network=None, white=None, chunk=8, sort=True):
@@ -27,6 +128,20 @@ def play(eng, games, network=None, white=None, chunk=8, sort=True):
     recs, st = eng.records(), eng.stats()
     assert len(recs) == games and st["pool_exhausted"] == 0 and st["pool_short_searches"] == 0
     return (sorted(recs, key=lambda r: r["game_id"]) if sort else recs), st
+
+
+RECORD = ("game_id", "num_moves", "moves", "result", "was_resign", "pis", "qs")
+
+
+def same_game(r, o, fields=RECORD):
+    """records r and o agree in `fields`: floats and float rows bit for bit"""
+    def same(k):
+        if k in ("pis", "qs"):
+            return bits_equal(r[k], o[k])
+        if k == "final_score":
+            return np.float32(r[k]) == np.float32(o[k])
+        return (r[k] == o[k]).all() if k == "moves" else r[k] == o[k]
+    return all(same(k) for k in fields)
 
 
 def assert_game_equals_twin(r, o, what, full=None):

@@ -1,4 +1,4 @@
-// explore_sanitize.cpp -- TEST INFRASTRUCTURE: a program of its own around hostsim_explore.cpp, for a build under
+// explore_sanitize.cpp -- TEST INFRASTRUCTURE: a program of its own around hostsim.cpp, for a build under
 // -fsanitize=address,undefined (tests/test_explore.py).  A check of memory and undefined behaviour, not of results: it
 // plays the shapes, options and counts of that test's game sets, not its networks or start positions -- 5x5 / R = 24 and 9x9 /
 // R = 32, eight games each on four slots, under the root policy temperature (1.25, 1.1, N), shaped noise of 10.83 and the
@@ -6,7 +6,7 @@
 // table of starts -- on a peaked hash network of its own, and reads the rows of every root once.
 #include <cstdio>
 
-#include "hostsim_explore.cpp"
+#include "hostsim.cpp"
 
 namespace {
 

@@ -71,6 +71,10 @@ void alloc_one(Sim* s, T*& p, size_t n) {
   s->bufs.push_back(p);
 }
 
+void clear_explore_counts(agz::View& V) {
+  for (int i = 0; i < 4; ++i) V.counters[agz::CT_EXP_TEMPERED + i] = 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -392,6 +396,108 @@ int hs_gumbel_schedule(int n, int m0, int32_t* out, int cap) {
     m = m == 1 ? 1 : (m / 2 > 2 ? m / 2 : 2);
   }
   return k;
+}
+
+// the PUCT rule options (View::fpu_on / fpu_r / fpu_r_root / c_base, agz_search_set_puct):
+// (0, 0, 0, 0) switches the rule off.  The two counters restart here (hs_start clears the enum's counters only).
+void hs_set_puct(void* h, int fpu_on, double r, double r_root, double c_base) {
+  agz::View& V = ((Sim*)h)->V;
+  agz::view_set_puct(V, fpu_on, r, r_root, c_base);
+  V.counters[agz::CT_PUCT_LEVELS] = 0;
+  V.counters[agz::CT_PUCT_UNVISITED] = 0;
+}
+
+// out[0] = tree levels scored under an active rule, out[1] = those that picked an unvisited child
+void hs_puct_counts(void* h, unsigned long long* out) {
+  const agz::View& V = ((Sim*)h)->V;
+  out[0] = V.counters[agz::CT_PUCT_LEVELS];
+  out[1] = V.counters[agz::CT_PUCT_UNVISITED];
+}
+
+// the leaves of slot g's last select phase: nodes [par], plen [par], paths [par][maxd] (root first); returns how many
+int hs_leaf_paths(void* h, int g, int32_t* nodes, int32_t* plen, int32_t* paths) {
+  const agz::View& V = ((Sim*)h)->V;
+  const int n = V.gs[g].nleaves;
+  for (int k = 0; k < n; ++k) {
+    const long li = (long)g * V.par + k;
+    nodes[k] = V.leaf_node[li];
+    plen[k] = V.leaf_plen[li];
+    for (int i = 0; i < V.leaf_plen[li]; ++i) paths[(long)k * V.maxd + i] = V.leaf_path[li * V.maxd + i];
+  }
+  return n;
+}
+
+// board symmetries of the leaf evaluations (View::symmetry, agz_selfplay_set_symmetry): mode -1 = none, 0..7 = fixed,
+// 8 = one drawn T_s per evaluation.  The simulator has no network: the caller evaluates leaf k under hs_leaf_syms()[k]
+void hs_set_symmetry(void* h, int mode) { ((Sim*)h)->V.symmetry = mode < 0 ? 0 : mode + 1; }
+
+// the s of every row of the batch hs_pre just assigned (out [batch]); all 0 while the mode is none
+void hs_leaf_syms(void* h, int32_t* out) {
+  const agz::View& V = ((Sim*)h)->V;
+  for (int g = 0; g < V.games; ++g)
+    for (int k = 0; k < V.gs[g].nleaves; ++k)
+      out[V.gs[g].leaf_base + k] = V.symmetry ? V.leaf_sym[(long)g * V.par + k] : 0;
+}
+
+// root exploration and the move temperature (View::pt_* / noise_* / mt_*; agz_selfplay_set_root_policy_temperature,
+// agz_selfplay_set_root_noise, agz_search_set_move_temperature).
+// The setters check their arguments with the engine's own checks (explore_*_refusal, agz_state.h) and return AGZ_OK, or
+// AGZ_BAD_ARGUMENT with the setting in force kept.  The counters restart at every setter that is taken (hs_start clears
+// the enum's counters only).
+int hs_set_root_policy_temperature(void* h, int on, double early, double late, double halflife) {
+  agz::View& V = ((Sim*)h)->V;
+  if (agz::explore_schedule_refusal(V, on, early, late, halflife, 0.1)) return AGZ_BAD_ARGUMENT;
+  agz::view_set_root_policy_temperature(V, on, early, late, halflife);
+  clear_explore_counts(V);
+  return AGZ_OK;
+}
+
+int hs_set_root_noise(void* h, double total_alpha, int shaped) {
+  agz::View& V = ((Sim*)h)->V;
+  if (agz::explore_noise_refusal(V, total_alpha, shaped)) return AGZ_BAD_ARGUMENT;
+  agz::view_set_root_noise(V, total_alpha, shaped);
+  clear_explore_counts(V);
+  return AGZ_OK;
+}
+
+int hs_set_move_temperature(void* h, int on, double early, double late, double halflife) {
+  agz::View& V = ((Sim*)h)->V;
+  if (agz::explore_schedule_refusal(V, on, early, late, halflife, 0.0)) return AGZ_BAD_ARGUMENT;
+  agz::view_set_move_temperature(V, on, early, late, halflife);
+  clear_explore_counts(V);
+  return AGZ_OK;
+}
+
+// out[4] = roots tempered, roots noised under total_alpha > 0, moves sampled, those off the most visited child
+void hs_explore_counts(void* h, unsigned long long* out) {
+  const agz::View& V = ((Sim*)h)->V;
+  for (int i = 0; i < 4; ++i) out[i] = V.counters[agz::CT_EXP_TEMPERED + i];
+}
+
+// what k_tree_explore_rows runs: root_explore of `node` of slot g on a copy of its prior row; tempered float[A], alpha
+// double[A], noised float[A], any may be null.  The tree is not written.
+void hs_explore_rows(void* h, int g, int node, float* tempered, double* alpha, float* noised) {
+  Sim* s = (Sim*)h;
+  SimWave w;
+  const agz::View& V = s->V;
+  const long ni = agz::node_index(V, g, node);
+  std::vector<float> row(V.childP + ni * V.AP, V.childP + (ni + 1) * V.AP);
+  agz::root_explore(w, V, s->S, g, node, row.data(), tempered, alpha);
+  if (noised) memcpy(noised, row.data(), sizeof(float) * (size_t)V.A);
+}
+
+double hs_temperature(int n, double early, double late, double halflife) {
+  return agz_temperature(n, early, late, halflife);
+}
+
+// child_N of `node` of slot g := row [A]; the draw key of the slot's next pick: game id and position.n of the root
+void hs_set_pick_case(void* h, int g, const float* child_N, unsigned long long game_id, int n) {
+  Sim* s = (Sim*)h;
+  agz::View& V = s->V;
+  const long ni = agz::node_index(V, g, V.gs[g].root);
+  for (int a = 0; a < V.A; ++a) V.childN[ni * V.AP + a] = child_N[a];
+  V.gs[g].game_id = game_id;
+  V.meta[ni].n = n;
 }
 
 // ---- batched analysis and game review (agz_analyze_start / agz_review_start; no lines, no reanalysis)

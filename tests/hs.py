@@ -4,10 +4,12 @@ import ctypes as C
 import os
 import re
 import subprocess
+import zlib
 
 import numpy as np
 
 import alphago_jl_amd as ag
+from alphago_jl_amd import symmetry as sy
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CT = ["steps", "positions", "started", "finished", "evals", "dup", "terminal", "rootvisits",
@@ -96,10 +98,11 @@ class GumbelStateC(C.Structure):
  TOP_SEARCH_SELECT, TOP_SEARCH_POST, TOP_PICK, TOP_PLAY, TOP_RESIGN, TOP_SCORES, TOP_PENDING) = range(14)
 
 _lib = None
+sig = None                   # name -> (restype, argtypes) of every export of hostsim.cpp, once lib() has run
 
 
 def lib():
-    global _lib
+    global _lib, sig
     if _lib is not None:
         return _lib
     d = os.path.join(HERE, "hostsim")
@@ -139,6 +142,13 @@ def lib():
         "hs_set_gumbel": (None, [vp, i, dbl, dbl]), "hs_gumbel_counts": (None, [vp, P(C.c_ulonglong)]),
         "hs_gumbel_state": (None, [vp, i, P(GumbelStateC)]), "hs_gumbel_pi": (None, [vp, i, i, dbl, dbl, P(f)]),
         "hs_gumbel_descend": (i, [vp, i, P(C.c_int16), i]), "hs_gumbel_schedule": (i, [i, i, P(C.c_int32), i]),
+        "hs_set_puct": (None, [vp, i, dbl, dbl, dbl]), "hs_puct_counts": (None, [vp, P(C.c_ulonglong)]),
+        "hs_leaf_paths": (i, [vp, i, P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
+        "hs_set_symmetry": (None, [vp, i]), "hs_leaf_syms": (None, [vp, P(C.c_int32)]),
+        "hs_set_root_policy_temperature": (i, [vp, i, dbl, dbl, dbl]), "hs_set_root_noise": (i, [vp, dbl, i]),
+        "hs_set_move_temperature": (i, [vp, i, dbl, dbl, dbl]), "hs_explore_counts": (None, [vp, P(C.c_ulonglong)]),
+        "hs_explore_rows": (None, [vp, i, i, P(f), P(dbl), P(f)]), "hs_temperature": (dbl, [i, dbl, dbl, dbl]),
+        "hs_set_pick_case": (None, [vp, i, P(f), C.c_ulonglong, i]),
         "hs_node_lines": (None, [vp, i, i, i, i, i, P(ag._lib.Line), P(C.c_int16), P(f)]),
         "hs_analysis_start": (None, [vp, P(C.c_int8), P(ag._lib.PositionInfo), P(C.c_int8), C.c_int64, P(C.c_int16),
                                      P(C.c_int64), C.c_uint64]),
@@ -174,6 +184,14 @@ def pf(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def bits32(x):
+    return np.ascontiguousarray(x, np.float32).view(np.uint32)
+
+
+def bits64(x):
+    return np.ascontiguousarray(x, np.float64).view(np.uint64)
+
+
 class Sim:
     """A hostsim engine plus the helpers the parity tests need."""
 
@@ -184,6 +202,7 @@ class Sim:
         d = (C.c_int32 * 10)()
         self.L.hs_dims(self.h, d)
         (self.N, self.P, self.A, self.AP, self.cap, self.games, self.par, self.mgl, self.tau, self.maxd) = list(d)
+        self.setting = (0, 0.0, 0.0, 0.0)          # the PUCT rule options: off
 
     def close(self):
         if self.h:
@@ -301,6 +320,71 @@ class Sim:
         out = (C.c_int32 * 128)()
         k = self.L.hs_gumbel_schedule(int(n), int(m0), out, 64)
         return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(k)]
+
+    # ---- the PUCT rule options (agz_search_set_puct) and the symmetry mode
+    def set_puct(self, fpu_on=0, r=0.0, r_root=0.0, c_base=0.0):
+        self.L.hs_set_puct(self.h, int(fpu_on), float(r), float(r_root), float(c_base))
+        self.setting = (int(fpu_on), float(r), float(r_root), float(c_base))      # (puct_twin.predict_phase reads it)
+
+    def puct_counts(self):
+        out = (C.c_ulonglong * 2)()
+        self.L.hs_puct_counts(self.h, out)
+        return int(out[0]), int(out[1])
+
+    def set_symmetry(self, mode):
+        """-1 none, 0..7 fixed, 8 random (agz_selfplay_set_symmetry)"""
+        self.L.hs_set_symmetry(self.h, int(mode))
+
+    def step_sym(self, forward):
+        """one self-play step whose leaves are evaluated under their recorded symmetries: forward(feats) -> (pi, v) is the
+        plain network; the features go in under T_s and the policy comes back under its inverse"""
+        def net(feats):
+            B = len(feats)
+            s = np.zeros(B, np.int32)
+            self.L.hs_leaf_syms(self.h, p32(s))
+            x = np.stack([sy.apply_features(feats[k], int(s[k]), self.N) for k in range(B)]).astype(np.float32)
+            pi, v = forward(x)
+            pi = np.stack([sy.apply_policy(pi[k], sy.inverse(int(s[k])), self.N) for k in range(B)]).astype(np.float32)
+            return pi, v
+        return self.step(net)
+
+    def scores(self, node, g=0):
+        out = np.zeros(self.A, np.float64)
+        st, _ = self.op(TOP_SCORES, g=g, node=node, dout=out)
+        assert st == 0
+        return out
+
+    def leaf_paths(self, g=0):
+        """the leaves of the last select phase of slot g: [(leaf, [root .. leaf])]"""
+        nodes = np.zeros(self.par, np.int32)
+        plen = np.zeros(self.par, np.int32)
+        paths = np.zeros((self.par, self.maxd), np.int32)
+        n = self.L.hs_leaf_paths(self.h, g, p32(nodes), p32(plen), p32(paths))
+        return [(int(nodes[k]), [int(x) for x in paths[k, :plen[k]]]) for k in range(n)]
+
+    # ---- root exploration and the move temperature (a setting: explore_twin.setting)
+    def apply(self, st):
+        """the three setters from a setting; an off part is set off"""
+        from explore_twin import schedule_of           # (the twin module imports this one)
+        pt, (total, shaped), mt = st["pt"], st["noise"], st["mt"]
+        off = (0, 1.0, 1.0, 1.0)
+        assert self.L.hs_set_root_policy_temperature(self.h, *(off if pt is None else (1,) + schedule_of(pt, self.N))) == 0
+        assert self.L.hs_set_root_noise(self.h, float(total), 1 if shaped else 0) == 0
+        assert self.L.hs_set_move_temperature(self.h, *(off if mt is None else (1,) + schedule_of(mt, self.N))) == 0
+
+    def explore_counts(self):
+        out = (C.c_ulonglong * 4)()
+        self.L.hs_explore_counts(self.h, out)
+        return tuple(int(x) for x in out)
+
+    def explore_rows(self, node, g=0):
+        t, al, nz = np.zeros(self.A, np.float32), np.zeros(self.A, np.float64), np.zeros(self.A, np.float32)
+        self.L.hs_explore_rows(self.h, g, node, pf(t), al.ctypes.data_as(C.POINTER(C.c_double)), pf(nz))
+        return t, al, nz
+
+    def set_pick_case(self, Nrow, game_id, n, g=0):
+        row = np.ascontiguousarray(Nrow, np.float32)
+        self.L.hs_set_pick_case(self.h, g, pf(row), int(game_id), int(n))
 
     # ---- batched analysis and game review
     def analysis_start(self, positions, games=None, game_id_base=0):
@@ -456,3 +540,30 @@ class Sim:
 
     def Q_(self, g, node):
         return np.float32(self.W_(g, node)) / (np.float32(1) + np.float32(self.N_(g, node)))
+
+
+class PeakedNet:
+    """pi and v from a hash of the features: one board point holds `peak` of the mass, the rest is spread over all
+    actions in four levels (equal priors: unvisited children tie under the FPU, so the tie draw is exercised); v is
+    spread over +-0.9"""
+
+    def __init__(self, N, peak=0.6, salt=0):
+        self.N, self.A, self.peak, self.salt = N, N * N + 1, peak, salt
+        self.calls = 0
+
+    def __call__(self, feats):
+        feats = np.ascontiguousarray(feats, np.float32)
+        B = feats.shape[0]
+        pi = np.zeros((B, self.A), np.float32)
+        v = np.zeros(B, np.float32)
+        for b in range(B):
+            h = zlib.crc32(feats[b].tobytes(), self.salt)
+            rng = np.random.RandomState(h)
+            rest = np.floor(rng.rand(self.A) * 4.0) / 4.0 + 0.05
+            rest[-1] *= 0.25                            # a pass is rarely the network's idea
+            row = (1.0 - self.peak) * rest / rest.sum()
+            row[h % (self.A - 1)] += self.peak
+            pi[b] = row.astype(np.float32)
+            v[b] = np.float32(((h >> 8) % 1801) / 1000.0 - 0.9)
+        self.calls += B
+        return pi, v

@@ -6,34 +6,19 @@ and the exponent bits).  predict_phase walks a tree's rows from the root as one 
 the pass-first rule and the tie draw of select_leaf, virtual losses between the descents) and says which leaves it must
 return.  The oracle's select_leaf is the reference's rule and cannot stand in here.
 
-Also here: the host simulator with the setter -- tests/hostsim/hostsim_puct.cpp, built to a library of its own with the
-flags of the Makefile next to it and bound like hs.lib() -- and the peaked deterministic network the tests search with."""
-import ctypes as C
-import os
-import re
-import shlex
+The simulator it is compared with is hs.Sim (set_puct, puct_counts, scores, leaf_paths); the peaked deterministic network
+the tests search with is hs.PeakedNet."""
 import struct
-import subprocess
-import zlib
 
 import numpy as np
 
-import hs
 from alphago_jl_amd import symmetry as sy
+from hs import bits64
+from selfplay_twin import SITE_PUCT_TIE
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 f32, f64 = np.float32, np.float64
 OFF = (0, 0.0, 0.0, 0.0)
 TWO30 = 1073741824.0
-
-
-def _site(name):
-    hdr = open(os.path.join(ROOT, "include", "agz_draws.h")).read()
-    return int(re.search(r"#define AGZ_SITE_%s (\d+)u" % name, hdr).group(1))
-
-
-SITE_PUCT_TIE = _site("PUCT_TIE")
 
 
 # ---------------------------------------------------------------- agz_log / agz_sqrt, restated
@@ -122,135 +107,6 @@ def puct_scores(N_row, W_row, P_row, N_s, W_s, to_play, is_root, c_puct, setting
         un = N == 0
         out[un] = (f64(f) + (f64(scale) * P.astype(f64)) / f64(f32(1)))[un]
     return out
-
-
-def bits64(x):
-    return np.ascontiguousarray(x, f64).view(np.uint64)
-
-
-# ---------------------------------------------------------------- the simulator with the setter
-
-_lib = None
-
-
-def _sources():
-    c = os.path.join(ROOT, "alphago.jl_amd", "csrc")
-    return [os.path.join(HERE, "hostsim", "hostsim_puct.cpp"), os.path.join(HERE, "hostsim", "hostsim.cpp"),
-            os.path.join(c, "agz_search.h"), os.path.join(c, "agz_state.h"), os.path.join(c, "agz_layout.h"),
-            os.path.join(ROOT, "include", "agz_draws.h"), os.path.join(ROOT, "include", "agz.h")]
-
-
-def lib():
-    """tests/hostsim/libhostsim_puct.so: hostsim.cpp + hs_set_puct / hs_puct_counts, with hs.lib()'s prototypes"""
-    global _lib
-    if _lib is not None:
-        return _lib
-    base = hs.lib()
-    d = os.path.join(HERE, "hostsim")
-    out = os.path.join(d, "libhostsim_puct.so")
-    if not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in _sources()):
-        mk = open(os.path.join(d, "Makefile")).read()
-        cmd = shlex.split(re.search(r"^\t(g\+\+ .*)$", mk, flags=re.M).group(1))
-        cmd = [os.path.join(d, "hostsim_puct.cpp") if t == "$<" else out + ".tmp" if t == "$@" else t for t in cmd]
-        subprocess.run(cmd + ["-Wno-unknown-pragmas"], check=True)
-        os.replace(out + ".tmp", out)
-    L = C.CDLL(out)
-    for name, fn in list(vars(base).items()):
-        if name.startswith("hs_") and hasattr(fn, "argtypes"):
-            g = getattr(L, name)
-            g.restype, g.argtypes = fn.restype, fn.argtypes
-    vp, i, dbl = C.c_void_p, C.c_int, C.c_double
-    P = C.POINTER
-    for name, (res, args) in {"hs_set_puct": (None, [vp, i, dbl, dbl, dbl]),
-                              "hs_puct_counts": (None, [vp, P(C.c_ulonglong)]),
-                              "hs_leaf_paths": (i, [vp, i, P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
-                              "hs_set_symmetry": (None, [vp, i]), "hs_leaf_syms": (None, [vp, P(C.c_int32)])}.items():
-        g = getattr(L, name)
-        g.restype, g.argtypes = res, args
-    _lib = L
-    return L
-
-
-class Sim(hs.Sim):
-    """hs.Sim on the library with the setter"""
-
-    def __init__(self, **cfg):
-        self.L = lib()
-        self.cfg = hs.default_config(**cfg)
-        self.h = self.L.hs_create(C.byref(self.cfg))
-        d = (C.c_int32 * 10)()
-        self.L.hs_dims(self.h, d)
-        (self.N, self.P, self.A, self.AP, self.cap, self.games, self.par, self.mgl, self.tau, self.maxd) = list(d)
-        self.setting = OFF
-
-    def set_puct(self, fpu_on=0, r=0.0, r_root=0.0, c_base=0.0):
-        self.L.hs_set_puct(self.h, int(fpu_on), float(r), float(r_root), float(c_base))
-        self.setting = (int(fpu_on), float(r), float(r_root), float(c_base))
-
-    def puct_counts(self):
-        out = (C.c_ulonglong * 2)()
-        self.L.hs_puct_counts(self.h, out)
-        return int(out[0]), int(out[1])
-
-    def set_symmetry(self, mode):
-        """-1 none, 0..7 fixed, 8 random (agz_selfplay_set_symmetry)"""
-        self.L.hs_set_symmetry(self.h, int(mode))
-
-    def step_sym(self, forward):
-        """one self-play step whose leaves are evaluated under their recorded symmetries: forward(feats) -> (pi, v) is the
-        plain network; the features go in under T_s and the policy comes back under its inverse"""
-        def net(feats):
-            B = len(feats)
-            s = np.zeros(B, np.int32)
-            self.L.hs_leaf_syms(self.h, hs.p32(s))
-            x = np.stack([sy.apply_features(feats[k], int(s[k]), self.N) for k in range(B)]).astype(f32)
-            pi, v = forward(x)
-            pi = np.stack([sy.apply_policy(pi[k], sy.inverse(int(s[k])), self.N) for k in range(B)]).astype(f32)
-            return pi, v
-        return self.step(net)
-
-    def scores(self, node, g=0):
-        out = np.zeros(self.A, f64)
-        st, _ = self.op(hs.TOP_SCORES, g=g, node=node, dout=out)
-        assert st == 0
-        return out
-
-    def leaf_paths(self, g=0):
-        """the leaves of the last select phase of slot g: [(leaf, [root .. leaf])]"""
-        nodes = np.zeros(self.par, np.int32)
-        plen = np.zeros(self.par, np.int32)
-        paths = np.zeros((self.par, self.maxd), np.int32)
-        n = self.L.hs_leaf_paths(self.h, g, hs.p32(nodes), hs.p32(plen), hs.p32(paths))
-        return [(int(nodes[k]), [int(x) for x in paths[k, :plen[k]]]) for k in range(n)]
-
-
-# ---------------------------------------------------------------- a peaked deterministic network
-
-class PeakedNet:
-    """pi and v from a hash of the features: one board point holds `peak` of the mass, the rest is spread over all
-    actions in four levels (equal priors: unvisited children tie under the FPU, so the tie draw is exercised); v is
-    spread over +-0.9"""
-
-    def __init__(self, N, peak=0.6, salt=0):
-        self.N, self.A, self.peak, self.salt = N, N * N + 1, peak, salt
-        self.calls = 0
-
-    def __call__(self, feats):
-        feats = np.ascontiguousarray(feats, f32)
-        B = feats.shape[0]
-        pi = np.zeros((B, self.A), f32)
-        v = np.zeros(B, f32)
-        for b in range(B):
-            h = zlib.crc32(feats[b].tobytes(), self.salt)
-            rng = np.random.RandomState(h)
-            rest = np.floor(rng.rand(self.A) * 4.0) / 4.0 + 0.05
-            rest[-1] *= 0.25                            # a pass is rarely the network's idea
-            row = (1.0 - self.peak) * rest / rest.sum()
-            row[h % (self.A - 1)] += self.peak
-            pi[b] = row.astype(f32)
-            v[b] = f32(((h >> 8) % 1801) / 1000.0 - 0.9)
-        self.calls += B
-        return pi, v
 
 
 # ---------------------------------------------------------------- one select phase, predicted from the rows

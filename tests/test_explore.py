@@ -15,44 +15,14 @@ import alphago_jl_amd as ag
 import explore_twin as ex
 import hs
 import orc
-import puct_twin
 import selfplay_twin as tw
+from explore_twin import COMPOSE, GAME_SETS, GAME_SETTING, SETTINGS, pick_rows, positions, starts_of
 from gpu_options import assert_game_equals_twin
 
 f32 = np.float32
-GAME_SETTING = ex.setting(pt=(1.25, 1.1, None), noise=(10.83, True), mt=(0.75, 0.0, 2.0))
-SETTINGS = {
-    "all": GAME_SETTING,
-    "katago": ex.KATAGO,
-    "temper_only": ex.setting(pt=(0.8, 1.3, 4.0)),
-    "unit_temper": ex.setting(pt=(1.0, 1.0, 7.0)),
-    "unshaped": ex.setting(noise=(3.0, False)),
-    "shaped": ex.setting(noise=(10.83, True)),
-    "off": ex.OFF,
-}
 
 
 # ---------------------------------------------------------------- rows
-
-def ko_position(N):
-    """tw.ko_start(N); on the boards where seeded random play meets no ko early enough, the textbook shape played out"""
-    try:
-        return tw.ko_start(N)
-    except AssertionError:
-        pass
-    b = np.zeros(N * N, np.int8)
-    for (r, c), s in {(0, 1): 1, (1, 0): 1, (2, 1): 1, (1, 1): -1, (0, 2): -1, (2, 2): -1, (1, 3): -1}.items():
-        b[r + N * c] = s
-    rcode, pos = orc.play(orc.make_pos(N, board=b, n=8), 1 + N * 2)
-    assert rcode == orc.OK and pos.ko == 1 + N * 1
-    return pos.copy()
-
-
-def positions(N):
-    cap = tw.random_start(N, (N * N * 6) // 5, 40 + N)
-    assert cap.caps[0] + cap.caps[1] > 0, "the random start has captures"
-    return {"empty": orc.make_pos(N), "ko": ko_position(N), "captures": cap}
-
 
 def root_at(sim, pos, game_id):
     """slot 0 of the simulator as a single tree on oracle position pos, its root expanded -> the root"""
@@ -88,7 +58,7 @@ def test_rows_equal_the_restatement():
     for N in (5, 9, 13, 19):
         A = N * N + 1
         assert {5: 26, 9: 82, 13: 170, 19: 362}[N] == A
-        sim = ex.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, seed=seed)
+        sim = hs.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, seed=seed)
         for pname, pos in positions(N).items():
             root = root_at(sim, pos, game)
             legal = sim.legal(0, root)
@@ -96,7 +66,7 @@ def test_rows_equal_the_restatement():
             if pname != "empty":
                 assert (legal[:A - 1] == 0).any(), "illegal points exist"
             kinds = ex.prior_kinds(A, legal, 7 * N)
-            kinds["net"] = puct_twin.PeakedNet(N)(orc.feats(pos).reshape(1, -1))[0][0]
+            kinds["net"] = hs.PeakedNet(N)(orc.feats(pos).reshape(1, -1))[0][0]
             for kname, P in kinds.items():
                 for sname, st in SETTINGS.items():
                     t, al, nz = check_rows(sim, root, P, legal, pos.n, seed, game, w, st, N, (N, pname, kname, sname))
@@ -123,7 +93,7 @@ def test_off_rows_are_the_stored_noise():
     """with both root rules off TOP_NOISE stores what it stored before: the row the reference's rule gives, and the rows
     read says the same"""
     N, seed, game = 5, 3, 9
-    sim = ex.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, seed=seed)
+    sim = hs.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, seed=seed)
     pos = tw.random_start(N, 9, 1)
     root = root_at(sim, pos, game)
     P = ex.prior_kinds(sim.A, sim.legal(0, root), 1)["random"]
@@ -147,7 +117,7 @@ def test_off_rows_are_the_stored_noise():
 # ---------------------------------------------------------------- schedule
 
 def test_schedule():
-    Lx = ex.lib()
+    Lx = hs.lib()
     for early, late, half in ((1.25, 1.1, 19.0), (0.75, 0.15, 9.0), (0.1, 10.0, 1.0), (3.0, 3.0, 5.0), (0.75, 0.0, 2.0)):
         # T(0) = late + (early - late) * 1.0: early exactly wherever the subtraction is exact (Sterbenz: late / 2 <= early
         # <= 2 late, and late = 0), which covers KataGo's schedules; elsewhere the two roundings leave at most an ulp of
@@ -171,29 +141,11 @@ def test_schedule():
 
 # ---------------------------------------------------------------- picks
 
-def pick_rows(A, seed):
-    rng = np.random.RandomState(seed)
-    one = np.zeros(A, f32)
-    one[A // 3] = 5
-    ties = np.zeros(A, f32)
-    ties[[1, A // 2, A - 2]] = 7
-    ties[2] = 3
-    only_pass = np.zeros(A, f32)
-    only_pass[A - 1] = 4
-    big = np.zeros(A, f32)
-    idx = rng.choice(A, min(A, 12), replace=False)
-    big[idx] = rng.randint(1, 1601, len(idx))
-    big[idx[0]] = 1600
-    dense = rng.randint(0, 40, A).astype(f32)
-    ones = np.ones(A, f32)
-    return {"one": one, "ties": ties, "only_pass": only_pass, "big": big, "dense": dense, "ones": ones}
-
-
 @pytest.mark.parametrize("N", [5, 9])
 def test_picks_equal_the_restatement(N):
     seed, mt = 5, (0.75, 0.0, 2.0)
-    sim = ex.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, seed=seed)
-    off = ex.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, seed=seed)
+    sim = hs.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, seed=seed)
+    off = hs.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, seed=seed)
     for s in (sim, off):
         root_at(s, orc.make_pos(N), 0)
     sim.apply(ex.setting(mt=mt))
@@ -230,19 +182,11 @@ def test_picks_equal_the_restatement(N):
 
 # ---------------------------------------------------------------- games
 
-GAME_SETS = {5: dict(R=24, seed=21, games=8, slots=4), 9: dict(R=32, seed=22, games=8, slots=4)}
-COMPOSE = {"plain": {}, "cap": dict(cap=(8, 0.5)), "forced": dict(forced=(2.0, True)), "starts": dict(starts=True)}
-
-
-def starts_of(N):
-    return tw.random_starts(N, (4, 7, 1), seed=0)
-
-
 def play_set(N, how, st=GAME_SETTING, setting_for_sim="same"):
     c = GAME_SETS[N]
     kw = dict(COMPOSE[how])
     starts = starts_of(N) if kw.pop("starts", False) else None
-    net = puct_twin.PeakedNet(N)
+    net = hs.PeakedNet(N)
     recs, cnt, counts = ex.run_sim(N, net, c["R"], c["seed"], c["games"], c["slots"],
                                    st if setting_for_sim == "same" else setting_for_sim, starts=starts, **kw)
     return recs, cnt, counts, starts, kw
@@ -254,7 +198,7 @@ def test_games_equal_the_twin(N, how):
     c = GAME_SETS[N]
     recs, cnt, counts, starts, kw = play_set(N, how)
     assert len(recs) == c["games"] and cnt["CT_POOL_EXHAUSTED"] == 0
-    cb = ex.FeatsNet(puct_twin.PeakedNet(N), N).cb
+    cb = ex.FeatsNet(hs.PeakedNet(N), N).cb
     twins = []
     for rec in recs:
         gid = int(rec["game_id"])
@@ -312,7 +256,7 @@ def test_refusals_keep_the_setting():
     flight and a pending select phase are states of the engine alone: tests/test_gpu_explore.py.)"""
     N, seed, game = 5, 1, 3
     kept = ex.setting(pt=(1.3, 0.9, 4.0), noise=(5.0, True), mt=(0.8, 0.2, 3.0))
-    sim = ex.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, seed=seed)
+    sim = hs.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, seed=seed)
     pos = tw.random_start(N, 6, 2)
     root = root_at(sim, pos, game)
     legal = sim.legal(0, root)
@@ -340,7 +284,7 @@ def test_refusals_keep_the_setting():
     for fn, args in TAKEN:                            # the bounds themselves are in range
         assert getattr(sim.L, fn)(sim.h, *args) == 0, (fn, args)
     sim.close()
-    arena = ex.Sim(board_size=N, games=2, num_readouts=8, max_nodes_per_game=16, arena_mode=1)
+    arena = hs.Sim(board_size=N, games=2, num_readouts=8, max_nodes_per_game=16, arena_mode=1)
     for fn, args in TAKEN + (("hs_set_root_policy_temperature", (0, 1.0, 1.0, 1.0)), ("hs_set_move_temperature", (0, 1.0, 1.0, 1.0))):
         assert getattr(arena.L, fn)(arena.h, *args) == ag._lib.BAD_ARGUMENT, ("arena", fn, args)
     arena.close()
@@ -360,18 +304,16 @@ def _static_sanitizer_runtimes():
 
 
 def test_sanitizer_build_plays_the_game_set(tmp_path):
-    """hostsim_explore.cpp with the main of explore_sanitize.cpp under -fsanitize=address,undefined, a program of its own
-    with both runtimes linked into it (so it starts in whatever environment the suite runs in, which is left as it is).
+    """hostsim.cpp with the main of explore_sanitize.cpp under -fsanitize=address,undefined (the `sanitize` target of
+    tests/hostsim/Makefile), a program of its own with both runtimes linked into it (so it starts in whatever environment the suite runs in, which is left as it is).
     A check of memory and undefined behaviour, not of results: it plays the boards, readouts, setting, cap, forced
     playouts, a table of three starts and the game counts of the sets above, but on a hash network and walk starts of
     its own, not on PeakedNet and tw.random_starts.  Skipped where g++ or its static sanitizer runtimes are missing."""
     if not _static_sanitizer_runtimes():
         pytest.skip("no g++ with static libasan / libubsan")
-    src = os.path.join(ex.HERE, "hostsim", "explore_sanitize.cpp")
     exe = str(tmp_path / "explore_sanitize")
-    cmd = [t for t in ex.compile_command(src, exe) if t not in ("-shared", "-fPIC", "-O2")]
-    r = subprocess.run(cmd + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
-                              "-static-libubsan"], capture_output=True, text=True)
+    r = subprocess.run(["make", "-s", "-C", os.path.join(hs.HERE, "hostsim"), "sanitize", "SANITIZE_OUT=" + exe],
+                       capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([exe], capture_output=True, text=True)
     print(r.stdout[-2000:])

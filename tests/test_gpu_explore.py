@@ -14,24 +14,15 @@ import explore_twin as ex
 import orc
 import selfplay_twin as tw
 from gpu_common import GpuNetForOracle
-from gpu_options import assert_game_equals_twin, assert_train_equals_twin, host_schedule, play
-from test_explore import COMPOSE, GAME_SETS, GAME_SETTING, SETTINGS, pick_rows, positions, starts_of
-from test_gpu_symmetry import peaked_engine, sharpen
+from explore_twin import COMPOSE, GAME_SETS, GAME_SETTING, SETTINGS, pick_rows, positions, starts_of
+from gpu_options import (api_game, api_positions, apply, assert_game_equals_twin, assert_train_equals_twin, configure,
+                         host_schedule, peaked_engine, play, same_game, sharpen)
 from test_hostsim_selfplay import bits_equal
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 BAD_ARGUMENT, OK = ag._lib.BAD_ARGUMENT, ag._lib.OK
 F_N, F_P = ag._lib.F_CHILD_N, ag._lib.F_CHILD_PRIOR
-
-
-def apply(eng, st):
-    """the three setters from a setting of explore_twin; an off part is set off"""
-    N = eng.N
-    sched = lambda t: None if t is None else ex.schedule_of(t, N)
-    eng.set_root_policy_temperature(sched(st["pt"]))
-    eng.set_root_noise(*st["noise"])
-    eng.set_move_temperature(sched(st["mt"]))
 
 
 def root_of(eng, pos, game_id):
@@ -132,15 +123,7 @@ def device_games(N, how, st, external=False):
         eng = ag.Engine(board_size=N, tower_height=0, external_network=1, **cfg)
     else:
         eng = peaked_engine(N, 1, **cfg)
-    if starts:
-        b, i, h = tw.opos_arrays(starts)
-        eng.set_starts(boards=b, info=i, history=h)
-    if "cap" in kw:
-        eng.set_playout_cap(*kw["cap"])
-    if "forced" in kw:
-        eng.set_forced_playouts(*kw["forced"])
-    if st is not None:
-        apply(eng, st)
+    configure(eng, dict(kw, starts=starts, explore=st))
     recs, stats = play(eng, c["games"], network=fwd.forward_features if external else None)
     counts = eng.explore_counts()
     eng.close()
@@ -184,10 +167,7 @@ def unset_games():
 
 
 def same_records(a, b):
-    return len(a) == len(b) and all(
-        r["game_id"] == o["game_id"] and r["num_moves"] == o["num_moves"] and (r["moves"] == o["moves"]).all()
-        and r["result"] == o["result"] and r["was_resign"] == o["was_resign"] and bits_equal(r["pis"], o["pis"])
-        and bits_equal(r["qs"], o["qs"]) for r, o in zip(a, b))
+    return len(a) == len(b) and all(same_game(r, o) for r, o in zip(a, b))
 
 
 def test_off_is_the_engine_that_never_made_the_calls():
@@ -229,7 +209,6 @@ MT = (0.75, 0.0, 2.0)
 
 
 def test_analyze_equals_the_player_under_the_move_temperature():
-    from test_gpu_analysis import api_positions
     env = ag.GoEnv(9)
     nn = ag.NeuralNet(env, tower_height=1, seed=1)
     sharpen(nn.engine, 9)
@@ -253,7 +232,6 @@ def test_analyze_equals_the_player_under_the_move_temperature():
 
 
 def test_review_equals_the_player_under_the_move_temperature():
-    from test_gpu_review import api_game
     env = ag.GoEnv(9)
     nn = ag.NeuralNet(env, tower_height=1, seed=1)
     sharpen(nn.engine, 9)

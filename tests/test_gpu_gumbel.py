@@ -14,7 +14,7 @@ import orc
 import selfplay_twin as tw
 from alphago_jl_amd import symmetry as sy
 from gpu_common import GpuNetForOracle
-from gpu_options import assert_game_equals_twin, assert_train_equals_twin, host_schedule, play
+from gpu_options import SymNetForOracle, assert_game_equals_twin, assert_train_equals_twin, host_schedule, peaked_engine, play
 from test_hostsim_selfplay import bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -71,7 +71,6 @@ def test_games_equal_the_twin(N, tower, R, m, cap, games, slots, seed, plies):
 
 
 def test_games_with_random_symmetry_equal_the_twin():
-    from test_gpu_symmetry import SymNetForOracle, peaked_engine
     N, tower, R, m, games, seed = 9, 1, 32, 16, 3, 4
     starts = tw.random_starts(N, (6, 11, 2), seed=0)
     eng = peaked_engine(N, tower, games=games, num_readouts=R, seed=seed, record_capacity_games=games + 8,

@@ -13,8 +13,8 @@ import orc
 import selfplay_twin as tw
 from alphago_jl_amd import symmetry as sy
 from gpu_common import GpuNetForOracle, pos_soa
-from gpu_options import (_twin_pairs, arena_pis, assert_game_equals_twin, assert_train_equals_twin, count_targets,
-                         host_schedule)
+from gpu_options import (SymNetForOracle, _twin_pairs, arena_pis, assert_game_equals_twin, assert_train_equals_twin,
+                         count_targets, host_schedule, peaked_engine)
 from gpu_options import play as play_sorted
 from test_hostsim_selfplay import bits_equal
 
@@ -121,7 +121,6 @@ def test_games_with_the_cap_from_a_starts_table_equal_the_twin():
 
 
 def test_games_with_the_cap_and_random_symmetry_equal_the_twin():
-    from test_gpu_symmetry import SymNetForOracle, peaked_engine
     N, tower, R, r, p, games, seed = 9, 1, 16, 4, 0.3, 3, 4
     eng = peaked_engine(N, tower, games=games, num_readouts=R, seed=seed, record_capacity_games=games + 8)
     eng.set_symmetry("random")

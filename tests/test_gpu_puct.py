@@ -1,7 +1,8 @@
 """PUCT rule options on the device (agz_search_set_puct): the scores of searched trees against the
 numpy restatement and whole trees against the host simulator at the four register-row widths of the descent and at the
 two boards (15x15, 17x17: 4 and 5 row elements per lane) that the widest one runs, rounded up;
-self-play games with every other search option against the simulator, counters included; analyze, review and evaluate
+self-play games with every other search option, root exploration and the move temperature among them, against the
+simulator, counters included; analyze, review and evaluate
 under the rule against their single-tree / per-game forms; off is the engine that never made the call; every refusal
 keeps the setting in force.  The simulator runs on the engine's own forward.  Tower 1 everywhere."""
 import functools
@@ -10,11 +11,11 @@ import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
+import explore_twin as ex
 import hs
 import puct_twin as pt
 import selfplay_twin as tw
-from gpu_options import play
-from test_gpu_symmetry import peaked_engine, sharpen
+from gpu_options import RECORD, api_game, api_positions, configure, peaked_engine, play, same_game, sharpen
 from test_hostsim_selfplay import bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -97,7 +98,7 @@ def tree_case(N, readouts, external):
     else:
         eng = ag.Engine(tower_height=1, **cfg)
         eng.init_synthetic(0)
-    sim = pt.Sim(**cfg)
+    sim = hs.Sim(**cfg)
     eng.set_puct(FPU, CB)
     sim.set_puct(*BOTH)
     root = eng.tree_init(0, np.zeros(N * N, np.int8))
@@ -141,22 +142,14 @@ def test_external_network_tree_equals_the_simulator():
 
 GAMES, R, SEED = 4, 16, 3
 CFG = dict(board_size=5, games=GAMES, num_readouts=R, seed=SEED, record_capacity_games=GAMES + 8, c_puct=C_PUCT)
-OPTIONS = {"alone": {}, "playout_cap": dict(cap=(4, 0.5)), "forced_playouts": dict(forced=2.0), "gumbel": dict(gumbel=4),
-           "symmetry": dict(symmetry=True)}
-
-
-def configure(x, opt):
-    if "cap" in opt:
-        x.set_playout_cap(*opt["cap"])
-    if "forced" in opt:
-        x.set_forced_playouts(opt["forced"], True)
-    if "gumbel" in opt:
-        x.set_gumbel(opt["gumbel"], 50.0, 1.0)
-    if "symmetry" in opt:
-        x.set_symmetry("random" if isinstance(x, ag.Engine) else 8)
+EXPLORATION = ex.setting(pt=(1.25, 1.1, 5.0), noise=(10.83, True), mt=(0.75, 0.15, 5.0))
+OPTIONS = {"alone": {}, "playout_cap": dict(cap=(4, 0.5)), "forced_playouts": dict(forced=(2.0, True)), "gumbel": dict(gumbel=4),
+           "symmetry": dict(symmetry=True), "exploration": dict(explore=EXPLORATION)}
+FIELDS = RECORD + ("resign_disabled", "final_score")
 
 
 def device_games(opt, puct, clear=False):
+    """-> (records, the two PUCT counters, the four exploration counters)"""
     eng = peaked_engine(5, 1, **{k: v for k, v in CFG.items() if k != "board_size"})
     configure(eng, opt)
     if puct:
@@ -164,9 +157,9 @@ def device_games(opt, puct, clear=False):
     if clear:
         eng.set_puct(None, 0.0)
     recs, st = play(eng, GAMES)
-    counts = eng.puct_counts()
+    counts = eng.puct_counts(), eng.explore_counts()
     eng.close()
-    return recs, counts
+    return (recs,) + counts
 
 
 @functools.lru_cache(maxsize=None)
@@ -176,7 +169,7 @@ def unset_games():
 
 def sim_games(opt):
     fwd = forward_engine(5, peaked=True)
-    sim = pt.Sim(**CFG)
+    sim = hs.Sim(**CFG)
     configure(sim, opt)
     sim.set_puct(*BOTH)
     sim.start(GAMES)
@@ -187,49 +180,42 @@ def sim_games(opt):
             sim.step(fwd.forward_features)
         if sim.L.hs_records_count(sim.h) >= GAMES:
             break
-    recs, counts = sim.records(), sim.puct_counts()
+    recs, counts = sim.records(), (sim.puct_counts(), sim.explore_counts())
     sim.close()
     fwd.close()
     assert len(recs) == GAMES
-    return recs, counts
-
-
-def same_game(r, o):
-    return (r["game_id"] == o["game_id"] and r["num_moves"] == o["num_moves"] and (r["moves"] == o["moves"]).all()
-            and r["result"] == o["result"] and r["was_resign"] == o["was_resign"]
-            and r["resign_disabled"] == o["resign_disabled"] and f32(r["final_score"]) == f32(o["final_score"])
-            and bits_equal(r["pis"], o["pis"]) and bits_equal(r["qs"], o["qs"]))
+    return (recs,) + counts
 
 
 @pytest.mark.parametrize("option", list(OPTIONS))
 def test_games_equal_the_simulator(option):
     opt = OPTIONS[option]
-    recs, counts = device_games(opt, True)
-    want, wcounts = sim_games(opt)
+    recs, counts, xcounts = device_games(opt, True)
+    want, wcounts, wxcounts = sim_games(opt)
     for r, o in zip(recs, want):
         print(f"{option} game {r['game_id']}: {r['num_moves']} moves, result {r['result']}; simulator {o['num_moves']} / {o['result']}")
-        assert same_game(r, o), (option, r["game_id"])
-    print(f"{option}: counters {counts}, simulator {wcounts}")
+        assert same_game(r, o, FIELDS), (option, r["game_id"])
+    print(f"{option}: counters {counts} {xcounts}, simulator {wcounts} {wxcounts}")
     assert counts == wcounts and counts[0] > 0 and counts[1] > 0
+    assert xcounts == wxcounts and (option != "exploration" or xcounts[2] > 0)
     if option == "alone":
-        unset, c0 = unset_games()
+        unset, c0, _ = unset_games()
         assert c0 == (0, 0)
         assert any(r["num_moves"] != u["num_moves"] or (r["moves"] != u["moves"]).any() for r, u in zip(recs, unset)), \
             "the rule changed no move"
 
 
 def test_set_then_clear_is_the_engine_that_never_set():
-    unset, _ = unset_games()
-    recs, counts = device_games({}, True, clear=True)
+    unset, _, _ = unset_games()
+    recs, counts, _ = device_games({}, True, clear=True)
     assert counts == (0, 0)
     for r, u in zip(recs, unset):
-        assert same_game(r, u), r["game_id"]
+        assert same_game(r, u, FIELDS), r["game_id"]
 
 
 # ---------------------------------------------------------------- d. modes
 
 def test_analyze_equals_the_player_under_the_rule():
-    from test_gpu_analysis import api_positions
     env = ag.GoEnv(5)
     nn = ag.NeuralNet(env, tower_height=1, seed=1)
     sharpen(nn.engine, 5)                      # a peaked policy: the searches go deep enough for the rule to matter
@@ -256,7 +242,6 @@ def test_analyze_equals_the_player_under_the_rule():
 
 
 def test_review_equals_the_player_under_the_rule():
-    from test_gpu_review import api_game
     env = ag.GoEnv(5)
     nn = ag.NeuralNet(env, tower_height=1, seed=1)
     sharpen(nn.engine, 5)
@@ -282,7 +267,7 @@ def test_evaluate_equals_the_simulator_arena_under_the_rule():
     a, b = ag.NeuralNet(env, tower_height=1, seed=0), ag.NeuralNet(env, tower_height=1, seed=5)
     games = 3
     ok, st = ag.evaluate(env, a, b, num_games=games, ro=16, seed=2, return_stats=True, fpu=FPU, c_base=CB, c_puct=C_PUCT)
-    sim = pt.Sim(board_size=5, games=2 * games, num_readouts=16, seed=2, arena_mode=1, record_capacity_games=games + 8,
+    sim = hs.Sim(board_size=5, games=2 * games, num_readouts=16, seed=2, arena_mode=1, record_capacity_games=games + 8,
                  c_puct=C_PUCT)
     sim.set_puct(*BOTH)
     sim.start(games)

@@ -14,40 +14,12 @@ import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
-import orc
 from alphago_jl_amd import symmetry as sy
-from gpu_common import pos_soa
+from gpu_options import SymNetForOracle, peaked_engine, rand_feats, sharpen
 from test_hostsim_arena import oracle_eval_game
 from test_hostsim_selfplay import bits_equal, oracle_game
 
 pytestmark = pytest.mark.gpu
-
-
-def sharpen(engine, N):
-    """scale the policy FC of the selected network by the smallest power of two k that makes pi max > 0.5 on random
-    positions (the synthetic FC bias is zero, so the logits scale by k): with the flat glorot policy a wrong remap
-    would hide in the noise"""
-    w = engine.get_weights(orc.L_POLICY_FC, 0)
-    pi0, _ = engine.forward_features(rand_feats(N, 8, seed=123))
-    logp = np.log(pi0.astype(np.float64))
-    for k in (2.0 ** i for i in range(1, 10)):
-        z = k * logp - (k * logp).max(axis=1, keepdims=True)
-        if (np.exp(z) / np.exp(z).sum(axis=1, keepdims=True)).max(axis=1).min() > 0.5:
-            break
-    engine.set_weights(orc.L_POLICY_FC, 0, (w * k).astype(np.float32))
-
-
-def peaked_engine(N, tower, **kw):
-    e = ag.Engine(board_size=N, tower_height=tower, **kw)
-    e.init_synthetic(0)
-    sharpen(e, N)
-    return e
-
-
-def rand_feats(N, B, seed=0):
-    x = (np.random.RandomState(seed).rand(B, 17 * N * N) < 0.3).astype(np.float32)
-    x[:, 16 * N * N:] = 1.0
-    return x
 
 
 @pytest.mark.parametrize("N,tower", [(9, 2), (19, 1)])
@@ -113,39 +85,6 @@ def test_mode_zero_equals_off():
         eng.close()
     same_records(out[0][0], out[1][0])
     assert out[0][1]["evals"] == out[1][1]["evals"] and out[0][1]["positions"] == out[1][1]["positions"]
-
-
-class SymNetForOracle:
-    """an or_net_fn for ONE game (or one arena player): evaluation e of the game is made under T_s with s predicted by
-    the mirror of the draw key (or fixed): features of the oracle's positions, host transform, the plain GPU forward,
-    host un-permute"""
-
-    def __init__(self, engine, seed, game_id, mode, plain_first=0):
-        self.engine, self.seed, self.game_id, self.mode = engine, seed, game_id, mode
-        self.plain_first = plain_first      # evaluations made before the mode was switched on: T_0
-        self.e = 0
-        self.syms = []
-        N = engine.N
-
-        def _fn(ctx, positions, B, pi, v):
-            plist = [positions[b].contents for b in range(B)]
-            feats = engine.features(*pos_soa(plist))
-            sym = []
-            for _ in range(B):
-                if self.e < self.plain_first:
-                    sym.append(0)
-                else:
-                    sym.append(self.mode if self.mode != sy.RANDOM else sy.draw_symmetry(self.seed, self.game_id, self.e))
-                self.e += 1
-            self.syms += sym
-            tx = np.stack([sy.apply_features(feats[b], sym[b], N) for b in range(B)])
-            gpi, gv = engine.forward_features(tx)
-            gpi = np.ascontiguousarray(np.stack([sy.apply_policy(gpi[b], sy.inverse(sym[b]), N) for b in range(B)]),
-                                       np.float32)
-            C.memmove(pi, gpi.ctypes.data, 4 * B * engine.A)
-            C.memmove(v, np.ascontiguousarray(gv, np.float32).ctypes.data, 4 * B)
-
-        self.cb = orc.NET_FN(_fn)
 
 
 @pytest.mark.parametrize("N,tower,readouts,games,mode", [

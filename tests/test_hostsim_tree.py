@@ -280,3 +280,20 @@ def test_pool_exhaustion_is_flagged():
     assert st == 8   # AGZ_POOL_EXHAUSTED
     assert t.counters()["pool_exhausted"] >= 1
     t.close()
+
+
+def test_hs_bindings_are_the_library():
+    """every export of hostsim.cpp has its prototype in hs.sig and the table names nothing else (the names are read from
+    the source's extern "C" block, as hs.counter_names() reads the enum); and the search options share the one library"""
+    import glob
+    import os
+    import re
+    hs.lib()
+    d = os.path.join(hs.HERE, "hostsim")
+    src = open(os.path.join(d, "hostsim.cpp")).read()
+    body = re.search(r'extern "C" \{(.*)\}  // extern "C"', src, flags=re.S).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    names = re.findall(r"^[A-Za-z_][\w:\* ]*?\b(hs_\w+)\(", body, flags=re.M)
+    assert len(names) == len(set(names)) > 50
+    assert sorted(names) == sorted(hs.sig)
+    assert [os.path.basename(p) for p in glob.glob(os.path.join(d, "*.so"))] == ["libhostsim.so"]

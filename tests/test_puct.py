@@ -64,7 +64,7 @@ def hand_node(sim, is_root, tp, N, W, P, N_s, W_s):
 def test_scores_equal_the_restatement(N):
     A = N * N + 1
     assert {5: 26, 9: 82, 19: 362}[N] == A
-    sim = pt.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, c_puct=C_PUCT)
+    sim = hs.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=16, c_puct=C_PUCT)
     checked = 0
     for ci, kind in enumerate(("none", "all", "mixed", "tiny", "negzero")):
         for is_root in (True, False):
@@ -117,9 +117,9 @@ def test_log_and_sqrt_restated():
 # ---------------------------------------------------------------- 2. descents, predicted then checked
 
 def searched_tree(par, setting, noise, readouts=200, seed=7, game_id=5):
-    sim = pt.Sim(board_size=5, games=1, num_readouts=readouts, parallel_readouts=8, seed=seed, max_nodes_per_game=1024,
+    sim = hs.Sim(board_size=5, games=1, num_readouts=readouts, parallel_readouts=8, seed=seed, max_nodes_per_game=1024,
                  c_puct=C_PUCT)
-    net = pt.PeakedNet(5)
+    net = hs.PeakedNet(5)
     root = sim.tree_init(0, np.zeros(sim.P, np.int8))
     sim.L.hs_game_set(sim.h, 0, 0, float(game_id))
     sim.set_puct(*setting)
@@ -173,8 +173,8 @@ def test_the_rule_changes_the_tree():
 # ---------------------------------------------------------------- 3 / 4. self-play
 
 def selfplay(setting=None, clear=False, games=3, R=16, seed=3, configure=None):
-    sim = pt.Sim(board_size=5, games=games, num_readouts=R, seed=seed, c_puct=C_PUCT, record_capacity_games=games + 4)
-    net = pt.PeakedNet(5)
+    sim = hs.Sim(board_size=5, games=games, num_readouts=R, seed=seed, c_puct=C_PUCT, record_capacity_games=games + 4)
+    net = hs.PeakedNet(5)
     if configure:
         configure(sim)
     if setting is not None:

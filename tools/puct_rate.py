@@ -16,18 +16,19 @@ shape, on rate_windows.py's alternating windows of one box.
 Prints one JSON object."""
 import json
 import os
-import subprocess
 import sys
+
+import rate_windows as rw
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SETTING = (1, 0.2, 0.0, 19652.0)
+KEYS = ("ms_per_step", "steps_per_s", "moves_per_s", "evals_per_move", "search_kernels_ms_per_step")
 
 
 def child(args):
     """one tree's windows, in this process: the modes this tree's library knows"""
     tree = os.path.abspath(args.tree)
     sys.path[:0] = [tree, os.path.join(tree, "tools")]
-    import rate_windows as rw
     modes = tuple(args.modes.split(","))
 
     def configure(eng, mode):
@@ -47,18 +48,6 @@ def child(args):
                             (lambda e: e.puct_counts()) if "on" in modes else None)
     eng.close()
     print("PUCT_RATE_CHILD " + json.dumps(windows))
-
-
-def run_child(args, tree, modes):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--tree", tree, "--modes", modes, "--pairs", "1"]
-    for k in ("board", "tower", "readouts", "games", "stagger", "steps", "warmup"):
-        cmd += ["--" + k, str(getattr(args, k))]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.child_timeout)
-    if r.returncode != 0:
-        raise RuntimeError(f"child on {tree} failed ({r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
-    line = [x for x in r.stdout.splitlines() if x.startswith("PUCT_RATE_CHILD ")][-1]
-    print(f"windows of {tree} ({modes}) done", file=sys.stderr, flush=True)
-    return json.loads(line[len("PUCT_RATE_CHILD "):])
 
 
 def data_part(args):
@@ -89,48 +78,30 @@ def data_part(args):
     return out
 
 
-def main():
-    sys.path[:0] = [os.path.dirname(HERE), HERE]
-    import rate_windows as rw
-    ap = rw.parser()
-    ap.add_argument("--child", action="store_true", help="(internal) time one tree's windows and print them")
-    ap.add_argument("--tree", default=os.path.dirname(HERE))
-    ap.add_argument("--modes", default="off,on")
-    ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit; none: no parent part")
-    ap.add_argument("--child-timeout", type=int, default=900)
-    ap.add_argument("--data-tower", type=int, default=2)
-    ap.add_argument("--data-readouts", type=int, default=100)
-    ap.add_argument("--data-games", type=int, default=256)
-    ap.add_argument("--no-data", action="store_true")
-    args = ap.parse_args()
-    if args.child:
-        return child(args)
-    this = os.path.dirname(HERE)
-    windows = dict(parent_off=[], off=[], on=[])
-    for k in range(args.pairs):
-        order = ["parent", "this"] if k % 2 == 0 else ["this", "parent"]
-        for which in order:
-            if which == "parent":
-                if args.parent_tree:
-                    windows["parent_off"] += run_child(args, args.parent_tree, "off")["off"]
-            else:
-                w = run_child(args, this, "off,on" if k % 2 == 0 else "on,off")
-                windows["off"] += w["off"]
-                windows["on"] += w["on"]
-    keys = ("ms_per_step", "steps_per_s", "moves_per_s", "evals_per_move", "search_kernels_ms_per_step")
-    res = rw.summary({m: w for m, w in windows.items() if w}, keys)
+def measure(windows):
+    """-> (the summary of the windows, on against off and off against the parent)"""
+    res = rw.summary({m: w for m, w in windows.items() if w}, KEYS)
     measured = dict(on_minus_off_ms_per_step=rw.on_minus_off(res, "ms_per_step"),
                     on_minus_off_search_kernels_ms=rw.on_minus_off(res, "search_kernels_ms_per_step"),
                     on_over_off_moves_per_s=round(res["on"]["moves_per_s"]["median"]
                                                   / max(res["off"]["moves_per_s"]["median"], 1e-9), 4),
                     off_spread_ms_per_step=res["off"]["ms_per_step"]["spread"])
-    if windows["parent_off"]:
-        d = round(res["off"]["ms_per_step"]["median"] - res["parent_off"]["ms_per_step"]["median"], 4)
-        ds = round(res["off"]["search_kernels_ms_per_step"]["median"]
-                   - res["parent_off"]["search_kernels_ms_per_step"]["median"], 4)
-        measured.update(off_minus_parent_ms_per_step=d, off_minus_parent_search_kernels_ms=ds,
-                        parent_spread_ms_per_step=res["parent_off"]["ms_per_step"]["spread"],
-                        off_within_parent_spread=bool(abs(d) <= res["parent_off"]["ms_per_step"]["spread"]))
+    if windows["parent_off"]:              # the bar is ms per step; the search kernels are a figure beside it
+        measured.update(rw.off_against_parent(res, dict(ms_per_step=("ms_per_step", 4))))
+        measured.update(off_minus_parent_search_kernels_ms=round(
+            res["off"]["search_kernels_ms_per_step"]["median"] - res["parent_off"]["search_kernels_ms_per_step"]["median"], 4))
+    return res, measured
+
+
+def main():
+    sys.path[:0] = [os.path.dirname(HERE), HERE]
+    ap = rw.parser()
+    rw.parent_args(ap)
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+    windows = rw.window_rounds(__file__, "PUCT_RATE_CHILD", args)
+    res, measured = measure(windows)
     print(json.dumps(dict(
         shape=dict(board=args.board, tower=args.tower, readouts=args.readouts, games=args.games, stagger=args.stagger),
         setting=dict(fpu_on=SETTING[0], r=SETTING[1], r_root=SETTING[2], c_base=SETTING[3]),

@@ -2,10 +2,16 @@
 starts_rate.py): one engine at the BASELINE.json configs[1] shape, and the modes of an option timed in alternating
 windows of the same process on the same box.  An option changes between runs only, so every window is a run of its
 own: the slots of the previous window are given up (agz_slot_abandon), the mode is set on a run without a step yet,
-the run is started, stepped through its prelude and a warm-up, and then K steps are timed, ending in a synchronise."""
+the run is started, stepped through its prelude and a warm-up, and then K steps are timed, ending in a synchronise.
+
+And what the tools that also measure against the parent commit share (puct_rate.py, explore_rate.py, surprise_rate.py):
+two libraries cannot share a process, so every round runs one child process per tree, in an order that reverses every
+round, and "off" on this tree is held against the spread of the parent's own windows."""
 import argparse
+import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -104,3 +110,72 @@ def measured(res):
                 search_kernels_on_minus_off=on_minus_off(res, "search_kernels_ms_per_step"),
                 off_spread_ms_per_step=res["off"]["ms_per_step"]["spread"],
                 off_spread_search_kernels=res["off"]["search_kernels_ms_per_step"]["spread"])
+
+
+# ---------------------------------------------------------------- this tree against a built checkout of the parent
+
+def parent_args(ap, child_timeout=900, data=True):
+    """the arguments of a tool with a parent part (data: and of a data part at a small shape)"""
+    ap.add_argument("--child", action="store_true", help="(internal) time one tree's windows and print them")
+    ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--modes", default="off,on")
+    ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit; none: no parent part")
+    ap.add_argument("--child-timeout", type=int, default=child_timeout)
+    if data:
+        ap.add_argument("--data-tower", type=int, default=2)
+        ap.add_argument("--data-readouts", type=int, default=100)
+        ap.add_argument("--data-games", type=int, default=256)
+        ap.add_argument("--no-data", action="store_true")
+
+
+def child_argv(args, names):
+    """the arguments `names` of this process, as a child's command line"""
+    return [x for k in names for x in ("--" + k.replace("_", "-"), str(getattr(args, k)))]
+
+
+def run_child(script, tag, tree, argv, timeout):
+    """`script --child --tree tree argv` in a process of its own -> what it printed as JSON behind `tag`; argv begins
+    with the modes of the child (--modes M), which name it in the progress line and in a failure"""
+    cmd = [sys.executable, os.path.abspath(script), "--child", "--tree", tree] + list(argv)
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+    if r.returncode != 0:
+        raise RuntimeError(f"child on {tree} ({argv[1]}) failed ({r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+    line = [x for x in r.stdout.splitlines() if x.startswith(tag + " ")][-1]
+    print(f"windows of {tree} ({argv[1]}) done", file=sys.stderr, flush=True)
+    return json.loads(line[len(tag) + 1:])
+
+
+def parent_rounds(pairs, parent_tree, run_parent, run_this):
+    """`pairs` rounds of run_parent(parent_tree) -> the parent's off windows and run_this(k) -> {off, on} windows of this
+    tree, the parent first in the even rounds and last in the odd ones; without a parent tree only this tree runs
+    -> {parent_off, off, on}"""
+    windows = dict(parent_off=[], off=[], on=[])
+    for k in range(pairs):
+        for which in (("parent", "this") if k % 2 == 0 else ("this", "parent")):
+            if which == "this":
+                w = run_this(k)
+                windows["off"] += w["off"]
+                windows["on"] += w["on"]
+            elif parent_tree:
+                windows["parent_off"] += run_parent(parent_tree)
+    return windows
+
+
+def window_rounds(script, tag, args):
+    """parent_rounds of a tool whose child times windows_of(): off on the parent; off and on, then on and off, on this"""
+    def run(tree, modes):
+        argv = ["--modes", modes, "--pairs", "1"] + child_argv(args, ("board", "tower", "readouts", "games", "stagger", "steps", "warmup"))
+        return run_child(script, tag, tree, argv, args.child_timeout)
+    this = os.path.dirname(os.path.dirname(os.path.abspath(script)))
+    return parent_rounds(args.pairs, args.parent_tree, lambda tree: run(tree, "off")["off"],
+                         lambda k: run(this, "off,on" if k % 2 == 0 else "on,off"))
+
+
+def off_against_parent(res, keys):
+    """keys = {name: (column, digits)}: off minus parent of the medians of every column, rounded to its digits, the
+    parent's own spread beside it, and whether every difference lies inside that spread"""
+    d = {k: round(res["off"][col]["median"] - res["parent_off"][col]["median"], nd) for k, (col, nd) in keys.items()}
+    out = {"off_minus_parent_" + k: v for k, v in d.items()}
+    out.update({"parent_spread_" + k: res["parent_off"][col]["spread"] for k, (col, _) in keys.items()})
+    out["off_within_parent_spread"] = all(abs(d[k]) <= res["parent_off"][col]["spread"] for k, (col, _) in keys.items())
+    return out

@@ -17,9 +17,10 @@ Writes one JSON object to --out (default profiles/surprise_rate.json) and prints
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
+
+import rate_windows as rw
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 RHO = 0.5
@@ -30,7 +31,7 @@ def child(args):
     sys.path[:0] = [tree]
     import alphago_jl_amd as ag
     env = ag.GoEnv(args.board)
-    kw = dict(surprise=RHO) if args.mode == "on" else {}
+    kw = dict(surprise=RHO) if args.modes == "on" else {}
     windows = []
     for w in range(args.warm + args.windows):
         prof = {}
@@ -45,15 +46,9 @@ def child(args):
 
 
 def run_child(args, tree, mode):
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", "--tree", tree, "--mode", mode]
-    for k in ("board", "tower", "readouts", "train_games", "memory", "batch", "start_after", "slots", "windows", "warm"):
-        cmd += ["--" + k.replace("_", "-"), str(getattr(args, k))]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.child_timeout)
-    if r.returncode != 0:
-        raise RuntimeError(f"child on {tree} ({mode}) failed ({r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
-    line = [x for x in r.stdout.splitlines() if x.startswith("SURPRISE_RATE_CHILD ")][-1]
-    print(f"windows of {tree} ({mode}) done", file=sys.stderr, flush=True)
-    return json.loads(line[len("SURPRISE_RATE_CHILD "):])
+    argv = ["--modes", mode] + rw.child_argv(args, ("board", "tower", "readouts", "train_games", "memory", "batch",
+                                                     "start_after", "slots", "windows", "warm"))
+    return rw.run_child(__file__, "SURPRISE_RATE_CHILD", tree, argv, args.child_timeout)
 
 
 def summary(ws, key):
@@ -63,28 +58,25 @@ def summary(ws, key):
                 spread=round(float(v.max() - v.min()), 4), windows=len(v))
 
 
-def train_part(args):
-    this = os.path.dirname(HERE)
-    windows = dict(parent_off=[], off=[], on=[])
-    for k in range(args.pairs):
-        order = [("parent", "off"), ("this", "off"), ("this", "on")]
-        for which, mode in (order if k % 2 == 0 else order[::-1]):
-            if which == "parent":
-                if args.parent_tree:
-                    windows["parent_off"] += run_child(args, args.parent_tree, "off")
-            else:
-                windows[mode] += run_child(args, this, mode)
+def measure(windows):
+    """-> (the summary of the windows, on against off and off against the parent)"""
     res = {m: {key: summary(w, key) for key in ("ms_per_iteration", "train_ms_per_iteration")} for m, w in windows.items() if w}
     measured = dict(on_minus_off_ms_per_iteration=round(res["on"]["ms_per_iteration"]["median"]
                                                         - res["off"]["ms_per_iteration"]["median"], 4),
                     off_spread_ms_per_iteration=res["off"]["ms_per_iteration"]["spread"])
     if windows["parent_off"]:
-        d = round(res["off"]["ms_per_iteration"]["median"] - res["parent_off"]["ms_per_iteration"]["median"], 4)
-        measured.update(off_minus_parent_ms_per_iteration=d,
-                        parent_spread_ms_per_iteration=res["parent_off"]["ms_per_iteration"]["spread"],
-                        off_within_parent_spread=bool(abs(d) <= res["parent_off"]["ms_per_iteration"]["spread"]))
+        measured.update(rw.off_against_parent(res, dict(ms_per_iteration=("ms_per_iteration", 4))))
     else:
         measured.update(parent="not measured (no --parent-tree)")
+    return res, measured
+
+
+def train_part(args):
+    this = os.path.dirname(HERE)
+    windows = rw.parent_rounds(          # (parent off, off, on) children, backwards in the odd rounds
+        args.pairs, args.parent_tree, lambda tree: run_child(args, tree, "off"),
+        lambda k: {m: run_child(args, this, m) for m in (("off", "on") if k % 2 == 0 else ("on", "off"))})
+    res, measured = measure(windows)
     return dict(shape=dict(board=args.board, tower=args.tower, readouts=args.readouts, games=args.train_games,
                            slots=args.slots, memory=args.memory, batch=args.batch, start_after=args.start_after),
                 windows=windows, summary=res, measured=measured)
@@ -166,11 +158,7 @@ def arena_part(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--child", action="store_true", help="(internal) time one tree's train() windows and print them")
-    ap.add_argument("--tree", default=os.path.dirname(HERE))
-    ap.add_argument("--mode", default="off")
-    ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit; none: no parent part")
-    ap.add_argument("--child-timeout", type=int, default=600)
+    rw.parent_args(ap, child_timeout=600, data=False)      # (a child here runs one mode: --modes off, or on)
     ap.add_argument("--board", type=int, default=9)
     ap.add_argument("--tower", type=int, default=2)
     ap.add_argument("--readouts", type=int, default=32)
