@@ -285,22 +285,22 @@ agz_status agz_replay_ingest_gathered(agz_engine* e, const void* buf, int32_t is
     if (added_out) *added_out = n;
   });
 }
-int64_t agz_replay_count(agz_engine* e) { return (e && e->impl) ? e->impl->replay_count() : -1; }
+int64_t agz_replay_count(agz_engine* e) { return (e && e->impl) ? e->impl->replay().count() : -1; }
 int64_t agz_selfplay_starts_count(agz_engine* e) { return (e && e->impl) ? e->impl->starts_count() : -1; }
-int64_t agz_replay_positions(agz_engine* e) { return (e && e->impl) ? e->impl->replay_positions() : -1; }
+int64_t agz_replay_positions(agz_engine* e) { return (e && e->impl) ? e->impl->replay().positions() : -1; }
 agz_status agz_replay_header(agz_engine* e, int64_t k, agz_game_header* out) {
   return guard(e, [&](agz::Engine& E) {
     AGZ_REQUIRE(out != nullptr, AGZ_BAD_ARGUMENT, "null pointer");
-    E.replay_header(k, out);
+    E.replay().header(k, out);
   });
 }
 agz_status agz_replay_game(agz_engine* e, int64_t k, int16_t* moves, float* pis, float* qs) {
-  return guard(e, [&](agz::Engine& E) { E.replay_game(k, moves, pis, qs); });
+  return guard(e, [&](agz::Engine& E) { E.replay().game(k, moves, pis, qs); });
 }
 agz_status agz_replay_trim(agz_engine* e, int64_t max_positions) {
-  return guard(e, [&](agz::Engine& E) { E.replay_trim(max_positions); });
+  return guard(e, [&](agz::Engine& E) { E.replay().trim(max_positions); });
 }
-agz_status agz_replay_clear(agz_engine* e) { return guard(e, [&](agz::Engine& E) { E.replay_clear(); }); }
+agz_status agz_replay_clear(agz_engine* e) { return guard(e, [&](agz::Engine& E) { E.replay().clear(); }); }
 agz_status agz_replay_batch(agz_engine* e, const int64_t* game, const int32_t* ply, int32_t B, float* feats,
                             float* pi, float* z, int32_t out_is_device) {
   return guard(e, [&](agz::Engine& E) { E.replay_batch(game, ply, B, feats, pi, z, out_is_device != 0); });
@@ -313,12 +313,12 @@ agz_status agz_replay_ingest_records(agz_engine* e, int64_t first, int64_t count
   });
 }
 agz_status agz_replay_set_window(agz_engine* e, int64_t max_entries) {
-  return guard(e, [&](agz::Engine& E) { E.replay_set_window(max_entries); });
+  return guard(e, [&](agz::Engine& E) { E.replay().set_window(max_entries); });
 }
-int64_t agz_replay_live_positions(agz_engine* e) { return (e && e->impl) ? e->impl->replay_live_positions() : -1; }
+int64_t agz_replay_live_positions(agz_engine* e) { return (e && e->impl) ? e->impl->replay().live_positions() : -1; }
 agz_status agz_replay_sample(agz_engine* e, int32_t B, uint64_t call, int32_t sym_mode, float* feats, float* pi, float* z,
                              int64_t* game_out, int32_t* ply_out) {
-  return guard(e, [&](agz::Engine& E) { E.replay_sample(B, call, sym_mode, feats, pi, z, game_out, ply_out); });
+  return guard(e, [&](agz::Engine& E) { E.replay().sample(B, call, sym_mode, feats, pi, z, game_out, ply_out); });
 }
 agz_status agz_selfplay_set_hold(agz_engine* e, int32_t on) {
   return guard(e, [&](agz::Engine& E) { E.set_hold(on != 0); });
@@ -398,10 +398,10 @@ agz_status agz_explore_temperature(int32_t n, double early, double late, double 
   return AGZ_OK;
 }
 agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on) {
-  return guard(e, [&](agz::Engine& E) { E.replay_set_targets_only(on != 0); });
+  return guard(e, [&](agz::Engine& E) { E.replay().set_targets_only(on != 0); });
 }
 agz_status agz_replay_set_value_target(agz_engine* e, double alpha, double lambda) {
-  return guard(e, [&](agz::Engine& E) { E.replay_set_value_target(alpha, lambda); });
+  return guard(e, [&](agz::Engine& E) { E.replay().set_value_target(alpha, lambda); });
 }
 // ---- policy surprise weighting (include/agz_surprise.h)
 agz_status agz_replay_score(agz_engine* e, int64_t first, int64_t count, int64_t* rows_out) {
@@ -411,10 +411,10 @@ agz_status agz_replay_score(agz_engine* e, int64_t first, int64_t count, int64_t
   });
 }
 agz_status agz_replay_set_surprise(agz_engine* e, double rho) {
-  return guard(e, [&](agz::Engine& E) { E.replay_set_surprise(rho); });
+  return guard(e, [&](agz::Engine& E) { E.replay().set_surprise(rho); });
 }
 agz_status agz_replay_surprise(agz_engine* e, int64_t k, double* kl_out, uint32_t* q_out, int32_t* scored_out) {
-  return guard(e, [&](agz::Engine& E) { E.replay_surprise(k, kl_out, q_out, scored_out); });
+  return guard(e, [&](agz::Engine& E) { E.replay().surprise(k, kl_out, q_out, scored_out); });
 }
 // engine-free: the host loops over include/agz_surprise.h for one game the caller holds
 agz_status agz_surprise_weights(const float* pis, const float* ps, int32_t T, int32_t A, double rho, double* kl_out,

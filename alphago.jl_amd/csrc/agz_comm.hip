@@ -207,7 +207,7 @@ int64_t comm_allgather_records(Engine& E, Comm* c) {
     cnrec[r] = counts[2 * r];
     cbytes[r] = counts[2 * r + 1];
   }
-  return E.replay_ingest_chunks(c->d_recv.p, coff, cbytes, cnrec);
+  return E.replay().ingest_chunks(c->d_recv.p, coff, cbytes, cnrec);
 }
 
 // rank `root`'s parameters overwrite every other rank's replica: ONE ncclBroadcast of the network's device master

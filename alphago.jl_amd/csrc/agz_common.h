@@ -68,6 +68,17 @@ struct DevBuf {
   }
 };
 
+// `b` becomes a buffer of `cap` elements that keeps [from, from + keep) of the old one at its front: copied on `s`,
+// waited for, then swapped in (the old buffer is freed)
+template <class T>
+void regrow(DevBuf<T>& b, size_t cap, size_t from, size_t keep, hipStream_t s) {
+  DevBuf<T> nb;
+  nb.alloc(cap);
+  if (keep) AGZ_HIP(hipMemcpyAsync(nb.p, b.p + from, sizeof(T) * keep, hipMemcpyDeviceToDevice, s));
+  AGZ_HIP(hipStreamSynchronize(s));
+  nb.swap(b);
+}
+
 // ---- host <-> device staging, written once.  Every copy is asynchronous on the caller's stream and counts ELEMENTS of
 // T: the byte count comes from the type, and host and device pointers must agree on it.  The rules the callers keep:
 //  * a copy from or into host memory that the caller owns on its stack or in a vector is followed by a

@@ -7,6 +7,7 @@
 #include "agz_common.h"
 #include "agz_layout.h"
 #include "agz_nn.h"
+#include "agz_replay.h"
 #include "agz_state.h"
 
 namespace agz {
@@ -92,39 +93,18 @@ class Engine {
   // the value targets y_t of ring record k under (alpha, lambda) (agz_records_value_targets, include/agz_value_target.h)
   void record_value_targets(int64_t k, double alpha, double lambda, float* out);
 
-  // device replay arena: finished games of every rank, packed, resident in HBM
+  // device replay arena (agz_replay.h): what is the arena's alone is called on replay(); here is what joins it to the
+  // record ring (the ingest entry points stage a host buffer or pack the ring, then file the bytes), to the network
+  // (agz_replay_score: one KL(pi || p) per ply of arena games [first, first + count) on the selected network) and to the
+  // engine's staging buffers (replay_batch)
+  ReplayArena& replay() { return *replay_; }
   int64_t replay_ingest(const void* packed, int64_t nbytes, bool is_device);
   int64_t replay_ingest_local();
   // records [first, first + count) of this engine's ring into the arena, device to device (agz_replay_ingest_records)
   int64_t replay_ingest_records(int64_t first, int64_t count);
   int64_t replay_ingest_gathered(const void* buf, bool is_device, size_t nbytes, const std::vector<int64_t>& coff,
                                  const std::vector<int64_t>& cbytes, const std::vector<int64_t>& cnrec);
-  int64_t replay_ingest_chunks(const uint8_t* dbuf, const std::vector<int64_t>& coff,
-                               const std::vector<int64_t>& cbytes, const std::vector<int64_t>& cnrec);
-  int64_t replay_count() const { return (int64_t)rp_hdr_.size(); }
-  int64_t replay_positions() const { return rp_positions_; }
-  int64_t replay_bytes() const { return (int64_t)rp_used_; }
-  void replay_header(int64_t k, agz_game_header* out) const;
-  void replay_game(int64_t k, int16_t* moves, float* pis, float* qs);
-  void replay_trim(int64_t max_positions);
-  void replay_clear();
-  // the sampling window of train(): the newest max_entries entries stay live (agz_replay_set_window)
-  void replay_set_window(int64_t max_entries);
-  int64_t replay_live_positions() const {
-    return rp_entry_cum().back() - rp_entry_cum()[(size_t)rp_first_game_] - rp_first_ply_;
-  }
-  // targets-only arena (agz_replay_set_targets_only): an entry is a ply whose pi row is not all zero
-  void replay_set_targets_only(bool on);
-  // the z of the batch calls is y_t under (alpha, lambda) (agz_replay_set_value_target); alpha = 0 (the default) is off
-  void replay_set_value_target(double alpha, double lambda);
-  // policy surprise weighting (agz_replay_score / _set_surprise / _surprise, include/agz_surprise.h): one KL(pi || p)
-  // per ply of arena games [first, first + count) on the selected network; rho = 0 (the default) is off
   int64_t replay_score(int64_t first, int64_t count);
-  void replay_set_surprise(double rho);
-  void replay_surprise(int64_t k, double* kl_out, uint32_t* q_out, int32_t* scored_out);
-  // get_replay_batch without the host: B distinct live entries drawn on the device (agz_replay_sample)
-  void replay_sample(int B, uint64_t call, int sym_mode, float* feats, float* pi, float* z, int64_t* game_out,
-                     int32_t* ply_out);
   // sym != NULL: sample b under the board symmetry T_sym[b] (agz_replay_batch_sym)
   void replay_batch(const int64_t* game, const int32_t* ply, int B, float* feats, float* pi, float* z,
                     bool out_is_device, const int32_t* sym = nullptr);
@@ -190,12 +170,6 @@ class Engine {
   std::string last_error;
 
  private:
-  void replay_reserve(size_t bytes);
-  void replay_drop_front(size_t drop);
-  void replay_scan_targets(size_t first_new);
-  void replay_index_to_device();
-  // the prefix the window and the sampler count entries by: every ply, or target plies only
-  const std::vector<int64_t>& rp_entry_cum() const { return rp_targets_only_ ? rp_tcum_ : rp_cum_; }
   void upload_view_outputs();
   void fill_synthetic_inputs(int B);
   void check_game(int g) const;
@@ -225,8 +199,6 @@ class Engine {
   void forward_staged(int B, const int32_t* d_sym, float* pi_out, float* v_out);
   template <class Launch>
   float time_launches(int iters, Launch launch);
-  void emit_replay_batch(int B, const int64_t* off, const int32_t* ply, const int32_t* sym, int8_t* boards, float* feats,
-                         float* pi, float* z);
   size_t packed_layout(int64_t first, int64_t last, std::vector<int64_t>& off);
 
   agz_config cfg_;
@@ -289,50 +261,8 @@ class Engine {
   DevBuf<uint64_t> an_gid_;
   DevBuf<float> an_pi_;
   DevBuf<unsigned long long> ra_counts_;
-  // replay arena
-  DevBuf<uint8_t> rp_buf_, s_pack_;
-  size_t rp_used_ = 0;
-  int64_t rp_positions_ = 0;
-  std::vector<int64_t> rp_off_;
-  std::vector<agz_game_header> rp_hdr_;
-  std::vector<int64_t> rp_cum_{0};  // [count + 1]: positions of the games before game k
-  int64_t rp_first_game_ = 0;       // the window (agz_replay_set_window): entries before ply rp_first_ply_ of game
-  int64_t rp_first_ply_ = 0;        // rp_first_game_ are dead
-  DevBuf<int64_t> d_rp_cum_, d_rp_off_;   // device copies of rp_cum_ / rp_off_ for the sampler
-  int64_t rp_dev_n_ = 0;            // games whose rp_cum_ / rp_off_ entries are on the device
-  uint64_t rp_change_ = 0;          // bumped by every ingest, trim, clear, window and targets-only call (reanalysis commit)
-  // targets-only mode: rp_tcum_[k] = target plies of the games before game k (next to rp_cum_; the window's
-  // rp_first_ply_ is then an index into rp_first_game_'s target list); d_rp_tply_[rp_cum_[k] + i] = the i-th target ply
-  // of game k, written by k_replay_targets at ingest
-  bool rp_targets_only_ = false;
-  std::vector<int64_t> rp_tcum_{0};
-  DevBuf<int64_t> d_rp_tcum_;
-  DevBuf<int16_t> d_rp_tply_;
-  DevBuf<int64_t> tgt_idx_;         // replay_scan_targets: offsets and position prefix of the games just filed
-  DevBuf<int32_t> tgt_cnt_;         // ... and their target counts
-  double vt_alpha_ = 0.0, vt_lambda_ = 1.0;   // agz_replay_set_value_target; alpha = 0: off, z stays the result
-  // policy surprise weighting: rp_scored_[k] = game k has scores; d_sp_kl_ / d_sp_tgt_[rp_cum_[k] + t] = the score and the
-  // target flag of ply t of a scored game (laid out by the position prefix, as d_rp_tply_ is; what lies under an unscored
-  // game is never read).  d_sp_q_ / d_sp_qcum_ = q and its inclusive prefix over all positions, rebuilt by
-  // replay_weights_to_device when the arena (rp_change_), the scores (sp_epoch_) or rho changed since they were built
-  double sp_rho_ = 0.0;
-  std::vector<uint8_t> rp_scored_;
-  DevBuf<double> d_sp_kl_;
-  DevBuf<uint8_t> d_sp_tgt_, d_sp_scored_;
-  DevBuf<uint32_t> d_sp_q_;
-  DevBuf<uint64_t> d_sp_qcum_, d_sp_tiles_;
-  DevBuf<int64_t> sp_off_;
-  DevBuf<int32_t> sp_ply_;
-  DevBuf<unsigned long long> sp_count_;
-  uint64_t sp_epoch_ = 0, sp_built_change_ = 0, sp_built_epoch_ = 0, sp_total_ = 0;
-  double sp_built_rho_ = 0.0;
-  bool sp_built_ = false;
-  void replay_scores_reserve();
-  void replay_scored_to_device();
-  void replay_weights_to_device();
-  DevBuf<int64_t> smp_off_, smp_game_;
-  DevBuf<int32_t> smp_ply_, smp_sym_;
-  DevBuf<int8_t> smp_boards_;
+  std::unique_ptr<ReplayArena> replay_;     // made behind stream_, which it enqueues on
+  DevBuf<uint8_t> s_pack_;          // packed records on their way out of the ring or into the arena
   DevBuf<int32_t> hold_rel_;        // View::released
   DevBuf<int8_t> st_board_, st_hist_;       // the start-position table in force (View::st_*)
   DevBuf<agz_position_info> st_info_;

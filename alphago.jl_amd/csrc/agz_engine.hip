@@ -15,98 +15,10 @@
 #include <algorithm>
 #include <cstring>
 
-#include "../../include/agz_surprise.h"
 #include "../../include/agz_value_target.h"
-#include "agz_search.h"
+#include "agz_wave.h"
 
 namespace agz {
-
-// ------------------------------------------------------------------ the wave primitives on gfx950
-
-struct HipWave {
-  static constexpr int kLanes = kWave;
-  int lane;
-  __device__ HipWave() : lane((int)threadIdx.x) {}
-  __device__ explicit HipWave(int l) : lane(l) {}      // (a wave of a multi-wave workgroup: kernels that never call sync())
-  template <class F>
-  __device__ __forceinline__ void for_each(int n, F f) const {
-    for (int i = lane; i < n; i += kWave) f(i);
-  }
-  __device__ __forceinline__ void sync() const { __syncthreads(); }
-  __device__ __forceinline__ bool leader() const { return lane == 0; }
-  __device__ __forceinline__ int reduce_sum(int v) const {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-  }
-  __device__ __forceinline__ int reduce_min(int v) const {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, kWave); v = t < v ? t : v; }
-    return v;
-  }
-  __device__ __forceinline__ int reduce_max(int v) const {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o, kWave); v = t > v ? t : v; }
-    return v;
-  }
-  __device__ __forceinline__ double reduce_max(double v) const {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const double t = __shfl_xor(v, o, kWave); v = t > v ? t : v; }
-    return v;
-  }
-  __device__ __forceinline__ float reduce_sum_f(float v) const {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-  }
-  __device__ __forceinline__ float reduce_max_f(float v) const {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float t = __shfl_xor(v, o, kWave); v = t > v ? t : v; }
-    return v;
-  }
-  __device__ __forceinline__ bool any(bool v) const { return __any(v) != 0; }
-  __device__ __forceinline__ float shfl(float v, int src) const { return __shfl(v, src, kWave); }
-  __device__ __forceinline__ int shfl(int v, int src) const { return __shfl(v, src, kWave); }
-  __device__ __forceinline__ unsigned long long clock() const { return wall_clock64(); }     // 100 MHz
-  __device__ __forceinline__ void count_max(unsigned long long* p, unsigned long long v) const {
-    if (lane == 0) atomicMax(p, v);
-  }
-  // append every get(i) >= 0, i ascending, to a downward stack (base[--sp]); returns the new sp
-  template <class F>
-  __device__ __forceinline__ int push_desc(int n, F get, int32_t* base, int sp) const {
-    for (int b = 0; b < n; b += kWave) {
-      const int i = b + lane;
-      const int c = i < n ? get(i) : -1;
-      const unsigned long long mask = __ballot(c >= 0);
-      if (c >= 0) base[sp - 1 - __popcll(mask & ((1ull << lane) - 1ull))] = c;
-      sp -= __popcll(mask);
-    }
-    return sp;
-  }
-  __device__ __forceinline__ void amin(int32_t* p, int v) const { atomicMin(p, v); }
-  __device__ __forceinline__ void amax(int32_t* p, int v) const { atomicMax(p, v); }
-  __device__ __forceinline__ void aor(int32_t* p, int v) const { atomicOr(p, v); }
-  __device__ __forceinline__ void count(unsigned long long* p, unsigned long long v) const {
-    if (lane == 0 && v) atomicAdd(p, v);
-  }
-  __device__ __forceinline__ unsigned long long fetch_add(unsigned long long* p, unsigned long long v) const {
-    unsigned long long r = 0;
-    if (lane == 0) r = atomicAdd(p, v);
-    const unsigned lo = __shfl((unsigned)(r & 0xffffffffull), 0, kWave);
-    const unsigned hi = __shfl((unsigned)(r >> 32), 0, kWave);
-    return ((unsigned long long)hi << 32) | lo;
-  }
-};
-
-#define AGZ_SCRATCH(S)                                                        \
-  __shared__ int8_t s_sb[kPPMax];                                             \
-  __shared__ int32_t s_label[kPPMax + kWave];                                 \
-  __shared__ int32_t s_minlib[kPPMax];                                        \
-  __shared__ int32_t s_maxlib[kPPMax];                                        \
-  __shared__ int8_t s_flag[kAPMax];                                           \
-  __shared__ double s_dbuf[kAPMax];                                           \
-  __shared__ int32_t s_path[kMaxdMax];                                        \
-  Scratch S{s_sb, s_label, s_minlib, s_maxlib, s_flag, s_dbuf, s_path};
 
 __global__ __launch_bounds__(kWave) void k_pre(View V) {
   AGZ_SCRATCH(S)
@@ -250,6 +162,10 @@ __global__ __launch_bounds__(256) void k_sym_rows(const float* in, float* out, c
     dst[i] = src[j];
   }
 }
+void launch_sym_rows(const float* in, float* out, const int32_t* sym, int B, int N, int planes, int tail, int inverse,
+                     hipStream_t s) {
+  hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, s, in, out, sym, N, planes, tail, inverse);
+}
 
 // The Vector{Position} a caller-supplied network receives (mcts_play.jl:89): per collected leaf of slot g, its own
 // board and the up-to-7 older boards behind the history planes (the same sources k_leaf_features reads), its NodeMeta
@@ -353,65 +269,8 @@ __global__ __launch_bounds__(kWave) void k_go_score(View V, const int8_t* boards
   go_score_one(w, V, S, boards + (long)b * V.P, komi[b], out + b);
 }
 
-// replay_position (board.jl:557-578) on the device: rebuild the 17 planes of positions of a game
-// from its move list.  One wave walks one game: block b replays moves[off[b] .. off[b]+nm[b]) from
-// the empty board, Black first -- or, with start >= 0, from entry `start` of the start-position table (View::st_*:
-// its board, its to_play and its history_len real older boards as the history planes) -- and writes the features of
-// the position BEFORE move k for every k >= emit_from[b] to out + out_off[b] + (k - emit_from[b]) * 17*P.  (record_features: one block, emit_from 0;
-// get_replay_batch, train.jl:4-12: one block per sampled (game, ply), nm = ply+1, emit_from = ply.)
-template <class W>
-__device__ __forceinline__ void replay_emit(W& w, const View& V, Scratch& S, const int16_t* moves, int nm, int from,
-                                            int8_t* hist, float* out, long start = -1) {
-  const int P = V.P;
-  // hist[0] = current board, hist[k] = k moves ago; avail = number of real older boards
-  w.for_each(8 * V.PP, [&](int i) { hist[i] = 0; });
-  w.sync();
-  int tp = 1, avail = 0;
-  if (start >= 0) {
-    const agz_position_info f = V.st_info[start];
-    tp = f.to_play;
-    avail = f.history_len < 7 ? f.history_len : 7;
-    w.for_each(P, [&](int p) { hist[p] = V.st_board[start * P + p]; });
-    for (int h = 0; h < avail; ++h)
-      w.for_each(P, [&](int p) { hist[(h + 1) * V.PP + p] = V.st_hist[(start * 7 + h) * P + p]; });
-    w.sync();
-  }
-  for (int k = 0; k < nm; ++k) {
-    if (k >= from) {
-      w.for_each(P, [&](int p) {
-        float* dst = out + (long)(k - from) * 17 * P;
-        for (int s = 0; s < 8; ++s) {
-          const int t = s <= avail ? s : avail;
-          const int c = hist[t * V.PP + p];
-          dst[(2 * s) * P + p] = c == tp ? 1.f : 0.f;
-          dst[(2 * s + 1) * P + p] = c == -tp ? 1.f : 0.f;
-        }
-        dst[16 * P + p] = (float)tp;
-      });
-      w.sync();
-    }
-    if (k + 1 == nm) break;      // the last listed move is never needed
-    // play move k on hist[0]
-    const int a = moves[k];
-    w.for_each(P, [&](int p) { S.sb[p] = hist[p]; });
-    w.sync();
-    int ncap = 0, nko = -1;
-    if (a >= 0 && a < P) {
-      label_components(w, V, S, true);
-      group_liberties(w, V, S);
-      apply_move_in_scratch(w, V, S, a, tp, &ncap, &nko);
-    }
-    for (int s = 7; s >= 1; --s) {
-      w.for_each(P, [&](int p) { hist[s * V.PP + p] = hist[(s - 1) * V.PP + p]; });
-      w.sync();
-    }
-    w.for_each(P, [&](int p) { hist[p] = S.sb[p]; });
-    w.sync();
-    tp = -tp;
-    if (avail < 7) avail++;
-  }
-}
-
+// replay_emit (agz_wave.h) on caller-given move lists: block b replays moves[off[b] .. off[b] + nms[b]) and writes the
+// features of the positions from emit_from[b] on to out_all + out_off[b]
 __global__ __launch_bounds__(kWave) void k_replay_features(View V, const int16_t* moves, const int32_t* off,
                                                             const int32_t* nms, const int32_t* emit_from,
                                                             const int64_t* out_off,
@@ -424,11 +283,6 @@ __global__ __launch_bounds__(kWave) void k_replay_features(View V, const int16_t
               start ? (long)start[b] : -1);
 }
 
-// the table entry a record's game began at, by the index rule of agz_selfplay_set_starts; -1: no table, the empty board
-__host__ __device__ inline long record_start(const View& V, uint64_t game_id) {
-  return V.st_count > 0 ? (long)((V.arena ? game_id >> 1 : game_id) % (uint64_t)V.st_count) : -1;
-}
-
 // agz_selfplay_set_starts: one wave per candidate entry, ok[s] = its board passes root_board_valid
 __global__ __launch_bounds__(kWave) void k_starts_valid(View V, const int8_t* boards, const agz_position_info* info,
                                                          int32_t* ok) {
@@ -439,121 +293,25 @@ __global__ __launch_bounds__(kWave) void k_starts_valid(View V, const int8_t* bo
   if (w.leader()) ok[s] = good;
 }
 
-// ---- the device replay arena (agz_replay_*): packed records
-//      [agz_game_header 32 B | moves i16[n] | pad 4 | pis f32[n][A] | qs f32[n] | pad 8] back to back in HBM.
-
-__host__ __device__ inline size_t packed_bytes(int A, int nm) {
-  size_t b = sizeof(agz_game_header) + sizeof(int16_t) * (size_t)nm;
-  b = (b + 3) & ~(size_t)3;
-  b += sizeof(float) * (size_t)nm * A + sizeof(float) * (size_t)nm;
-  return (b + 7) & ~(size_t)7;
-}
-
-// one workgroup per finished record k: copy it from the engine's record ring into dst + off[k]
+// one workgroup per finished record k: copy it from the engine's record ring into dst + off[k], packed (PackedRecord)
 __global__ __launch_bounds__(256) void k_pack_records(View V, const int64_t* off, uint8_t* dst, long first) {
   const long k = first + blockIdx.x;
   const agz_game_header h = V.fin_hdr[k];
   const int nm = h.num_moves, mgl = V.max_game_length, A = V.A;
   uint8_t* r = dst + off[blockIdx.x];
-  if (threadIdx.x == 0) *reinterpret_cast<agz_game_header*>(r) = h;
-  int16_t* mv = reinterpret_cast<int16_t*>(r + sizeof(agz_game_header));
-  const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * (size_t)nm + 3) & ~(size_t)3;
-  float* pi = reinterpret_cast<float*>(r + o_pi);
-  float* q = pi + (size_t)nm * A;
+  const PackedRecordW rec{r, nm};
+  if (threadIdx.x == 0) *rec.header() = h;
+  int16_t* mv = rec.moves();
+  float* pi = rec.pi(A);
+  float* q = rec.qs(A);
   for (int i = threadIdx.x; i < nm; i += 256) {
     mv[i] = V.fin_moves[k * mgl + i];
     q[i] = V.fin_q[k * mgl + i];
   }
   if ((nm & 1) && threadIdx.x == 0) mv[nm] = 0;                       // the 2 pad bytes in front of pis
   for (long i = threadIdx.x; i < (long)nm * A; i += 256) pi[i] = V.fin_pi[k * (long)mgl * A + i];
-  const size_t end = o_pi + sizeof(float) * (size_t)nm * (A + 1);
+  const size_t end = rec.unpadded(A);
   if ((end & 7) && threadIdx.x == 0) *reinterpret_cast<uint32_t*>(r + end) = 0u;   // pad to 8
-}
-
-// one wave per source chunk (= one rank's part of the padded all-gather): walk its records and write where
-// each one starts: out_off[first[c] + i] = byte offset of record i of chunk c inside `buf`.  nrec[c] >= 0 is
-// the record count the sender announced (checked); nrec[c] = -(cap + 1) means "unknown, at most cap".
-__global__ __launch_bounds__(kWave) void k_index_records(const uint8_t* buf, const int64_t* chunk_off,
-                                                          const int64_t* chunk_bytes, const int64_t* nrec,
-                                                          const int64_t* first, int A, int mgl, int64_t* out_off,
-                                                          agz_game_header* out_hdr, int64_t* found, int32_t* bad) {
-  if (threadIdx.x != 0) return;
-  const int c = blockIdx.x;
-  int64_t o = chunk_off[c];
-  const int64_t end = o + chunk_bytes[c];
-  const int64_t want = nrec[c], cap = want < 0 ? -(want + 1) : want;
-  int64_t i = 0;
-  bool ok = true;
-  while (o < end) {
-    if (i >= cap || o + (int64_t)sizeof(agz_game_header) > end) { ok = false; break; }
-    const agz_game_header h = *reinterpret_cast<const agz_game_header*>(buf + o);
-    if (h.num_moves < 0 || h.num_moves > mgl || o + (int64_t)packed_bytes(A, h.num_moves) > end) { ok = false; break; }
-    out_off[first[c] + i] = o;
-    out_hdr[first[c] + i] = h;
-    o += (int64_t)packed_bytes(A, h.num_moves);
-    ++i;
-  }
-  if (!ok || o != end || (want >= 0 && i != want)) atomicAdd(bad, 1);
-  found[c] = i;
-}
-
-// get_replay_batch (train.jl:4-12) straight from the arena: sample b = (record at rec_off[b], ply[b]):
-// features of the position before move ply (replay_position, board.jl:557-578), pi of that move, z = result
-__global__ __launch_bounds__(kWave) void k_replay_arena_batch(View V, const uint8_t* arena, const int64_t* rec_off,
-                                                               const int32_t* ply, int8_t* hist_all, float* feats,
-                                                               float* pi_out, float* z_out) {
-  AGZ_SCRATCH(S)
-  HipWave w;
-  const int b = blockIdx.x, A = V.A;
-  const uint8_t* r = arena + rec_off[b];
-  const agz_game_header h = *reinterpret_cast<const agz_game_header*>(r);
-  const int16_t* mv = reinterpret_cast<const int16_t*>(r + sizeof(agz_game_header));
-  const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * (size_t)h.num_moves + 3) & ~(size_t)3;
-  const float* pi = reinterpret_cast<const float*>(r + o_pi) + (size_t)ply[b] * A;
-  replay_emit(w, V, S, mv, ply[b] + 1, ply[b], hist_all + (long)b * 8 * V.PP, feats + (long)b * 17 * V.P,
-              record_start(V, h.game_id));
-  if (pi_out) w.for_each(A, [&](int i) { pi_out[(long)b * A + i] = pi[i]; });
-  if (z_out && w.leader()) z_out[b] = (float)h.result;
-}
-
-// agz_replay_set_value_target with alpha > 0: z of sample b = y_ply[b] of its record (include/agz_value_target.h), written
-// over the result k_replay_arena_batch left there.  One lane per sample walks the record's qs from its last ply down to
-// the sampled one: at most max_game_length dependent f64 steps.
-__global__ __launch_bounds__(kWave) void k_replay_value_targets(const uint8_t* arena, const int64_t* rec_off,
-                                                                 const int32_t* ply, int B, int A, double alpha,
-                                                                 double lambda, float* z_out) {
-  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (b >= B) return;
-  const uint8_t* r = arena + rec_off[b];
-  const agz_game_header h = *reinterpret_cast<const agz_game_header*>(r);
-  const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * (size_t)h.num_moves + 3) & ~(size_t)3;
-  const float* qs = reinterpret_cast<const float*>(r + o_pi) + (size_t)h.num_moves * A;
-  z_out[b] = agz_value_target(qs, h.num_moves, ply[b], h.result, alpha, lambda);
-}
-
-// agz_replay_set_targets_only, the index: one wave per newly filed game scans its pi rows; a ply whose row is not all
-// zero is a policy target (a fast search of agz_selfplay_set_playout_cap and an arena record leave zero rows).  The
-// game's target plies go, in order, to tply[cum[g] ..] -- its share of an array laid out by the arena's position prefix,
-// which has room for every ply -- and their number to count[g].
-__global__ __launch_bounds__(kWave) void k_replay_targets(const uint8_t* arena, const int64_t* rec_off,
-                                                           const int64_t* cum, int A, int16_t* tply, int32_t* count) {
-  HipWave w;
-  const int g = blockIdx.x;
-  const uint8_t* r = arena + rec_off[g];
-  const agz_game_header h = *reinterpret_cast<const agz_game_header*>(r);
-  const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * (size_t)h.num_moves + 3) & ~(size_t)3;
-  const float* pi = reinterpret_cast<const float*>(r + o_pi);
-  int16_t* out = tply + cum[g];
-  int n = 0;
-  for (int k = 0; k < h.num_moves; ++k) {
-    bool nz = false;
-    w.for_each(A, [&](int i) { nz = nz || pi[(size_t)k * A + i] != 0.f; });
-    if (w.any(nz)) {
-      if (w.leader()) out[n] = (int16_t)k;
-      ++n;
-    }
-  }
-  if (w.leader()) count[g] = n;
 }
 
 // ---- reanalysis (agz_replay_reanalyze_start / _commit): a review run whose games are arena records
@@ -570,8 +328,8 @@ __global__ __launch_bounds__(kWave) void k_reanalyze_gather(View V, const uint8_
   const long j = blockIdx.x;
   const int P = V.P;
   const uint8_t* r = arena + rec_off[j];
-  const agz_game_header h = *reinterpret_cast<const agz_game_header*>(r);
-  const int16_t* mv = reinterpret_cast<const int16_t*>(r + sizeof(agz_game_header));
+  const agz_game_header h = *PackedRecord{r, 0}.header();
+  const int16_t* mv = PackedRecord{r, h.num_moves}.moves();
   int16_t* out = rv_moves + rv_off[j];
   w.for_each(h.num_moves, [&](int i) { out[i] = mv[i]; });
   const long s = record_start(V, h.game_id);
@@ -583,282 +341,10 @@ __global__ __launch_bounds__(kWave) void k_reanalyze_gather(View V, const uint8_
   }
 }
 
-// the commit behind it: one wave per result row = (game j, ply k) of the run, j found in the row prefix rv_off.  A row
-// whose search finished in full (status AGZ_OK) writes qs[k] = Q, and its pi row over the record's unless that one is all
-// zero -- "no policy target" (k_replay_targets) stays that, so the targets-only index, the window and the sampler's entry
-// numbering hold.  Every other row leaves the record alone.  counts = {rows committed, pi rows overwritten, rows skipped}
-__global__ __launch_bounds__(kWave) void k_replay_refresh(uint8_t* arena, const int64_t* rec_off, const int64_t* rv_off,
-                                                           int64_t G, int A, const agz_analysis* res, const float* an_pi,
-                                                           unsigned long long* counts) {
-  HipWave w;
-  const int64_t row = blockIdx.x;
-  int64_t lo = 0, hi = G;                                         // rv_off[lo] <= row < rv_off[hi]
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (rv_off[mid] <= row) lo = mid; else hi = mid;
-  }
-  const agz_analysis a = res[row];
-  if (a.status != AGZ_OK) {
-    if (w.leader()) atomicAdd(&counts[2], 1ull);
-    return;
-  }
-  const size_t k = (size_t)(row - rv_off[lo]);
-  uint8_t* r = arena + rec_off[lo];
-  const agz_game_header h = *reinterpret_cast<const agz_game_header*>(r);
-  const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * (size_t)h.num_moves + 3) & ~(size_t)3;
-  float* pi = reinterpret_cast<float*>(r + o_pi) + k * A;
-  float* qs = reinterpret_cast<float*>(r + o_pi) + (size_t)h.num_moves * A;
-  bool nz = false;
-  w.for_each(A, [&](int i) { nz = nz || pi[i] != 0.f; });
-  const bool target = w.any(nz);
-  if (target) w.for_each(A, [&](int i) { pi[i] = an_pi[row * A + i]; });
-  if (w.leader()) {
-    qs[k] = a.Q;
-    atomicAdd(&counts[0], 1ull);
-    if (target) atomicAdd(&counts[1], 1ull);
-  }
-}
-
 // agz_selfplay_release: every slot parked in G_IDLE may claim its next game at the next k_pre
 __global__ void k_release(View V) {
   const int g = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (g < V.games && V.gs[g].phase == G_IDLE) V.released[g] = 1;
-}
-
-// agz_replay_sample, the draw: B distinct entries of the window [0, L) by Floyd's algorithm -- for b = 0..B-1 with
-// j = L - B + b: t_b = agz_index(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_SAMPLE, j), j + 1); sample b is t_b unless
-// t_b is already taken by a sample before it, then j.  All t_b are drawn at once; "t_b is taken" is
-//   dup(b)  -- some b' < b drew the same t (the first of them took it, or t was taken before that one), or
-//   t_b = j' = L - B + b' for a b' < b that fell back to j' itself (b' collided),
-// and b' < b: the second case is a chain through strictly smaller b that each thread follows on its own.  dup is the
-// first-drawer test of an LDS hash table (atomicCAS on the key, atomicMin on the drawer).  Each entry e of the window is
-// then mapped to (game, ply) by a binary search for the last k with cum[k] <= first + e over the arena's position prefix.
-// Targets-only arena (tply != NULL): the entries are target plies, cum is the target prefix, and the entry's index
-// inside its game is looked up in the game's target list tply[pcum[k] ..] (k_replay_targets) to give the ply.
-constexpr int kSampleMax = 2048, kSampleHash = 4096, kSampleThreads = 1024;
-__global__ __launch_bounds__(kSampleThreads) void k_replay_sample(uint64_t seed, uint64_t call, int B, int64_t L,
-                                                                  int64_t first, const int64_t* cum, const int64_t* goff,
-                                                                  const int64_t* pcum, const int16_t* tply,
-                                                                  int64_t ngames, int sym_mode, int64_t* rec_off,
-                                                                  int32_t* ply, int32_t* sym, int64_t* game_out,
-                                                                  int32_t* ply_out) {
-  __shared__ int32_t s_t[kSampleMax];
-  __shared__ int32_t s_dup[kSampleMax];
-  __shared__ int32_t s_key[kSampleHash];
-  __shared__ int32_t s_min[kSampleHash];
-  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-  const int64_t j0 = L - B;
-  for (int h = tid; h < kSampleHash; h += nt) { s_key[h] = -1; s_min[h] = 0x7fffffff; }
-  __syncthreads();
-  for (int b = tid; b < B; b += nt) {
-    const uint64_t j = (uint64_t)(j0 + b);
-    const int32_t t = (int32_t)agz_index(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_SAMPLE, j), (uint32_t)(j + 1));
-    s_t[b] = t;
-    uint32_t h = ((uint32_t)t * 0x9E3779B1u) >> (32 - 12);       // kSampleHash = 2^12 slots, at most half of them used
-    for (;;) {
-      const int32_t k = atomicCAS(&s_key[h], -1, t);
-      if (k == -1 || k == t) break;
-      h = (h + 1) & (kSampleHash - 1);
-    }
-    atomicMin(&s_min[h], b);
-    s_dup[b] = (int32_t)h;                                       // the slot, until every drawer is in
-  }
-  __syncthreads();
-  for (int b = tid; b < B; b += nt) s_dup[b] = s_min[s_dup[b]] < b;
-  __syncthreads();
-  for (int b = tid; b < B; b += nt) {
-    bool taken = false;
-    for (int x = b;;) {
-      if (s_dup[x]) { taken = true; break; }
-      const int64_t tx = s_t[x];
-      if (tx >= j0 && tx - j0 < x) x = (int)(tx - j0); else break;
-    }
-    const int64_t a = first + (taken ? j0 + b : (int64_t)s_t[b]);
-    int64_t lo = 0, hi = ngames;                                  // cum[lo] <= a < cum[hi]
-    while (hi - lo > 1) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (cum[mid] <= a) lo = mid; else hi = mid;
-    }
-    int32_t p = (int32_t)(a - cum[lo]);
-    if (tply) p = (int32_t)tply[pcum[lo] + p];
-    rec_off[b] = goff[lo];
-    ply[b] = p;
-    if (sym)
-      sym[b] = sym_mode == AGZ_SYMMETRY_RANDOM
-                   ? (int32_t)agz_index(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_SYM, (uint64_t)b), 8u)
-                   : sym_mode;
-    if (game_out) game_out[b] = lo;
-    if (ply_out) ply_out[b] = p;
-  }
-}
-
-// ---- policy surprise weighting (agz_replay_score / agz_replay_set_surprise, include/agz_surprise.h)
-
-// the scoring pass, behind the forward: one wave per row = (record at rec_off[b], ply[b]).  The row's pi is read from the
-// arena, p is row b of the forward's output.  Each lane computes whole terms into LDS; lane 0 adds them in ascending a,
-// the order the header's loop adds them in.  A row that is all zero is no target: score 0, flag 0.
-constexpr int kSurpriseMaxA = 19 * 19 + 1;
-__global__ __launch_bounds__(kWave) void k_replay_surprise(const uint8_t* arena, const int64_t* rec_off,
-                                                            const int32_t* ply, const float* p_all, int A, double* kl,
-                                                            uint8_t* tgt, unsigned long long* ntargets) {
-  __shared__ double s_term[kSurpriseMaxA];
-  HipWave w;
-  const long b = blockIdx.x;
-  const uint8_t* r = arena + rec_off[b];
-  const agz_game_header h = *reinterpret_cast<const agz_game_header*>(r);
-  const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * (size_t)h.num_moves + 3) & ~(size_t)3;
-  const float* pi = reinterpret_cast<const float*>(r + o_pi) + (size_t)ply[b] * A;
-  const float* p = p_all + b * A;
-  bool nz = false;
-  w.for_each(A, [&](int a) {
-    const float x = pi[a];
-    nz = nz || x != 0.f;
-    s_term[a] = x > 0.f ? agz_surprise_term(x, p[a]) : 0.0;
-  });
-  const bool target = w.any(nz);
-  w.sync();
-  if (!w.leader()) return;
-  double s = 0.0;
-  if (target) {
-    for (int a = 0; a < A; ++a)
-      if (pi[a] > 0.f) s = s + s_term[a];
-    s = s > 0.0 ? s : 0.0;
-    atomicAdd(ntargets, 1ull);
-  }
-  kl[b] = s;
-  tgt[b] = target ? 1 : 0;
-}
-
-// the weights: one wave per game g0 + blockIdx.x.  Every lane walks the game's plies in order for S and n (the same
-// loads in every lane), then the lanes share the plies out for q.  A game that has not been scored, and a ply that is no
-// target, weigh 1.  Two masks force q to 0: the plies in front of the window (first_game, first_ply -- counted in target
-// plies when the arena is targets-only) and, targets-only (tply != NULL), the plies that are no targets; those are looked
-// up in the game's ascending target list tply[cum[g] .. + tcum[g+1] - tcum[g]).  q goes to q_out[cum[g] - shift + ply].
-__global__ __launch_bounds__(kWave) void k_replay_weights(const int64_t* cum, int64_t g0, const uint8_t* scored,
-                                                           const double* kl, const uint8_t* tgt, double rho,
-                                                           int64_t first_game, int64_t first_ply, const int64_t* tcum,
-                                                           const int16_t* tply, uint32_t* q_out, int64_t shift) {
-  HipWave w;
-  const int64_t g = g0 + blockIdx.x;
-  const int64_t base = cum[g];
-  const int nm = (int)(cum[g + 1] - base);
-  uint32_t* q = q_out + (base - shift);
-  if (g < first_game) {
-    w.for_each(nm, [&](int t) { q[t] = 0u; });
-    return;
-  }
-  const bool sc = scored[g] != 0;
-  double S = 0.0;
-  int n = 0;
-  if (sc)
-    for (int t = 0; t < nm; ++t)
-      if (tgt[base + t]) { S = S + kl[base + t]; ++n; }
-  const int nt = tply ? (int)(tcum[g + 1] - tcum[g]) : 0;
-  const int16_t* tl = tply ? tply + base : nullptr;
-  const int64_t dead = g == first_game ? first_ply : 0;
-  w.for_each(nm, [&](int t) {
-    uint32_t v = AGZ_SURPRISE_UNIT;
-    if (sc && tgt[base + t]) v = agz_surprise_q(kl[base + t], n, S, rho);
-    if (tl) {
-      int lo = 0, hi = nt;                                         // the first i with tl[i] >= t
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (tl[mid] < t) lo = mid + 1; else hi = mid;
-      }
-      if (lo >= nt || tl[lo] != t || lo < dead) v = 0u;
-    } else if (t < dead) {
-      v = 0u;
-    }
-    q[t] = v;
-  });
-}
-
-// the inclusive prefix of q (u32 -> u64) over n positions in three launches: k_scan_reduce (one sum per tile of kScanTile
-// positions), k_scan_tiles (one workgroup turns the tile sums into their exclusive prefix) and k_scan_add (each tile scans
-// its own positions and adds its offset).  No workgroup waits for another: the order is the order of the launches.
-constexpr int kScanThreads = 256, kScanItems = 4, kScanTile = kScanThreads * kScanItems, kScanTop = 1024;
-
-// the block-wide inclusive scan of one value per thread (Hillis-Steele in LDS); s has blockDim.x entries
-__device__ __forceinline__ uint64_t block_scan_inclusive(uint64_t v, uint64_t* s) {
-  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-  s[tid] = v;
-  __syncthreads();
-  for (int o = 1; o < nt; o <<= 1) {
-    const uint64_t add = tid >= o ? s[tid - o] : 0ull;
-    __syncthreads();
-    s[tid] += add;
-    __syncthreads();
-  }
-  return s[tid];
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_scan_reduce(const uint32_t* q, int64_t n, uint64_t* tile_sum) {
-  __shared__ uint64_t s[kScanThreads];
-  const int64_t at = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-  uint64_t v = 0;
-  for (int i = 0; i < kScanItems; ++i)
-    if (at + i < n) v += q[at + i];
-  const uint64_t incl = block_scan_inclusive(v, s);
-  if (threadIdx.x == kScanThreads - 1) tile_sum[blockIdx.x] = incl;
-}
-
-__global__ __launch_bounds__(kScanTop) void k_scan_tiles(uint64_t* tile_sum, int64_t ntiles) {
-  __shared__ uint64_t s[kScanTop];
-  const int64_t per = (ntiles + kScanTop - 1) / kScanTop;          // consecutive tiles per thread
-  const int64_t lo = (int64_t)threadIdx.x * per, hi = lo + per < ntiles ? lo + per : ntiles;
-  uint64_t v = 0;
-  for (int64_t i = lo; i < hi; ++i) v += tile_sum[i];
-  uint64_t run = block_scan_inclusive(v, s) - v;                  // the sum of every tile in front of `lo`
-  for (int64_t i = lo; i < hi; ++i) {
-    const uint64_t x = tile_sum[i];
-    tile_sum[i] = run;
-    run += x;
-  }
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_scan_add(const uint32_t* q, int64_t n, const uint64_t* tile_off,
-                                                            uint64_t* out) {
-  __shared__ uint64_t s[kScanThreads];
-  const int64_t at = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-  uint32_t x[kScanItems];
-  uint64_t v = 0;
-  for (int i = 0; i < kScanItems; ++i) {
-    x[i] = at + i < n ? q[at + i] : 0u;
-    v += x[i];
-  }
-  uint64_t run = tile_off[blockIdx.x] + (block_scan_inclusive(v, s) - v);
-  for (int i = 0; i < kScanItems; ++i) {
-    run += x[i];
-    if (at + i < n) out[at + i] = run;
-  }
-}
-
-// agz_replay_sample under rho > 0: one lane per sample.  Sample b is the position agz_weighted_pick finds for its draw in
-// the prefix qcum of all npos arena positions (with replacement), mapped to (game, ply) by the binary search over the
-// position prefix pcum that k_replay_sample makes.  Everything behind the draw is k_replay_sample's.
-__global__ __launch_bounds__(kWave) void k_replay_sample_weighted(uint64_t seed, uint64_t call, int B,
-                                                                   const uint64_t* qcum, int64_t npos,
-                                                                   const int64_t* pcum, const int64_t* goff,
-                                                                   int64_t ngames, int sym_mode, int64_t* rec_off,
-                                                                   int32_t* ply, int32_t* sym, int64_t* game_out,
-                                                                   int32_t* ply_out) {
-  const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (b >= B) return;
-  const int64_t a = agz_weighted_pick(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_WEIGHTED, (uint64_t)b), qcum, npos);
-  int64_t lo = 0, hi = ngames;                                    // pcum[lo] <= a < pcum[hi]
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (pcum[mid] <= a) lo = mid; else hi = mid;
-  }
-  const int32_t p = (int32_t)(a - pcum[lo]);
-  rec_off[b] = goff[lo];
-  ply[b] = p;
-  if (sym)
-    sym[b] = sym_mode == AGZ_SYMMETRY_RANDOM
-                 ? (int32_t)agz_index(agz_draw_u64(seed, call, 0, AGZ_SITE_REPLAY_SYM, (uint64_t)b), 8u)
-                 : sym_mode;
-  if (game_out) game_out[b] = lo;
-  if (ply_out) ply_out[b] = p;
 }
 
 __global__ void k_debug_draws(uint64_t seed, uint64_t game, uint32_t move, int n, double alpha, double* out) {
@@ -919,6 +405,7 @@ Engine::Engine(const agz_config& cfg) : cfg_(cfg) {
   AGZ_REQUIRE(std::string(prop.gcnArchName).rfind("gfx950", 0) == 0, AGZ_HIP_ERROR,
               "device %d is %s; libagz is built for gfx950 (MI355X) only", cfg.device, prop.gcnArchName);
   AGZ_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+  replay_.reset(new ReplayArena(stream_, V_));
   fill_dims(V_, cfg);
   V_.defer_expand = 1;      // k_expand follows every k_pre (step, select_external)
   AGZ_REQUIRE(V_.PP <= kPPMax && V_.AP <= kAPMax && V_.maxd <= kMaxdMax, AGZ_BAD_ARGUMENT, "board too large");
@@ -1231,9 +718,9 @@ void Engine::set_starts(const int8_t* boards, const agz_position_info* info, con
               "starts: a table and the bench stagger exclude each other (the stagger prefix starts on the empty board)");
   // records are rebuilt through the table: it changes only while nothing is kept that was played under the old one
   const int64_t held = records_count();
-  AGZ_REQUIRE(held == 0 && rp_hdr_.empty(), AGZ_BAD_ARGUMENT,
+  AGZ_REQUIRE(held == 0 && replay_->count() == 0, AGZ_BAD_ARGUMENT,
               "starts: the record ring holds %lld games and the replay arena %lld; clear both first", (long long)held,
-              (long long)rp_hdr_.size());
+              (long long)replay_->count());
   // ... and while no game is on its way into the ring (the table set before a run's first step is that run's)
   require_between_games("starts");
   const int P = V_.P, mgl = V_.max_game_length;
@@ -1455,18 +942,19 @@ void Engine::review_start(const int16_t* moves, const int64_t* game_offset, cons
 
 void Engine::replay_reanalyze_start(int64_t first, int64_t count, uint64_t game_id_base) {
   require_selfplay_engine("reanalyze");
-  const int64_t n = (int64_t)rp_hdr_.size();
+  const int64_t n = replay_->count();
+  const std::vector<agz_game_header>& hdr = replay_->index().hdr();
   AGZ_REQUIRE(n > 0, AGZ_BAD_ARGUMENT, "reanalyze: the replay arena is empty");
   AGZ_REQUIRE(first >= 0 && count >= 1 && count <= n && first <= n - count, AGZ_BAD_ARGUMENT,
               "reanalyze: games %lld .. %lld + %lld: the replay arena holds %lld", (long long)first, (long long)first,
               (long long)count, (long long)n);
   std::vector<int64_t> off((size_t)count + 1, 0);
-  for (int64_t j = 0; j < count; ++j) off[(size_t)j + 1] = off[(size_t)j] + rp_hdr_[(size_t)(first + j)].num_moves;
+  for (int64_t j = 0; j < count; ++j) off[(size_t)j + 1] = off[(size_t)j] + hdr[(size_t)(first + j)].num_moves;
   const int64_t total = off[(size_t)count];
   AGZ_REQUIRE(total <= 0x7fffffffLL, AGZ_BAD_ARGUMENT, "reanalyze: %lld rows in one run: at most 2^31 - 1",
               (long long)total);
   wait();     // nothing in flight may still read the tables that are replaced here
-  replay_index_to_device();
+  replay_->index_to_device();
   const size_t G = (size_t)count, P = (size_t)V_.P, A = (size_t)V_.A, R = (size_t)(total > 0 ? total : 1);
   an_board_.ensure(G * P);
   an_hist_.ensure(7 * G * P);
@@ -1477,8 +965,8 @@ void Engine::replay_reanalyze_start(int64_t first, int64_t count, uint64_t game_
   clear_result_tables(total);
   rv_moves_.ensure(R);
   stage(rv_off_, off.data(), G + 1);
-  hipLaunchKernelGGL(k_reanalyze_gather, dim3((unsigned)G), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
-                     (const int64_t*)(d_rp_off_.p + first), (const int64_t*)rv_off_.p, game_id_base, rv_moves_.p,
+  hipLaunchKernelGGL(k_reanalyze_gather, dim3((unsigned)G), dim3(kWave), 0, stream_, V_, replay_->buffer(),
+                     replay_->offsets_device(first), (const int64_t*)rv_off_.p, game_id_base, rv_moves_.p,
                      an_board_.p, an_hist_.p, an_info_.p, an_gid_.p);
   AGZ_HIP(hipGetLastError());
   rv_off_host_.swap(off);
@@ -1491,32 +979,27 @@ void Engine::replay_reanalyze_start(int64_t first, int64_t count, uint64_t game_
   ra_on_ = true;
   ra_committed_ = false;
   ra_first_ = first;
-  ra_stamp_ = rp_change_;
+  ra_stamp_ = replay_->index().change();
 }
 
 void Engine::replay_reanalyze_commit(int64_t counts_out[3]) {
   AGZ_REQUIRE(ra_on_, AGZ_BAD_ARGUMENT,
               "reanalyze commit: no reanalysis run in force (a later analysis, review or self-play start ends one)");
   AGZ_REQUIRE(!ra_committed_, AGZ_BAD_ARGUMENT, "reanalyze commit: the run has been committed already");
-  AGZ_REQUIRE(ra_stamp_ == rp_change_, AGZ_BAD_ARGUMENT,
+  AGZ_REQUIRE(ra_stamp_ == replay_->index().change(), AGZ_BAD_ARGUMENT,
               "reanalyze commit: the replay arena changed since the run started (ingest, trim, clear, window or targets-only)");
   const int64_t done = analyze_progress(), rows = an_count_;
   AGZ_REQUIRE(done >= rows, AGZ_BAD_ARGUMENT, "reanalyze commit: %lld of %lld rows finished", (long long)done,
               (long long)rows);
   ra_counts_.ensure(3);
   ra_counts_.zero(stream_);
-  if (rows > 0)
-    hipLaunchKernelGGL(k_replay_refresh, dim3((unsigned)rows), dim3(kWave), 0, stream_, rp_buf_.p,
-                       (const int64_t*)(d_rp_off_.p + ra_first_), (const int64_t*)rv_off_.p, (int64_t)V_.an_count, V_.A,
-                       (const agz_analysis*)an_res_.p, (const float*)an_pi_.p, ra_counts_.p);
-  AGZ_HIP(hipGetLastError());
+  replay_->refresh(ra_first_, rv_off_.p, (int64_t)V_.an_count, rows, an_res_.p, an_pi_.p, ra_counts_.p);
   unsigned long long c[3];
   down(c, ra_counts_.p, 3);
   wait();
   ra_committed_ = true;
   // the run's games carry new pi rows: their surprise scores are of the old ones (agz_replay_score scores them again)
-  for (size_t j = 0; j + 1 < rv_off_host_.size(); ++j) rp_scored_[(size_t)ra_first_ + j] = 0;
-  ++sp_epoch_;
+  replay_->forget_scores(ra_first_, (int64_t)rv_off_host_.size() - 1);
   if (counts_out)
     for (int i = 0; i < 3; ++i) counts_out[i] = (int64_t)c[i];
 }
@@ -1825,92 +1308,13 @@ void Engine::records_export_packed(void* dst, int64_t capacity, bool is_device) 
 
 // ---- device replay arena
 
-void Engine::replay_reserve(size_t bytes) {
-  if (bytes <= rp_buf_.n) return;
-  size_t cap = std::max<size_t>(bytes, std::max<size_t>(2 * rp_buf_.n, (size_t)1 << 20));
-  DevBuf<uint8_t> nb;
-  nb.alloc(cap);
-  if (rp_used_) AGZ_HIP(hipMemcpyAsync(nb.p, rp_buf_.p, rp_used_, hipMemcpyDeviceToDevice, stream_));
-  wait();
-  std::swap(nb.p, rp_buf_.p);
-  std::swap(nb.n, rp_buf_.n);
-}
-
-// Append packed records lying in device memory as `chunks` (offset, bytes, expected record count or -1) of
-// `dbuf` -- a padded all-gather receive buffer has one chunk per rank.  The variable-length records are
-// indexed ON THE DEVICE (one wave walks one chunk); only the index (8 B + 32 B per game) visits the host.
-int64_t Engine::replay_ingest_chunks(const uint8_t* dbuf, const std::vector<int64_t>& coff,
-                                     const std::vector<int64_t>& cbytes, const std::vector<int64_t>& cnrec) {
-  const int nc = (int)coff.size();
-  int64_t total_rec = 0, total_bytes = 0;
-  std::vector<int64_t> first((size_t)nc), nrec(cnrec);
-  for (int c = 0; c < nc; ++c) {
-    // an unknown count is bounded by the smallest record (a bare header)
-    if (nrec[c] < 0) nrec[c] = -(cbytes[c] / (int64_t)sizeof(agz_game_header)) - 1;
-    first[c] = total_rec;
-    total_rec += nrec[c] < 0 ? -(nrec[c] + 1) : nrec[c];
-    total_bytes += cbytes[c];
-  }
-  if (total_rec == 0 || total_bytes == 0) return 0;
-  ++rp_change_;
-  // device scratch: [coff | cbytes | nrec | first] int64 x nc, then offsets, found counts, bad flag, headers
-  DevBuf<int64_t> d_meta, d_off;
-  DevBuf<agz_game_header> d_hdr;
-  DevBuf<int32_t> d_flag;
-  d_meta.alloc((size_t)5 * nc);
-  d_off.alloc((size_t)total_rec);
-  d_hdr.alloc((size_t)total_rec);
-  d_flag.alloc(1);
-  std::vector<int64_t> meta;
-  meta.insert(meta.end(), coff.begin(), coff.end());
-  meta.insert(meta.end(), cbytes.begin(), cbytes.end());
-  meta.insert(meta.end(), nrec.begin(), nrec.end());
-  meta.insert(meta.end(), first.begin(), first.end());
-  meta.resize((size_t)5 * nc, 0);
-  up(d_meta.p, meta.data(), meta.size());
-  AGZ_HIP(hipMemsetAsync(d_flag.p, 0, sizeof(int32_t), stream_));
-  hipLaunchKernelGGL(k_index_records, dim3(nc), dim3(kWave), 0, stream_, dbuf, (const int64_t*)d_meta.p,
-                     (const int64_t*)(d_meta.p + nc), (const int64_t*)(d_meta.p + 2 * nc),
-                     (const int64_t*)(d_meta.p + 3 * nc), V_.A, V_.max_game_length, d_off.p, d_hdr.p, d_meta.p + 4 * nc,
-                     d_flag.p);
-  AGZ_HIP(hipGetLastError());
-  std::vector<int64_t> off((size_t)total_rec), found((size_t)nc);
-  std::vector<agz_game_header> hdr((size_t)total_rec);
-  int32_t bad = 0;
-  down(off.data(), d_off.p, off.size());
-  down(hdr.data(), d_hdr.p, hdr.size());
-  down(found.data(), d_meta.p + 4 * nc, (size_t)nc);
-  down(&bad, d_flag.p, 1);
-  wait();
-  AGZ_REQUIRE(bad == 0, AGZ_BAD_ARGUMENT, "packed records are malformed (a record runs past its chunk or a count does not match)");
-  replay_reserve(rp_used_ + (size_t)total_bytes);
-  const size_t first_new = rp_hdr_.size();
-  int64_t added = 0;
-  for (int c = 0; c < nc; ++c) {
-    if (cbytes[c] == 0) continue;
-    AGZ_HIP(hipMemcpyAsync(rp_buf_.p + rp_used_, dbuf + coff[c], (size_t)cbytes[c], hipMemcpyDeviceToDevice, stream_));
-    for (int64_t i = 0; i < found[c]; ++i) {
-      rp_off_.push_back((int64_t)rp_used_ + off[first[c] + i] - coff[c]);
-      rp_hdr_.push_back(hdr[first[c] + i]);
-      rp_scored_.push_back(0);              // a new game has no surprise scores (agz_replay_score)
-      rp_positions_ += hdr[first[c] + i].num_moves;
-      rp_cum_.push_back(rp_positions_);
-    }
-    added += found[c];
-    rp_used_ += (size_t)cbytes[c];
-  }
-  if (rp_targets_only_ && added > 0) replay_scan_targets(first_new);
-  wait();
-  return added;
-}
-
 int64_t Engine::replay_ingest(const void* packed, int64_t nbytes, bool is_device) {
   AGZ_REQUIRE(nbytes >= 0 && (nbytes == 0 || packed), AGZ_BAD_ARGUMENT, "bad packed buffer");
   AGZ_REQUIRE(nbytes % 8 == 0, AGZ_BAD_ARGUMENT, "packed records are a multiple of 8 bytes");
   if (nbytes == 0) return 0;
   const uint8_t* d = (const uint8_t*)packed;
   if (!is_device) d = stage(s_pack_, d, (size_t)nbytes);
-  return replay_ingest_chunks(d, {0}, {nbytes}, {-1});
+  return replay_->ingest_chunks(d, {0}, {nbytes}, {-1});
 }
 
 int64_t Engine::replay_ingest_gathered(const void* buf, bool is_device, size_t nbytes, const std::vector<int64_t>& coff,
@@ -1921,7 +1325,7 @@ int64_t Engine::replay_ingest_gathered(const void* buf, bool is_device, size_t n
     up(s_pack_.p, d, nbytes);
     d = s_pack_.p;
   }
-  return replay_ingest_chunks(d, coff, cbytes, cnrec);
+  return replay_->ingest_chunks(d, coff, cbytes, cnrec);
 }
 
 // files the engine's own finished records that no exchange has filed yet (the watermark rec_sent_ moves; the
@@ -1932,7 +1336,7 @@ int64_t Engine::replay_ingest_local() {
   s_pack_.ensure((size_t)need);
   int64_t nb = 0;
   const int64_t n = pack_records_device(s_pack_.p, need, &nb, rec_sent_);
-  const int64_t added = replay_ingest_chunks(s_pack_.p, {0}, {nb}, {n});
+  const int64_t added = replay_->ingest_chunks(s_pack_.p, {0}, {nb}, {n});
   rec_sent_ += n;
   return added;
 }
@@ -1948,408 +1352,27 @@ int64_t Engine::replay_ingest_records(int64_t first, int64_t count) {
   s_pack_.ensure((size_t)need);
   int64_t nb = 0;
   const int64_t n = pack_records_device(s_pack_.p, need, &nb, first, first + count);
-  return replay_ingest_chunks(s_pack_.p, {0}, {nb}, {n});
+  return replay_->ingest_chunks(s_pack_.p, {0}, {nb}, {n});
 }
 
-void Engine::replay_header(int64_t k, agz_game_header* out) const {
-  AGZ_REQUIRE(k >= 0 && k < (int64_t)rp_hdr_.size(), AGZ_BAD_ARGUMENT, "replay game %lld out of range", (long long)k);
-  *out = rp_hdr_[(size_t)k];
-}
-
-void Engine::replay_game(int64_t k, int16_t* moves, float* pis, float* qs) {
-  agz_game_header h;
-  replay_header(k, &h);
-  const size_t nm = (size_t)h.num_moves;
-  if (nm == 0) return;
-  const uint8_t* r = rp_buf_.p + rp_off_[(size_t)k];
-  const size_t o_pi = (sizeof(agz_game_header) + sizeof(int16_t) * nm + 3) & ~(size_t)3;
-  const float* r_pi = (const float*)(r + o_pi);
-  down(moves, (const int16_t*)(r + sizeof(agz_game_header)), nm);
-  down(pis, r_pi, nm * V_.A);
-  down(qs, r_pi + nm * V_.A, nm);
-  wait();
-}
-
-// the FIFO window of train() (`shrink`, train.jl:52): forget the oldest games until at most max_positions remain
-void Engine::replay_trim(int64_t max_positions) {
-  AGZ_REQUIRE(max_positions >= 0, AGZ_BAD_ARGUMENT, "negative window");
-  ++rp_change_;
-  size_t drop = 0;
-  int64_t pos = rp_positions_;
-  while (drop < rp_hdr_.size() && pos > max_positions) pos -= rp_hdr_[drop++].num_moves;
-  if (drop == 0) return;
-  if (drop == rp_hdr_.size()) { replay_clear(); return; }
-  replay_drop_front(drop);
-}
-
-// forget the oldest `drop` games (0 < drop < count): one copy of the rest into a fresh buffer
-void Engine::replay_drop_front(size_t drop) {
-  const size_t cut = (size_t)rp_off_[drop], keep = rp_used_ - cut;
-  const int64_t pos = rp_positions_ - rp_cum_[drop];
-  DevBuf<uint8_t> nb;
-  nb.alloc(std::max(keep, (size_t)1 << 20));
-  AGZ_HIP(hipMemcpyAsync(nb.p, rp_buf_.p + cut, keep, hipMemcpyDeviceToDevice, stream_));
-  wait();
-  std::swap(nb.p, rp_buf_.p);
-  std::swap(nb.n, rp_buf_.n);
-  if (rp_targets_only_) {           // the target lists lie by position prefix: they move up with it
-    DevBuf<int16_t> nt;
-    nt.alloc(std::max((size_t)pos, (size_t)1 << 16));
-    if (pos > 0)
-      AGZ_HIP(hipMemcpyAsync(nt.p, d_rp_tply_.p + rp_cum_[drop], sizeof(int16_t) * (size_t)pos, hipMemcpyDeviceToDevice,
-                             stream_));
-    wait();
-    std::swap(nt.p, d_rp_tply_.p);
-    std::swap(nt.n, d_rp_tply_.n);
-    const int64_t t0 = rp_tcum_[drop];
-    rp_tcum_.erase(rp_tcum_.begin(), rp_tcum_.begin() + drop);
-    for (auto& c : rp_tcum_) c -= t0;
-  }
-  if (d_sp_kl_.p) {                 // so do the surprise scores and their target flags, as far as they were ever written
-    const size_t c0 = (size_t)rp_cum_[drop], have = d_sp_kl_.n > c0 ? std::min(d_sp_kl_.n - c0, (size_t)pos) : 0;
-    DevBuf<double> nk;
-    DevBuf<uint8_t> ng;
-    nk.alloc(std::max((size_t)pos, (size_t)1 << 16));
-    ng.alloc(nk.n);
-    if (have) {
-      AGZ_HIP(hipMemcpyAsync(nk.p, d_sp_kl_.p + c0, sizeof(double) * have, hipMemcpyDeviceToDevice, stream_));
-      AGZ_HIP(hipMemcpyAsync(ng.p, d_sp_tgt_.p + c0, have, hipMemcpyDeviceToDevice, stream_));
-    }
-    wait();
-    nk.swap(d_sp_kl_);
-    ng.swap(d_sp_tgt_);
-  }
-  rp_scored_.erase(rp_scored_.begin(), rp_scored_.begin() + drop);
-  rp_off_.erase(rp_off_.begin(), rp_off_.begin() + drop);
-  rp_hdr_.erase(rp_hdr_.begin(), rp_hdr_.begin() + drop);
-  for (auto& o : rp_off_) o -= (int64_t)cut;
-  const int64_t c0 = rp_cum_[drop];
-  rp_cum_.erase(rp_cum_.begin(), rp_cum_.begin() + drop);
-  for (auto& c : rp_cum_) c -= c0;
-  rp_used_ = keep;
-  rp_positions_ = pos;
-  if (rp_first_game_ >= (int64_t)drop) {
-    rp_first_game_ -= (int64_t)drop;
-  } else {
-    rp_first_game_ = 0;
-    rp_first_ply_ = 0;
-  }
-  rp_dev_n_ = 0;
-}
-
-// (the targets-only mode is a setting of the arena, not part of its contents: it stays as it is)
-void Engine::replay_clear() {
-  ++rp_change_;
-  rp_off_.clear();
-  rp_hdr_.clear();
-  rp_scored_.clear();               // (the surprise scores go with their games; rho is a setting and stays)
-  rp_cum_.assign(1, 0);
-  rp_tcum_.assign(1, 0);
-  rp_used_ = 0;
-  rp_positions_ = 0;
-  rp_first_game_ = 0;
-  rp_first_ply_ = 0;
-  rp_dev_n_ = 0;
-}
-
-// the window of train() (shrink, train.jl:52, per entry): entries before the newest max_entries are dead; the window's
-// start never moves back.  Dead games are dropped physically only once they hold more than half of the arena's bytes,
-// so the copy is amortised over many calls.  max_entries < 0: every entry live again (nothing dropped comes back).
-void Engine::replay_set_window(int64_t max_entries) {
-  ++rp_change_;
-  if (max_entries < 0) { rp_first_game_ = 0; rp_first_ply_ = 0; return; }
-  const std::vector<int64_t>& ec = rp_entry_cum();       // every ply, or (targets-only) the target plies
-  const int64_t cur = ec[(size_t)rp_first_game_] + rp_first_ply_;
-  const int64_t first = std::max(cur, ec.back() - max_entries);
-  int64_t k = rp_first_game_;
-  const int64_t n = (int64_t)rp_hdr_.size();
-  while (k < n && ec[(size_t)k + 1] <= first) ++k;
-  rp_first_game_ = k;
-  rp_first_ply_ = first - ec[(size_t)k];
-  if (k == n) {                     // nothing live
-    replay_clear();
-    return;
-  }
-  if (k > 0 && (size_t)rp_off_[(size_t)k] > rp_used_ / 2) replay_drop_front((size_t)k);
-}
-
-// The arena counts entries by target plies (agz_replay_set_targets_only).  Only while it is empty: the index of target
-// plies is built as games are filed.
-void Engine::replay_set_targets_only(bool on) {
-  AGZ_REQUIRE(rp_hdr_.empty(), AGZ_BAD_ARGUMENT, "targets only: the replay arena holds %lld games; clear it first",
-              (long long)rp_hdr_.size());
-  rp_targets_only_ = on;
-  ++rp_change_;
-  rp_first_game_ = 0;
-  rp_first_ply_ = 0;
-}
-
-// The value target of the batch calls (agz_replay_set_value_target).  A host-side pair read at the next batch call: the
-// arena and its index do not depend on it, so it may change at any time, and agz_replay_clear leaves it alone.
-void Engine::replay_set_value_target(double alpha, double lambda) {
-  AGZ_REQUIRE(agz_value_target_params_ok(alpha, lambda), AGZ_BAD_ARGUMENT, "value target: alpha %g, lambda %g: both 0..1",
-              alpha, lambda);
-  vt_alpha_ = alpha;
-  vt_lambda_ = lambda;
-}
-
-// games [first_new, count) have just been filed: k_replay_targets writes their target lists, the host extends the
-// target prefix by their counts
-void Engine::replay_scan_targets(size_t first_new) {
-  const size_t n = rp_hdr_.size(), m = n - first_new;
-  if (d_rp_tply_.n < (size_t)rp_positions_) {
-    DevBuf<int16_t> nt;
-    nt.alloc(std::max<size_t>(2 * (size_t)rp_positions_, (size_t)1 << 16));
-    const size_t have = (size_t)rp_cum_[first_new];
-    if (have) AGZ_HIP(hipMemcpyAsync(nt.p, d_rp_tply_.p, sizeof(int16_t) * have, hipMemcpyDeviceToDevice, stream_));
-    wait();
-    std::swap(nt.p, d_rp_tply_.p);
-    std::swap(nt.n, d_rp_tply_.n);
-  }
-  DevBuf<int64_t>& d_idx = tgt_idx_;          // kept between calls: train() files one game at a time
-  DevBuf<int32_t>& d_cnt = tgt_cnt_;
-  d_idx.ensure(2 * m);
-  d_cnt.ensure(m);
-  up(d_idx.p, rp_off_.data() + first_new, m);
-  up(d_idx.p + m, rp_cum_.data() + first_new, m);
-  hipLaunchKernelGGL(k_replay_targets, dim3((unsigned)m), dim3(kWave), 0, stream_, (const uint8_t*)rp_buf_.p,
-                     (const int64_t*)d_idx.p, (const int64_t*)(d_idx.p + m), V_.A, d_rp_tply_.p, d_cnt.p);
-  AGZ_HIP(hipGetLastError());
-  std::vector<int32_t> cnt(m);
-  down(cnt.data(), d_cnt.p, m);
-  wait();
-  rp_tcum_.resize(first_new + 1);
-  for (size_t i = 0; i < m; ++i) rp_tcum_.push_back(rp_tcum_.back() + cnt[i]);
-}
-
-// get_replay_batch (train.jl:4-12) with the draw on the device: k_replay_sample picks B distinct live entries and maps
-// them to (record offset, ply), k_replay_arena_batch (and k_sym_rows) turn them into the batch.  No host copy of the
-// samples; only the arena's index (rp_cum_ / rp_off_) is uploaded, and only what changed since the last call.
-void Engine::replay_sample(int B, uint64_t call, int sym_mode, float* feats, float* pi, float* z, int64_t* game_out,
-                           int32_t* ply_out) {
-  const int64_t L = replay_live_positions();
-  AGZ_REQUIRE(B >= 1 && B <= kSampleMax, AGZ_BAD_ARGUMENT, "batch %d: 1..%d samples", B, kSampleMax);
-  const bool weighted = sp_rho_ > 0.0;      // agz_replay_set_surprise: drawn by weight, with replacement
-  if (weighted)
-    AGZ_REQUIRE(L >= 1, AGZ_BAD_ARGUMENT, "batch %d from an empty window", B);
-  else
-    AGZ_REQUIRE(B <= L, AGZ_BAD_ARGUMENT, "batch %d from a window of %lld entries (sampling without replacement)", B,
-                (long long)L);
-  AGZ_REQUIRE(L <= 0x7fffffffLL, AGZ_BAD_ARGUMENT, "window of %lld entries: at most 2^31 - 1", (long long)L);
-  AGZ_REQUIRE(sym_mode >= AGZ_SYMMETRY_NONE && sym_mode <= AGZ_SYMMETRY_RANDOM, AGZ_BAD_ARGUMENT,
-              "sym_mode %d: -1 (none), 0..7 (fixed T_s) or 8 (drawn)", sym_mode);
-  AGZ_REQUIRE(feats, AGZ_BAD_ARGUMENT, "feats is NULL");
-  const int64_t n = (int64_t)rp_hdr_.size();
-  replay_index_to_device();
-  smp_off_.ensure(kSampleMax);
-  smp_ply_.ensure(kSampleMax);
-  smp_sym_.ensure(kSampleMax);
-  smp_boards_.ensure((size_t)B * 8 * V_.PP);
-  const bool with_sym = sym_mode != AGZ_SYMMETRY_NONE;
-  if (weighted) {
-    replay_weights_to_device();
-    AGZ_REQUIRE(sp_total_ > 0, AGZ_BAD_ARGUMENT, "every live entry has weight 0 (rho = %g)", sp_rho_);
-    hipLaunchKernelGGL(k_replay_sample_weighted, dim3((unsigned)((B + kWave - 1) / kWave)), dim3(kWave), 0, stream_,
-                       (uint64_t)V_.seed, call, B, (const uint64_t*)d_sp_qcum_.p, rp_positions_,
-                       (const int64_t*)d_rp_cum_.p, (const int64_t*)d_rp_off_.p, n, sym_mode, smp_off_.p, smp_ply_.p,
-                       with_sym ? smp_sym_.p : nullptr, game_out, ply_out);
-  } else {
-    hipLaunchKernelGGL(k_replay_sample, dim3(1), dim3(kSampleThreads), 0, stream_, (uint64_t)V_.seed, call, B, L,
-                       rp_entry_cum()[(size_t)rp_first_game_] + rp_first_ply_,
-                       (const int64_t*)(rp_targets_only_ ? d_rp_tcum_.p : d_rp_cum_.p), (const int64_t*)d_rp_off_.p,
-                       (const int64_t*)d_rp_cum_.p, (const int16_t*)(rp_targets_only_ ? d_rp_tply_.p : nullptr), n,
-                       sym_mode, smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, game_out, ply_out);
-  }
-  AGZ_HIP(hipGetLastError());
-  emit_replay_batch(B, smp_off_.p, smp_ply_.p, with_sym ? smp_sym_.p : nullptr, smp_boards_.p, feats, pi, z);
-}
-
-// ---- policy surprise weighting (include/agz_surprise.h)
-
-// room in d_sp_kl_ / d_sp_tgt_ for every arena position; what has been written stays where it is
-void Engine::replay_scores_reserve() {
-  const size_t need = (size_t)rp_positions_;
-  if (d_sp_kl_.n >= need && d_sp_kl_.p) return;
-  DevBuf<double> nk;
-  DevBuf<uint8_t> ng;
-  nk.alloc(std::max<size_t>(2 * need, (size_t)1 << 16));
-  ng.alloc(nk.n);
-  if (d_sp_kl_.n) {
-    AGZ_HIP(hipMemcpyAsync(nk.p, d_sp_kl_.p, sizeof(double) * d_sp_kl_.n, hipMemcpyDeviceToDevice, stream_));
-    AGZ_HIP(hipMemcpyAsync(ng.p, d_sp_tgt_.p, d_sp_tgt_.n, hipMemcpyDeviceToDevice, stream_));
-  }
-  wait();
-  nk.swap(d_sp_kl_);
-  ng.swap(d_sp_tgt_);
-}
-
-// the per-game scored flags on the device (a byte per game: all of them, every time)
-void Engine::replay_scored_to_device() {
-  const size_t n = rp_hdr_.size();
-  if (d_sp_scored_.n < n) d_sp_scored_.alloc(std::max<size_t>(2 * n, 1024));
-  up(d_sp_scored_.p, rp_scored_.data(), n);
-  wait();
-}
-
-// agz_replay_score: the games' plies in chunks of at most the engine's forward batch -- k_replay_arena_batch for the
-// features, the staged forward of the ABI calls (its buffers are not the ones the games in flight use), k_replay_surprise
-// for one score per row.  Everything runs on stream_, between steps.
+// agz_replay_score: what concerns the engine is checked here, and the arena's scoring loop gets the staged forward of
+// the ABI calls on the selected network (its buffers are not the ones the games in flight use) in chunks of at most the
+// engine's forward batch.  Scoring never runs without a network: the first check.
 int64_t Engine::replay_score(int64_t first, int64_t count) {
   AGZ_REQUIRE(!cfg_.external_network, AGZ_BAD_ARGUMENT,
               "score: engine was created with external_network=1 and has no network to score on");
   AGZ_REQUIRE(!(ra_on_ && !ra_committed_), AGZ_BAD_ARGUMENT, "score: a reanalysis run is open; commit it first");
-  const int64_t n = (int64_t)rp_hdr_.size();
-  AGZ_REQUIRE(first >= 0 && count >= 0 && count <= n && first <= n - count, AGZ_BAD_ARGUMENT,
-              "score: games %lld .. %lld + %lld: the replay arena holds %lld", (long long)first, (long long)first,
-              (long long)count, (long long)n);
-  if (count == 0) return 0;
-  const int64_t pos0 = rp_cum_[(size_t)first], rows = rp_cum_[(size_t)(first + count)] - pos0;
-  std::vector<int64_t> off((size_t)rows);
-  std::vector<int32_t> ply((size_t)rows);
-  for (int64_t k = first, r = 0; k < first + count; ++k)
-    for (int32_t t = 0; t < rp_hdr_[(size_t)k].num_moves; ++t, ++r) {
-      off[(size_t)r] = rp_off_[(size_t)k];
-      ply[(size_t)r] = t;
-    }
-  replay_scores_reserve();
-  sp_count_.ensure(1);
-  sp_count_.zero(stream_);
-  unsigned long long targets = 0;
-  if (rows > 0) {
-    sp_off_.ensure((size_t)rows);
-    sp_ply_.ensure((size_t)rows);
-    up(sp_off_.p, off.data(), (size_t)rows);
-    up(sp_ply_.p, ply.data(), (size_t)rows);
-    const int cap = bcap_;
-    s_boards_.ensure((size_t)cap * 8 * V_.PP);
-    d_whcn_.ensure((size_t)cap * 17 * V_.P);
-    for (int64_t r0 = 0; r0 < rows; r0 += cap) {
-      const int Bc = (int)std::min<int64_t>(cap, rows - r0);
-      hipLaunchKernelGGL(k_replay_arena_batch, dim3(Bc), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p,
-                         (const int64_t*)(sp_off_.p + r0), (const int32_t*)(sp_ply_.p + r0), s_boards_.p, d_whcn_.p,
-                         (float*)nullptr, (float*)nullptr);
-      launch_whcn_to_x32(d_whcn_.p, Bc, V_.N, stage_forward(Bc), stream_);
-      forward_x32(Bc);
-      hipLaunchKernelGGL(k_replay_surprise, dim3(Bc), dim3(kWave), 0, stream_, (const uint8_t*)rp_buf_.p,
-                         (const int64_t*)(sp_off_.p + r0), (const int32_t*)(sp_ply_.p + r0), (const float*)s_f32b_.p, V_.A,
-                         d_sp_kl_.p + pos0 + r0, d_sp_tgt_.p + pos0 + r0, sp_count_.p);
-      AGZ_HIP(hipGetLastError());
-      wait();                           // Bc was uploaded from this frame (stage_forward)
-      net().check_async_error();
-    }
-    down(&targets, sp_count_.p, 1);
-    wait();
-  }
-  for (int64_t k = first; k < first + count; ++k) rp_scored_[(size_t)k] = 1;
-  ++sp_epoch_;
-  return (int64_t)targets;
-}
-
-// rho of agz_replay_sample's draw.  A host-side value read at the next sample call: it may change at any time, and
-// agz_replay_clear leaves it alone.
-void Engine::replay_set_surprise(double rho) {
-  AGZ_REQUIRE(agz_surprise_rho_ok(rho), AGZ_BAD_ARGUMENT, "surprise: rho %g: 0..1", rho);
-  sp_rho_ = rho;
-}
-
-// game k's scores, its q under the rho in force (k_replay_weights on that game alone, without the sampler's masks) and
-// its scored flag
-void Engine::replay_surprise(int64_t k, double* kl_out, uint32_t* q_out, int32_t* scored_out) {
-  AGZ_REQUIRE(k >= 0 && k < (int64_t)rp_hdr_.size(), AGZ_BAD_ARGUMENT, "replay game %lld out of range", (long long)k);
-  const size_t nm = (size_t)rp_hdr_[(size_t)k].num_moves;
-  const bool sc = rp_scored_[(size_t)k] != 0;
-  if (scored_out) *scored_out = sc ? 1 : 0;
-  if (nm == 0) return;
-  if (kl_out) {
-    if (sc) down(kl_out, d_sp_kl_.p + rp_cum_[(size_t)k], nm);
-    else std::fill(kl_out, kl_out + nm, 0.0);
-  }
-  if (q_out) {
-    replay_index_to_device();
-    replay_scored_to_device();
-    d_sp_q_.ensure(std::max<size_t>((size_t)rp_positions_, (size_t)1 << 16));     // (the sampler reads d_sp_qcum_ only)
-    hipLaunchKernelGGL(k_replay_weights, dim3(1), dim3(kWave), 0, stream_, (const int64_t*)d_rp_cum_.p, k,
-                       (const uint8_t*)d_sp_scored_.p, (const double*)d_sp_kl_.p, (const uint8_t*)d_sp_tgt_.p, sp_rho_,
-                       (int64_t)0, (int64_t)0, (const int64_t*)nullptr, (const int16_t*)nullptr, d_sp_q_.p,
-                       rp_cum_[(size_t)k]);
-    AGZ_HIP(hipGetLastError());
-    down(q_out, d_sp_q_.p, nm);
-  }
-  wait();
-}
-
-// q of every arena position and its inclusive prefix on the device, if the arena, the scores or rho changed since they
-// were built: k_replay_weights, then the scan in three launches; the total comes back for the sampler's check
-void Engine::replay_weights_to_device() {
-  if (sp_built_ && sp_built_change_ == rp_change_ && sp_built_epoch_ == sp_epoch_ && sp_built_rho_ == sp_rho_) return;
-  const int64_t n = (int64_t)rp_hdr_.size(), npos = rp_positions_;
-  replay_index_to_device();
-  replay_scored_to_device();
-  const int64_t ntiles = (npos + kScanTile - 1) / kScanTile;
-  if (d_sp_q_.n < (size_t)npos) d_sp_q_.alloc(std::max<size_t>(2 * (size_t)npos, (size_t)1 << 16));
-  if (d_sp_qcum_.n < (size_t)npos) d_sp_qcum_.alloc(std::max<size_t>(2 * (size_t)npos, (size_t)1 << 16));
-  if (d_sp_tiles_.n < (size_t)ntiles) d_sp_tiles_.alloc(std::max<size_t>(2 * (size_t)ntiles, 1024));
-  hipLaunchKernelGGL(k_replay_weights, dim3((unsigned)n), dim3(kWave), 0, stream_, (const int64_t*)d_rp_cum_.p, (int64_t)0,
-                     (const uint8_t*)d_sp_scored_.p, (const double*)d_sp_kl_.p, (const uint8_t*)d_sp_tgt_.p, sp_rho_,
-                     rp_first_game_, rp_first_ply_, (const int64_t*)(rp_targets_only_ ? d_rp_tcum_.p : nullptr),
-                     (const int16_t*)(rp_targets_only_ ? d_rp_tply_.p : nullptr), d_sp_q_.p, (int64_t)0);
-  hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)ntiles), dim3(kScanThreads), 0, stream_, (const uint32_t*)d_sp_q_.p,
-                     npos, d_sp_tiles_.p);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kScanTop), 0, stream_, d_sp_tiles_.p, ntiles);
-  hipLaunchKernelGGL(k_scan_add, dim3((unsigned)ntiles), dim3(kScanThreads), 0, stream_, (const uint32_t*)d_sp_q_.p, npos,
-                     (const uint64_t*)d_sp_tiles_.p, d_sp_qcum_.p);
-  AGZ_HIP(hipGetLastError());
-  sp_total_ = fetch(d_sp_qcum_.p + (npos - 1));
-  sp_built_ = true;
-  sp_built_change_ = rp_change_;
-  sp_built_epoch_ = sp_epoch_;
-  sp_built_rho_ = sp_rho_;
-}
-
-// the arena's index (rp_off_, rp_cum_ and, targets-only, rp_tcum_) on the device: only what changed since the last call
-void Engine::replay_index_to_device() {
-  const int64_t n = (int64_t)rp_hdr_.size();
-  if (d_rp_cum_.n < (size_t)n + 1 || d_rp_off_.n < (size_t)n || (rp_targets_only_ && d_rp_tcum_.n < (size_t)n + 1)) {
-    const size_t cap = std::max<size_t>(2 * (size_t)n + 1, 1024);
-    d_rp_cum_.alloc(cap);
-    d_rp_off_.alloc(cap);
-    if (rp_targets_only_) d_rp_tcum_.alloc(cap);
-    rp_dev_n_ = 0;
-  }
-  if (rp_dev_n_ < n) {
-    const size_t at = (size_t)rp_dev_n_, fresh = (size_t)n - at;
-    up(d_rp_off_.p + at, rp_off_.data() + at, fresh);
-    up(d_rp_cum_.p + at, rp_cum_.data() + at, fresh + 1);
-    if (rp_targets_only_) up(d_rp_tcum_.p + at, rp_tcum_.data() + at, fresh + 1);
-    wait();      // the host vectors may move with the next ingest
-    rp_dev_n_ = n;
-  }
-}
-
-// B samples given on the device as (record offset, ply) -> feats [B][17 P], pi [B][A] (or NULL) and z [B] (or NULL) in
-// device memory; `boards` is replay scratch of B * 8 * PP.  With `sym` (device, [B]) the samples are written as they are
-// into s_symf_ / s_symp_ and sample b goes under T_sym[b] into the outputs.  The sampler and agz_replay_batch share that
-// pair: both enqueue on stream_ only, so the later call's kernels start after the earlier call's have read it, and a
-// regrow goes through hipFree, which waits for the device.  Nothing here waits: agz_replay_sample stays asynchronous.
-void Engine::emit_replay_batch(int B, const int64_t* off, const int32_t* ply, const int32_t* sym, int8_t* boards,
-                               float* feats, float* pi, float* z) {
-  float *f = feats, *p = pi;
-  if (sym) {
-    s_symf_.ensure((size_t)B * 17 * V_.P);
-    s_symp_.ensure((size_t)B * V_.A);
-    f = s_symf_.p;
-    p = pi ? s_symp_.p : nullptr;
-  }
-  hipLaunchKernelGGL(k_replay_arena_batch, dim3(B), dim3(kWave), 0, stream_, V_, (const uint8_t*)rp_buf_.p, off, ply,
-                     boards, f, p, z);
-  if (sym) {
-    hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)f, feats, sym, V_.N, 17, 0, 0);
-    if (pi) hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)p, pi, sym, V_.N, 1, 1, 0);
-  }
-  if (z && vt_alpha_ > 0.0)         // agz_replay_set_value_target: z becomes y (a symmetry does not touch it)
-    hipLaunchKernelGGL(k_replay_value_targets, dim3((unsigned)((B + kWave - 1) / kWave)), dim3(kWave), 0, stream_,
-                       (const uint8_t*)rp_buf_.p, off, ply, B, V_.A, vt_alpha_, vt_lambda_, z);
-  AGZ_HIP(hipGetLastError());
+  d_whcn_.ensure((size_t)bcap_ * 17 * V_.P);
+  ReplayForward fwd;
+  fwd.cap = bcap_;
+  fwd.whcn = d_whcn_.p;
+  fwd.run = [this](const int& B) -> const float* {
+    launch_whcn_to_x32(d_whcn_.p, B, V_.N, stage_forward(B), stream_);
+    forward_x32(B);
+    return s_f32b_.p;
+  };
+  fwd.check = [this] { net().check_async_error(); };
+  return replay_->score(first, count, fwd);
 }
 
 void Engine::train_step(const float* feats, const float* pi, const float* z, int B, bool is_device, float eta, float rho,
@@ -2399,11 +1422,12 @@ void Engine::replay_batch(const int64_t* game, const int32_t* ply, int B, float*
   if (sym)
     for (int b = 0; b < B; ++b) AGZ_REQUIRE(sym[b] >= 0 && sym[b] < 8, AGZ_BAD_ARGUMENT, "sym[%d] = %d: 0..7", b, sym[b]);
   std::vector<int64_t> off((size_t)B);
+  const ReplayIndex& ix = replay_->index();
   for (int b = 0; b < B; ++b) {
-    AGZ_REQUIRE(game[b] >= 0 && game[b] < (int64_t)rp_hdr_.size(), AGZ_BAD_ARGUMENT, "sample %d: game out of range", b);
-    AGZ_REQUIRE(ply[b] >= 0 && ply[b] < rp_hdr_[(size_t)game[b]].num_moves, AGZ_BAD_ARGUMENT,
+    AGZ_REQUIRE(game[b] >= 0 && game[b] < ix.count(), AGZ_BAD_ARGUMENT, "sample %d: game out of range", b);
+    AGZ_REQUIRE(ply[b] >= 0 && ply[b] < ix.hdr()[(size_t)game[b]].num_moves, AGZ_BAD_ARGUMENT,
                 "sample %d: ply outside the game (searches_pi has one entry per move played)", b);
-    off[b] = rp_off_[(size_t)game[b]];
+    off[b] = ix.off()[(size_t)game[b]];
   }
   const size_t n = (size_t)B, per = (size_t)17 * V_.P, A = V_.A;
   s_boards_.ensure(n * 8 * V_.PP);
@@ -2418,7 +1442,7 @@ void Engine::replay_batch(const int64_t* game, const int32_t* ply, int B, float*
   const int64_t* d_off = stage(s_i64a_, off.data(), n);
   const int32_t* d_ply = stage(s_i32a_, ply, n);
   const int32_t* d_sym = sym ? stage(s_sym_, sym, n) : nullptr;      // agz_replay_batch_sym
-  emit_replay_batch(B, d_off, d_ply, d_sym, s_boards_.p, df, dp, dz);
+  replay_->emit(B, d_off, d_ply, d_sym, s_boards_.p, df, dp, dz);
   if (!out_is_device) {
     down(feats, df, per * n);
     down(pi, dp, n * A);
@@ -2526,7 +1550,7 @@ void Engine::forward_staged(int B, const int32_t* d_sym, float* pi_out, float* v
   const float* pi = s_f32b_.p;
   forward_x32(B);
   if (d_sym) {      // s_symp_: sized by the caller, next to s_symf_
-    hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, (const float*)s_f32b_.p, s_symp_.p, d_sym, V_.N, 1, 1, 1);
+    launch_sym_rows(s_f32b_.p, s_symp_.p, d_sym, B, V_.N, 1, 1, 1, stream_);
     AGZ_HIP(hipGetLastError());
     pi = s_symp_.p;
   }
@@ -2577,7 +1601,7 @@ void Engine::net_forward_features_sym(const float* feats, const int32_t* sym, in
   const int32_t* d_sym = stage(s_sym_, sym, (size_t)B);
   s_symf_.ensure(n);
   s_symp_.ensure((size_t)B * V_.A);
-  hipLaunchKernelGGL(k_sym_rows, dim3(B), dim3(256), 0, stream_, whcn, s_symf_.p, d_sym, V_.N, 17, 0, 0);
+  launch_sym_rows(whcn, s_symf_.p, d_sym, B, V_.N, 17, 0, 0, stream_);
   launch_whcn_to_x32(s_symf_.p, B, V_.N, stage_forward(B), stream_);
   forward_staged(B, d_sym, pi_out, v_out);
 }

@@ -185,7 +185,7 @@ def test_surface_is_declared_everywhere():
         assert name in hdr and name in lib._agz_signatures and hasattr(lib, name) and ":" + name in jl, name
     assert "agz_surprise.h" in hdr
     assert "AGZ_SITE_REPLAY_WEIGHTED 13u" in open(os.path.join(ROOT, "include", "agz_draws.h")).read()
-    for rel in ("alphago.jl_amd/csrc/agz_engine.hip", "alphago.jl_amd/csrc/agz_capi.hip"):        # one arithmetic, included
+    for rel in ("alphago.jl_amd/csrc/agz_replay.hip", "alphago.jl_amd/csrc/agz_capi.hip"):        # one arithmetic, included
         assert "include/agz_surprise.h" in open(os.path.join(ROOT, rel)).read()
     assert "surprise::Real = 0.0" in jl
     assert lib.agz_version() == 103
