@@ -47,6 +47,9 @@ CASES = {
     "b-9-t10": dict(family="B", N=9, tower=10, B=3, seed=910, probes=16),
     "b-19-t3": dict(family="B", N=19, tower=3, B=2, seed=193, probes=16, k_tower=(24, 24, 48, 48, 48, 4)),
 }
+# every other board size (family A, tower 2): the batches of trunk_probe.SIZE_BATCH, the geometry cases' shift, seed 500 + N
+CASES.update({f"a-{N}-t2": dict(family="A", N=N, tower=2, B=B, seed=500 + N, probes=8, shift=(-2, 1))
+              for N, B in tp.SIZE_BATCH.items()})
 # tile geometry (family A, tower 3): name -> N, B; D_ref is taken on `geometry_boards` only
 GEOMETRY = {"g-4-14": (4, 14), "g-4-15": (4, 15), "g-4-16": (4, 16), "g-4-17": (4, 17), "g-9-820": (9, 820), "g-16-8": (16, 8)}
 GEOMETRY_TOWER, GEOMETRY_SEED, GEOMETRY_SHIFT = 3, 77, (-2, 1)    # (the shift: >= 25 % alive on a 4x4 board too)

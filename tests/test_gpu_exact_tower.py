@@ -17,7 +17,35 @@ rounding or a lost row each move some D_ref by >= 1.
     valid at the board runs under the same criterion;
   * family B (halves are rounded, ties included, down to the last block): `f16` against oracle precision 16 at (9, t10) and
     (19, t3) -- and the `direct` f32 read-out of the same network differs, so the fp16 kernels produced it;
-  * tile geometry of the persistent fp16 kernels (256-row and 224-row tiles) at their edges."""
+  * tile geometry of the persistent fp16 kernels (256-row and 224-row tiles) at their edges.
+
+Family A at tower 2 runs at EVERY board size from 3 to 19 under every form the size has (test_gpu_trunk.forms_at; the batches of
+trunk_probe.SIZE_BATCH fill one tile block of every form, leave a partial one and span two fp16 tiles), because the edge code of
+every tower form depends on the size: T tiles a side, the boards a tile block holds, and the overhang, the points by which the
+last tile hangs over the board edge --
+
+                F(3x3,3x3)                        F(4x4,3x3), from 13
+     N    T   boards per block   overhang    T   boards per block    overhang
+     3    1   64                 0
+     4    2   16                 2
+     5    2   16                 1
+     6    2   16                 0
+     7    3   7                  2
+     8    3   7                  1
+     9    3   7                  0
+    10    4   4                  2
+    11    4   4                  1
+    12    4   4                  0
+    13    5   dense              2           4   4                   3
+    14    5   dense              1           4   4                   2
+    15    5   dense              0           4   4                   1
+    16    6   dense              2           4   4                   0
+    17    6   dense              1           5   5 per block pair    3
+    18    6   dense              0           5   5 per block pair    2
+    19    7   dense              2           5   5 per block pair    1
+
+-- and because k_conv3x3_f16_w2 and k_conv3x3_f16_q find a row's board point with float reciprocals of N and P and mask their
+taps by it: a quotient that is off by one at some size, or a tap mask wrong at an edge, changes an integer here."""
 import numpy as np
 import pytest
 
@@ -25,13 +53,14 @@ import alphago_jl_amd as ag
 import exact_nets as en
 import trunk_probe as tp
 from gpu_common import copy_weights_from_oracle
-from test_gpu_trunk import FORMS, SMALL, _where
+from test_gpu_trunk import FORMS, SIZES, SMALL, _where, forms_at
 
 pytestmark = pytest.mark.gpu
 BAR = 0.25
 LARGE = ["winograd", "f33-dense", "direct", "f32s", "f16"]
 A_CASES = ([(n, f) for n in ("a-9-t1", "a-9-t2", "a-9-t3", "a-9-t5") for f in ["f16"] + SMALL]
-           + [(n, f) for n in ("a-19-t2", "a-13-t2") for f in LARGE])
+           + [(n, f) for n in ("a-19-t2", "a-13-t2") for f in LARGE]
+           + [(f"a-{N}-t2", f) for N in SIZES for f in forms_at(N)])
 
 
 def _engine(N, tower, onet, form):

@@ -11,7 +11,9 @@ entries, in every case except that test's N = 3 and 10; at (5, 1, 7) and at N = 
 depend on the input at all.
 Where a plane is live it sits behind a softmax with pi max 0.004 .. 0.1.  These tests keep their meaning for layouts, batch
 rows and entry points (the bit-for-bit assertions); the arithmetic of every tower form is held against float64 on the trunk
-itself, and pi / v on networks with live heads, in tests/test_gpu_trunk.py."""
+itself, and pi / v on networks with live heads, in tests/test_gpu_trunk.py -- at every board size from 3 to 19, so at every
+tiling class and edge overhang that test_every_tiling_class_of_the_winograd_tower visits and at 5, 7, 11 and 14, which it does
+not -- and to the integer on the exact networks of tests/test_gpu_exact_tower.py at the same sizes."""
 import ctypes as C
 
 import numpy as np

@@ -17,7 +17,39 @@ Bars, on e_gpu = max |l_gpu - l_f64| against e_ref = max |l_directf32oracle - l_
     tests/test_gpu_exact_tower.py, where every rounded value is an integer and the trunk has to agree exactly;
   * every form: a row's read-out does not depend on its batch position, to the bit.
 tests/test_trunk_probe.py::test_defect_audit shows a dropped tap or tf32-class weight noise at >= 16 e_ref.  No bar here comes from
-a device measurement.  Then the ordinary heads, on live networks: |dpi|, |dv| <= 1e-4 against float64, the project's bar."""
+a device measurement.  Then the ordinary heads, on live networks: |dpi|, |dv| <= 1e-4 against float64, the project's bar.
+
+Board size is what the tower's edge code depends on, so tower 2 (the stem epilogue that emits the first V, a conv1 / conv2 pair
+with its residual, the hand-over to the next block, the last layer; in fp16 `w2` on the first and last layer and `q` on the two
+between) runs at EVERY size from 3 to 19, under every form the size has (`forms_at`).  The size classes -- T tiles a side, the
+boards a tile block holds, and the overhang: the points by which the last tile hangs over the board edge:
+
+         F(3x3,3x3): winograd up to 12, persistent, five-pass,      F(4x4,3x3): winograd from 13
+         f32s; from 13 on dense blocks (f33-dense, f32s)
+     N    T   boards per block   overhang                            T   boards per block    overhang
+     3    1   64                 0
+     4    2   16                 2
+     5    2   16                 1
+     6    2   16                 0
+     7    3   7                  2
+     8    3   7                  1
+     9    3   7                  0
+    10    4   4                  2
+    11    4   4                  1
+    12    4   4                  0
+    13    5   dense              2                                   4   4                   3
+    14    5   dense              1                                   4   4                   2
+    15    5   dense              0                                   4   4                   1
+    16    6   dense              2                                   4   4                   0
+    17    6   dense              1                                   5   5 per block pair    3
+    18    6   dense              0                                   5   5 per block pair    2
+    19    7   dense              2                                   5   5 per block pair    1
+
+The batches (trunk_probe.SIZE_BATCH) fill one tile block of every form and leave a partial one; 7 boards at 17 are one block pair
+and one block, 8 at 18 a pair and two blocks (75 left-over tiles > 64).  The fp16 kernels have no tiles of the board: they find a
+row's board point with float reciprocals of N and P and take a halo of N + 1 rows, which depends on N as well.
+tests/test_trunk_probe.py::test_edge_defect_audit shows a lost corner point, one lost channel of it and a last row off by 1e-3
+at >= 16 e_ref at sizes of both overhang classes."""
 import functools
 
 import numpy as np
@@ -49,6 +81,18 @@ PROBE_CASES = ([(9, 1, f) for f in SMALL] + [(9, 2, f) for f in SMALL + ["f16"]]
                + [(19, 2, f) for f in ("winograd", "f33-dense", "direct", "f32s", "f16")])
 LIVE_CASES = ([(9, 10, f) for f in SMALL + ["f16"]] + [(13, 2, f) for f in ("winograd", "f33-dense", "direct", "f32s", "f16")]
               + [(19, 2, f) for f in ("winograd", "f33-dense", "direct", "f32s", "f16")])
+
+
+def forms_at(N):
+    """Every tower form a board size has.  The engine refuses none of them at any size: the setters check their argument's
+    range only, and the forward takes the form Net::tower_form() names -- persistent and five-pass exist up to 12 (whole-board
+    tile blocks; persistent on a 256-CU device, which every MI355X is), F(3x3,3x3) on dense blocks is a form of its own from 13."""
+    return SMALL + ["f16"] if N <= 12 else ["winograd", "f33-dense", "direct", "f32s", "f16"]
+
+
+SIZES = sorted(tp.SIZE_BATCH)          # every size from 3 to 18 that the cases above do not visit
+PROBE_CASES += [(N, 2, f) for N in SIZES for f in forms_at(N)]
+LIVE_CASES += [(N, 2, f) for N in SIZES for f in ("winograd", "direct", "f32s", "f16")]
 
 
 def _engine(N, tower, onet, form):

@@ -1,5 +1,6 @@
 """tests/trunk_probe.py on the CPU: the probe head reads the trunk exactly, `live_heads` gives networks whose heads see the
-tower, and the bar of tests/test_gpu_trunk.py is far below what a defect in a tower weight tensor does to the read-out."""
+tower, and the bar of tests/test_gpu_trunk.py is far below what a defect in a tower weight tensor, or in an activation at a
+board edge, does to the read-out."""
 import functools
 
 import numpy as np
@@ -131,3 +132,53 @@ def test_defect_audit(N, tower, which):
             assert moved >= 16 * e_ref, (name, moved, e_ref)
     finally:
         set_fn(layer, orc.K_WEIGHT, w0)
+
+
+def _edge_defects(N, c):
+    """name -> function on the first block's t [B, 256, i, j], in place.  What a tower kernel gets wrong at a board edge: a
+    tile that hangs over the edge and is cut one point short, one channel of it, a last row that comes from the wrong place."""
+    def corner(t):
+        t[1, :, N - 1, N - 1] = 0
+
+    def corner_channel(t):
+        t[1, c, N - 1, N - 1] = 0
+
+    def last_row(t):
+        t[1, :, N - 1, :] *= 1 - 1e-3
+
+    return {"board 1's corner point zeroed": corner, f"channel {c} of board 1's corner point zeroed": corner_channel,
+            "board 1's last row x (1 - 1e-3)": last_row}
+
+
+@pytest.mark.parametrize("N", [3, 4, 5, 8, 11, 14, 17])
+def test_edge_defect_audit(N):
+    """Sizes of both overhang classes (tests/test_gpu_trunk.py has the table), on the network, features and probes of the GPU
+    case.  An independent float64 trunk (torch) gives the oracle's probe read-out; then each defect at the board edge, put
+    into the first block's t of that trunk, moves the read-out by at least 16 e_ref, as the weight defects above do.  The
+    channel is a seeded draw among those alive at the corner point."""
+    tower = 2
+    onet, feats, ws, l64, e_ref, _ = _audit_reference(N, tower)
+    B, P = feats.shape[0], N * N
+    x_bcij = np.ascontiguousarray(feats.reshape(B, 17, N, N).transpose(0, 1, 3, 2), np.float64)
+    wt = torch.tensor(ws, dtype=torch.float64)
+
+    def read_out(defect=None):
+        def store(kind, blk, a):
+            if defect is not None and (kind, blk) == ("t", 0):
+                a = a.clone()
+                defect(a)
+            return a
+        return torch.einsum("kc,bcij->kbji", wt, torch_trunk(onet, tower, x_bcij, store=store)).reshape(len(ws), B, P).numpy()
+
+    seen = {}
+    read_out(lambda t: seen.update(t=t.clone()))
+    alive = np.flatnonzero(seen["t"][1, :, N - 1, N - 1].numpy() > 0)
+    assert alive.size >= 16, alive.size
+    c = int(alive[np.random.RandomState(1000 * N).randint(alive.size)])
+    clean = np.abs(read_out() - l64).max()
+    print(f"({N}, t{tower}) torch trunk against the oracle's probe: {clean:.1e}; {alive.size} channels alive at the corner")
+    assert clean < 1e-12, clean
+    for name, defect in _edge_defects(N, c).items():
+        moved = np.abs(read_out(defect) - l64).max()
+        print(f"({N}, t{tower}) first block's t, {name}: probe moves {moved:.2e} = {moved / e_ref:.0f} e_ref (e_ref {e_ref:.2e})")
+        assert moved >= 16 * e_ref, (name, moved, e_ref)
