@@ -294,6 +294,13 @@ class NodeView:
     child_W = property(lambda s: s._p.engine.node_floats(0, s.id, _lib.F_CHILD_W))
     child_prior = property(lambda s: s._p.engine.node_floats(0, s.id, _lib.F_CHILD_PRIOR))
     child_action_score = property(lambda s: s._p.engine.node_scores(0, s.id))
+    # (ours) value uncertainty, with the moments on (lcb= / puct_variance= or Engine.set_value_moments)
+    child_S = property(lambda s: s._p.engine.node_floats(0, s.id, _lib.F_CHILD_S))
+    child_stdev = property(lambda s: s._p.engine.tree_child_lcb(0, s.id, 0.0)[1])
+
+    def child_lcb(self, z):
+        """the lower confidence bounds of the children under z, from the side to move (agz_tree_child_lcb)"""
+        return self._p.engine.tree_child_lcb(0, self.id, z)[2]
 
     @property
     def child_Q(self):
@@ -461,7 +468,7 @@ class MCTSPlayer:
 
     def __init__(self, env, network, num_readouts=800, two_player_mode=False, resign_threshold=-0.9, seed=0,
                  game_id=0, symmetry=None, fpu=None, c_base=0.0, root_policy_temperature=None, root_noise=None,
-                 move_temperature=None):
+                 move_temperature=None, lcb=None, puct_variance=None):
         self.env = env
         self.network = network
         self.num_readouts = num_readouts
@@ -480,6 +487,7 @@ class MCTSPlayer:
                 raise ValueError("symmetry needs a NeuralNet of this package: a caller's network receives Positions")
             self.engine.set_symmetry(symmetry)
         _apply_puct(self.engine, fpu, c_base)      # (ours) the PUCT rule options of Engine.set_puct
+        _apply_uncertainty(self.engine, lcb, puct_variance)
         # (ours) root exploration in inject_noise and the move temperature in pick_move, as selfplay() takes them
         _apply_explore(self.engine, root_policy_temperature, root_noise, move_temperature)
         self._game_id = game_id
@@ -693,6 +701,20 @@ def _apply_puct(eng, fpu, c_base):
         eng.set_puct(fpu, c_base)
 
 
+def _apply_uncertainty(eng, lcb=None, puct_variance=None):
+    """(ours) value uncertainty on a fresh engine: lcb = z | (z, min_visits, min_ratio) -- the move is the child with the
+    largest lower confidence bound (Engine.set_lcb); puct_variance = k | (k, prior, weight) -- exploration scaled by the
+    spread of a node's values (Engine.set_puct_variance).  Either switches the value moments on; nothing asked for,
+    nothing set"""
+    if lcb is None and puct_variance is None:
+        return
+    eng.set_value_moments(True)
+    if lcb is not None:
+        eng.set_lcb(lcb)
+    if puct_variance is not None:
+        eng.set_puct_variance(puct_variance)
+
+
 def _apply_explore(eng, root_policy_temperature=None, root_noise=None, move_temperature=None):
     """root exploration and the move temperature (Engine.set_root_policy_temperature / set_root_noise /
     set_move_temperature) on a fresh engine; nothing asked for, nothing set"""
@@ -707,10 +729,11 @@ def _apply_explore(eng, root_policy_temperature=None, root_noise=None, move_temp
 
 def _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit, gumbel_c_scale,
                           targets_only_arena=False, fpu=None, c_base=0.0, root_policy_temperature=None, root_noise=None,
-                          move_temperature=None):
+                          move_temperature=None, lcb=None, puct_variance=None):
     """selfplay()'s and train()'s search options on a fresh engine (train(): a targets-only arena under the cap)"""
     _refuse_two_root_rules(gumbel, forced_playouts)
     _apply_puct(eng, fpu, c_base)
+    _apply_uncertainty(eng, lcb, puct_variance)
     _apply_explore(eng, root_policy_temperature, root_noise, move_temperature)
     if starts:
         eng.set_starts(starts)
@@ -732,7 +755,7 @@ def seed(s):
 def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="f32", game_id_base=None, symmetry=None,
              starts=None, playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
              gumbel_c_scale=1.0, fpu=None, c_base=0.0, root_policy_temperature=None, root_noise=None,
-             move_temperature=None, **cfg):
+             move_temperature=None, lcb=None, puct_variance=None, **cfg):
     """selfplay(env, nn, num_ro) (src/selfplay.jl:1-45) -> the finished game's player (SelfPlayPlayer), exactly the
     call train() makes (train.jl:57).  `games=G` (ours) plays G games concurrently on the device and returns a list of
     G such players ordered by game id.  Game ids continue from the previous call (module stream, `seed()`), unless
@@ -773,7 +796,7 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     if symmetry is not None:
         eng.set_symmetry(symmetry)
     _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit, gumbel_c_scale,
-                          fpu=fpu, c_base=c_base, root_policy_temperature=root_policy_temperature, root_noise=root_noise,
+                          fpu=fpu, c_base=c_base, lcb=lcb, puct_variance=puct_variance, root_policy_temperature=root_policy_temperature, root_noise=root_noise,
                           move_temperature=move_temperature)
     eng.start(games)
     while eng.records_count() < games:
@@ -799,6 +822,22 @@ Analysis = namedtuple("Analysis", "move N W Q child_N child_W child_Q prior stat
 Line = namedtuple("Line", "move N W Q prior pv pv_N end_Q")
 # a row of analyze() / review() with lines > 0: Analysis's fields, then the list of Line (at most `lines` of them)
 AnalysisLines = namedtuple("AnalysisLines", Analysis._fields + ("lines",))
+
+
+# a row of analyze() / review() with the value moments on (lcb= / puct_variance=): the same tuple, and beside it the
+# attributes child_S (the root's row of squared-value sums) and root_S (the root's own)
+class AnalysisS(Analysis):
+    pass
+
+
+class AnalysisLinesS(AnalysisLines):
+    pass
+
+
+def _with_S(row, child_S, root_S):
+    out = (AnalysisLinesS if isinstance(row, AnalysisLines) else AnalysisS)(*row)
+    out.child_S, out.root_S = child_S, root_S
+    return out
 
 
 def _check_lines(lines, pv_depth, pv_min_visits):
@@ -830,7 +869,7 @@ def _line_rows(env, t):
 
 def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=None, two_player_mode=False,
             symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, fpu=None, c_base=0.0,
-            move_temperature=None, **cfg):
+            move_temperature=None, lcb=None, puct_variance=None, **cfg):
     """suggest_move over many positions in one device run (ours).  Record i is what
     `MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + i, symmetry=symmetry)`,
     `initialize_game(positions[i])`, `suggest_move()` computes (mcts_play.jl:110-118,144-151), bit for bit, except that
@@ -877,6 +916,7 @@ def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=
         if symmetry is not None:
             eng.set_symmetry(symmetry)
         _apply_puct(eng, fpu, c_base)      # the PUCT rule options of Engine.set_puct, as MCTSPlayer(fpu=, c_base=)
+        _apply_uncertainty(eng, lcb, puct_variance)
         _apply_explore(eng, move_temperature=move_temperature)      # pick_move's, as MCTSPlayer(move_temperature=)
         if lines:
             eng.analyze_set_lines(lines, pv_depth, pv_min_visits)
@@ -888,6 +928,7 @@ def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=
                                                          "stall): raise max_nodes_per_game or use the default policy")
         r = eng.analyze_results()
         t = eng.analyze_lines() if lines else None
+        S = eng.analyze_child_S() if (lcb is not None or puct_variance is not None) else None
     finally:
         eng.close()
     out = []
@@ -896,7 +937,8 @@ def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=
         a = Analysis(None if r["move"][k] < 0 else from_flat(int(r["move"][k]), env), r["N"][k], r["W"][k],
                      r["Q"][k], cn, cw, cw / (np.float32(1) + cn), r["prior"][k], int(r["status"][k]),
                      int(r["nodes_used"][k]), int(game_id_base) + k)
-        out.append(AnalysisLines(*a, _line_rows(env, {f: v[k] for f, v in t.items()})) if lines else a)
+        a = AnalysisLines(*a, _line_rows(env, {f: v[k] for f, v in t.items()})) if lines else a
+        out.append(a if S is None else _with_S(a, S[0][k], S[1][k]))
     return out
 
 
@@ -938,7 +980,7 @@ def review_arrays(env, games):
 
 def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, seed=0, game_id_base=0, slots=None,
            symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, fpu=None, c_base=0.0,
-           move_temperature=None, **cfg):
+           move_temperature=None, lcb=None, puct_variance=None, **cfg):
     """Batched game review (ours; the loop of play(), src/play.jl:25-77, over recorded games): for game j, what
     `p = MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + j, symmetry=symmetry)`,
     `p.initialize_game(starts[j])`, then for every recorded move m_k `p.suggest_move()` and `p.play_move(m_k)` compute,
@@ -994,16 +1036,18 @@ def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, 
         if symmetry is not None:
             eng.set_symmetry(symmetry)
         _apply_puct(eng, fpu, c_base)      # the PUCT rule options of Engine.set_puct, as MCTSPlayer(fpu=, c_base=)
+        _apply_uncertainty(eng, lcb, puct_variance)
         _apply_explore(eng, move_temperature=move_temperature)      # pick_move's, as MCTSPlayer(move_temperature=)
         if lines:
             eng.analyze_set_lines(lines, pv_depth, pv_min_visits)
         eng.review_start(moves, off, boards, infos, hist, game_id_base)
-        return _review_rows(env, eng, off, [int(game_id_base) + j for j in range(G)], lines)
+        return _review_rows(env, eng, off, [int(game_id_base) + j for j in range(G)], lines,
+                            with_S=lcb is not None or puct_variance is not None)
     finally:
         eng.close()
 
 
-def _review_rows(env, eng, off, game_ids, lines):
+def _review_rows(env, eng, off, game_ids, lines, with_S=False):
     """The loop behind review() and reanalyze(): step the review run on `eng` until its off[-1] rows are finished, then
     read them as one list of Analysis (AnalysisLines with lines on) per game: game j's rows off[j] .. off[j + 1] - 1."""
     total = int(off[-1])
@@ -1014,6 +1058,7 @@ def _review_rows(env, eng, off, game_ids, lines):
                                                      "stall): raise max_nodes_per_game or use the default policy")
     r = eng.review_results()
     t = eng.analyze_lines() if lines else None
+    S = eng.analyze_child_S() if with_S else None
     out = []
     for j, gid in enumerate(game_ids):
         rows = []
@@ -1022,7 +1067,8 @@ def _review_rows(env, eng, off, game_ids, lines):
             a = Analysis(None if r["move"][i] < 0 else from_flat(int(r["move"][i]), env), r["N"][i], r["W"][i],
                          r["Q"][i], cn, cw, cw / (np.float32(1) + cn), r["prior"][i], int(r["status"][i]),
                          int(r["nodes_used"][i]), gid)
-            rows.append(AnalysisLines(*a, _line_rows(env, {f: v[i] for f, v in t.items()})) if lines else a)
+            a = AnalysisLines(*a, _line_rows(env, {f: v[i] for f, v in t.items()})) if lines else a
+            rows.append(a if S is None else _with_S(a, S[0][i], S[1][i]))
         out.append(rows)
     return out
 
@@ -1052,7 +1098,7 @@ EvalStats = namedtuple("EvalStats", "games_won num_games win_rate resigned moves
 
 
 def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, seed=0, slots=None,
-             return_stats=False, symmetry=None, starts=None, fpu=None, c_base=0.0, **cfg):
+             return_stats=False, symmetry=None, starts=None, fpu=None, c_base=0.0, lcb=None, puct_variance=None, **cfg):
     """evaluate(env, black_net, white_net; num_games, ro) (src/neural_net.jl:103-158): black_net plays
     Black and white_net White in `num_games` games of two two_player_mode MCTSPlayers (arg-max moves,
     no noise, resign at -0.9); True iff Black's win rate reaches 0.55.  All games run concurrently on
@@ -1075,6 +1121,7 @@ def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, se
     if symmetry is not None:
         eng.set_symmetry(symmetry)
     _apply_puct(eng, fpu, c_base)
+    _apply_uncertainty(eng, lcb, puct_variance)
     if starts:
         eng.set_starts(starts)
     eng.start(num_games)
@@ -1179,7 +1226,7 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
           augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, starts=None,
           playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
           gumbel_c_scale=1.0, value_target=None, fpu=None, c_base=0.0, surprise=0.0, root_policy_temperature=None,
-          root_noise=None, move_temperature=None, **cfg):
+          root_noise=None, move_temperature=None, lcb=None, puct_variance=None, **cfg):
     """train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model,
     start_training_after) (src/train.jl:38-92) with `slots` games in flight on the device.  One engine
     plays, keeps the replay arena and trains; per step: agz_selfplay_step(1), one read of how many games finished, and
@@ -1235,7 +1282,7 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
         z = torch.empty(batch_size, dtype=torch.float32, device=dev)
         cuts = _minibatch_cuts(batch_size)
         _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit,
-                              gumbel_c_scale, targets_only_arena=True, fpu=fpu, c_base=c_base,
+                              gumbel_c_scale, targets_only_arena=True, fpu=fpu, c_base=c_base, lcb=lcb, puct_variance=puct_variance,
                               root_policy_temperature=root_policy_temperature, root_noise=root_noise,
                               move_temperature=move_temperature)
         if value_target is not None:

@@ -397,6 +397,47 @@ agz_status agz_explore_temperature(int32_t n, double early, double late, double 
   *out = agz_temperature(n, early, late, halflife);
   return AGZ_OK;
 }
+// ---- value uncertainty (include/agz_uncertainty.h)
+agz_status agz_search_set_value_moments(agz_engine* e, int32_t on) {
+  return guard(e, [&](agz::Engine& E) { E.set_value_moments(on); });
+}
+agz_status agz_search_set_lcb(agz_engine* e, double z, int32_t min_visits, double min_ratio) {
+  return guard(e, [&](agz::Engine& E) { E.set_lcb(z, min_visits, min_ratio); });
+}
+agz_status agz_search_set_puct_variance(agz_engine* e, double k, double prior, double prior_weight) {
+  return guard(e, [&](agz::Engine& E) { E.set_puct_variance(k, prior, prior_weight); });
+}
+agz_status agz_search_uncertainty_counts(agz_engine* e, uint64_t* out) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+    E.uncertainty_counts(out);
+  });
+}
+agz_status agz_tree_child_lcb(agz_engine* e, int32_t g, int32_t node, double z, double* mean, double* sd, double* lcb) {
+  return guard(e, [&](agz::Engine& E) { E.tree_child_lcb(g, node, z, mean, sd, lcb); });
+}
+agz_status agz_tree_node_S(agz_engine* e, int32_t g, int32_t node, float* out) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+    *out = E.node_stat(g, node, 2);
+  });
+}
+agz_status agz_analyze_child_S(agz_engine* e, float* child_S, float* root_S) {
+  return guard(e, [&](agz::Engine& E) { E.analyze_child_S(child_S, root_S); });
+}
+agz_status agz_value_lcb(float n, float w, float s, int32_t to_play, double z, double* mean, double* sd, double* lcb) {
+  if (!mean || !sd || !lcb) return AGZ_BAD_ARGUMENT;
+  const agz_value_stats st = agz_child_stats(n, w, s);
+  *mean = st.mean;
+  *sd = st.sd;
+  *lcb = agz_stats_lcb(st, (float)to_play, z);
+  return AGZ_OK;
+}
+agz_status agz_puct_variance_factor(float n, float w, float s, double k, double prior, double prior_weight, double* out) {
+  if (!out) return AGZ_BAD_ARGUMENT;
+  *out = agz_variance_factor(n, w, s, k, prior, prior_weight);
+  return AGZ_OK;
+}
 agz_status agz_replay_set_targets_only(agz_engine* e, int32_t on) {
   return guard(e, [&](agz::Engine& E) { E.replay().set_targets_only(on != 0); });
 }

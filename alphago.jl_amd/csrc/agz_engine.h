@@ -69,6 +69,13 @@ class Engine {
   void set_move_temperature(int on, double early, double late, double halflife);
   void explore_counts(uint64_t out[4]);
   void tree_explore_rows(int g, int node, float* tempered, double* alpha, float* noised);
+  // value uncertainty (agz_search_set_value_moments / _set_lcb / _set_puct_variance): off by default
+  void set_value_moments(int on);
+  void set_lcb(double z, int min_visits, double min_ratio);
+  void set_puct_variance(double k, double prior, double prior_weight);
+  void uncertainty_counts(uint64_t out[4]);
+  void tree_child_lcb(int g, int node, double z, double* mean, double* sd, double* lcb);
+  void analyze_child_S(float* child_S, float* root_S);
   int64_t analyze_progress();
   void analyze_results(agz_analysis* out, float* child_N, float* child_W, float* prior);
   // analysis lines (agz_analyze_set_lines / agz_analyze_lines / agz_tree_lines): top-K candidates with their PVs
@@ -164,7 +171,7 @@ class Engine {
   void node_row_set(int g, int node, int field, const float* in);
   void node_children(int g, int node, int32_t* out);
   void node_board(int g, int node, int8_t* out);
-  float node_stat(int g, int node, int which);     // 0 = N, 1 = W
+  float node_stat(int g, int node, int which);     // 0 = N, 1 = W, 2 = S (moments on)
   void node_set_N(int g, int node, float v);
 
   std::string last_error;
@@ -236,6 +243,8 @@ class Engine {
   DevBuf<agz_position_info> an_info_;
   DevBuf<agz_analysis> an_res_;
   DevBuf<float> an_rows_;       // [3][B][A]: child_N, child_W, prior
+  DevBuf<float> an_s_;          // [B][A] child_S, then [B] root_S: a run begun with moments on (View::an_childS / an_rootS)
+  DevBuf<float> child_s_, root_s_;   // View::childS / rootS once agz_search_set_value_moments has switched them on
   int64_t an_count_ = 0;         // rows of the current run
   DevBuf<int16_t> rv_moves_;    // review mode: the recorded moves and game offsets (View::rv_*)
   DevBuf<int64_t> rv_off_;

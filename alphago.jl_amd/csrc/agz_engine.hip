@@ -242,6 +242,13 @@ __global__ __launch_bounds__(kWave) void k_tree_explore_rows(View V, int g, int 
   root_explore(w, V, S, g, node, row, tempered, alpha);
 }
 
+// agz_tree_child_lcb: child_lcb_rows of one node of single tree g under z, whatever the engine's setting of the rule;
+// out [3][A]: mean, sd, lcb
+__global__ __launch_bounds__(kWave) void k_tree_child_lcb(View V, int g, int node, double z, double* out) {
+  HipWave w;
+  child_lcb_rows(w, V, g, node, z, out, out + V.A, out + 2 * V.A);
+}
+
 __global__ __launch_bounds__(kWave) void k_go_play(View V, const int8_t* boards, const int8_t* tp, const int32_t* ko,
                                                     const int32_t* moves, int B, int8_t* bo, int32_t* ko_o,
                                                     int32_t* nc, int32_t* st) {
@@ -687,6 +694,73 @@ void Engine::set_move_temperature(int on, double early, double late, double half
              CT_EXP_TEMPERED, 4);
 }
 
+// ---- value uncertainty (agz_search_set_value_moments / _set_lcb / _set_puct_variance): every search of
+// every engine.  The range checks are *_refusal of agz_state.h, shared with the host simulator; every taken setter
+// restarts the four counters
+
+static_assert(CT_UNC_LCB_OFF_MAX == CT_UNC_LCB + 1 && CT_UNC_LEVELS == CT_UNC_LCB + 2 && CT_UNC_RAISED == CT_UNC_LCB + 3,
+              "the four counters are cleared and read as one run");
+void Engine::uncertainty_counts(uint64_t out[4]) { read_counters(CT_UNC_LCB, 4, out); }
+
+void Engine::set_value_moments(int on) {
+  check_explore("value moments", value_moments_refusal(V_, on));
+  // the state checks first (games in flight, a select phase awaiting its incorporate): a call they refuse allocates
+  // nothing.  Then the arrays, made the first time the option goes on (a row the size of childW's, and one float per
+  // slot); an allocation that fails throws here, with the option as it was
+  set_option("value moments", true, [](View&) {}, 0, 0);
+  if (on && !child_s_.p) {
+    const size_t n = (size_t)V_.games * V_.cap * V_.AP;
+    DevBuf<float> c, r;
+    c.alloc(n);
+    r.alloc((size_t)V_.games);
+    c.zero(stream_);
+    r.zero(stream_);
+    wait();
+    child_s_.swap(c);
+    root_s_.swap(r);
+  }
+  set_option("value moments", true, [&](View& V) {
+    V.childS = on ? child_s_.p : nullptr;
+    V.rootS = on ? root_s_.p : nullptr;
+  }, CT_UNC_LCB, 4);
+}
+
+void Engine::set_lcb(double z, int min_visits, double min_ratio) {
+  check_explore("lcb", lcb_refusal(V_, z, min_visits, min_ratio));
+  set_option("lcb", true, [&](View& V) { view_set_lcb(V, z, min_visits, min_ratio); }, CT_UNC_LCB, 4);
+}
+
+void Engine::set_puct_variance(double k, double prior, double prior_weight) {
+  check_explore("puct variance", puct_variance_refusal(V_, k, prior, prior_weight));
+  set_option("puct variance", true, [&](View& V) { view_set_puct_variance(V, k, prior, prior_weight); }, CT_UNC_LCB, 4);
+}
+
+void Engine::tree_child_lcb(int g, int node, double z, double* mean, double* sd, double* lcb) {
+  check_node(g, node);
+  AGZ_REQUIRE(mean && sd && lcb, AGZ_BAD_ARGUMENT, "null pointer");
+  AGZ_REQUIRE(V_.childS != nullptr, AGZ_BAD_ARGUMENT, "child lcb: the value moments are off");
+  AGZ_REQUIRE(z >= 0.0 && z <= 100.0, AGZ_BAD_ARGUMENT, "child lcb: z = %g, not in 0 .. 100", z);
+  const size_t A = (size_t)V_.A;
+  s_f64_.ensure(3 * A);
+  hipLaunchKernelGGL(k_tree_child_lcb, dim3(1), dim3(kWave), 0, stream_, V_, g, node, z, s_f64_.p);
+  AGZ_HIP(hipGetLastError());
+  down(mean, s_f64_.p, A);
+  down(sd, s_f64_.p + A, A);
+  down(lcb, s_f64_.p + 2 * A, A);
+  wait();
+}
+
+void Engine::analyze_child_S(float* child_S, float* root_S) {
+  AGZ_REQUIRE(child_S && root_S, AGZ_BAD_ARGUMENT, "null pointer");
+  const int64_t done = analyze_progress(), B = an_count_;
+  AGZ_REQUIRE(V_.an_childS != nullptr, AGZ_BAD_ARGUMENT, "analysis: the run began with the value moments off");
+  AGZ_REQUIRE(done >= B, AGZ_NOT_READY, "analysis: %lld of %lld rows finished", (long long)done, (long long)B);
+  const size_t rows = (size_t)B * V_.A;
+  down(child_S, V_.an_childS, rows);
+  down(root_S, V_.an_rootS, (size_t)B);
+  wait();
+}
+
 void Engine::tree_explore_rows(int g, int node, float* tempered, double* alpha, float* noised) {
   check_node(g, node);
   const size_t A = (size_t)V_.A, AP = (size_t)V_.AP;
@@ -831,6 +905,15 @@ void Engine::begin_analysis_run(int64_t B, int64_t rows, uint64_t game_id_base) 
   V_.an_childN = an_rows_.p;
   V_.an_childW = an_rows_.p + R * A;
   V_.an_prior = an_rows_.p + 2 * R * A;
+  // with the moments on, the root's S row and own S beside the three rows (agz_analyze_child_S)
+  V_.an_childS = nullptr;
+  V_.an_rootS = nullptr;
+  if (V_.childS) {
+    an_s_.ensure(R * A + R);
+    AGZ_HIP(hipMemsetAsync(an_s_.p, 0, sizeof(float) * (R * A + R), stream_));
+    V_.an_childS = an_s_.p;
+    V_.an_rootS = an_s_.p + R * A;
+  }
   V_.an_gid = nullptr;           // agz_replay_reanalyze_start sets the two behind this call
   V_.an_pi = nullptr;
   ra_on_ = false;
@@ -1885,17 +1968,22 @@ void Engine::node_meta_set(int g, int node, const NodeMeta& m) {
   put(V_.meta + node_index(V_, g, node), m);
 }
 static float* row_base(const View& V, int field) {
-  return field == AGZ_F_CHILD_N ? V.childN : field == AGZ_F_CHILD_W ? V.childW : V.childP;
+  return field == AGZ_F_CHILD_N ? V.childN : field == AGZ_F_CHILD_W ? V.childW : field == AGZ_F_CHILD_S ? V.childS : V.childP;
+}
+// the float rows a caller reads and writes: N, W, prior, and with the moments on S
+static void check_row_field(const View& V, int field) {
+  AGZ_REQUIRE((field >= 0 && field <= 2) || field == AGZ_F_CHILD_S, AGZ_BAD_ARGUMENT, "field %d", field);
+  AGZ_REQUIRE(field != AGZ_F_CHILD_S || V.childS != nullptr, AGZ_BAD_ARGUMENT, "field %d: the value moments are off", field);
 }
 void Engine::node_row_get(int g, int node, int field, float* out) {
   check_node(g, node);
-  AGZ_REQUIRE(field >= 0 && field <= 2, AGZ_BAD_ARGUMENT, "field %d", field);
+  check_row_field(V_, field);
   down(out, row_base(V_, field) + node_index(V_, g, node) * V_.AP, (size_t)V_.A);
   wait();
 }
 void Engine::node_row_set(int g, int node, int field, const float* in) {
   check_node(g, node);
-  AGZ_REQUIRE(field >= 0 && field <= 2, AGZ_BAD_ARGUMENT, "field %d", field);
+  check_row_field(V_, field);
   up(row_base(V_, field) + node_index(V_, g, node) * V_.AP, in, (size_t)V_.A);
   wait();
 }
@@ -1913,10 +2001,11 @@ float Engine::node_stat(int g, int node, int which) {
   NodeMeta m;
   node_meta(g, node, &m);
   const float* src;
+  AGZ_REQUIRE(which != 2 || V_.childS != nullptr, AGZ_BAD_ARGUMENT, "node S: the value moments are off");
   if (m.parent < 0) {
-    src = which == 0 ? &V_.gs[g].rootN : &V_.gs[g].rootW;
+    src = which == 2 ? &V_.rootS[g] : which == 0 ? &V_.gs[g].rootN : &V_.gs[g].rootW;
   } else {
-    src = (which == 0 ? V_.childN : V_.childW) + node_index(V_, g, m.parent) * V_.AP + m.fmove;
+    src = (which == 2 ? V_.childS : which == 0 ? V_.childN : V_.childW) + node_index(V_, g, m.parent) * V_.AP + m.fmove;
   }
   return fetch(src);
 }

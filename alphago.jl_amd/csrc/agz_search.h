@@ -31,6 +31,7 @@
 
 #include "../../include/agz_draws.h"
 #include "../../include/agz_explore.h"
+#include "../../include/agz_uncertainty.h"
 #include "agz_state.h"
 
 #if defined(__HIPCC__)
@@ -138,6 +139,12 @@ AGZ_FN float* slotN(const View& V, int g, int node) {
 AGZ_FN float* slotW(const View& V, int g, int node) {
   const NodeMeta& m = V.meta[node_index(V, g, node)];
   return m.parent < 0 ? &V.gs[g].rootW : &V.childW[node_index(V, g, m.parent) * V.AP + m.fmove];
+}
+
+// S(x), the sum of squared values beside W(x) (View::childS / rootS, agz_search_set_value_moments): only with moments on
+AGZ_FN float* slotS(const View& V, int g, int node) {
+  const NodeMeta& m = V.meta[node_index(V, g, node)];
+  return m.parent < 0 ? &V.rootS[g] : &V.childS[node_index(V, g, m.parent) * V.AP + m.fmove];
 }
 
 AGZ_FN bool node_is_done(const View& V, int g, int node) {
@@ -430,6 +437,7 @@ AGZ_FN void node_init_from_scratch(W& w, const View& V, Scratch& S, int g, int i
     V.childW[ni * V.AP + a] = 0.f;
     V.childP[ni * V.AP + a] = 0.f;
     V.child[ni * V.AP + a] = -1;
+    if (V.childS) V.childS[ni * V.AP + a] = 0.f;
   });
   w.for_each(V.P, [&](int p) { V.board[ni * V.PP + p] = S.sb[p]; });
   if (w.leader()) { V.meta[ni] = m; V.meta[ni].flags = (uint8_t)(m.flags | NF_ALLOC); }
@@ -537,6 +545,16 @@ AGZ_FN double puct_scale(const View& V, float n_node) {
   return V.c_puct * (double)sqrtf(one_plus_n);
 }
 
+// pv_k > 0 (agz_search_set_puct_variance): that scale times the variance factor of the node's own (n, W, S); the factor
+// goes out through `factor` when asked for
+AGZ_FN double puct_scale(const View& V, float n_node, float w_node, float s_node, double* factor = nullptr) {
+  const double scale = puct_scale(V, n_node);
+  if (!(V.pv_k > 0.0)) return scale;
+  const double f = agz_variance_factor(n_node, w_node, s_node, V.pv_k, V.pv_prior, V.pv_weight);
+  if (factor) *factor = f;
+  return scale * f;
+}
+
 // PUCT rule options (View::fpu_on / c_base, agz_search_set_puct): is either part on?
 AGZ_FN bool puct_rule_on(const View& V) { return V.fpu_on != 0 || V.c_base > 0.0; }
 
@@ -614,18 +632,23 @@ AGZ_FN int descend(W& w, const View& V, Scratch& S, int g, int from, int* plen_o
   const uint32_t sel = (uint32_t)G.sel;
   // the PUCT rule options (agz_search_set_puct): uniform branches on the View, so that off nothing below is new work
   const bool rule = puct_rule_on(V), fpu = V.fpu_on != 0;
+  // the variance factor (agz_search_set_puct_variance): uniform too; off, no S row is loaded
+  const bool pv = V.pv_k > 0.0;
   const int root = G.root;
   int cur = from, depth = 0, plen = 0;
   int levels = 0, unvisited = 0;                               // CT_PUCT_LEVELS / CT_PUCT_UNVISITED of this descent
+  int pv_levels = 0, pv_raised = 0;                            // CT_UNC_LEVELS / CT_UNC_RAISED of this descent
   w.sync();
   float* np = slotN(V, g, cur);
   float n_cur = *np;
   float w_cur = 0.f;                                           // the node's own W: its parent's row, like n_cur
-  if (fpu) w_cur = *slotW(V, g, cur);
+  float s_cur = 0.f;                                           // ... and its own S, under the variance factor
+  if (fpu || pv) w_cur = *slotW(V, g, cur);
+  if (pv) s_cur = *slotS(V, g, cur);
   for (;;) {
     const long ni = node_index(V, g, cur);
     const NodeMeta m = V.meta[ni];
-    float cn[R], cw[R], cp[R];
+    float cn[R], cw[R], cp[R], cs[R];
     int cc[R];
     bool lg[R];
 #pragma unroll
@@ -636,6 +659,7 @@ AGZ_FN int descend(W& w, const View& V, Scratch& S, int g, int from, int* plen_o
       cn[r] = V.childN[o];
       cw[r] = V.childW[o];
       cp[r] = V.childP[o];
+      cs[r] = pv ? V.childS[o] : 0.f;
       cc[r] = in ? V.child[o] : -1;
       lg[r] = a < A && legal_bit(V, ni, a);
     }
@@ -659,7 +683,9 @@ AGZ_FN int descend(W& w, const View& V, Scratch& S, int g, int from, int* plen_o
     } else if (given) {
       pick = root_pick;
     } else {
-      const double scale = puct_scale(V, n_new);
+      double factor = 1.0;
+      const double scale = pv ? puct_scale(V, n_new, w_cur, s_cur, &factor) : puct_scale(V, n_new);
+      if (pv) { pv_levels++; pv_raised += factor > 1.0; }
       const float tp = (float)m.to_play;
       double sc[R];
       double best = -1.0e300;
@@ -717,7 +743,8 @@ AGZ_FN int descend(W& w, const View& V, Scratch& S, int g, int from, int* plen_o
     for (int r = 0; r < R; ++r) { const int t = wave_shfl(w, cc[r], lane_of(pick)); if (r == row_of(pick)) nx = t; }
     const float n_next = row_f(cn, pick);
     if (scored) { levels++; unvisited += n_next == 0.0f; }
-    if (fpu) w_cur = row_f(cw, pick);
+    if (fpu || pv) w_cur = row_f(cw, pick);
+    if (pv) s_cur = row_f(cs, pick);
     if (nx < 0) nx = node_create_child(w, V, S, g, cur, pick, defer);
     if (nx < 0) break;   // pool exhausted: hand back the current node (flagged in the counters)
     np = &V.childN[ni * AP + pick];      // the child's own N lives in this row (slotN)
@@ -729,6 +756,10 @@ AGZ_FN int descend(W& w, const View& V, Scratch& S, int g, int from, int* plen_o
   if (rule) {
     w.count(&V.counters[CT_PUCT_LEVELS], (unsigned long long)levels);
     w.count(&V.counters[CT_PUCT_UNVISITED], (unsigned long long)unvisited);
+  }
+  if (pv) {
+    w.count(&V.counters[CT_UNC_LEVELS], (unsigned long long)pv_levels);
+    w.count(&V.counters[CT_UNC_RAISED], (unsigned long long)pv_raised);
   }
   w.sync();
   *plen_out = plen < V.maxd ? plen : V.maxd;
@@ -789,6 +820,7 @@ AGZ_FN void path_virtual_loss(W& w, const View& V, int g, const int32_t* path, i
     NodeMeta& m = V.meta[node_index(V, g, node)];
     float* wp = slotW(V, g, node);
     *wp = *wp + (float)(sign * m.to_play);
+    if (V.childS) { float* sp = slotS(V, g, node); *sp = *sp + (float)sign; }   // a virtual loss is a value of +-1
     m.losses = (int16_t)(m.losses + sign);
   });
   w.sync();
@@ -800,6 +832,7 @@ AGZ_FN void path_backup(W& w, const View& V, int g, const int32_t* path, int len
   w.for_each(len, [&](int i) {
     float* wp = slotW(V, g, path[i]);
     *wp = *wp + value;
+    if (V.childS) { float* sp = slotS(V, g, path[i]); const float sq = value * value; *sp = *sp + sq; }
   });
   w.sync();
 }
@@ -831,6 +864,7 @@ AGZ_FN int incorporate(W& w, const View& V, int g, int node, const float* probs,
   w.for_each(V.A, [&](int a) {
     V.childP[ni * V.AP + a] = probs[a];
     V.childW[ni * V.AP + a] = value;   // initialise child Q as the parent's value, mcts.jl:203-211
+    if (V.childS) V.childS[ni * V.AP + a] = value * value;
   });
   w.sync();
   path_backup(w, V, g, path, len, value);
@@ -1019,7 +1053,10 @@ AGZ_FN bool pruned_pi(W& w, const View& V, Scratch& S, long ni, float rootN, boo
   w.for_each(A, [&](int a) { if (cN[a] == mx && a < cs) cs = a; });
   cs = w.reduce_min(cs);
   const float tp = (float)V.meta[ni].to_play;
-  const double scale = puct_scale(V, rootN);
+  // (under the variance factor, with the node's own W and S: node ni is node ni % cap of slot ni / cap)
+  const int pg = (int)(ni / V.cap), pnode = (int)(ni % V.cap);
+  const double scale =
+      V.pv_k > 0.0 ? puct_scale(V, rootN, *slotW(V, pg, pnode), *slotS(V, pg, pnode)) : puct_scale(V, rootN);
   const float* cW = V.childW + ni * V.AP;
   const float* cP = V.childP + ni * V.AP;
   const double s_star = action_score(cN[cs], cW[cs], cP[cs], tp, scale);
@@ -1055,6 +1092,22 @@ AGZ_FN bool pruned_pi(W& w, const View& V, Scratch& S, long ni, float rootN, boo
   return changed;
 }
 
+// The value statistics of a node's children under z (agz_tree_child_lcb; include/agz_uncertainty.h rules 1 and 2), from the
+// node's side to move, whatever the setting of the LCB rule: mean, sd and lcb [A] each.  Needs the moments on.
+template <class W>
+AGZ_FN void child_lcb_rows(W& w, const View& V, int g, int node, double z, double* mean, double* sd, double* lcb) {
+  const long ni = node_index(V, g, node);
+  const float tp = (float)V.meta[ni].to_play;
+  w.for_each(V.A, [&](int a) {
+    const long o = ni * V.AP + a;
+    const agz_value_stats st = agz_child_stats(V.childN[o], V.childW[o], V.childS[o]);
+    mean[a] = st.mean;
+    sd[a] = st.sd;
+    lcb[a] = agz_stats_lcb(st, tp, z);
+  });
+  w.sync();
+}
+
 // pick_move (mcts_play.jl:52-71).  Returns AGZ_OK / AGZ_ASSERT_SOFTPICK.
 template <class W>
 AGZ_FN int pick_move(W& w, const View& V, Scratch& S, int g, int* a_out) {
@@ -1069,6 +1122,40 @@ AGZ_FN int pick_move(W& w, const View& V, Scratch& S, int g, int* a_out) {
     float mx = -1.0f;
     w.for_each(A, [&](int a) { const float c = V.childN[ni * V.AP + a]; mx = c > mx ? c : mx; });
     mx = w.reduce_max_f(mx);
+    // the LCB rule (agz_search_set_lcb): among the children with enough visits the largest lower confidence bound,
+    // ties to the larger N, then to the lower action; no draw.  Below min_visits at the top, today's branch
+    if (V.lcb_z > 0.0 && !(mx < (float)V.lcb_min_visits)) {
+      const float tp = (float)V.meta[ni].to_play;
+      const double floor_n = V.lcb_min_ratio * (double)mx;
+      double best = -1.0e300;
+      w.for_each(V.AP, [&](int a) {
+        const long o = ni * V.AP + a;
+        const float c = a < A ? V.childN[o] : -1.0f;
+        const bool el = a < A && c >= (float)V.lcb_min_visits && (double)c >= floor_n;
+        S.flag[a] = el;
+        if (!el) return;
+        const double l = agz_child_lcb(c, V.childW[o], V.childS[o], tp, V.lcb_z);
+        S.dbuf[a] = l;
+        if (l > best) best = l;
+      });
+      best = w.reduce_max(best);
+      w.sync();
+      float bn = -1.0f;
+      w.for_each(A, [&](int a) {
+        if (S.flag[a] && S.dbuf[a] == best) { const float c = V.childN[ni * V.AP + a]; bn = c > bn ? c : bn; }
+      });
+      bn = w.reduce_max_f(bn);
+      int pick = kIntMax;
+      w.for_each(A, [&](int a) {
+        if (S.flag[a] && S.dbuf[a] == best && V.childN[ni * V.AP + a] == bn && a < pick) pick = a;
+      });
+      pick = w.reduce_min(pick);
+      w.sync();
+      w.count(&V.counters[CT_UNC_LCB], 1);
+      w.count(&V.counters[CT_UNC_LCB_OFF_MAX], bn != mx ? 1 : 0);
+      *a_out = pick;
+      return AGZ_OK;
+    }
     int cnt = 0, idx = kIntMax;
     w.for_each(V.AP, [&](int a) {
       const bool f = a < A && V.childN[ni * V.AP + a] == mx;
@@ -1160,11 +1247,13 @@ AGZ_FN void reroot(W& w, const View& V, Scratch& S, int g, int a, int child) {
   const int old_root = G.root;
   const long oi = node_index(V, g, old_root);
   const float cn = V.childN[oi * V.AP + a], cw = V.childW[oi * V.AP + a];
+  const float cs = V.childS ? V.childS[oi * V.AP + a] : 0.f;
   push_history(w, V, g, oi);
   discard_except(w, V, g, old_root, a);
   if (w.leader()) {
     G.rootN = cn;
     G.rootW = cw;
+    if (V.childS) V.rootS[g] = cs;
     G.root = child;
     G.sel = 0;
     NodeMeta& cm = V.meta[node_index(V, g, child)];
@@ -1229,7 +1318,7 @@ AGZ_FN void game_start(W& w, const View& V, Scratch& S, int g, uint64_t game_id,
       const int ch = node_create_child(w, V, S, g, G.root, a);
       if (ch < 0) break;
       reroot(w, V, S, g, a, ch);
-      if (w.leader()) { G.rootN = 0.f; G.rootW = 0.f; }
+      if (w.leader()) { G.rootN = 0.f; G.rootW = 0.f; if (V.childS) V.rootS[g] = 0.f; }
       w.sync();
     }
   }
@@ -1273,6 +1362,7 @@ AGZ_FN bool root_install(W& w, const View& V, Scratch& S, int g, const int8_t* b
   w.sync();
   if (w.leader()) {
     G.rootN = 0.f; G.rootW = 0.f; G.target = 0.f; G.komi = info.komi;
+    if (V.childS) V.rootS[g] = 0.f;
     G.sel = 0; G.move_count = 0; G.nqs = 0; G.hist_len = info.history_len;
     G.free_top = V.cap; G.garbage = 0; G.nleaves = 0; G.err = 0; G.result = 0; G.was_resign = 0; G.nodes_used = 0;
     G.short_searches = 0;
@@ -2118,7 +2208,9 @@ AGZ_FN void analysis_finish(W& w, const View& V, Scratch& S, int g) {
     V.an_childN[i * A + k] = V.childN[ri * V.AP + k];
     V.an_childW[i * A + k] = V.childW[ri * V.AP + k];
     V.an_prior[i * A + k] = V.childP[ri * V.AP + k];
+    if (V.an_childS) V.an_childS[i * A + k] = V.childS[ri * V.AP + k];
   });
+  if (V.an_childS && w.leader()) V.an_rootS[i] = V.rootS[g];
   // reanalysis: the pi row the self-play move phase records at this root, under the same squash rule
   if (V.an_pi) children_as_pi(w, V, S, ri, V.meta[ri].n <= V.tau, V.an_pi + i * A);
   if (V.an_lines > 0) {                                 // (review mode: before review_play re-roots)
@@ -2561,7 +2653,8 @@ AGZ_FN void tree_op(W& w, const View& V, Scratch& S, const TreeArgs& T) {
       const long ni = node_index(V, g, T.node);
       const NodeMeta m = V.meta[ni];
       const float n_s = *slotN(V, g, T.node), tp = (float)m.to_play;
-      const double scale = puct_scale(V, n_s);
+      const double scale =
+          V.pv_k > 0.0 ? puct_scale(V, n_s, *slotW(V, g, T.node), *slotS(V, g, T.node)) : puct_scale(V, n_s);
       float f = 0.f;
       if (V.fpu_on) {
         long long M = 0;

@@ -121,7 +121,12 @@ constexpr int CT_PUCT_LEVELS = CT_COUNT + 2, CT_PUCT_UNVISITED = CT_COUNT + 3;
 // not a most-visited child.  The four slots after the PUCT ones, outside the enum for the same reason.
 constexpr int CT_EXP_TEMPERED = CT_COUNT + 4, CT_EXP_NOISED = CT_COUNT + 5, CT_EXP_SAMPLED = CT_COUNT + 6,
               CT_EXP_OFF_MAX = CT_COUNT + 7;
-constexpr int kCounterSlots = CT_COUNT + 8;     // what View::counters holds
+// Value uncertainty (agz_search.h pick_move / descend): moves picked under the LCB rule / those of them not
+// on a most-visited child / tree levels a descent scored under a variance factor / those of them with factor > 1.  The
+// four slots after the exploration ones, outside the enum for the same reason.
+constexpr int CT_UNC_LCB = CT_COUNT + 8, CT_UNC_LCB_OFF_MAX = CT_COUNT + 9, CT_UNC_LEVELS = CT_COUNT + 10,
+              CT_UNC_RAISED = CT_COUNT + 11;
+constexpr int kCounterSlots = CT_COUNT + 12;    // what View::counters holds
 
 struct View {
   // dimensions
@@ -252,6 +257,19 @@ struct View {
   double pt_early, pt_late, pt_half;
   double mt_early, mt_late, mt_half;
   double noise_total;
+  // Value uncertainty (agz_search_set_value_moments / _set_lcb / _set_puct_variance; zero = off, the View{} of the host
+  // simulator and of fill_dims; include/agz_uncertainty.h states the arithmetic).  childS: the sum of
+  // squared values beside every childW entry, rootS the root's own beside GameState::rootW (a side table: tests/hs.py
+  // mirrors GameState); NULL = no moments are kept.  lcb_z > 0: the arg-max branch of pick_move takes the largest
+  // lower confidence bound among the children with N_a >= lcb_min_visits and N_a >= lcb_min_ratio * max N.  pv_k > 0:
+  // puct_scale is multiplied by the variance factor of the node's own (n, W, S)
+  float* childS;                      // [games*cap][AP]
+  float* rootS;                       // [games]
+  double lcb_z, lcb_min_ratio;
+  int32_t lcb_min_visits;
+  double pv_k, pv_prior, pv_weight;
+  float* an_childS;                   // [rows][A]: the root's S row of an analysis / review run begun with moments on
+  float* an_rootS;                    // [rows]
 };
 
 // option values -> View fields, for the engine's setters (which check the arguments first) and the host simulator's
@@ -302,6 +320,36 @@ inline void view_set_root_policy_temperature(View& V, int on, double early, doub
 inline void view_set_root_noise(View& V, double total_alpha, int shaped) {
   V.noise_total = total_alpha > 0.0 ? total_alpha : 0.0;
   V.noise_shaped = (total_alpha > 0.0 && shaped) ? 1 : 0;
+}
+// value uncertainty: the argument checks of the two rules (the moments' pointers are the caller's) and their stores
+inline const char* lcb_refusal(const View& V, double z, int min_visits, double min_ratio) {
+  if (!(z >= 0.0 && z <= 100.0)) return "z is not in 0 (off) .. 100";
+  if (min_visits < 1) return "min_visits is not >= 1";
+  if (!(min_ratio >= 0.0 && min_ratio <= 1.0)) return "min_ratio is not in [0, 1]";
+  if (z > 0.0 && !V.childS) return "the value moments are off";
+  return nullptr;
+}
+inline const char* puct_variance_refusal(const View& V, double k, double prior, double prior_weight) {
+  if (!(k >= 0.0 && k < 1.0)) return "k is not in [0, 1)";
+  if (!(prior >= 0.01 && prior <= 2.0)) return "prior is not in [0.01, 2]";
+  if (!(prior_weight >= 0.0 && prior_weight <= 1000.0)) return "prior_weight is not in [0, 1000]";
+  if (k > 0.0 && !V.childS) return "the value moments are off";
+  return nullptr;
+}
+inline const char* value_moments_refusal(const View& V, int on) {
+  if (on != 0 && on != 1) return "on is not 0 or 1";
+  if (!on && (V.lcb_z > 0.0 || V.pv_k > 0.0)) return "a rule that reads the moments is on";
+  return nullptr;
+}
+inline void view_set_lcb(View& V, double z, int min_visits, double min_ratio) {
+  V.lcb_z = z > 0.0 ? z : 0.0;
+  V.lcb_min_visits = z > 0.0 ? min_visits : 0;
+  V.lcb_min_ratio = z > 0.0 ? min_ratio : 0.0;
+}
+inline void view_set_puct_variance(View& V, double k, double prior, double prior_weight) {
+  V.pv_k = k > 0.0 ? k : 0.0;
+  V.pv_prior = k > 0.0 ? prior : 0.0;
+  V.pv_weight = k > 0.0 ? prior_weight : 0.0;
 }
 inline void view_set_move_temperature(View& V, int on, double early, double late, double halflife) {
   V.mt_on = on ? 1 : 0;

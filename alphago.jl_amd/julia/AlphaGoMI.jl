@@ -970,6 +970,69 @@ function explore_temperature(n::Integer, early::Real, late::Real, halflife::Real
   ccall((:agz_explore_temperature, libagz), Int32, (Int32, Float64, Float64, Float64, Ref{Float64}), n, early, late, halflife, out)
   out[]
 end
+# Value uncertainty (ours; include/agz.h agz_search_set_value_moments and what follows it, DESIGN.md 5w).  Moments: a sum
+# of squared values S beside every W.  lcb = nothing (off), z, or (z, min_visits, min_ratio): the arg-max branch of pick_move
+# takes the largest lower confidence bound among the well-visited children.  puct_variance = nothing (off), k, or (k,
+# prior, prior_weight): the PUCT scale times 1 + k * (sd / prior - 1) of the node's own values.
+function set_value_moments!(e::Engine, on::Bool = true)
+  check(e, ccall((:agz_search_set_value_moments, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, on ? 1 : 0))
+end
+function set_lcb!(e::Engine, lcb = nothing)
+  z, mv, ratio = lcb === nothing ? (0.0, 1, 0.0) : lcb isa Tuple ? (lcb[1], lcb[2], lcb[3]) : (lcb, 1, 0.0)
+  check(e, ccall((:agz_search_set_lcb, libagz), Int32, (Ptr{Cvoid}, Float64, Int32, Float64), e.handle, z, mv, ratio))
+end
+function set_puct_variance!(e::Engine, pv = nothing)
+  k, prior, weight = pv === nothing ? (0.0, 0.4, 2.0) : pv isa Tuple ? (pv[1], pv[2], pv[3]) : (pv, 0.4, 2.0)
+  check(e, ccall((:agz_search_set_puct_variance, libagz), Int32, (Ptr{Cvoid}, Float64, Float64, Float64), e.handle, k, prior,
+                 weight))
+end
+# (moves picked under the LCB rule, those off the most visited child, levels scored under a variance factor, those with
+# factor > 1) since the later of a setter call and agz_selfplay_start
+function uncertainty_counts(e::Engine)
+  out = zeros(UInt64, 4)
+  check(e, ccall((:agz_search_uncertainty_counts, libagz), Int32, (Ptr{Cvoid}, Ptr{UInt64}), e.handle, out))
+  Tuple(Int.(out))
+end
+# (mean, sd, lcb) of the children of `node` of single tree g under z, from the node's side to move
+function child_lcb(e::Engine, g::Integer, node::Integer, z::Real, A::Integer)
+  m, sd, l = zeros(Float64, A), zeros(Float64, A), zeros(Float64, A)
+  check(e, ccall((:agz_tree_child_lcb, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                 e.handle, g, node, z, m, sd, l))
+  m, sd, l
+end
+function node_S(e::Engine, g::Integer, node::Integer)
+  out = Ref{Float32}(0.0f0)
+  check(e, ccall((:agz_tree_node_S, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Ref{Float32}), e.handle, g, node, out))
+  out[]
+end
+# (child_S [A, rows], root_S [rows]) of the analysis / review run, which began with moments on
+function analyze_child_S(e::Engine, rows::Integer, A::Integer)
+  cs, rs = zeros(Float32, A, rows), zeros(Float32, rows)
+  check(e, ccall((:agz_analyze_child_S, libagz), Int32, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}), e.handle, cs, rs))
+  cs, rs
+end
+function value_lcb(n::Real, w::Real, s::Real, to_play::Integer, z::Real)
+  m, sd, l = Ref{Float64}(0.0), Ref{Float64}(0.0), Ref{Float64}(0.0)
+  ccall((:agz_value_lcb, libagz), Int32, (Float32, Float32, Float32, Int32, Float64, Ref{Float64}, Ref{Float64}, Ref{Float64}),
+        n, w, s, to_play, z, m, sd, l)
+  m[], sd[], l[]
+end
+function puct_variance_factor(n::Real, w::Real, s::Real, k::Real, prior::Real, weight::Real)
+  out = Ref{Float64}(0.0)
+  ccall((:agz_puct_variance_factor, libagz), Int32, (Float32, Float32, Float32, Float64, Float64, Float64, Ref{Float64}),
+        n, w, s, k, prior, weight, out)
+  out[]
+end
+# the keywords lcb = / puct_variance = of selfplay, train, analyze, review, evaluate and MCTSPlayer: either switches the
+# moments on; nothing asked, nothing set
+function apply_uncertainty!(e::Engine, lcb, puct_variance)
+  (lcb === nothing && puct_variance === nothing) && return nothing
+  set_value_moments!(e, true)
+  lcb === nothing || set_lcb!(e, lcb)
+  puct_variance === nothing || set_puct_variance!(e, puct_variance)
+  nothing
+end
+
 # the keywords root_policy_temperature = / root_noise = (total_alpha, shaped) / move_temperature = of selfplay, train and
 # MCTSPlayer (analyze and review take move_temperature): nothing asked, nothing set
 function apply_explore!(e::Engine, root_policy_temperature, root_noise, move_temperature)

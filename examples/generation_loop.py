@@ -3,7 +3,7 @@
 self-play -> replay arena -> training batches -> optimiser step -> arena match -> checkpoint.
 
     python examples/generation_loop.py [--board 9] [--tower 2] [--games 32] [--readouts 64] [--reanalyze]
-                                       [--surprise RHO] [--explore]
+                                       [--surprise RHO] [--explore] [--uncertainty]
 
 What runs where:
   selfplay          G concurrent games on the device (one wave per tree, one network batch per step)
@@ -14,6 +14,11 @@ What runs where:
                     Dirichlet noise of total concentration 10.83 over the legal moves, the move sampled at temperature
                     0.75 -> 0.15, each with a halflife of the board size (agz_selfplay_set_root_policy_temperature /
                     _set_root_noise, agz_search_set_move_temperature)
+  uncertainty       (--uncertainty) value uncertainty in self-play and in the arena match: a second moment beside every W,
+                    the move picked by the lower confidence bound (z = 5 among the children with at least 0.15 of the top
+                    visits) and the PUCT scale times 1 + 0.85 (sd / 0.4 - 1) of a node's own values, the expected spread
+                    0.4 weighing 2 visits (agz_search_set_value_moments / _set_lcb / _set_puct_variance); values of the
+                    kind KataGo ships, quoted from memory
   reanalyze         (--reanalyze) the arena's games are searched again on the current weights and their pi / q
                     targets overwritten in place, moves and results as played (agz_replay_reanalyze_start / _commit)
   surprise          (--surprise RHO) every arena ply is scored by KL(pi || prior) on the current weights and the batches
@@ -49,6 +54,8 @@ def main(argv=None):
                          "sampling mass in proportion to KL(pi || prior)")
     ap.add_argument("--explore", action="store_true",
                     help="KataGo's root policy temperature, shaped root noise and move temperature in self-play")
+    ap.add_argument("--uncertainty", action="store_true",
+                    help="value moments, the move by lower confidence bound and variance-scaled exploration")
     args = ap.parse_args(argv)
 
     env = ag.GoEnv(args.board)
@@ -59,7 +66,9 @@ def main(argv=None):
     if args.explore:        # KataGo's values; the halflife of both schedules is the board size
         explore = dict(root_policy_temperature=(1.25, 1.1, args.board), root_noise=(10.83, True),
                        move_temperature=(0.75, 0.15, args.board))
-    records = ag.selfplay(env, cur, args.readouts, games=args.games, seed=1, **explore)
+    # values of the kind KataGo ships (no strength claim: there is no trained network here)
+    uncertainty = dict(lcb=(5.0, 1, 0.15), puct_variance=(0.85, 0.4, 2.0)) if args.uncertainty else {}
+    records = ag.selfplay(env, cur, args.readouts, games=args.games, seed=1, **explore, **uncertainty)
     buf = ag.ReplayBuffer(env, memory_size=500000)
     buf.extend(records)
     print(f"self-play: {len(records)} games, {len(buf)} positions, "
@@ -102,7 +111,8 @@ def main(argv=None):
         eng.copy_weights_to(cur.engine)
         eng.close()
 
-    ok, st = ag.evaluate(env, cur, prev, num_games=args.eval_games, ro=args.readouts, seed=2, return_stats=True)
+    ok, st = ag.evaluate(env, cur, prev, num_games=args.eval_games, ro=args.readouts, seed=2, return_stats=True,
+                         **uncertainty)
     print(f"evaluate: Black (candidate) won {st.games_won}/{st.num_games} -> {'keep' if ok else 'revert'}")
 
     with tempfile.TemporaryDirectory() as d:

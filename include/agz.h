@@ -572,6 +572,7 @@ agz_status agz_tree_node_info(agz_engine* e, int32_t g, int32_t node, agz_node_i
 #define AGZ_F_CHILD_W 1
 #define AGZ_F_CHILD_PRIOR 2
 #define AGZ_F_ACTION_SCORE 3     /* Float64 scores narrowed to double[A] */
+#define AGZ_F_CHILD_S 4          /* the sums of squared values; needs agz_search_set_value_moments on */
 agz_status agz_tree_node_floats(agz_engine* e, int32_t g, int32_t node, int32_t field, float* out);
 agz_status agz_tree_node_scores(agz_engine* e, int32_t g, int32_t node, double* out);
 agz_status agz_tree_node_set_floats(agz_engine* e, int32_t g, int32_t node, int32_t field, const float* in);
@@ -822,6 +823,60 @@ agz_status agz_search_explore_counts(agz_engine* e, uint64_t* out /* [4] */);
 agz_status agz_tree_explore_rows(agz_engine* e, int32_t g, int32_t node, float* tempered, double* alpha, float* noised);
 /* *out = T(n) of the schedule above; host only, needs no engine.  AGZ_BAD_ARGUMENT: out is NULL. */
 agz_status agz_explore_temperature(int32_t n, double early, double late, double halflife, double* out);
+/* Value uncertainty (ours; the arithmetic is include/agz_uncertainty.h): a second moment S beside every W,
+ * the move picked by a lower confidence bound (Leela Zero, KataGo), and exploration scaled by the spread of the values
+ * seen below a node (KataGo).  All three are off by default, and off is the engine as it was, bit for bit.
+ * Everything is Float64, every multiply, add and divide rounded on its own, unless cast.
+ *   1. agz_search_set_value_moments(on).  With moments on every store to a W has its S store beside it: 0 where W is
+ *      zeroed; value * value (one Float32 product) in every child entry at a node's first expansion; S = S + (value *
+ *      value) in Float32 along a backed-up path; S = S + (float)sign along a path of virtual losses (a virtual loss is
+ *      a value of +-1); the child's entry into the root's own S at a re-root.  The arrays (a row the size of child_W's,
+ *      one float per slot) are allocated the first time the option goes on; an allocation that fails refuses the call
+ *      with the option off.  Moments cover trees begun after the call.  Moments alone observe: every record, row,
+ *      counter and move is what it is with moments off.
+ *      CHILD STATISTICS of a row entry (N_a, W_a, S_a): cnt = (double)(1.0f + N_a), mean = (double)W_a / cnt,
+ *      m2 = (double)S_a / cnt, var = m2 - mean*mean, 0 unless var > 0, sd = agz_sqrt(var).  cnt counts the parent's value
+ *      that the first expansion puts into W_a and S_a.
+ *   2. agz_search_set_lcb(z, min_visits, min_ratio), z = 0 off: in the arg-max branch of pick_move only (two_player_mode,
+ *      n >= tau, a move temperature T <= 0.01).  mx = max child_N.  mx < min_visits: that branch as it is, tie draw
+ *      included.  Otherwise a is eligible iff N_a >= min_visits and (double)N_a >= min_ratio * (double)mx, and the pick
+ *      is the largest  lcb = (mean * (double)tp) - (z * agz_sqrt(var / cnt)),  tp the root's to_play; ties to the larger
+ *      N, then to the lower action; no draw is made.  The soft pick, the sampling branch of the move temperature, the
+ *      Gumbel move, the recorded pi row, q, the resign check, re-rooting and the pool rules do not change.  Applies to
+ *      every pick_move: self-play, the arena (both players), analysis, review, reanalysis, agz_tree_pick_move.
+ *   3. agz_search_set_puct_variance(k, prior, prior_weight), k = 0 off: `scale` of the PUCT rule (agz_search_set_puct)
+ *      is multiplied by the factor of the node's own stored (n, W_s, S_s), n as the scale itself receives it:
+ *      cnt = (double)(1.0f + n), mean = (double)W_s / cnt, m2 = (double)S_s / cnt, pw = prior_weight,
+ *      var = ((((mean*mean) + (prior*prior)) * pw) + (m2 * cnt)) / (pw + cnt) - (mean*mean), 0 unless var > 0,
+ *      factor = 1.0 + k * ((agz_sqrt(var) / prior) - 1.0).  At every level of every descent, in the scale of the pruned
+ *      policy target (the root's own n, W and S) and in agz_tree_node_scores.  It composes with the FPU, c_base, the forced
+ *      rule and the Gumbel root search as agz_search_set_puct does.
+ * No draw site is added or moved; records, agz_game_header, agz_config and agz_stats do not change.
+ * The setters synchronise and restart the counters of agz_search_uncertainty_counts.  Refused (AGZ_BAD_ARGUMENT, the
+ * setting in force kept): `on` outside {0, 1}; z NaN, negative or above 100; min_visits < 1; min_ratio outside [0, 1];
+ * k outside [0, 1); prior outside [0.01, 2]; prior_weight outside [0, 1000]; either rule while moments are off; moments
+ * switched off while a rule is on; games of a run still being played; between agz_tree_search_select and
+ * agz_tree_search_incorporate.  An arena_mode engine takes all three. */
+agz_status agz_search_set_value_moments(agz_engine* e, int32_t on);
+agz_status agz_search_set_lcb(agz_engine* e, double z, int32_t min_visits, double min_ratio);
+agz_status agz_search_set_puct_variance(agz_engine* e, double k, double prior, double prior_weight);
+/* out[0] = moves picked under the LCB rule, out[1] = those of them not on a most-visited child, out[2] = tree levels a
+ * descent scored under a variance factor, out[3] = those of them with factor > 1; since the later of a setter call and
+ * agz_selfplay_start.  Synchronises. */
+agz_status agz_search_uncertainty_counts(agz_engine* e, uint64_t* out /* [4] */);
+/* the child statistics of `node` of single tree g and their lower confidence bounds under the z given here (0 <= z <=
+ * 100), from the node's side to move, whatever the setting of rule 2: mean, sd, lcb double[A] each.  Needs moments on.
+ * One small kernel; synchronises. */
+agz_status agz_tree_child_lcb(agz_engine* e, int32_t g, int32_t node, double z, double* mean, double* sd, double* lcb);
+/* a node's own S (the root's: the slot's side entry); needs moments on */
+agz_status agz_tree_node_S(agz_engine* e, int32_t g, int32_t node, float* out);
+/* child_S [B][A] and root_S [B] of the analysis / review run, filled beside the three rows of agz_analyze_results.
+ * AGZ_BAD_ARGUMENT when the run began with moments off. */
+agz_status agz_analyze_child_S(agz_engine* e, float* child_S, float* root_S);
+/* rules 1 and 2 on one entry (n, w, s) seen by to_play = +-1, and the factor of rule 3; host only, need no engine.
+ * AGZ_BAD_ARGUMENT: an output is NULL. */
+agz_status agz_value_lcb(float n, float w, float s, int32_t to_play, double z, double* mean, double* sd, double* lcb);
+agz_status agz_puct_variance_factor(float n, float w, float s, double k, double prior, double prior_weight, double* out);
 agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out);
 /* out[B], child_N / child_W / prior [B][A] (the root's rows when the search ended); any of them may be NULL */
 agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N, float* child_W, float* prior);
