@@ -13,6 +13,7 @@ BAD_ARGUMENT, HIP_ERROR, POOL_EXHAUSTED, RCCL_ERROR, NOT_READY = 6, 7, 8, 9, 10
 L_VALUE_CONV, L_POLICY_CONV, L_VALUE_FC1, L_VALUE_FC2, L_POLICY_FC = -1, -2, -3, -4, -5
 K_WEIGHT, K_BIAS, K_BN_BETA, K_BN_GAMMA, K_BN_MEAN, K_BN_VAR, K_BN_EPS = range(7)
 F_CHILD_N, F_CHILD_W, F_CHILD_PRIOR = 0, 1, 2
+KO_RULES = {"simple": 0, "positional": 1, "situational": 2}      # AGZ_KO_* of include/agz_superko.h
 F_CHILD_S = 4                # (3 is the action scores, doubles: agz_tree_node_scores)
 
 
@@ -177,6 +178,13 @@ def load():
         "agz_search_explore_counts": (i32, [E, P(u64)]),
         "agz_tree_explore_rows": (i32, [E, i32, i32, f32p, f64p, f32p]),
         "agz_explore_temperature": (i32, [i32, C.c_double, C.c_double, C.c_double, f64p]),
+        "agz_search_set_ko_rule": (i32, [E, i32]),
+        "agz_search_superko_counts": (i32, [E, P(u64)]),
+        "agz_tree_node_key": (i32, [E, i32, i32, P(u64)]),
+        "agz_tree_node_legal": (i32, [E, i32, i32, P(C.c_int8)]),
+        "agz_go_keys": (i32, [E, P(C.c_int8), P(C.c_int8), i32, i32, P(u64)]),
+        "agz_go_legal_seen": (i32, [E, P(C.c_int8), P(C.c_int8), P(i32), P(u64), P(C.c_int64), i32, i32, P(C.c_int8)]),
+        "agz_go_position_key": (i32, [P(C.c_int8), i32, i32, i32, P(u64)]),
         "agz_search_set_value_moments": (i32, [E, i32]),
         "agz_search_set_lcb": (i32, [E, C.c_double, i32, C.c_double]),
         "agz_search_set_puct_variance": (i32, [E, C.c_double, C.c_double, C.c_double]),

@@ -298,6 +298,13 @@ class NodeView:
     child_S = property(lambda s: s._p.engine.node_floats(0, s.id, _lib.F_CHILD_S))
     child_stdev = property(lambda s: s._p.engine.tree_child_lcb(0, s.id, 0.0)[1])
 
+    # (ours) superko: the node's key under the rule in force, and its legal mask as the search reads it
+    key = property(lambda s: s._p.engine.node_key(0, s.id))
+
+    def legal(self):
+        """the node's legal mask int8[A] (agz_tree_node_legal): under ko_rule= the moves that repeat a position are off"""
+        return self._p.engine.node_legal(0, self.id)
+
     def child_lcb(self, z):
         """the lower confidence bounds of the children under z, from the side to move (agz_tree_child_lcb)"""
         return self._p.engine.tree_child_lcb(0, self.id, z)[2]
@@ -468,7 +475,7 @@ class MCTSPlayer:
 
     def __init__(self, env, network, num_readouts=800, two_player_mode=False, resign_threshold=-0.9, seed=0,
                  game_id=0, symmetry=None, fpu=None, c_base=0.0, root_policy_temperature=None, root_noise=None,
-                 move_temperature=None, lcb=None, puct_variance=None):
+                 move_temperature=None, lcb=None, puct_variance=None, ko_rule=None):
         self.env = env
         self.network = network
         self.num_readouts = num_readouts
@@ -488,6 +495,7 @@ class MCTSPlayer:
             self.engine.set_symmetry(symmetry)
         _apply_puct(self.engine, fpu, c_base)      # (ours) the PUCT rule options of Engine.set_puct
         _apply_uncertainty(self.engine, lcb, puct_variance)
+        _apply_ko_rule(self.engine, ko_rule)
         # (ours) root exploration in inject_noise and the move temperature in pick_move, as selfplay() takes them
         _apply_explore(self.engine, root_policy_temperature, root_noise, move_temperature)
         self._game_id = game_id
@@ -701,6 +709,13 @@ def _apply_puct(eng, fpu, c_base):
         eng.set_puct(fpu, c_base)
 
 
+def _apply_ko_rule(eng, ko_rule=None):
+    """(ours) the superko rule of a fresh engine: "simple" | "positional" | "situational" (Engine.set_ko_rule); nothing
+    asked for, nothing set"""
+    if ko_rule is not None:
+        eng.set_ko_rule(ko_rule)
+
+
 def _apply_uncertainty(eng, lcb=None, puct_variance=None):
     """(ours) value uncertainty on a fresh engine: lcb = z | (z, min_visits, min_ratio) -- the move is the child with the
     largest lower confidence bound (Engine.set_lcb); puct_variance = k | (k, prior, weight) -- exploration scaled by the
@@ -729,11 +744,12 @@ def _apply_explore(eng, root_policy_temperature=None, root_noise=None, move_temp
 
 def _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit, gumbel_c_scale,
                           targets_only_arena=False, fpu=None, c_base=0.0, root_policy_temperature=None, root_noise=None,
-                          move_temperature=None, lcb=None, puct_variance=None):
+                          move_temperature=None, lcb=None, puct_variance=None, ko_rule=None):
     """selfplay()'s and train()'s search options on a fresh engine (train(): a targets-only arena under the cap)"""
     _refuse_two_root_rules(gumbel, forced_playouts)
     _apply_puct(eng, fpu, c_base)
     _apply_uncertainty(eng, lcb, puct_variance)
+    _apply_ko_rule(eng, ko_rule)
     _apply_explore(eng, root_policy_temperature, root_noise, move_temperature)
     if starts:
         eng.set_starts(starts)
@@ -755,7 +771,7 @@ def seed(s):
 def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="f32", game_id_base=None, symmetry=None,
              starts=None, playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
              gumbel_c_scale=1.0, fpu=None, c_base=0.0, root_policy_temperature=None, root_noise=None,
-             move_temperature=None, lcb=None, puct_variance=None, **cfg):
+             move_temperature=None, lcb=None, puct_variance=None, ko_rule=None, **cfg):
     """selfplay(env, nn, num_ro) (src/selfplay.jl:1-45) -> the finished game's player (SelfPlayPlayer), exactly the
     call train() makes (train.jl:57).  `games=G` (ours) plays G games concurrently on the device and returns a list of
     G such players ordered by game id.  Game ids continue from the previous call (module stream, `seed()`), unless
@@ -796,7 +812,7 @@ def selfplay(env, nn, num_ro=800, games=None, seed=None, slots=None, precision="
     if symmetry is not None:
         eng.set_symmetry(symmetry)
     _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit, gumbel_c_scale,
-                          fpu=fpu, c_base=c_base, lcb=lcb, puct_variance=puct_variance, root_policy_temperature=root_policy_temperature, root_noise=root_noise,
+                          fpu=fpu, c_base=c_base, lcb=lcb, puct_variance=puct_variance, ko_rule=ko_rule, root_policy_temperature=root_policy_temperature, root_noise=root_noise,
                           move_temperature=move_temperature)
     eng.start(games)
     while eng.records_count() < games:
@@ -869,7 +885,7 @@ def _line_rows(env, t):
 
 def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=None, two_player_mode=False,
             symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, fpu=None, c_base=0.0,
-            move_temperature=None, lcb=None, puct_variance=None, **cfg):
+            move_temperature=None, lcb=None, puct_variance=None, ko_rule=None, **cfg):
     """suggest_move over many positions in one device run (ours).  Record i is what
     `MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + i, symmetry=symmetry)`,
     `initialize_game(positions[i])`, `suggest_move()` computes (mcts_play.jl:110-118,144-151), bit for bit, except that
@@ -917,6 +933,7 @@ def analyze(env, nn, positions, num_readouts=800, seed=0, game_id_base=0, slots=
             eng.set_symmetry(symmetry)
         _apply_puct(eng, fpu, c_base)      # the PUCT rule options of Engine.set_puct, as MCTSPlayer(fpu=, c_base=)
         _apply_uncertainty(eng, lcb, puct_variance)
+        _apply_ko_rule(eng, ko_rule)
         _apply_explore(eng, move_temperature=move_temperature)      # pick_move's, as MCTSPlayer(move_temperature=)
         if lines:
             eng.analyze_set_lines(lines, pv_depth, pv_min_visits)
@@ -980,7 +997,7 @@ def review_arrays(env, games):
 
 def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, seed=0, game_id_base=0, slots=None,
            symmetry=None, precision="f32", lines=0, pv_depth=16, pv_min_visits=1, fpu=None, c_base=0.0,
-           move_temperature=None, lcb=None, puct_variance=None, **cfg):
+           move_temperature=None, lcb=None, puct_variance=None, ko_rule=None, **cfg):
     """Batched game review (ours; the loop of play(), src/play.jl:25-77, over recorded games): for game j, what
     `p = MCTSPlayer(env, nn, num_readouts, two_player_mode, seed=seed, game_id=game_id_base + j, symmetry=symmetry)`,
     `p.initialize_game(starts[j])`, then for every recorded move m_k `p.suggest_move()` and `p.play_move(m_k)` compute,
@@ -1037,6 +1054,7 @@ def review(env, nn, games, num_readouts=800, starts=None, two_player_mode=True, 
             eng.set_symmetry(symmetry)
         _apply_puct(eng, fpu, c_base)      # the PUCT rule options of Engine.set_puct, as MCTSPlayer(fpu=, c_base=)
         _apply_uncertainty(eng, lcb, puct_variance)
+        _apply_ko_rule(eng, ko_rule)
         _apply_explore(eng, move_temperature=move_temperature)      # pick_move's, as MCTSPlayer(move_temperature=)
         if lines:
             eng.analyze_set_lines(lines, pv_depth, pv_min_visits)
@@ -1098,7 +1116,7 @@ EvalStats = namedtuple("EvalStats", "games_won num_games win_rate resigned moves
 
 
 def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, seed=0, slots=None,
-             return_stats=False, symmetry=None, starts=None, fpu=None, c_base=0.0, lcb=None, puct_variance=None, **cfg):
+             return_stats=False, symmetry=None, starts=None, fpu=None, c_base=0.0, lcb=None, puct_variance=None, ko_rule=None, **cfg):
     """evaluate(env, black_net, white_net; num_games, ro) (src/neural_net.jl:103-158): black_net plays
     Black and white_net White in `num_games` games of two two_player_mode MCTSPlayers (arg-max moves,
     no noise, resign at -0.9); True iff Black's win rate reaches 0.55.  All games run concurrently on
@@ -1122,6 +1140,7 @@ def evaluate(env, black_net, white_net, num_games=400, ro=800, verbose=False, se
         eng.set_symmetry(symmetry)
     _apply_puct(eng, fpu, c_base)
     _apply_uncertainty(eng, lcb, puct_variance)
+    _apply_ko_rule(eng, ko_rule)
     if starts:
         eng.set_starts(starts)
     eng.start(num_games)
@@ -1226,7 +1245,7 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
           augment=False, precision="f32", checkpoint_dir=None, callback=print, return_log=False, profile=None, starts=None,
           playout_cap=None, forced_playouts=None, prune_targets=True, gumbel=None, gumbel_c_visit=50.0,
           gumbel_c_scale=1.0, value_target=None, fpu=None, c_base=0.0, surprise=0.0, root_policy_temperature=None,
-          root_noise=None, move_temperature=None, lcb=None, puct_variance=None, **cfg):
+          root_noise=None, move_temperature=None, lcb=None, puct_variance=None, ko_rule=None, **cfg):
     """train(env; num_games, memory_size, batch_size, epochs, ckp_freq, readouts, tower_height, model,
     start_training_after) (src/train.jl:38-92) with `slots` games in flight on the device.  One engine
     plays, keeps the replay arena and trains; per step: agz_selfplay_step(1), one read of how many games finished, and
@@ -1282,7 +1301,7 @@ def train(env, num_games=25000, memory_size=500000, batch_size=32, epochs=1, ckp
         z = torch.empty(batch_size, dtype=torch.float32, device=dev)
         cuts = _minibatch_cuts(batch_size)
         _apply_search_options(eng, starts, playout_cap, forced_playouts, prune_targets, gumbel, gumbel_c_visit,
-                              gumbel_c_scale, targets_only_arena=True, fpu=fpu, c_base=c_base, lcb=lcb, puct_variance=puct_variance,
+                              gumbel_c_scale, targets_only_arena=True, fpu=fpu, c_base=c_base, lcb=lcb, puct_variance=puct_variance, ko_rule=ko_rule,
                               root_policy_temperature=root_policy_temperature, root_noise=root_noise,
                               move_temperature=move_temperature)
         if value_target is not None:

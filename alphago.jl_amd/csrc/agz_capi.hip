@@ -198,6 +198,48 @@ agz_status agz_go_legal(agz_engine* e, const int8_t* boards, const int8_t* to_pl
                         int8_t* legal_out) {
   return guard(e, [&](agz::Engine& E) { E.go_legal(boards, to_play, ko, B, legal_out); });
 }
+agz_status agz_go_keys(agz_engine* e, const int8_t* boards, const int8_t* to_play, int32_t B, int32_t rule,
+                       uint64_t* keys_out) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(B <= 0 || (boards && to_play && keys_out), AGZ_BAD_ARGUMENT, "null pointer");
+    E.go_keys(boards, to_play, B, rule, keys_out);
+  });
+}
+agz_status agz_go_legal_seen(agz_engine* e, const int8_t* boards, const int8_t* to_play, const int32_t* ko,
+                             const uint64_t* seen_keys, const int64_t* seen_off, int32_t B, int32_t rule,
+                             int8_t* legal_out) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(B <= 0 || (boards && to_play && ko && seen_off && legal_out), AGZ_BAD_ARGUMENT, "null pointer");
+    AGZ_REQUIRE(B <= 0 || seen_off[B] == 0 || seen_keys, AGZ_BAD_ARGUMENT, "null pointer");
+    E.go_legal_seen(boards, to_play, ko, seen_keys, seen_off, B, rule, legal_out);
+  });
+}
+agz_status agz_go_position_key(const int8_t* board, int32_t P, int32_t to_play, int32_t rule, uint64_t* out) {
+  if (!board || !out || P < 0 || !agz_ko_rule_valid(rule) || (to_play != 1 && to_play != -1)) return AGZ_BAD_ARGUMENT;
+  *out = agz_position_key(board, P, to_play, rule);
+  return AGZ_OK;
+}
+agz_status agz_search_set_ko_rule(agz_engine* e, int32_t rule) {
+  return guard(e, [&](agz::Engine& E) { E.set_ko_rule(rule); });
+}
+agz_status agz_search_superko_counts(agz_engine* e, uint64_t* out) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+    E.superko_counts(out);
+  });
+}
+agz_status agz_tree_node_key(agz_engine* e, int32_t g, int32_t node, uint64_t* key) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(key, AGZ_BAD_ARGUMENT, "null pointer");
+    *key = E.node_key(g, node);
+  });
+}
+agz_status agz_tree_node_legal(agz_engine* e, int32_t g, int32_t node, int8_t* out) {
+  return guard(e, [&](agz::Engine& E) {
+    AGZ_REQUIRE(out, AGZ_BAD_ARGUMENT, "null pointer");
+    E.node_legal(g, node, out);
+  });
+}
 agz_status agz_go_score(agz_engine* e, const int8_t* boards, const float* komi, int32_t B, float* score_out) {
   return guard(e, [&](agz::Engine& E) { E.go_score(boards, komi, B, score_out); });
 }

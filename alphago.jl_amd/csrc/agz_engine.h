@@ -74,6 +74,9 @@ class Engine {
   void set_lcb(double z, int min_visits, double min_ratio);
   void set_puct_variance(double k, double prior, double prior_weight);
   void uncertainty_counts(uint64_t out[4]);
+  // superko (agz_search_set_ko_rule): AGZ_KO_SIMPLE by default
+  void set_ko_rule(int rule);
+  void superko_counts(uint64_t out[2]);
   void tree_child_lcb(int g, int node, double z, double* mean, double* sd, double* lcb);
   void analyze_child_S(float* child_S, float* root_S);
   int64_t analyze_progress();
@@ -154,6 +157,9 @@ class Engine {
   void go_play(const int8_t* boards, const int8_t* to_play, const int32_t* ko, const int32_t* moves, int B,
                int8_t* boards_out, int32_t* ko_out, int32_t* ncap_out, int32_t* status_out);
   void go_legal(const int8_t* boards, const int8_t* to_play, const int32_t* ko, int B, int8_t* out);
+  void go_keys(const int8_t* boards, const int8_t* to_play, int B, int rule, uint64_t* out);
+  void go_legal_seen(const int8_t* boards, const int8_t* to_play, const int32_t* ko, const uint64_t* seen_keys,
+                     const int64_t* seen_off, int B, int rule, int8_t* out);
   void go_score(const int8_t* boards, const float* komi, int B, float* out);
 
   // single-tree compat
@@ -171,6 +177,8 @@ class Engine {
   void node_row_set(int g, int node, int field, const float* in);
   void node_children(int g, int node, int32_t* out);
   void node_board(int g, int node, int8_t* out);
+  uint64_t node_key(int g, int node);              // under the rule in force; the position key with none
+  void node_legal(int g, int node, int8_t* out);   // the node's mask, [A]
   float node_stat(int g, int node, int which);     // 0 = N, 1 = W, 2 = S (moments on)
   void node_set_N(int g, int node, float v);
 
@@ -245,6 +253,9 @@ class Engine {
   DevBuf<float> an_rows_;       // [3][B][A]: child_N, child_W, prior
   DevBuf<float> an_s_;          // [B][A] child_S, then [B] root_S: a run begun with moments on (View::an_childS / an_rootS)
   DevBuf<float> child_s_, root_s_;   // View::childS / rootS once agz_search_set_value_moments has switched them on
+  DevBuf<uint64_t> sk_key_, sk_log_;   // View::sk_key / sk_log / sk_len once agz_search_set_ko_rule has taken a superko rule
+  DevBuf<int32_t> sk_len_;
+  DevBuf<uint64_t> s_u64_;
   int64_t an_count_ = 0;         // rows of the current run
   DevBuf<int16_t> rv_moves_;    // review mode: the recorded moves and game offsets (View::rv_*)
   DevBuf<int64_t> rv_off_;

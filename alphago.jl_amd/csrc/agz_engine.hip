@@ -27,16 +27,31 @@ __global__ __launch_bounds__(kWave) void k_pre(View V) {
 }
 
 // the board updates of the leaves k_pre created (node_create_child, defer): one wave per leaf
-__global__ __launch_bounds__(kWave) void k_expand(View V) {
-  AGZ_SCRATCH(S)
+__device__ __forceinline__ void expand_block(const View& V, Scratch& S) {
   HipWave w;
   const int half = kMaxPend / 2;                 // a game rarely creates more than parallel_readouts leaves per step
   const int g = (int)blockIdx.x / half, i = (int)blockIdx.x % half;
   game_expand(w, V, S, g, i);
   game_expand(w, V, S, g, i + half);
 }
+// k_expand holds no key scratch, so with no superko rule its LDS and occupancy are what they were (7 waves per SIMD);
+// under a rule (View::sk_key set) the host launches k_expand_keys
+__global__ __launch_bounds__(kWave) void k_expand(View V) {
+  AGZ_SCRATCH_NO_KEYS(S)
+  expand_block(V, S);
+}
+__global__ __launch_bounds__(kWave) void k_expand_keys(View V) {
+  AGZ_SCRATCH(S)
+  expand_block(V, S);
+}
 
+// (as k_expand: no key scratch while no superko rule is set -- LDS and occupancy as they were -- else k_post_keys)
 __global__ __launch_bounds__(kWave) void k_post(View V) {
+  AGZ_SCRATCH_NO_KEYS(S)
+  HipWave w;
+  game_post(w, V, S, (int)blockIdx.x);
+}
+__global__ __launch_bounds__(kWave) void k_post_keys(View V) {
   AGZ_SCRATCH(S)
   HipWave w;
   game_post(w, V, S, (int)blockIdx.x);
@@ -266,6 +281,25 @@ __global__ __launch_bounds__(kWave) void k_go_legal(View V, const int8_t* boards
   const int b = blockIdx.x;
   if (b >= B) return;
   go_legal_one(w, V, S, boards + (long)b * V.P, tp[b], ko[b], out + (long)b * V.A);
+}
+
+__global__ __launch_bounds__(kWave) void k_go_keys(View V, const int8_t* boards, const int8_t* tp, int B, int rule,
+                                                   uint64_t* out) {
+  HipWave w;
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  go_key_one(w, V, boards + (long)b * V.P, tp[b], rule, out + b);
+}
+
+__global__ __launch_bounds__(kWave) void k_go_legal_seen(View V, const int8_t* boards, const int8_t* tp, const int32_t* ko,
+                                                         const uint64_t* seen, const int64_t* off, int B, int rule,
+                                                         int8_t* out) {
+  AGZ_SCRATCH(S)
+  HipWave w;
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  go_legal_seen_one(w, V, S, boards + (long)b * V.P, tp[b], ko[b], seen + off[b], (int)(off[b + 1] - off[b]), rule,
+                    out + (long)b * V.A);
 }
 
 __global__ __launch_bounds__(kWave) void k_go_score(View V, const int8_t* boards, const float* komi, int B, float* out) {
@@ -500,7 +534,7 @@ void Engine::step(int nsteps) {
     if (ev) (void)hipEventRecord(ev[0], stream_);
     hipLaunchKernelGGL(k_pre, dim3(V_.games), dim3(kWave), 0, stream_, V_);
     if (ev) (void)hipEventRecord(ev[1], stream_);
-    hipLaunchKernelGGL(k_expand, dim3(V_.games * (kMaxPend / 2)), dim3(kWave), 0, stream_, V_);
+    hipLaunchKernelGGL(V_.sk_key ? k_expand_keys : k_expand, dim3(V_.games * (kMaxPend / 2)), dim3(kWave), 0, stream_, V_);
     if (ev) (void)hipEventRecord(ev[2], stream_);
     hipLaunchKernelGGL(cfg_.arena_mode ? k_scan_arena : k_scan, dim3(1), dim3(256), 0, stream_, V_);
     if (ev) (void)hipEventRecord(ev[3], stream_);
@@ -519,7 +553,7 @@ void Engine::step(int nsteps) {
     }
     if (V_.symmetry) hipLaunchKernelGGL(k_pi_unpermute, dim3(bcap_), dim3(kWave), 0, stream_, V_, 0, bcap_, d_pi_.p);
     if (ev) (void)hipEventRecord(ev[5], stream_);
-    hipLaunchKernelGGL(k_post, dim3(V_.games), dim3(kWave), 0, stream_, V_);
+    hipLaunchKernelGGL(V_.sk_key ? k_post_keys : k_post, dim3(V_.games), dim3(kWave), 0, stream_, V_);
     if (ev) {
       (void)hipEventRecord(ev[6], stream_);
       ++sprof_n_;
@@ -723,6 +757,37 @@ void Engine::set_value_moments(int on) {
     V.childS = on ? child_s_.p : nullptr;
     V.rootS = on ? root_s_.p : nullptr;
   }, CT_UNC_LCB, 4);
+}
+
+// ---- superko (agz_search_set_ko_rule): every search of every engine.  The key arrays are made the first
+// time a rule other than simple is taken, behind the state checks, as the moment arrays above
+static_assert(CT_SK_MOVES == CT_SK_NODES + 1, "the two counters are cleared and read as one pair");
+void Engine::superko_counts(uint64_t out[2]) { read_counters(CT_SK_NODES, 2, out); }
+
+void Engine::set_ko_rule(int rule) {
+  AGZ_REQUIRE(agz_ko_rule_valid(rule), AGZ_BAD_ARGUMENT, "ko rule: %d is not 0 (simple), 1 (positional) or 2 (situational)", rule);
+  set_option("ko rule", true, [](View&) {}, 0, 0);
+  if (rule != AGZ_KO_SIMPLE && !sk_key_.p) {
+    DevBuf<uint64_t> k, l;
+    DevBuf<int32_t> n;
+    k.alloc((size_t)V_.games * V_.cap);
+    l.alloc((size_t)V_.games * sk_log_stride(V_));
+    n.alloc((size_t)V_.games);
+    k.zero(stream_);
+    l.zero(stream_);
+    n.zero(stream_);
+    wait();
+    sk_key_.swap(k);
+    sk_log_.swap(l);
+    sk_len_.swap(n);
+  }
+  set_option("ko rule", true, [&](View& V) {
+    const bool on = rule != AGZ_KO_SIMPLE;
+    V.ko_rule = rule;
+    V.sk_key = on ? sk_key_.p : nullptr;
+    V.sk_log = on ? sk_log_.p : nullptr;
+    V.sk_len = on ? sk_len_.p : nullptr;
+  }, CT_SK_NODES, 2);
 }
 
 void Engine::set_lcb(double z, int min_visits, double min_ratio) {
@@ -1131,7 +1196,7 @@ void Engine::profile_search_read(double* ms5, int64_t* steps) {
 int Engine::select_external() {
   stepped_ = true;
   hipLaunchKernelGGL(k_pre, dim3(V_.games), dim3(kWave), 0, stream_, V_);
-  hipLaunchKernelGGL(k_expand, dim3(V_.games * (kMaxPend / 2)), dim3(kWave), 0, stream_, V_);
+  hipLaunchKernelGGL(V_.sk_key ? k_expand_keys : k_expand, dim3(V_.games * (kMaxPend / 2)), dim3(kWave), 0, stream_, V_);
   hipLaunchKernelGGL(cfg_.arena_mode ? k_scan_arena : k_scan, dim3(1), dim3(256), 0, stream_, V_);
   int32_t n[2] = {0, 0};
   down(n, V_.batch_count, 2);
@@ -1169,7 +1234,7 @@ void Engine::incorporate_external(const float* pi, const float* v) {
     up(d_pi_.p + half * A, pi + (size_t)B * A, (size_t)B2 * A);
     up(d_v_.p + half, v + B, (size_t)B2);
   }
-  hipLaunchKernelGGL(k_post, dim3(V_.games), dim3(kWave), 0, stream_, V_);
+  hipLaunchKernelGGL(V_.sk_key ? k_post_keys : k_post, dim3(V_.games), dim3(kWave), 0, stream_, V_);
   wait();
   external_batch_ = 0;
   external_batch2_ = 0;
@@ -1816,6 +1881,43 @@ void Engine::go_legal(const int8_t* boards, const int8_t* to_play, const int32_t
   wait();
 }
 
+static void check_ko_rule(const char* what, int rule) {
+  AGZ_REQUIRE(agz_ko_rule_valid(rule), AGZ_BAD_ARGUMENT, "%s: rule %d", what, rule);
+}
+
+void Engine::go_keys(const int8_t* boards, const int8_t* to_play, int B, int rule, uint64_t* out) {
+  check_ko_rule("go keys", rule);
+  if (B <= 0) return;
+  const size_t n = (size_t)B;
+  const int8_t *d_boards = stage(s_boards_, boards, n * V_.P), *d_tp = stage(s_tp_, to_play, n);
+  s_u64_.ensure(n);
+  hipLaunchKernelGGL(k_go_keys, dim3(B), dim3(kWave), 0, stream_, V_, d_boards, d_tp, B, rule, s_u64_.p);
+  down(out, s_u64_.p, n);
+  wait();
+}
+
+void Engine::go_legal_seen(const int8_t* boards, const int8_t* to_play, const int32_t* ko, const uint64_t* seen_keys,
+                           const int64_t* seen_off, int B, int rule, int8_t* out) {
+  check_ko_rule("go legal seen", rule);
+  if (B <= 0) return;
+  const size_t n = (size_t)B;
+  AGZ_REQUIRE(seen_off[0] == 0, AGZ_BAD_ARGUMENT, "go legal seen: seen_off[0] = %lld", (long long)seen_off[0]);
+  for (size_t b = 0; b < n; ++b)
+    AGZ_REQUIRE(seen_off[b + 1] >= seen_off[b] && seen_off[b + 1] - seen_off[b] <= (1 << 30), AGZ_BAD_ARGUMENT,
+                "go legal seen: seen_off is not ascending at %lld", (long long)b);
+  const size_t total = (size_t)seen_off[n];
+  const int8_t *d_boards = stage(s_boards_, boards, n * V_.P), *d_tp = stage(s_tp_, to_play, n);
+  const int32_t* d_ko = stage(s_i32a_, ko, n);
+  const int64_t* d_off = stage(s_i64a_, seen_off, n + 1);
+  s_u64_.ensure(total + 1);
+  if (total) up(s_u64_.p, seen_keys, total);
+  s_legal_.ensure(n * V_.A);
+  hipLaunchKernelGGL(k_go_legal_seen, dim3(B), dim3(kWave), 0, stream_, V_, d_boards, d_tp, d_ko,
+                     (const uint64_t*)s_u64_.p, d_off, B, rule, s_legal_.p);
+  down(out, s_legal_.p, n * V_.A);
+  wait();
+}
+
 void Engine::go_score(const int8_t* boards, const float* komi, int B, float* out) {
   if (B <= 0) return;
   const size_t n = (size_t)B;
@@ -1996,6 +2098,20 @@ void Engine::node_board(int g, int node, int8_t* out) {
   check_node(g, node);
   down(out, V_.board + node_index(V_, g, node) * V_.PP, (size_t)V_.P);
   wait();
+}
+uint64_t Engine::node_key(int g, int node) {
+  check_node(g, node);
+  if (V_.sk_key) return fetch(V_.sk_key + node_index(V_, g, node));
+  std::vector<int8_t> b((size_t)V_.P);
+  node_board(g, node, b.data());
+  return agz_position_key(b.data(), V_.P, 1, AGZ_KO_SIMPLE);
+}
+void Engine::node_legal(int g, int node, int8_t* out) {
+  check_node(g, node);
+  std::vector<uint32_t> words((size_t)V_.LW);
+  down(words.data(), V_.legal + node_index(V_, g, node) * V_.LW, (size_t)V_.LW);
+  wait();
+  for (int a = 0; a < V_.A; ++a) out[a] = (int8_t)((words[a >> 5] >> (a & 31)) & 1u);
 }
 float Engine::node_stat(int g, int node, int which) {
   NodeMeta m;

@@ -31,6 +31,7 @@
 
 #include "../../include/agz_draws.h"
 #include "../../include/agz_explore.h"
+#include "../../include/agz_superko.h"
 #include "../../include/agz_uncertainty.h"
 #include "agz_state.h"
 
@@ -107,7 +108,43 @@ struct Scratch {
   int8_t* flag;      // [AP]
   double* dbuf;      // [AP]
   int32_t* path;     // [maxd]
+  // superko (View::sk_key): [AP] keys -- a stone group's at its label, a candidate move's child key at its empty point --
+  // then one chunk of kSkChunk seen keys.  Last, so that an initialiser of the seven above leaves it null: a lane-serial
+  // wave then works in a buffer of its own (sk_keybuf)
+  uint64_t* key;     // [AP + kSkChunk]
 };
+constexpr int kSkChunk = 64;
+
+// The 64-bit wave operations of the superko filter, for any wave: the XOR of v over the lanes (a butterfly of shuffles; a
+// wave of one lane has folded its whole range into v already) and an XOR into a cell that several lanes may hit (the LDS
+// atomic; one lane alone has no one to race with).
+template <class W>
+AGZ_FN uint64_t wave_xor64(const W& w, uint64_t v) {
+  if constexpr (wave_lanes<W>::value > 1) {
+    int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
+    for (int o = wave_lanes<W>::value / 2; o > 0; o >>= 1) {
+      lo ^= w.shfl(lo, w.lane ^ o);
+      hi ^= w.shfl(hi, w.lane ^ o);
+    }
+    return ((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo;
+  } else {
+    return v;
+  }
+}
+template <class W>
+AGZ_FN void wave_axor64(const W& w, uint64_t* p, uint64_t v) {
+  if constexpr (wave_lanes<W>::value > 1) w.axor64(p, v); else *p ^= v;
+}
+template <class W>
+AGZ_FN uint64_t* sk_keybuf(const W& w, const Scratch& S) {
+#if !defined(__HIPCC__)
+  if constexpr (wave_lanes<W>::value == 1) {
+    static thread_local uint64_t buf[kAPMax + kSkChunk];
+    return S.key ? S.key : buf;
+  }
+#endif
+  return S.key;
+}
 
 constexpr int kIntMax = 0x7fffffff;
 
@@ -232,10 +269,103 @@ AGZ_FN void compute_legal_flags(W& w, const View& V, Scratch& S, int tp, int ko)
   w.sync();
 }
 
+// ---- superko (include/agz_superko.h): the filter behind compute_legal_flags
+
+// the key under `rule` of board b [P] with tp to move
 template <class W>
-AGZ_FN void write_legal_mask(W& w, const View& V, Scratch& S, long ni, int tp, int ko) {
+AGZ_FN uint64_t board_key(W& w, const View& V, const int8_t* b, int tp, int rule) {
+  uint64_t k = 0;
+  w.for_each(V.P, [&](int p) { const int c = b[p]; if (c != 0) k ^= agz_zobrist(p, c); });
+  return wave_xor64(w, k) ^ agz_ko_side_key(tp, rule);
+}
+
+// K[a] := the key of the position after move a, for every flagged board move a of the side tp on the board in S.sb
+// (labels, liberties and flags current), node_key being the board's own key under `rule`.  The stone groups' keys are
+// built in K at the groups' labels first: a label is a stone and a candidate an empty point, so the two never share a cell.
+template <class W>
+AGZ_FN void sk_child_keys(W& w, const View& V, Scratch& S, uint64_t* K, int tp, int rule, uint64_t node_key) {
+  const int P = V.P, N = V.N;
+  w.for_each(V.AP, [&](int a) { K[a] = 0; });
+  w.sync();
+  w.for_each(P, [&](int p) {
+    const int c = S.sb[p];
+    if (c != 0) wave_axor64(w, &K[S.label[p]], agz_zobrist(p, c));
+  });
+  w.sync();
+  const uint64_t flip = rule == AGZ_KO_SITUATIONAL ? AGZ_ZOBRIST_WHITE_TO_PLAY : 0ull;   // the side to move changes
+  w.for_each(P, [&](int a) {
+    if (!S.flag[a]) return;
+    uint64_t k = node_key ^ agz_zobrist(a, tp) ^ flip;
+    int nb[4], dead[4];
+    const int n = nbrs<W>(N, a, nb);
+    for (int t = 0; t < n; ++t) {
+      dead[t] = -1;
+      if (S.sb[nb[t]] != -tp) continue;
+      const int gl = S.label[nb[t]];
+      if (S.minlib[gl] != a || S.maxlib[gl] != a) continue;
+      bool dup = false;
+      for (int u = 0; u < t; ++u) dup = dup || dead[u] == gl;
+      if (dup) continue;
+      dead[t] = gl;
+      k ^= K[gl];
+    }
+    K[a] = k;
+  });
+  w.sync();
+}
+
+// clear the flag of every board move whose child key is one of seen[0 .. cnt); returns this lane's count of them
+template <class W>
+AGZ_FN int sk_strike(W& w, const View& V, Scratch& S, const uint64_t* K, const uint64_t* seen, int cnt) {
+  int struck = 0;
+  w.sync();
+  w.for_each(V.P, [&](int a) {
+    if (!S.flag[a]) return;
+    const uint64_t k = K[a];
+    bool hit = false;
+    for (int i = 0; i < cnt; ++i) hit = hit || seen[i] == k;
+    if (hit) { S.flag[a] = 0; struck++; }
+  });
+  w.sync();
+  return struck;
+}
+
+// The filter of a tree node: `key` is node id's own key, its seen set the keys of the node, of its ancestors (from
+// `parent` up) and of the slot's log.  Counts the node and its removed moves.
+template <class W>
+AGZ_FN void superko_filter_node(W& w, const View& V, Scratch& S, int g, int parent, int tp, uint64_t key) {
+  uint64_t* K = sk_keybuf(w, S);
+  uint64_t* seen = K + V.AP;
+  sk_child_keys(w, V, S, K, tp, V.ko_rule, key);
+  int struck = 0, c = 1;
+  if (w.leader()) seen[0] = key;
+  for (int n = parent; n >= 0;) {
+    const long ni = node_index(V, g, n);
+    if (w.leader()) seen[c] = V.sk_key[ni];
+    n = V.meta[ni].parent;
+    if (++c == kSkChunk) { struck += sk_strike(w, V, S, K, seen, c); c = 0; }
+  }
+  const int len = V.sk_len[g];
+  const uint64_t* log = V.sk_log + (long)g * sk_log_stride(V);
+  for (int at = 0; c > 0 || at < len;) {
+    const int take = kSkChunk - c < len - at ? kSkChunk - c : len - at;
+    w.for_each(take, [&](int i) { seen[c + i] = log[at + i]; });
+    c += take;
+    at += take;
+    struck += sk_strike(w, V, S, K, seen, c);
+    c = 0;
+  }
+  struck = w.reduce_sum(struck);
+  if (struck > 0) {
+    w.count(&V.counters[CT_SK_NODES], 1);
+    w.count(&V.counters[CT_SK_MOVES], (unsigned long long)struck);
+  }
+}
+
+// S.flag -> the packed mask words of node index ni
+template <class W>
+AGZ_FN void pack_legal_mask(W& w, const View& V, Scratch& S, long ni) {
   const int A = V.A;
-  compute_legal_flags(w, V, S, tp, ko);
   w.for_each(V.LW, [&](int wi) {
     uint32_t bits = 0;
     for (int b = 0; b < 32; ++b) {
@@ -443,7 +573,13 @@ AGZ_FN void node_init_from_scratch(W& w, const View& V, Scratch& S, int g, int i
   if (w.leader()) { V.meta[ni] = m; V.meta[ni].flags = (uint8_t)(m.flags | NF_ALLOC); }
   label_components(w, V, S, true);
   group_liberties(w, V, S);
-  write_legal_mask(w, V, S, ni, m.to_play, m.ko);
+  compute_legal_flags(w, V, S, m.to_play, m.ko);
+  if (V.sk_key) {      // a superko rule is in force (wave-uniform)
+    const uint64_t key = board_key(w, V, S.sb, m.to_play, V.ko_rule);
+    if (w.leader()) V.sk_key[ni] = key;
+    superko_filter_node(w, V, S, g, m.parent, m.to_play, key);
+  }
+  pack_legal_mask(w, V, S, ni);
 }
 
 // The board half of node_create_child: play the node's move (meta.fmove) on its parent's board in scratch and
@@ -1250,6 +1386,10 @@ AGZ_FN void reroot(W& w, const View& V, Scratch& S, int g, int a, int child) {
   const float cs = V.childS ? V.childS[oi * V.AP + a] : 0.f;
   push_history(w, V, g, oi);
   discard_except(w, V, g, old_root, a);
+  if (V.sk_key && w.leader()) {      // the old root's position stays seen
+    const int len = V.sk_len[g];
+    if (len < sk_log_stride(V)) { V.sk_log[(long)g * sk_log_stride(V) + len] = V.sk_key[oi]; V.sk_len[g] = len + 1; }
+  }
   if (w.leader()) {
     G.rootN = cn;
     G.rootW = cw;
@@ -1373,6 +1513,15 @@ AGZ_FN bool root_install(W& w, const View& V, Scratch& S, int g, const int8_t* b
   w.sync();
   for (int h = 0; hist && h < info.history_len && h < 7; ++h)
     w.for_each(V.P, [&](int p) { V.hist[((long)g * 7 + h) * V.PP + p] = hist[(long)h * V.P + p]; });
+  if (V.sk_key) {      // the key log begins with the history boards: board h had (-1)^(h+1) * to_play to move
+    int len = 0;
+    for (int h = 0; hist && h < info.history_len && h < 7; ++h, ++len) {
+      const uint64_t k = board_key(w, V, hist + (long)h * V.P, (h & 1) ? info.to_play : -info.to_play, V.ko_rule);
+      if (w.leader()) V.sk_log[(long)g * sk_log_stride(V) + h] = k;
+    }
+    if (w.leader()) V.sk_len[g] = len;
+    w.sync();
+  }
   const int id = pool_alloc(w, V, S, g);
   w.for_each(V.P, [&](int p) { S.sb[p] = board ? board[p] : (int8_t)0; });
   w.sync();
@@ -2535,6 +2684,37 @@ AGZ_FN void go_legal_one(W& w, const View& V, Scratch& S, const int8_t* board, i
   label_components(w, V, S, true);
   group_liberties(w, V, S);
   compute_legal_flags(w, V, S, tp, ko);
+  w.for_each(V.A, [&](int a) { out[a] = S.flag[a]; });
+  w.sync();
+}
+
+// agz_go_keys: the key under `rule` of one position
+template <class W>
+AGZ_FN void go_key_one(W& w, const View& V, const int8_t* board, int tp, int rule, uint64_t* out) {
+  const uint64_t k = board_key(w, V, board, tp, rule);
+  if (w.leader()) *out = k;
+  w.sync();
+}
+
+// agz_go_legal_seen: all_legal_moves under `rule` with the caller's seen set seen[0 .. cnt)
+template <class W>
+AGZ_FN void go_legal_seen_one(W& w, const View& V, Scratch& S, const int8_t* board, int tp, int ko, const uint64_t* seen,
+                              int cnt, int rule, int8_t* out) {
+  w.for_each(V.P, [&](int p) { S.sb[p] = board[p]; });
+  w.sync();
+  label_components(w, V, S, true);
+  group_liberties(w, V, S);
+  compute_legal_flags(w, V, S, tp, ko);
+  if (rule != AGZ_KO_SIMPLE) {
+    uint64_t* K = sk_keybuf(w, S);
+    uint64_t* chunk = K + V.AP;
+    sk_child_keys(w, V, S, K, tp, rule, board_key(w, V, S.sb, tp, rule));
+    for (int at = 0; at < cnt; at += kSkChunk) {
+      const int take = cnt - at < kSkChunk ? cnt - at : kSkChunk;
+      w.for_each(take, [&](int i) { chunk[i] = seen[at + i]; });
+      sk_strike(w, V, S, K, chunk, take);
+    }
+  }
   w.for_each(V.A, [&](int a) { out[a] = S.flag[a]; });
   w.sync();
 }

@@ -12,6 +12,7 @@
 
 #include "../../include/agz.h"
 #include "../../include/agz_draws.h"
+#include "../../include/agz_superko.h"
 
 namespace agz {
 
@@ -126,7 +127,10 @@ constexpr int CT_EXP_TEMPERED = CT_COUNT + 4, CT_EXP_NOISED = CT_COUNT + 5, CT_E
 // four slots after the exploration ones, outside the enum for the same reason.
 constexpr int CT_UNC_LCB = CT_COUNT + 8, CT_UNC_LCB_OFF_MAX = CT_COUNT + 9, CT_UNC_LEVELS = CT_COUNT + 10,
               CT_UNC_RAISED = CT_COUNT + 11;
-constexpr int kCounterSlots = CT_COUNT + 12;    // what View::counters holds
+// Superko (agz_search.h superko_filter): nodes that lost at least one move to the rule / moves removed.
+// The two slots after the uncertainty ones, outside the enum for the same reason.
+constexpr int CT_SK_NODES = CT_COUNT + 12, CT_SK_MOVES = CT_COUNT + 13;
+constexpr int kCounterSlots = CT_COUNT + 14;    // what View::counters holds
 
 struct View {
   // dimensions
@@ -270,7 +274,17 @@ struct View {
   double pv_k, pv_prior, pv_weight;
   float* an_childS;                   // [rows][A]: the root's S row of an analysis / review run begun with moments on
   float* an_rootS;                    // [rows]
+  // Superko (agz_search_set_ko_rule; zero = off, the View{} of the host simulator and of fill_dims; include/agz_superko.h
+  // states the keys and the rule).  sk_key: every node's key under the rule, written by
+  // node_init_from_scratch.  sk_log: the keys of the positions a slot's game has left behind -- the history boards of the
+  // install, then every old root -- and sk_len how many (a side table: tests/hs.py mirrors GameState).  NULL = off
+  int32_t ko_rule;                    // AGZ_KO_*
+  uint64_t* sk_key;                   // [games*cap]
+  uint64_t* sk_log;                   // [games][7 + max_game_length]
+  int32_t* sk_len;                    // [games]
 };
+// the key log of one slot holds the 7 history boards and one key per ply
+AGZ_HD inline int sk_log_stride(const View& V) { return 7 + V.max_game_length; }
 
 // option values -> View fields, for the engine's setters (which check the arguments first) and the host simulator's
 inline void view_set_playout_cap(View& V, int fast_readouts, double full_prob) {

@@ -75,6 +75,9 @@ struct HipWave {
   __device__ __forceinline__ void amin(int32_t* p, int v) const { atomicMin(p, v); }
   __device__ __forceinline__ void amax(int32_t* p, int v) const { atomicMax(p, v); }
   __device__ __forceinline__ void aor(int32_t* p, int v) const { atomicOr(p, v); }
+  __device__ __forceinline__ void axor64(uint64_t* p, uint64_t v) const {
+    atomicXor((unsigned long long*)p, (unsigned long long)v);
+  }
   __device__ __forceinline__ void count(unsigned long long* p, unsigned long long v) const {
     if (lane == 0 && v) atomicAdd(p, v);
   }
@@ -87,15 +90,22 @@ struct HipWave {
   }
 };
 
-#define AGZ_SCRATCH(S)                                                        \
+#define AGZ_SCRATCH_ARRAYS                                                    \
   __shared__ int8_t s_sb[kPPMax];                                             \
   __shared__ int32_t s_label[kPPMax + kWave];                                 \
   __shared__ int32_t s_minlib[kPPMax];                                        \
   __shared__ int32_t s_maxlib[kPPMax];                                        \
   __shared__ int8_t s_flag[kAPMax];                                           \
   __shared__ double s_dbuf[kAPMax];                                           \
-  __shared__ int32_t s_path[kMaxdMax];                                        \
-  Scratch S{s_sb, s_label, s_minlib, s_maxlib, s_flag, s_dbuf, s_path};
+  __shared__ int32_t s_path[kMaxdMax];
+#define AGZ_SCRATCH(S)                                                        \
+  AGZ_SCRATCH_ARRAYS                                                          \
+  __shared__ uint64_t s_key[kAPMax + kSkChunk];                               \
+  Scratch S{s_sb, s_label, s_minlib, s_maxlib, s_flag, s_dbuf, s_path, s_key};
+// without the superko keys: for a kernel that the host launches only while View::sk_key is null
+#define AGZ_SCRATCH_NO_KEYS(S)                                                \
+  AGZ_SCRATCH_ARRAYS                                                          \
+  Scratch S{s_sb, s_label, s_minlib, s_maxlib, s_flag, s_dbuf, s_path, nullptr};
 
 // replay_position (board.jl:557-578) on the device: rebuild the 17 planes of positions of a game
 // from its move list.  One wave walks one game: it replays moves[0 .. nm) from

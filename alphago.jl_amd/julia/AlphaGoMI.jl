@@ -1033,6 +1033,61 @@ function apply_uncertainty!(e::Engine, lcb, puct_variance)
   nothing
 end
 
+# Superko (ours; include/agz.h agz_search_set_ko_rule and what follows it, include/agz_superko.h, DESIGN.md 5x): beside the
+# simple ko, a move that recreates a position the game has seen is refused -- :positional the board alone, :situational
+# the board with the side to move; :simple (the default) is the engine as it was.
+const KO_RULES = Dict(:simple => Int32(0), :positional => Int32(1), :situational => Int32(2))
+ko_rule_number(rule) = rule === nothing ? Int32(0) : rule isa Integer ? Int32(rule) : KO_RULES[Symbol(rule)]
+function set_ko_rule!(e::Engine, rule = :simple)
+  check(e, ccall((:agz_search_set_ko_rule, libagz), Int32, (Ptr{Cvoid}, Int32), e.handle, ko_rule_number(rule)))
+end
+# (nodes that lost at least one move to the rule, moves removed)
+function superko_counts(e::Engine)
+  out = zeros(UInt64, 2)
+  check(e, ccall((:agz_search_superko_counts, libagz), Int32, (Ptr{Cvoid}, Ptr{UInt64}), e.handle, out))
+  (Int(out[1]), Int(out[2]))
+end
+function node_key(e::Engine, g::Integer, node::Integer)
+  out = Ref{UInt64}(0)
+  check(e, ccall((:agz_tree_node_key, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{UInt64}), e.handle, g, node, out))
+  out[]
+end
+function node_legal(e::Engine, g::Integer, node::Integer, A::Integer)
+  out = zeros(Int8, A)
+  check(e, ccall((:agz_tree_node_legal, libagz), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Int8}), e.handle, g, node, out))
+  out
+end
+# the keys of B positions (boards Int8 [P, B], to_play Int8 [B]) under `rule`
+function position_keys(e::Engine, boards::Matrix{Int8}, to_play::Vector{Int8}, rule = :positional)
+  out = zeros(UInt64, length(to_play))
+  check(e, ccall((:agz_go_keys, libagz), Int32, (Ptr{Cvoid}, Ptr{Int8}, Ptr{Int8}, Int32, Int32, Ptr{UInt64}), e.handle,
+                 boards, to_play, length(to_play), ko_rule_number(rule), out))
+  out
+end
+# all_legal_moves under `rule`; seen: one vector of keys per position
+function legal_moves_seen(e::Engine, boards::Matrix{Int8}, to_play::Vector{Int8}, ko::Vector{Int32}, seen, A::Integer,
+                          rule = :positional)
+  B = length(to_play)
+  off = Int64[0; cumsum(length.(seen))]
+  flat = UInt64[k for s in seen for k in s]
+  push!(flat, 0)
+  out = zeros(Int8, A, B)
+  check(e, ccall((:agz_go_legal_seen, libagz), Int32,
+                 (Ptr{Cvoid}, Ptr{Int8}, Ptr{Int8}, Ptr{Int32}, Ptr{UInt64}, Ptr{Int64}, Int32, Int32, Ptr{Int8}), e.handle,
+                 boards, to_play, ko, flat, off, B, ko_rule_number(rule), out))
+  out
+end
+# host only, no engine
+function position_key(board::Vector{Int8}, to_play::Integer, rule = :positional)
+  out = Ref{UInt64}(0)
+  st = ccall((:agz_go_position_key, libagz), Int32, (Ptr{Int8}, Int32, Int32, Int32, Ptr{UInt64}), board, length(board),
+             to_play, ko_rule_number(rule), out)
+  st == 0 || error("position_key: to_play is +-1, rule one of :simple, :positional, :situational")
+  out[]
+end
+# the keyword ko_rule = of selfplay, train, analyze, review, evaluate and MCTSPlayer: nothing asked, nothing set
+apply_ko_rule!(e::Engine, ko_rule) = ko_rule === nothing ? nothing : set_ko_rule!(e, ko_rule)
+
 # the keywords root_policy_temperature = / root_noise = (total_alpha, shaped) / move_temperature = of selfplay, train and
 # MCTSPlayer (analyze and review take move_temperature): nothing asked, nothing set
 function apply_explore!(e::Engine, root_policy_temperature, root_noise, move_temperature)

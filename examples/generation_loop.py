@@ -3,7 +3,7 @@
 self-play -> replay arena -> training batches -> optimiser step -> arena match -> checkpoint.
 
     python examples/generation_loop.py [--board 9] [--tower 2] [--games 32] [--readouts 64] [--reanalyze]
-                                       [--surprise RHO] [--explore] [--uncertainty]
+                                       [--surprise RHO] [--explore] [--uncertainty] [--ko-rule RULE]
 
 What runs where:
   selfplay          G concurrent games on the device (one wave per tree, one network batch per step)
@@ -56,6 +56,8 @@ def main(argv=None):
                     help="KataGo's root policy temperature, shaped root noise and move temperature in self-play")
     ap.add_argument("--uncertainty", action="store_true",
                     help="value moments, the move by lower confidence bound and variance-scaled exploration")
+    ap.add_argument("--ko-rule", default=None, choices=["simple", "positional", "situational"], metavar="RULE",
+                    help="superko in self-play and in the arena match: positional or situational repetition is refused")
     args = ap.parse_args(argv)
 
     env = ag.GoEnv(args.board)
@@ -68,7 +70,8 @@ def main(argv=None):
                        move_temperature=(0.75, 0.15, args.board))
     # values of the kind KataGo ships (no strength claim: there is no trained network here)
     uncertainty = dict(lcb=(5.0, 1, 0.15), puct_variance=(0.85, 0.4, 2.0)) if args.uncertainty else {}
-    records = ag.selfplay(env, cur, args.readouts, games=args.games, seed=1, **explore, **uncertainty)
+    ko = dict(ko_rule=args.ko_rule) if args.ko_rule else {}      # (ours) agz_search_set_ko_rule, DESIGN.md §5x
+    records = ag.selfplay(env, cur, args.readouts, games=args.games, seed=1, **explore, **uncertainty, **ko)
     buf = ag.ReplayBuffer(env, memory_size=500000)
     buf.extend(records)
     print(f"self-play: {len(records)} games, {len(buf)} positions, "
@@ -112,7 +115,7 @@ def main(argv=None):
         eng.close()
 
     ok, st = ag.evaluate(env, cur, prev, num_games=args.eval_games, ro=args.readouts, seed=2, return_stats=True,
-                         **uncertainty)
+                         **uncertainty, **ko)
     print(f"evaluate: Black (candidate) won {st.games_won}/{st.num_games} -> {'keep' if ok else 'revert'}")
 
     with tempfile.TemporaryDirectory() as d:

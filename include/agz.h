@@ -877,6 +877,41 @@ agz_status agz_analyze_child_S(agz_engine* e, float* child_S, float* root_S);
  * AGZ_BAD_ARGUMENT: an output is NULL. */
 agz_status agz_value_lcb(float n, float w, float s, int32_t to_play, double z, double* mean, double* sd, double* lcb);
 agz_status agz_puct_variance_factor(float n, float w, float s, double k, double prior, double prior_weight, double* out);
+
+/* Superko (ours; the keys and the rule are include/agz_superko.h): beside the simple ko of board.jl, which
+ * stays, a move is refused when it recreates a position the game has seen -- the board alone (AGZ_KO_POSITIONAL) or the
+ * board with the side to move (AGZ_KO_SITUATIONAL).  AGZ_KO_SIMPLE, the default, is the reference's rule and leaves
+ * every output as it was.  The seen set of a node: its own position, its ancestors up to the root, the roots the slot has
+ * left behind since its install, and the history_len boards handed to that install (start tables, agz_tree_init,
+ * analysis and review starts).  Positions older than a supplied history are unknown to the rule.  Pass is always legal.
+ * The rule lives where a node's legal mask is written, so it holds in every search the engine runs: self-play, the
+ * arena, analysis, review, reanalysis and single trees.  Records, features and meta.ko are unchanged.
+ * Known limit: positions are compared by 64-bit keys, so a key collision forbids a legal move.
+ * Review and reanalysis: review_next_ply gives a game up at a recorded move that is not in the root's mask, so under a
+ * rule a game recorded without it can be given up from that ply on, with the existing status (AGZ_BAD_ARGUMENT rows)
+ * and counters; reanalysis skips and counts such rows as it does other invalid ones.
+ * The setter synchronises and restarts the two counters.  Refused (AGZ_BAD_ARGUMENT, the setting in force kept): an
+ * unknown rule; games of a run still being played; between agz_tree_search_select and agz_tree_search_incorporate.
+ * The key arrays (8 bytes per node, 8 * (7 + max_game_length) bytes per slot) are allocated when a rule is first taken. */
+#include "agz_superko.h"
+agz_status agz_search_set_ko_rule(agz_engine* e, int32_t rule);
+/* out[0] = nodes that lost at least one move to the rule, out[1] = moves removed; since the later of the setter call and agz_selfplay_start.  Synchronises. */
+agz_status agz_search_superko_counts(agz_engine* e, uint64_t* out /* [2] */);
+/* the key of `node` of single tree g under the rule in force; with no rule set, its position key computed on demand */
+agz_status agz_tree_node_key(agz_engine* e, int32_t g, int32_t node, uint64_t* key);
+/* the legal mask of `node` as the search reads it: out int8[A] */
+agz_status agz_tree_node_legal(agz_engine* e, int32_t g, int32_t node, int8_t* out /* [A] */);
+/* the keys of B positions under `rule` (AGZ_KO_SIMPLE: position keys); SoA as agz_go_legal, one launch */
+agz_status agz_go_keys(agz_engine* e, const int8_t* boards, const int8_t* to_play, int32_t B, int32_t rule,
+                       uint64_t* keys_out /* [B] */);
+/* all_legal_moves under `rule`: position b is refused the moves whose resulting key is one of the caller's
+ * seen_keys[seen_off[b] .. seen_off[b+1]) (seen_off int64[B + 1], ascending from 0); one launch */
+agz_status agz_go_legal_seen(agz_engine* e, const int8_t* boards, const int8_t* to_play, const int32_t* ko,
+                             const uint64_t* seen_keys, const int64_t* seen_off, int32_t B, int32_t rule,
+                             int8_t* legal_out /* [B][A] */);
+/* agz_position_key of include/agz_superko.h; host only, needs no engine.  AGZ_BAD_ARGUMENT: a NULL pointer, an unknown
+ * rule, to_play not +-1. */
+agz_status agz_go_position_key(const int8_t* board, int32_t P, int32_t to_play, int32_t rule, uint64_t* out);
 agz_status agz_analyze_progress(agz_engine* e, int64_t* done_out);
 /* out[B], child_N / child_W / prior [B][A] (the root's rows when the search ended); any of them may be NULL */
 agz_status agz_analyze_results(agz_engine* e, agz_analysis* out, float* child_N, float* child_W, float* prior);

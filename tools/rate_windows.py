@@ -79,6 +79,7 @@ def windows_of(eng, args, modes, configure, collect, prelude, counts=None, profi
                 eng.profile_search(False)
                 w["search_kernels_ms_per_step"] = round(float(sum(search_ms.values())) / max(search_steps, 1), 4)
                 w["k_pre_us_per_step"] = round(1e3 * float(search_ms.get("k_pre", 0.0)) / max(search_steps, 1), 2)
+                w["k_expand_us_per_step"] = round(1e3 * float(search_ms.get("k_expand", 0.0)) / max(search_steps, 1), 2)
             s1, c1 = eng.stats(), counts(eng) if counts else None
             moves = s1["positions"] - s0["positions"]
             w.update(moves=moves, moves_per_s=round(moves / dt, 1),
