@@ -194,6 +194,8 @@ class Engine {
   void require_between_games(const char* what);
   template <class Write>
   void set_option(const char* what, bool single_trees, Write write, int first, int n);
+  template <class Visit, class... T>
+  void alloc_group(Visit visit, DevBuf<T>&... own);
   template <class T>
   void read_counters(int first, int n, T* out);
   template <class Launch>

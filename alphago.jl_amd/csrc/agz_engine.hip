@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <tuple>
 
 #include "../../include/agz_value_target.h"
 #include "agz_wave.h"
@@ -736,23 +737,30 @@ static_assert(CT_UNC_LCB_OFF_MAX == CT_UNC_LCB + 1 && CT_UNC_LEVELS == CT_UNC_LC
               "the four counters are cleared and read as one run");
 void Engine::uncertainty_counts(uint64_t out[4]) { read_counters(CT_UNC_LCB, 4, out); }
 
+// the middle of a lazy setter: the arrays of one optional group -- `own`, in the order of the group's visitor of
+// agz_layout.h, which states their sizes -- allocated and zeroed as temporaries, waited for, then swapped in.  An
+// allocation that fails throws here, with `own` and so the option as they were
+template <class Visit, class... T>
+void Engine::alloc_group(Visit visit, DevBuf<T>&... own) {
+  size_t count[sizeof...(T)], k = 0;
+  View dims = V_;
+  visit(dims, [&](auto*&, size_t n) { count[k++] = n; });
+  std::tuple<DevBuf<T>...> fresh;
+  std::apply([&](auto&... b) {
+    k = 0;
+    (b.alloc(count[k++]), ...);
+    (b.zero(stream_), ...);
+    wait();
+    (b.swap(own), ...);
+  }, fresh);
+}
+
 void Engine::set_value_moments(int on) {
   check_explore("value moments", value_moments_refusal(V_, on));
   // the state checks first (games in flight, a select phase awaiting its incorporate): a call they refuse allocates
-  // nothing.  Then the arrays, made the first time the option goes on (a row the size of childW's, and one float per
-  // slot); an allocation that fails throws here, with the option as it was
+  // nothing.  Then the arrays, made the first time the option goes on
   set_option("value moments", true, [](View&) {}, 0, 0);
-  if (on && !child_s_.p) {
-    const size_t n = (size_t)V_.games * V_.cap * V_.AP;
-    DevBuf<float> c, r;
-    c.alloc(n);
-    r.alloc((size_t)V_.games);
-    c.zero(stream_);
-    r.zero(stream_);
-    wait();
-    child_s_.swap(c);
-    root_s_.swap(r);
-  }
+  if (on && !child_s_.p) alloc_group([](View& V, auto f) { for_each_moment_buffer(V, f); }, child_s_, root_s_);
   set_option("value moments", true, [&](View& V) {
     V.childS = on ? child_s_.p : nullptr;
     V.rootS = on ? root_s_.p : nullptr;
@@ -767,20 +775,8 @@ void Engine::superko_counts(uint64_t out[2]) { read_counters(CT_SK_NODES, 2, out
 void Engine::set_ko_rule(int rule) {
   AGZ_REQUIRE(agz_ko_rule_valid(rule), AGZ_BAD_ARGUMENT, "ko rule: %d is not 0 (simple), 1 (positional) or 2 (situational)", rule);
   set_option("ko rule", true, [](View&) {}, 0, 0);
-  if (rule != AGZ_KO_SIMPLE && !sk_key_.p) {
-    DevBuf<uint64_t> k, l;
-    DevBuf<int32_t> n;
-    k.alloc((size_t)V_.games * V_.cap);
-    l.alloc((size_t)V_.games * sk_log_stride(V_));
-    n.alloc((size_t)V_.games);
-    k.zero(stream_);
-    l.zero(stream_);
-    n.zero(stream_);
-    wait();
-    sk_key_.swap(k);
-    sk_log_.swap(l);
-    sk_len_.swap(n);
-  }
+  if (rule != AGZ_KO_SIMPLE && !sk_key_.p)
+    alloc_group([](View& V, auto f) { for_each_superko_buffer(V, f); }, sk_key_, sk_log_, sk_len_);
   set_option("ko rule", true, [&](View& V) {
     const bool on = rule != AGZ_KO_SIMPLE;
     V.ko_rule = rule;

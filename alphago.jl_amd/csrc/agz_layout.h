@@ -122,4 +122,21 @@ inline void for_each_buffer(View& V, F&& f) {
   f(V.gumbel, (size_t)V.games);
 }
 
+// The optional array groups, in the same form.  fill_dims and for_each_buffer leave their pointers null (off); the
+// engine's setter and the simulator's allocate a group through its visitor the first time the option goes on, so the
+// element counts are stated here only.
+// the value moments (agz_search_set_value_moments)
+template <class F>
+inline void for_each_moment_buffer(View& V, F&& f) {
+  f(V.childS, (size_t)V.games * V.cap * V.AP);
+  f(V.rootS, (size_t)V.games);
+}
+// the superko keys (agz_search_set_ko_rule)
+template <class F>
+inline void for_each_superko_buffer(View& V, F&& f) {
+  f(V.sk_key, (size_t)V.games * V.cap);
+  f(V.sk_log, (size_t)V.games * sk_log_stride(V));
+  f(V.sk_len, (size_t)V.games);
+}
+
 }  // namespace agz

@@ -1,6 +1,6 @@
 """What the GPU tests of the search options share (test_gpu_starts.py, test_gpu_playout_cap.py,
-test_gpu_forced_playouts.py, test_gpu_gumbel.py, test_gpu_symmetry.py, test_gpu_puct.py, test_gpu_explore.py;
-test_gpu_train_batched.py takes the arena helpers): engines with a peaked policy, setting the options of an engine or a
+test_gpu_forced_playouts.py, test_gpu_gumbel.py, test_gpu_symmetry.py, test_gpu_puct.py, test_gpu_explore.py,
+test_gpu_uncertainty.py, test_gpu_superko.py; test_gpu_train_batched.py takes the arena helpers): engines with a peaked policy, setting the options of an engine or a
 simulator from one dict, playing a run to its records, a record against another record or against the twin's game
 (tests/selfplay_twin.py), and train() against the same schedule composed of single calls, whose games are the twin's on
 the weights in force round by round.  Test infrastructure only."""
@@ -13,6 +13,7 @@ import explore_twin as ex
 import hs
 import orc
 import selfplay_twin as tw
+import superko_twin as sk
 from alphago_jl_amd import symmetry as sy
 from gpu_common import GpuNetForOracle, pos_soa
 from test_gpu_analysis import api_positions        # noqa: F401  (the API positions and games that the option files
@@ -91,9 +92,14 @@ def apply(eng, st):
 
 def configure(x, opt):
     """the options of ag.Engine or hs.Sim x from opt: starts (oracle positions), cap (fast readouts, full probability),
-    forced (k, prune), gumbel (m), symmetry (random), explore (a setting of explore_twin).  A key left out is a setter
-    not called."""
+    forced (k, prune), gumbel (m), symmetry (random), explore (a setting of explore_twin), puct ((r, r_root), c_base),
+    lcb (z, min_visits, min_ratio) and pv (k, prior, weight) with moments (left out or None: "a rule is asked for"),
+    ko_rule (0 simple, 1 positional, 2 situational).  A key left out -- or, of the last five, None -- is a setter not
+    called; a simulator's setter that returns a status is held to OK."""
     sim = isinstance(x, hs.Sim)
+
+    def ok(status):                  # (an engine's setter raises instead)
+        assert not sim or status == ag._lib.OK, status
     if opt.get("starts"):
         if sim:
             x.set_starts(opt["starts"])
@@ -110,6 +116,18 @@ def configure(x, opt):
         x.set_symmetry(8 if sim else "random")
     if opt.get("explore") is not None:
         x.apply(opt["explore"]) if sim else apply(x, opt["explore"])
+    if opt.get("puct") is not None:
+        fpu, c_base = opt["puct"]
+        x.set_puct(1, *fpu, c_base) if sim else x.set_puct(fpu, c_base)
+    lcb, pv = opt.get("lcb"), opt.get("pv")
+    if (lcb is not None or pv is not None) if opt.get("moments") is None else opt["moments"]:
+        ok(x.set_value_moments(True))
+    if lcb is not None:
+        ok(x.set_lcb(*lcb) if sim else x.set_lcb(lcb))
+    if pv is not None:
+        ok(x.set_puct_variance(*pv) if sim else x.set_puct_variance(pv))
+    if opt.get("ko_rule") is not None:
+        ok(x.set_ko_rule(opt["ko_rule"] if sim else sk.RULE_NAMES[opt["ko_rule"]]))
 
 
 def play(eng, games, network=None, white=None, chunk=8, sort=True):

@@ -54,6 +54,8 @@ struct SimWave {
 
 struct Sim {
   agz::View V{};
+  agz::View made{};                    // V's dimensions, and the arrays of the optional groups (agz_layout.h) once made:
+                                       // V's own pointers to them are null while the option is off
   std::vector<void*> bufs;
   std::vector<int8_t> sb;
   std::vector<int32_t> label, minlib, maxlib, path;
@@ -71,8 +73,9 @@ void alloc_one(Sim* s, T*& p, size_t n) {
   s->bufs.push_back(p);
 }
 
-void clear_explore_counts(agz::View& V) {
-  for (int i = 0; i < 4; ++i) V.counters[agz::CT_EXP_TEMPERED + i] = 0;
+// the counters [first, first + n) of an option restart at its setters (hs_start clears the enum's counters only)
+void clear_counts(agz::View& V, int first, int n) {
+  for (int i = 0; i < n; ++i) V.counters[first + i] = 0;
 }
 
 }  // namespace
@@ -82,6 +85,7 @@ extern "C" {
 void* hs_create(const agz_config* cfg) {
   Sim* s = new Sim();
   agz::fill_dims(s->V, *cfg);
+  s->made = s->V;
   agz::for_each_buffer(s->V, [&](auto*& p, size_t n) { alloc_one(s, p, n); });
   s->sb.resize(s->V.PP);
   s->label.resize(s->V.PP + 64);
@@ -344,8 +348,7 @@ int hs_pruned_pi(void* h, int g, int node, double k, float* out) {
 void hs_set_gumbel(void* h, int m, double c_visit, double c_scale) {
   agz::View& V = ((Sim*)h)->V;
   agz::view_set_gumbel(V, m, c_visit, c_scale);
-  V.counters[agz::CT_GUMBEL_BEGUN] = 0;
-  V.counters[agz::CT_GUMBEL_HALVED] = 0;
+  clear_counts(V, agz::CT_GUMBEL_BEGUN, 2);
 }
 
 // out[0] = Gumbel searches begun, out[1] = halvings made
@@ -403,8 +406,7 @@ int hs_gumbel_schedule(int n, int m0, int32_t* out, int cap) {
 void hs_set_puct(void* h, int fpu_on, double r, double r_root, double c_base) {
   agz::View& V = ((Sim*)h)->V;
   agz::view_set_puct(V, fpu_on, r, r_root, c_base);
-  V.counters[agz::CT_PUCT_LEVELS] = 0;
-  V.counters[agz::CT_PUCT_UNVISITED] = 0;
+  clear_counts(V, agz::CT_PUCT_LEVELS, 2);
 }
 
 // out[0] = tree levels scored under an active rule, out[1] = those that picked an unvisited child
@@ -448,7 +450,7 @@ int hs_set_root_policy_temperature(void* h, int on, double early, double late, d
   agz::View& V = ((Sim*)h)->V;
   if (agz::explore_schedule_refusal(V, on, early, late, halflife, 0.1)) return AGZ_BAD_ARGUMENT;
   agz::view_set_root_policy_temperature(V, on, early, late, halflife);
-  clear_explore_counts(V);
+  clear_counts(V, agz::CT_EXP_TEMPERED, 4);
   return AGZ_OK;
 }
 
@@ -456,7 +458,7 @@ int hs_set_root_noise(void* h, double total_alpha, int shaped) {
   agz::View& V = ((Sim*)h)->V;
   if (agz::explore_noise_refusal(V, total_alpha, shaped)) return AGZ_BAD_ARGUMENT;
   agz::view_set_root_noise(V, total_alpha, shaped);
-  clear_explore_counts(V);
+  clear_counts(V, agz::CT_EXP_TEMPERED, 4);
   return AGZ_OK;
 }
 
@@ -464,7 +466,7 @@ int hs_set_move_temperature(void* h, int on, double early, double late, double h
   agz::View& V = ((Sim*)h)->V;
   if (agz::explore_schedule_refusal(V, on, early, late, halflife, 0.0)) return AGZ_BAD_ARGUMENT;
   agz::view_set_move_temperature(V, on, early, late, halflife);
-  clear_explore_counts(V);
+  clear_counts(V, agz::CT_EXP_TEMPERED, 4);
   return AGZ_OK;
 }
 
@@ -498,6 +500,174 @@ void hs_set_pick_case(void* h, int g, const float* child_N, unsigned long long g
   for (int a = 0; a < V.A; ++a) V.childN[ni * V.AP + a] = child_N[a];
   V.gs[g].game_id = game_id;
   V.meta[ni].n = n;
+}
+
+// ---- value uncertainty (View::childS / rootS, lcb_* / pv_*; agz_search_set_value_moments / _set_lcb /
+// _set_puct_variance).  The three setters: the engine's own checks (agz_state.h), AGZ_OK or
+// AGZ_BAD_ARGUMENT with the setting in force kept; the four counters restart at every setter that is taken.  The moment
+// arrays are made the first time the option goes on and live as long as the Sim.
+int hs_set_value_moments(void* h, int on) {
+  Sim* s = (Sim*)h;
+  agz::View& V = s->V;
+  if (agz::value_moments_refusal(V, on)) return AGZ_BAD_ARGUMENT;
+  if (on && !s->made.childS)
+    agz::for_each_moment_buffer(s->made, [&](auto*& p, size_t n) { alloc_one(s, p, n); });
+  V.childS = on ? s->made.childS : nullptr;
+  V.rootS = on ? s->made.rootS : nullptr;
+  clear_counts(V, agz::CT_UNC_LCB, 4);
+  return AGZ_OK;
+}
+
+int hs_set_lcb(void* h, double z, int min_visits, double min_ratio) {
+  agz::View& V = ((Sim*)h)->V;
+  if (agz::lcb_refusal(V, z, min_visits, min_ratio)) return AGZ_BAD_ARGUMENT;
+  agz::view_set_lcb(V, z, min_visits, min_ratio);
+  clear_counts(V, agz::CT_UNC_LCB, 4);
+  return AGZ_OK;
+}
+
+int hs_set_puct_variance(void* h, double k, double prior, double prior_weight) {
+  agz::View& V = ((Sim*)h)->V;
+  if (agz::puct_variance_refusal(V, k, prior, prior_weight)) return AGZ_BAD_ARGUMENT;
+  agz::view_set_puct_variance(V, k, prior, prior_weight);
+  clear_counts(V, agz::CT_UNC_LCB, 4);
+  return AGZ_OK;
+}
+
+// out[8] = moments on, z, min_visits, min_ratio, k, prior, prior_weight, 0: the setting in force
+void hs_uncertainty_setting(void* h, double* out) {
+  const agz::View& V = ((Sim*)h)->V;
+  out[0] = V.childS ? 1.0 : 0.0;
+  out[1] = V.lcb_z; out[2] = (double)V.lcb_min_visits; out[3] = V.lcb_min_ratio;
+  out[4] = V.pv_k; out[5] = V.pv_prior; out[6] = V.pv_weight; out[7] = 0.0;
+}
+
+// out[4] = moves picked under the LCB rule, those off the most visited child, levels scored under a variance factor,
+// those with factor > 1
+void hs_uncertainty_counts(void* h, unsigned long long* out) {
+  const agz::View& V = ((Sim*)h)->V;
+  for (int i = 0; i < 4; ++i) out[i] = V.counters[agz::CT_UNC_LCB + i];
+}
+
+// a node's own S; the S row of its children (NULL with moments off)
+float hs_node_S(void* h, int g, int node) {
+  Sim* s = (Sim*)h;
+  return s->V.childS ? *agz::slotS(s->V, g, node) : 0.f;
+}
+float* hs_node_row_S(void* h, int g, int node) {
+  Sim* s = (Sim*)h;
+  return s->V.childS ? s->V.childS + agz::node_index(s->V, g, node) * s->V.AP : nullptr;
+}
+
+// hand-made own statistics of slot g's root: W, and with moments on S (hs_game_set has the root's N)
+void hs_root_set(void* h, int g, float W, float S) {
+  Sim* s = (Sim*)h;
+  s->V.gs[g].rootW = W;
+  if (s->V.rootS) s->V.rootS[g] = S;
+}
+
+// what k_tree_child_lcb runs: child_lcb_rows of `node` of slot g under z; mean, sd, lcb double[A] each
+int hs_child_lcb(void* h, int g, int node, double z, double* mean, double* sd, double* lcb) {
+  Sim* s = (Sim*)h;
+  SimWave w;
+  if (!s->V.childS) return AGZ_BAD_ARGUMENT;
+  agz::child_lcb_rows(w, s->V, g, node, z, mean, sd, lcb);
+  return AGZ_OK;
+}
+
+// the arithmetic of include/agz_uncertainty.h and its square root, for the restatement of tests/uncertainty_twin.py
+double hs_sqrt(double x) { return agz_sqrt(x); }
+void hs_value_lcb(float n, float w, float s, int to_play, double z, double* out /* mean, sd, lcb */) {
+  const agz_value_stats st = agz_child_stats(n, w, s);
+  out[0] = st.mean;
+  out[1] = st.sd;
+  out[2] = agz_stats_lcb(st, (float)to_play, z);
+}
+double hs_variance_factor(float n, float w, float s, double k, double prior, double pw) {
+  return agz_variance_factor(n, w, s, k, prior, pw);
+}
+
+// ---- superko (View::ko_rule / sk_*; agz_search_set_ko_rule).  The setter: AGZ_OK, or AGZ_BAD_ARGUMENT
+// with the setting in force kept -- an unknown rule, a call inside a select / incorporate window of a single tree
+// (leaves recorded and not yet incorporated), a call while games are being played.  The two counters restart at every
+// call that is taken.  The key arrays are made the first time a superko rule is taken and live as long as the Sim.
+int hs_set_ko_rule(void* h, int rule) {
+  Sim* s = (Sim*)h;
+  agz::View& V = s->V;
+  if (!agz_ko_rule_valid(rule)) return AGZ_BAD_ARGUMENT;
+  for (int g = 0; g < V.games; ++g) {
+    const agz::GameState& G = V.gs[g];
+    if (G.phase == agz::G_MANUAL && G.nleaves > 0) return AGZ_BAD_ARGUMENT;
+    if (G.phase != agz::G_MANUAL && G.phase != agz::G_RETIRED && G.phase != agz::G_IDLE) return AGZ_BAD_ARGUMENT;
+  }
+  const bool on = rule != AGZ_KO_SIMPLE;
+  if (on && !s->made.sk_key)
+    agz::for_each_superko_buffer(s->made, [&](auto*& p, size_t n) { alloc_one(s, p, n); });
+  V.ko_rule = rule;
+  V.sk_key = on ? s->made.sk_key : nullptr;
+  V.sk_log = on ? s->made.sk_log : nullptr;
+  V.sk_len = on ? s->made.sk_len : nullptr;
+  clear_counts(V, agz::CT_SK_NODES, 2);
+  return AGZ_OK;
+}
+
+int hs_ko_rule(void* h) { return ((Sim*)h)->V.ko_rule; }
+
+// out[0] = nodes that lost at least one move, out[1] = moves removed
+void hs_superko_counts(void* h, unsigned long long* out) {
+  const agz::View& V = ((Sim*)h)->V;
+  out[0] = V.counters[agz::CT_SK_NODES];
+  out[1] = V.counters[agz::CT_SK_MOVES];
+}
+
+// a node's key under the rule in force; its position key with none
+unsigned long long hs_node_key(void* h, int g, int node) {
+  Sim* s = (Sim*)h;
+  const long ni = agz::node_index(s->V, g, node);
+  if (s->V.sk_key) return s->V.sk_key[ni];
+  return agz_position_key(s->V.board + ni * s->V.PP, s->V.P, 1, AGZ_KO_SIMPLE);
+}
+
+// the key log of slot g into out [7 + max_game_length]; returns its length (0 with no rule)
+int hs_game_log(void* h, int g, unsigned long long* out) {
+  const agz::View& V = ((Sim*)h)->V;
+  if (!V.sk_key) return 0;
+  const int n = V.sk_len[g];
+  for (int i = 0; i < n; ++i) out[i] = V.sk_log[(long)g * agz::sk_log_stride(V) + i];
+  return n;
+}
+
+// the flags of every node slot of game g: out uint8[cap] (NF_ALLOC = 4: the node is live)
+void hs_node_flags(void* h, int g, uint8_t* out) {
+  const agz::View& V = ((Sim*)h)->V;
+  for (int i = 0; i < V.cap; ++i) out[i] = V.meta[agz::node_index(V, g, i)].flags;
+}
+
+// the two batched entries, run on SimWave
+void hs_go_keys(void* h, const int8_t* boards, const int8_t* to_play, int B, int rule, unsigned long long* out) {
+  Sim* s = (Sim*)h;
+  SimWave w;
+  for (int b = 0; b < B; ++b) {
+    uint64_t k = 0;
+    agz::go_key_one(w, s->V, boards + (size_t)b * s->V.P, to_play[b], rule, &k);
+    out[b] = k;
+  }
+}
+void hs_go_legal_seen(void* h, const int8_t* boards, const int8_t* to_play, const int32_t* ko,
+                      const unsigned long long* seen_keys, const int64_t* seen_off, int B, int rule, int8_t* out) {
+  Sim* s = (Sim*)h;
+  SimWave w;
+  for (int b = 0; b < B; ++b)
+    agz::go_legal_seen_one(w, s->V, s->S, boards + (size_t)b * s->V.P, to_play[b], ko[b],
+                           (const uint64_t*)seen_keys + seen_off[b], (int)(seen_off[b + 1] - seen_off[b]), rule,
+                           out + (size_t)b * s->V.A);
+}
+
+// the arithmetic of include/agz_superko.h, for the restatement of tests/superko_twin.py
+unsigned long long hs_zobrist(int point, int colour) { return agz_zobrist(point, colour); }
+unsigned long long hs_white_to_play() { return AGZ_ZOBRIST_WHITE_TO_PLAY; }
+unsigned long long hs_position_key(const int8_t* board, int P, int to_play, int rule) {
+  return agz_position_key(board, P, to_play, rule);
 }
 
 // ---- batched analysis and game review (agz_analyze_start / agz_review_start; no lines, no reanalysis)

@@ -112,8 +112,9 @@ def lib():
         if not os.path.exists(os.path.join(d, "libhostsim.so")):
             raise
     L = C.CDLL(os.path.join(d, "libhostsim.so"))
-    vp, i, f, dbl = C.c_void_p, C.c_int, C.c_float, C.c_double
+    vp, i, f, dbl, ull = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_ulonglong
     P = C.POINTER
+    i8p, i32p = P(C.c_int8), P(C.c_int32)
     sig = {
         "hs_create": (vp, [P(AgzConfig)]), "hs_destroy": (None, [vp]), "hs_dims": (None, [vp, P(C.c_int32)]),
         "hs_start": (None, [vp, C.c_int64]), "hs_pre": (i, [vp]), "hs_leaf_features": (None, [vp, P(f)]),
@@ -153,6 +154,19 @@ def lib():
         "hs_analysis_start": (None, [vp, P(C.c_int8), P(ag._lib.PositionInfo), P(C.c_int8), C.c_int64, P(C.c_int16),
                                      P(C.c_int64), C.c_uint64]),
         "hs_analysis_results": (C.c_longlong, [vp, P(ag._lib.Analysis), P(f), P(f), P(f)]),
+        # value uncertainty
+        "hs_set_value_moments": (i, [vp, i]), "hs_set_lcb": (i, [vp, dbl, i, dbl]),
+        "hs_set_puct_variance": (i, [vp, dbl, dbl, dbl]), "hs_uncertainty_setting": (None, [vp, P(dbl)]),
+        "hs_uncertainty_counts": (None, [vp, P(ull)]), "hs_node_S": (f, [vp, i, i]),
+        "hs_node_row_S": (P(f), [vp, i, i]), "hs_child_lcb": (i, [vp, i, i, dbl, P(dbl), P(dbl), P(dbl)]),
+        "hs_root_set": (None, [vp, i, f, f]), "hs_sqrt": (dbl, [dbl]), "hs_value_lcb": (None, [f, f, f, i, dbl, P(dbl)]),
+        "hs_variance_factor": (dbl, [f, f, f, dbl, dbl, dbl]),
+        # superko
+        "hs_set_ko_rule": (i, [vp, i]), "hs_ko_rule": (i, [vp]),
+        "hs_superko_counts": (None, [vp, P(ull)]), "hs_node_key": (ull, [vp, i, i]), "hs_game_log": (i, [vp, i, P(ull)]),
+        "hs_node_flags": (None, [vp, i, P(C.c_uint8)]), "hs_go_keys": (None, [vp, i8p, i8p, i, i, P(ull)]),
+        "hs_go_legal_seen": (None, [vp, i8p, i8p, i32p, P(ull), P(C.c_int64), i, i, i8p]),
+        "hs_zobrist": (ull, [i, i]), "hs_white_to_play": (ull, []), "hs_position_key": (ull, [i8p, i, i, i]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -182,6 +196,14 @@ def p32(a):
 
 def pf(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def pd(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def pu64(a):
+    return a.ctypes.data_as(C.POINTER(C.c_ulonglong))
 
 
 def bits32(x):
@@ -385,6 +407,84 @@ class Sim:
     def set_pick_case(self, Nrow, game_id, n, g=0):
         row = np.ascontiguousarray(Nrow, np.float32)
         self.L.hs_set_pick_case(self.h, g, pf(row), int(game_id), int(n))
+
+    # ---- value uncertainty (agz_search_set_value_moments / _set_lcb / _set_puct_variance).  The setters return the
+    # status; gpu_options.configure asserts it
+    def set_value_moments(self, on=True):
+        return self.L.hs_set_value_moments(self.h, int(on))
+
+    def set_lcb(self, z=0.0, min_visits=1, min_ratio=0.0):
+        return self.L.hs_set_lcb(self.h, float(z), int(min_visits), float(min_ratio))
+
+    def set_puct_variance(self, k=0.0, prior=0.4, weight=2.0):
+        return self.L.hs_set_puct_variance(self.h, float(k), float(prior), float(weight))
+
+    def uncertainty_setting(self):
+        """(moments on, z, min_visits, min_ratio, k, prior, weight)"""
+        out = np.zeros(8, np.float64)
+        self.L.hs_uncertainty_setting(self.h, pd(out))
+        return (int(out[0]), out[1], int(out[2]), out[3], out[4], out[5], out[6])
+
+    def uncertainty_counts(self):
+        out = (C.c_ulonglong * 4)()
+        self.L.hs_uncertainty_counts(self.h, out)
+        return tuple(int(x) for x in out)
+
+    def S_(self, g, node):
+        return self.L.hs_node_S(self.h, g, node)
+
+    def row_S(self, g, node):
+        return np.ctypeslib.as_array(self.L.hs_node_row_S(self.h, g, node), shape=(self.AP,))[: self.A]
+
+    def child_lcb(self, node, z, g=0):
+        m, sd, l = np.zeros(self.A, np.float64), np.zeros(self.A, np.float64), np.zeros(self.A, np.float64)
+        assert self.L.hs_child_lcb(self.h, g, node, float(z), pd(m), pd(sd), pd(l)) == ag._lib.OK
+        return m, sd, l
+
+    # ---- superko (agz_search_set_ko_rule)
+    def set_ko_rule(self, rule):
+        """the status; gpu_options.configure asserts it"""
+        return self.L.hs_set_ko_rule(self.h, int(rule))
+
+    def ko_rule(self):
+        return self.L.hs_ko_rule(self.h)
+
+    def superko_counts(self):
+        out = (C.c_ulonglong * 2)()
+        self.L.hs_superko_counts(self.h, out)
+        return int(out[0]), int(out[1])
+
+    def node_key(self, node, g=0):
+        return int(self.L.hs_node_key(self.h, g, node))
+
+    def game_log(self, g=0):
+        out = np.zeros(7 + self.mgl, np.uint64)
+        n = self.L.hs_game_log(self.h, g, pu64(out))
+        return [int(x) for x in out[:n]]
+
+    def live_nodes(self, g=0):
+        out = np.zeros(self.cap, np.uint8)
+        self.L.hs_node_flags(self.h, g, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return [int(i) for i in np.nonzero(out & 4)[0]]
+
+    def position_keys(self, boards, to_play, rule):
+        B = len(to_play)
+        out = np.zeros(B, np.uint64)
+        self.L.hs_go_keys(self.h, p8(np.ascontiguousarray(boards, np.int8)), p8(np.ascontiguousarray(to_play, np.int8)), B,
+                          int(rule), pu64(out))
+        return out
+
+    def legal_moves(self, boards, to_play, ko, seen, rule):
+        """seen: one list of keys per position"""
+        B = len(to_play)
+        off = np.zeros(B + 1, np.int64)
+        off[1:] = np.cumsum([len(k) for k in seen])
+        flat = np.array([x for k in seen for x in k] + [0], np.uint64)
+        out = np.zeros((B, self.A), np.int8)
+        self.L.hs_go_legal_seen(self.h, p8(np.ascontiguousarray(boards, np.int8)), p8(np.ascontiguousarray(to_play, np.int8)),
+                                p32(np.ascontiguousarray(ko, np.int32)), pu64(flat), off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                B, int(rule), p8(out))
+        return out
 
     # ---- batched analysis and game review
     def analysis_start(self, positions, games=None, game_id_base=0):

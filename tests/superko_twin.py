@@ -1,143 +1,30 @@
-"""Superko (agz_search_set_ko_rule) for the tests (TEST INFRASTRUCTURE): the binding of
-tests/superko_sim/libsuperko_sim.so -- the host simulator of hs.Sim with the exports of the rule -- as a subclass of hs.Sim;
-the independent statement of the rule, which is go_shapes.ff_legal / ff_play plus a Python set of board bytes (positional)
-or of (board bytes, to_play) pairs (situational) and uses no keys at all; the keys of include/agz_superko.h restated in
-numpy from the header's text; and the fixtures both test files play: random legal games and hand-built cycles."""
-import ctypes as C
-import os
-import subprocess
+"""Superko (agz_search_set_ko_rule) for the tests (TEST INFRASTRUCTURE): the independent statement
+of the rule, which is go_shapes.ff_legal / ff_play plus a Python set of board bytes (positional) or of (board bytes,
+to_play) pairs (situational) and uses no keys at all; the keys of include/agz_superko.h restated in numpy from the
+header's text; and the fixtures both test files play: random legal games and hand-built cycles.  The simulator is hs.Sim,
+which has the setter; gpu_options.configure sets it from a dict."""
 from functools import lru_cache
 
 import numpy as np
 
 import alphago_jl_amd as ag
 import go_shapes as gs
-import hs
 from alphago_jl_amd.symmetry import transform_points
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "superko_sim")
 OK, BAD_ARGUMENT = ag._lib.OK, ag._lib.BAD_ARGUMENT
 SIMPLE, POSITIONAL, SITUATIONAL = 0, 1, 2
 RULES = (POSITIONAL, SITUATIONAL)
 RULE_NAMES = {SIMPLE: "simple", POSITIONAL: "positional", SITUATIONAL: "situational"}
 u64 = np.uint64
-
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    hs.lib()                                   # (hs.sig: the prototypes of every hs_* export, which this library has too)
-    try:
-        subprocess.run(["make", "-s", "-C", DIR], check=True)
-    except Exception:
-        if not os.path.exists(os.path.join(DIR, "libsuperko_sim.so")):
-            raise
-    L = C.CDLL(os.path.join(DIR, "libsuperko_sim.so"))
-    vp, i, P, ull = C.c_void_p, C.c_int, C.POINTER, C.c_ulonglong
-    i8p, i32p = P(C.c_int8), P(C.c_int32)
-    sig = dict(hs.sig)
-    sig.update({
-        "hk_destroy": (None, [vp]), "hk_set_ko_rule": (i, [vp, i]), "hk_ko_rule": (i, [vp]),
-        "hk_superko_counts": (None, [vp, P(ull)]), "hk_node_key": (ull, [vp, i, i]), "hk_game_log": (i, [vp, i, P(ull)]),
-        "hk_node_flags": (None, [vp, i, P(C.c_uint8)]), "hk_go_keys": (None, [vp, i8p, i8p, i, i, P(ull)]),
-        "hk_go_legal_seen": (None, [vp, i8p, i8p, i32p, P(ull), P(C.c_int64), i, i, i8p]),
-        "hk_zobrist": (ull, [i, i]), "hk_white_to_play": (ull, []), "hk_position_key": (ull, [i8p, i, i, i]),
-    })
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib = L
-    return L
-
-
-def pu64(a):
-    return a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+# for gpu_options.configure: the options that steer the same descent and the same pick_move as the rule -- the LCB pick,
+# the variance-scaled PUCT (both need the moments, which configure switches on) and the PUCT option (FPU reduction, c_base)
+COMBINED = dict(lcb=(5.0, 3, 0.15), pv=(0.85, 0.4, 2.0), puct=((0.2, 0.05), 19652.0))
 
 
 def soa(positions):
     """(boards int8[B][P], to_play int8[B], ko int32[B]) of a list of (board, to_play, ko, ...) tuples"""
     return (np.ascontiguousarray(np.stack([p[0] for p in positions]), np.int8),
             np.array([p[1] for p in positions], np.int8), np.array([p[2] for p in positions], np.int32))
-
-
-def seen_soa(key_lists):
-    off = np.zeros(len(key_lists) + 1, np.int64)
-    off[1:] = np.cumsum([len(k) for k in key_lists])
-    flat = np.array([x for k in key_lists for x in k] + [0], u64)
-    return flat, off
-
-
-class Sim(hs.Sim):
-    """hs.Sim on the library that also has the hk_* exports"""
-
-    def __init__(self, **cfg):
-        self.L = lib()
-        self.cfg = hs.default_config(**cfg)
-        self.h = self.L.hs_create(C.byref(self.cfg))
-        d = (C.c_int32 * 10)()
-        self.L.hs_dims(self.h, d)
-        (self.N, self.P, self.A, self.AP, self.cap, self.games, self.par, self.mgl, self.tau, self.maxd) = list(d)
-        self.setting = (0, 0.0, 0.0, 0.0)
-
-    def close(self):
-        if self.h:
-            self.L.hk_destroy(self.h)
-            self.h = None
-
-    def set_ko_rule(self, rule):
-        """the status; `configure` asserts it"""
-        return self.L.hk_set_ko_rule(self.h, int(rule))
-
-    def ko_rule(self):
-        return self.L.hk_ko_rule(self.h)
-
-    def superko_counts(self):
-        out = (C.c_ulonglong * 2)()
-        self.L.hk_superko_counts(self.h, out)
-        return int(out[0]), int(out[1])
-
-    def node_key(self, node, g=0):
-        return int(self.L.hk_node_key(self.h, g, node))
-
-    def game_log(self, g=0):
-        out = np.zeros(7 + self.mgl, u64)
-        n = self.L.hk_game_log(self.h, g, pu64(out))
-        return [int(x) for x in out[:n]]
-
-    def live_nodes(self, g=0):
-        out = np.zeros(self.cap, np.uint8)
-        self.L.hk_node_flags(self.h, g, out.ctypes.data_as(C.POINTER(C.c_uint8)))
-        return [int(i) for i in np.nonzero(out & 4)[0]]
-
-    def position_keys(self, boards, to_play, rule):
-        B = len(to_play)
-        out = np.zeros(B, u64)
-        self.L.hk_go_keys(self.h, hs.p8(np.ascontiguousarray(boards, np.int8)),
-                          hs.p8(np.ascontiguousarray(to_play, np.int8)), B, int(rule), pu64(out))
-        return out
-
-    def legal_moves(self, boards, to_play, ko, seen, rule):
-        """seen: one list of keys per position"""
-        B = len(to_play)
-        flat, off = seen_soa(seen)
-        out = np.zeros((B, self.A), np.int8)
-        self.L.hk_go_legal_seen(self.h, hs.p8(np.ascontiguousarray(boards, np.int8)),
-                                hs.p8(np.ascontiguousarray(to_play, np.int8)), hs.p32(np.ascontiguousarray(ko, np.int32)),
-                                pu64(flat), off.ctypes.data_as(C.POINTER(C.c_int64)), B, int(rule), hs.p8(out))
-        return out
-
-
-def configure(x, rule):
-    """the rule of an engine (ag.Engine) or a simulator (Sim) x"""
-    if isinstance(x, Sim):
-        assert x.set_ko_rule(rule) == OK
-    else:
-        x.set_ko_rule(RULE_NAMES[rule])
 
 
 # ---------------------------------------------------------------- the keys, restated from the text of include/agz_superko.h

@@ -4,9 +4,12 @@ tests/explore_twin.py, bit for bit; off against the simulator that never made th
 stand-alone address + undefined sanitizer build of the simulator (the same boards, readouts, options and counts, on a
 network and starts of its own); and the argument refusals, which the simulator's setters share with the engine (the
 refusals that depend on an engine's state are in tests/test_gpu_explore.py)."""
+import atexit
+import functools
 import os
 import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 import pytest
@@ -303,19 +306,33 @@ def _static_sanitizer_runtimes():
     return True
 
 
-def test_sanitizer_build_plays_the_game_set(tmp_path):
-    """hostsim.cpp with the main of explore_sanitize.cpp under -fsanitize=address,undefined (the `sanitize` target of
-    tests/hostsim/Makefile), a program of its own with both runtimes linked into it (so it starts in whatever environment the suite runs in, which is left as it is).
-    A check of memory and undefined behaviour, not of results: it plays the boards, readouts, setting, cap, forced
-    playouts, a table of three starts and the game counts of the sets above, but on a hash network and walk starts of
-    its own, not on PeakedNet and tw.random_starts.  Skipped where g++ or its static sanitizer runtimes are missing."""
+@functools.lru_cache(None)
+def _sanitizer_program():
+    """hostsim.cpp with the main of hostsim_sanitize.cpp under -fsanitize=address,undefined (the `sanitize` target of
+    tests/hostsim/Makefile), built once per test process into a directory of its own -> (the program, make's result)"""
+    d = tempfile.mkdtemp(prefix="hostsim_sanitize_")
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    exe = os.path.join(d, "hostsim_sanitize")
+    return exe, subprocess.run(["make", "-s", "-C", os.path.join(hs.HERE, "hostsim"), "sanitize", "SANITIZE_OUT=" + exe],
+                               capture_output=True, text=True)
+
+
+def run_sanitizer_part(part):
+    """one part of the sanitizer program (explore, uncertainty, superko): a program of its own with both runtimes linked
+    into it (so it starts in whatever environment the suite runs in, which is left as it is).  Skipped where g++ or its
+    static sanitizer runtimes are missing."""
     if not _static_sanitizer_runtimes():
         pytest.skip("no g++ with static libasan / libubsan")
-    exe = str(tmp_path / "explore_sanitize")
-    r = subprocess.run(["make", "-s", "-C", os.path.join(hs.HERE, "hostsim"), "sanitize", "SANITIZE_OUT=" + exe],
-                       capture_output=True, text=True)
+    exe, r = _sanitizer_program()
     assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
+    r = subprocess.run([exe, part], capture_output=True, text=True)
     print(r.stdout[-2000:])
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     assert "games played" in r.stdout and "ERROR" not in r.stderr
+
+
+def test_sanitizer_build_plays_the_game_set():
+    """The `explore` part.  A check of memory and undefined behaviour, not of results: it plays the boards, readouts,
+    setting, cap, forced playouts, a table of three starts and the game counts of the sets above, but on a hash network
+    and walk starts of its own, not on PeakedNet and tw.random_starts."""
+    run_sanitizer_part("explore")

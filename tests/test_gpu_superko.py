@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
+import gpu_options as go
 import hs
 import superko_twin as sk
 from gpu_options import RECORD, api_game, api_positions, peaked_engine, play, same_game, sharpen
@@ -91,9 +92,9 @@ def test_single_tree_nodes_equal_the_twin_and_the_simulator(N, rule):
     if f.N != N:
         pytest.skip(f"the two-group fixture lies at {f.N}x{f.N}")
     eng = rules_engine(N)
-    sim = sk.Sim(board_size=N, games=1, num_readouts=8, two_player_mode=1, max_nodes_per_game=4096 if N < 19 else 2600)
-    sk.configure(eng, rule)
-    sk.configure(sim, rule)
+    sim = hs.Sim(board_size=N, games=1, num_readouts=8, two_player_mode=1, max_nodes_per_game=4096 if N < 19 else 2600)
+    go.configure(eng, dict(ko_rule=rule))
+    go.configure(sim, dict(ko_rule=rule))
     assert eng.tree_init(0, f.board, to_play=f.to_play) == sim.tree_init(0, f.board, to_play=f.to_play)
     line = sk.Line(N, rule, f.board, f.to_play)
     walked = 0
@@ -144,14 +145,15 @@ def test_single_tree_nodes_equal_the_twin_and_the_simulator(N, rule):
 FIELDS = RECORD + ("resign_disabled", "final_score")
 
 
-def lockstep_games(N, rule, games, readouts=16, seed=3):
+def lockstep_games(N, rule, games, readouts=16, seed=3, options=None):
+    """-> (the engine's records, the simulator's, superko counts of both; with options, the uncertainty counts of both)"""
     cfg = dict(games=games, num_readouts=readouts, seed=seed, record_capacity_games=games + 8, c_puct=0.96,
                resign_threshold=-2.0, resign_disable_fraction=1.0)
     eng = peaked_engine(N, 1, **cfg)
     fwd = peaked_engine(N, 1, games=1, num_readouts=8, max_nodes_per_game=16)
-    sim = sk.Sim(board_size=N, **cfg)
-    sk.configure(eng, rule)
-    sk.configure(sim, rule)
+    sim = hs.Sim(board_size=N, **cfg)
+    go.configure(eng, dict(options or {}, ko_rule=rule))
+    go.configure(sim, dict(options or {}, ko_rule=rule))
     eng.start(games)
     sim.start(games)
     for step in range(20000):
@@ -161,6 +163,8 @@ def lockstep_games(N, rule, games, readouts=16, seed=3):
             break
     assert eng.records_count() == games
     out = (sorted(eng.records(), key=lambda r: r["game_id"]), sim.records(), eng.superko_counts(), sim.superko_counts())
+    if options:
+        out += (eng.uncertainty_counts(), sim.uncertainty_counts())
     for x in (eng, fwd):
         x.close()
     sim.close()
@@ -186,6 +190,19 @@ def test_counters_are_positive_somewhere():
     """the positional rule at 3x3 removes moves in these searches (the simulator's run of tests/test_superko.py does)"""
     recs, want, counts, wcounts = lockstep_games(3, POS, 8)
     assert counts == wcounts and counts[0] > 0 and counts[1] >= counts[0]
+
+
+def test_selfplay_with_lcb_variance_and_puct_options_equals_the_simulator():
+    """the combined case of tests/test_superko.py (3x3, 8 games, 16 readouts, seed 3: the positional rule with lcb,
+    puct_variance and the PUCT option) on the engine's own forward: records bit for bit, both sets of counters equal,
+    and every option exercised"""
+    recs, want, counts, wcounts, unc, wunc = lockstep_games(3, POS, 8, options=sk.COMBINED)
+    print(f"combined: superko {counts} / {wcounts}, uncertainty {unc} / {wunc}")
+    assert len(recs) == len(want) == 8
+    assert all(same_game(r, o, RECORD) for r, o in zip(recs, want))
+    assert counts == wcounts and unc == wunc
+    assert counts[0] > 0
+    assert unc[0] > 0 and unc[2] > 0
 
 
 # ---------------------------------------------------------------- c2. analyze, review, the arena at 5x5
@@ -269,9 +286,9 @@ def test_evaluate_equals_the_simulator_arena_under_the_rule():
     a, b = ag.NeuralNet(env, tower_height=1, seed=0), ag.NeuralNet(env, tower_height=1, seed=5)
     games = 2
     ok, st = ag.evaluate(env, a, b, num_games=games, ro=16, seed=2, return_stats=True, ko_rule="positional", c_puct=0.96)
-    sim = sk.Sim(board_size=5, games=2 * games, num_readouts=16, seed=2, arena_mode=1, record_capacity_games=games + 8,
+    sim = hs.Sim(board_size=5, games=2 * games, num_readouts=16, seed=2, arena_mode=1, record_capacity_games=games + 8,
                  c_puct=0.96)
-    sk.configure(sim, POS)
+    go.configure(sim, dict(ko_rule=POS))
     sim.start(games)
     for _ in range(20000):
         sim.step(a.engine.forward_features, b.engine.forward_features)

@@ -1,5 +1,5 @@
 """Value uncertainty on the device (agz_search_set_value_moments / _set_lcb / _set_puct_variance),
-engine against the host simulator (uncertainty_twin.Sim: agz_search.h lane-serial, on the engine's own forward), floats
+engine against the host simulator (hs.Sim: agz_search.h lane-serial, on the engine's own forward), floats
 bit for bit: self-play games with their counters and the S rows of the live roots; one single tree per register-row width
 of the descent with every node's rows and agz_tree_child_lcb, and hand-made rows with entries at the lane boundaries;
 analyze and review against the single-tree player; an arena; every refusal keeps the setting.  Tower 1 everywhere."""
@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
+import gpu_options as go
 import hs
 import uncertainty_twin as ut
 from gpu_options import RECORD, api_game, api_positions, peaked_engine, play, same_game, sharpen
@@ -36,9 +37,9 @@ def lockstep_games(lcb, pv, moments):
     counters, simulator counters, the live roots whose S rows were compared)"""
     eng = peaked_engine(5, 1, **{k: v for k, v in CFG.items() if k != "board_size"})
     fwd = peaked_engine(5, 1, games=1, num_readouts=8, max_nodes_per_game=16)
-    sim = ut.Sim(**CFG)
-    ut.configure(eng, lcb, pv, moments)
-    ut.configure(sim, lcb, pv, moments)
+    sim = hs.Sim(**CFG)
+    go.configure(eng, dict(lcb=lcb, pv=pv, moments=moments))
+    go.configure(sim, dict(lcb=lcb, pv=pv, moments=moments))
     eng.start(GAMES)
     sim.start(GAMES)
     compared = 0
@@ -114,9 +115,9 @@ def test_single_tree_equals_the_simulator(N):
     eng.init_synthetic(0)
     fwd = ag.Engine(board_size=N, tower_height=1, games=1, num_readouts=8, max_nodes_per_game=16)
     fwd.init_synthetic(0)
-    sim = ut.Sim(**cfg)
-    ut.configure(eng, LCB, PV)
-    ut.configure(sim, LCB, PV)
+    sim = hs.Sim(**cfg)
+    go.configure(eng, dict(lcb=LCB, pv=PV))
+    go.configure(sim, dict(lcb=LCB, pv=PV))
     root = eng.tree_init(0, np.zeros(N * N, np.int8))
     eng.set_draw(0, 11, 0)
     assert sim.tree_init(0, np.zeros(N * N, np.int8)) == root
@@ -234,9 +235,9 @@ def test_evaluate_equals_the_simulator_arena_under_lcb():
     a, b = ag.NeuralNet(env, tower_height=1, seed=0), ag.NeuralNet(env, tower_height=1, seed=5)
     games = 2
     ok, st = ag.evaluate(env, a, b, num_games=games, ro=16, seed=2, return_stats=True, lcb=LCB, c_puct=C_PUCT)
-    sim = ut.Sim(board_size=5, games=2 * games, num_readouts=16, seed=2, arena_mode=1, record_capacity_games=games + 8,
+    sim = hs.Sim(board_size=5, games=2 * games, num_readouts=16, seed=2, arena_mode=1, record_capacity_games=games + 8,
                  c_puct=C_PUCT)
-    ut.configure(sim, LCB, None)
+    go.configure(sim, dict(lcb=LCB))
     sim.start(games)
     for _ in range(20000):
         sim.step(a.engine.forward_features, b.engine.forward_features)
@@ -264,7 +265,7 @@ def test_refusals_keep_the_setting():
     assert L.agz_search_set_lcb(h, 1.0, 1, 0.0) == BAD_ARGUMENT and L.agz_search_set_puct_variance(h, 0.5, 0.4, 2.0) == BAD_ARGUMENT
     root = eng.tree_init(0, np.zeros(25, np.int8))
     d = np.zeros(26, f64)
-    assert L.agz_tree_child_lcb(h, 0, root, 1.0, ut.pd(d), ut.pd(d), ut.pd(d)) == BAD_ARGUMENT
+    assert L.agz_tree_child_lcb(h, 0, root, 1.0, hs.pd(d), hs.pd(d), hs.pd(d)) == BAD_ARGUMENT
     assert L.agz_tree_node_S(h, 0, root, C.byref(C.c_float())) == BAD_ARGUMENT
     env = ag.GoEnv(5)
     positions = api_positions(env, 3, 2, 6)

@@ -284,7 +284,8 @@ def test_pool_exhaustion_is_flagged():
 
 def test_hs_bindings_are_the_library():
     """every export of hostsim.cpp has its prototype in hs.sig and the table names nothing else (the names are read from
-    the source's extern "C" block, as hs.counter_names() reads the enum); and the search options share the one library"""
+    the source's extern "C" block, as hs.counter_names() reads the enum); and the search options share the one library:
+    no other *.so anywhere under tests/, and no translation unit around hostsim.cpp but its own sanitizer program"""
     import glob
     import os
     import re
@@ -294,6 +295,12 @@ def test_hs_bindings_are_the_library():
     body = re.search(r'extern "C" \{(.*)\}  // extern "C"', src, flags=re.S).group(1)
     body = re.sub(r"//[^\n]*", "", body)
     names = re.findall(r"^[A-Za-z_][\w:\* ]*?\b(hs_\w+)\(", body, flags=re.M)
-    assert len(names) == len(set(names)) > 50
+    assert len(names) == len(set(names)) >= 80
     assert sorted(names) == sorted(hs.sig)
     assert [os.path.basename(p) for p in glob.glob(os.path.join(d, "*.so"))] == ["libhostsim.so"]
+    rel = lambda p: os.path.relpath(p, hs.HERE)
+    assert [rel(p) for p in glob.glob(os.path.join(hs.HERE, "**", "*.so"), recursive=True)] == [
+        os.path.join("hostsim", "libhostsim.so")]
+    files = [p for p in glob.glob(os.path.join(hs.HERE, "**", "*"), recursive=True) if os.path.isfile(p)]
+    around = [rel(p) for p in files if re.search(rb'#\s*include\s*"[^"\n]*hostsim\.cpp"', open(p, "rb").read())]
+    assert around == [os.path.join("hostsim", "hostsim_sanitize.cpp")]

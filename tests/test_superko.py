@@ -1,17 +1,16 @@
 """Superko on the host (agz_search_set_ko_rule): the keys of include/agz_superko.h against a numpy
-restatement bit for bit, and the rule -- run by the host simulator (superko_twin.Sim: agz_search.h lane-serial) -- against
+restatement bit for bit, and the rule -- run by the host simulator (hs.Sim: agz_search.h lane-serial) -- against
 its independent statement, go_shapes.ff_legal / ff_play plus a Python set of boards (superko_twin.Line), which uses no
 keys: random legal play with a census of what it reaches, hand-built cycles in every image and both colourings, single
 trees, whole self-play games with their counters, the refusals, and a stand-alone sanitizer program."""
-import subprocess
-
 import numpy as np
 import pytest
 
 import go_shapes as gs
+import gpu_options
 import hs
 import superko_twin as sk
-from test_explore import _static_sanitizer_runtimes
+from test_explore import run_sanitizer_part
 
 u64 = np.uint64
 POS, SIT = sk.POSITIONAL, sk.SITUATIONAL
@@ -21,25 +20,25 @@ G_SEARCH = 3
 # ---------------------------------------------------------------- the header
 
 def test_keys_equal_the_restatement_bit_for_bit():
-    L = sk.lib()
-    assert L.hk_white_to_play() == sk.WHITE_TO_PLAY
+    L = hs.lib()
+    assert L.hs_white_to_play() == sk.WHITE_TO_PLAY
     pts = np.arange(0, 19 * 19 + 40)
     for colour in (1, -1):
         want = sk.zobrist(pts, np.full(len(pts), colour))
-        got = np.array([L.hk_zobrist(int(p), colour) for p in pts], u64)
+        got = np.array([L.hs_zobrist(int(p), colour) for p in pts], u64)
         assert (got == want).all()
     both = np.concatenate([sk.zobrist(pts, np.ones(len(pts))), sk.zobrist(pts, -np.ones(len(pts)))])
     assert len(set(both.tolist()) | {sk.WHITE_TO_PLAY, 0}) == 2 * len(pts) + 2, "the stone keys are distinct"
     rng = np.random.RandomState(5)
     for N in (2, 3, 9, 19):
-        sim = sk.Sim(board_size=N, games=1, num_readouts=4, max_nodes_per_game=8)
+        sim = hs.Sim(board_size=N, games=1, num_readouts=4, max_nodes_per_game=8)
         boards = rng.randint(-1, 2, size=(24, N * N)).astype(np.int8)
         boards[0] = 0
         tp = np.where(rng.rand(24) < 0.5, 1, -1).astype(np.int8)
         for rule in (sk.SIMPLE, POS, SIT):
             want = np.array([sk.np_key(b, t, rule) for b, t in zip(boards, tp)], u64)
             assert (sim.position_keys(boards, tp, rule) == want).all(), (N, rule)
-            host = np.array([L.hk_position_key(hs.p8(np.ascontiguousarray(b)), N * N, int(t), rule)
+            host = np.array([L.hs_position_key(hs.p8(np.ascontiguousarray(b)), N * N, int(t), rule)
                              for b, t in zip(boards, tp)], u64)
             assert (host == want).all(), (N, rule)
         assert sim.position_keys(boards[:1], tp[:1], POS)[0] == 0, "the empty board"
@@ -83,7 +82,7 @@ def sim_masks(sim, positions, rule):
 @pytest.mark.parametrize("N", sorted(sk.RANDOM_PLAY))
 def test_random_play_masks_equal_the_twin(N, rule):
     positions = sk.random_games(N, rule)
-    sim = sk.Sim(board_size=N, games=1, num_readouts=4, max_nodes_per_game=8)
+    sim = hs.Sim(board_size=N, games=1, num_readouts=4, max_nodes_per_game=8)
     got = sim_masks(sim, positions, rule)
     want = np.stack([p["legal"] for p in positions])
     bad = np.nonzero((got != want).any(axis=1))[0]
@@ -148,7 +147,7 @@ def test_hand_built_cycles(rule):
         assert refused == (rule in f.refused), (f.name, rule)
         by_size.setdefault(f.N, []).extend((f.name, i, p) for i, p in enumerate(positions))
     for N, rows in by_size.items():
-        sim = sims.setdefault(N, sk.Sim(board_size=N, games=1, num_readouts=4, max_nodes_per_game=8))
+        sim = sims.setdefault(N, hs.Sim(board_size=N, games=1, num_readouts=4, max_nodes_per_game=8))
         b, tp, ko = sk.soa([p for _, _, p in rows])
         got = sim.legal_moves(b, tp, ko, [p[3] for _, _, p in rows], rule)
         want = np.stack([p[4] for _, _, p in rows])
@@ -162,7 +161,7 @@ def test_a_pass_between_the_repetitions_splits_the_rules():
     """send two, capture, pass, pass, return one: the board of the start with the other side to move -- the positional rule
     refuses the return, the situational rule allows it"""
     f = [x for x in sk.fixtures() if x.name == "send_two_pass_pass_return_one_5/s0"][0]
-    sim = sk.Sim(board_size=5, games=1, num_readouts=4, max_nodes_per_game=8)
+    sim = hs.Sim(board_size=5, games=1, num_readouts=4, max_nodes_per_game=8)
     last = {}
     for rule in sk.RULES:
         positions, refused = sk.fixture_positions(f, rule)
@@ -217,8 +216,8 @@ def tree_fixture(N):
 @pytest.mark.parametrize("N", (3, 5))
 def test_single_tree_nodes_equal_the_twin(N, rule):
     rng = np.random.RandomState(N)
-    sim = sk.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=512, two_player_mode=1)
-    sk.configure(sim, rule)
+    sim = hs.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=512, two_player_mode=1)
+    gpu_options.configure(sim, dict(ko_rule=rule))
     board = tree_fixture(N)
     root = sim.tree_init(0, board)
     line = sk.Line(N, rule, board)
@@ -243,8 +242,8 @@ def test_new_nodes_see_the_log_after_play_move(rule):
     them.  The send-two-return-one cycle, played at the root, then searched one level down."""
     N = 5
     board, cyc = sk.send_two_return_one(N)
-    sim = sk.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=256, two_player_mode=1)
-    sk.configure(sim, rule)
+    sim = hs.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=256, two_player_mode=1)
+    gpu_options.configure(sim, dict(ko_rule=rule))
     root = sim.tree_init(0, board)
     line = sk.Line(N, rule, board)
     for k, a in enumerate(cyc[:2]):
@@ -286,8 +285,8 @@ def test_new_nodes_see_the_history_boards(H, rule):
             break
     assert len(boards) == H + 1
     history = boards[:-1][::-1]                      # newest first
-    sim = sk.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=512, two_player_mode=1)
-    sk.configure(sim, rule)
+    sim = hs.Sim(board_size=N, games=1, num_readouts=8, max_nodes_per_game=512, two_player_mode=1)
+    gpu_options.configure(sim, dict(ko_rule=rule))
     root = sim.tree_init(0, known.board, n=6 + H, to_play=known.to_play, ko=known.ko, history=np.stack(history))
     tw = sk.Line(N, rule, known.board, known.to_play, known.ko, history=history)
     assert sorted(sim.game_log()) == sorted(tw.seen_keys()[:-1]) and len(sim.game_log()) == H
@@ -318,13 +317,9 @@ def replay_repeats(rec, N, rule):
 def play_games(N, rule, games=8, slots=4, readouts=16, seed=3, tally=True, options=None, **cfg):
     """self-play on the simulator under `rule`; the tally: every node, when it first shows up live, adds what its mask
     lacks against all_legal_moves of its own board"""
-    sim = sk.Sim(board_size=N, games=slots, num_readouts=readouts, seed=seed, record_capacity_games=games + 8,
+    sim = hs.Sim(board_size=N, games=slots, num_readouts=readouts, seed=seed, record_capacity_games=games + 8,
                  resign_threshold=-2.0, resign_disable_fraction=1.0, max_nodes_per_game=384, **cfg)
-    if options:
-        import gpu_options
-        gpu_options.configure(sim, options)
-    if rule is not None:
-        sk.configure(sim, rule)
+    gpu_options.configure(sim, dict(options or {}, ko_rule=rule))
     net = hs.PeakedNet(N)
     sim.start(games)
     known, nodes, moves = [dict() for _ in range(slots)], 0, 0
@@ -346,6 +341,7 @@ def play_games(N, rule, games=8, slots=4, readouts=16, seed=3, tally=True, optio
         if sim.L.hs_records_count(sim.h) >= games:
             break
     recs, counts, cnt = sim.records(), sim.superko_counts(), sim.all_counters()
+    cnt["uncertainty"], cnt["puct"] = sim.uncertainty_counts(), sim.puct_counts()
     sim.close()
     assert len(recs) == games and cnt["CT_POOL_EXHAUSTED"] == 0
     return recs, counts, (nodes, moves), cnt
@@ -384,8 +380,8 @@ def test_a_run_whose_counters_stay_zero_is_the_run_without_the_rule(rule):
     import ctypes as C
     cfg = dict(board_size=9, games=4, num_readouts=16, seed=3, resign_threshold=-2.0, resign_disable_fraction=1.0,
                max_nodes_per_game=768)
-    off, on = sk.Sim(**cfg), sk.Sim(**cfg)
-    sk.configure(on, rule)
+    off, on = hs.Sim(**cfg), hs.Sim(**cfg)
+    gpu_options.configure(on, dict(ko_rule=rule))
     nets = hs.PeakedNet(9), hs.PeakedNet(9)
     off.start(4)
     on.start(4)
@@ -423,7 +419,7 @@ def start_table(N):
 @pytest.mark.parametrize("options", ("cap_forced", "gumbel_starts"))
 def test_the_rule_under_the_other_search_options(options):
     """the 4x4 games with the playout cap and forced playouts, and with the Gumbel root search from a start table,
-    through gpu_options.configure on this library's Sim: the records are stable run to run, and both counters equal
+    through gpu_options.configure: the records are stable run to run, and both counters equal
     the tally"""
     opt = (dict(cap=(6, 0.5), forced=(2.0, True)) if options == "cap_forced" else
            dict(gumbel=4, starts=start_table(4)))
@@ -434,10 +430,27 @@ def test_the_rule_under_the_other_search_options(options):
     assert runs[0][1][0] > 0
 
 
+def test_the_rule_with_lcb_variance_and_puct_options():
+    """The positional rule together with lcb, puct_variance and the PUCT option on one simulator: 3x3, 8 games on 4
+    slots, 16 readouts, seed 3, hs.PeakedNet -- the first shape of the superko tests at which all three counts are
+    positive.  The records are stable run to run, the superko counters equal the key-free tally, and the options were
+    exercised: measured superko counts (4, 4), uncertainty counts (96 LCB picks, 23 off the most visited child, 4482
+    levels under a variance factor, 3422 of them raised), all 4482 levels under the PUCT option."""
+    runs = [play_games(3, POS, options=sk.COMBINED, tally=(k == 0)) for k in range(2)]
+    (recs, counts, tally, cnt), again = runs[0], runs[1]
+    unc = cnt["uncertainty"]
+    print("combined:", counts, tally, unc)
+    assert same_records(recs, again[0]) and counts == again[1] and unc == again[3]["uncertainty"]
+    assert counts == tally
+    assert counts[0] > 0
+    assert unc[0] > 0 and unc[2] > 0 and cnt["puct"][0] > 0
+    assert all(replay_repeats(r, 3, POS) == 0 for r in recs)
+
+
 # ---------------------------------------------------------------- refusals
 
 def test_refusals_keep_the_setting():
-    sim = sk.Sim(board_size=3, games=2, num_readouts=8, max_nodes_per_game=64)
+    sim = hs.Sim(board_size=3, games=2, num_readouts=8, max_nodes_per_game=64)
     assert sim.ko_rule() == sk.SIMPLE
     assert sim.set_ko_rule(POS) == sk.OK and sim.ko_rule() == POS
     for bad in (-1, 3, 99):
@@ -460,17 +473,7 @@ def test_refusals_keep_the_setting():
 
 # ---------------------------------------------------------------- sanitizers
 
-def test_sanitizer_build_plays_the_rule(tmp_path):
-    """superko_sim.cpp (and hostsim.cpp inside it) with the main of superko_sanitize.cpp under
-    -fsanitize=address,undefined (the `sanitize` target of tests/superko_sim/Makefile), a program of its own with both
-    runtimes linked into it: the 2x2 random games, one triple ko, and 3x3 self-play under the rule.  Skipped where g++ or
-    its static sanitizer runtimes are missing."""
-    if not _static_sanitizer_runtimes():
-        pytest.skip("no g++ with static libasan / libubsan")
-    exe = str(tmp_path / "superko_sanitize")
-    r = subprocess.run(["make", "-s", "-C", sk.DIR, "sanitize", "SANITIZE_OUT=" + exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout[-2000:])
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "games played" in r.stdout and "ERROR" not in r.stderr
+def test_sanitizer_build_plays_the_rule():
+    """the `superko` part of the stand-alone sanitizer program (tests/hostsim/hostsim_sanitize.cpp, built once per
+    process by test_explore.run_sanitizer_part): the 2x2 random games, one triple ko, and 3x3 self-play under the rule"""
+    run_sanitizer_part("superko")

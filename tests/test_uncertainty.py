@@ -2,20 +2,20 @@
 arithmetic of include/agz_uncertainty.h against its numpy restatement, the moment rule on a tree driven one call at a
 time against a dict mirror, the LCB pick and the variance factor on hand-made rows, whole games on the simulator with
 moments only (nothing changes) and with both rules (counters against a Python tally of the rows), the argument checks,
-and a stand-alone sanitizer build.  The simulator is uncertainty_twin.Sim: agz_search.h itself, lane-serial.  CPU only."""
+and a stand-alone sanitizer build.  The simulator is hs.Sim: agz_search.h itself, lane-serial.  CPU only."""
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import alphago_jl_amd as ag
+import gpu_options
 import hs
 import puct_twin as pt
 import uncertainty_twin as ut
-from test_explore import _static_sanitizer_runtimes
+from test_explore import run_sanitizer_part
 
 f32, f64 = np.float32, np.float64
 bits32, bits64 = hs.bits32, hs.bits64
@@ -43,16 +43,16 @@ FACTOR_SETTINGS = [(0.85, 0.4, 2.0), (0.5, 0.01, 0.0), (0.999, 2.0, 1000.0), (0.
 
 def header_lcb(n, w, s, tp, z):
     out = np.zeros(3, f64)
-    ut.lib().hu_value_lcb(n, w, s, tp, z, ut.pd(out))
+    hs.lib().hs_value_lcb(n, w, s, tp, z, hs.pd(out))
     return out
 
 
 def test_header_equals_the_restatement_bit_for_bit():
     """mean, sd, lcb and the factor of include/agz_uncertainty.h, as g++ compiles it into the simulator's library and as
     hipcc compiles the host side of libagz.so (agz_value_lcb, agz_puct_variance_factor), against the numpy restatement
-    written from include/agz.h, with the square root taken from the library (hu_sqrt) and from its own restatement
+    written from include/agz.h, with the square root taken from the library (hs_sqrt) and from its own restatement
     (puct_twin.agz_sqrt)"""
-    L = ut.lib()
+    L = hs.lib()
     clamped = 0
     for n, w, s in stat_rows():
         for tp in (1, -1):
@@ -68,7 +68,7 @@ def test_header_equals_the_restatement_bit_for_bit():
         cnt, mean, var, _ = ut.child_stats([n], [w], [s])
         clamped += bool(f64(f32(s)) / cnt[0] - mean[0] * mean[0] < 0 and var[0] == 0)
         for k, prior, pw in FACTOR_SETTINGS:
-            got = L.hu_variance_factor(n, w, s, k, prior, pw)
+            got = L.hs_variance_factor(n, w, s, k, prior, pw)
             for sqrt in (ut.lib_sqrt, pt.agz_sqrt):
                 assert bits64(got) == bits64(ut.variance_factor(n, w, s, k, prior, pw, sqrt)), (n, w, s, k, prior, pw)
             assert ag.puct_variance_factor(n, w, s, k, prior, pw) == got
@@ -108,7 +108,7 @@ def test_header_against_math_sqrt():
                 se = math.sqrt(var[0] / cnt[0])
                 assert abs(got[2] - l[0]) <= z * gap(var[0] / cnt[0]) + math.ulp(z * se) + math.ulp(max(abs(got[2]), abs(l[0])))
         for k, prior, pw in FACTOR_SETTINGS:
-            got = ut.lib().hu_variance_factor(n, w, s, k, prior, pw)
+            got = hs.lib().hs_variance_factor(n, w, s, k, prior, pw)
             want = ut.variance_factor(n, w, s, k, prior, pw, math.sqrt)
             c, mn = f64(f32(1) + f32(n)), f64(f32(w)) / f64(f32(1) + f32(n))
             v = ((((mn * mn) + (f64(prior) * f64(prior))) * f64(pw)) + ((f64(f32(s)) / c) * c)) / (f64(pw) + c) - (mn * mn)
@@ -120,7 +120,7 @@ def test_header_against_math_sqrt():
 # ---------------------------------------------------------------- the moments, one call at a time
 
 def single_tree(N=5, seed=3, game_id=11, two_player=0, to_play=1, **kw):
-    sim = ut.Sim(board_size=N, games=1, num_readouts=64, parallel_readouts=8, seed=seed, max_nodes_per_game=256,
+    sim = hs.Sim(board_size=N, games=1, num_readouts=64, parallel_readouts=8, seed=seed, max_nodes_per_game=256,
                  two_player_mode=two_player, **kw)
     assert sim.set_value_moments(True) == ut.OK
     root = sim.tree_init(0, np.zeros(N * N, np.int8), to_play=to_play)
@@ -292,7 +292,7 @@ def test_variance_factor_in_the_scores(setting):
         # the root: its own statistics are the slot's
         set_rows(sim, root, N, W, np.abs(W), P)
         sim.L.hs_game_set(sim.h, 0, 2, float(n))
-        sim.L.hu_root_set(sim.h, 0, w, s)
+        sim.L.hs_root_set(sim.h, 0, w, s)
         assert (f32(sim.N_(0, root)), f32(sim.W_(0, root)), f32(sim.S_(0, root))) == (f32(n), f32(w), f32(s))
         want = ut.scores(N, W, P, n, w, s, 1, True, C_PUCT, setting, PV)
         assert (bits64(sim.scores(root)) == bits64(want)).all(), ("root", n, w, s)
@@ -316,7 +316,7 @@ def test_variance_factor_in_the_pruned_target(monkeypatch):
     the row of the root and of a node one level down, on the second slot of the simulator, equals selfplay_twin's
     pruned_pi with its scale multiplied by the restated factor of the node's own (n, W, S)"""
     import selfplay_twin as tw
-    sim = ut.Sim(board_size=5, games=2, num_readouts=64, seed=3, max_nodes_per_game=64, c_puct=C_PUCT)
+    sim = hs.Sim(board_size=5, games=2, num_readouts=64, seed=3, max_nodes_per_game=64, c_puct=C_PUCT)
     assert sim.set_value_moments(True) == ut.OK and sim.set_puct_variance(*PV) == ut.OK
     g = 1
     root = sim.tree_init(g, np.zeros(25, np.int8))
@@ -342,7 +342,7 @@ def test_variance_factor_in_the_pruned_target(monkeypatch):
         assert factor[0] != 1.0
         set_rows(sim, root, N, W, np.abs(W), P, g=g)
         sim.L.hs_game_set(sim.h, g, 2, float(n))
-        sim.L.hu_root_set(sim.h, g, w, s)
+        sim.L.hs_root_set(sim.h, g, w, s)
         got, ch = sim.pruned_pi(g, root, k)
         want, wch = tw.pruned_pi(N, W, P, 1, n, C_PUCT, k, True)
         assert (bits32(got) == bits32(want)).all() and ch == wch, ("root", n, w, s)
@@ -412,8 +412,8 @@ def tally_pick(sim, g, lcb, tally):
 
 
 def play_games(lcb=None, pv=None, moments=None, tally=None):
-    sim = ut.Sim(board_size=5, games=SLOTS, num_readouts=R, seed=SEED, record_capacity_games=GAMES + 8)
-    ut.configure(sim, lcb, pv, moments)
+    sim = hs.Sim(board_size=5, games=SLOTS, num_readouts=R, seed=SEED, record_capacity_games=GAMES + 8)
+    gpu_options.configure(sim, dict(lcb=lcb, pv=pv, moments=moments))
     net = hs.PeakedNet(5)
     sim.start(GAMES)
     expect, thresholds = {}, {}
@@ -460,8 +460,8 @@ def test_moments_alone_change_nothing_and_the_rules_change_the_games():
     assert on[2][:2] == tuple(tally)
     # all four counters: the same games again call by call on a single tree, every select phase and every pick predicted
     # from the rows before the simulator runs it -- the same moves, the same counters, and the Python tallies equal them
-    sim = ut.Sim(board_size=5, games=1, num_readouts=R, parallel_readouts=8, seed=SEED, max_nodes_per_game=2048)
-    ut.configure(sim, LCB, PVG)
+    sim = hs.Sim(board_size=5, games=1, num_readouts=R, parallel_readouts=8, seed=SEED, max_nodes_per_game=2048)
+    gpu_options.configure(sim, dict(lcb=LCB, pv=PVG))
     tally = [0] * 7
     for r in on[0]:
         moves = game_call_by_call(sim, hs.PeakedNet(5), int(r["game_id"]), R, 8, LCB, PVG, SEED, tally,
@@ -533,20 +533,20 @@ def game_call_by_call(sim, net, game_id, R, par, lcb, pv, seed, tally, resign_th
 # ---------------------------------------------------------------- refusals
 
 REFUSED = {
-    "hu_set_value_moments": ((2,), (-1,), (0,)),                       # (0: a rule is on)
-    "hu_set_lcb": ((NAN, 1, 0.0), (-1e-9, 1, 0.0), (100.001, 1, 0.0), (1.0, 0, 0.0), (1.0, -3, 0.0), (1.0, 1, -1e-9),
+    "hs_set_value_moments": ((2,), (-1,), (0,)),                       # (0: a rule is on)
+    "hs_set_lcb": ((NAN, 1, 0.0), (-1e-9, 1, 0.0), (100.001, 1, 0.0), (1.0, 0, 0.0), (1.0, -3, 0.0), (1.0, 1, -1e-9),
                    (1.0, 1, 1.000001), (1.0, 1, NAN)),
-    "hu_set_puct_variance": ((NAN, 0.4, 2.0), (-1e-9, 0.4, 2.0), (1.0, 0.4, 2.0), (0.5, 0.00999, 2.0), (0.5, 2.001, 2.0),
+    "hs_set_puct_variance": ((NAN, 0.4, 2.0), (-1e-9, 0.4, 2.0), (1.0, 0.4, 2.0), (0.5, 0.00999, 2.0), (0.5, 2.001, 2.0),
                              (0.5, NAN, 2.0), (0.5, 0.4, -1e-9), (0.5, 0.4, 1000.001), (0.5, 0.4, NAN)),
 }
-TAKEN = (("hu_set_lcb", (100.0, 1, 1.0)), ("hu_set_lcb", (0.5, 2000000, 0.0)), ("hu_set_puct_variance", (0.999999, 0.01, 0.0)),
-         ("hu_set_puct_variance", (0.1, 2.0, 1000.0)))
+TAKEN = (("hs_set_lcb", (100.0, 1, 1.0)), ("hs_set_lcb", (0.5, 2000000, 0.0)), ("hs_set_puct_variance", (0.999999, 0.01, 0.0)),
+         ("hs_set_puct_variance", (0.1, 2.0, 1000.0)))
 
 
 def test_refusals_keep_the_setting():
     """the argument checks the engine and the simulator share (agz_state.h): every refusal leaves the setting in force.
     (Games in flight and a pending select phase are states of the engine alone: tests/test_gpu_uncertainty.py.)"""
-    sim = ut.Sim(board_size=5, games=2, num_readouts=8, max_nodes_per_game=16, arena_mode=1)    # an arena takes all three
+    sim = hs.Sim(board_size=5, games=2, num_readouts=8, max_nodes_per_game=16, arena_mode=1)    # an arena takes all three
     # either rule while moments are off
     assert sim.set_lcb(1.0, 1, 0.0) == ut.BAD_ARGUMENT and sim.set_puct_variance(0.5, 0.4, 2.0) == ut.BAD_ARGUMENT
     assert sim.set_lcb(0.0, 1, 0.0) == ut.OK and sim.set_puct_variance(0.0, 0.4, 2.0) == ut.OK      # off is taken
@@ -596,17 +596,8 @@ def test_recorded_windows_give_the_recorded_summary():
 
 # ---------------------------------------------------------------- sanitizers
 
-def test_sanitizer_build_plays_a_game(tmp_path):
-    """uncertainty_sim.cpp (and hostsim.cpp inside it) with the main of uncertainty_sanitize.cpp under
-    -fsanitize=address,undefined (the `sanitize` target of tests/uncertainty_sim/Makefile), a program of its own with both
-    runtimes linked into it: one 5x5 game with all three options on, the rows of every root read once per step.  A check
-    of memory and undefined behaviour, not of results.  Skipped where g++ or its static sanitizer runtimes are missing."""
-    if not _static_sanitizer_runtimes():
-        pytest.skip("no g++ with static libasan / libubsan")
-    exe = str(tmp_path / "uncertainty_sanitize")
-    r = subprocess.run(["make", "-s", "-C", ut.DIR, "sanitize", "SANITIZE_OUT=" + exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    print(r.stdout[-2000:])
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "games played" in r.stdout and "ERROR" not in r.stderr
+def test_sanitizer_build_plays_a_game():
+    """the `uncertainty` part of the stand-alone sanitizer program (tests/hostsim/hostsim_sanitize.cpp, built once per
+    process by test_explore.run_sanitizer_part): 5x5 games with all three options on, the rows of every root read once per
+    step.  A check of memory and undefined behaviour, not of results."""
+    run_sanitizer_part("uncertainty")

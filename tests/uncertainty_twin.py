@@ -1,11 +1,7 @@
 """Value uncertainty (agz_search_set_value_moments / _set_lcb / _set_puct_variance) for the tests
-(TEST INFRASTRUCTURE): the binding of tests/uncertainty_sim/libuncertainty_sim.so -- the host simulator of hs.Sim with the
-exports of the three options -- as a subclass of hs.Sim, the arithmetic of include/agz_uncertainty.h restated in numpy from
-the text of include/agz.h, and a dict mirror of the moment rule for trees driven one call at a time."""
-import ctypes as C
-import os
-import subprocess
-
+(TEST INFRASTRUCTURE): the arithmetic of include/agz_uncertainty.h restated in numpy from the text of include/agz.h, a dict
+mirror of the moment rule for trees driven one call at a time, and one select phase predicted from the rows.  The simulator
+is hs.Sim, which has the three setters; gpu_options.configure sets them from a dict."""
 import numpy as np
 
 import alphago_jl_amd as ag
@@ -13,120 +9,13 @@ import hs
 import puct_twin as pt
 
 f32, f64 = np.float32, np.float64
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "uncertainty_sim")
 OK, BAD_ARGUMENT = ag._lib.OK, ag._lib.BAD_ARGUMENT
-
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    hs.lib()                                   # (hs.sig: the prototypes of every hs_* export, which this library has too)
-    try:
-        subprocess.run(["make", "-s", "-C", DIR], check=True)
-    except Exception:
-        if not os.path.exists(os.path.join(DIR, "libuncertainty_sim.so")):
-            raise
-    L = C.CDLL(os.path.join(DIR, "libuncertainty_sim.so"))
-    vp, i, f, dbl, P = C.c_void_p, C.c_int, C.c_float, C.c_double, C.POINTER
-    sig = dict(hs.sig)
-    sig.update({
-        "hu_destroy": (None, [vp]), "hu_set_value_moments": (i, [vp, i]), "hu_set_lcb": (i, [vp, dbl, i, dbl]),
-        "hu_set_puct_variance": (i, [vp, dbl, dbl, dbl]), "hu_setting": (None, [vp, P(dbl)]),
-        "hu_uncertainty_counts": (None, [vp, P(C.c_ulonglong)]), "hu_node_S": (f, [vp, i, i]),
-        "hu_node_row_S": (P(f), [vp, i, i]), "hu_child_lcb": (i, [vp, i, i, dbl, P(dbl), P(dbl), P(dbl)]),
-        "hu_root_set": (None, [vp, i, f, f]), "hu_sqrt": (dbl, [dbl]), "hu_value_lcb": (None, [f, f, f, i, dbl, P(dbl)]),
-        "hu_variance_factor": (dbl, [f, f, f, dbl, dbl, dbl]),
-    })
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib = L
-    return L
-
-
-def pd(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-class Sim(hs.Sim):
-    """hs.Sim on the library that also has the hu_* exports"""
-
-    def __init__(self, **cfg):
-        self.L = lib()
-        self.cfg = hs.default_config(**cfg)
-        self.h = self.L.hs_create(C.byref(self.cfg))
-        d = (C.c_int32 * 10)()
-        self.L.hs_dims(self.h, d)
-        (self.N, self.P, self.A, self.AP, self.cap, self.games, self.par, self.mgl, self.tau, self.maxd) = list(d)
-        self.setting = (0, 0.0, 0.0, 0.0)
-
-    def close(self):
-        if self.h:
-            self.L.hu_destroy(self.h)
-            self.h = None
-
-    # the setters return the status; `configure` asserts it
-    def set_value_moments(self, on=True):
-        return self.L.hu_set_value_moments(self.h, int(on))
-
-    def set_lcb(self, z=0.0, min_visits=1, min_ratio=0.0):
-        return self.L.hu_set_lcb(self.h, float(z), int(min_visits), float(min_ratio))
-
-    def set_puct_variance(self, k=0.0, prior=0.4, weight=2.0):
-        return self.L.hu_set_puct_variance(self.h, float(k), float(prior), float(weight))
-
-    def uncertainty_setting(self):
-        """(moments on, z, min_visits, min_ratio, k, prior, weight)"""
-        out = np.zeros(8, f64)
-        self.L.hu_setting(self.h, pd(out))
-        return (int(out[0]), out[1], int(out[2]), out[3], out[4], out[5], out[6])
-
-    def uncertainty_counts(self):
-        out = (C.c_ulonglong * 4)()
-        self.L.hu_uncertainty_counts(self.h, out)
-        return tuple(int(x) for x in out)
-
-    def S_(self, g, node):
-        return self.L.hu_node_S(self.h, g, node)
-
-    def row_S(self, g, node):
-        return np.ctypeslib.as_array(self.L.hu_node_row_S(self.h, g, node), shape=(self.AP,))[: self.A]
-
-    def child_lcb(self, node, z, g=0):
-        m, sd, l = np.zeros(self.A, f64), np.zeros(self.A, f64), np.zeros(self.A, f64)
-        assert self.L.hu_child_lcb(self.h, g, node, float(z), pd(m), pd(sd), pd(l)) == OK
-        return m, sd, l
-
-
-def configure(x, lcb=None, pv=None, moments=None):
-    """the three options of an engine (ag.Engine) or a simulator (Sim) x: lcb = (z, min_visits, min_ratio), pv = (k, prior,
-    weight); moments defaults to "a rule is asked for\""""
-    on = (lcb is not None or pv is not None) if moments is None else moments
-    if isinstance(x, Sim):
-        if on:
-            assert x.set_value_moments(True) == OK
-        if lcb is not None:
-            assert x.set_lcb(*lcb) == OK
-        if pv is not None:
-            assert x.set_puct_variance(*pv) == OK
-    else:
-        if on:
-            x.set_value_moments(True)
-        if lcb is not None:
-            x.set_lcb(lcb)
-        if pv is not None:
-            x.set_puct_variance(pv)
 
 
 # ---------------------------------------------------------------- the arithmetic, restated from include/agz.h
 
 def lib_sqrt(x):
-    return lib().hu_sqrt(float(x))
+    return hs.lib().hs_sqrt(float(x))
 
 
 def _sqrt_each(v, sqrt):
